@@ -10,11 +10,15 @@ every CTU) over one batch of pictures that is already resident in HBM.
 max-split-depth 3 (the full CT-partition search), 240 pictures per step and GPU.  Pictures are independent I-slices, so
 with N GPUs every rank runs its own 240 (weak scaling, no data-path collective).
 
-Objects next to it on the same JSON line (rank 0 prints ONE line), each measured IN this run unless labelled:
+A plain run prints the headline alone: `value`, `ms_per_step` (wall time of one timed step, max over ranks) and the
+`roofline` object taken from the same timed steps.  `--dump-outputs DIR` writes what the timed path computed in its last
+step to DIR/<plane>.npy (see dump_outputs).  `--full` adds the other objects below (rank 0 prints ONE line), each
+measured IN this run unless labelled:
   roofline      the dominant kernel (ctu_search_kernel) against HBM with the algorithmic 6 bytes per luma pixel
                 (SURVEY.md 8d): per launch from the kernel's own HIP events (its average named separately from the
                 team kernel's), and for the whole device; `traffic` / `issue_bound` come from the committed rocprofv3
                 counter passes of the same workload and say which commit they were taken on
+  host_bitstream  host CABAC + syntax of picture 0 of the timed run, from its record and from the device's tokens
   cpu_baseline  the CPU oracle (a port of the reference algorithm: the Rust reference cannot be built here) on one
                 host core over a bounded crop of one picture of the same workload; N = 1 only
   parity        the record of picture 0 of the timed run compared, bit for bit, with the record the cpu_baseline leg
@@ -36,6 +40,7 @@ import subprocess
 import sys
 import tempfile
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -51,6 +56,42 @@ ALGO_BYTES_PER_PIXEL = 6.0      # 1.5 B read + 1.5 B recon + 3.0 B levels (SURVE
 HBM_PEAK_GBS = 8000.0           # MI355X_MICROARCH.md: 8 TB/s spec
 TRAFFIC_FILE = os.path.join(ROOT, "profiles", "traffic.json")
 REC_KEYS = ("cu_log2_size", "luma_mode", "chroma_mode", "lev_y", "lev_cb", "lev_cr", "rec_y", "rec_cb", "rec_cr", "ctu_cost")
+# --dump-outputs: a fixed, seeded sample of the last step's records (a whole 3840x2176 record is ~100 MB as float32):
+# DUMP_PICTURES slots, and of every plane of each at most DUMP_SAMPLES[plane] positions (ctu_cost whole)
+DUMP_SEED = 20240611
+DUMP_PICTURES = 8
+DUMP_SAMPLES = {"rec_y": 1 << 17, "lev_y": 1 << 17, "rec_cb": 1 << 15, "rec_cr": 1 << 15, "lev_cb": 1 << 15, "lev_cr": 1 << 15,
+                "cu_log2_size": 1 << 15, "luma_mode": 1 << 15, "chroma_mode": 1 << 15, "ctu_cost": None}
+
+
+def synth_frames(make, w, h, indices):
+    """{f: make(w, h, f)} for every f in `indices`, on up to 8 threads (numpy releases the GIL in the array arithmetic;
+    a 3840x2176 picture takes about 2 s of one core).  The same arrays as one call after the other."""
+    indices = sorted(set(indices))
+    cores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    with ThreadPoolExecutor(max(1, min(8, cores, len(indices)))) as ex:
+        return dict(zip(indices, ex.map(lambda f: make(w, h, f), indices)))
+
+
+def dump_outputs(enc, n_slots, out_dir):
+    """What the timed path computed in its last step, as a caller receives it (enc.download), into out_dir/<plane>.npy:
+    float32 arrays of shape (pictures, samples), row i from slot `slots[i]`.  Slots and sample positions come from
+    DUMP_SEED and the workload's shape alone, so two runs with the same arguments write the same positions of the same
+    inputs' records.  Returns a summary for the result line."""
+    import numpy as np
+    rng = np.random.default_rng(DUMP_SEED)
+    slots = sorted(int(s) for s in rng.choice(n_slots, size=min(n_slots, DUMP_PICTURES), replace=False))
+    recs = [enc.download(s) for s in slots]
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for k in REC_KEYS:
+        n = recs[0][k].size
+        cap = DUMP_SAMPLES[k]
+        idx = np.arange(n) if cap is None or cap >= n else np.sort(rng.choice(n, size=cap, replace=False))
+        arr = np.stack([r[k].reshape(-1)[idx] for r in recs]).astype(np.float32)
+        np.save(os.path.join(out_dir, k + ".npy"), arr)
+        total += arr.nbytes
+    return {"dir": out_dir, "slots": slots, "planes": list(REC_KEYS), "bytes": total, "dtype": "float32", "seed": DUMP_SEED}
 
 
 def committed_profile(name):
@@ -180,27 +221,35 @@ def kernel_roofline(ks, dt, total_ctu_pictures, name, lanes=4):
     return out
 
 
-def measure(grp, rank, world, local_rank, wl, steps, warmup, with_cpu):
+def measure(grp, rank, world, local_rank, wl, steps, warmup, with_cpu, full=True, dump_dir=None):
     """One workload on this rank's GPU: `batch` resident pictures, `steps` timed encode calls; on rank 0 the result
-    objects (value, roofline, host_bitstream; with_cpu: cpu_baseline + parity)."""
+    objects (value, roofline; full: host_bitstream; with_cpu: cpu_baseline + parity) and, dump_dir given, the last
+    step's outputs (dump_outputs)."""
     from wrenc_amd import gpu, sharding, synth
     w, h, B = wl["w"], wl["h"], wl["batch"]
     enc = gpu.Encoder(w, h, qp=wl["qp"], max_split_depth=wl["depth"], device=local_rank, n_slots=B)
     enc.stats_enable(True)      # per-launch HIP events: measurement mode (off in the product path)
     # synthetic pictures, resident in HBM before the timed region; each rank owns the POCs p with p mod world == rank
     distinct = min(B, 8)
-    frames = {}
-    for s, poc in enumerate(sharding.picture_shard(world * B, rank, world)):
-        f = poc % (distinct * world)
-        if f not in frames:
-            frames[f] = synth.synth_frame(w, h, f)
-        enc.upload(s, *frames[f])
+    pocs = sharding.picture_shard(world * B, rank, world)
+    frames = synth_frames(synth.synth_frame, w, h, [poc % (distinct * world) for poc in pocs])
+    for s, poc in enumerate(pocs):
+        enc.upload(s, *frames[poc % (distinct * world)])
     enc.sync()
     frames = None
     dt, ks = run_resident(enc, grp, 0, B, steps, warmup, timed_stats=True)
     mism = enc.final_pass_mismatches()
     out = None
     if rank == 0:
+        fps = world * B * steps / dt
+        ctus = B * steps * (w // 32) * (h // 32)
+        out = {"value": fps, "unit": "frames/s", "mpix_per_s": fps * w * h / 1e6, "ms_per_step": dt * 1e3 / steps,
+               "workload": "%dx%d synthetic YUV420 QP%d max-split-depth %d" % (w, h, wl["qp"], wl["depth"]),
+               "pictures_per_step_per_gpu": B, "final_pass_mismatches": mism,
+               "roofline": kernel_roofline(ks, dt, ctus, wl["name"], lanes=enc.device_info()[1])}
+        if dump_dir:
+            out["dump_outputs"] = dump_outputs(enc, B, dump_dir)
+    if rank == 0 and full:
         from wrenc_amd import bitstream
         rec0 = enc.download(0)
         pool0, pics0 = enc.download_tokens(0, 1)     # the same picture as residual tokens made on the device (dev_bins.h)
@@ -213,18 +262,12 @@ def measure(grp, rank, world, local_rank, wl, steps, warmup, with_cpu):
             t3 = time.perf_counter()
             best = t2 - t1 if best is None else min(best, t2 - t1)
             best_tok = t3 - t2 if best_tok is None else min(best_tok, t3 - t2)
-        fps = world * B * steps / dt
-        ctus = B * steps * (w // 32) * (h // 32)
-        out = {"value": fps, "unit": "frames/s", "mpix_per_s": fps * w * h / 1e6, "ms_per_step": dt * 1e3 / steps,
-               "workload": "%dx%d synthetic YUV420 QP%d max-split-depth %d" % (w, h, wl["qp"], wl["depth"]),
-               "pictures_per_step_per_gpu": B, "final_pass_mismatches": mism,
-               "roofline": kernel_roofline(ks, dt, ctus, wl["name"], lanes=enc.device_info()[1]),
-               "host_bitstream": {"ms_per_picture_one_core": best * 1e3, "bytes_per_picture": len(nal),
-                                  "ms_per_picture_one_core_from_device_tokens": best_tok * 1e3, "token_bytes_per_picture": enc.last_token_words * 4,
-                                  "same_bytes_from_tokens": nal == nal_tok,
-                                  "note": "host CABAC + syntax of one searched picture from its level planes, and from the residual "
-                                          "tokens the device makes of it (the host then runs the CU-level syntax and the arithmetic "
-                                          "coder only); pictures are independent, one host thread each"}}
+        out["host_bitstream"] = {"ms_per_picture_one_core": best * 1e3, "bytes_per_picture": len(nal),
+                                 "ms_per_picture_one_core_from_device_tokens": best_tok * 1e3, "token_bytes_per_picture": enc.last_token_words * 4,
+                                 "same_bytes_from_tokens": nal == nal_tok,
+                                 "note": "host CABAC + syntax of one searched picture from its level planes, and from the residual "
+                                         "tokens the device makes of it (the host then runs the CU-level syntax and the arithmetic "
+                                         "coder only); pictures are independent, one host thread each"}
         if nal != nal_tok:
             out["host_bitstream"]["error"] = "the token path wrote other bytes"
         if with_cpu:
@@ -362,14 +405,21 @@ def e2e_native(w, h, qp, depth, n_pictures, batch, threads, textured):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: host_bitstream, cpu_baseline + parity, config1 / config3, textured, "
+                         "fill_curve, e2e (minutes)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write a fixed, seeded sample of the last timed step's records to DIR/<plane>.npy (float32)")
     ap.add_argument("--batch", type=int, default=int(os.environ.get("WRENC_BENCH_BATCH", str(HEADLINE["batch"]))),
                     help="pictures resident per GPU and encoded per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the contract's line: no config1 / config3 / fill_curve / e2e")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline / parity")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no config1 / config3 / fill_curve / e2e")
     ap.add_argument("--config3-pictures", type=int, default=240)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     from wrenc_amd import gpu, sharding  # noqa: F401  (gpu: see GPU_MAX_HW_QUEUES above)
@@ -386,8 +436,9 @@ def main():
     wl = dict(HEADLINE, batch=args.batch)
     if args.batch != HEADLINE["batch"]:
         wl["name"] = "3840x2176_qp32_d3_b%d" % args.batch
-    with_cpu = world == 1 and not args.no_cpu_baseline
-    head = measure(grp, rank, world, local_rank, wl, args.steps, args.warmup, with_cpu)
+    with_cpu = args.full and world == 1 and not args.no_cpu_baseline
+    head = measure(grp, rank, world, local_rank, wl, args.steps, args.warmup, with_cpu, full=args.full,
+                   dump_dir=args.dump_outputs)
     result, failed = None, []
     if rank == 0:
         result = {
@@ -399,18 +450,22 @@ def main():
             "config": {"workload": head["workload"] + " (BASELINE.json configs[2]/[3]: the largest single-GPU configuration)",
                        "pictures_per_step_per_gpu": wl["batch"], "parallelism": "picture-sharded x%d, no collective" % world,
                        "final_pass_mismatches": head["final_pass_mismatches"]},
-            "roofline": head["roofline"], "host_bitstream": head["host_bitstream"]}
+            "roofline": head["roofline"]}
+        if "dump_outputs" in head:
+            result["dump_outputs"] = head["dump_outputs"]
         if head["final_pass_mismatches"]:
             failed.append("final pass mismatches (headline)")
-        if not head["host_bitstream"]["same_bytes_from_tokens"]:
-            failed.append("token path bytes (headline)")
+        if "host_bitstream" in head:
+            result["host_bitstream"] = head["host_bitstream"]
+            if not head["host_bitstream"]["same_bytes_from_tokens"]:
+                failed.append("token path bytes (headline)")
         if "cpu_baseline" in head:
             result["cpu_baseline"] = head["cpu_baseline"]
             result["parity"] = head["parity"]
             result["parity_checked"] = head["parity"]["bit_exact"]
             if not head["parity"]["bit_exact"]:
                 failed.append("parity (headline)")
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         if world == 1:
             c1 = measure(grp, rank, world, local_rank, CONFIG1, 2, 1, with_cpu)
             if with_cpu:

@@ -2,6 +2,7 @@
 invariants, and the committed golden fixtures.  PARITY UNPINNED (see
 oracle/wrenc_oracle.h): the fixtures come from this restatement, not from wrenc."""
 import glob
+import json
 import os
 import re
 
@@ -25,16 +26,15 @@ def test_dct_matrix_structure():
         assert np.array_equal(m[k, ::-1], m[k] * (1 if k % 2 == 0 else -1))
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/src/transformer.rs"), reason="reference not mounted")
+def _ref_tables():
+    """The reference's tables as its source holds them (tests/golden/make_ref_source_data.py extracted them)."""
+    return json.load(open(os.path.join(HERE, "golden", "ref_source_data.json")))["tables"]
+
+
 def test_dct_matrix_equals_reference_rows_in_use():
-    """Rows k*(64/N), N<=32 (the only rows the live config uses) equal the reference's table.
+    """Rows k*(64/N), N<=32 (the only rows the live config uses) equal the reference's table (transformer.rs:934).
     Row 11 of the reference (64-point only, never used) carries 4 entries copied from row 10."""
-    txt = open("/root/reference/src/transformer.rs").read()
-    i = txt.index("const TRANS_MATRIX_0_")
-    body = txt[i:txt.index("lazy_static!", i)]
-    body = body[body.index("= [") + 2:]
-    nums = [int(x) for x in re.findall(r"-?\d+", body)][:64 * 32]
-    ref = np.array(nums).reshape(64, 32)
+    ref = np.array(_ref_tables()["trans_matrix_0"]).reshape(64, 32)
     m = po.dct64()
     assert np.array_equal(ref[0::2], m[0::2, :32])
     bad = np.argwhere(ref != m[:, :32])
@@ -52,33 +52,23 @@ def _c_table(path, name):
     return _ints(txt[i:txt.index("};", i)])
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/src/common.rs"), reason="reference not mounted")
 def test_prediction_tables_equal_the_reference_source():
     """intraPredAngle (common.rs:145), the cubic filter fC (:153) and the Gaussian filter fG (:188), as the
-    reference's source text holds them, against the oracle's and the device code's copies."""
+    reference's source text holds them (tests/golden/ref_source_data.json), against the oracle's and the device code's
+    copies."""
     root = os.path.dirname(HERE)
-    txt = open("/root/reference/src/common.rs").read()
-
-    def ref_table(name):
-        i = txt.index("pub const %s" % name)
-        i = txt.index("= [", i)
-        return _ints(txt[i:txt.index("];", i)])
-
-    angle, fc, fg = ref_table("INTRA_ANGLE_TABLE"), ref_table("F_C"), ref_table("F_G")
+    ref = _ref_tables()
+    angle, fc, fg = ref["intra_angle"], ref["f_c"], ref["f_g"]
     assert len(angle) == 95 and len(fc) == 128 and len(fg) == 128
     assert fg == [v for p in range(32) for v in (16 - (p >> 1), 32 - (p >> 1), 16 + (p >> 1), p >> 1)]   # both copies compute it
     for path in (os.path.join(root, "oracle", "wrenc_oracle.cpp"), os.path.join(root, "wrenc_amd", "csrc", "wrenc_gpu.hip")):
         assert _c_table(path, "kIntraAngle[95]") == angle, path
         assert _c_table(path, "kFC[32][4]") == fc, path
-    ls = open("/root/reference/src/quantizer.rs").read()
-    i = ls.index("=", ls.index("const LEVEL_SCALE"))
-    assert _ints(ls[i:ls.index("];", i)])[:6] == [40, 45, 51, 57, 64, 72]
+    assert ref["level_scale"] == [40, 45, 51, 57, 64, 72]
     assert _c_table(os.path.join(root, "wrenc_amd", "csrc", "wrenc_gpu.hip"), "level_scale[6]") == [40, 45, 51, 57, 64, 72]
     # dependent-quantisation state machine (encoder_context.rs:339): oracle, host writer, stream parser (the device walk
     # has it folded into its lane permutations, dev_quant.h:295-296, and is covered by the parity tests)
-    ec = open("/root/reference/src/encoder_context.rs").read()
-    i = ec.index("q_state_trans_table: [[0")
-    trans = _ints(ec[i + len("q_state_trans_table:"):ec.index("]],", i)])
+    trans = ref["q_state_trans"]
     assert trans == [0, 2, 2, 0, 1, 3, 3, 1]
     for rel, name in (("oracle/wrenc_oracle.cpp", "kQStateTrans[4][2]"), ("wrenc_amd/csrc/host/slice_data.cpp", "kQStateTrans[4][2]"),
                       ("oracle/vvc_parse.cpp", "kTrans[4][2]")):
