@@ -61,7 +61,8 @@ int wrenc_bs_write_picture(int width, int height, int qp, int poc, const wrenc_b
 /* The same picture from the device's TOKEN record (include/wrenc_gpu.h, wrenc_gpu_download_tokens: residual_coding done
  * on the device): the maps, the page pool the call filled, and this picture's table of first pages.  Writes the bytes
  * wrenc_bs_write_picture writes from the level planes of the same search result; the host then runs the CU-level syntax
- * and the arithmetic coder only.  WRENC_BS_EDATA on a token stream that ends early or names a context that does not exist. */
+ * and the arithmetic coder only.  WRENC_BS_EDATA on a token stream that ends early, names a context that does not exist
+ * or holds a bypass group of more than 25 bits. */
 #define WRENC_BS_TOKEN_PAGE 64
 typedef struct wrenc_bs_tokens {
     const uint8_t* cu_log2_size;

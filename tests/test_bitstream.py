@@ -322,6 +322,28 @@ def test_error_paths(built):
     assert e.value.code == bs.EDATA
 
 
+def test_a_bypass_group_of_more_than_25_bits_is_edata(built):
+    """A hand-made token record of one 32x32 picture (one 32x32 CU, planar, chroma from luma) whose luma residual is a
+    single bypass group: a group longer than the 25 bits a token holds (length field 25 or more) is WRENC_BS_EDATA, the
+    same record with a 25-bit group encodes."""
+    from wrenc_amd import bitstream as bs
+
+    def record(length_field):
+        pool = np.zeros(64, np.uint32)                          # one page: 63 words of tokens, the link to the next page
+        pool[0] = (1 << 31) | 1                                 # luma: coded, one token follows; Cb and Cr not coded
+        pool[3] = (1 << 31) | (length_field << 25) | 0x1555555  # bypass group of length_field + 1 bits
+        pool[63] = 0xFFFFFFFF                                   # the CTU's last page
+        pic = {"cu_log2_size": np.full((8, 8), 5, np.uint8), "luma_mode": np.zeros((8, 8), np.uint8),
+               "chroma_mode": np.zeros((4, 4), np.uint8), "first_page": np.zeros(1, np.uint32)}
+        return pool, pic
+
+    assert len(bs.write_picture_tokens(32, 32, 32, 0, *record(24))) > 20
+    for field in (25, 31, 32, 63):
+        with pytest.raises(bs.BitstreamError) as e:
+            bs.write_picture_tokens(32, 32, 32, 0, *record(field))
+        assert e.value.code == bs.EDATA, field
+
+
 def test_parser_rejects_damaged_streams(built):
     from wrenc_amd import bitstream as bs
     from oracle import pyoracle as po

@@ -1,7 +1,8 @@
-"""Command lines (the native program wrenc_amd/csrc/host/wrenc and its Python twin wrenc_amd/cli.py): the
+"""Command lines (the native program wrenc_amd/csrc/host/wrenc and wrenc_amd/cli.py, which starts it): the
 reference's options (main.rs:85-115) and its error behaviour (message on stderr, exit status 0:
 main.rs:127-133)."""
 import os
+import re
 import subprocess
 import sys
 
@@ -17,9 +18,9 @@ NATIVE = os.path.join(ROOT, "wrenc_amd", "csrc", "host", "wrenc")
 FRONT_ENDS = ["native", "python"]
 
 
-def _run(front, args, stdin=None):
+def _run(front, args, stdin=None, env=None):
     cmd = [NATIVE] if front == "native" else [sys.executable, "-m", "wrenc_amd.cli"]
-    return subprocess.run(cmd + args, cwd=ROOT, input=stdin, capture_output=True, timeout=600)
+    return subprocess.run(cmd + args, cwd=ROOT, input=stdin, capture_output=True, timeout=600, env=env)
 
 
 @pytest.mark.parametrize("front", FRONT_ENDS)
@@ -187,6 +188,33 @@ def test_a_run_that_ends_on_smaller_batches_writes_the_same_bytes(built, tmp_pat
     r = _run("native", ["-i", str(src), "-o", str(tmp_path / "x.vvc"), "--input-size", "64x64", "--output-size", "64x64",
                         "--num-pictures", "21", "--ramp-down", "sometimes"])
     assert r.returncode == 0 and b"error: Invalid ramp-down: sometimes" in r.stderr
+
+
+@pytest.mark.gpu
+def test_batches_whose_tokens_do_not_fit_the_pool_are_read_back_compact(built, tmp_path):
+    """WRENC_TOKEN_POOL_WORDS (a test hook of the native program) cuts every unit's token pool to a page or two: every batch's
+    token read-back then ends in WRENC_GPU_ENOMEM and the batch is read back as the compact record inside the run.  The
+    stream and the reconstruction are those of the same run with pools of the usual size, whose batches come back as tokens."""
+    w, h = 64, 64
+    frames = [content(k, w, h, i) for i, k in enumerate(("cclm", "noise", "ramp", "checker", "stripes70"))]
+    src = tmp_path / "in.yuv"
+    src.write_bytes(b"".join(p.tobytes() for f in frames for p in f))
+    outs = []
+    for words in (None, "64", "128"):
+        env = {k: v for k, v in os.environ.items() if k != "WRENC_TOKEN_POOL_WORDS"}
+        if words:
+            env["WRENC_TOKEN_POOL_WORDS"] = words
+        out, rec = tmp_path / ("o%d.vvc" % len(outs)), tmp_path / ("o%d.yuv" % len(outs))
+        r = _run("native", ["-i", str(src), "-o", str(out), "-r", str(rec), "--input-size", "64x64", "--output-size", "64x64",
+                            "--num-pictures", "5", "--qp", "30", "--max-split-depth", "2", "--batch", "2", "--ramp-down", "never",
+                            "--verbose"], env=env)
+        assert r.returncode == 0 and b"5 pictures" in r.stderr, r.stderr
+        outs.append((out.read_bytes(), rec.read_bytes(), re.findall(rb"read back \((\w+)\)", r.stderr)))
+    assert outs[0][2] == [b"tokens"] * 3                # 2 + 2 + 1 pictures
+    assert outs[1][2] == [b"compact"] * 3 and outs[2][2] == [b"compact"] * 3
+    assert len(outs[0][0]) > 1000 and len(outs[0][1]) == 5 * w * h * 3 // 2
+    for o in outs[1:]:
+        assert o[:2] == outs[0][:2]
 
 
 @pytest.mark.gpu

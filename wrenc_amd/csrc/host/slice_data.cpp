@@ -58,12 +58,10 @@ const int kRiceParams[32] = {0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 2, 2,
 
 class PictureCoder {
 public:
-    PictureCoder(int width, int height, int qp, const wrenc_bs_record& rec, BitWriter& bw)
-        : W_(width), H_(height), qp_(qp), r_(rec), cabac_(bw) {}
-    // the residual syntax as device-made tokens (include/wrenc_gpu.h, wrenc_gpu_download_tokens): the record then
-    // carries the maps only
-    PictureCoder(int width, int height, int qp, const wrenc_bs_record& maps, const wrenc_bs_tokens& tok, BitWriter& bw)
-        : W_(width), H_(height), qp_(qp), r_(maps), cabac_(bw), tok_(&tok) {}
+    // tok: the residual syntax as device-made tokens (include/wrenc_gpu.h, wrenc_gpu_download_tokens), the record then
+    // carries the maps only; NULL: the residuals from the record's level planes
+    PictureCoder(int width, int height, int qp, const wrenc_bs_record& rec, const wrenc_bs_tokens* tok, BitWriter& bw)
+        : W_(width), H_(height), qp_(qp), r_(rec), cabac_(bw), tok_(tok) {}
 
     // ctu_encoder.rs:38-47 (CABAC initialised at the picture's first CTU) + :172-201 (the CTU's coding tree)
     int encode_ctu(int x, int y) {
@@ -284,7 +282,9 @@ private:
                     if ((t >> 1) >= (uint32_t)CTX_COUNT) return WRENC_BS_EDATA;
                     cabac_.encode((int)(t >> 1), (int)(t & 1));
                 } else {
-                    cabac_.bypass_bits(t & 0x1FFFFFFu, (int)((t >> 25) & 63) + 1);
+                    const int nbits = (int)((t >> 25) & 63) + 1; // a bypass group holds at most 25 bits
+                    if (nbits > 25) return WRENC_BS_EDATA;
+                    cabac_.bypass_bits(t & 0x1FFFFFFu, nbits);
                 }
             }
             tk_pos_ += (int)run;
@@ -594,47 +594,23 @@ int CtuEncoder::encode(Bins& bins, const Ctu& ctu, const SliceHeader& sh) {
 }
 
 // slice_encoder.rs:343-427 with one tile and one slice per picture: CTUs in raster order
-static int encode_ctus(const Slice& slice, const SliceHeader& sh, Bins& bins) {
-    PictureCoder coder(slice.width, slice.height, sh.slice_qp, *slice.record, bins);
-    for (int y = 0; y < slice.height; y += 32)
-        for (int x = 0; x < slice.width; x += 32) {
-            CtuEncoder ctu_encoder(coder); // slice_encoder.rs:378: one CtuEncoder per CTU
-            const Ctu ctu = {x, y};
-            const int rc = ctu_encoder.encode(bins, ctu, sh);
-            if (rc) return rc;
-        }
-    coder.end_of_slice();
-    return WRENC_BS_OK;
-}
-
 Bins SliceEncoder::encode(const Slice& slice, const SliceHeader& sh, int* status) {
     Bins bins;
     write_slice_header(bins, sh.slice_qp); // encode_sh, slice_encoder.rs:32-341 (ends byte aligned)
     const size_t header_bits = bins.bit_count();
-    const int rc = encode_ctus(slice, sh, bins);
+    PictureCoder coder(slice.width, slice.height, sh.slice_qp, *slice.record, slice.tokens, bins);
+    int rc = WRENC_BS_OK;
+    for (int y = 0; y < slice.height && !rc; y += 32)
+        for (int x = 0; x < slice.width && !rc; x += 32) {
+            CtuEncoder ctu_encoder(coder); // slice_encoder.rs:378: one CtuEncoder per CTU
+            const Ctu ctu = {x, y};
+            rc = ctu_encoder.encode(bins, ctu, sh);
+        }
+    if (!rc) coder.end_of_slice();
     slice_data_bits_ = (long long)(bins.bit_count() - header_bits);
     if (status) *status = rc;
     bins.align(); // slice_encoder.rs:418
     return bins;
-}
-
-// the same picture loop with the residual syntax read from the device's tokens
-int write_slice_data_tokens(int width, int height, int qp, const wrenc_bs_tokens& tok, BitWriter& bw) {
-    const wrenc_bs_record maps = {tok.cu_log2_size, tok.luma_mode, tok.chroma_mode, nullptr, nullptr, nullptr};
-    PictureCoder coder(width, height, qp, maps, tok, bw);
-    for (int y = 0; y < height; y += 32)
-        for (int x = 0; x < width; x += 32) {
-            const int rc = coder.encode_ctu(x, y);
-            if (rc) return rc;
-        }
-    coder.end_of_slice();
-    return WRENC_BS_OK;
-}
-
-int write_slice_data(int width, int height, int qp, const wrenc_bs_record& rec, BitWriter& bw) {
-    const Slice slice = {width, height, &rec};
-    const SliceHeader sh = {qp};
-    return encode_ctus(slice, sh, bw);
 }
 
 } // namespace wrenc_host

@@ -17,6 +17,7 @@ struct SliceHeader {
 struct Slice {    // one slice = one tile = the picture (slice_splitter.rs:11-20, tile_splitter.rs:10)
     int width, height;
     const wrenc_bs_record* record; // what split_ct left in the reference's CT / CU / TU graph
+    const wrenc_bs_tokens* tokens; // the residuals as the device's tokens (record: the maps only), or NULL
 };
 struct Ctu {
     int x, y; // luma position of the 32x32 CTU
@@ -46,10 +47,6 @@ public:
 private:
     long long slice_data_bits_ = 0;
 };
-
-// CABAC-coded CTUs of the whole picture followed by end_of_slice_one_bit; bw must be byte aligned.
-int write_slice_data(int width, int height, int qp, const wrenc_bs_record& rec, BitWriter& bw);
-int write_slice_data_tokens(int width, int height, int qp, const wrenc_bs_tokens& tok, BitWriter& bw);
 
 // Raw byte sequence payloads (headers.cpp)
 void write_vps(BitWriter& bw, int width, int height);

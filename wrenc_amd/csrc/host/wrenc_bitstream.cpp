@@ -21,6 +21,25 @@ int hand_over(const std::vector<uint8_t>& bytes, uint8_t* out, size_t cap, size_
     return WRENC_BS_OK;
 }
 
+// picture header NAL + the slice's NAL (main.rs:307-313, :377-383), from either form of the record
+int write_picture(int poc, const Slice& slice, int qp, uint8_t* out, size_t cap, size_t* len) {
+    std::vector<uint8_t> stream;
+    {
+        BitWriter bw;
+        write_picture_header(bw, poc);
+        append_nal(stream, 9, NAL_PH, 0, bw.bytes());
+    }
+    // main.rs:380-382: let bins = slice_encoder.encode(&slice, &sh)
+    const SliceHeader sh = {qp};
+    SliceEncoder slice_encoder;
+    int rc = WRENC_BS_OK;
+    const Bins bins = slice_encoder.encode(slice, sh, &rc);
+    if (rc) return rc;
+    g_last_slice_data_bits = slice_encoder.slice_data_bits();
+    append_nal(stream, 9, NAL_IDR_W_RADL, 0, bins.bytes());
+    return hand_over(stream, out, cap, len);
+}
+
 } // namespace
 
 extern "C" {
@@ -58,24 +77,7 @@ int wrenc_bs_write_picture(int width, int height, int qp, int poc, const wrenc_b
     if (!size_ok(width, height, qp) || poc < 0 || !rec || !rec->cu_log2_size || !rec->luma_mode ||
         !rec->chroma_mode || !rec->lev_y || !rec->lev_cb || !rec->lev_cr)
         return WRENC_BS_EINVAL;
-    std::vector<uint8_t> stream;
-    {
-        BitWriter bw;
-        write_picture_header(bw, poc);
-        append_nal(stream, 9, NAL_PH, 0, bw.bytes()); // main.rs:307-313
-    }
-    {
-        // main.rs:380-382: let bins = slice_encoder.encode(&slice, &sh)
-        const Slice slice = {width, height, rec};
-        const SliceHeader sh = {qp};
-        SliceEncoder slice_encoder;
-        int rc = WRENC_BS_OK;
-        const Bins bins = slice_encoder.encode(slice, sh, &rc);
-        if (rc) return rc;
-        g_last_slice_data_bits = slice_encoder.slice_data_bits();
-        append_nal(stream, 9, NAL_IDR_W_RADL, 0, bins.bytes()); // main.rs:377-383
-    }
-    return hand_over(stream, out, cap, len);
+    return write_picture(poc, Slice{width, height, rec, nullptr}, qp, out, cap, len);
 }
 
 int wrenc_bs_write_picture_tokens(int width, int height, int qp, int poc, const wrenc_bs_tokens* tok, uint8_t* out, size_t cap,
@@ -83,23 +85,8 @@ int wrenc_bs_write_picture_tokens(int width, int height, int qp, int poc, const 
     if (!size_ok(width, height, qp) || poc < 0 || !tok || !tok->cu_log2_size || !tok->luma_mode || !tok->chroma_mode ||
         !tok->pool || !tok->first_page)
         return WRENC_BS_EINVAL;
-    std::vector<uint8_t> stream;
-    {
-        BitWriter bw;
-        write_picture_header(bw, poc);
-        append_nal(stream, 9, NAL_PH, 0, bw.bytes());
-    }
-    {
-        Bins bins;
-        write_slice_header(bins, qp);
-        const size_t header_bits = bins.bit_count();
-        const int rc = write_slice_data_tokens(width, height, qp, *tok, bins);
-        if (rc) return rc;
-        g_last_slice_data_bits = (long long)(bins.bit_count() - header_bits);
-        bins.align();
-        append_nal(stream, 9, NAL_IDR_W_RADL, 0, bins.bytes());
-    }
-    return hand_over(stream, out, cap, len);
+    const wrenc_bs_record maps = {tok->cu_log2_size, tok->luma_mode, tok->chroma_mode, nullptr, nullptr, nullptr};
+    return write_picture(poc, Slice{width, height, &maps, tok}, qp, out, cap, len);
 }
 
 long long wrenc_bs_last_slice_data_bits(void) { return g_last_slice_data_bits; }

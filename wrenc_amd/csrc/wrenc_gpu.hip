@@ -674,6 +674,69 @@ size_t plane_bytes(const wrenc_gpu_config& c, int comp, size_t elem) {
     return w * h * elem;
 }
 
+// ---- the steps the read-back entry points share (wrenc_gpu_sync, wrenc_gpu_download, _download_compact, _download_tokens) ----
+
+// slots first .. first + n - 1 exist (else WRENC_GPU_EINVAL with `range_msg`) and have been searched
+int check_encoded(wrenc_gpu_ctx* ctx, int first, int n, const char* range_msg) {
+    if (first < 0 || n < 1 || first + n > ctx->cfg.n_slots) return fail(ctx, WRENC_GPU_EINVAL, range_msg);
+    for (int s = first; s < first + n; ++s)
+        if (ctx->state[s] != 2) return fail(ctx, WRENC_GPU_ESTATE, "slot has not been encoded");
+    return WRENC_GPU_OK;
+}
+
+// the copy stream waits for the encode calls that searched these slots and for nothing queued after them (the slots of
+// one read-back usually share one call's event: each event is waited for once)
+int wait_for_search(wrenc_gpu_ctx* ctx, int first, int n) {
+    hipStream_t cs = ctx->copy_stream;
+    hipEvent_t last = nullptr;
+    for (int s = first; s < first + n; ++s)
+        if (ctx->slot_event[s] && ctx->slot_event[s] != last) {
+            last = ctx->slot_event[s];
+            HIP_TRY(ctx, hipStreamWaitEvent(cs, last, 0));
+        }
+    return WRENC_GPU_OK;
+}
+
+// the encode calls' sticky overflow word, read on the copy stream behind what is queued there, as a status
+int read_overflow(wrenc_gpu_ctx* ctx) {
+    int ovf = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&ovf, ctx->d_overflow, sizeof(int), hipMemcpyDeviceToHost, ctx->copy_stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->copy_stream));
+    if (ovf & 2) return fail(ctx, WRENC_GPU_EHIP, "internal: a team member never reached a meeting point of the level schedule");
+    if (ovf) return fail(ctx, WRENC_GPU_ELEVEL, "a quantised level reached 1024 (reference panics: block_splitter.rs:453)");
+    return WRENC_GPU_OK;
+}
+
+// one slot's maps and reconstruction planes to the caller's buffers, NULL ones skipped (asynchronous, on the copy stream)
+int copy_maps(wrenc_gpu_ctx* ctx, int slot, uint8_t* cu_log2_size, uint8_t* luma_mode, uint8_t* chroma_mode, uint8_t* rec_y,
+              uint8_t* rec_cb, uint8_t* rec_cr) {
+    const wrenc_gpu_config& c = ctx->cfg;
+    const PicBufs& b = ctx->slots[slot];
+    hipStream_t cs = ctx->copy_stream;
+    const size_t n4 = (size_t)(c.width / 4) * (c.height / 4), n8 = (size_t)(c.width / 8) * (c.height / 8);
+    if (cu_log2_size) HIP_TRY(ctx, hipMemcpyAsync(cu_log2_size, b.cu_log2, n4, hipMemcpyDeviceToHost, cs));
+    if (luma_mode) HIP_TRY(ctx, hipMemcpyAsync(luma_mode, b.luma_mode, n4, hipMemcpyDeviceToHost, cs));
+    if (chroma_mode) HIP_TRY(ctx, hipMemcpyAsync(chroma_mode, b.chroma_mode, n8, hipMemcpyDeviceToHost, cs));
+    uint8_t* rec[3] = {rec_y, rec_cb, rec_cr};
+    for (int p = 0; p < 3; ++p)
+        if (rec[p]) HIP_TRY(ctx, hipMemcpyAsync(rec[p], b.rec[p], plane_bytes(c, p, 1), hipMemcpyDeviceToHost, cs));
+    return WRENC_GPU_OK;
+}
+
+// replaces a device scratch buffer by one of `bytes` (contents dropped).  On failure it is NULL and HIP's last error is
+// cleared, so that the next launch check (hipGetLastError) does not report the failed allocation as its own.
+template <class T>
+hipError_t realloc_scratch(T*& p, size_t bytes) {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    const hipError_t e = hipMalloc((void**)&p, bytes);
+    if (e != hipSuccess) {
+        p = nullptr;
+        (void)hipGetLastError();
+    }
+    return e;
+}
+
 // DevConst::head_rng: the coefficients that do not end the head proof's region, and those with a quotient below 2, as one
 // interval around zero each (dev_quant.h: head_alpha, quotient -- the same integer arithmetic here on the host, over
 // every 16-bit coefficient; test_head_ranges_kernel holds the result against the device functions).  An interval that
@@ -1328,42 +1391,27 @@ int wrenc_gpu_sync(wrenc_gpu_ctx* ctx) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->copy_stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (hipStream_t st : ctx->lanes) HIP_TRY(ctx, hipStreamSynchronize(st));
-    int ovf = 0;
-    HIP_TRY(ctx, hipMemcpy(&ovf, ctx->d_overflow, sizeof(int), hipMemcpyDeviceToHost));
-    if (ovf & 2) return fail(ctx, WRENC_GPU_EHIP, "internal: a team member never reached a meeting point of the level schedule");
-    if (ovf) return fail(ctx, WRENC_GPU_ELEVEL, "a quantised level reached 1024 (reference panics: block_splitter.rs:453)");
-    return WRENC_GPU_OK;
+    return read_overflow(ctx);
 }
 
 int wrenc_gpu_download(wrenc_gpu_ctx* ctx, int slot, wrenc_gpu_picture* out) {
     if (!ctx || !out) return WRENC_GPU_EINVAL;
-    if (slot < 0 || slot >= ctx->cfg.n_slots) return fail(ctx, WRENC_GPU_EINVAL, "bad slot");
-    if (ctx->state[slot] != 2) return fail(ctx, WRENC_GPU_ESTATE, "slot has not been encoded");
+    if (const int rc = check_encoded(ctx, slot, 1, "bad slot")) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
     const PicBufs& b = ctx->slots[slot];
     const wrenc_gpu_config& c = ctx->cfg;
-    uint8_t* rec[3] = {out->rec_y, out->rec_cb, out->rec_cr};
     int16_t* lev[3] = {out->lev_y, out->lev_cb, out->lev_cr};
     // on the copy stream, behind the encode call that searched this slot and nothing later
     hipStream_t cs = ctx->copy_stream;
-    if (ctx->slot_event[slot]) HIP_TRY(ctx, hipStreamWaitEvent(cs, ctx->slot_event[slot], 0));
-    for (int k = 0; k < 3; ++k) {
-        if (rec[k]) HIP_TRY(ctx, hipMemcpyAsync(rec[k], b.rec[k], plane_bytes(c, k, 1), hipMemcpyDeviceToHost, cs));
+    if (const int rc = wait_for_search(ctx, slot, 1)) return rc;
+    for (int k = 0; k < 3; ++k)
         if (lev[k]) HIP_TRY(ctx, hipMemcpyAsync(lev[k], b.lev[k], plane_bytes(c, k, 2), hipMemcpyDeviceToHost, cs));
-    }
-    const size_t n4 = (size_t)(c.width / 4) * (c.height / 4), n8 = (size_t)(c.width / 8) * (c.height / 8);
-    if (out->cu_log2_size) HIP_TRY(ctx, hipMemcpyAsync(out->cu_log2_size, b.cu_log2, n4, hipMemcpyDeviceToHost, cs));
-    if (out->luma_mode) HIP_TRY(ctx, hipMemcpyAsync(out->luma_mode, b.luma_mode, n4, hipMemcpyDeviceToHost, cs));
-    if (out->chroma_mode) HIP_TRY(ctx, hipMemcpyAsync(out->chroma_mode, b.chroma_mode, n8, hipMemcpyDeviceToHost, cs));
+    if (const int rc = copy_maps(ctx, slot, out->cu_log2_size, out->luma_mode, out->chroma_mode, out->rec_y, out->rec_cb, out->rec_cr))
+        return rc;
     if (out->ctu_cost)
         HIP_TRY(ctx, hipMemcpyAsync(out->ctu_cost, b.ctu_cost, sizeof(float) * ctx->ctu_cols * ctx->ctu_rows,
                                     hipMemcpyDeviceToHost, cs));
-    int ovf = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&ovf, ctx->d_overflow, sizeof(int), hipMemcpyDeviceToHost, cs));
-    HIP_TRY(ctx, hipStreamSynchronize(cs));
-    if (ovf & 2) return fail(ctx, WRENC_GPU_EHIP, "internal: a team member never reached a meeting point of the level schedule");
-    if (ovf) return fail(ctx, WRENC_GPU_ELEVEL, "a quantised level reached 1024 (reference panics: block_splitter.rs:453)");
-    return WRENC_GPU_OK;
+    return read_overflow(ctx);
 }
 
 size_t wrenc_gpu_compact_mask_words(int width, int height) {
@@ -1373,48 +1421,29 @@ size_t wrenc_gpu_compact_mask_words(int width, int height) {
 
 int wrenc_gpu_download_compact(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_gpu_compact* out) {
     if (!ctx || !out) return WRENC_GPU_EINVAL;
-    if (first_slot < 0 || n < 1 || first_slot + n > ctx->cfg.n_slots) return fail(ctx, WRENC_GPU_EINVAL, "slot range out of bounds");
-    for (int s = first_slot; s < first_slot + n; ++s)
-        if (ctx->state[s] != 2) return fail(ctx, WRENC_GPU_ESTATE, "slot has not been encoded");
+    if (const int rc = check_encoded(ctx, first_slot, n, "slot range out of bounds")) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
     const wrenc_gpu_config& c = ctx->cfg;
     const size_t mask_words = wrenc_gpu_compact_mask_words(c.width, c.height);
     const size_t blocks = (size_t)(c.width / 4) * (c.height / 4) * 3 / 2;
     if (ctx->compact_cap < n) {
-        if (ctx->d_cmask) (void)hipFree(ctx->d_cmask);
-        if (ctx->d_cpayload) (void)hipFree(ctx->d_cpayload);
-        if (ctx->d_ccount) (void)hipFree(ctx->d_ccount);
-        ctx->d_cmask = nullptr;
-        ctx->d_cpayload = nullptr;
-        ctx->d_ccount = nullptr;
         ctx->compact_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_cmask, (size_t)n * mask_words * sizeof(uint32_t)));
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_cpayload, (size_t)n * blocks * 16 * sizeof(int16_t)));
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_ccount, (size_t)n * sizeof(unsigned)));
+        HIP_TRY(ctx, realloc_scratch(ctx->d_cmask, (size_t)n * mask_words * sizeof(uint32_t)));
+        HIP_TRY(ctx, realloc_scratch(ctx->d_cpayload, (size_t)n * blocks * 16 * sizeof(int16_t)));
+        HIP_TRY(ctx, realloc_scratch(ctx->d_ccount, (size_t)n * sizeof(unsigned)));
         ctx->compact_cap = n;
     }
     hipStream_t cs = ctx->copy_stream;
-    hipEvent_t last = nullptr; // the slots of one call usually share one encode call's event
-    for (int s = first_slot; s < first_slot + n; ++s)
-        if (ctx->slot_event[s] && ctx->slot_event[s] != last) {
-            last = ctx->slot_event[s];
-            HIP_TRY(ctx, hipStreamWaitEvent(cs, last, 0));
-        }
+    if (const int rc = wait_for_search(ctx, first_slot, n)) return rc;
     hipLaunchKernelGGL(compact_levels_kernel, dim3(n), dim3(1024), 0, cs, ctx->d_slots, first_slot, c.width, c.height, ctx->d_cmask,
                        mask_words, ctx->d_cpayload, blocks, ctx->d_ccount);
     HIP_TRY(ctx, hipGetLastError());
     std::vector<unsigned> counts((size_t)n);
-    int ovf = 0;
     HIP_TRY(ctx, hipMemcpyAsync(counts.data(), ctx->d_ccount, (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost, cs));
-    HIP_TRY(ctx, hipMemcpyAsync(&ovf, ctx->d_overflow, sizeof(int), hipMemcpyDeviceToHost, cs));
-    HIP_TRY(ctx, hipStreamSynchronize(cs));
-    if (ovf & 2) return fail(ctx, WRENC_GPU_EHIP, "internal: a team member never reached a meeting point of the level schedule");
-    if (ovf) return fail(ctx, WRENC_GPU_ELEVEL, "a quantised level reached 1024 (reference panics: block_splitter.rs:453)");
+    if (const int rc = read_overflow(ctx)) return rc;
     bool short_buf = false;
-    const size_t n4 = (size_t)(c.width / 4) * (c.height / 4), n8 = (size_t)(c.width / 8) * (c.height / 8);
     for (int k = 0; k < n; ++k) {
         wrenc_gpu_compact& o = out[k];
-        const PicBufs& b = ctx->slots[first_slot + k];
         o.n_blocks = counts[(size_t)k];
         if (o.mask) HIP_TRY(ctx, hipMemcpyAsync(o.mask, ctx->d_cmask + (size_t)k * mask_words, mask_words * sizeof(uint32_t), hipMemcpyDeviceToHost, cs));
         if (o.n_blocks > o.payload_cap || (o.n_blocks && !o.payload)) {
@@ -1423,12 +1452,8 @@ int wrenc_gpu_download_compact(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_
             HIP_TRY(ctx, hipMemcpyAsync(o.payload, ctx->d_cpayload + (size_t)k * blocks * 16, o.n_blocks * 16 * sizeof(int16_t),
                                         hipMemcpyDeviceToHost, cs));
         }
-        if (o.cu_log2_size) HIP_TRY(ctx, hipMemcpyAsync(o.cu_log2_size, b.cu_log2, n4, hipMemcpyDeviceToHost, cs));
-        if (o.luma_mode) HIP_TRY(ctx, hipMemcpyAsync(o.luma_mode, b.luma_mode, n4, hipMemcpyDeviceToHost, cs));
-        if (o.chroma_mode) HIP_TRY(ctx, hipMemcpyAsync(o.chroma_mode, b.chroma_mode, n8, hipMemcpyDeviceToHost, cs));
-        uint8_t* rec[3] = {o.rec_y, o.rec_cb, o.rec_cr};
-        for (int p = 0; p < 3; ++p)
-            if (rec[p]) HIP_TRY(ctx, hipMemcpyAsync(rec[p], b.rec[p], plane_bytes(c, p, 1), hipMemcpyDeviceToHost, cs));
+        if (const int rc = copy_maps(ctx, first_slot + k, o.cu_log2_size, o.luma_mode, o.chroma_mode, o.rec_y, o.rec_cb, o.rec_cr))
+            return rc;
     }
     HIP_TRY(ctx, hipStreamSynchronize(cs));
     if (short_buf) return fail(ctx, WRENC_GPU_ENOMEM, "wrenc_gpu_download_compact: payload_cap is smaller than n_blocks of a picture");
@@ -1438,37 +1463,31 @@ int wrenc_gpu_download_compact(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_
 int wrenc_gpu_download_tokens(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_gpu_tokens* out, uint32_t* pool, size_t pool_cap_words,
                               size_t* pool_words_used) {
     if (!ctx || !out || !pool || !pool_words_used || n < 1) return WRENC_GPU_EINVAL;
-    if (first_slot < 0 || first_slot + n > ctx->cfg.n_slots) return fail(ctx, WRENC_GPU_EINVAL, "bad slot range");
-    for (int s = first_slot; s < first_slot + n; ++s)
-        if (ctx->state[s] != 2) return fail(ctx, WRENC_GPU_ESTATE, "slot has not been encoded");
+    if (const int rc = check_encoded(ctx, first_slot, n, "bad slot range")) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-    const wrenc_gpu_config& c = ctx->cfg;
     const int ctus = ctx->ctu_cols * ctx->ctu_rows;
     const size_t pages = pool_cap_words / kTokPage;
     if (pages < 1 || pages > 0xFFFFFFF0u) return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_download_tokens: pool_cap_words");
+    // device scratch of the pass, grown on demand; where there is no room for it the caller falls back as for a short pool
+    constexpr int kCounterWords = kTokPools * kTokCounterStride + 1; // the sub-pools' page counters, the "a sub-pool ran out" flag
+    const auto no_room = [&](hipError_t e) {
+        *pool_words_used = 0;
+        return fail(ctx, WRENC_GPU_ENOMEM, std::string("wrenc_gpu_download_tokens: device scratch: ") + hipGetErrorString(e));
+    };
     if (ctx->tok_pool_words < pages * kTokPage) {
-        if (ctx->d_tok_pool) (void)hipFree(ctx->d_tok_pool);
-        ctx->d_tok_pool = nullptr;
         ctx->tok_pool_words = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_tok_pool, pages * kTokPage * sizeof(uint32_t)));
+        if (const hipError_t e = realloc_scratch(ctx->d_tok_pool, pages * kTokPage * sizeof(uint32_t))) return no_room(e);
         ctx->tok_pool_words = pages * kTokPage;
     }
-    constexpr int kCounterWords = kTokPools * kTokCounterStride + 1; // the sub-pools' page counters, the "a sub-pool ran out" flag
-    if (!ctx->d_tok_counter) HIP_TRY(ctx, hipMalloc((void**)&ctx->d_tok_counter, kCounterWords * sizeof(unsigned)));
+    if (!ctx->d_tok_counter)
+        if (const hipError_t e = realloc_scratch(ctx->d_tok_counter, kCounterWords * sizeof(unsigned))) return no_room(e);
     if (ctx->tok_first_cap < n) {
-        if (ctx->d_tok_first) (void)hipFree(ctx->d_tok_first);
-        ctx->d_tok_first = nullptr;
         ctx->tok_first_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_tok_first, (size_t)n * ctus * sizeof(uint32_t)));
+        if (const hipError_t e = realloc_scratch(ctx->d_tok_first, (size_t)n * ctus * sizeof(uint32_t))) return no_room(e);
         ctx->tok_first_cap = n;
     }
     hipStream_t cs = ctx->copy_stream;
-    hipEvent_t last = nullptr;
-    for (int s = first_slot; s < first_slot + n; ++s)
-        if (ctx->slot_event[s] && ctx->slot_event[s] != last) {
-            last = ctx->slot_event[s];
-            HIP_TRY(ctx, hipStreamWaitEvent(cs, last, 0));
-        }
+    if (const int rc = wait_for_search(ctx, first_slot, n)) return rc;
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_tok_counter, 0, kCounterWords * sizeof(unsigned), cs));
     const int waves = n * ctus;
     // sub-pools: enough CTUs in each (16 or more) that they fill evenly; one for a handful of CTUs
@@ -1479,12 +1498,8 @@ int wrenc_gpu_download_tokens(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_g
                        ctx->d_tok_pool, (unsigned)sub, n_pools - 1, ctx->d_tok_counter, ctx->d_tok_first, (int*)(ctx->d_tok_counter + kCounterWords - 1));
     HIP_TRY(ctx, hipGetLastError());
     std::vector<unsigned> cnt((size_t)kCounterWords);
-    int ovf = 0;
     HIP_TRY(ctx, hipMemcpyAsync(cnt.data(), ctx->d_tok_counter, kCounterWords * sizeof(unsigned), hipMemcpyDeviceToHost, cs));
-    HIP_TRY(ctx, hipMemcpyAsync(&ovf, ctx->d_overflow, sizeof(int), hipMemcpyDeviceToHost, cs));
-    HIP_TRY(ctx, hipStreamSynchronize(cs));
-    if (ovf & 2) return fail(ctx, WRENC_GPU_EHIP, "internal: a team member never reached a meeting point of the level schedule");
-    if (ovf) return fail(ctx, WRENC_GPU_ELEVEL, "a quantised level reached 1024 (reference panics: block_splitter.rs:453)");
+    if (const int rc = read_overflow(ctx)) return rc;
     size_t asked = 0;
     bool short_of = cnt[(size_t)kCounterWords - 1] != 0;
     for (int p = 0; p < n_pools; ++p) {
@@ -1497,17 +1512,11 @@ int wrenc_gpu_download_tokens(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_g
         if (cnt[(size_t)p * kTokCounterStride])
             HIP_TRY(ctx, hipMemcpyAsync(pool + (size_t)p * sub * kTokPage, ctx->d_tok_pool + (size_t)p * sub * kTokPage,
                                         (size_t)cnt[(size_t)p * kTokCounterStride] * kTokPage * sizeof(uint32_t), hipMemcpyDeviceToHost, cs));
-    const size_t n4 = (size_t)(c.width / 4) * (c.height / 4), n8 = (size_t)(c.width / 8) * (c.height / 8);
     for (int k = 0; k < n; ++k) {
         wrenc_gpu_tokens& o = out[k];
-        const PicBufs& b = ctx->slots[first_slot + k];
         if (o.first_page) HIP_TRY(ctx, hipMemcpyAsync(o.first_page, ctx->d_tok_first + (size_t)k * ctus, (size_t)ctus * sizeof(uint32_t), hipMemcpyDeviceToHost, cs));
-        if (o.cu_log2_size) HIP_TRY(ctx, hipMemcpyAsync(o.cu_log2_size, b.cu_log2, n4, hipMemcpyDeviceToHost, cs));
-        if (o.luma_mode) HIP_TRY(ctx, hipMemcpyAsync(o.luma_mode, b.luma_mode, n4, hipMemcpyDeviceToHost, cs));
-        if (o.chroma_mode) HIP_TRY(ctx, hipMemcpyAsync(o.chroma_mode, b.chroma_mode, n8, hipMemcpyDeviceToHost, cs));
-        uint8_t* rec[3] = {o.rec_y, o.rec_cb, o.rec_cr};
-        for (int p = 0; p < 3; ++p)
-            if (rec[p]) HIP_TRY(ctx, hipMemcpyAsync(rec[p], b.rec[p], plane_bytes(c, p, 1), hipMemcpyDeviceToHost, cs));
+        if (const int rc = copy_maps(ctx, first_slot + k, o.cu_log2_size, o.luma_mode, o.chroma_mode, o.rec_y, o.rec_cb, o.rec_cr))
+            return rc;
     }
     HIP_TRY(ctx, hipStreamSynchronize(cs));
     return WRENC_GPU_OK;
@@ -1572,6 +1581,7 @@ void* wrenc_gpu_alloc_host(wrenc_gpu_ctx* ctx, size_t bytes) {
     if (!ctx || bytes == 0) return nullptr;
     void* p = nullptr;
     if (hipSetDevice(ctx->cfg.device) != hipSuccess || hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError(); // (not to be reported by the next launch check: the caller may go on without the memory)
         (void)fail(ctx, WRENC_GPU_ENOMEM, "hipHostMalloc failed");
         return nullptr;
     }

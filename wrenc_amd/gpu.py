@@ -279,25 +279,9 @@ class Encoder:
         self._pinned.append(ptr)
         return np.ctypeslib.as_array((C.c_uint8 * nbytes).from_address(ptr))
 
-    def alloc_picture_host(self, keys=None):
-        """alloc_picture() in page-locked memory (optionally only `keys`)."""
-        shapes = alloc_picture(8, 8)
-        w, h = self.width, self.height
-        dims = {"rec_y": (h, w), "rec_cb": (h // 2, w // 2), "rec_cr": (h // 2, w // 2), "lev_y": (h, w),
-                "lev_cb": (h // 2, w // 2), "lev_cr": (h // 2, w // 2), "cu_log2_size": (h // 4, w // 4),
-                "luma_mode": (h // 4, w // 4), "chroma_mode": (h // 8, w // 8), "ctu_cost": ((h // 32) * (w // 32),)}
-        out = {}
-        for k in _PIC_KEYS:
-            if keys is not None and k not in keys:
-                continue
-            dt = shapes[k].dtype
-            n = int(np.prod(dims[k])) * dt.itemsize
-            out[k] = self.alloc_host(n).view(dt).reshape(dims[k])
-        return out
-
     def download(self, slot, keys=None, out=None):
         """All planes of the record, or only `keys` (the C ABI skips NULL pointers); `out` = arrays to fill
-        (e.g. from alloc_picture_host) instead of fresh ones."""
+        instead of fresh ones."""
         if out is None:
             out = alloc_picture(self.width, self.height)
         if keys is not None:
