@@ -2,8 +2,8 @@
 deals its pictures to workgroups of WPB = 4 pictures and the workgroups to up to 4 HIP streams ("lanes");
 the last workgroup is padded with waves that compute and never store.  19 pictures = 5 workgroups on 4 lanes
 with 1 padding wave; 33 pictures = 9 workgroups on 4 lanes with 3 padding waves; 9 pictures = 3 workgroups with 3.
-The pictures of a workgroup are of DIFFERENT content kinds, so its waves walk the pooled Viterbi's barriers with
-different data.  Every slot's full record (ctu_cost included) must equal the oracle's and the stream bytes the CPU path's."""
+The pictures of a workgroup are of DIFFERENT content kinds, so its waves share a workgroup (its LDS tables, the
+padding waves) with different data.  Every slot's full record (ctu_cost included) must equal the oracle's and the stream bytes the CPU path's."""
 import numpy as np
 import pytest
 

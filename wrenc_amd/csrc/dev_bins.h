@@ -37,9 +37,6 @@ constexpr int kTokCounterStride = 32;      // words from one sub-pool's counter 
 constexpr int CTXD_LAST_X = 32, CTXD_LAST_Y = CTXD_LAST_X + 23, CTXD_SB_CODED = CTXD_LAST_Y + 23, CTXD_SIG = CTXD_SB_CODED + 7,
               CTXD_PAR = CTXD_SIG + 63, CTXD_GTX = CTXD_PAR + 33;
 
-#ifndef WRENC_TOKENS_4X4_ROWS
-#define WRENC_TOKENS_4X4_ROWS 1 // 0: every 4x4 block a step of its own (as first built; for A/B runs)
-#endif
 struct TokLds {
     int16_t lv[1024];                 // the transform block's levels, raster
     uint16_t tpl[34 * 34 + 2];        // AbsLevelPass1 | significant << 8, two zero columns / rows behind the block
@@ -555,7 +552,7 @@ __global__ __launch_bounds__(256) void residual_tokens_kernel(const DevConst* __
             o.n_tok += 3;
             const uint32_t hy = tb_tokens(k, o, 0, lg, ly + (size_t)y0 * W + x0, W);
             uint32_t hb, hr;
-            if (WRENC_TOKENS_4X4_ROWS && lg == 3) { // the 4x4 chroma pair in one step
+            if (lg == 3) { // the 4x4 chroma pair in one step
                 const int cs[4] = {1, 2, 0, 0}, st[4] = {Wc, Wc, 0, 0};
                 const GLOBAL_AS int16_t* const l[4] = {lcb + (size_t)(y0 >> 1) * Wc + (x0 >> 1), lcr + (size_t)(y0 >> 1) * Wc + (x0 >> 1), nullptr, nullptr};
                 uint32_t hd4[4];
@@ -574,42 +571,22 @@ __global__ __launch_bounds__(256) void residual_tokens_kernel(const DevConst* __
             z += 1 << (2 * (lg - 2));
         } else {
             // an 8x8 CU split into four 4x4 luma CUs (one transform unit each), then the chroma CU of the 8x8
-            if (WRENC_TOKENS_4X4_ROWS) {
-                uint32_t hd4[4];
-                {
-                    const int cs[4] = {0, 0, 0, 0}, st[4] = {W, W, W, W};
-                    const GLOBAL_AS int16_t* b = ly + (size_t)y0 * W + x0;
-                    const GLOBAL_AS int16_t* const l[4] = {b, b + 4, b + (size_t)4 * W, b + (size_t)4 * W + 4};
-                    tb4_tokens(k, o, 4, cs, l, st, true, hd4);
-                }
-                tok_reserve(o, 2);
-                const int h = o.n_tok;
-                o.n_tok += 2;
-                const int cs[4] = {1, 2, 0, 0}, st[4] = {Wc, Wc, 0, 0};
-                const GLOBAL_AS int16_t* const l[4] = {lcb + (size_t)(y0 >> 1) * Wc + (x0 >> 1), lcr + (size_t)(y0 >> 1) * Wc + (x0 >> 1), nullptr, nullptr};
-                tb4_tokens(k, o, 2, cs, l, st, false, hd4);
-                if (LANE == 0) {
-                    tok_put(o, h, hd4[0]);
-                    tok_put(o, h + 1, hd4[1]);
-                }
-                z += 4;
-                continue;
-            }
-            for (int i = 0; i < 4; ++i) {
-                tok_reserve(o, 1);
-                const int h = o.n_tok;
-                o.n_tok += 1;
-                const uint32_t hy = tb_tokens(k, o, 0, 2, ly + (size_t)(y0 + 4 * (i >> 1)) * W + x0 + 4 * (i & 1), W);
-                if (LANE == 0) tok_put(o, h, hy);
+            uint32_t hd4[4];
+            {
+                const int cs[4] = {0, 0, 0, 0}, st[4] = {W, W, W, W};
+                const GLOBAL_AS int16_t* b = ly + (size_t)y0 * W + x0;
+                const GLOBAL_AS int16_t* const l[4] = {b, b + 4, b + (size_t)4 * W, b + (size_t)4 * W + 4};
+                tb4_tokens(k, o, 4, cs, l, st, true, hd4);
             }
             tok_reserve(o, 2);
             const int h = o.n_tok;
             o.n_tok += 2;
-            const uint32_t hb = tb_tokens(k, o, 1, 2, lcb + (size_t)(y0 >> 1) * Wc + (x0 >> 1), Wc);
-            const uint32_t hr = tb_tokens(k, o, 2, 2, lcr + (size_t)(y0 >> 1) * Wc + (x0 >> 1), Wc);
+            const int cs[4] = {1, 2, 0, 0}, st[4] = {Wc, Wc, 0, 0};
+            const GLOBAL_AS int16_t* const l[4] = {lcb + (size_t)(y0 >> 1) * Wc + (x0 >> 1), lcr + (size_t)(y0 >> 1) * Wc + (x0 >> 1), nullptr, nullptr};
+            tb4_tokens(k, o, 2, cs, l, st, false, hd4);
             if (LANE == 0) {
-                tok_put(o, h, hb);
-                tok_put(o, h + 1, hr);
+                tok_put(o, h, hd4[0]);
+                tok_put(o, h + 1, hd4[1]);
             }
             z += 4;
         }

@@ -336,8 +336,7 @@ struct __attribute__((aligned(16))) Lds {
     //                   lifetime as PRED_PARK
     //   [448, 504)      team kernel, member 0 as pack-A server of 4x4 leaves (kSrv4Byte): results until the owner's job4_ack
     uint32_t decw[128];
-    int32_t q_istar[2];        // shared-Viterbi hand-off, per block: first position with a non-zero state-0 level
-    int32_t q_active;          // this wave's TB takes part in the shared Viterbi
+    int32_t slot_xfer;         // acquire_scratch (wrenc_gpu.hip): the workgroup's scratch region, from thread 0 to every wave
     uint32_t fsum;             // final pass: checksum of the search's reconstruction of the block being re-made
     uint16_t q_pm[3][4][4];    // per block and sub-block of the chunk: parity masks (delta 0, 1), state-0 flag
     uint8_t cu_log2[64];       // per 4x4 luma unit
@@ -376,15 +375,14 @@ struct Ctx {
     int write;        // 0 for a padding wave (batch not a multiple of WPB): compute, never store
     int member;       // team schedule: this wave's place in its team of kTeam waves (0 otherwise)
     int store;        // team schedule: this wave's final-pass blocks are of a real picture (it stores their levels); = write otherwise
-    int solo;         // team kernel: no pooled (workgroup-wide) trellis walk, whatever a request says
+    int solo;         // 1 in the team kernel (where the level schedule's pack-A server runs), 0 in the wave kernel
     int trace;        // diagnostic trace: this wave's evaluations are of a real picture
 };
 
 // LDS: one working set per wave (= per CTU), WPB waves per workgroup, plus tables shared
 // by the workgroup.  File scope so that every access is a DS instruction (no FLAT ops).
 // The waves of a workgroup process the SAME CTU position of WPB different pictures, so
-// they execute the same schedule; the 4-lane Viterbi of all WPB transform blocks is run by
-// one wave in WPB quads at once (see quantize()).
+// they execute the same schedule; each walks its own trellis (dev_quant.h).
 #ifndef WRENC_WPB
 #define WRENC_WPB 4
 #endif
@@ -632,7 +630,8 @@ __device__ __forceinline__ bool nb_avail(Ctx c, int gx, int gy, int tn, int xn, 
 }
 // The five segment availabilities of build_refs (dev_predict.h) as one mask, from the formulas above (the reference's:
 // above_right_avail, below_left_avail, five nb_avail -- some 150 scalar instructions per block, a tenth of the kernel's
-// scalar stream at max-split-depth 3, profiles/r04_issue_model.md).
+// scalar stream at max-split-depth 3, profiles/r04_issue_model.md).  The search reads the table of block_avail_mask
+// below instead; test_avail_tab_kernel holds the two against each other.
 __device__ __forceinline__ int block_avail_formula(Ctx c, int tx, int ty, int tlg, int st) {
     const int tn = 1 << tlg;
     const int gx = c.ctu_x + tx, gy = c.ctu_y + ty;
@@ -649,11 +648,7 @@ __device__ __forceinline__ int block_avail_formula(Ctx c, int tx, int ty, int tl
 // The same from the table: what the coding order allows inside the CTU (and across its borders) is a function of the
 // block's place in the CTU alone; the picture's edges take segments away: everything left of the block needs a column
 // left of it, everything above a row above it, above-right a column right of it, below-left a row below it.
-#ifndef WRENC_AVAIL_TAB
-#define WRENC_AVAIL_TAB 1 // 0: the formulas at every call (until round 4; for A/B runs)
-#endif
 __device__ __forceinline__ int block_avail_mask(Ctx c, int tx, int ty, int tlg, int st) {
-    if (!WRENC_AVAIL_TAB) return block_avail_formula(c, tx, ty, tlg, st);
     const int tn = 1 << tlg;
     const int gx = c.ctu_x + tx, gy = c.ctu_y + ty;
     const int in_ctu = c.k->avail_tab[tlg - 2][(ty >> 2) * 8 + (tx >> 2)];

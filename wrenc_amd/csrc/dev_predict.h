@@ -720,9 +720,6 @@ constexpr int kNoMode = 255; // list entry that is not evaluated (cost f32::MAX)
 //     during SAD lists), stride 4n per block;
 //   * a lane adds the SAD of entry mi into its accumulator when LANE == mi.
 // acc (lane mi): summed SAD of entry mi over the components; entries with mode kNoMode stay 0.
-#ifndef WRENC_SAD4X4
-#define WRENC_SAD4X4 1 // 0: one sample per lane and iteration (rounds 1 .. 3a; kept for A/B runs)
-#endif
 #ifdef WRENC_EXP_NOINLINE_SAD // code-size experiment (profiles/r04_issue_model.md): one copy of the list, called
 #define WRENC_SAD_INLINE __attribute__((noinline))
 #else
@@ -822,7 +819,6 @@ __device__ WRENC_SAD_INLINE unsigned sad_list_angular(const Ctx& c, int comps, i
         WSYNC();
         PROF_MARK(sl1_);
         PROF_ADD2(PH_LEAF + 8, sl0_, sl1_);
-#if WRENC_SAD4X4
         // An iteration of the block-per-lane code costs about nine of the sample-per-lane code below (16 samples a lane
         // instead of one, PDPC for every lane as soon as one entry has it) and takes 64 / G entries, whatever the list's
         // length: it pays when the list fills its iterations -- the 13 directional candidates at every size from 8x8, the
@@ -967,7 +963,6 @@ __device__ WRENC_SAD_INLINE unsigned sad_list_angular(const Ctx& c, int comps, i
             PROF_ADD2(PH_LEAF + 9, sl1_, sl2_);
             continue;
         }
-#endif
         if (nb * nn <= 32) {
             // ---- small blocks (4x4 luma: 16 samples, 4x4 chroma pair: 32): 4 or 2 entries share an
             // iteration, the entry's parameters are per-lane values ----

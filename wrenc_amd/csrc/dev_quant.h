@@ -1,4 +1,4 @@
-// dev_quant.h -- dependent quantisation as a pooled 4-state Viterbi, forward trace + level cost, dequantisation (quantizer.rs)
+// dev_quant.h -- dependent quantisation as a 4-state Viterbi, forward trace + level cost, dequantisation (quantizer.rs)
 // Part of the gfx950 device code of the RD-search path; see wrenc_dev.h for the overall model.
 #pragma once
 
@@ -55,11 +55,6 @@ __device__ __forceinline__ int position_map(int tc, int qd, bool dcn, int nib) {
     const unsigned x = (unsigned)(pv ^ 10);
     return (int)(0x01010000u + (((x * 0x00204081u) & 0x01010101u) << 1));
 }
-
-// Which wave of the workgroup walks the pooled Viterbi.  Waves w and w + 4 share a SIMD with the same
-// two waves of the CU's other workgroup; if every workgroup walked in wave 0, one SIMD of each CU would
-// carry all the serial walks and its waves would reach every barrier last.  Spread by workgroup index.
-__device__ __forceinline__ int walker_wave() { return (int)((blockIdx.x * 2654435761u) >> 30) & (WPB < 4 ? WPB - 1 : 3); }
 
 // Path costs are kept in 32 bits, DOUBLED, with the tie-break of quantizer.rs:505 in the low bit.
 // Only cost DIFFERENCES between the four states decide the path, and they are bounded: any
@@ -183,235 +178,6 @@ __device__ __forceinline__ unsigned shift_in_less(unsigned bits, int kb, int ka)
     return __builtin_amdgcn_alignbit(bits, (unsigned)(kb - ka), 31);
 }
 
-// Dependent quantisation of nb transform blocks of side n (nb = 1 luma, 2 = Cb+Cr pair):
-// coefficients r1 ([blk][y][x]) -> levels in place; returns the summed level cost
-// (block_splitter.rs:436-458).  Scratch: r2, decw.  `*overflow` is set when a level needs a table
-// entry >= 1024 (the reference panics there).
-//
-// Backward pass = 4-state Viterbi equivalent of the reference's memoised DFS (SURVEY.md Q3,
-// proven equal to the literal DFS in tests/test_oracle.py).  Per chunk of positions all lanes
-// precompute the two branch costs for both values of delta = (state > 1); then ONE lane per
-// state and block walks the chunk, exchanging path costs with two DPP quad permutes.
-//   shared == true : every wave of the workgroup is in this call with blocks of the same size
-//                    (same schedule, see SHW above); wave 0 walks all WPB*nb blocks at once, one
-//                    quad of lanes per block, between two workgroup barriers per chunk.
-//                    `active == false` = this wave only keeps the barriers company.
-//   shared == false: the wave walks its own blocks in quads 0..nb-1 (final pass, tests).
-// Forward trace = composition of per-position state maps (prefix scan over lanes), then every
-// lane emits its own positions and their level costs.
-// parity of this wave's pooled quantisation calls, kept in an unused cell of q_pm (reset in encode_ctu)
-__device__ __forceinline__ int zero_flag_cell() {
-    const int par = uni((int)SH.q_pm[0][0][3]) & 1;
-    if (LANE == 0) SH.q_pm[0][0][3] = (uint16_t)(par ^ 1);
-    return par;
-}
-
-// Zero blocks: when every coefficient of the call is zero the levels are zero and cost nothing (zeros behind the
-// last non-zero level are free, block_splitter.rs:436-458), and r1 already holds them.  A wave in that case skips
-// the trace; when NO wave of the workgroup has a non-zero coefficient (the usual case in flat areas) the pooled
-// walk ends after the first barrier of its first chunk, where the waves see each other's flags.  *any_level tells
-// the caller whether any level is non-zero (else dequantisation and the inverse transform are skipped too).
-__device__ __forceinline__ long long quantize(Ctx c, int lg, int nb, bool shared, bool active, int* overflow, bool* any_level) {
-    c = uni(c);
-    lg = uni(lg);
-    nb = uni(nb);
-    const CONST_AS DevConst* k = c.k;
-    const int n = 1 << lg;
-    const int P = n * n;
-    const int lgP = 2 * lg;
-    const int sh = 8 + lg - 5 + 1; // quantizer.rs:558-569
-    const int off = (1 << sh) >> 1;
-    const int lsc = k->lsc;
-    const CONST_AS uint16_t* scan = k->scan_idx[lg - 2];
-    int16_t* tcs = (int16_t*)SH.r2;          // [blk][p]: coefficient in reverse-scan order (all of r2 for a 32x32 block)
-    int32_t* cc = (int32_t*)SH.r1;           // chunk: [blk][CH][6] ints (coefficients are dead after the gather)
-    const uint16_t* dec16 = (const uint16_t*)SH.decw; // decisions: [blk][sub-block][state] 16-bit masks
-    PROF_MARK(q0_);
-    int istar0 = P, istar1 = P;
-    bool any_nz = false;
-    if (active) {
-        int first0 = P, first1 = P, nzl = 0;
-        for (int idx = LANE; idx < nb * P; idx += 64) {
-            const int blk = idx >> lgP, p = idx & (P - 1);
-            const int tc = SH.r1[blk * P + scan[p]];
-            nzl |= tc;
-            const int qd = quotient(k, tc, sh, off);
-            tcs[idx] = (int16_t)tc;
-            if (tc != 0 && (qd >> 1) > 0) {
-                if (blk)
-                    first1 = min(first1, p);
-                else
-                    first0 = min(first0, p);
-            }
-        }
-        istar0 = wave_min_i32(first0);
-        if (nb == 2) istar1 = wave_min_i32(first1);
-        any_nz = __ballot(nzl != 0) != 0ULL;
-    }
-    *any_level = false;
-    if (!shared && !any_nz) return 0; // solo call on a zero block (or an inactive one): nothing to walk
-    // "this wave has a non-zero coefficient", read by the whole workgroup below; two cells in turn (every wave makes
-    // the same sequence of pooled calls), so that a wave already in its next call cannot overwrite a flag that a
-    // slow wave has yet to read
-    const int fcell = shared ? zero_flag_cell() : 0;
-    if (LANE == 0) {
-        SH.q_istar[fcell] = any_nz ? 1 : 0;
-        SH.q_active = (active && any_nz) ? 1 : 0;
-    }
-    PROF_MARK(q1_);
-    PROF_ADD2(PH_QPRE, q0_, q1_);
-    const int ldq1 = (int)ldq_at(c, 1);
-    const int st = LANE & 3;
-    const int delta = st > 1 ? 1 : 0;
-    const int CH = min(P, nb == 2 ? 32 : 64); // chunk positions per block
-    // which block this lane's quad walks: (wave, blk) = (quad / nb, quad % nb) in shared mode
-    const int quad = LANE >> 2;
-    const int wblk = nb == 2 ? (quad & 1) : 0;
-    const int wwave = nb == 2 ? (quad >> 1) : quad;
-    const bool walker = shared ? (WAVE == walker_wave() && wwave < WPB) : (quad < nb);
-    const Lds* tb = shared ? &SHW[wwave < WPB ? wwave : 0] : &SH;
-    const int32_t* wcc = (const int32_t*)tb->r1 + wblk * CH * 6;
-    int C = 0;
-    int ovf = 0;
-    for (int base = P - CH; base >= 0; base -= CH) {
-        PROF_MARK(qb0_);
-        WSYNC();
-        if (active && any_nz) { // (a zero block writes no entries: r1 stays its all-zero levels)
-            // per position and state class (0: state 0, 1: state 1, 2: states 2 and 3): (u, w) doubled,
-            // see above; per sub-block: parity masks of the two delta classes and, for state 0, whether
-            // its first position in coding order (kk == 15) keeps a zero inside the trailing run
-            const bool mine = LANE < nb * CH;
-            const int blk = LANE >= CH ? 1 : 0;
-            const int i = LANE - blk * CH;
-            const int p = base + i;
-            int par0 = 0, par1 = 0, adj = 0;
-            if (mine) {
-                const int tc = tcs[blk * P + p];
-                chunk_entry(c, cc + LANE * 6, tc, quotient(k, tc, sh, off), p == P - 1, p <= (blk ? istar1 : istar0),
-                            sh, off, lsc, ldq1, &par0, &par1, &adj, &ovf);
-            }
-            const unsigned long long b0 = __ballot(mine && par0), b1 = __ballot(mine && par1), ba = __ballot(mine && adj);
-            if (mine && (LANE & 15) == 0) {
-                uint16_t* pm = SH.q_pm[blk][i >> 4];
-                pm[0] = (uint16_t)(b0 >> LANE);
-                pm[1] = (uint16_t)(b1 >> LANE);
-                pm[2] = (uint16_t)((ba >> (LANE + 15)) & 1);
-            }
-        }
-        PROF_MARK(qb1_);
-        if (shared)
-            __syncthreads();
-        else
-            WSYNC();
-        PROF_MARK(qb2_);
-        if (shared && base == P - CH) {
-            // first chunk: does ANY wave of the workgroup have a non-zero coefficient?  (lane w reads wave w's flag)
-            const bool wg_nz = __ballot(LANE < WPB && SHW[LANE < WPB ? LANE : 0].q_istar[fcell] != 0) != 0ULL;
-            if (!wg_nz) break; // every wave takes this exit: no barrier is left behind
-        }
-        if (walker && (!shared || tb->q_active)) {
-            const int cls = st == 0 ? 0 : (st == 1 ? 1 : 2);
-            uint16_t* wdec = (uint16_t*)const_cast<uint32_t*>(tb->decw) + wblk * (P >> 2);
-            for (int g16 = CH - 16; g16 >= 0; g16 -= 16) { // one 4x4 sub-block per iteration
-                const uint16_t* pm = tb->q_pm[wblk][g16 >> 4];
-                const unsigned parmask = pm[st > 1 ? 1 : 0];
-                const bool adj = st == 0 && pm[2] != 0;
-                // all 16 entries of the sub-block are fetched before its walk (a serial dependency
-                // chain that should not wait for LDS position by position)
-                int2 cur[16];
-#pragma unroll
-                for (int kk = 0; kk < 16; ++kk) cur[kk] = *(const int2*)&wcc[(g16 + kk) * 6 + 2 * cls];
-                unsigned bits = 0;
-#pragma unroll
-                for (int kk = 15; kk >= 0; --kk) {
-                    const int2 e = cur[kk];
-                    const int KA = e.x + dpp_quad<0xD8>(C); // C[trans[s][0]]: quad_perm [0,2,1,3]
-                    const int KB = e.y + dpp_quad<0x72>(C); // C[trans[s][1]]: quad_perm [2,0,3,1]
-                    C = min(KA, KB) & ~1;
-                    bits = shift_in_less(bits, KB, KA);
-                    if (kk == 15) { // first position of a sub-block in coding order (:512-514)
-                        const bool choseB = KB < KA;
-                        const bool pick1 = choseB != (((parmask >> 15) & 1) != 0);
-                        if (!pick1 && adj) C -= 2 * ldq1;
-                    }
-                }
-                bits ^= parmask; // choseB -> pick1
-                // renormalise: subtract the quad minimum (decisions depend on differences only)
-                int m = min(C, dpp_quad<0xB1>(C));  // quad_perm [1,0,3,2]
-                m = min(m, dpp_quad<0x4E>(m));      // quad_perm [2,3,0,1]
-                C -= m;
-                wdec[((base + g16) >> 4) * 4 + st] = (uint16_t)bits;
-            }
-        }
-        PROF_MARK(qb3_);
-        if (shared) __syncthreads();
-        PROF_MARK(qb4_);
-        PROF_ADD2(PH_QB_PRE, qb0_, qb1_);
-        PROF_ADD2(PH_QB_WAIT1, qb1_, qb2_);
-        PROF_ADD2(PH_QB_WALK, qb2_, qb3_);
-        PROF_ADD2(PH_QB_WAIT2, qb3_, qb4_);
-    }
-    WSYNC();
-    PROF_MARK(q2_);
-    PROF_ADD2(PH_QBACK, q1_, q2_);
-    if (!active || !any_nz) return 0;
-    // ---- forward trace from state 0 (quantizer.rs:686-721) + level-cost walk ----
-    // lanes are split evenly between the blocks; each lane owns `per` consecutive positions
-    const int half = nb == 2 ? 32 : 64;
-    const int blk = nb == 2 ? (LANE >> 5) : 0;
-    const int lane_in = LANE & (half - 1);
-    const int per = P >= half ? P / half : 1;
-    const int p0 = lane_in * per;
-    const bool act = p0 < P;
-    const int16_t* btcs = tcs + blk * P;
-    const uint16_t* bdec = dec16 + blk * (P >> 2);
-    int fmap = kMapId;
-    const DecMasks dm = dec_masks(bdec, act ? p0 : 0); // a lane's positions lie in one sub-block (per divides 16)
-    if (act) {
-        for (int j = 0; j < per; ++j) {
-            const int p = p0 + j;
-            const int tc = btcs[p];
-            fmap = compose_map(position_map(tc, quotient(k, tc, sh, off), p == P - 1, dec_nib(dm, p)), fmap);
-        }
-    }
-    // inclusive prefix composition across the lanes of a block: Hillis-Steele inside the 16-lane rows
-    // with row_shr DPP moves (lanes without a source get the identity map), then the row totals
-    // travel with row_bcast:15 / row_bcast:31 (the two blocks of a chroma pair are lanes 0..31 and
-    // 32..63, so they simply skip the last step).  No LDS-crossbar shuffles.
-    int pre = fmap;
-    pre = compose_map(pre, __builtin_amdgcn_update_dpp(kMapId, pre, 0x111, 0xF, 0xF, false)); // row_shr:1
-    pre = compose_map(pre, __builtin_amdgcn_update_dpp(kMapId, pre, 0x112, 0xF, 0xF, false)); // row_shr:2
-    pre = compose_map(pre, __builtin_amdgcn_update_dpp(kMapId, pre, 0x114, 0xF, 0xF, false)); // row_shr:4
-    pre = compose_map(pre, __builtin_amdgcn_update_dpp(kMapId, pre, 0x118, 0xF, 0xF, false)); // row_shr:8
-    pre = compose_map(pre, __builtin_amdgcn_update_dpp(kMapId, pre, 0x142, 0xA, 0xF, false)); // row_bcast:15 -> rows 1, 3
-    if (nb == 1) pre = compose_map(pre, __builtin_amdgcn_update_dpp(kMapId, pre, 0x143, 0xC, 0xF, false)); // row_bcast:31 -> rows 2, 3
-    // state after all previous lanes of the block, starting from 0
-    int entry = __builtin_amdgcn_update_dpp(0, pre, 0x138, 0xF, 0xF, false) & 3; // wave_shr:1
-    if (lane_in == 0) entry = 0;
-    long long sum_nz = 0;
-    unsigned zmask = 0;
-    int fnz = P;
-    if (act) {
-        int state = entry;
-        for (int j = 0; j < per; ++j) {
-            const int p = p0 + j;
-            const int tc = btcs[p];
-            SH.r1[blk * P + scan[p]] = (int16_t)emit_level(c, tc, quotient(k, tc, sh, off), p == P - 1, dec_nib(dm, p), p, j,
-                                                           state, zmask, sum_nz, fnz, ovf);
-        }
-    }
-    const int pf = group_min_i32(fnz, half); // zeros before a block's first non-zero level cost nothing
-    if (act) // zeros after the first non-zero position: positions j > pf - p0 of this lane
-        sum_nz += (long long)__popc(zmask >> min(max(pf - p0 + 1, 0), 16)) * SHT.lv[0];
-    *any_level = __ballot(pf < P) != 0ULL;
-    const long long sum = wave_sum_i64(sum_nz);
-    if (__ballot(ovf != 0) != 0ULL) *overflow = 1;
-    WSYNC();
-    PROF_MARK(q3_);
-    PROF_ADD2(PH_QTRACE, q2_, q3_);
-    return sum;
-}
-
 // ---------------------------------------------------------------------------
 // The head of a chain, proven zero without walking it (round 4).
 //
@@ -504,14 +270,7 @@ __device__ __forceinline__ int head_alpha1(int tc, const HeadK& h) {
 // One batch of 64 positions (lane = position p0 + LANE of a chain of P) of the region search: `open` while no position has
 // ended the region (still open behind the last batch: the whole block is zero, head_sb gives P / 16); arun = this lane's
 // minimum of alpha over the region so far; sb = the sub-block the walk must reach
-#ifndef WRENC_HEAD_EXIT
-#define WRENC_HEAD_EXIT 1 // 0: every chain is walked to its end (round 3's behaviour; for A/B runs)
-#endif
 __device__ __forceinline__ void head_batch(int tc, int p, int P, bool valid, const HeadK& h, const HeadT& t, bool& open, int& arun, int& sb) {
-    if (!WRENC_HEAD_EXIT) {
-        sb = 0;
-        open = false;
-    }
     if (!open) return;
     const int alpha = head_alpha1(tc, h);
     const unsigned long long B = __ballot(valid && head_bad(tc, p == P - 1, t));
@@ -525,7 +284,7 @@ __device__ __forceinline__ void head_batch(int tc, int p, int P, bool valid, con
     }
 }
 // the sub-block the walk must reach, once every batch of the chain has been seen: nsb (= nothing to walk) if none ended the region
-__device__ __forceinline__ int head_sb(bool open, int sb, int nsb) { return (open && WRENC_HEAD_EXIT) ? nsb : sb; }
+__device__ __forceinline__ int head_sb(bool open, int sb, int nsb) { return open ? nsb : sb; }
 // After the walk of sub-block sb (path costs C of the quad's four states, doubled): is G >= -alpha_min ?
 __device__ __forceinline__ bool head_test(int C, int st, int amin) {
     const int c0 = dpp_quad<0x00>(C);                  // state 0's cost in every lane of the quad
@@ -535,7 +294,21 @@ __device__ __forceinline__ bool head_test(int C, int st, int amin) {
     return (m - c0) + 2 * amin >= 0;                   // |m - c0| < 2^30 (see kNoBranch), amin <= 2^28
 }
 
-// quantize() for ONE wave on its own blocks (no pooling), with the head exit: same results.
+// Dependent quantisation of nb transform blocks of side n (nb = 1 luma, 2 = Cb+Cr pair) by one wave:
+// coefficients r1 ([blk][y][x]) -> levels in place; returns the summed level cost
+// (block_splitter.rs:436-458).  Scratch: r2, decw.  `*overflow` is set when a level needs a table
+// entry >= 1024 (the reference panics there).
+//
+// Backward pass = 4-state Viterbi equivalent of the reference's memoised DFS (SURVEY.md Q3,
+// proven equal to the literal DFS in tests/test_oracle.py).  Per chunk of positions all lanes
+// precompute the two branch costs for both values of delta = (state > 1); then ONE lane per
+// state and block (quads 0..nb-1) walks the chunk, exchanging path costs with two DPP quad permutes,
+// down to where the head exit (above) proves the rest of the chain zero.
+// Forward trace = composition of per-position state maps (prefix scan over lanes), then every
+// lane emits its own positions and their level costs.
+// Zero blocks: when every coefficient of the call is zero the levels are zero and cost nothing (zeros behind the
+// last non-zero level are free, block_splitter.rs:436-458), and r1 already holds them.  *any_level tells the caller
+// whether any level is non-zero (else dequantisation and the inverse transform are skipped too).
 __device__ __forceinline__ long long quantize_solo(Ctx c, int lg, int nb, int* overflow, bool* any_level) {
     c = uni(c);
     lg = uni(lg);
@@ -670,7 +443,7 @@ __device__ __forceinline__ long long quantize_solo(Ctx c, int lg, int nb, int* o
                     }
                 }
                 bits ^= parmask; // choseB -> pick1
-                int m = min(C, dpp_quad<0xB1>(C));  // renormalise (see quantize())
+                int m = min(C, dpp_quad<0xB1>(C));  // renormalise: subtract the quad minimum (decisions depend on differences only)
                 m = min(m, dpp_quad<0x4E>(m));
                 C -= m;
                 wdec[sb * 4 + st] = (uint16_t)bits;
@@ -691,7 +464,7 @@ __device__ __forceinline__ long long quantize_solo(Ctx c, int lg, int nb, int* o
     WSYNC();
     PROF_MARK(q2_);
     PROF_ADD2(PH_QBACK, q1_, q2_);
-    // ---- forward trace from state 0 (quantizer.rs:686-721) + level-cost walk, as in quantize(), from where each block's
+    // ---- forward trace from state 0 (quantizer.rs:686-721) + level-cost walk, from where each block's
     //      walk ended: the levels before that are zero (r1's chunk entries are dead: zero all levels first), the trace
     //      reaches that position in state 0, and the block's lanes share what is left ----
     const int start0 = 16 * __builtin_amdgcn_readlane(wsb, 0), start1 = nb == 2 ? 16 * __builtin_amdgcn_readlane(wsb, 4) : 0;
@@ -749,19 +522,15 @@ __device__ __forceinline__ long long quantize_solo(Ctx c, int lg, int nb, int* o
     return sum;
 }
 
-// Dependent quantisation of the three transform blocks of one candidate in ONE pooled pass: luma
+// Dependent quantisation of the three transform blocks of one candidate in ONE pass: luma
 // n0 x n0 at r1[0, P0), Cb and Cr (n0/2)^2 at r1[P0, P0 + Pc) and r1[P0 + Pc, P0 + 2 Pc), n0 = 8 or
-// 16 (search only: every wave of the workgroup is in this call with the same block size).  Same
-// algorithm as quantize(); the chroma chains are a quarter as long as the luma chain, so a chunk is
-// 64 luma + 16 + 16 chroma positions and the chroma blocks ride along for free.  The 3 * WPB walks take one quad
-// of lanes each, all luma blocks first, then Cb, then Cr, over as many walker waves as that needs (WPB = 4: twelve
-// quads of one wave).
+// 16 (search only).  Same algorithm as quantize_solo without the head exit; the chroma chains are a quarter as
+// long as the luma chain, so a chunk is 64 luma + 16 + 16 chroma positions and the chroma blocks ride along for
+// free: the wave walks its three blocks in quads 0..2.  `active == false`: nothing to do.
 // Scratch: r2 = [scan-order coefficients | chroma chunk entries], r1 = luma chunk entries (the coefficients are
-// dead after the gather and every level is written at the end, as in quantize()), decw.
-// shared == false: the wave walks its own three blocks in quads 0..2, no workgroup barrier (as in quantize()).
-__device__ __forceinline__ void quantize3(Ctx c, int lg0, bool shared, bool active, int* overflow, long long* lvl_y,
+// dead after the gather and every level is written at the end), decw.
+__device__ __forceinline__ void quantize3(Ctx c, int lg0, bool active, int* overflow, long long* lvl_y,
                                           long long* lvl_c, bool* any_y, bool* any_c) {
-    static_assert(WPB <= 8, "a walker wave has 16 quads; walker_wave() + 1 must stay below WPB");
     c = uni(c);
     lg0 = uni(lg0);
     const CONST_AS DevConst* k = c.k;
@@ -808,28 +577,19 @@ __device__ __forceinline__ void quantize3(Ctx c, int lg0, bool shared, bool acti
         istar2 = wave_min_i32(first2);
         any_nz = __ballot(nzl != 0) != 0ULL;
     }
-    if (!shared && !any_nz) return; // solo call on three zero blocks (or an inactive wave): nothing to walk
-    const int fcell = shared ? zero_flag_cell() : 0;
-    if (LANE == 0) {
-        SH.q_istar[fcell] = any_nz ? 1 : 0;
-        SH.q_active = (active && any_nz) ? 1 : 0;
-    }
+    if (!any_nz) return; // three zero blocks (or an inactive call): nothing to walk
     PROF_MARK(q1_);
     PROF_ADD2(PH_QPRE, q0_, q1_);
     const int ldq1 = (int)ldq_at(c, 1);
     const int st = LANE & 3;
     const int cls = st == 0 ? 0 : (st == 1 ? 1 : 2);
-    // walker quads: global quad gq = 16 * (walker wave) + LANE / 4 walks block kind gq / WPB of wave gq % WPB
-    // (solo: quad gq walks block kind gq of this wave)
-    constexpr int kWalkers = (3 * WPB + 15) / 16;
-    const int wv = shared ? ((WAVE - walker_wave()) & (WPB - 1)) : 0; // 0 .. kWalkers - 1: the walker waves
-    const int gq = 16 * wv + (LANE >> 2);
-    const int wb = min(shared ? gq / WPB : gq, 2);
-    const bool walker = shared ? (wv < kWalkers && gq < 3 * WPB) : (gq < 3);
-    const Lds* tb = shared ? &SHW[gq % WPB] : &SH;
-    const int32_t* wcc = wb == 0 ? (const int32_t*)tb->r1
-                                 : (const int32_t*)((const char*)tb->r2 + kCcByte) + (wb == 1 ? 0 : 16) * 6;
-    uint16_t* wdec = (uint16_t*)const_cast<uint32_t*>(tb->decw) + (wb == 0 ? 0 : (wb == 1 ? (P0 >> 2) : (P0 >> 2) + (Pc >> 2)));
+    // walker quads: quad gq = LANE / 4 walks block kind gq (0 luma, 1 Cb, 2 Cr)
+    const int gq = LANE >> 2;
+    const int wb = min(gq, 2);
+    const bool walker = gq < 3;
+    const int32_t* wcc = wb == 0 ? (const int32_t*)SH.r1
+                                 : (const int32_t*)((const char*)SH.r2 + kCcByte) + (wb == 1 ? 0 : 16) * 6;
+    uint16_t* wdec = (uint16_t*)SH.decw + (wb == 0 ? 0 : (wb == 1 ? (P0 >> 2) : (P0 >> 2) + (Pc >> 2)));
     const int wnsb = wb == 0 ? 4 : 1; // sub-blocks of the walker's block per chunk
     int C = 0;
     int ovf = 0;
@@ -838,7 +598,7 @@ __device__ __forceinline__ void quantize3(Ctx c, int lg0, bool shared, bool acti
         const int base0 = P0 - 64 * (ch + 1), basec = Pc - 16 * (ch + 1);
         PROF_MARK(qb0_);
         WSYNC();
-        if (active && any_nz) {
+        {
 #pragma unroll 1
             for (int pass = 0; pass < 2; ++pass) {
                 const int e = LANE + 64 * pass;
@@ -867,20 +627,12 @@ __device__ __forceinline__ void quantize3(Ctx c, int lg0, bool shared, bool acti
                 }
             }
         }
+        WSYNC();
         PROF_MARK(qb1_);
-        if (shared)
-            __syncthreads();
-        else
-            WSYNC();
-        PROF_MARK(qb2_);
-        if (shared && ch == 0) { // zero blocks in every wave of the workgroup: see quantize()
-            const bool wg_nz = __ballot(LANE < WPB && SHW[LANE < WPB ? LANE : 0].q_istar[fcell] != 0) != 0ULL;
-            if (!wg_nz) break;
-        }
-        if (walker && (!shared || tb->q_active)) {
+        if (walker) {
             for (int sbi = wnsb - 1; sbi >= 0; --sbi) { // one 4x4 sub-block per iteration
                 const int g16 = sbi * 16;
-                const uint16_t* pm = tb->q_pm[wb][sbi];
+                const uint16_t* pm = SH.q_pm[wb][sbi];
                 const unsigned parmask = pm[st > 1 ? 1 : 0];
                 const bool adj = st == 0 && pm[2] != 0;
                 int2 cur[16];
@@ -908,17 +660,12 @@ __device__ __forceinline__ void quantize3(Ctx c, int lg0, bool shared, bool acti
             }
         }
         PROF_MARK(qb3_);
-        if (shared) __syncthreads();
-        PROF_MARK(qb4_);
         PROF_ADD2(PH_QB_PRE, qb0_, qb1_);
-        PROF_ADD2(PH_QB_WAIT1, qb1_, qb2_);
-        PROF_ADD2(PH_QB_WALK, qb2_, qb3_);
-        PROF_ADD2(PH_QB_WAIT2, qb3_, qb4_);
+        PROF_ADD2(PH_QB_WALK, qb1_, qb3_);
     }
     WSYNC();
     PROF_MARK(q2_);
     PROF_ADD2(PH_QBACK, q1_, q2_);
-    if (!active || !any_nz) return;
     // ---- forward trace + level cost: lanes 0..31 luma, 32..47 Cb, 48..63 Cr ----
     const int b = LANE < 32 ? 0 : (LANE < 48 ? 1 : 2);
     const int lane_in = b == 0 ? LANE : (LANE & 15);
@@ -988,7 +735,7 @@ __device__ __forceinline__ void quantize3(Ctx c, int lg0, bool shared, bool acti
 
 // Dependent quantisation of nb <= 4 luma blocks of 4x4 at once (the candidates of a packed 4x4 leaf search,
 // dev_search.h K_LEAF4): block b = lanes 16 b .. 16 b + 15, one lane per position, one quad walks each block's
-// 16 positions (a single chunk: no barrier of any kind).  Same algorithm and arithmetic as quantize(); block b's
+// 16 positions (a single chunk: no barrier of any kind).  Same algorithm and arithmetic as quantize_solo; block b's
 // level cost (block_splitter.rs:436-458) comes back in lvl[b], "has a non-zero level" in bit b of *any_mask.
 // Coefficients r1[16 b ..] -> levels in place (a lane keeps its coefficient in a register).  Scratch: r1 chunk
 // entries, decw.
@@ -1020,14 +767,12 @@ __device__ __forceinline__ void quantize_p16(Ctx c, int nb, int* overflow, long 
     lvl[0] = lvl[1] = lvl[2] = lvl[3] = 0;
     *any_mask = 0;
     if (nzb == 0ULL) return; // every block is zero: the levels are the zero coefficients already in r1
-    if (WRENC_HEAD_EXIT) {
-        // every block's levels proven zero (the head proof over the whole block, head_alpha): nothing to walk or trace
-        if (__ballot(mine && head_bad(tc, p == P - 1, ht)) == 0ULL) {
-            WSYNC();
-            if (mine) SH.r1[blk * P + scan[p]] = 0;
-            WSYNC();
-            return;
-        }
+    // every block's levels proven zero (the head proof over the whole block, head_alpha): nothing to walk or trace
+    if (__ballot(mine && head_bad(tc, p == P - 1, ht)) == 0ULL) {
+        WSYNC();
+        if (mine) SH.r1[blk * P + scan[p]] = 0;
+        WSYNC();
+        return;
     }
     PROF_MARK(q1_);
     PROF_ADD2(PH_QPRE, q0_, q1_);
@@ -1131,7 +876,7 @@ __device__ __forceinline__ void quantize_p16(Ctx c, int nb, int* overflow, long 
 // rows once the luma chains are done, take the chroma chains one after the other, a chain staying in its row until
 // it is finished.  The serial part of a pack of three 8x8 candidates is 5 x 16 steps for nine chains, of two 16x16
 // candidates 16 x 16 steps for six chains -- where the one-candidate-per-request search walked the luma chain of each
-// candidate between two workgroup barriers per 64 positions.  Same arithmetic as quantize(): chunk_entry, the
+// candidate between two workgroup barriers per 64 positions.  Same arithmetic as quantize_solo: chunk_entry, the
 // one-compare walk, the forward trace by composed state maps, emit_level.  Levels in place; per candidate the level
 // cost of the luma block and of the chroma pair (block_splitter.rs:436-458) and whether any level of the pack's luma /
 // chroma blocks is non-zero.
@@ -1236,7 +981,7 @@ __device__ __forceinline__ void trace_rows16(const Ctx& c, int nblk, const int16
     }
 }
 
-// the same for ONE block of 256 positions over the whole wave (four consecutive positions per lane), as quantize()
+// the same for ONE block of 256 positions over the whole wave (four consecutive positions per lane), as quantize_solo
 __device__ __forceinline__ void trace_wave256(const Ctx& c, const int16_t* tcs, const uint16_t* dec16, int rbase,
                                               const CONST_AS uint16_t* scan, int sh, int off, long long* lvl, bool* any, int& ovf,
                                               int start = 0) {
@@ -1359,7 +1104,7 @@ __device__ __forceinline__ void quantize_pk(Ctx c, int nc, int* overflow, long l
             const unsigned long long B = __ballot(mine && head_bad(tc, i16 == 15, htc));
 #pragma unroll
             for (int rw = 0; rw < 4; ++rw) // (lane 4 + block of v_low: 1 = nothing to walk)
-                if (lane == 4 + 4 * ps + rw) v_low = (WRENC_HEAD_EXIT && ((B >> (16 * rw)) & 0xFFFFULL) == 0ULL) ? 1 : 0;
+                if (lane == 4 + 4 * ps + rw) v_low = (((B >> (16 * rw)) & 0xFFFFULL) == 0ULL) ? 1 : 0;
         }
     } else {
         const HeadK hkc = head_consts(shc, offc, lsc);
@@ -1500,7 +1245,7 @@ __device__ __forceinline__ void quantize_pk(Ctx c, int nc, int* overflow, long l
                     }
                 }
                 bits ^= parmask; // choseB -> pick1
-                int m = min(C, dpp_quad<0xB1>(C)); // renormalise (see quantize())
+                int m = min(C, dpp_quad<0xB1>(C)); // renormalise (see quantize_solo)
                 m = min(m, dpp_quad<0x4E>(m));
                 C -= m;
                 dec16[(wid < 4 ? 4 * SBL * wid : 4 * SBL * nc + 4 * SBC * (wid - 4)) + 4 * wsb + st] = (uint16_t)bits;

@@ -10,23 +10,7 @@ namespace wrenc {
 // Evaluation requests and the evaluator
 // ---------------------------------------------------------------------------
 enum { K_SADLIST = 0, K_FULL = 1, K_NOP = 2, K_SADSEARCH = 3, K_CCLMSEARCH = 4, K_LEAF4 = 5, K_LEAFC4 = 6, K_LEAF8 = 7, K_LEAF16 = 8, K_SPLIT8 = 9, K_SERVE4 = 10 };
-#ifndef WRENC_POOL_MIN_TLG
-#define WRENC_POOL_MIN_TLG 6
-#endif
 enum { COPY_NONE = 0, COPY_SAVE = 1, COPY_RESTORE = 2, COPY_PULL = 3 };
-// build knobs (tools/README.md): the level schedule of the team kernel at max-split-depth 3; an 8x8 CU's split as one request
-#ifndef WRENC_LEVELS
-#define WRENC_LEVELS 1
-#endif
-#ifndef WRENC_SPLIT8
-#define WRENC_SPLIT8 1
-#endif
-#ifndef WRENC_SERVER // level schedule: member 0, idle once the 32x32 candidate is done, runs pack {planar, DC} of member 2's 8x8 leaves
-#define WRENC_SERVER 1
-#endif
-#ifndef WRENC_LEVELS_ALL_DEPTHS  // 0: the level schedule at max-split-depth 3 only, round 2's team below
-#define WRENC_LEVELS_ALL_DEPTHS 1
-#endif
 
 struct Req {
     int kind;       // K_SADLIST: predict + SAD of a list of modes (block_splitter.rs:64-108, 476-522);
@@ -49,8 +33,7 @@ struct Req {
     int comps;      // bit 0: luma block, bit 1: Cb+Cr pair
     int tx, ty, tlg;
     int ml, mc;     // K_FULL: luma / chroma mode
-    bool shared;    // quantiser: pooled Viterbi of the workgroup (search) or solo (regen, final pass)
-    bool active;    // false: walk the schedule only (keeps the workgroup's barriers aligned)
+    bool active;    // false: the request computes nothing (a candidate the reference skips keeps its place in the sequence)
     bool refs0, refs1; // (re)build the luma / chroma reference samples of the block first
     bool final;     // final pass: store the levels, count reconstruction changes
     int stage;      // before anything else: stage the block's originals in LDS (component bits; blocks <= 16x16 only)
@@ -288,9 +271,6 @@ __device__ __forceinline__ ListOut angular_list(const Ctx& c, const Req& q, int 
     return o;
 }
 
-#ifndef WRENC_STEP_ONE_LIST
-#define WRENC_STEP_ONE_LIST 1
-#endif
 // The SAD part of a luma / single-tree leaf search: the 13 directional candidates, their first minimum and the two
 // step-search rounds around it (block_splitter.rs:899-973).  cm: the mode found, smin: its SAD.
 // ONE copy of the list code (sad_list_angular is a couple of thousand instructions, inlined): the rounds are iterations
@@ -305,7 +285,7 @@ __device__ __forceinline__ void sad_search(const Ctx& c, const Req& q, int& cm_o
     // mode's SAD does not depend on the list it is in; the decisions below are the two rounds' in their order, an
     // entry the reference would not evaluate (Q12) is kNoMode here as there, and only the probes the reference makes
     // are traced.
-    const bool six = WRENC_STEP_ONE_LIST && q.tlg <= 3;
+    const bool six = q.tlg <= 3;
     const int rounds = six ? 2 : 3;
     int cm = 0;
     unsigned cur = kNoSad;
@@ -431,15 +411,11 @@ __device__ __forceinline__ Res evaluate(const Ctx& c, const PicBufs& pb, const R
     PROF_ADD2(PH_COPY, tcp0_, tcp1_);
     if (q.kind == K_NOP) return r;
     if (q.stage) stage_org_leaf(c, q.stage, q.tx, q.ty, q.tlg);
-    // (with K_SPLIT8 and the level schedule on, nothing asks for a 4x4 leaf by itself: one copy of the two searches less)
-    if (D3 && !(WRENC_SPLIT8 && WRENC_LEVELS)) {
-        if (q.kind == K_LEAF4) return leaf4_search(c, q, overflow);
-        if (q.kind == K_LEAFC4) return leafc4_search(c, q, overflow);
-    }
+    // (4x4 leaves are searched inside K_SPLIT8 only: nothing asks for one by itself)
     if (q.kind == K_LEAF8) return leaf8_search(c, q, overflow);
     if (q.kind == K_LEAF16) return leaf16_search(c, q, overflow);
     if (D3 && q.kind == K_SPLIT8) return split8_search(c, q, overflow);
-    if (D3 && WRENC_SERVER && q.kind == K_SERVE4) { // (team kernel, member 0 only)
+    if (D3 && q.kind == K_SERVE4) { // (team kernel, member 0 only)
         serve_pack4(c, q, overflow);
         return r;
     }
@@ -462,17 +438,13 @@ __device__ __forceinline__ Res evaluate(const Ctx& c, const PicBufs& pb, const R
     }
     if (q.kind == K_FULL || q.kind == K_CCLMSEARCH) {
         // A candidate of the search with an 8x8 or 16x16 luma block quantises its three transform
-        // blocks in one pass (quantize3, pooled or not): both components go through the first half, then
-        // the pass, then both through the second half.  Everything else runs component by component
-        // (the two share r1 / r2).  One copy of each stage either way.
-        // Pooling the Viterbi walk of the workgroup's WPB blocks pays for long walks; a block of few positions walks
-        // faster alone than the two workgroup barriers per chunk cost (WRENC_POOL_MIN_TLG: smallest CU size, log2,
-        // whose transform blocks are pooled; every wave of the workgroup evaluates the same size, so they agree)
-        const bool pooled = q.shared && !c.solo && q.tlg >= WRENC_POOL_MIN_TLG;
+        // blocks in one pass (quantize3): both components go through the first half, then the pass, then
+        // both through the second half.  Everything else runs component by component (the two share r1 / r2).
+        // One copy of each stage either way.  Every trellis walk is the wave's own.
         #ifdef WRENC_EXP_NO_MERGED
         const bool merged = false;
 #else
-        const bool merged = !q.final && q.comps == 3 && q.tlg >= 3 && q.tlg <= 4; // (pooled or not)
+        const bool merged = !q.final && q.comps == 3 && q.tlg >= 3 && q.tlg <= 4;
 #endif
         const int p0 = 1 << (2 * q.tlg);
         const int rounds = merged ? 1 : 2;
@@ -494,13 +466,11 @@ __device__ __forceinline__ Res evaluate(const Ctx& c, const PicBufs& pb, const R
             PROF_MARK(ts0_);
             bool any_y = false, any_c = false;
             if (merged) {
-                quantize3(c, q.tlg, pooled, q.active, overflow, &r.lvl_y, &r.lvl_c, &any_y, &any_c);
+                quantize3(c, q.tlg, q.active, overflow, &r.lvl_y, &r.lvl_c, &any_y, &any_c);
             } else {
                 bool any = false;
                 long long lvl = 0;
-                if (pooled)
-                    lvl = quantize(c, q.tlg - round, round ? 2 : 1, true, q.active, overflow, &any);
-                else if (q.active)
+                if (q.active)
                     lvl = quantize_solo(c, q.tlg - round, round ? 2 : 1, overflow, &any);
                 if (round) {
                     r.lvl_c = lvl;
@@ -512,7 +482,7 @@ __device__ __forceinline__ Res evaluate(const Ctx& c, const PicBufs& pb, const R
             }
             PROF_MARK(ts1_);
             PROF_ADD2(PH_QZ + ((q.tlg - 2) & 3), ts0_, ts1_);
-            if (!q.active) { // only kept the shared-Viterbi barriers company
+            if (!q.active) { // an inactive evaluation (a candidate the reference skips): nothing was computed
                 PROF_ADD2(PH_SKIP, ts0_, ts1_);
                 continue;
             }
@@ -877,7 +847,7 @@ __device__ __forceinline__ Res leaf4_search(const Ctx& c, const Req& q, int* ove
     // level schedule (team kernel): member 3's 4x4 luma leaves get their pack A from member 0, the server (serve_pack4;
     // the same protocol as for member 2's 8x8 leaves, leaf8_search)
     constexpr int kSrv4Byte = 448; // in the server's decw: 2 x 16 reconstructed samples, then ssd[2] (u32), lvl[2] (i64)
-    const bool served = WRENC_SERVER && c.solo && c.member == 3 && q.n == 3 && lv_word(&SHT.lvb.srv_ready) != 0;
+    const bool served = c.solo && c.member == 3 && q.n == 3 && lv_word(&SHT.lvb.srv_ready) != 0;
     unsigned my_job = 0;
     if (served) {
         if (lane == 0) {
@@ -1239,7 +1209,7 @@ __device__ __forceinline__ Res leaf8_search(const Ctx& c, const Req& q, int* ove
     }
     // member 2 of a team in the level schedule, and the server is polling: post the job (the block's reference samples
     // and originals are ready and stay untouched until the leaf is decided), skip pack A here, merge its results below
-    const bool served = WRENC_SERVER && c.solo && c.member == 2 && (q.n & 7) == 7 && lv_word(&SHT.lvb.srv_ready) != 0;
+    const bool served = c.solo && c.member == 2 && (q.n & 7) == 7 && lv_word(&SHT.lvb.srv_ready) != 0;
     unsigned my_job = 0;
     if (served) {
         if (lane == 0) {
@@ -1673,8 +1643,8 @@ __device__ __forceinline__ Res split8_search(const Ctx& c, const Req& q, int* ov
 // it again with the result.  All state lives in LDS (CtuSt / LeafSt, wave-uniform); the control
 // flow is a plain loop around a switch (reducible, all scalar branches).
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void req_full(Req& q, int comps, int tx, int ty, int tlg, int ml, int mc, bool shared,
-                                         bool active, bool refs0, bool refs1, bool final) {
+__device__ __forceinline__ void req_full(Req& q, int comps, int tx, int ty, int tlg, int ml, int mc, bool active,
+                                         bool refs0, bool refs1, bool final) {
     q.kind = K_FULL;
     q.comps = comps;
     q.tx = tx;
@@ -1682,7 +1652,6 @@ __device__ __forceinline__ void req_full(Req& q, int comps, int tx, int ty, int 
     q.tlg = tlg;
     q.ml = ml;
     q.mc = mc;
-    q.shared = shared;
     q.active = active;
     q.refs0 = refs0;
     q.refs1 = refs1;
@@ -1751,11 +1720,10 @@ __device__ __forceinline__ void leaf_copy_only(LeafSF& s, Req& q, int mode, int 
 
 // full evaluation (get_intra_pred_cost, block_splitter.rs:110-474) of comps with modes [ml, mc, mc];
 // the first request of a leaf for a component also (re)builds its reference samples
-__device__ __forceinline__ void leaf_full(LeafSF& s, Req& q, int comps, int ml, int mc, bool act, int cont,
-                                          bool solo = false) {
+__device__ __forceinline__ void leaf_full(LeafSF& s, Req& q, int comps, int ml, int mc, bool act, int cont) {
     const bool r0 = (comps & 1) && s.need_refs0 != 0;
     const bool r1 = (comps & 2) && mc < LT_CCLM && s.need_refs1 != 0;
-    req_full(q, comps, s.bx, s.by, s.lg, ml, mc, !solo, act, r0, r1, false);
+    req_full(q, comps, s.bx, s.by, s.lg, ml, mc, act, r0, r1, false);
     q.tree = s.tree;
     leaf_attach_org(s, q);
     leaf_attach_save(s, q);
@@ -1792,8 +1760,8 @@ __device__ __forceinline__ void leaf_sadlist(LeafSF& s, Req& q, int comps, int n
 }
 
 // the whole CCLM part of a leaf search as one request (K_CCLMSEARCH): chroma pair only
-__device__ __forceinline__ void leaf_cclmsearch(LeafSF& s, Req& q, int cont, bool solo = false) {
-    leaf_full(s, q, 2, 0, LT_CCLM, true, cont, solo); // (the mode is a placeholder >= LT_CCLM: no reference samples needed)
+__device__ __forceinline__ void leaf_cclmsearch(LeafSF& s, Req& q, int cont) {
+    leaf_full(s, q, 2, 0, LT_CCLM, true, cont); // (the mode is a placeholder >= LT_CCLM: no reference samples needed)
     q.kind = K_CCLMSEARCH;
 }
 
@@ -1804,12 +1772,9 @@ __device__ __forceinline__ void leaf_sadsearch(LeafSF& s, Req& q, int comps, int
 }
 
 // the whole search of a 4x4 DUAL_TREE_LUMA leaf as one request (K_LEAF4, leaf4_search)
-#ifndef WRENC_LEAF4
-#define WRENC_LEAF4 1
-#endif
-__device__ __forceinline__ bool leaf_is_leaf4(const LeafSF& s) { return WRENC_LEAF4 && s.tree == TREE_DUAL_LUMA && s.lg == 2; }
+__device__ __forceinline__ bool leaf_is_leaf4(const LeafSF& s) { return s.tree == TREE_DUAL_LUMA && s.lg == 2; }
 __device__ __forceinline__ void leaf_leaf4(LeafSF& s, Req& q, int cont) {
-    req_full(q, 1, s.bx, s.by, s.lg, 0, 0, false, true, s.need_refs0 != 0, false, false);
+    req_full(q, 1, s.bx, s.by, s.lg, 0, 0, true, s.need_refs0 != 0, false, false);
     q.kind = K_LEAF4;
     q.n = 3;
     q.tree = s.tree;
@@ -1821,12 +1786,9 @@ __device__ __forceinline__ void leaf_leaf4(LeafSF& s, Req& q, int cont) {
 
 // the whole search of an 8x8 SINGLE_TREE leaf as one request (K_LEAF8, leaf8_search); parts: bit 0 pack {planar, DC},
 // bit 1 SAD search + pack {cm, cm - 1, cm + 1}, bit 2 the CCLM part
-#ifndef WRENC_LEAF8
-#define WRENC_LEAF8 1
-#endif
-__device__ __forceinline__ bool leaf_is_leaf8(const LeafSF& s) { return WRENC_LEAF8 && s.tree == TREE_SINGLE && s.lg == 3; }
+__device__ __forceinline__ bool leaf_is_leaf8(const LeafSF& s) { return s.tree == TREE_SINGLE && s.lg == 3; }
 __device__ __forceinline__ void leaf_leaf8(LeafSF& s, Req& q, int parts, int cont) {
-    req_full(q, 3, s.bx, s.by, s.lg, 0, 0, false, true, s.need_refs0 != 0, s.need_refs1 != 0, false);
+    req_full(q, 3, s.bx, s.by, s.lg, 0, 0, true, s.need_refs0 != 0, s.need_refs1 != 0, false);
     q.kind = K_LEAF8;
     q.n = parts;
     q.tree = s.tree;
@@ -1839,10 +1801,7 @@ __device__ __forceinline__ void leaf_leaf8(LeafSF& s, Req& q, int parts, int con
 }
 
 // the full candidates of a 16x16 SINGLE_TREE leaf as one request (K_LEAF16, leaf16_search); wave schedule only
-#ifndef WRENC_LEAF16
-#define WRENC_LEAF16 1
-#endif
-__device__ __forceinline__ bool leaf_is_leaf16(const LeafSF& s) { return WRENC_LEAF16 && s.tree == TREE_SINGLE && s.lg == 4; }
+__device__ __forceinline__ bool leaf_is_leaf16(const LeafSF& s) { return s.tree == TREE_SINGLE && s.lg == 4; }
 __device__ __forceinline__ void leaf_leaf16(LeafSF& s, Req& q, int cont) {
     leaf_leaf8(s, q, 3, cont);
     q.kind = K_LEAF16;
@@ -1959,8 +1918,7 @@ __device__ __forceinline__ bool leaf_step(const Ctx& c, LeafSF& s, const Res& r,
         case C_LIST: {
             // step_search(mode, 1, _, aux=false) (:974) on {cur, cur - 1, cur + 1}, then the minimum of
             // {planar, DC, dir} (:975-978): first minimum of [planar, DC, cur, cur - 1, cur + 1], kept as
-            // one running best.  Out-of-range neighbours are "evaluated" inactive: the wave still
-            // walks the schedule so that the workgroup's shared Viterbi barriers stay aligned
+            // one running best.  Out-of-range neighbours are "evaluated" inactive (the request computes nothing)
             const int cm = r.imin;
             s.cur_mode = (uint8_t)cm;
             s.cur_cost = r.vmin;
@@ -2036,13 +1994,9 @@ __device__ __forceinline__ bool leaf_step(const Ctx& c, LeafSF& s, const Res& r,
         case C_DM:
             return false;
         // ---- DUAL_TREE_CHROMA leaf (:794-885) ----
-        case C_DC_START: // the three CCLM probes, the pick and the evaluation of the picked mode (K_CCLMSEARCH)
-            if (WRENC_LEAF4) { // the whole chroma leaf in one request, CCLM and DM candidates side by side (K_LEAFC4)
-                leaf_full(s, q, 2, 0, s.dm_mode, true, C_LC4, true);
-                q.kind = K_LEAFC4;
-                return true;
-            }
-            leaf_cclmsearch(s, q, C_DC3);
+        case C_DC_START: // the whole chroma leaf in one request, CCLM and DM candidates side by side (K_LEAFC4)
+            leaf_full(s, q, 2, 0, s.dm_mode, true, C_LC4);
+            q.kind = K_LEAFC4;
             return true;
         case C_LC4:
             s.luma_mode = 0;
@@ -2131,10 +2085,7 @@ __device__ __forceinline__ void team_publish(const Req& q, const Res& r, int par
     if (LANE == 0) SH.xr[par] = x;
 }
 
-enum { TC_START = 0, TC_A, TC_D, TC_E, TC_F, TC_DONE, TC_DC_START, TC_DC_A, TC_DC_B, TC_L4, TC_L8A, TC_L8B };
-// round 2's team stages for the nodes below the CTU (8x8 and 4x4 leaves, the chroma leaf): only built when the level
-// schedule does not take those nodes
-#define WRENC_OLD_TEAM_SMALL_LEAVES (!(WRENC_LEVELS && WRENC_LEVELS_ALL_DEPTHS))
+enum { TC_START = 0, TC_A, TC_D, TC_E, TC_F, TC_DONE, TC_DC_START };
 
 // a member with nothing to evaluate in a stage
 __device__ __forceinline__ void team_idle(Req& q) {
@@ -2165,37 +2116,10 @@ __device__ __forceinline__ bool leaf_step_team(const Ctx& c, CtuSt& t, LeafSF& s
     for (;;) {
         switch (cont) {
         case TC_START: // stage A: planar | DC | the directional SAD search (:887-973)
-#if WRENC_OLD_TEAM_SMALL_LEAVES // (the level schedule takes every node below the CTU: these stages of round 2's team are unreachable)
-            if (leaf_is_leaf4(s)) {
-                // a 4x4 luma leaf: the packed search in two halves side by side -- member 0 planar and DC, member 1
-                // the SAD search and {cm, cm - 1, cm + 1} -- one exchange, then everybody pulls the winner
-                if (me < 2) {
-                    leaf_leaf4(s, q, TC_L4);
-                    q.n = 1 + me;
-                } else {
-                    team_idle(q);
-                }
-                s.cont = TC_L4;
-                q.xchg = true;
-                return true;
-            }
-            if (leaf_is_leaf8(s)) {
-                // an 8x8 single-tree leaf: the packed search in two halves side by side -- member 0 pack {planar, DC},
-                // member 1 the SAD search and pack {cm, cm - 1, cm + 1} -- then the CCLM part on the member that holds
-                // the winner (its tile has the winner's reconstruction already), then everybody pulls from it
-                if (me < 2)
-                    leaf_leaf8(s, q, 1 + me, TC_L8A);
-                else
-                    team_idle(q);
-                s.cont = TC_L8A;
-                q.xchg = true;
-                return true;
-            }
-#endif
             if (me == 0) {
-                leaf_full(s, q, both, PLANAR, PLANAR, true, TC_A, true);
+                leaf_full(s, q, both, PLANAR, PLANAR, true, TC_A);
             } else if (me == 1) {
-                leaf_full(s, q, both, DC, DC, true, TC_A, true);
+                leaf_full(s, q, both, DC, DC, true, TC_A);
             } else if (me == 2) {
                 leaf_sadsearch(s, q, both, TC_A); // the 13 directional SADs + both step-search rounds (K_SADSEARCH)
             } else {
@@ -2204,68 +2128,6 @@ __device__ __forceinline__ bool leaf_step_team(const Ctx& c, CtuSt& t, LeafSF& s
             s.cont = TC_A;
             q.xchg = true;
             return true;
-#if WRENC_OLD_TEAM_SMALL_LEAVES // (the level schedule takes every node below the CTU: these stages of round 2's team are unreachable)
-        case TC_L4: {
-            // first minimum of [planar, DC | cm, cm - 1, cm + 1]: the second half wins only if strictly cheaper
-            const float va = xvmin(c, par, 0), vb = xvmin(c, par, 1);
-            const int holder = vb < va ? 1 : 0;
-            const int m = ximin(c, par, holder);
-            s.cost = holder ? vb : va;
-            s.luma_mode = (uint8_t)m;
-            s.chroma_mode = (uint8_t)m;
-            team_defer_pull(t, s, 1, holder);
-            return false;
-        }
-        case TC_L8A: {
-            // first minimum of [planar, DC | cm, cm - 1, cm + 1]: the second half wins only if strictly cheaper; each
-            // half published its best candidate's parts with the mode in the top byte of ssd_y (an 8x8 SSD is < 2^23)
-            EvalParts e0 = xparts(c, par, 0), e1 = xparts(c, par, 1);
-            const int m0 = (int)(e0.ssd_y >> 24), m1 = (int)(e1.ssd_y >> 24);
-            e0.ssd_y &= 0xFFFFFFu;
-            e1.ssd_y &= 0xFFFFFFu;
-            const int cls0 = mpm_class(c, s.bx, s.by, s.lg, m0), cls1 = mpm_class(c, s.bx, s.by, s.lg, m1);
-            const float va = uni_f(assemble_cost(c, tree, cls0, m0, e0)), vb = uni_f(assemble_cost(c, tree, cls1, m1, e1));
-            const int holder = vb < va ? 1 : 0;
-            const int m = holder ? m1 : m0;
-            s.holder = (uint8_t)holder;
-            s.best_cost = holder ? vb : va;
-            put_parts(s.e_best, holder ? e1 : e0);
-            s.mode = (uint8_t)m;
-            s.best_cls = (uint8_t)(holder ? cls1 : cls0);
-            // :1040 the winner's chroma cost; the CCLM part (three probes, the pick, the evaluation, DM against CCLM) runs
-            // on the holder alone
-            s.cur_cost = uni_f(assemble_chroma_cost(c, m, s.e_best.get()));
-            if (me == holder) {
-                if (c.trace && LANE == 0)
-                    TRACE_REC(c.ctu_x + s.bx, c.ctu_y + s.by, s.lg, tree, 3, 0, m, __float_as_int((float)s.cur_cost));
-                leaf_leaf8(s, q, 4, TC_L8B);
-                q.ml = m;
-                q.fcur = s.cur_cost;
-            } else {
-                team_idle(q);
-            }
-            s.cont = TC_L8B;
-            q.xchg = true;
-            return true;
-        }
-        case TC_L8B: {
-            const int holder = s.holder;
-            const EvalParts rp = xparts(c, par, holder); // ssd_y: the CCLM mode picked; ssd_c / lvl_c: its chroma parts
-            const int cm = (int)rp.ssd_y;
-            EvalParts e = s.e_best.get();
-            e.ssd_c = rp.ssd_c;
-            e.lvl_c = rp.lvl_c;
-            const float cclm_cost = uni_f(assemble_chroma_cost(c, cm, e));
-            const float cur = s.cur_cost;
-            const bool dm_wins = cur == fminf(cclm_cost, fminf(cur, 3.40282347e+38f));
-            const int m = s.mode, bcls = s.best_cls;
-            s.luma_mode = (uint8_t)m;
-            s.chroma_mode = (uint8_t)(dm_wins ? m : cm);
-            s.cost = dm_wins ? uni_f(assemble_cost(c, tree, bcls, m, s.e_best.get())) : uni_f(assemble_cost(c, tree, bcls, cm, e));
-            team_defer_pull(t, s, 3, holder);
-            return false;
-        }
-#endif
         case TC_A: {
             const EvalParts e0 = xparts(c, par, 0), e1 = xparts(c, par, 1);
             const float v0 = uni_f(assemble_cost(c, tree, 0, PLANAR, e0));
@@ -2298,7 +2160,7 @@ __device__ __forceinline__ bool leaf_step_team(const Ctx& c, CtuSt& t, LeafSF& s
             const int mode = k == 0 ? cm : (k == 1 ? cm - 1 : cm + 1);
             const bool act = k == 0 || (k == 1 ? !(cm < 3) : !(cm + 1 > 66));
             if (me != holder && act) {
-                leaf_full(s, q, both, mode, mode, true, TC_D, true);
+                leaf_full(s, q, both, mode, mode, true, TC_D);
             } else {
                 team_idle(q);
             }
@@ -2335,7 +2197,7 @@ __device__ __forceinline__ bool leaf_step_team(const Ctx& c, CtuSt& t, LeafSF& s
                 team_defer_pull(t, s, 1, holder);
                 return false;
             }
-            if (WRENC_LEVELS && (WRENC_LEVELS_ALL_DEPTHS || c.k->max_depth == 3) && s.lg == 5 && c.k->max_depth >= 1) {
+            if (s.lg == 5 && c.k->max_depth >= 1) {
                 // The CTU's 32x32 candidate, and the level schedule follows: its LUMA mode is all the other levels need
                 // (their MPM classes), and it is decided now.  Everybody pulls the winner (member 0 keeps
                 // the candidate for the CTU's decision); then members 1 .. 3 are done with this leaf and start their
@@ -2372,7 +2234,7 @@ __device__ __forceinline__ bool leaf_step_team(const Ctx& c, CtuSt& t, LeafSF& s
             const int ev = (s.holder + 1) & (kTeam - 1); // never the holder: its tile keeps the DM chroma
             s.evalr = (uint8_t)ev;
             if (me == ev) {
-                leaf_full(s, q, 2, 0, cm, true, TC_F, true);
+                leaf_full(s, q, 2, 0, cm, true, TC_F);
             } else {
                 team_idle(q);
             }
@@ -2405,51 +2267,8 @@ __device__ __forceinline__ bool leaf_step_team(const Ctx& c, CtuSt& t, LeafSF& s
         case TC_DONE:
             return false;
         // ---- DUAL_TREE_CHROMA leaf (:794-885): the three CCLM probes and the DM evaluation side by side ----
-#if WRENC_OLD_TEAM_SMALL_LEAVES // (the level schedule takes every node below the CTU: these stages of round 2's team are unreachable)
-        case TC_DC_START: // the three CCLM probes and the DM evaluation side by side
-            if (me < 3) {
-                leaf_sadlist(s, q, 2, 1, (uint32_t)(me == 0 ? LT_CCLM : (me == 1 ? T_CCLM : L_CCLM)), 0, 0, 0, false, TC_DC_A);
-            } else {
-                leaf_full(s, q, 2, 0, s.dm_mode, true, TC_DC_A, true);
-            }
-            s.cont = TC_DC_A;
-            q.xchg = true;
-            return true;
-        case TC_DC_A: {
-            const int cm = pick_cclm(xv0(c, par, 0), xv0(c, par, 1), xv0(c, par, 2));
-            s.cclm_mode = (uint8_t)cm;
-            const float dm_cost = uni_f(assemble_chroma_cost(c, s.dm_mode, xparts(c, par, 3)));
-            s.cur_cost = dm_cost;
-            if (me == 0) {
-                leaf_full(s, q, 2, 0, cm, true, TC_DC_B, true);
-            } else {
-                team_idle(q);
-            }
-            s.cont = TC_DC_B;
-            q.xchg = true;
-            return true;
-        }
-#endif
-        default: // (TC_DC_B)
-#if WRENC_OLD_TEAM_SMALL_LEAVES // (the level schedule takes every node below the CTU: these stages of round 2's team are unreachable)
-        {
-            const float c0 = uni_f(assemble_chroma_cost(c, s.cclm_mode, xparts(c, par, 0)));
-            const float dm_cost = s.cur_cost;
-            if (c.write && LANE == 0) {
-                TRACE_REC(c.ctu_x + s.bx, c.ctu_y + s.by, s.lg, tree, 3, 0, s.cclm_mode, __float_as_int(c0));
-                TRACE_REC(c.ctu_x + s.bx, c.ctu_y + s.by, s.lg, tree, 3, 0, s.dm_mode, __float_as_int(dm_cost));
-            }
-            const float cost = fminf(c0, fminf(dm_cost, 3.40282347e+38f));
-            s.luma_mode = 0;
-            s.cost = cost;
-            const bool dm = dm_cost == cost;
-            s.chroma_mode = dm ? s.dm_mode : s.cclm_mode;
-            team_defer_pull(t, s, 2, dm ? 3 : 0); // member 3 evaluated DM, member 0 the CCLM mode
+        default:
             return false;
-        }
-#else
-            return false;
-#endif
         }
     }
 }
@@ -2647,7 +2466,7 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
                 cont = T_RETURN;
                 break;
             }
-            if (TEAM && WRENC_LEVELS && (WRENC_LEVELS_ALL_DEPTHS || D3)) { // (max-split-depth >= 1 here)
+            if (TEAM) { // (max-split-depth >= 1 here)
                 // ---- level schedule from here on (see lv_decide): every member has searched the 32x32 candidate ----
                 if (t.dp0) { // its winner into every member's tile first (team_defer_pull)
                     const int dp = t.dp0, dq = t.dp1;
@@ -2666,7 +2485,7 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
             // the unsplit candidate's reconstruction goes to slot 1 + level (cache_reconsts, :1085-1100).  Wave schedule:
             // the search saved its winner there already (luma and DM chroma, leaf_init above), so all that is left to
             // save is the chroma pair when the CCLM candidate won; a packed 8x8 search (K_LEAF8) saved nothing.
-            t.pend = (uint8_t)((TEAM || (WRENC_LEAF8 && lg == 3)) ? 3 : (mc >= LT_CCLM ? 2 : 0));
+            t.pend = (uint8_t)((TEAM || lg == 3) ? 3 : (mc >= LT_CCLM ? 2 : 0));
             t.pbx = t.bx;
             t.pby = t.by;
             t.plg = (uint8_t)lg;
@@ -2684,23 +2503,17 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
                 cont = T_ENTER;
                 break;
             }
-            // 8x8: four DUAL_TREE_LUMA 4x4 leaves, then the DUAL_TREE_CHROMA leaf
-            if (WRENC_SPLIT8) { // ... as one request (K_SPLIT8)
-                req_full(q, 3, t.bx, t.by, 3, 0, 0, false, true, false, false, false);
-                q.kind = K_SPLIT8;
-                q.stage = 0;
-                q.tree = TREE_DUAL_LUMA;
-                if (t.pend) { // the unsplit 8x8 candidate is saved first
-                    req_copy(q, COPY_SAVE, t.pend, t.pslot, t.pbx, t.pby, t.plg);
-                    t.pend = 0;
-                }
-                t.cont = T_SPLIT8;
-                return true;
+            // 8x8: four DUAL_TREE_LUMA 4x4 leaves, then the DUAL_TREE_CHROMA leaf, as one request (K_SPLIT8)
+            req_full(q, 3, t.bx, t.by, 3, 0, 0, true, false, false, false);
+            q.kind = K_SPLIT8;
+            q.stage = 0;
+            q.tree = TREE_DUAL_LUMA;
+            if (t.pend) { // the unsplit 8x8 candidate is saved first
+                req_copy(q, COPY_SAVE, t.pend, t.pslot, t.pbx, t.pby, t.plg);
+                t.pend = 0;
             }
-            t.split8 = 0.0f;
-            t.i8 = 0;
-            cont = T_LEAF4_EMIT;
-            break;
+            t.cont = T_SPLIT8;
+            return true;
         }
         case T_SPLIT8: {
             if constexpr (D3) { // the split candidate of the 8x8 node came back: against the unsplit one, as T_LEAFC does
@@ -2849,27 +2662,21 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
         }
         // ---- level schedule: this member's next unit (members 1, 2: a leaf search; member 3: an 8x8 split) ----
         case T_LV_UNIT: {
-            if constexpr (TEAM && (WRENC_LEVELS_ALL_DEPTHS || D3)) {
+            if constexpr (TEAM) {
                 const int me = c.member, i = t.lv_i;
                 int bx, by;
                 lv_node(me == 1 ? 1 : 2, i, bx, by);
                 t.bx = (uint8_t)bx;
                 t.by = (uint8_t)by;
                 if constexpr (D3) {
-                    if (me == 3) { // four DUAL_TREE_LUMA 4x4 leaves, then the DUAL_TREE_CHROMA leaf
+                    if (me == 3) { // four DUAL_TREE_LUMA 4x4 leaves, then the DUAL_TREE_CHROMA leaf, as one request (K_SPLIT8)
                         t.lg = 3;
-                        if (WRENC_SPLIT8) { // ... as one request (K_SPLIT8)
-                            req_full(q, 3, bx, by, 3, 0, 0, false, true, false, false, false);
-                            q.kind = K_SPLIT8;
-                            q.stage = 0;
-                            q.tree = TREE_DUAL_LUMA;
-                            t.cont = T_SPLIT8;
-                            return true;
-                        }
-                        t.split8 = 0.0f;
-                        t.i8 = 0;
-                        cont = T_LEAF4_EMIT;
-                        break;
+                        req_full(q, 3, bx, by, 3, 0, 0, true, false, false, false);
+                        q.kind = K_SPLIT8;
+                        q.stage = 0;
+                        q.tree = TREE_DUAL_LUMA;
+                        t.cont = T_SPLIT8;
+                        return true;
                     }
                 }
                 const int lg = me == 1 ? 4 : 3;
@@ -2882,7 +2689,7 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
             }
             break;
         case T_LV_LEAFDONE: {
-            if constexpr (TEAM && (WRENC_LEVELS_ALL_DEPTHS || D3)) {
+            if constexpr (TEAM) {
                 const int me = c.member;
                 if (me < t.max_depth) { // the unsplit candidate of node (member, lv_i), to be decided against its children
                     lv_post_unsplit(me, t.leaf.cost, t.leaf.luma_mode, t.leaf.chroma_mode);
@@ -2895,14 +2702,14 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
             }
             break;
         case T_LV_UP: {
-            if constexpr (TEAM && (WRENC_LEVELS_ALL_DEPTHS || D3)) { // the decisions this member takes part in now, deepest first
+            if constexpr (TEAM) { // the decisions this member takes part in now, deepest first
                 const int me = c.member, i = t.lv_i, dl = t.max_depth;
-                if (WRENC_SERVER && me == 0 && dl >= 2 && !t.lv_i) { // (lv_i of member 0: 1 = the server is through)
+                if (me == 0 && dl >= 2 && !t.lv_i) { // (lv_i of member 0: 1 = the server is through)
                     cont = T_LV_SERVE;
                     break;
                 }
-                if (WRENC_SERVER && me == 2 && me <= dl && i == 15) lv_word_add(&SHT.lvb.job_fin); // no more 8x8 leaves
-                if (WRENC_SERVER && D3 && me == 3 && i == 15) lv_word_add(&SHT.lvb.job4_fin);              // ... 4x4 leaves
+                if (me == 2 && me <= dl && i == 15) lv_word_add(&SHT.lvb.job_fin); // no more 8x8 leaves
+                if (D3 && me == 3 && i == 15) lv_word_add(&SHT.lvb.job4_fin);              // ... 4x4 leaves
                 if (me >= 2 && me <= dl) {
                     // an 8x8 node: decided against its split at max-split-depth 3, final at depth 2
                     const float d2 = dl == 3 ? lv_decide(c, 2, i) : (float)t.leaf.cost;
@@ -2936,7 +2743,7 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
             }
             break;
         case T_LV_SERVE: {
-            if constexpr (TEAM && (WRENC_LEVELS_ALL_DEPTHS || D3)) {
+            if constexpr (TEAM) {
                 // Member 0 between its 32x32 candidate and the CTU's decision: pack {planar, DC} of member 2's 8x8 leaves
                 // (leaf8_search, q.n & 16), one job at a time: wait for a job or for "no more jobs", wait until the
                 // previous job's results have been taken, run it.
@@ -2978,7 +2785,7 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
                 }
                 if (what == 3) {
                     lv_word_wait(&SHT.lvb.job4_ack, served4); // the previous results have been taken
-                    req_full(q, 1, uni((int)SHT.lvb.job4_bx), uni((int)SHT.lvb.job4_by), 2, 0, 0, false, true, false, false, false);
+                    req_full(q, 1, uni((int)SHT.lvb.job4_bx), uni((int)SHT.lvb.job4_by), 2, 0, 0, true, false, false, false);
                     q.kind = K_SERVE4;
                     q.n = 1;
                     q.stage = 0;
@@ -2987,7 +2794,7 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
                     return true;
                 }
                 lv_word_wait(&SHT.lvb.job_ack, served8); // the previous job's reconstructions are still in this wave's park
-                req_full(q, 3, uni((int)SHT.lvb.job_bx), uni((int)SHT.lvb.job_by), 3, 0, 0, false, true, false, false, false);
+                req_full(q, 3, uni((int)SHT.lvb.job_bx), uni((int)SHT.lvb.job_by), 3, 0, 0, true, false, false, false);
                 q.kind = K_LEAF8;
                 q.n = 16;
                 q.stage = 0;
@@ -3015,7 +2822,7 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
             if ((bx & ((1 << lg) - 1)) == 0 && (by & ((1 << lg) - 1)) == 0) {
                 const int ml = uni((int)SH.luma_mode[(by >> 2) * 8 + (bx >> 2)]);
                 const int mc = uni((int)SH.chroma_mode[(by >> 3) * 4 + (bx >> 3)]);
-                req_full(q, lg >= 3 ? 3 : 1, bx, by, lg, ml, mc, false, true, true, true, true);
+                req_full(q, lg >= 3 ? 3 : 1, bx, by, lg, ml, mc, true, true, true, true);
                 t.cont = T_FZ_TAIL;
                 return true;
             }
@@ -3025,7 +2832,7 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
         case T_FZ_TAIL: {
             const int bx = t.bx, by = t.by;
             if (t.lg == 2 && (t.z & 3) == 3) { // after the fourth 4x4 luma CU: the 8x8's chroma CU
-                req_full(q, 2, bx & ~7, by & ~7, 3, 0, uni((int)SH.chroma_mode[(by >> 3) * 4 + (bx >> 3)]), false, true,
+                req_full(q, 2, bx & ~7, by & ~7, 3, 0, uni((int)SH.chroma_mode[(by >> 3) * 4 + (bx >> 3)]), true,
                          true, true, true);
                 t.cont = T_FZ_NEXT;
                 return true;
@@ -3118,7 +2925,6 @@ __device__ __forceinline__ void encode_ctu(Ctx& c, const PicBufs& pb, int ctu_co
     SH.st.xpar = 0;
     SH.st.lvmode = 0;
     SH.st.fz_on = 0;
-    if (LANE == 0) SH.q_pm[0][0][3] = 0; // parity of the pooled quantisation calls (dev_quant.h, zero_flag_cell)
     SH.st.max_depth = (uint8_t)k->max_depth;
     Res r = {};
     Req q = {};

@@ -2,7 +2,7 @@
 //
 // Execution model: ONE 64-lane wavefront owns one 32x32 CTU; a workgroup is WPB = 4 waves working on
 // the SAME CTU position of 4 different pictures, so the waves make the same sequence of full
-// evaluations and pool their one serial stage (the Viterbi walk) in one wave.  A wave keeps its
+// evaluations; each walks its own trellis (the one serial stage).  A wave keeps its
 // working set in LDS (transform buffers, cached reference samples, the reconstruction tile with its
 // neighbour border, trellis decisions, decision maps, search state: 7.2 KB, sized so that five workgroups
 // = 20 waves fit a CU: the kernel is latency-bound per wave and its throughput follows the waves in
@@ -19,6 +19,17 @@
 //   dev_search.h     block_splitter.rs:64-1154, ctu_encoder.rs:1421-1461
 //   dev_bins.h       ctu_encoder.rs:1786-2269       residual_coding as a token stream for the host's arithmetic coder
 #pragma once
+
+// The WRENC_EXP_* switches are measurement builds (tools/README.md); several of them give wrong results on purpose.
+// tools/build_exp.sh builds them with WRENC_EXPERIMENT_BUILD, which nothing else defines.
+#if !defined(WRENC_EXPERIMENT_BUILD) &&                                                                             \
+    (defined(WRENC_EXP_CTRL_ONLY) || defined(WRENC_EXP_LDS_PAD) || defined(WRENC_EXP_NOINLINE_SAD) ||               \
+     defined(WRENC_EXP_NO_MERGED) || defined(WRENC_EXP_NO_ORG) || defined(WRENC_EXP_OLD_PDPC) ||                    \
+     defined(WRENC_EXP_SKIP_DCT) || defined(WRENC_EXP_SKIP_PRED) || defined(WRENC_EXP_SKIP_QUANT) ||                \
+     defined(WRENC_EXP_SKIP_REFS) || defined(WRENC_EXP_SKIP_SAD))
+#error "a WRENC_EXP_* switch is set outside an experiment build: use tools/build_exp.sh"
+#endif
+
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

@@ -73,10 +73,10 @@ __device__ __forceinline__ int acquire_scratch(unsigned long long* slot_map) {
             // the overflow partition has a region for every workgroup that can be resident: a free one turns up
             while (slot < 0) slot = take_region(slot_map, kAffineRegions / 64, kOverflowRegions / 64);
         }
-        SHW[0].q_istar[0] = slot;
+        SHW[0].slot_xfer = slot;
     }
     __syncthreads();
-    const int scratch_slot = uni(SHW[0].q_istar[0]);
+    const int scratch_slot = uni(SHW[0].slot_xfer);
     __syncthreads(); // everybody has read the cell before the search may overwrite it
     return scratch_slot;
 }
