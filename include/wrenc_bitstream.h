@@ -75,6 +75,8 @@ typedef struct wrenc_bs_tokens {
 int wrenc_bs_write_picture_tokens(int width, int height, int qp, int poc, const wrenc_bs_tokens* tok, uint8_t* out,
                                   size_t cap, size_t* len);
 
+/* Pictures whose slice QP differs from the parameter sets' QP: include/wrenc_bitstream_qp.h. */
+
 /* Bits the CABAC engine produced for the CTU data of the last wrenc_bs_write_picture call made by
  * this thread (slice data without headers and framing): the true rate the search's estimate models. */
 long long wrenc_bs_last_slice_data_bits(void);

@@ -126,6 +126,20 @@ int wrenc_gpu_upload(wrenc_gpu_ctx* ctx, int slot, const uint8_t* y, const uint8
  * makes in place of the per-CTU split_ct loop. */
 int wrenc_gpu_encode(wrenc_gpu_ctx* ctx, int first_slot, int n_pictures);
 
+/* Per-picture QP: slot `slot` is searched at qcfg->qp by the wrenc_gpu_encode calls enqueued from now on (a call already
+ * enqueued keeps what it read).  qcfg is a config resolved for that QP the way the context's was (wrenc_gpu_default_config,
+ * then wrenc_gpu_config_extra_params with the same string): the library derives nothing itself.
+ *   Per QP, may differ from the context's config:  qp, lambda_q, lambda_rd, lambda_rd_chroma.
+ *   Must equal the context's, bit for bit:         width, height, max_split_depth, lv_table, dq_table, header_bits_luma,
+ *                                                  header_bits_chroma   (device and n_slots are not read).
+ * A context holds one lambda set per QP: its own at its own QP, and for any other the first one registered.
+ * WRENC_GPU_EINVAL (slot unchanged, context usable) for a bad slot, a QP outside 0..63, a field that must match and does
+ * not, a second lambda set for a QP, or a rate model outside the range wrenc_gpu_create accepts (lambda_q grows with the
+ * QP: a model that fits at the context's QP may not at QP 63).  qcfg NULL puts the slot back to the context's config.
+ * An encode call whose pictures share one QP runs exactly as one of a context created at that QP; a mixed call orders
+ * its pictures by QP (each workgroup holds one) and pads every QP class to a multiple of 4 pictures. */
+int wrenc_gpu_set_slot_qp(wrenc_gpu_ctx* ctx, int slot, const wrenc_gpu_config* qcfg);
+
 /* Wait for everything queued on the context. */
 int wrenc_gpu_sync(wrenc_gpu_ctx* ctx);
 

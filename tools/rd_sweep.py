@@ -22,27 +22,55 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def _search_one_pass(w, h, depth, pics, qps, extra_params):
+    """Every QP of the sweep in ONE encoder and ONE encode call (frames x QPs slots, per-picture QP): per QP the records,
+    the call's search time (shared by all QPs) and the context's final-pass mismatches."""
+    from wrenc_amd import gpu
+    n = len(pics)
+    enc = gpu.Encoder(w, h, qp=qps[0], max_split_depth=depth, n_slots=n * len(qps), extra_params=extra_params)
+    for i, qp in enumerate(qps):
+        for f in range(n):
+            enc.upload(i * n + f, *pics[f])
+            enc.set_qp(i * n + f, qp)
+    enc.sync()
+    t0 = time.perf_counter()
+    enc.encode(0, n * len(qps))
+    enc.sync()
+    t_search = time.perf_counter() - t0
+    recs = {qp: [enc.download(i * n + f) for f in range(n)] for i, qp in enumerate(qps)}
+    mism = enc.final_pass_mismatches()
+    enc.close()
+    return recs, t_search, mism
+
+
 def run_sweep(width=3840, height=2176, frames=8, depth=3, qps=(22, 27, 32, 37), threads=8, extra_params=None,
-              keep_streams=False, verbose=True):
+              keep_streams=False, verbose=True, one_pass=False):
     """The sweep as a function (tests/test_gpu_rd_sweep.py runs it too).  keep_streams: each result also carries
-    "_stream" (parameter sets + pictures), "_recs" and the doc "_frames", for a decoder-side check by the caller."""
+    "_stream" (parameter sets + pictures), "_recs" and the doc "_frames", for a decoder-side check by the caller.
+    one_pass: all QPs in one encode call (per-picture QP); each result's search time is then that of the whole call."""
     from wrenc_amd import bitstream, gpu, metrics, synth
     w, h, n = width, height, frames
     pics = [synth.synth_textured_frame(w, h, f) for f in range(n)]
     results = []
     pool = ThreadPoolExecutor(max_workers=threads)
-    for qp in [int(q) for q in qps]:
-        enc = gpu.Encoder(w, h, qp=qp, max_split_depth=depth, n_slots=n, extra_params=extra_params)
-        for s in range(n):
-            enc.upload(s, *pics[s])
-        enc.sync()
-        t0 = time.perf_counter()
-        enc.encode(0, n)
-        enc.sync()
-        t_search = time.perf_counter() - t0
-        recs = [enc.download(s) for s in range(n)]
-        mism = enc.final_pass_mismatches()
-        enc.close()
+    qps = [int(q) for q in qps]
+    if one_pass:
+        all_recs, t_all, mism_all = _search_one_pass(w, h, depth, pics, qps, extra_params)
+    for qp in qps:
+        if one_pass:
+            recs, t_search, mism = all_recs[qp], t_all, mism_all
+        else:
+            enc = gpu.Encoder(w, h, qp=qp, max_split_depth=depth, n_slots=n, extra_params=extra_params)
+            for s in range(n):
+                enc.upload(s, *pics[s])
+            enc.sync()
+            t0 = time.perf_counter()
+            enc.encode(0, n)
+            enc.sync()
+            t_search = time.perf_counter() - t0
+            recs = [enc.download(s) for s in range(n)]
+            mism = enc.final_pass_mismatches()
+            enc.close()
         t0 = time.perf_counter()
         nals = list(pool.map(lambda t: bitstream.write_picture(w, h, qp, t[0], t[1]), enumerate(recs)))
         t_write = time.perf_counter() - t0
@@ -72,7 +100,7 @@ def run_sweep(width=3840, height=2176, frames=8, depth=3, qps=(22, 27, 32, 37), 
                 summ["SSIM"]["Avg"], summ["SSIM"]["Y"], n / t_search, n / t_write), flush=True)
     pool.shutdown()
     doc = {"config": {"width": w, "height": h, "frames": n, "max_split_depth": depth, "content": "synth_textured_frame",
-                      "extra_params": extra_params},
+                      "extra_params": extra_params, "one_pass": bool(one_pass)},
            "results": results}
     if keep_streams:
         doc["_frames"] = pics
@@ -88,9 +116,11 @@ def main():
     ap.add_argument("--qps", default="22,27,32,37")
     ap.add_argument("--threads", type=int, default=8)
     ap.add_argument("--extra-params", help="the reference's RD-model knobs, K1=V1,K2=V2")
+    ap.add_argument("--one-pass", action="store_true", help="all QPs in one encoder and one encode call")
     ap.add_argument("--out")
     a = ap.parse_args()
-    doc = run_sweep(a.width, a.height, a.frames, a.depth, [int(q) for q in a.qps.split(",")], a.threads, a.extra_params)
+    doc = run_sweep(a.width, a.height, a.frames, a.depth, [int(q) for q in a.qps.split(",")], a.threads, a.extra_params,
+                    one_pass=a.one_pass)
     if a.out:
         json.dump(doc, open(a.out, "w"), indent=1)
     return 0

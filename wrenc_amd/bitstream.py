@@ -13,6 +13,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "host", "libwrenc_host.so")
 EXPORTED_SYMBOLS = ("wrenc_bs_picture_bound", "wrenc_bs_write_parameter_sets", "wrenc_bs_write_picture",
                     "wrenc_bs_write_picture_tokens", "wrenc_bs_last_slice_data_bits")
+# per-picture QP (include/wrenc_bitstream_qp.h)
+EXPORTED_QP_SYMBOLS = ("wrenc_bs_write_picture_qp", "wrenc_bs_write_picture_tokens_qp")
 
 OK, EINVAL, ENOSPC, EDATA = 0, -1, -2, -3
 
@@ -75,54 +77,72 @@ def _plane(rec, key, shape, dtype):
     return a
 
 
-def write_picture(width, height, qp, poc, rec):
-    """Picture header NAL + IDR slice NAL (bytes) of one picture from its search record: a dict with
-    cu_log2_size, luma_mode, chroma_mode, lev_y, lev_cb, lev_cr as gpu.Encoder.download returns them."""
+def _write(name, qps, w, h, poc, arg, struct):
+    """Call writer `name` with (w, h, *qps, poc, record) into a buffer that grows to what it reports it needs."""
     lib = load_library()
-    w, h = int(width), int(height)
-    arrs = [_plane(rec, "cu_log2_size", (h // 4, w // 4), np.uint8), _plane(rec, "luma_mode", (h // 4, w // 4), np.uint8),
-            _plane(rec, "chroma_mode", (h // 8, w // 8), np.uint8), _plane(rec, "lev_y", (h, w), np.int16),
-            _plane(rec, "lev_cb", (h // 2, w // 2), np.int16), _plane(rec, "lev_cr", (h // 2, w // 2), np.int16)]
-    r = _Record(*[a.ctypes.data for a in arrs])
+    fn = getattr(lib, name)
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int] * (3 + len(qps)) + [C.POINTER(struct), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    args = [w, h] + [int(q) for q in qps] + [int(poc), C.byref(arg)]
     # wrenc_bs_picture_bound is the proven worst case (12 bytes per luma sample); real pictures need a small
     # fraction, and the writer reports the size it needs when the buffer is too small
     cap = min(lib.wrenc_bs_picture_bound(w, h), w * h // 2 + 65536)
     buf = np.empty(cap, np.uint8)
     n = C.c_size_t()
-    rc = lib.wrenc_bs_write_picture(w, h, int(qp), int(poc), C.byref(r), buf.ctypes.data, cap, C.byref(n))
+    rc = fn(*args, buf.ctypes.data, cap, C.byref(n))
     if rc == ENOSPC:
         cap = n.value
         buf = np.empty(cap, np.uint8)
-        rc = lib.wrenc_bs_write_picture(w, h, int(qp), int(poc), C.byref(r), buf.ctypes.data, cap, C.byref(n))
+        rc = fn(*args, buf.ctypes.data, cap, C.byref(n))
     if rc != OK:
-        raise BitstreamError(rc, "wrenc_bs_write_picture")
+        raise BitstreamError(rc, name)
     return buf[:n.value].tobytes()
+
+
+def _record(w, h, rec):
+    arrs = [_plane(rec, "cu_log2_size", (h // 4, w // 4), np.uint8), _plane(rec, "luma_mode", (h // 4, w // 4), np.uint8),
+            _plane(rec, "chroma_mode", (h // 8, w // 8), np.uint8), _plane(rec, "lev_y", (h, w), np.int16),
+            _plane(rec, "lev_cb", (h // 2, w // 2), np.int16), _plane(rec, "lev_cr", (h // 2, w // 2), np.int16)]
+    return _Record(*[a.ctypes.data for a in arrs]), arrs
+
+
+def _tokens(w, h, pool, pic):
+    pool = np.ascontiguousarray(pool, np.uint32)
+    arrs = [_plane(pic, "cu_log2_size", (h // 4, w // 4), np.uint8), _plane(pic, "luma_mode", (h // 4, w // 4), np.uint8),
+            _plane(pic, "chroma_mode", (h // 8, w // 8), np.uint8), pool, np.ascontiguousarray(pic["first_page"], np.uint32)]
+    return _Tokens(arrs[0].ctypes.data, arrs[1].ctypes.data, arrs[2].ctypes.data, pool.ctypes.data, pool.size,
+                   arrs[4].ctypes.data), arrs
+
+
+def write_picture(width, height, qp, poc, rec):
+    """Picture header NAL + IDR slice NAL (bytes) of one picture from its search record: a dict with
+    cu_log2_size, luma_mode, chroma_mode, lev_y, lev_cb, lev_cr as gpu.Encoder.download returns them."""
+    w, h = int(width), int(height)
+    r, _keep = _record(w, h, rec)
+    return _write("wrenc_bs_write_picture", (qp,), w, h, poc, r, _Record)
+
+
+def write_picture_qp(width, height, pps_qp, slice_qp, poc, rec):
+    """write_picture for a picture searched at slice_qp in a sequence whose parameter sets carry pps_qp
+    (include/wrenc_bitstream_qp.h)."""
+    w, h = int(width), int(height)
+    r, _keep = _record(w, h, rec)
+    return _write("wrenc_bs_write_picture_qp", (pps_qp, slice_qp), w, h, poc, r, _Record)
 
 
 def write_picture_tokens(width, height, qp, poc, pool, pic):
     """The same NAL units from the device's token record (gpu.Encoder.download_tokens: `pool` and one of its per-picture
     dicts): the host runs the CU-level syntax and the arithmetic coder only."""
-    lib = load_library()
     w, h = int(width), int(height)
-    pool = np.ascontiguousarray(pool, np.uint32)
-    arrs = [_plane(pic, "cu_log2_size", (h // 4, w // 4), np.uint8), _plane(pic, "luma_mode", (h // 4, w // 4), np.uint8),
-            _plane(pic, "chroma_mode", (h // 8, w // 8), np.uint8)]
-    first = np.ascontiguousarray(pic["first_page"], np.uint32)
-    t = _Tokens(arrs[0].ctypes.data, arrs[1].ctypes.data, arrs[2].ctypes.data, pool.ctypes.data, pool.size, first.ctypes.data)
-    lib.wrenc_bs_write_picture_tokens.restype = C.c_int
-    lib.wrenc_bs_write_picture_tokens.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_Tokens), C.c_void_p, C.c_size_t,
-                                                  C.POINTER(C.c_size_t)]
-    cap = min(lib.wrenc_bs_picture_bound(w, h), w * h // 2 + 65536)
-    buf = np.empty(cap, np.uint8)
-    n = C.c_size_t()
-    rc = lib.wrenc_bs_write_picture_tokens(w, h, int(qp), int(poc), C.byref(t), buf.ctypes.data, cap, C.byref(n))
-    if rc == ENOSPC:
-        cap = n.value
-        buf = np.empty(cap, np.uint8)
-        rc = lib.wrenc_bs_write_picture_tokens(w, h, int(qp), int(poc), C.byref(t), buf.ctypes.data, cap, C.byref(n))
-    if rc != OK:
-        raise BitstreamError(rc, "wrenc_bs_write_picture_tokens")
-    return buf[:n.value].tobytes()
+    t, _keep = _tokens(w, h, pool, pic)
+    return _write("wrenc_bs_write_picture_tokens", (qp,), w, h, poc, t, _Tokens)
+
+
+def write_picture_tokens_qp(width, height, pps_qp, slice_qp, poc, pool, pic):
+    """write_picture_tokens for a picture searched at slice_qp in a sequence whose parameter sets carry pps_qp."""
+    w, h = int(width), int(height)
+    t, _keep = _tokens(w, h, pool, pic)
+    return _write("wrenc_bs_write_picture_tokens_qp", (pps_qp, slice_qp), w, h, poc, t, _Tokens)
 
 
 def last_slice_data_bits():

@@ -206,11 +206,11 @@ void write_picture_header(BitWriter& bw, int poc) {
     trailing_bits(bw);
 }
 
-// slice_encoder.rs:32-341, SliceHeader::new (slice_header.rs:63-122): qp_delta = qp - init_qp
-void write_slice_header(BitWriter& bw, int qp) {
+// slice_encoder.rs:32-341, SliceHeader::new (slice_header.rs:63-122): qp_delta = qp - init_qp, init_qp = max(pps_qp, 26)
+void write_slice_header(BitWriter& bw, int slice_qp, int pps_qp) {
     bw.bit(0); // picture_header_in_slice_header_flag
     bw.bit(0); // no_output_of_prior_pics_flag (IDR_W_RADL)
-    bw.se(qp - (qp > 26 ? qp : 26));
+    bw.se(slice_qp - (pps_qp > 26 ? pps_qp : 26));
     bw.bit(1); // dep_quant_used_flag
     bw.bit(1); // byte_alignment: bit equal to one, then zeros (:339-341)
     bw.align();

@@ -596,7 +596,7 @@ int CtuEncoder::encode(Bins& bins, const Ctu& ctu, const SliceHeader& sh) {
 // slice_encoder.rs:343-427 with one tile and one slice per picture: CTUs in raster order
 Bins SliceEncoder::encode(const Slice& slice, const SliceHeader& sh, int* status) {
     Bins bins;
-    write_slice_header(bins, sh.slice_qp); // encode_sh, slice_encoder.rs:32-341 (ends byte aligned)
+    write_slice_header(bins, sh.slice_qp, sh.pps_qp); // encode_sh, slice_encoder.rs:32-341 (ends byte aligned)
     const size_t header_bits = bins.bit_count();
     PictureCoder coder(slice.width, slice.height, sh.slice_qp, *slice.record, slice.tokens, bins);
     int rc = WRENC_BS_OK;

@@ -13,6 +13,7 @@ namespace wrenc_host {
 // wavefront of whole pictures), so a Ctu is a position plus the picture's record and encode() writes syntax only.
 struct SliceHeader {
     int slice_qp; // sh_qp_delta + pps_init_qp (slice_header.rs:95-99)
+    int pps_qp;   // the QP given to the parameter sets: pps_init_qp = max(pps_qp, 26)
 };
 struct Slice {    // one slice = one tile = the picture (slice_splitter.rs:11-20, tile_splitter.rs:10)
     int width, height;
@@ -53,7 +54,7 @@ void write_vps(BitWriter& bw, int width, int height);
 void write_sps(BitWriter& bw, int width, int height);
 void write_pps(BitWriter& bw, int width, int height, int qp);
 void write_picture_header(BitWriter& bw, int poc);
-void write_slice_header(BitWriter& bw, int qp);
+void write_slice_header(BitWriter& bw, int slice_qp, int pps_qp);
 
 enum NalType { NAL_IDR_W_RADL = 7, NAL_VPS = 14, NAL_SPS = 15, NAL_PPS = 16, NAL_PH = 19 };
 

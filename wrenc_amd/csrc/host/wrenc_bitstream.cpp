@@ -1,4 +1,5 @@
-// wrenc_bitstream.cpp -- the C ABI of include/wrenc_bitstream.h.
+// wrenc_bitstream.cpp -- the C ABI of include/wrenc_bitstream.h and include/wrenc_bitstream_qp.h.
+#include "../../../include/wrenc_bitstream_qp.h"
 #include "slice_data.h"
 
 #include <cstring>
@@ -22,7 +23,7 @@ int hand_over(const std::vector<uint8_t>& bytes, uint8_t* out, size_t cap, size_
 }
 
 // picture header NAL + the slice's NAL (main.rs:307-313, :377-383), from either form of the record
-int write_picture(int poc, const Slice& slice, int qp, uint8_t* out, size_t cap, size_t* len) {
+int write_picture(int poc, const Slice& slice, int pps_qp, int slice_qp, uint8_t* out, size_t cap, size_t* len) {
     std::vector<uint8_t> stream;
     {
         BitWriter bw;
@@ -30,7 +31,7 @@ int write_picture(int poc, const Slice& slice, int qp, uint8_t* out, size_t cap,
         append_nal(stream, 9, NAL_PH, 0, bw.bytes());
     }
     // main.rs:380-382: let bins = slice_encoder.encode(&slice, &sh)
-    const SliceHeader sh = {qp};
+    const SliceHeader sh = {slice_qp, pps_qp};
     SliceEncoder slice_encoder;
     int rc = WRENC_BS_OK;
     const Bins bins = slice_encoder.encode(slice, sh, &rc);
@@ -72,21 +73,31 @@ int wrenc_bs_write_parameter_sets(int width, int height, int qp, uint8_t* out, s
     return hand_over(stream, out, cap, len);
 }
 
+int wrenc_bs_write_picture_qp(int width, int height, int pps_qp, int slice_qp, int poc, const wrenc_bs_record* rec,
+                              uint8_t* out, size_t cap, size_t* len) {
+    if (!size_ok(width, height, pps_qp) || slice_qp < 0 || slice_qp > 63 || poc < 0 || !rec || !rec->cu_log2_size ||
+        !rec->luma_mode || !rec->chroma_mode || !rec->lev_y || !rec->lev_cb || !rec->lev_cr)
+        return WRENC_BS_EINVAL;
+    return write_picture(poc, Slice{width, height, rec, nullptr}, pps_qp, slice_qp, out, cap, len);
+}
+
 int wrenc_bs_write_picture(int width, int height, int qp, int poc, const wrenc_bs_record* rec, uint8_t* out,
                            size_t cap, size_t* len) {
-    if (!size_ok(width, height, qp) || poc < 0 || !rec || !rec->cu_log2_size || !rec->luma_mode ||
-        !rec->chroma_mode || !rec->lev_y || !rec->lev_cb || !rec->lev_cr)
+    return wrenc_bs_write_picture_qp(width, height, qp, qp, poc, rec, out, cap, len);
+}
+
+int wrenc_bs_write_picture_tokens_qp(int width, int height, int pps_qp, int slice_qp, int poc, const wrenc_bs_tokens* tok,
+                                     uint8_t* out, size_t cap, size_t* len) {
+    if (!size_ok(width, height, pps_qp) || slice_qp < 0 || slice_qp > 63 || poc < 0 || !tok || !tok->cu_log2_size ||
+        !tok->luma_mode || !tok->chroma_mode || !tok->pool || !tok->first_page)
         return WRENC_BS_EINVAL;
-    return write_picture(poc, Slice{width, height, rec, nullptr}, qp, out, cap, len);
+    const wrenc_bs_record maps = {tok->cu_log2_size, tok->luma_mode, tok->chroma_mode, nullptr, nullptr, nullptr};
+    return write_picture(poc, Slice{width, height, &maps, tok}, pps_qp, slice_qp, out, cap, len);
 }
 
 int wrenc_bs_write_picture_tokens(int width, int height, int qp, int poc, const wrenc_bs_tokens* tok, uint8_t* out, size_t cap,
                                   size_t* len) {
-    if (!size_ok(width, height, qp) || poc < 0 || !tok || !tok->cu_log2_size || !tok->luma_mode || !tok->chroma_mode ||
-        !tok->pool || !tok->first_page)
-        return WRENC_BS_EINVAL;
-    const wrenc_bs_record maps = {tok->cu_log2_size, tok->luma_mode, tok->chroma_mode, nullptr, nullptr, nullptr};
-    return write_picture(poc, Slice{width, height, &maps, tok}, qp, out, cap, len);
+    return wrenc_bs_write_picture_tokens_qp(width, height, qp, qp, poc, tok, out, cap, len);
 }
 
 long long wrenc_bs_last_slice_data_bits(void) { return g_last_slice_data_bits; }

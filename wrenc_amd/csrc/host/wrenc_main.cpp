@@ -35,6 +35,7 @@
 #include <unistd.h>
 
 #include "../../../include/wrenc_bitstream.h"
+#include "../../../include/wrenc_bitstream_qp.h"
 #include "../../../include/wrenc_gpu.h"
 
 namespace {
@@ -134,11 +135,38 @@ struct Options {
     bool tokens = true; // --tokens auto | on: batches come back as residual tokens; --tokens off, --no-tokens: as the compact record
     int ramp_mode = 0;  // --ramp-down auto (0) | always (1) | never (2)
     std::vector<int> devices;
+    std::vector<int> pic_qp; // --qp-file: the QP of every picture (empty: --qp for all)
+    int min_qp = 26;         // the smallest QP of the run
 };
+
+// --qp-file: whitespace-separated integers 0..63, entry i the QP of picture i, at least one per picture
+std::vector<int> read_qp_file(const char* path, long num_pictures) {
+    FILE* f = fopen(path, "r");
+    if (!f) die("failed to open qp file: %s: %s", path, strerror(errno));
+    std::vector<int> qps;
+    char tok[64];
+    while (fscanf(f, "%63s", tok) == 1) {
+        char* end = nullptr;
+        errno = 0;
+        const long v = strtol(tok, &end, 10);
+        if (end == tok || *end || errno) {
+            fclose(f);
+            die("Invalid qp-file entry %zu: %s", qps.size(), tok);
+        }
+        if (v < 0 || v > 63) {
+            fclose(f);
+            die("qp-file entry %zu is %ld: qp must be 0..63", qps.size(), v);
+        }
+        qps.push_back((int)v);
+    }
+    fclose(f);
+    if ((long)qps.size() < num_pictures) die("qp-file has %zu entries, fewer than --num-pictures %ld", qps.size(), num_pictures);
+    return qps;
+}
 
 Options parse_options(int argc, char** argv) {
     Options o;
-    const char *in_size = nullptr, *out_size = nullptr, *device_list = nullptr;
+    const char *in_size = nullptr, *out_size = nullptr, *device_list = nullptr, *qp_file = nullptr;
     int device = 0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -153,6 +181,7 @@ Options parse_options(int argc, char** argv) {
         else if (a == "--output-size") out_size = val();
         else if (a == "--num-pictures") o.num_pictures = atol(val());
         else if (a == "--qp") o.qp = atoi(val());
+        else if (a == "--qp-file") qp_file = val();
         else if (a == "--max-split-depth") o.depth = atoi(val());
         else if (a == "--extra-params") o.extra = val();
         else if (a == "--batch") o.batch = atoi(val());
@@ -191,6 +220,13 @@ Options parse_options(int argc, char** argv) {
     }
     if (o.w % 32 || o.h % 32) die("output-size must be a multiple of the 32x32 CTU (picture.rs:178-181): %dx%d", o.w, o.h);
     if (o.qp < 0 || o.qp > 63 || o.depth < 0 || o.depth > 3) die("qp must be 0..63, max-split-depth 0..3");
+    o.min_qp = o.qp;
+    if (qp_file) {
+        o.pic_qp = read_qp_file(qp_file, o.num_pictures);
+        o.pic_qp.resize((size_t)o.num_pictures);
+        if (!o.pic_qp.empty()) o.min_qp = 63;
+        for (int q : o.pic_qp) o.min_qp = q < o.min_qp ? q : o.min_qp;
+    }
     if (o.batch < 1) o.batch = 1;
     if (o.num_pictures > 0 && o.batch > o.num_pictures) o.batch = (int)o.num_pictures;
     if (o.n_threads < 1) o.n_threads = 1;
@@ -282,7 +318,7 @@ std::vector<HostSet> make_units(const Options& o, const Geometry& g, const std::
         if (with_rec) s.rec = (uint8_t*)wrenc_gpu_alloc_host(s.ctx, g.pic * batch);
         if (!s.in || !s.maps || (with_rec && !s.rec)) fatal("%s", wrenc_gpu_last_error(s.ctx));
         if (o.tokens) {
-            s.tok_cap = token_pool_words(g, o.qp, o.batch);
+            s.tok_cap = token_pool_words(g, o.min_qp, o.batch);
             s.tok_pool = (uint32_t*)wrenc_gpu_alloc_host(s.ctx, s.tok_cap * sizeof(uint32_t));
             s.tok_first = (uint32_t*)wrenc_gpu_alloc_host(s.ctx, g.n_ctus * sizeof(uint32_t) * batch);
             s.tks.resize(batch);
@@ -326,7 +362,14 @@ struct Run {
           seekable(fin != stdin && lseek(fileno(fin), 0, SEEK_CUR) != (off_t)-1),
           n_readers(seekable ? (o.n_threads < 8 ? o.n_threads : 8) : 1), pool(o.n_threads) {}
 
+    // --qp-file: the config of every QP of the file other than --qp (indexed by QP), built once by main()
+    std::vector<const wrenc_gpu_config*> qcfg = std::vector<const wrenc_gpu_config*>(64, nullptr);
+
+    int slice_qp(long picture) const { return o.pic_qp.empty() ? o.qp : o.pic_qp[(size_t)picture]; }
+
     void upload(HostSet& s, int k) {
+        // the slot's QP first: the encode call of the batch reads it (NULL: the context's, --qp)
+        if (!o.pic_qp.empty()) gpu_check(s, wrenc_gpu_set_slot_qp(s.ctx, s.base + k, qcfg[(size_t)slice_qp(poc + k)]));
         uint8_t* p = s.in + g.pic * k;
         gpu_check(s, wrenc_gpu_upload(s.ctx, s.base + k, p, p + g.ysz, p + g.ysz + g.csz, (size_t)g.w, (size_t)g.w / 2));
         ++s.count;
@@ -433,8 +476,9 @@ struct Run {
         }
         std::vector<uint8_t>& out = s.nal[(size_t)k];
         const auto write = [&](size_t* n) {
-            return s.bs_tokens ? wrenc_bs_write_picture_tokens(g.w, g.h, o.qp, poc_k, &tk, out.data(), out.size(), n)
-                               : wrenc_bs_write_picture(g.w, g.h, o.qp, poc_k, &rec, out.data(), out.size(), n);
+            const int q = slice_qp(poc_k);
+            return s.bs_tokens ? wrenc_bs_write_picture_tokens_qp(g.w, g.h, o.qp, q, poc_k, &tk, out.data(), out.size(), n)
+                               : wrenc_bs_write_picture_qp(g.w, g.h, o.qp, q, poc_k, &rec, out.data(), out.size(), n);
         };
         // wrenc_bs_picture_bound is the proven worst case (12 bytes per luma sample); real pictures need a small fraction,
         // and the writer reports the size it needs when the buffer is too small
@@ -515,6 +559,14 @@ int main(int argc, char** argv) {
 
     const auto t_start = std::chrono::steady_clock::now();
     Run run(o, g, fin, fout, frec, per_dev);
+    std::vector<wrenc_gpu_config> qcfgs(o.pic_qp.empty() ? 0 : 64); // --qp-file: resolved as the contexts' config was
+    for (int q : o.pic_qp) {
+        if (q == o.qp || run.qcfg[(size_t)q]) continue;
+        wrenc_gpu_config& c = qcfgs[(size_t)q];
+        if (wrenc_gpu_default_config(&c, o.w, o.h, q, o.depth)) fatal("%s", wrenc_gpu_last_error(nullptr));
+        if (o.extra && wrenc_gpu_config_extra_params(&c, o.extra)) fatal("%s", wrenc_gpu_last_error(nullptr));
+        run.qcfg[(size_t)q] = &c;
+    }
     // Fill every unit, then go round: read the oldest batch back (waits for its search only), collect the
     // slices of the batch before it (written meanwhile), start this batch's slices, and give the unit the next
     // batch.  With --reconst the planes of a batch are written out before its unit is read back into again.

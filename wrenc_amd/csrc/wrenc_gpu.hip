@@ -177,20 +177,35 @@ __global__ __launch_bounds__(1024) void compact_levels_kernel(const PicBufs* __r
     if (threadIdx.x == 0) counts[blockIdx.x] = s_base;
 }
 
+// A mixed-QP encode call (wrenc_gpu_set_slot_qp) runs its pictures from a per-call list, ordered by QP and padded so that
+// every group of WPB consecutive entries holds ONE QP: load_tables fills the workgroup's LDS tables (lambda_q x dq_table)
+// with each thread reading its own wave's constant block, so a workgroup must never mix blocks.  Per group: the QP's
+// constant block and how many of its WPB entries are pictures (the rest are padding: same work, no stores).
+struct CallGroup {
+    const DevConst* k;
+    int n_real;
+};
+
 // Wave schedule: one workgroup = the same CTU of WPB consecutive pictures, one wave each.
 // D3: built for max-split-depth 3 (with the 4x4 leaves of split 8x8 CUs) or for the smaller depths (without)
+// groups: NULL for a call at one QP (block k); else the call's groups from this launch's first one (k unused).
 template <bool D3>
 __global__ __launch_bounds__(64 * WPB, 5) void ctu_search_kernel(const DevConst* __restrict__ k,
                                                               const PicBufs* __restrict__ slots, int first_slot,
                                                               int n_pictures, int diag, int r_min, int count,
                                                               uint8_t* pred_scratch, unsigned long long* slot_map,
-                                                              unsigned long long* mismatch, int* overflow) {
+                                                              unsigned long long* mismatch, int* overflow,
+                                                              const CallGroup* __restrict__ groups) {
     const int scratch_slot = acquire_scratch(slot_map);
     const int group = blockIdx.x / count;
     const int j = blockIdx.x - group * count;
     const int row = r_min + j;
     const int col = diag - 2 * row;
     int pic = group * WPB + WAVE;
+    if (groups) {
+        k = groups[group].k;
+        n_pictures = group * WPB + groups[group].n_real;
+    }
     Ctx c = {};
     c.k = (const CONST_AS DevConst*)k;
     c.mismatch = mismatch;
@@ -201,9 +216,9 @@ __global__ __launch_bounds__(64 * WPB, 5) void ctu_search_kernel(const DevConst*
     c.member = 0;
     if (pic >= n_pictures) pic = n_pictures - 1; // padding wave: same work, no stores
     const PicBufs pb = slots[first_slot + pic];
-    c.org = (const GLOBAL_AS uint8_t*)pb.org_t + (size_t)(row * k->ctu_cols + col) * kOrgTile;
-    c.W = k->W;
-    c.WH = k->W * k->H;
+    c.org = (const GLOBAL_AS uint8_t*)pb.org_t + (size_t)(row * c.k->ctu_cols + col) * kOrgTile;
+    c.W = c.k->W;
+    c.WH = c.k->W * c.k->H;
     c.pred_scratch = nullptr;
     c.slots = (GLOBAL_AS uint8_t*)(pred_scratch + ((size_t)scratch_slot * WPB + WAVE) * kWaveScratch);
     int ovf = 0;
@@ -214,6 +229,8 @@ __global__ __launch_bounds__(64 * WPB, 5) void ctu_search_kernel(const DevConst*
 
 // Team schedule: one workgroup = the same CTU of WPB / kTeam consecutive pictures, kTeam waves each
 // (dev_search.h, leaf_step_team).  For encode calls with too few pictures to fill the GPU one wave per CTU.
+// (A mixed-QP call launches it once per QP class of a lane: reading a group's block here, as the wave kernel does,
+// costs this kernel 12 VGPRs.)
 template <bool D3>
 __global__ __launch_bounds__(64 * WPB, 5) void ctu_search_team_kernel(const DevConst* __restrict__ k,
                                                                    const PicBufs* __restrict__ slots, int first_slot,
@@ -621,6 +638,20 @@ struct wrenc_gpu_ctx {
     hipEvent_t ev_fork = nullptr;
     hipEvent_t last_done = nullptr;            // completion event of the most recent encode call
     DevConst* d_const = nullptr;
+    // per-picture QP (wrenc_gpu_set_slot_qp): one constant block per QP in use, built on first use and kept until destroy
+    // (a call in flight may read it); the QP of every slot (-1: the context's); per encode call in flight (ring of
+    // enc_events), the call's picture list and its groups, host copy kept until the call is done
+    DevConst* d_qconst[64] = {};
+    wrenc_gpu_config* qcfg[64] = {};           // the per-QP config a block was built from (its lambdas are the QP's)
+    std::vector<int> slot_qp;
+    struct CallList {
+        PicBufs* d_pics = nullptr;
+        CallGroup* d_groups = nullptr;
+        int cap = 0;                            // entries of d_pics (d_groups: cap / WPB)
+        std::vector<PicBufs> pics;
+        std::vector<CallGroup> groups;
+    };
+    std::vector<CallList> call_lists;
     PicBufs* d_slots = nullptr;
     std::vector<PicBufs> slots;
     std::vector<int> state; // 0 empty, 1 uploaded, 2 encoded
@@ -1100,6 +1131,14 @@ void wrenc_gpu_destroy(wrenc_gpu_ctx* ctx) {
         if (b.ctu_cost) (void)hipFree(b.ctu_cost);
     }
     if (ctx->d_const) (void)hipFree(ctx->d_const);
+    for (int q = 0; q < 64; ++q) {
+        if (ctx->d_qconst[q]) (void)hipFree(ctx->d_qconst[q]);
+        delete ctx->qcfg[q];
+    }
+    for (auto& cl : ctx->call_lists) {
+        if (cl.d_pics) (void)hipFree(cl.d_pics);
+        if (cl.d_groups) (void)hipFree(cl.d_groups);
+    }
     if (ctx->d_slots) (void)hipFree(ctx->d_slots);
     if (ctx->d_mismatch) (void)hipFree(ctx->d_mismatch);
     if (ctx->d_overflow) (void)hipFree(ctx->d_overflow);
@@ -1124,6 +1163,21 @@ void wrenc_gpu_destroy(wrenc_gpu_ctx* ctx) {
     delete ctx;
 }
 
+// The trellis keeps path costs in 32 bits (dev_quant.h, above kNoBranch): exact as long as one step costs less than 2^25,
+// i.e. 128 * 65535 + lambda_q * dq_table[bits] < 2^25 for every table entry -- true for the reference's defaults at every
+// QP (22.6 M at QP 63) and for rate models anywhere near them, not for e.g. quant_lv_pow = 2.5 or quant_qp_div_trellis =
+// 1.5 (--extra-params), where the reference's own i64 products reach 10^11 .. 10^19.  Refused rather than searched
+// with other results than the reference's.  (lambda_q grows with the QP: a model may fit at one QP and not at another.)
+static bool rate_model_fits(const wrenc_gpu_config& cfg) {
+    constexpr long long kStepRoom = (1LL << 25) - 128LL * 65535LL;
+    bool fits = cfg.lambda_q >= 0 && cfg.lambda_q < kStepRoom;
+    for (int i = 0; fits && i < 1024; ++i)
+        fits = cfg.dq_table[i] >= 0 && cfg.dq_table[i] < kStepRoom && cfg.lambda_q * cfg.dq_table[i] < kStepRoom;
+    return fits;
+}
+static const char* const kRateModelMsg =
+    "the quantiser's rate model (lambda_q x dq_table) is outside the range the device's 32-bit trellis costs cover";
+
 int wrenc_gpu_create(const wrenc_gpu_config* cfg, wrenc_gpu_ctx** out) {
     if (!cfg || !out) return fail(nullptr, WRENC_GPU_EINVAL, "null argument");
     *out = nullptr;
@@ -1133,20 +1187,7 @@ int wrenc_gpu_create(const wrenc_gpu_config* cfg, wrenc_gpu_ctx** out) {
     if (cfg->max_split_depth < 0 || cfg->max_split_depth > 3)
         return fail(nullptr, WRENC_GPU_EINVAL, "max_split_depth out of range 0..3");
     if (cfg->n_slots < 1) return fail(nullptr, WRENC_GPU_EINVAL, "n_slots must be >= 1");
-    // The trellis keeps path costs in 32 bits (dev_quant.h, above kNoBranch): exact as long as one step costs less than 2^25,
-    // i.e. 128 * 65535 + lambda_q * dq_table[bits] < 2^25 for every table entry -- true for the reference's defaults at every
-    // QP (22.6 M at QP 63) and for rate models anywhere near them, not for e.g. quant_lv_pow = 2.5 or quant_qp_div_trellis =
-    // 1.5 (--extra-params), where the reference's own i64 products reach 10^11 .. 10^19.  Refused rather than searched
-    // with other results than the reference's.
-    {
-        constexpr long long kStepRoom = (1LL << 25) - 128LL * 65535LL;
-        bool fits = cfg->lambda_q >= 0 && cfg->lambda_q < kStepRoom;
-        for (int i = 0; fits && i < 1024; ++i)
-            fits = cfg->dq_table[i] >= 0 && cfg->dq_table[i] < kStepRoom && cfg->lambda_q * cfg->dq_table[i] < kStepRoom;
-        if (!fits)
-            return fail(nullptr, WRENC_GPU_EINVAL,
-                        "the quantiser's rate model (lambda_q x dq_table) is outside the range the device's 32-bit trellis costs cover");
-    }
+    if (!rate_model_fits(*cfg)) return fail(nullptr, WRENC_GPU_EINVAL, kRateModelMsg);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(nullptr, WRENC_GPU_ENODEV, "no HIP device available");
@@ -1213,6 +1254,8 @@ int wrenc_gpu_create(const wrenc_gpu_config* cfg, wrenc_gpu_ctx** out) {
     CREATE_TRY(hipMemset(ctx->d_overflow, 0, 2 * sizeof(int)));
     ctx->slots.assign(cfg->n_slots, PicBufs{});
     ctx->state.assign(cfg->n_slots, 0);
+    ctx->slot_qp.assign(cfg->n_slots, -1);
+    ctx->call_lists.resize(ctx->enc_events.size());
     for (int s = 0; s < cfg->n_slots; ++s) {
         PicBufs& b = ctx->slots[s];
         // Y | Cb | Cr of a picture are one slab each for originals, reconstruction and levels: the
@@ -1272,6 +1315,59 @@ int wrenc_gpu_upload(wrenc_gpu_ctx* ctx, int slot, const uint8_t* y, const uint8
     return WRENC_GPU_OK;
 }
 
+int wrenc_gpu_set_slot_qp(wrenc_gpu_ctx* ctx, int slot, const wrenc_gpu_config* qcfg) {
+    if (!ctx) return WRENC_GPU_EINVAL;
+    if (slot < 0 || slot >= ctx->cfg.n_slots) return fail(ctx, WRENC_GPU_EINVAL, "bad slot");
+    if (!qcfg) {
+        ctx->slot_qp[slot] = -1;
+        return WRENC_GPU_OK;
+    }
+    const wrenc_gpu_config& c = ctx->cfg;
+    if (qcfg->qp < 0 || qcfg->qp > 63) return fail(ctx, WRENC_GPU_EINVAL, "qp out of range 0..63");
+    if (qcfg->width != c.width || qcfg->height != c.height || qcfg->max_split_depth != c.max_split_depth ||
+        memcmp(qcfg->lv_table, c.lv_table, sizeof(c.lv_table)) || memcmp(qcfg->dq_table, c.dq_table, sizeof(c.dq_table)) ||
+        memcmp(qcfg->header_bits_luma, c.header_bits_luma, sizeof(c.header_bits_luma)) ||
+        memcmp(qcfg->header_bits_chroma, c.header_bits_chroma, sizeof(c.header_bits_chroma)))
+        return fail(ctx, WRENC_GPU_EINVAL,
+                    "a slot's config may differ from the context's in qp, lambda_q, lambda_rd and lambda_rd_chroma only");
+    const auto same_lambdas = [](const wrenc_gpu_config& a, const wrenc_gpu_config& b) {
+        return a.lambda_q == b.lambda_q && !memcmp(&a.lambda_rd, &b.lambda_rd, sizeof(float)) &&
+               !memcmp(&a.lambda_rd_chroma, &b.lambda_rd_chroma, sizeof(float));
+    };
+    const int q = qcfg->qp;
+    const wrenc_gpu_config* known = q == c.qp ? &c : ctx->qcfg[q];
+    if (known) {
+        if (!same_lambdas(*qcfg, *known)) return fail(ctx, WRENC_GPU_EINVAL, "the context has another lambda set for this QP");
+        ctx->slot_qp[slot] = q == c.qp ? -1 : q;
+        return WRENC_GPU_OK;
+    }
+    if (!rate_model_fits(*qcfg)) return fail(ctx, WRENC_GPU_EINVAL, kRateModelMsg);
+    // the QP's constant block, built once: it is never changed or freed while the context lives, so a call in flight
+    // that reads it is not disturbed
+    HIP_TRY(ctx, hipSetDevice(c.device));
+    DevConst* hk = new (std::nothrow) DevConst();
+    wrenc_gpu_config* kept = new (std::nothrow) wrenc_gpu_config(*qcfg);
+    DevConst* d = nullptr;
+    hipError_t e = hipErrorOutOfMemory;
+    if (hk && kept) {
+        fill_dev_const(*qcfg, *hk);
+        e = hipMalloc((void**)&d, sizeof(DevConst));
+        if (e == hipSuccess) e = hipMemcpy(d, hk, sizeof(DevConst), hipMemcpyHostToDevice);
+    }
+    delete hk;
+    if (e != hipSuccess) {
+        delete kept;
+        if (d) (void)hipFree(d);
+        (void)hipGetLastError();
+        return fail(ctx, e == hipErrorOutOfMemory ? WRENC_GPU_ENOMEM : WRENC_GPU_EHIP,
+                    std::string("constant block of a QP: ") + hipGetErrorString(e));
+    }
+    ctx->d_qconst[q] = d;
+    ctx->qcfg[q] = kept;
+    ctx->slot_qp[slot] = q;
+    return WRENC_GPU_OK;
+}
+
 int wrenc_gpu_encode(wrenc_gpu_ctx* ctx, int first_slot, int n_pictures) {
     if (!ctx) return WRENC_GPU_EINVAL;
     if (first_slot < 0 || n_pictures < 1 || first_slot + n_pictures > ctx->cfg.n_slots)
@@ -1279,6 +1375,55 @@ int wrenc_gpu_encode(wrenc_gpu_ctx* ctx, int first_slot, int n_pictures) {
     for (int s = first_slot; s < first_slot + n_pictures; ++s)
         if (ctx->state[s] == 0) return fail(ctx, WRENC_GPU_ESTATE, "slot has no uploaded picture");
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+    // The pictures' QPs are read now: a later wrenc_gpu_set_slot_qp does not change this call.  A call at one QP runs its
+    // slots in place with that QP's constant block; a mixed one from a list of its own (CallGroup, above the kernels).
+    const DevConst* d_k = ctx->d_const;
+    const PicBufs* d_pics = ctx->d_slots;
+    const CallGroup* d_groups = nullptr;
+    wrenc_gpu_ctx::CallList* cl = nullptr;
+    int list_first = first_slot, n_entries = n_pictures;
+    {
+        const int q0 = ctx->slot_qp[first_slot];
+        bool mixed = false;
+        for (int s = first_slot; s < first_slot + n_pictures; ++s) mixed |= ctx->slot_qp[s] != q0;
+        if (!mixed && q0 >= 0) d_k = ctx->d_qconst[q0];
+        if (mixed) {
+            // this call's list: the ring entry of the completion event it will record, last used by the call that recorded
+            // that event before -- which must be done before the list is rewritten
+            const size_t ring = ctx->enc_event_next % ctx->enc_events.size();
+            HIP_TRY(ctx, hipEventSynchronize(ctx->enc_events[ring]));
+            cl = &ctx->call_lists[ring];
+            cl->pics.clear();
+            cl->groups.clear();
+            // QP classes in ascending order, each padded to whole groups of WPB (padding repeats the class's last picture)
+            for (int q = 0; q < 64; ++q) {
+                int n_q = 0;
+                for (int s = first_slot; s < first_slot + n_pictures; ++s)
+                    if ((ctx->slot_qp[s] < 0 ? ctx->cfg.qp : ctx->slot_qp[s]) == q) {
+                        cl->pics.push_back(ctx->slots[s]);
+                        ++n_q;
+                    }
+                if (!n_q) continue;
+                while (cl->pics.size() % WPB) cl->pics.push_back(cl->pics.back());
+                const DevConst* kq = q == ctx->cfg.qp ? ctx->d_const : ctx->d_qconst[q];
+                for (int g = 0; g * WPB < n_q; ++g) cl->groups.push_back(CallGroup{kq, n_q - g * WPB < WPB ? n_q - g * WPB : WPB});
+            }
+            n_entries = (int)cl->pics.size();
+            if (cl->cap < n_entries) {
+                cl->cap = 0;
+                if (realloc_scratch(cl->d_pics, sizeof(PicBufs) * n_entries) != hipSuccess ||
+                    realloc_scratch(cl->d_groups, sizeof(CallGroup) * (n_entries / WPB)) != hipSuccess)
+                    return fail(ctx, WRENC_GPU_ENOMEM, "no device memory for the picture list of a mixed-QP call");
+                cl->cap = n_entries;
+            }
+            HIP_TRY(ctx, hipMemcpyAsync(cl->d_pics, cl->pics.data(), sizeof(PicBufs) * n_entries, hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(cl->d_groups, cl->groups.data(), sizeof(CallGroup) * cl->groups.size(), hipMemcpyHostToDevice,
+                                        ctx->stream));
+            d_pics = cl->d_pics;
+            d_groups = cl->d_groups;
+            list_first = 0;
+        }
+    }
     const int cols = ctx->ctu_cols, rows = ctx->ctu_rows;
     const int ndiag = cols + 2 * (rows - 1);
     // Which schedule, decided PER ANTI-DIAGONAL: one wave per CTU fills the GPU only with thousands of CTUs
@@ -1288,7 +1433,7 @@ int wrenc_gpu_encode(wrenc_gpu_ctx* ctx, int first_slot, int n_pictures) {
     // picture stays on one stream; a team launch covers its lane's pictures in groups of WPB / kTeam.
     const int per_group = WPB;
     constexpr int kTeamsPerGroup = WPB >= kTeam ? WPB / kTeam : 1;
-    const int total_groups = (n_pictures + per_group - 1) / per_group;
+    const int total_groups = (n_entries + per_group - 1) / per_group;
     int n_team_diags = 0, n_wave_diags = 0;
     const int n_lanes = total_groups < kEncodeLanes ? total_groups : kEncodeLanes;
     if (!ctx->d_pred_scratch) {
@@ -1337,32 +1482,57 @@ int wrenc_gpu_encode(wrenc_gpu_ctx* ctx, int first_slot, int n_pictures) {
         ++(team ? n_team_diags : n_wave_diags);
         for (int l = 0; l < n_lanes; ++l) {
             const int g0 = (int)((long long)total_groups * l / n_lanes), g1 = (int)((long long)total_groups * (l + 1) / n_lanes);
-            const int lane_first = first_slot + g0 * per_group;
+            const int lane_first = list_first + g0 * per_group;
             int lane_pics = (g1 - g0) * per_group;
-            if (g0 * per_group + lane_pics > n_pictures) lane_pics = n_pictures - g0 * per_group;
+            if (g0 * per_group + lane_pics > n_entries) lane_pics = n_entries - g0 * per_group;
             if (lane_pics <= 0) continue;
+            const CallGroup* lane_groups = d_groups ? d_groups + g0 : nullptr;
             hipStream_t st = l == 0 ? ctx->stream : ctx->lanes[l - 1];
             if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_pool[2 * launches], st));
-            const dim3 grid(team ? count * ((lane_pics + kTeamsPerGroup - 1) / kTeamsPerGroup) : count * (g1 - g0));
-#define WRENC_LAUNCH(KERNEL)                                                                                                   \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL), grid, dim3(64 * WPB), 0, st, ctx->d_const, ctx->d_slots, lane_first, lane_pics, d, \
-                       r_min, count, ctx->d_pred_scratch, ctx->d_slot_map, ctx->d_mismatch, ctx->d_overflow)
             if (team) {
-                if (d3)
-                    WRENC_LAUNCH(ctu_search_team_kernel<true>);
-                else
-                    WRENC_LAUNCH(ctu_search_team_kernel<false>);
+                // a call at one QP: one launch; a mixed call: one per QP class of the lane, its pictures only (a class's
+                // real pictures are contiguous, its padding is at its end)
+                for (int ga = g0; ga < g1;) {
+                    const DevConst* kq = d_k;
+                    int gb = g1, first = lane_first, n = lane_pics;
+                    if (cl) {
+                        kq = cl->groups[(size_t)ga].k;
+                        n = 0;
+                        for (gb = ga; gb < g1 && cl->groups[(size_t)gb].k == kq; ++gb) n += cl->groups[(size_t)gb].n_real;
+                        first = ga * per_group;
+                    }
+                    const dim3 grid(count * ((n + kTeamsPerGroup - 1) / kTeamsPerGroup));
+#define WRENC_LAUNCH(KERNEL)                                                                                                   \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL), grid, dim3(64 * WPB), 0, st, kq, d_pics, first, n, d, r_min, count,             \
+                       ctx->d_pred_scratch, ctx->d_slot_map, ctx->d_mismatch, ctx->d_overflow)
+                    if (d3)
+                        WRENC_LAUNCH(ctu_search_team_kernel<true>);
+                    else
+                        WRENC_LAUNCH(ctu_search_team_kernel<false>);
+#undef WRENC_LAUNCH
+                    HIP_TRY(ctx, hipGetLastError());
+                    ga = gb;
+                }
             } else {
+                const dim3 grid(count * (g1 - g0));
+#define WRENC_LAUNCH(KERNEL)                                                                                                   \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL), grid, dim3(64 * WPB), 0, st, d_k, d_pics, lane_first, lane_pics, d, r_min, count, \
+                       ctx->d_pred_scratch, ctx->d_slot_map, ctx->d_mismatch, ctx->d_overflow, lane_groups)
                 if (d3)
                     WRENC_LAUNCH(ctu_search_kernel<true>);
                 else
                     WRENC_LAUNCH(ctu_search_kernel<false>);
-            }
 #undef WRENC_LAUNCH
-            HIP_TRY(ctx, hipGetLastError());
+                HIP_TRY(ctx, hipGetLastError());
+            }
             if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_pool[2 * launches + 1], st));
             ctx->launch_team.push_back(team ? 1 : 0);
-            ctx->launch_ctus.push_back((long long)count * lane_pics);
+            int lane_real = lane_pics; // (without a mixed call's padding)
+            if (cl) {
+                lane_real = 0;
+                for (int g = g0; g < g1; ++g) lane_real += cl->groups[(size_t)g].n_real;
+            }
+            ctx->launch_ctus.push_back((long long)count * lane_real);
             ++launches;
         }
     }

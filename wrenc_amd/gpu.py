@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("WRENC_GPU_LIB", os.path.join(_HERE, "csrc", "libwrenc
 
 EXPORTED_SYMBOLS = [
     "wrenc_gpu_default_config", "wrenc_gpu_config_extra_params", "wrenc_gpu_create", "wrenc_gpu_destroy", "wrenc_gpu_last_error",
-    "wrenc_gpu_upload", "wrenc_gpu_encode", "wrenc_gpu_sync", "wrenc_gpu_download", "wrenc_gpu_download_compact", "wrenc_gpu_compact_mask_words", "wrenc_gpu_expand_levels", "wrenc_gpu_download_tokens", "wrenc_gpu_test_load_record", "wrenc_gpu_device_info",
+    "wrenc_gpu_upload", "wrenc_gpu_encode", "wrenc_gpu_set_slot_qp", "wrenc_gpu_sync", "wrenc_gpu_download", "wrenc_gpu_download_compact", "wrenc_gpu_compact_mask_words", "wrenc_gpu_expand_levels", "wrenc_gpu_download_tokens", "wrenc_gpu_test_load_record", "wrenc_gpu_device_info",
     "wrenc_gpu_alloc_host", "wrenc_gpu_free_host", "wrenc_gpu_encode_picture", "wrenc_gpu_set_schedule", "wrenc_gpu_last_schedule", "wrenc_gpu_stats_enable", "wrenc_gpu_last_encode_stats", "wrenc_gpu_last_encode_kernel_stats", "wrenc_gpu_final_pass_mismatches",
     "wrenc_gpu_test_fwd_dct", "wrenc_gpu_test_inv_dct", "wrenc_gpu_test_quantize",
     "wrenc_gpu_test_dequantize", "wrenc_gpu_test_predict", "wrenc_gpu_test_fwd_dct32", "wrenc_gpu_test_inv_dct32", "wrenc_gpu_test_quantize_p16", "wrenc_gpu_test_quantize_pk", "wrenc_gpu_test_set_wave_slots", "wrenc_gpu_test_scratch_overflows", "wrenc_gpu_test_head_ranges", "wrenc_gpu_test_avail_tab",
@@ -148,6 +148,8 @@ class Encoder:
         self.lib = load_library()
         self.cfg = config if config is not None else default_config(width, height, qp, max_split_depth,
                                                                      device, n_slots, extra_params)
+        self.extra_params = extra_params
+        self._qcfg = {}
         self.width, self.height = self.cfg.width, self.cfg.height
         self.ctx = C.c_void_p()
         rc = self.lib.wrenc_gpu_create(C.byref(self.cfg), C.byref(self.ctx))
@@ -188,6 +190,22 @@ class Encoder:
 
     def encode(self, first_slot=0, n_pictures=1):
         self._check(self.lib.wrenc_gpu_encode(self.ctx, first_slot, n_pictures))
+
+    def set_qp(self, slot, qp):
+        """Search `slot` at `qp` from the next encode call on (None: the context's QP again).  The per-QP config is
+        resolved like the context's, from the encoder's own extra_params (include/wrenc_gpu.h, wrenc_gpu_set_slot_qp)."""
+        if qp is None:
+            return self.set_slot_config(slot, None)
+        qp = int(qp)
+        if qp not in self._qcfg:
+            self._qcfg[qp] = default_config(self.width, self.height, qp, self.cfg.max_split_depth, self.cfg.device,
+                                            self.cfg.n_slots, self.extra_params)
+        self.set_slot_config(slot, self._qcfg[qp])
+
+    def set_slot_config(self, slot, qcfg):
+        """wrenc_gpu_set_slot_qp with a config of the caller's (None: the context's)."""
+        self.lib.wrenc_gpu_set_slot_qp.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        self._check(self.lib.wrenc_gpu_set_slot_qp(self.ctx, slot, C.addressof(qcfg) if qcfg is not None else None))
 
     def sync(self):
         self._check(self.lib.wrenc_gpu_sync(self.ctx))
