@@ -328,7 +328,7 @@ int wrenc_gpu_test_dequantize(wrenc_gpu_ctx* ctx, const int16_t* levels, int log
  * n x n; pair: Cb (n/2)^2 then Cr (n/2)^2); out_bytes must equal their total.
  * comp 4 / 5 / 6: not a prediction but a SAD LIST of the search (get_intra_pred_aux_cost, block_splitter.rs:64-108, of each
  * entry) over the luma block / the chroma pair (log2 size >= 3) / both, against the block's own samples in the planes as
- * originals: mode = first mode (2..66) | entries (1..13) << 8 | stride (1..64) << 16, entry j = first mode + j * stride (an
+ * originals: mode = first mode (2..66) | entries (1..16) << 8 | stride (1..64) << 16, entry j = first mode + j * stride (an
  * entry beyond 66 is not evaluated and reads 0).  comp 7 (log2 size >= 3, mode 0): the CCLM SAD list of the chroma pair,
  * entries LT_CCLM, T_CCLM, L_CCLM (get_chroma_intra_pred_aux_cost, :476-522).  A list item's output is 16 uint32 (64 bytes):
  * the SAD of entry j at index j. */

@@ -718,7 +718,9 @@ constexpr int kNoMode = 255; // list entry that is not evaluated (cost f32::MAX)
 //     the uniform loop over the entries fetches them with v_readlane;
 //   * the projected main references of ALL entries are built in one pass into r1 .. r2 (free
 //     during SAD lists), stride 4n per block;
-//   * a lane adds the SAD of entry mi into its accumulator when LANE == mi.
+//   * a lane adds the SAD of entry mi into its accumulator when LANE == mi;
+//   * the samples go through one of three loops, chosen per list and component by a cost count: a 4x4 block of samples
+//     per lane, one row of four per lane, or entry by entry with one sample per lane (see rows_per_lane below).
 // acc (lane mi): summed SAD of entry mi over the components; entries with mode kNoMode stay 0.
 #ifdef WRENC_EXP_NOINLINE_SAD // code-size experiment (profiles/r04_issue_model.md): one copy of the list, called
 #define WRENC_SAD_INLINE __attribute__((noinline))
@@ -819,34 +821,58 @@ __device__ WRENC_SAD_INLINE unsigned sad_list_angular(const Ctx& c, int comps, i
         WSYNC();
         PROF_MARK(sl1_);
         PROF_ADD2(PH_LEAF + 8, sl0_, sl1_);
-        // An iteration of the block-per-lane code costs about nine of the sample-per-lane code below (16 samples a lane
-        // instead of one, PDPC for every lane as soon as one entry has it) and takes 64 / G entries, whatever the list's
-        // length: it pays when the list fills its iterations -- the 13 directional candidates at every size from 8x8, the
-        // two probes of a step-search round only for the big blocks.
-        const int lgG_ = 2 * (lg - 2) + (nb == 2 ? 1 : 0);
-        const int its4_ = (nmodes + (64 >> lgG_) - 1) >> (6 - lgG_), its1_ = nmodes * ((nb * nn + 63) >> 6);
-        if (nb * nn > 32 && its4_ * 9 < its1_) {
-            // ---- a lane predicts one 4x4 BLOCK of samples of one entry: the G = nb (n / 4)^2 blocks of an entry sit side
-            // by side in the wave, 64 / G entries share an iteration (32x32 luma: one entry per iteration, all 1024
-            // samples in it).  The four samples of a block that lie next to each other ACROSS the prediction direction (a
-            // row of the block for the vertical modes, a column for the horizontal ones) share the projection (i_idx,
-            // i_fact), the filter taps and one 7-byte window of the projected references; their four results are
-            // packed into a dword and meet the originals in one v_sad_u8 -- against the block's rows, or against its
-            // columns (the originals transposed once per lane, in front of the loop over the entries).
-            const int lgb = lg - 2;                        // blocks per side, log2
-            const int lgG = 2 * lgb + (nb == 2 ? 1 : 0);   // blocks per entry, log2
+        // Three ways through a list.  BLOCKS: a lane predicts a 4x4 block of samples of one entry (four rows of four).
+        // LINES: a lane predicts ONE row of four -- the same code with a quarter of the samples per lane, so four times the
+        // lanes per entry.  SAMPLES (below): entry by entry, one sample per lane and iteration.  An iteration of the
+        // block code costs about nine of the sample code (16 samples a lane instead of one, PDPC for every lane as soon as
+        // one entry has it), one of the line code about three (the per-entry part -- parameters, PDPC weights, the
+        // reduction -- and one row instead of four); both take 64 / G entries an iteration whatever the list's length, so
+        // they pay when the list fills their iterations.  What the searches ask for: the 13 directional candidates go
+        // by blocks from 8x8 luma and the 8x8 chroma pair up, by lines at 4x4 (luma: all 13 in one iteration; the chroma
+        // pair of an 8x8: two); the six-entry list of a small block by lines (4x4 luma: one iteration, 8x8 luma: two,
+        // its chroma pair: one); the two probes of a step-search round by lines for 16x16 luma and the 8x8 chroma pair, by
+        // blocks for 32x32 luma and the 16x16 chroma pair (an entry has more than 64 rows of four there).
+        const int lgG4_ = 2 * (lg - 2) + (nb == 2 ? 1 : 0), lgGL_ = lgG4_ + 2;
+        const int cost1_ = nmodes * ((nb * nn + 63) >> 6);
+        const int cost4_ = nb * nn > 32 ? 9 * ((nmodes + (64 >> lgG4_) - 1) >> (6 - lgG4_)) : 1 << 20;
+        const int costL_ = lgGL_ <= 6 ? 3 * ((nmodes + (64 >> lgGL_) - 1) >> (6 - lgGL_)) : 1 << 20;
+        // ---- a lane predicts R rows of four samples of one entry: the G = nb n^2 / (4 R) lanes of an entry sit side by
+        // side in the wave, 64 / G entries share an iteration (32x32 luma by blocks: one entry per iteration, all 1024
+        // samples in it).  The four samples of a row lie next to each other ACROSS the prediction direction (a row of the
+        // block for the vertical modes, a column for the horizontal ones): they share the projection (i_idx,
+        // i_fact), the filter taps and one 7-byte window of the projected references; their four results are
+        // packed into a dword and meet the originals in one v_sad_u8 -- against the block's rows, or against its
+        // columns (the originals transposed once per lane, in front of the loop over the entries).
+        auto rows_per_lane = [&](auto rows_) {
+            constexpr int R = decltype(rows_)::value;
+            static_assert(R == 1 || R == 4, "a lane takes one row of four samples, or the four rows of a 4x4 block");
+            const int lgb = lg - 2;                        // 4x4 blocks per side = rows of four per line of the block, log2
+            const int lgP = 2 * lgb + (R == 1 ? 2 : 0);    // lanes per entry and plane, log2
+            const int lgG = lgP + (nb == 2 ? 1 : 0);       // lanes per entry, log2
             const int g = LANE & ((1 << lgG) - 1);
             const int slot = LANE >> lgG;
-            const int blk = g >> (2 * lgb);
-            const int bq = g & ((1 << (2 * lgb)) - 1);
+            const int blk = g >> lgP;
+            const int bq = g & ((1 << lgP) - 1);
+            // R = 4: the lane's block is at (x0, y0).  R = 1: its row is line la (a row y for the vertical modes, a column x for
+            // the horizontal ones), samples lc .. lc + 3 of it
             const int x0 = 4 * (bq & ((1 << lgb) - 1)), y0 = 4 * (bq >> lgb);
-            const uint32_t* orow = (const uint32_t*)((const uint8_t*)SH.r2 + obyte + blk * nn + y0 * n + x0);
-            const uint32_t o0 = orow[0], o1 = orow[n >> 2], o2 = orow[2 * (n >> 2)], o3 = orow[3 * (n >> 2)];
-            // the 4x4 bytes transposed: t_r = byte r of o0 | o1 | o2 | o3
-            const uint32_t a01 = __builtin_amdgcn_perm(o1, o0, 0x05010400u), b01 = __builtin_amdgcn_perm(o1, o0, 0x07030602u);
-            const uint32_t a23 = __builtin_amdgcn_perm(o3, o2, 0x05010400u), b23 = __builtin_amdgcn_perm(o3, o2, 0x07030602u);
-            const uint32_t t0 = __builtin_amdgcn_perm(a23, a01, 0x05040100u), t1 = __builtin_amdgcn_perm(a23, a01, 0x07060302u);
-            const uint32_t t2 = __builtin_amdgcn_perm(b23, b01, 0x05040100u), t3 = __builtin_amdgcn_perm(b23, b01, 0x07060302u);
+            const int la = bq >> lgb, lc = x0;
+            const uint8_t* oblk = (const uint8_t*)SH.r2 + obyte + blk * nn;
+            // R = 4: the block's rows o0..o3 and its columns t0..t3 (t_r = byte r of o0 | o1 | o2 | o3).  R = 1: o0 = the
+            // four samples as a piece of row la, t0 = as a piece of column la (byte la & 3 of the rows lc .. lc + 3)
+            const uint32_t* orow = (const uint32_t*)(oblk + (R == 4 ? y0 * n + x0 : lc * n + (la & ~3)));
+            uint32_t o0 = orow[0], o1 = orow[n >> 2], o2 = orow[2 * (n >> 2)], o3 = orow[3 * (n >> 2)];
+            uint32_t t0, t1 = 0, t2 = 0, t3 = 0;
+            if (R == 4) {
+                const uint32_t a01 = __builtin_amdgcn_perm(o1, o0, 0x05010400u), b01 = __builtin_amdgcn_perm(o1, o0, 0x07030602u);
+                const uint32_t a23 = __builtin_amdgcn_perm(o3, o2, 0x05010400u), b23 = __builtin_amdgcn_perm(o3, o2, 0x07030602u);
+                t0 = __builtin_amdgcn_perm(a23, a01, 0x05040100u), t1 = __builtin_amdgcn_perm(a23, a01, 0x07060302u);
+                t2 = __builtin_amdgcn_perm(b23, b01, 0x05040100u), t3 = __builtin_amdgcn_perm(b23, b01, 0x07060302u);
+            } else {
+                const uint32_t sel = 0x0C0C0400u + (uint32_t)(la & 3) * 0x0101u; // byte la & 3 of the second | of the first operand
+                t0 = __builtin_amdgcn_perm(__builtin_amdgcn_perm(o3, o2, sel), __builtin_amdgcn_perm(o1, o0, sel), 0x05040100u);
+                o0 = *(const uint32_t*)(oblk + la * n + lc);
+            }
 #ifndef WRENC_SAD_SUMS_AT
 #define WRENC_SAD_SUMS_AT 64
 #endif
@@ -866,7 +892,8 @@ __device__ WRENC_SAD_INLINE unsigned sad_list_angular(const Ctx& c, int comps, i
                 const bool filter_flag = flags & 1;
                 const int kind = (flags >> 1) & 3;
                 const int n_scale = flags >> 4;
-                const int a0 = vertical ? y0 : x0, c0 = vertical ? x0 : y0; // along / across the prediction direction
+                // along / across the prediction direction
+                const int a0 = R == 4 ? (vertical ? y0 : x0) : la, c0 = R == 4 ? (vertical ? x0 : y0) : lc;
                 const bool filt = comp == 0 && nn > 32 && (mode == 2 || mode == 34 || mode == 66);
                 const int oL = blk ? R_LC1 : (comp == 0 ? (filt ? R_LF : R_L0) : R_LC0);
                 const int oA = blk ? R_AC1 : (comp == 0 ? (filt ? R_AF : R_A0) : R_AC0);
@@ -887,7 +914,7 @@ __device__ WRENC_SAD_INLINE unsigned sad_list_angular(const Ctx& c, int comps, i
                 }
                 int sad = 0;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
+                for (int r = 0; r < R; ++r) {
                     const int along = a0 + r;
                     const int pr = M24(along + 1, angle);
                     const int i_idx = pr >> 5, i_fact = pr & 31;
@@ -940,7 +967,7 @@ __device__ WRENC_SAD_INLINE unsigned sad_list_angular(const Ctx& c, int comps, i
                     sad = (int)__builtin_amdgcn_sad_u8(packed, org, (uint32_t)sad);
                 }
                 if (!on) sad = 0;
-                // the entry's total: over the G lanes of its blocks
+                // the entry's total: over the G lanes of its rows
                 int tot = sad;
                 if (lgG >= 1) tot += dpp_mov<kDppSwap1>(tot);
                 if (lgG >= 2) tot += dpp_mov<kDppSwap2>(tot);
@@ -959,82 +986,17 @@ __device__ WRENC_SAD_INLINE unsigned sad_list_angular(const Ctx& c, int comps, i
             WSYNC();
             if (LANE < nmodes) acc += sums[LANE];
             WSYNC(); // the next component overwrites the tables
+        };
+        if (cost4_ < cost1_ && cost4_ < costL_) {
+            rows_per_lane(std::integral_constant<int, 4>());
             PROF_MARK(sl2_);
             PROF_ADD2(PH_LEAF + 9, sl1_, sl2_);
             continue;
         }
-        if (nb * nn <= 32) {
-            // ---- small blocks (4x4 luma: 16 samples, 4x4 chroma pair: 32): 4 or 2 entries share an
-            // iteration, the entry's parameters are per-lane values ----
-            const int lgS = nb * nn == 32 ? 5 : 4;
-            const int slot = LANE >> lgS;
-            const int i = LANE & ((1 << lgS) - 1);
-            const int blk = i >> (2 * lg);
-            const int ii = i & (nn - 1);
-            const int x = ii & (n - 1), y = ii >> lg;
-            const int o = ((const uint8_t*)SH.r2)[obyte + i];
-            const ref_t* L = SH.refs + (blk ? R_LC1 : (comp == 0 ? R_L0 : R_LC0));
-            const ref_t* A = SH.refs + (blk ? R_AC1 : (comp == 0 ? R_A0 : R_AC0));
-#pragma unroll 1
-            for (int base = 0; base < nmodes; base += 64 >> lgS) {
-                const int mi = base + slot;
-                const uint32_t pw = ptab[min(mi, 15)], pw2 = ptab2[min(mi, 15)];
-                const bool on = mi < nmodes && ((pw >> 17) & 1);
-                const int inv_angle = (int)(int16_t)(pw & 0xFFFF);
-                const bool vertical = (pw >> 16) & 1;
-                const int angle = (int)(int16_t)(pw2 & 0xFFFF);
-                const int flags = (int)((pw2 >> 16) & 0xFF);
-                const int mode = (int)(pw2 >> 24);
-                const bool filter_flag = flags & 1;
-                const int kind = (flags >> 1) & 3;
-                const int n_scale = flags >> 4;
-                const int along = vertical ? y : x, across = vertical ? x : y;
-                const int i_idx = M24(along + 1, angle) >> 5;
-                const int i_fact = M24(along + 1, angle) & 31;
-                const int ta = (((min(mi, 15) << cs) + blk) << lgs) + n + across + i_idx; // taps = ref[across + i_idx + 0..3]
-                const uint32_t* tp = (const uint32_t*)(tab + (ta & ~3));
-                const int taps = (int)__builtin_amdgcn_alignbyte(tp[1], tp[0], ta & 3);
-                int v;
-                if (comp == 0) {
-                    const int w = filter_flag ? 0x00102010 + (i_fact >> 1) * 0x0100FEFF : *(const int*)&SHT.fc[i_fact][0];
-                    v = min(max(__builtin_amdgcn_sdot4(w, taps, 8192 + 32, false) >> 6, 0), 255);
-                } else {
-                    v = __builtin_amdgcn_sdot4(((32 - i_fact) << 8) | (i_fact << 16), taps, 4096 + 16, false) >> 5;
-                }
-                if (kind != 0) { // PDPC, intra_predictor.rs:355-757; left[] = L+1, above[] = A
-                    int rl = 0, rt = 0, wl = 0, wt = 0;
-                    if (kind == 1) {
-                        const int alrs = L[0];
-                        rl = (int16_t)(L[y + 1] - alrs + v);
-                        rt = (int16_t)(A[x] - alrs + v);
-                        wl = mode == 50 ? pdpc_w(n_scale, x) : 0;
-                        wt = mode == 18 ? pdpc_w(n_scale, y) : 0;
-                    } else if (kind == 2) {
-                        const int dx_int = (M24(y + 1, inv_angle) + 256) >> 9;
-                        rt = y < (3 << n_scale) ? A[x + dx_int] : 0;
-                        wt = pdpc_w(n_scale, y);
-                    } else {
-                        const int dy_int = (M24(x + 1, inv_angle) + 256) >> 9;
-                        rl = x < (3 << n_scale) ? L[1 + y + dy_int] : 0;
-                        wl = pdpc_w(n_scale, x);
-                    }
-                    v = (int16_t)(M24(rl, wl) + M24(rt, wt) + M24(64 - wt - wl, v) + 32) >> 6;
-                    v = min(max(v, 0), 255);
-                }
-                const int d = o - v;
-                const int rs = row_sum_i32(on ? (d < 0 ? -d : d) : 0); // every lane: total of its row of 16
-                // slot totals: 16-sample slots are the rows, 32-sample slots two rows each
-                const int t0 = __builtin_amdgcn_readlane(rs, 0), t1 = __builtin_amdgcn_readlane(rs, 16),
-                          t2 = __builtin_amdgcn_readlane(rs, 32), t3 = __builtin_amdgcn_readlane(rs, 48);
-                if (lgS == 4) {
-                    acc += LANE == base ? (unsigned)t0 : (LANE == base + 1 ? (unsigned)t1 : (LANE == base + 2 ? (unsigned)t2 : (LANE == base + 3 ? (unsigned)t3 : 0u)));
-                } else {
-                    acc += LANE == base ? (unsigned)(t0 + t1) : (LANE == base + 1 ? (unsigned)(t2 + t3) : 0u);
-                }
-            }
-            WSYNC();
+        if (costL_ <= cost1_) {
+            rows_per_lane(std::integral_constant<int, 1>());
             PROF_MARK(sl3_);
-            PROF_ADD2(PH_LEAF + 10, sl1_, sl3_);
+            PROF_ADD2(PH_LEAF + 12, sl1_, sl3_);
             continue;
         }
         // ---- entry by entry: one predicted sample per lane and iteration, |org - pred| summed ----

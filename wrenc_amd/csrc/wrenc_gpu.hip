@@ -2085,7 +2085,7 @@ int wrenc_gpu_test_predict(wrenc_gpu_ctx* ctx, const uint8_t* rec_y, const uint8
         const bool ok = lg >= 2 && lg <= 5 && x >= 0 && y >= 0 && x + n <= W && y + n <= H && !(x & (n - 1)) && !(y & (n - 1)) &&
                         (comp == 0 || (comp == 1 && lg >= 3) || (comp == 2 && lg == 2) || (comp == 4) || (list && lg >= 3) ||
                          (comp == 7 && lg >= 3)) &&
-                        (comp == 7 ? mode == 0 : list ? (mode >= 0 && m0 >= 2 && m0 <= 66 && nm >= 1 && nm <= 13 && stride >= 1 && stride <= 64)
+                        (comp == 7 ? mode == 0 : list ? (mode >= 0 && m0 >= 2 && m0 <= 66 && nm >= 1 && nm <= 16 && stride >= 1 && stride <= 64)
                               : ((mode >= 0 && mode <= 66) || (comp == 1 && mode >= LT_CCLM && mode <= T_CCLM)));
         if (!ok) return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_test_predict: bad item");
         int* d = &dev_items[(size_t)i * 6];

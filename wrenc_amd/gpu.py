@@ -439,7 +439,7 @@ class Encoder:
 
     def sad_lists(self, rec_y, rec_cb, rec_cr, items):
         """SAD lists (the search's sad_list_angular) of blocks against their own samples in the planes as originals.
-        items: (n, 7) {x, y, log2 luma size, comps (1 luma, 2 chroma pair, 3 both), first mode, entries (<= 13), stride};
+        items: (n, 7) {x, y, log2 luma size, comps (1 luma, 2 chroma pair, 3 both), first mode, entries (<= 16), stride};
         entry j = first mode + j * stride (not evaluated beyond 66: its SAD stays 0).  Returns (n, 16) uint32."""
         it = np.ascontiguousarray(items, np.int32).reshape(-1, 7)
         dev = np.zeros((len(it), 5), np.int32)
