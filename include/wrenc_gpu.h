@@ -210,6 +210,37 @@ int wrenc_gpu_download_tokens(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_g
  * had produced it, so that the token pass can be compared with the host-only writer on records no search emits. */
 int wrenc_gpu_test_load_record(wrenc_gpu_ctx* ctx, int slot, const wrenc_gpu_picture* rec);
 
+/* Metrics read-back: PSNR and SSIM of what a slot was given against what the search made of it, without the planes
+ * crossing the bus.  A device pass behind the search reads the slot's originals (the upload's target) and its
+ * reconstruction once and leaves, per plane, the sums the two metrics are made of, in the definitions of ffmpeg's psnr and
+ * ssim filters as wrenc_amd/metrics.py restates them: the squared error; and over all (w/4 - 1)(h/4 - 1) windows of the
+ * plane (2x2 blocks of 4x4 samples, one block apart) the sum of the window's f32 value
+ *     ((float)(2 s1 s2 + c1) * (float)(2 cov + c2)) / ((float)(s1^2 + s2^2 + c1) * (float)(var + c2)),
+ *     s1 = sum a, s2 = sum b, ss = sum (a^2 + b^2), s12 = sum a b over the window, var = 64 ss - s1^2 - s2^2,
+ *     cov = 64 s12 - s1 s2, c1 = 416, c2 = 235963,
+ * every f32 operation rounded on its own, the quotient correctly rounded.  The sums are added in a fixed order: the same
+ * planes give the same bytes in any slot, any batch size and any run. */
+typedef struct wrenc_gpu_metrics {
+    uint64_t sse[3];           /* Y, Cb, Cr: sum of squared differences, exact */
+    double   ssim_sum[3];      /* sum of the per-window f32 values */
+    uint32_t ssim_windows[3];  /* (w/4 - 1)(h/4 - 1) of the plane */
+} wrenc_gpu_metrics;
+
+/* n slots in one call; blocking; waits for the encode call that searched them and for nothing queued later.
+ * WRENC_GPU_ESTATE unless every slot is in the encoded state (an upload into a slot replaces its originals
+ * and puts it back to "uploaded": ask before re-using the slot).  Changes nothing in the slot. */
+int wrenc_gpu_download_metrics(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_gpu_metrics* out);
+
+/* Host only, no device: PSNR (dB) and SSIM as {Avg, Y, U, V} in wrenc_amd/metrics.py's definitions:
+ * plane PSNR 10 log10(255^2 n / sse) (+infinity for sse 0), Avg from the MSE over all samples of the frame,
+ * SSIM Avg = (4 Y + U + V) / 6. */
+void wrenc_gpu_metrics_values(int width, int height, const wrenc_gpu_metrics* m, double psnr[4], double ssim[4]);
+
+/* Test entry: the same kernel on two arbitrary pictures of the context's size (host planes), no search involved;
+ * ssim_map[p] (may be NULL) receives the plane's per-window f32 values in raster order. */
+int wrenc_gpu_test_metrics(wrenc_gpu_ctx* ctx, const uint8_t* const org[3], const uint8_t* const rec[3],
+                           wrenc_gpu_metrics* out, float* const ssim_map[3]);
+
 /* Page-locked host memory for the planes handed to wrenc_gpu_upload / wrenc_gpu_download: transfers from
  * and to it run at PCIe rate and truly asynchronously (pageable buffers are staged by the runtime at a
  * fraction of that).  Optional: any host memory works.  Free with wrenc_gpu_free_host before destroy. */

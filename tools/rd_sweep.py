@@ -22,9 +22,10 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def _search_one_pass(w, h, depth, pics, qps, extra_params):
+def _search_one_pass(w, h, depth, pics, qps, extra_params, device_metrics=False):
     """Every QP of the sweep in ONE encoder and ONE encode call (frames x QPs slots, per-picture QP): per QP the records,
-    the call's search time (shared by all QPs) and the context's final-pass mismatches."""
+    the call's search time (shared by all QPs), the context's final-pass mismatches and, with device_metrics, per QP the
+    frames' metrics from the device's sums (else None)."""
     from wrenc_amd import gpu
     n = len(pics)
     enc = gpu.Encoder(w, h, qp=qps[0], max_split_depth=depth, n_slots=n * len(qps), extra_params=extra_params)
@@ -39,15 +40,18 @@ def _search_one_pass(w, h, depth, pics, qps, extra_params):
     t_search = time.perf_counter() - t0
     recs = {qp: [enc.download(i * n + f) for f in range(n)] for i, qp in enumerate(qps)}
     mism = enc.final_pass_mismatches()
+    dev = {qp: enc.download_metrics(i * n, n) for i, qp in enumerate(qps)} if device_metrics else None
     enc.close()
-    return recs, t_search, mism
+    return recs, t_search, mism, dev
 
 
 def run_sweep(width=3840, height=2176, frames=8, depth=3, qps=(22, 27, 32, 37), threads=8, extra_params=None,
-              keep_streams=False, verbose=True, one_pass=False):
+              keep_streams=False, verbose=True, one_pass=False, device_metrics=False):
     """The sweep as a function (tests/test_gpu_rd_sweep.py runs it too).  keep_streams: each result also carries
     "_stream" (parameter sets + pictures), "_recs" and the doc "_frames", for a decoder-side check by the caller.
-    one_pass: all QPs in one encode call (per-picture QP); each result's search time is then that of the whole call."""
+    one_pass: all QPs in one encode call (per-picture QP); each result's search time is then that of the whole call.
+    device_metrics: PSNR / SSIM from the sums the device takes of the originals and the reconstruction it holds
+    (Encoder.download_metrics, 60 bytes a picture) instead of a numpy pass over the downloaded planes."""
     from wrenc_amd import bitstream, gpu, metrics, synth
     w, h, n = width, height, frames
     pics = [synth.synth_textured_frame(w, h, f) for f in range(n)]
@@ -55,10 +59,10 @@ def run_sweep(width=3840, height=2176, frames=8, depth=3, qps=(22, 27, 32, 37), 
     pool = ThreadPoolExecutor(max_workers=threads)
     qps = [int(q) for q in qps]
     if one_pass:
-        all_recs, t_all, mism_all = _search_one_pass(w, h, depth, pics, qps, extra_params)
+        all_recs, t_all, mism_all, dev_all = _search_one_pass(w, h, depth, pics, qps, extra_params, device_metrics)
     for qp in qps:
         if one_pass:
-            recs, t_search, mism = all_recs[qp], t_all, mism_all
+            recs, t_search, mism, dev = all_recs[qp], t_all, mism_all, dev_all and dev_all[qp]
         else:
             enc = gpu.Encoder(w, h, qp=qp, max_split_depth=depth, n_slots=n, extra_params=extra_params)
             for s in range(n):
@@ -70,6 +74,7 @@ def run_sweep(width=3840, height=2176, frames=8, depth=3, qps=(22, 27, 32, 37), 
             t_search = time.perf_counter() - t0
             recs = [enc.download(s) for s in range(n)]
             mism = enc.final_pass_mismatches()
+            dev = enc.download_metrics(0, n) if device_metrics else None
             enc.close()
         t0 = time.perf_counter()
         nals = list(pool.map(lambda t: bitstream.write_picture(w, h, qp, t[0], t[1]), enumerate(recs)))
@@ -78,7 +83,10 @@ def run_sweep(width=3840, height=2176, frames=8, depth=3, qps=(22, 27, 32, 37), 
         total = len(head) + sum(len(x) for x in nals)
         per_frame = []
         for f in range(n):
-            m = metrics.frame_metrics(pics[f], (recs[f]["rec_y"], recs[f]["rec_cb"], recs[f]["rec_cr"]))
+            if dev is not None:
+                m = {k: dev[f][k] for k in ("PSNR", "SSIM")}
+            else:
+                m = metrics.frame_metrics(pics[f], (recs[f]["rec_y"], recs[f]["rec_cb"], recs[f]["rec_cr"]))
             m["n"] = f + 1
             m["bytes"] = len(nals[f])
             per_frame.append(m)
@@ -100,7 +108,7 @@ def run_sweep(width=3840, height=2176, frames=8, depth=3, qps=(22, 27, 32, 37), 
                 summ["SSIM"]["Avg"], summ["SSIM"]["Y"], n / t_search, n / t_write), flush=True)
     pool.shutdown()
     doc = {"config": {"width": w, "height": h, "frames": n, "max_split_depth": depth, "content": "synth_textured_frame",
-                      "extra_params": extra_params, "one_pass": bool(one_pass)},
+                      "extra_params": extra_params, "one_pass": bool(one_pass), "device_metrics": bool(device_metrics)},
            "results": results}
     if keep_streams:
         doc["_frames"] = pics
@@ -117,10 +125,11 @@ def main():
     ap.add_argument("--threads", type=int, default=8)
     ap.add_argument("--extra-params", help="the reference's RD-model knobs, K1=V1,K2=V2")
     ap.add_argument("--one-pass", action="store_true", help="all QPs in one encoder and one encode call")
+    ap.add_argument("--device-metrics", action="store_true", help="PSNR / SSIM from the device's sums (download_metrics)")
     ap.add_argument("--out")
     a = ap.parse_args()
     doc = run_sweep(a.width, a.height, a.frames, a.depth, [int(q) for q in a.qps.split(",")], a.threads, a.extra_params,
-                    one_pass=a.one_pass)
+                    one_pass=a.one_pass, device_metrics=a.device_metrics)
     if a.out:
         json.dump(doc, open(a.out, "w"), indent=1)
     return 0

@@ -13,7 +13,9 @@
 // reference does (main.rs:127-133); a failure inside the search or the stream writer (a HIP error, a level
 // that overflows the rate tables, ...) is where the reference panics (block_splitter.rs:453): status 101,
 // Rust's panic status, so that a truncated stream never comes with a success status.  Options the reference does not have: --batch, --threads, --device,
-// --devices (several GPUs of the node, batches in turn), --verbose, --ramp-down auto|always|never, --tokens auto|on|off
+// --devices (several GPUs of the node, batches in turn), --metrics PATH (PSNR and SSIM of every picture from sums the
+// device takes of the originals and the reconstruction it holds, wrenc_gpu_download_metrics: a JSON report in the shape of
+// the reference's evaluation harness, and one summary line on stderr), --verbose, --ramp-down auto|always|never, --tokens auto|on|off
 // (how a batch comes back.  auto and on: as the residual tokens the device makes of it, wrenc_gpu_download_tokens -- the
 // host then runs the CU-level syntax and the arithmetic coder only, 1.8x less host time per picture, 20x the bytes over
 // PCIe -- and as the compact level record, with residual_coding on the host, when they do not fit the token pool.  off,
@@ -21,6 +23,7 @@
 // Python.
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
@@ -127,7 +130,7 @@ private:
 };
 
 struct Options {
-    const char *input = nullptr, *output = nullptr, *reconst = nullptr, *extra = nullptr;
+    const char *input = nullptr, *output = nullptr, *reconst = nullptr, *extra = nullptr, *metrics = nullptr;
     long num_pictures = -1;
     int w = 0, h = 0, qp = 26; // ctu.rs:382 when --qp is absent
     int depth = 3, batch = 64, n_threads = 8;
@@ -188,6 +191,7 @@ Options parse_options(int argc, char** argv) {
         else if (a == "--threads") o.n_threads = atoi(val());
         else if (a == "--device") device = atoi(val());
         else if (a == "--devices") device_list = val();
+        else if (a == "--metrics") o.metrics = val();
         else if (a == "--verbose") o.verbose = true;
         else if (a == "--no-tokens") o.tokens = false;
         else if (a == "--ramp-down") { // how a run ends: auto (smaller last batches when the host's tail is heavy), always, never
@@ -272,6 +276,7 @@ struct HostSet { // one (device, slot set) unit: page-locked planes of one batch
     std::vector<std::vector<uint8_t>> nal; // per picture
     std::vector<int> status;
     std::vector<size_t> len;
+    std::vector<wrenc_gpu_metrics> metrics; // --metrics: the batch's sums
     int count = 0, first_poc = 0;       // the batch being searched / read back in this set
     int bs_count = 0, bs_first_poc = 0; // the batch whose slices are being written from this set
 };
@@ -335,6 +340,7 @@ std::vector<HostSet> make_units(const Options& o, const Geometry& g, const std::
         s.nal.resize(batch);
         s.status.assign(batch, 0);
         s.len.assign(batch, 0);
+        if (o.metrics) s.metrics.resize(batch);
     }
     return units;
 }
@@ -355,6 +361,8 @@ struct Run {
     long poc = 0;               // the next picture to read
     long pictures = 0;          // pictures written
     unsigned long long bytes = 0;
+    std::vector<wrenc_gpu_metrics> pic_metrics; // --metrics: every picture's sums and the bytes of its NAL units
+    std::vector<size_t> pic_bytes;
     bool tail_heavy = false;    // writing a batch's slices keeps the threads busy for more than 0.4 of the batch's turn
 
     Run(const Options& o_, const Geometry& g_, FILE* in, FILE* out, FILE* rec, int per_dev_)
@@ -433,6 +441,11 @@ struct Run {
     // time and the host writes a picture 1.8 .. 2.1x faster from them -- or, when they do not fit the pool or the unit has
     // none, the compact level record (mask of coded 4x4 blocks + those blocks); either way with the maps.  True: tokens.
     bool read_back(HostSet& s) {
+        if (o.metrics) { // the slots still hold the batch's originals next to its reconstruction: their sums, 60 bytes a picture
+            gpu_check(s, wrenc_gpu_download_metrics(s.ctx, s.base, s.count, s.metrics.data()));
+            if (pic_metrics.size() < (size_t)(s.first_poc + s.count)) pic_metrics.resize((size_t)(s.first_poc + s.count));
+            for (int k = 0; k < s.count; ++k) pic_metrics[(size_t)(s.first_poc + k)] = s.metrics[(size_t)k];
+        }
         if (s.tok_pool) {
             for (int k = 0; k < s.count; ++k) {
                 uint8_t* m = s.maps + g.maps * k;
@@ -510,11 +523,68 @@ struct Run {
             if (s.status[(size_t)k]) fatal("wrenc_bs_write_picture failed with %d on picture %d", s.status[(size_t)k], s.bs_first_poc + k);
             fwrite(s.nal[(size_t)k].data(), 1, s.len[(size_t)k], fout);
             bytes += s.len[(size_t)k];
+            if (o.metrics) pic_bytes.push_back(s.len[(size_t)k]);
             if (frec) fwrite(s.rec + g.pic * k, 1, g.pic, frec); // main.rs:387-399
         }
         pictures += s.bs_count;
     }
 };
+
+// --metrics: the report of the run in the shape of the reference's evaluation harness (metrics.json: per metric a summary and
+// the frames, attributes Avg / Y / U / V), with the pictures' bytes and QPs; a summary is the mean over the frames, an
+// infinite one (every frame identical) written as 100 as the harness does.  Numbers round-trip (%.17g).
+void write_metrics_report(const Run& run, const char* path, unsigned long long stream_bytes) {
+    const Options& o = run.o;
+    const size_t n = run.pic_metrics.size();
+    std::vector<double> psnr(4 * n), ssim(4 * n);
+    double mean[2][4] = {};
+    for (size_t i = 0; i < n; ++i) {
+        wrenc_gpu_metrics_values(o.w, o.h, &run.pic_metrics[i], &psnr[4 * i], &ssim[4 * i]);
+        for (int a = 0; a < 4; ++a) {
+            mean[0][a] += psnr[4 * i + a];
+            mean[1][a] += ssim[4 * i + a];
+        }
+    }
+    for (auto& m : mean)
+        for (double& v : m) {
+            v = n ? v / (double)n : 0.0;
+            if (std::isinf(v)) v = 100.0;
+        }
+    FILE* f = fopen(path, "w");
+    if (!f) die("failed to open metrics file: %s", strerror(errno));
+    const char* const attr[4] = {"Avg", "Y", "U", "V"};
+    const auto number = [&](double v) {
+        if (std::isinf(v)) fputs(v > 0 ? "Infinity" : "-Infinity", f);
+        else fprintf(f, "%.17g", v);
+    };
+    fprintf(f, "{\"width\": %d, \"height\": %d, \"frames\": %zu", o.w, o.h, n);
+    for (int m = 0; m < 2; ++m) {
+        const std::vector<double>& v = m ? ssim : psnr;
+        fprintf(f, ",\n \"%s\": {\"summary\": {", m ? "SSIM" : "PSNR");
+        for (int a = 0; a < 4; ++a) {
+            fprintf(f, "%s\"%s\": ", a ? ", " : "", attr[a]);
+            number(mean[m][a]);
+        }
+        fputs("}, \"per_frame\": [", f);
+        for (size_t i = 0; i < n; ++i) {
+            fprintf(f, "%s\n  {\"n\": %zu", i ? "," : "", i + 1);
+            for (int a = 0; a < 4; ++a) {
+                fprintf(f, ", \"%s\": ", attr[a]);
+                number(v[4 * i + a]);
+            }
+            fputc('}', f);
+        }
+        fputs("]}", f);
+    }
+    fputs(",\n \"frame_bytes\": [", f);
+    for (size_t i = 0; i < run.pic_bytes.size(); ++i) fprintf(f, "%s%zu", i ? ", " : "", run.pic_bytes[i]);
+    fputs("],\n \"frame_qp\": [", f);
+    for (size_t i = 0; i < n; ++i) fprintf(f, "%s%d", i ? ", " : "", run.slice_qp((long)i));
+    fputs("]}\n", f);
+    fclose(f);
+    fprintf(stderr, "%llu bytes  %.4f bpp  PSNR Avg %.2f Y %.2f U %.2f V %.2f dB  SSIM All %.4f Y %.4f\n", stream_bytes,
+            n ? 8.0 * (double)stream_bytes / ((double)n * o.w * o.h) : 0.0, mean[0][0], mean[0][1], mean[0][2], mean[0][3], mean[1][0], mean[1][1]);
+}
 
 double since(std::chrono::steady_clock::time_point t) {
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
@@ -550,11 +620,13 @@ int main(int argc, char** argv) {
     }
     const Geometry g(o.w, o.h);
     std::vector<HostSet> units = make_units(o, g, ctxs, per_dev, frec != nullptr);
+    size_t hdr_bytes = 0;
     {
         uint8_t hdr[512];
         size_t n = 0;
         if (wrenc_bs_write_parameter_sets(o.w, o.h, o.qp, hdr, sizeof(hdr), &n)) fatal("parameter sets do not fit");
         fwrite(hdr, 1, n, fout);
+        hdr_bytes = n;
     }
 
     const auto t_start = std::chrono::steady_clock::now();
@@ -619,6 +691,7 @@ int main(int argc, char** argv) {
     fflush(fout);
     if (frec) fclose(frec);
     if (fout != stdout) fclose(fout);
+    if (o.metrics) write_metrics_report(run, o.metrics, run.bytes + hdr_bytes);
     if (o.verbose) {
         const double dt = since(t_start);
         fprintf(stderr, "%ld pictures, %llu bytes, %.2f s, %.1f pictures/s (file to stream, %d GPU context(s), %d host threads)\n",

@@ -18,6 +18,7 @@
 //   dev_quant.h      quantizer.rs:338-759           backward 4-state Viterbi, one lane per state, DPP
 //   dev_search.h     block_splitter.rs:64-1154, ctu_encoder.rs:1421-1461
 //   dev_bins.h       ctu_encoder.rs:1786-2269       residual_coding as a token stream for the host's arithmetic coder
+//   dev_metrics.h    (the evaluation harness)       PSNR / SSIM sums of originals against the reconstruction
 #pragma once
 
 // The WRENC_EXP_* switches are measurement builds (tools/README.md); several of them give wrong results on purpose.
@@ -40,3 +41,4 @@
 #include "dev_search.h"
 #define WRENC_TOKENS_KERNEL_TU
 #include "dev_bins.h"
+#include "dev_metrics.h"

@@ -676,6 +676,10 @@ struct wrenc_gpu_ctx {
     unsigned* d_tok_counter = nullptr;
     uint32_t* d_tok_first = nullptr;
     int tok_first_cap = 0;
+    // metrics read-back: the waves' partial sums of one call and the pictures' totals, grown on demand
+    MetricsPartial* d_mpartial = nullptr;
+    MetricsSums* d_msums = nullptr;
+    int metrics_cap = 0; // pictures the scratch holds
     int schedule = WRENC_GPU_SCHEDULE_AUTO;
     int last_schedule = WRENC_GPU_SCHEDULE_WAVE; // what the most recent encode call ran
     bool stats_valid = false;
@@ -1150,6 +1154,8 @@ void wrenc_gpu_destroy(wrenc_gpu_ctx* ctx) {
     if (ctx->d_cmask) (void)hipFree(ctx->d_cmask);
     if (ctx->d_cpayload) (void)hipFree(ctx->d_cpayload);
     if (ctx->d_ccount) (void)hipFree(ctx->d_ccount);
+    if (ctx->d_mpartial) (void)hipFree(ctx->d_mpartial);
+    if (ctx->d_msums) (void)hipFree(ctx->d_msums);
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
     if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
@@ -1689,6 +1695,120 @@ int wrenc_gpu_download_tokens(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_g
             return rc;
     }
     HIP_TRY(ctx, hipStreamSynchronize(cs));
+    return WRENC_GPU_OK;
+}
+
+// the metrics pass over n pictures of `slots` from `first` on, on `st`: the waves' partial sums, then the pictures' totals
+// (maps: the test entry's per-window values, else NULL)
+static hipError_t launch_metrics(const wrenc_gpu_config& c, hipStream_t st, const PicBufs* slots, int first, int n, MetricsPartial* partials,
+                                 MetricsSums* sums, float* maps) {
+    const int per_pic = met_plane(c.width, c.height, 0).waves + 2 * met_plane(c.width, c.height, 1).waves;
+    const long long waves = (long long)n * per_pic;
+    const dim3 grid((unsigned)((waves + 3) / 4));
+    if (maps)
+        hipLaunchKernelGGL(metrics_kernel<true>, grid, dim3(256), 0, st, slots, first, n, c.width, c.height, partials, maps);
+    else
+        hipLaunchKernelGGL(metrics_kernel<false>, grid, dim3(256), 0, st, slots, first, n, c.width, c.height, partials, maps);
+    hipLaunchKernelGGL(metrics_finish_kernel, dim3(n), dim3(64), 0, st, partials, c.width, c.height, sums);
+    return hipGetLastError();
+}
+
+static void fill_metrics(const wrenc_gpu_config& c, const MetricsSums& s, wrenc_gpu_metrics& m) {
+    for (int p = 0; p < 3; ++p) {
+        m.sse[p] = s.sse[p];
+        m.ssim_sum[p] = s.ssim[p];
+        m.ssim_windows[p] = (uint32_t)met_plane(c.width, c.height, p ? 1 : 0).windows;
+    }
+}
+
+int wrenc_gpu_download_metrics(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_gpu_metrics* out) {
+    if (!ctx || !out) return WRENC_GPU_EINVAL;
+    if (const int rc = check_encoded(ctx, first_slot, n, "slot range out of bounds")) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+    const wrenc_gpu_config& c = ctx->cfg;
+    const size_t per_pic = (size_t)met_plane(c.width, c.height, 0).waves + 2 * (size_t)met_plane(c.width, c.height, 1).waves;
+    if (ctx->metrics_cap < n) {
+        ctx->metrics_cap = 0;
+        HIP_TRY(ctx, realloc_scratch(ctx->d_mpartial, (size_t)n * per_pic * sizeof(MetricsPartial)));
+        HIP_TRY(ctx, realloc_scratch(ctx->d_msums, (size_t)n * sizeof(MetricsSums)));
+        ctx->metrics_cap = n;
+    }
+    // on the copy stream, behind the encode call that searched these slots and nothing later
+    hipStream_t cs = ctx->copy_stream;
+    if (const int rc = wait_for_search(ctx, first_slot, n)) return rc;
+    HIP_TRY(ctx, launch_metrics(c, cs, ctx->d_slots, first_slot, n, ctx->d_mpartial, ctx->d_msums, nullptr));
+    std::vector<MetricsSums> sums((size_t)n);
+    HIP_TRY(ctx, hipMemcpyAsync(sums.data(), ctx->d_msums, (size_t)n * sizeof(MetricsSums), hipMemcpyDeviceToHost, cs));
+    if (const int rc = read_overflow(ctx)) return rc;
+    for (int k = 0; k < n; ++k) fill_metrics(c, sums[(size_t)k], out[k]);
+    return WRENC_GPU_OK;
+}
+
+void wrenc_gpu_metrics_values(int width, int height, const wrenc_gpu_metrics* m, double psnr[4], double ssim[4]) {
+    const double samples[3] = {(double)width * height, (double)(width / 2) * (height / 2), (double)(width / 2) * (height / 2)};
+    const auto db = [](double mse) { return mse == 0.0 ? (double)INFINITY : 10.0 * log10(255.0 * 255.0 / mse); };
+    double weighted = 0.0;
+    for (int p = 0; p < 3; ++p) {
+        const double mse = (double)m->sse[p] / samples[p];
+        psnr[1 + p] = db(mse);
+        weighted += mse * samples[p];
+        ssim[1 + p] = m->ssim_sum[p] / (double)m->ssim_windows[p];
+    }
+    psnr[0] = db(weighted / (samples[0] + samples[1] + samples[2]));
+    ssim[0] = (4.0 * ssim[1] + ssim[2] + ssim[3]) / 6.0;
+}
+
+int wrenc_gpu_test_metrics(wrenc_gpu_ctx* ctx, const uint8_t* const org[3], const uint8_t* const rec[3], wrenc_gpu_metrics* out,
+                           float* const ssim_map[3]) {
+    if (!ctx || !org || !rec || !out) return WRENC_GPU_EINVAL;
+    for (int p = 0; p < 3; ++p)
+        if (!org[p] || !rec[p]) return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_test_metrics: null plane");
+    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+    const wrenc_gpu_config& c = ctx->cfg;
+    const MetPlane L = met_plane(c.width, c.height, 0), C = met_plane(c.width, c.height, 1);
+    const size_t wh = (size_t)c.width * c.height, n_win = (size_t)L.windows + 2 * (size_t)C.windows;
+    // two pictures of its own (planes as one slab each, like a slot's), never a slot of the context
+    uint8_t* d_planes = nullptr;
+    PicBufs* d_pic = nullptr;
+    MetricsPartial* d_part = nullptr;
+    MetricsSums* d_sums = nullptr;
+    float* d_map = nullptr;
+    MetricsSums sums = {};
+    std::vector<float> map(ssim_map ? n_win : 0);
+    hipError_t e = hipMalloc((void**)&d_planes, 2 * (wh + wh / 2));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_pic, sizeof(PicBufs));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_part, (size_t)(L.waves + 2 * C.waves) * sizeof(MetricsPartial));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_sums, sizeof(MetricsSums));
+    if (e == hipSuccess && ssim_map) e = hipMalloc((void**)&d_map, n_win * sizeof(float));
+    if (e == hipSuccess) {
+        PicBufs pb = {};
+        uint8_t* at = d_planes;
+        for (int p = 0; p < 6 && e == hipSuccess; ++p) { // Y | Cb | Cr of the originals, then of the reconstruction
+            const int comp = p % 3;
+            if (p < 3) pb.org[comp] = at; else pb.rec[comp] = at;
+            e = hipMemcpy(at, p < 3 ? org[comp] : rec[comp], plane_bytes(c, comp, 1), hipMemcpyHostToDevice);
+            at += plane_bytes(c, comp, 1);
+        }
+        if (e == hipSuccess) e = hipMemcpy(d_pic, &pb, sizeof(pb), hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess)
+        e = launch_metrics(c, 0, d_pic, 0, 1, d_part, d_sums, d_map);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(&sums, d_sums, sizeof(sums), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && ssim_map) e = hipMemcpy(map.data(), d_map, n_win * sizeof(float), hipMemcpyDeviceToHost);
+    (void)hipFree(d_planes);
+    (void)hipFree(d_pic);
+    (void)hipFree(d_part);
+    (void)hipFree(d_sums);
+    (void)hipFree(d_map);
+    if (e != hipSuccess) (void)hipGetLastError();
+    HIP_TRY(ctx, e);
+    fill_metrics(c, sums, *out);
+    if (ssim_map) {
+        const size_t at[3] = {0, (size_t)L.windows, (size_t)L.windows + (size_t)C.windows};
+        for (int p = 0; p < 3; ++p)
+            if (ssim_map[p]) memcpy(ssim_map[p], map.data() + at[p], (size_t)(p ? C.windows : L.windows) * sizeof(float));
+    }
     return WRENC_GPU_OK;
 }
 

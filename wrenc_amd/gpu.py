@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("WRENC_GPU_LIB", os.path.join(_HERE, "csrc", "libwrenc
 
 EXPORTED_SYMBOLS = [
     "wrenc_gpu_default_config", "wrenc_gpu_config_extra_params", "wrenc_gpu_create", "wrenc_gpu_destroy", "wrenc_gpu_last_error",
-    "wrenc_gpu_upload", "wrenc_gpu_encode", "wrenc_gpu_set_slot_qp", "wrenc_gpu_sync", "wrenc_gpu_download", "wrenc_gpu_download_compact", "wrenc_gpu_compact_mask_words", "wrenc_gpu_expand_levels", "wrenc_gpu_download_tokens", "wrenc_gpu_test_load_record", "wrenc_gpu_device_info",
+    "wrenc_gpu_upload", "wrenc_gpu_encode", "wrenc_gpu_set_slot_qp", "wrenc_gpu_sync", "wrenc_gpu_download", "wrenc_gpu_download_compact", "wrenc_gpu_compact_mask_words", "wrenc_gpu_expand_levels", "wrenc_gpu_download_tokens", "wrenc_gpu_download_metrics", "wrenc_gpu_metrics_values", "wrenc_gpu_test_metrics", "wrenc_gpu_test_load_record", "wrenc_gpu_device_info",
     "wrenc_gpu_alloc_host", "wrenc_gpu_free_host", "wrenc_gpu_encode_picture", "wrenc_gpu_set_schedule", "wrenc_gpu_last_schedule", "wrenc_gpu_stats_enable", "wrenc_gpu_last_encode_stats", "wrenc_gpu_last_encode_kernel_stats", "wrenc_gpu_final_pass_mismatches",
     "wrenc_gpu_test_fwd_dct", "wrenc_gpu_test_inv_dct", "wrenc_gpu_test_quantize",
     "wrenc_gpu_test_dequantize", "wrenc_gpu_test_predict", "wrenc_gpu_test_fwd_dct32", "wrenc_gpu_test_inv_dct32", "wrenc_gpu_test_quantize_p16", "wrenc_gpu_test_quantize_pk", "wrenc_gpu_test_set_wave_slots", "wrenc_gpu_test_scratch_overflows", "wrenc_gpu_test_head_ranges", "wrenc_gpu_test_avail_tab",
@@ -58,6 +58,23 @@ class Tokens(C.Structure):
 
 
 TOKEN_PAGE = 64  # WRENC_GPU_TOKEN_PAGE
+
+
+class Metrics(C.Structure):
+    _fields_ = [("sse", C.c_uint64 * 3), ("ssim_sum", C.c_double * 3), ("ssim_windows", C.c_uint32 * 3)]
+
+
+def metrics_values(width, height, m):
+    """wrenc_gpu_metrics_values (host only): a Metrics record as {"PSNR": {Avg, Y, U, V}, "SSIM": {...}, "_raw": {...}}, the
+    shape of metrics.frame_metrics."""
+    lib = load_library()
+    psnr, ssim = (C.c_double * 4)(), (C.c_double * 4)()
+    lib.wrenc_gpu_metrics_values.restype = None
+    lib.wrenc_gpu_metrics_values.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.wrenc_gpu_metrics_values(width, height, C.byref(m), psnr, ssim)
+    names = ("Avg", "Y", "U", "V")
+    return {"PSNR": dict(zip(names, psnr)), "SSIM": dict(zip(names, ssim)),
+            "_raw": {"sse": list(m.sse), "ssim_sum": list(m.ssim_sum), "ssim_windows": list(m.ssim_windows), "bytes": bytes(m)}}
 
 
 class WrencGpuError(RuntimeError):
@@ -259,6 +276,30 @@ class Encoder:
         self._check(rc)
         self.last_token_words = int(used.value)   # words of the pages in use (they are spread over the whole pool)
         return pool, pics
+
+    def download_metrics(self, first_slot, n):
+        """PSNR / SSIM of n encoded slots from the device's sums (include/wrenc_gpu.h, wrenc_gpu_download_metrics): per
+        picture {"PSNR": {...}, "SSIM": {...}} as metrics.frame_metrics gives them, the raw sums under "_raw"."""
+        outs = (Metrics * max(n, 1))()
+        self.lib.wrenc_gpu_download_metrics.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        self._check(self.lib.wrenc_gpu_download_metrics(self.ctx, first_slot, n, outs))
+        return [metrics_values(self.width, self.height, outs[k]) for k in range(n)]
+
+    def test_metrics(self, org, rec, maps=False):
+        """Test entry: the metrics kernel on two arbitrary pictures (y, cb, cr) of the context's size.  Returns the entry of
+        download_metrics; with maps, also the three planes' per-window f32 SSIM values as (h/4 - 1, w/4 - 1) arrays."""
+        o = [np.ascontiguousarray(a, np.uint8) for a in org]
+        r = [np.ascontiguousarray(a, np.uint8) for a in rec]
+        shapes = [(self.height, self.width)] + [(self.height // 2, self.width // 2)] * 2
+        assert [a.shape for a in o] == shapes and [a.shape for a in r] == shapes
+        out = Metrics()
+        wins = [np.zeros((hh // 4 - 1, ww // 4 - 1), np.float32) for hh, ww in shapes] if maps else None
+        self.lib.wrenc_gpu_test_metrics.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._check(self.lib.wrenc_gpu_test_metrics(self.ctx, (C.c_void_p * 3)(*[_p(a).value for a in o]),
+                                                    (C.c_void_p * 3)(*[_p(a).value for a in r]), C.byref(out),
+                                                    (C.c_void_p * 3)(*[_p(a).value for a in wins]) if maps else None))
+        m = metrics_values(self.width, self.height, out)
+        return (m, wins) if maps else m
 
     def device_info(self):
         """(wavefronts of the search kernel the device holds at once, HIP streams an encode call uses)."""
