@@ -2,6 +2,7 @@
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -mllvm -sink-insts-to-avoid-spills=1 -DWRENC_PROFILE \
         -o xbuild/libwrenc_gpu_prof.so wrenc_amd/csrc/wrenc_gpu.hip
   python tools/phase_profile.py WxH DEPTH B SCHEDULE [1 = textured content]
+(WRENC_PROF_LIB=path: another -DWRENC_PROFILE build, e.g. one with -DWRENC_EXHAUSTIVE_SPLITS.)
 The counters are s_memtime differences of thread 0 of each workgroup (wave 0 = member 0 of its team in the team
 schedule), summed over all CTUs."""
 import ctypes as C
@@ -10,7 +11,7 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-os.environ["WRENC_GPU_LIB"] = os.path.join(ROOT, "xbuild", "libwrenc_gpu_prof.so")
+os.environ["WRENC_GPU_LIB"] = os.environ.get("WRENC_PROF_LIB", os.path.join(ROOT, "xbuild", "libwrenc_gpu_prof.so"))
 sys.path.insert(0, ROOT)
 from wrenc_amd import gpu, synth  # noqa: E402
 
@@ -24,6 +25,8 @@ enc = gpu.Encoder(w, h, qp=32, max_split_depth=depth, n_slots=B, schedule=schedu
 for s in range(B):
     enc.upload(s, *frames[s % 4])
 enc.sync()
+# children a split cut left unsearched (dev_search.h, kSplitCut)
+CUTS = ["cut_leaf4", "cut_leafc4", "cut_node16", "cut_node8"]
 names = (["predict", "fdct", "q_pre", "q_back", "q_trace", "deq", "idct", "recon", "total", "ctrl", "refs", "skip", "nstep", "nfull"]
          + ["stages_t%d_c%d" % (4 << (i // 2), i % 2) for i in range(8)] + ["x"] + ["stages_n%d_c%d" % (4 << (i // 2), i % 2) for i in range(8)]
          + ["x2", "qb_pre", "qb_wait1", "qb_walk", "qb_wait2", "t_xchg", "copy"] + ["cb%d" % i for i in range(32)] + ["y"]
@@ -32,7 +35,8 @@ names = (["predict", "fdct", "q_pre", "q_back", "q_trace", "deq", "idct", "recon
          + ["ev%d" % i for i in range(64)] + ["y6"] + ["evn%d" % i for i in range(64)] + ["y7"] + ["quant_t%d" % (4 << i) for i in range(4)] + ["y8"]
          + ["leaf8_packA", "leaf8_sad", "leaf8_packB", "leaf8_cclm", "leaf16_packA", "leaf16_sad", "leaf16_packB", "leaf16_packC",
             "sad_tables", "sad_blocks", "sad_samples", "leaf8_cclm_sad", "sad_lines"] + ["y9"]
-         + ["leaf4_stage", "leaf4_packA", "leaf4_sad", "leaf4_packB", "leafc4", "split8_other"] + ["hist%d" % i for i in range(64)])
+         + ["leaf4_stage", "leaf4_packA", "leaf4_sad", "leaf4_packB", "leafc4", "split8_other"] + ["y10"] + ["hist%d" % i for i in range(64)]
+         + ["y11"] + CUTS)
 KINDS = ["sadlist", "full", "nop/copy", "sadsearch", "cclmsearch", "leaf4", "leafc4", "leaf8", "leaf16", "split8"] + ["?"] * 6
 N = len(names)
 out = (C.c_ulonglong * N)()
@@ -52,6 +56,9 @@ for i, n in enumerate(names):
     if i == 8 or n.startswith("x") or n.startswith("y") or n.startswith("cbn") or out[i] == 0:
         continue
     if n.startswith("stn") or n.startswith("evn") or n.startswith("hist"):
+        continue
+    if n in CUTS:
+        print("%-10s %10.2f per CTU (children not searched)" % (n, out[i] / nctu))
         continue
     if n.startswith("ev"):
         k = int(n[2:])

@@ -12,6 +12,21 @@ namespace wrenc {
 enum { K_SADLIST = 0, K_FULL = 1, K_NOP = 2, K_SADSEARCH = 3, K_CCLMSEARCH = 4, K_LEAF4 = 5, K_LEAFC4 = 6, K_LEAF8 = 7, K_LEAF16 = 8, K_SPLIT8 = 9, K_SERVE4 = 10 };
 enum { COPY_NONE = 0, COPY_SAVE = 1, COPY_RESTORE = 2, COPY_PULL = 3 };
 
+// Split cut (wave schedule): a node's children are searched only until their partial cost, summed in z-order in f32 from
+// 0.0 as the full sum is (:1116-1123), is strictly greater than the node's unsplit cost.  Every child cost is >= 0 and
+// f32 addition is monotone in either operand, so every later partial sum, the final one included, is >= this one: the
+// comparison of :1125-1145 is decided (a tie would still go to the split, so equality searches on), the unsplit
+// candidate is restored over the whole node exactly as after the last child, and what the skipped children would have
+// written is never read.  Off in the trace build, which exists to pin the candidates that lose (tests/test_gpu_trace.py),
+// and with -DWRENC_EXHAUSTIVE_SPLITS (A/B measurements, tools/README.md).  The team / level schedule stays exhaustive
+// whatever the build: its members search a node and its subtree at the same time, so a node's unsplit cost is not
+// known when its children start.
+#if defined(WRENC_TRACE) || defined(WRENC_EXHAUSTIVE_SPLITS)
+constexpr bool kSplitCut = false;
+#else
+constexpr bool kSplitCut = true;
+#endif
+
 struct Req {
     int kind;       // K_SADLIST: predict + SAD of a list of modes (block_splitter.rs:64-108, 476-522);
                     // K_FULL: predict .. reconstruct (:146-185); K_SADSEARCH: the whole SAD part of a leaf search in
@@ -49,6 +64,8 @@ struct Req {
     int pre_copy, copy_comps, copy_slot, copy_tx, copy_ty, copy_tlg;
     unsigned long long modes_lo, modes_hi; // K_SADLIST: one byte per entry (8 + 8), the same mode for luma and chroma
     float fcur;     // K_LEAF8, part 4 alone (team schedule): the winner's DM chroma cost (:1040)
+                    // K_SPLIT8: the 8x8 node's unsplit cost, the search stops once the split's partial cost is greater
+                    // (kSplitCut; +inf = search every leaf)
 };
 
 struct Res {
@@ -1584,6 +1601,7 @@ __device__ __forceinline__ void fill_maps(int bx, int by, int lg, int luma_mode,
 // leaf's originals staged, the decision maps filled (the chroma leaf's DM mode is the luma mode of the 4x4 covering
 // the parent's centre, block_splitter.rs:795-805), the costs summed in z-order in f32 from 0.0 (:1116-1123).  Five control
 // steps of 3-6 k cycles each fewer per 8x8 node, 80 per CTU at max-split-depth 3.
+// The leaves after the one at which the running cost exceeds q.fcur, the node's unsplit cost, are not searched (kSplitCut).
 // (Only the kernels built for max-split-depth 3 contain it, D3 below: inlined into the one evaluator of a kernel that also
 // serves depth 2, which never splits an 8x8, it cost that depth 2.5 %; as an out-of-line function it cost both depths more.)
 __device__ __forceinline__ Res split8_search(const Ctx& c, const Req& q, int* overflow) {
@@ -1615,6 +1633,14 @@ __device__ __forceinline__ Res split8_search(const Ctx& c, const Req& q, int* ov
         const Res rl = leaf4_search(c, ql, overflow);
         fill_maps(ql.tx, ql.ty, 2, rl.imin, 0, true, false);
         split8 = uni_f(split8 + rl.vmin);
+        // the split has lost (kSplitCut above; strictly greater: a tie is a split): T_SPLIT8 restores the unsplit
+        // candidate over the whole node, the maps and the tile of the leaves that did run included
+        if (kSplitCut && split8 > q.fcur) {
+            PROF_ADD2(PH_CUT + 0, 0, 3 - i8);
+            PROF_ADD2(PH_CUT + 1, 0, 1);
+            r.vmin = split8;
+            return r;
+        }
     }
     Req qc = {};
     qc.kind = K_LEAFC4;
@@ -2508,6 +2534,7 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
             q.kind = K_SPLIT8;
             q.stage = 0;
             q.tree = TREE_DUAL_LUMA;
+            q.fcur = ns; // (kSplitCut)
             if (t.pend) { // the unsplit 8x8 candidate is saved first
                 req_copy(q, COPY_SAVE, t.pend, t.pslot, t.pbx, t.pby, t.plg);
                 t.pend = 0;
@@ -2635,17 +2662,21 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
                 SH.child[pl] = (uint8_t)ch;
             }
             WSYNC();
-            if (ch < 4) { // next sibling
+            // the parent's split has lost once its partial cost is strictly greater than its unsplit cost (kSplitCut:
+            // the children still to come add costs >= 0 in f32, which never lowers the sum): no sibling is entered
+            const bool lost = acc > uni_f(SH.ns_cost[pl]);
+            if (ch < 4 && !(kSplitCut && lost)) { // next sibling
                 t.bx = (uint8_t)(pbx + (ch & 1) * (psz >> 1));
                 t.by = (uint8_t)(pby + (ch >> 1) * (psz >> 1));
                 cont = T_ENTER;
                 break;
             }
+            PROF_ADD2(PH_CUT + 1 + level, 0, 4 - ch); // (level 2: 8x8 nodes not searched, level 1: 16x16 nodes)
             // parent complete: split vs unsplit (:1125-1145)
             t.bx = (uint8_t)pbx;
             t.by = (uint8_t)pby;
             t.level = (uint8_t)pl;
-            if (acc > uni_f(SH.ns_cost[pl])) {
+            if (lost) {
                 t.rbx = (uint8_t)pbx;
                 t.rby = (uint8_t)pby;
                 t.rlg = (uint8_t)(5 - pl);
@@ -2675,6 +2706,7 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
                         q.kind = K_SPLIT8;
                         q.stage = 0;
                         q.tree = TREE_DUAL_LUMA;
+                        q.fcur = __builtin_inff(); // every leaf: member 2 is still searching the unsplit candidate
                         t.cont = T_SPLIT8;
                         return true;
                     }
