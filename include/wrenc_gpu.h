@@ -38,14 +38,24 @@ enum wrenc_gpu_status {
     WRENC_GPU_EHIP = -4,     /* HIP runtime error, see last_error */
     WRENC_GPU_ESTATE = -5,   /* slot not submitted / still in flight */
     WRENC_GPU_ELEVEL = -6    /* a quantised level reached 1024 (reference would panic,
-                                block_splitter.rs:453) */
+                                block_splitter.rs:453).  Raised where a coefficient's quotient
+                                qd = |(tc << sh) - off| / lsc is >= 2044, as the reference does in every
+                                state.  At qd = 2043 the reference panics only if its search reaches the
+                                position in a state with delta 1 (some non-zero coefficient later in scan
+                                order); the device costs both delta classes at every position and raises
+                                the error there regardless -- one step early for a position reached in
+                                states 0 / 1 only, never late.  The DC position is exempt: its level is
+                                qd / 2 in both delta classes, so 2043 quantises there on both sides */
 };
 /* WRENC_GPU_ELEVEL and the internal WRENC_GPU_EHIP "a team member never reached a meeting point" are reported by sync /
  * download / download_compact and are STICKY, like the reference's panic: the pictures of the call that raised them --
  * and of every call in flight next to it -- are undefined (a team that times out stops storing, its CTU and everything
  * that depends on it are garbage; the slots' zero-block bookkeeping no longer matches their level planes), every later
  * sync / download of the context fails the same way, and the context must be destroyed.  The wrenc_gpu_test_* entries
- * keep a word of their own and never poison a context. */
+ * keep a word of their own and never poison a context: wrenc_gpu_test_quantize / _quantize_p16 / _quantize_pk return
+ * WRENC_GPU_ELEVEL from the call whose blocks raised it (the levels and costs they wrote are then those of table
+ * indices clamped to 1023, not the reference's) and clear the word on every return path, so the next call on the
+ * context starts clean. */
 
 /* Resolved configuration.  The RD-model constants are resolved on the host
  * (libm pow/powf, exactly as block_splitter.rs:29-53,187-375 and

@@ -50,6 +50,7 @@ def lib():
         _lib.wro_encode_picture.restype = C.c_int
         _lib.wro_last_final_pass_mismatches.restype = C.c_long
         _lib.wro_level_cost.restype = C.c_int64
+        _lib.wro_quantize.restype = C.c_int
         _lib.wro_header_bits.restype = C.c_int64
         _lib.wro_chroma_header_bits.restype = C.c_int64
     return _lib
@@ -197,9 +198,17 @@ def quantize(coef, qp, viterbi=False):
     n = coef.shape[0]
     coef = np.ascontiguousarray(coef, np.int16)
     out = np.zeros_like(coef)
-    fn = lib().wro_quantize_viterbi if viterbi else lib().wro_quantize
-    fn(_p(coef), int(n).bit_length() - 1, int(qp), _p(out))
+    if viterbi:
+        lib().wro_quantize_viterbi(_p(coef), int(n).bit_length() - 1, int(qp), _p(out))
+    elif lib().wro_quantize(_p(coef), int(n).bit_length() - 1, int(qp), _p(out)) != 0:
+        raise OverflowError("the search asked dq_table for entry %d: the reference panics (quantizer.rs:30)" % last_table_index())
     return out
+
+
+def last_table_index():
+    """The largest dq_table entry the last quantize() call asked for (1023 is the table's last)."""
+    lib().wro_last_table_index.restype = C.c_long
+    return int(lib().wro_last_table_index())
 
 
 def quantize_sc(coef, qp, use_head=True, use_z=True, use_seg=False, use_whole=True):

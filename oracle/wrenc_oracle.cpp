@@ -40,7 +40,9 @@ static int16_t g_dct64[64][64];
 // set when a table index reaches 1024: the reference panics there (block_splitter.rs:453,
 // quantizer.rs:30); the oracle clamps the index and reports failure
 static bool g_table_overflow = false;
+static size_t g_table_top = 0; // largest index asked for since wro_quantize last reset it (wro_last_table_index)
 static inline size_t tbl(size_t i) {
+    if (i > g_table_top) g_table_top = i;
     if (i >= 1024) {
         g_table_overflow = true;
         return 1023;
@@ -2524,7 +2526,9 @@ void wro_inv_dct(const int16_t* deq, int log2n, int16_t* res) {
     init_tables();
     inv_dct(deq, log2n, res);
 }
-void wro_quantize(const int16_t* coef, int log2n, int qp, int16_t* levels) {
+// returns -4 when the DFS asked dq_table for an entry >= 1024 (the reference panics there, quantizer.rs:30): the levels
+// are then those of the clamped index, not the reference's
+int wro_quantize(const int16_t* coef, int log2n, int qp, int16_t* levels) {
     init_tables();
     static thread_local RdConst rd;
     static thread_local int rd_qp = -1, rd_gen = -1;
@@ -2533,8 +2537,13 @@ void wro_quantize(const int16_t* coef, int log2n, int qp, int16_t* levels) {
         rd_qp = qp;
         rd_gen = g_extra_gen;
     }
+    g_table_overflow = false;
+    g_table_top = 0;
     quantize(rd, coef, log2n, qp, levels);
+    return g_table_overflow ? -4 : 0;
 }
+// the largest dq_table index the last wro_quantize call asked for (1023 is the last entry)
+long wro_last_table_index(void) { return (long)g_table_top; }
 void wro_quantize_viterbi(const int16_t* coef, int log2n, int qp, int16_t* levels) {
     init_tables();
     static thread_local RdConst rd;

@@ -75,8 +75,11 @@ void wro_debug_last_cost(unsigned long long* ssd, long long* level);
 void wro_fwd_dct(const int16_t* res, int log2n, int16_t* coef);
 // transformer.rs:2380-2737
 void wro_inv_dct(const int16_t* deq, int log2n, int16_t* res);
-// quantizer.rs:519-759 with the literal memoised DFS search_dq (:338-517)
-void wro_quantize(const int16_t* coef, int log2n, int qp, int16_t* levels);
+// quantizer.rs:519-759 with the literal memoised DFS search_dq (:338-517).  Returns 0, or -4 when the search asked
+// dq_table for an entry >= 1024, where the reference panics (quantizer.rs:30); wro_last_table_index: the largest entry
+// that call asked for
+int wro_quantize(const int16_t* coef, int log2n, int qp, int16_t* levels);
+long wro_last_table_index(void);
 // same result via backward 4-state Viterbi; used to prove the
 // equivalence the GPU kernel relies on
 void wro_quantize_viterbi(const int16_t* coef, int log2n, int qp, int16_t* levels);

@@ -32,9 +32,9 @@ def enc_at(built):
         e.close()
 
 
-def _trellis_blocks(rng, n, count, big):
-    """Decaying spectra at four scales, zero blocks, +-3 noise, a lone DC, a lone last coefficient; `big`: coefficients up
-    to the i16 range (levels beyond the 1024-entry tables are the caller's to avoid: QP >= 30 keeps them inside)."""
+def _trellis_blocks(rng, n, count):
+    """Decaying spectra at four scales, zero blocks, +-3 noise, a lone DC, a lone last coefficient (coefficients up to the
+    i16 range, at every QP: tests/test_gpu_quant_bounds.py)."""
     decay = np.exp(-np.add.outer(np.arange(n), np.arange(n)) / (n / 3.0))
     blocks = []
     for it in range(count):
@@ -49,9 +49,6 @@ def _trellis_blocks(rng, n, count, big):
         if it % 17 == 5:
             b[:] = 0
             b[n - 1, n - 1] = [2, -700][it % 2]
-        if big and it % 19 == 3:
-            b[0, 0] = [32767, -32768][it % 2]
-            b[n - 1, 0] = [-32768, 32767][it % 2]
         blocks.append(b)
     return np.stack(blocks)
 
@@ -129,7 +126,7 @@ def test_quantize_trellis_at_every_qp_class(enc_at, qp):
     e = enc_at(qp)
     rng = np.random.default_rng(4000 + qp)
     for n in (4, 8, 16, 32):
-        blocks = _trellis_blocks(rng, n, 24, big=False)
+        blocks = _trellis_blocks(rng, n, 24)
         if qp >= 37:  # 32767 / step stays below 1024 levels from here on (step = lsc / 2^sh grows with the QP)
             blocks[3, 0, 0] = 32767
             blocks[4, n - 1, n - 1] = -32768
@@ -200,7 +197,7 @@ def test_packed_quantisers_at_other_qps(enc_at, qp):
     from oracle import pyoracle as po
     e = enc_at(qp)
     rng = np.random.default_rng(5000 + qp)
-    b4 = _trellis_blocks(rng, 4, 41, big=False)
+    b4 = _trellis_blocks(rng, 4, 41)
     got, cost = e.quantize_p16(b4)
     for i in range(b4.shape[0]):
         ref = po.quantize(b4[i], qp)
@@ -209,8 +206,8 @@ def test_packed_quantisers_at_other_qps(enc_at, qp):
     for log2n, nc in ((3, 3), (3, 2), (4, 2), (4, 1)):
         n, nch = 1 << log2n, 1 << (log2n - 1)
         n_packs = 12
-        luma = _trellis_blocks(rng, n, n_packs * nc, big=False)
-        chroma = _trellis_blocks(rng, nch, n_packs * 2 * nc, big=False)
+        luma = _trellis_blocks(rng, n, n_packs * nc)
+        chroma = _trellis_blocks(rng, nch, n_packs * 2 * nc)
         packs = [np.concatenate([b.ravel() for b in list(luma[p * nc:(p + 1) * nc]) + list(chroma[p * 2 * nc:(p + 1) * 2 * nc])])
                  for p in range(n_packs)]
         levels, cost = e.quantize_pk(np.stack(packs), log2n, nc)

@@ -980,6 +980,21 @@ int run_block_test(wrenc_gpu_ctx* ctx, const int16_t* in, int log2n, int count, 
     if (e != hipSuccess) return fail(ctx, WRENC_GPU_EHIP, hipGetErrorString(e));
     return WRENC_GPU_OK;
 }
+
+// the quantiser test entries' own overflow word (d_overflow[1]), read once the entry's kernel has finished and cleared
+// again whatever `rc`, the entry's status so far, is: the call that raised it fails with WRENC_GPU_ELEVEL -- or with the
+// earlier failure `rc` names --, and the next call on the context starts clean either way
+// (include/wrenc_gpu.h: "keep a word of their own and never poison a context")
+int take_test_overflow(wrenc_gpu_ctx* ctx, int rc) {
+    int ovf = 0;
+    hipError_t e = hipMemcpyAsync(&ovf, ctx->d_overflow + 1, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(ctx->d_overflow + 1, 0, sizeof(int), ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (rc != WRENC_GPU_OK) return rc;
+    if (e != hipSuccess) return fail(ctx, WRENC_GPU_EHIP, hipGetErrorString(e));
+    if (!ovf) return WRENC_GPU_OK;
+    return fail(ctx, WRENC_GPU_ELEVEL, "a quantised level reached 1024 (reference panics: block_splitter.rs:453)");
+}
 } // namespace
 
 extern "C" {
@@ -2140,7 +2155,7 @@ int wrenc_gpu_test_quantize(wrenc_gpu_ctx* ctx, const int16_t* coef, int log2n, 
         if (e != hipSuccess) rc = fail(ctx, WRENC_GPU_EHIP, hipGetErrorString(e));
     }
     (void)hipFree(d_cost);
-    return rc;
+    return take_test_overflow(ctx, rc);
 }
 
 int wrenc_gpu_test_quantize_p16(wrenc_gpu_ctx* ctx, const int16_t* coef, int count, int16_t* levels, int64_t* level_cost) {
@@ -2158,7 +2173,7 @@ int wrenc_gpu_test_quantize_p16(wrenc_gpu_ctx* ctx, const int16_t* coef, int cou
         if (e != hipSuccess) rc = fail(ctx, WRENC_GPU_EHIP, hipGetErrorString(e));
     }
     (void)hipFree(d_cost);
-    return rc;
+    return take_test_overflow(ctx, rc);
 }
 
 int wrenc_gpu_test_quantize_pk(wrenc_gpu_ctx* ctx, const int16_t* coef, int log2n, int nc, int n_packs, int16_t* levels,
@@ -2185,8 +2200,7 @@ int wrenc_gpu_test_quantize_pk(wrenc_gpu_ctx* ctx, const int16_t* coef, int log2
     if (d_in) (void)hipFree(d_in);
     if (d_out) (void)hipFree(d_out);
     if (d_cost) (void)hipFree(d_cost);
-    if (e != hipSuccess) return fail(ctx, WRENC_GPU_EHIP, hipGetErrorString(e));
-    return WRENC_GPU_OK;
+    return take_test_overflow(ctx, e != hipSuccess ? fail(ctx, WRENC_GPU_EHIP, hipGetErrorString(e)) : WRENC_GPU_OK);
 }
 
 int wrenc_gpu_test_predict(wrenc_gpu_ctx* ctx, const uint8_t* rec_y, const uint8_t* rec_cb, const uint8_t* rec_cr,
