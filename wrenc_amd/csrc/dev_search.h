@@ -13,8 +13,9 @@ enum { K_SADLIST = 0, K_FULL = 1, K_NOP = 2, K_SADSEARCH = 3, K_CCLMSEARCH = 4, 
 enum { COPY_NONE = 0, COPY_SAVE = 1, COPY_RESTORE = 2, COPY_PULL = 3 };
 
 // Split cut (wave schedule): a node's children are searched only until their partial cost, summed in z-order in f32 from
-// 0.0 as the full sum is (:1116-1123), is strictly greater than the node's unsplit cost.  Every child cost is >= 0 and
-// f32 addition is monotone in either operand, so every later partial sum, the final one included, is >= this one: the
+// 0.0 as the full sum is (:1116-1123), with every child still to come counted at its floor (split_floor_cut below), is
+// strictly greater than the node's unsplit cost.  Every child costs at least its floor, every floor is >= 0 and f32
+// addition is monotone in either operand, so the final sum is >= this bound: the
 // comparison of :1125-1145 is decided (a tie would still go to the split, so equality searches on), the unsplit
 // candidate is restored over the whole node exactly as after the last child, and what the skipped children would have
 // written is never read.  Off in the trace build, which exists to pin the candidates that lose (tests/test_gpu_trace.py),
@@ -1596,12 +1597,36 @@ __device__ __forceinline__ void fill_maps(int bx, int by, int lg, int luma_mode,
 }
 
 
+// Split cut, the check before a child is searched: the partial cost of the children searched so far, then the floor
+// of every child still to come (DevConst::split_floor: `n` children of floor index `fi`, then the chroma leaf's if
+// `chroma`) added one by one in z-order, exactly where the full sum adds that child's cost.  Each floor is <= the cost
+// it stands for and f32 addition is monotone in either operand, so the full sum is >= this bound whatever the
+// children hold: a bound strictly greater than the unsplit cost means the split has lost (a tie is a split).  Never a
+// sum of floors formed on its own and never a budget taken off the unsplit cost: f32 addition is not associative, and
+// only this order is the order of the sum the bound stands for.  With no child left it is the plain comparison.
+// *bound = the bound where it cut: it loses the comparison the caller makes next and is never used as a cost.
+// The floors are read from the constant block here, at the check, not carried through the searches as scalars; the
+// adds run on the vector unit (no scalar f32 add on gfx950) and the branch is scalar (uni_f).
+__device__ __forceinline__ bool split_floor_cut(const Ctx& c, float partial, int n, int fi, bool chroma, float unsplit,
+                                                float* bound) {
+    if (!kSplitCut) return false;
+    float b = partial;
+    const float f = c.k->split_floor[fi];
+    for (int i = 0; i < n; ++i) b = b + f;
+    if (chroma) b = b + c.k->split_floor[1];
+    b = uni_f(b);
+    if (!(b > unsplit)) return false;
+    *bound = b;
+    return true;
+}
+
 // K_SPLIT8: the split candidate of an 8x8 CU (ctu.rs:1990-2063: four DUAL_TREE_LUMA 4x4 CUs, then the DUAL_TREE_CHROMA
 // CU) in ONE request: leaf4_search four times, leafc4_search once, with what the tree walk did between them -- the
 // leaf's originals staged, the decision maps filled (the chroma leaf's DM mode is the luma mode of the 4x4 covering
 // the parent's centre, block_splitter.rs:795-805), the costs summed in z-order in f32 from 0.0 (:1116-1123).  Five control
 // steps of 3-6 k cycles each fewer per 8x8 node, 80 per CTU at max-split-depth 3.
-// The leaves after the one at which the running cost exceeds q.fcur, the node's unsplit cost, are not searched (kSplitCut).
+// The leaves from the one on before which the split has lost against q.fcur, the node's unsplit cost, are not searched (kSplitCut).
+// The check runs before every leaf, the first one included, with the leaves still to come at their floors (split_floor_cut).
 // (Only the kernels built for max-split-depth 3 contain it, D3 below: inlined into the one evaluator of a kernel that also
 // serves depth 2, which never splits an 8x8, it cost that depth 2.5 %; as an out-of-line function it cost both depths more.)
 __device__ __forceinline__ Res split8_search(const Ctx& c, const Req& q, int* overflow) {
@@ -1626,6 +1651,12 @@ __device__ __forceinline__ Res split8_search(const Ctx& c, const Req& q, int* ov
         ql.refs1 = false;
         ql.n = 3;
         ql.tree = TREE_DUAL_LUMA;
+        if (split_floor_cut(c, split8, 4 - i8, 0, true, q.fcur, &r.vmin)) { // (before the first leaf: the split is skipped whole)
+            PROF_ADD2(PH_CUT + 0, 0, 4 - i8);
+            PROF_ADD2(PH_CUT + 1, 0, 1);
+            PROF_ADD2(PH_CUT + 4, 0, split8 > q.fcur ? 0 : 1);
+            return r;
+        }
         PROF_MARK(l4g0_);
         stage_org_leaf(c, 1, ql.tx, ql.ty, 2);
         PROF_MARK(l4g1_);
@@ -1633,14 +1664,11 @@ __device__ __forceinline__ Res split8_search(const Ctx& c, const Req& q, int* ov
         const Res rl = leaf4_search(c, ql, overflow);
         fill_maps(ql.tx, ql.ty, 2, rl.imin, 0, true, false);
         split8 = uni_f(split8 + rl.vmin);
-        // the split has lost (kSplitCut above; strictly greater: a tie is a split): T_SPLIT8 restores the unsplit
-        // candidate over the whole node, the maps and the tile of the leaves that did run included
-        if (kSplitCut && split8 > q.fcur) {
-            PROF_ADD2(PH_CUT + 0, 0, 3 - i8);
-            PROF_ADD2(PH_CUT + 1, 0, 1);
-            r.vmin = split8;
-            return r;
-        }
+    }
+    if (split_floor_cut(c, split8, 0, 0, true, q.fcur, &r.vmin)) {
+        PROF_ADD2(PH_CUT + 1, 0, 1);
+        PROF_ADD2(PH_CUT + 4, 0, split8 > q.fcur ? 0 : 1);
+        return r;
     }
     Req qc = {};
     qc.kind = K_LEAFC4;
@@ -2525,6 +2553,18 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
             }
             WSYNC();
             if (lg > 3 || !D3) { // (an 8x8 node splits at max-split-depth 3 only)
+                // four children at their floors already cost more than the unsplit candidate (split_floor_cut): the split has
+                // lost before its first child.  No child has touched the tile or the maps, which hold the unsplit candidate
+                // as they do for a node at max-split-depth, so there is nothing to save or to restore
+                float bound;
+                if (!TEAM && split_floor_cut(c, 0.0f, 4, 2 + level + 1, false, ns, &bound)) {
+                    PROF_ADD2(PH_CUT + 2 + level, 0, 4);
+                    PROF_ADD2(PH_CUT + 5, 0, 1);
+                    t.pend = 0;
+                    t.ret = ns;
+                    cont = T_RETURN;
+                    break;
+                }
                 t.level = (uint8_t)(level + 1); // descend into child 0 (same top-left corner)
                 cont = T_ENTER;
                 break;
@@ -2662,16 +2702,20 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
                 SH.child[pl] = (uint8_t)ch;
             }
             WSYNC();
-            // the parent's split has lost once its partial cost is strictly greater than its unsplit cost (kSplitCut:
-            // the children still to come add costs >= 0 in f32, which never lowers the sum): no sibling is entered
-            const bool lost = acc > uni_f(SH.ns_cost[pl]);
-            if (ch < 4 && !(kSplitCut && lost)) { // next sibling
+            // the parent's split has lost once its partial cost, with the children still to come at their floors, is
+            // strictly greater than its unsplit cost (split_floor_cut): no sibling is entered.  After the last child
+            // this is the comparison itself (:1125-1145)
+            const float ns_p = uni_f(SH.ns_cost[pl]);
+            float bound;
+            const bool lost = ch < 4 ? split_floor_cut(c, acc, 4 - ch, 2 + level, false, ns_p, &bound) : acc > ns_p;
+            if (ch < 4 && !lost) { // next sibling
                 t.bx = (uint8_t)(pbx + (ch & 1) * (psz >> 1));
                 t.by = (uint8_t)(pby + (ch >> 1) * (psz >> 1));
                 cont = T_ENTER;
                 break;
             }
             PROF_ADD2(PH_CUT + 1 + level, 0, 4 - ch); // (level 2: 8x8 nodes not searched, level 1: 16x16 nodes)
+            PROF_ADD2(PH_CUT + 5, 0, (ch < 4 && !(acc > ns_p)) ? 1 : 0);
             // parent complete: split vs unsplit (:1125-1145)
             t.bx = (uint8_t)pbx;
             t.by = (uint8_t)pby;

@@ -872,8 +872,49 @@ void fill_avail_tab(DevConst& k) {
             }
 }
 
+// DevConst::split_floor (dev_search.h, kSplitCut): lower bounds of what the children of a split cost, from the tables of
+// this config alone.  A leaf costs (float)ssd + lambda * ((float)(level cost + header bits) / 16384) with ssd >= 0.  The
+// level cost is a sum of lv_table entries (block_splitter.rs:415-460) and 0 for a block without levels, so 0 is its
+// greatest lower bound when no entry is negative; the header bits are one entry of the leaf's tree type.  Conversion to
+// f32, the product with a lambda >= 0 and the f32 sum are monotone, so the same expression over the smallest entry is
+// <= every cost of that tree type.  A node returns its unsplit cost or the f32 sum of its children in z-order from 0.0,
+// hence min(the unsplit floor, the children's floors summed the same way); a node at max-split-depth is a leaf.
+// Where the tables prove nothing (a negative lv_table entry or header-bit minimum, a lambda that is not >= 0) every
+// floor is 0.0, which is the sibling rule's own premise that costs are >= 0.
+void fill_split_floors(const wrenc_gpu_config& cfg, DevConst& k) {
+#pragma clang fp contract(off)
+    for (float& f : k.split_floor) f = 0.0f;
+    for (int i = 0; i < 1024; ++i)
+        if (cfg.lv_table[i] < 0) return;
+    if (!(cfg.lambda_rd >= 0.0f) || !(cfg.lambda_rd_chroma >= 0.0f)) return;
+    int64_t dual = INT64_MAX, single = INT64_MAX, chroma = INT64_MAX;
+    for (int cls = 0; cls < 67; ++cls) dual = std::min(dual, cfg.header_bits_luma[1][0][cls]); // (a 4x4 luma leaf is never CCLM)
+    for (int cc = 0; cc < 4; ++cc) {
+        for (int cls = 0; cls < 67; ++cls) single = std::min(single, cfg.header_bits_luma[0][cc][cls]);
+        chroma = std::min(chroma, cfg.header_bits_chroma[cc]);
+    }
+    if (dual < 0 || single < 0 || chroma < 0) return;
+    const auto floor_of = [](float lambda, int64_t bits) {
+        const float f = 0.0f + lambda * ((float)bits / 16384.0f);
+        return f >= 0.0f ? f : 0.0f;
+    };
+    const float f4 = floor_of(cfg.lambda_rd, dual), fc = floor_of(cfg.lambda_rd_chroma, chroma);
+    const float fs = floor_of(cfg.lambda_rd, single);
+    k.split_floor[0] = f4;
+    k.split_floor[1] = fc;
+    for (int level = 2; level >= 0; --level) {
+        float sum = 0.0f;
+        if (level == 2)
+            sum = ((((sum + f4) + f4) + f4) + f4) + fc;
+        else
+            for (int i = 0; i < 4; ++i) sum = sum + k.split_floor[2 + level + 1];
+        k.split_floor[2 + level] = level < cfg.max_split_depth ? std::min(fs, sum) : fs;
+    }
+}
+
 void fill_dev_const(const wrenc_gpu_config& cfg, DevConst& k) {
     memset(&k, 0, sizeof(k));
+    fill_split_floors(cfg, k);
     k.W = cfg.width;
     k.H = cfg.height;
     k.qp = cfg.qp;
