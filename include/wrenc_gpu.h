@@ -241,6 +241,22 @@ typedef struct wrenc_gpu_metrics {
  * and puts it back to "uploaded": ask before re-using the slot).  Changes nothing in the slot. */
 int wrenc_gpu_download_metrics(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_gpu_metrics* out);
 
+/* Complexity read-back: how hard a slot's picture is to code, from its originals alone, BEFORE any search -- what a rate
+ * controller needs to choose the picture's QP (include/wrenc_rate.h).  Over every picture-aligned 8x8 block of a plane
+ * (Y at W x H, Cb and Cr at W/2 x H/2): the unnormalised 2-D 8x8 Hadamard transform (the +-1 matrix) of the 64 samples,
+ * act = sum |coefficient| over the 63 coefficients other than DC (at most 130,560).  satd[p] is the plane's sum of act;
+ * ctu_satd[c] the sum over the 16 luma, 4 Cb and 4 Cr blocks of CTU c (raster order).  Exact integers: the same planes
+ * give the same figures in any slot, any batch size and any run.
+ * n slots in one call; blocking.  Runs on the copy stream behind the slots' uploads and waits for those only: a search
+ * queued or running on other slots goes on meanwhile.  Works on every slot that holds originals ("uploaded" or
+ * "encoded"); WRENC_GPU_ESTATE for a slot never uploaded into, WRENC_GPU_EINVAL for a bad range.  Changes nothing in the
+ * slot. */
+typedef struct wrenc_gpu_complexity {
+    uint64_t satd[3];        /* Y, Cb, Cr */
+    uint32_t* ctu_satd;      /* (width/32)*(height/32) entries, may be NULL */
+} wrenc_gpu_complexity;
+int wrenc_gpu_download_complexity(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_gpu_complexity* out);
+
 /* Host only, no device: PSNR (dB) and SSIM as {Avg, Y, U, V} in wrenc_amd/metrics.py's definitions:
  * plane PSNR 10 log10(255^2 n / sse) (+infinity for sse 0), Avg from the MSE over all samples of the frame,
  * SSIM Avg = (4 Y + U + V) / 6. */

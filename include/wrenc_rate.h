@@ -1,0 +1,67 @@
+/* wrenc_rate.h -- rate control of an all-intra run: the QPs of a batch of pictures from their complexities.
+ *
+ * Host only: no device, no threads, no I/O.  Built into libwrenc_host.so (wrenc_amd/csrc/host/rate_control.cpp).
+ * The caller measures every picture before it is searched (wrenc_gpu_download_complexity, include/wrenc_gpu.h), asks
+ * wrenc_rate_choose for the batch's QPs, searches the pictures at them (wrenc_gpu_set_slot_qp) and reports the bytes of
+ * the pictures' NAL units whenever they become known -- in a pipeline, some batches later.
+ *
+ * Model.  bytes of a picture ~ a * N * (C / N)^b * 2^(-QP / s), N = width * height, C = the picture's weighted plane sum
+ * satd[0] + WRENC_RATE_CHROMA_WEIGHT * (satd[1] + satd[2]).  a, b, s start from a prior fitted on fixed-QP searches
+ * (wrenc_rate_prior; DESIGN.md has the fit); b and s stay, a is replaced by (reported bytes) / (what a = 1 predicted for
+ * them), the older reports counting half as much with every new one.  Below the mean QP of the reports the slope is not
+ * the prior's but a steep one (bytes double every 3 QPs), so a first step towards more bytes is a short one; a report that
+ * lies a QP or more below the earlier ones shows the slope between them, which then replaces the steep one, kept between
+ * it and the prior's s.
+ * Budget of a batch of n pictures: n * target + (target of everything chosen so far - its bytes) * n / window, where the
+ * bytes of a picture chosen but not yet reported are the model's with the current a, and the window is the pictures
+ * still to come including the batch, at most WRENC_RATE_WINDOW: at the end of the run the whole error is due.  No buffer
+ * model (VBV / HRD): the target is the run's total.
+ * QPs.  Pictures are independent, so the batch gets one QP -- or q for its first pictures and q + 1 for the rest, the
+ * split whose predicted bytes come closest to the budget.  Complexity predicts bytes; it never makes a picture's QP differ
+ * from its neighbours' by more than that.  QPs stay within [qp_min, qp_max]; a target out of reach pins the bound.
+ * The same sequence of calls gives the same QPs.
+ */
+#ifndef WRENC_RATE_H
+#define WRENC_RATE_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define WRENC_RATE_CHROMA_WEIGHT 1.0
+#define WRENC_RATE_WINDOW 64
+
+enum wrenc_rate_status { WRENC_RATE_OK = 0, WRENC_RATE_EINVAL = -1 };
+
+typedef struct wrenc_rate wrenc_rate;
+
+typedef struct wrenc_rate_config {
+    int32_t width, height;        /* luma samples */
+    int32_t qp_min, qp_max;       /* 0 <= qp_min <= qp_max <= 63 */
+    int64_t num_pictures;         /* of the run, > 0 */
+    double target_bytes;          /* per picture, > 0 (kbit/s * 1000 / 8 / fps) */
+    double header_bytes;          /* spent outside the pictures (parameter sets): counted against the total */
+} wrenc_rate_config;
+
+/* The prior: bytes ~ a * N * (C / N)^b * 2^(-QP / s).  Any pointer may be NULL. */
+void wrenc_rate_prior(double* a, double* b, double* s);
+
+/* WRENC_RATE_EINVAL for a field outside the ranges above. */
+int wrenc_rate_create(const wrenc_rate_config* cfg, wrenc_rate** out);
+void wrenc_rate_destroy(wrenc_rate* rc);
+
+/* The QPs of the next n pictures (n >= 1) from their plane sums satd[3 * k + p] (wrenc_gpu_complexity::satd of picture
+ * k): qp[k] is q for k < some split and q + 1 from it on.  The pictures count as chosen: their bytes are expected by
+ * wrenc_rate_report in this order. */
+int wrenc_rate_choose(wrenc_rate* rc, int n, const uint64_t* satd, int32_t* qp);
+
+/* The bytes of the n oldest pictures chosen and not yet reported (WRENC_RATE_EINVAL if fewer are outstanding). */
+int wrenc_rate_report(wrenc_rate* rc, int n, const uint64_t* bytes);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* WRENC_RATE_H */

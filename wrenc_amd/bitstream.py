@@ -15,6 +15,8 @@ EXPORTED_SYMBOLS = ("wrenc_bs_picture_bound", "wrenc_bs_write_parameter_sets", "
                     "wrenc_bs_write_picture_tokens", "wrenc_bs_last_slice_data_bits")
 # per-picture QP (include/wrenc_bitstream_qp.h)
 EXPORTED_QP_SYMBOLS = ("wrenc_bs_write_picture_qp", "wrenc_bs_write_picture_tokens_qp")
+# rate control (include/wrenc_rate.h; the Python mirror is wrenc_amd/rate.py)
+EXPORTED_RATE_SYMBOLS = ("wrenc_rate_prior", "wrenc_rate_create", "wrenc_rate_destroy", "wrenc_rate_choose", "wrenc_rate_report")
 
 OK, EINVAL, ENOSPC, EDATA = 0, -1, -2, -3
 

@@ -13,7 +13,11 @@
 // reference does (main.rs:127-133); a failure inside the search or the stream writer (a HIP error, a level
 // that overflows the rate tables, ...) is where the reference panics (block_splitter.rs:453): status 101,
 // Rust's panic status, so that a truncated stream never comes with a success status.  Options the reference does not have: --batch, --threads, --device,
-// --devices (several GPUs of the node, batches in turn), --metrics PATH (PSNR and SSIM of every picture from sums the
+// --devices (several GPUs of the node, batches in turn), --bitrate KBPS [--fps N] (rate control: every batch is measured
+// on the device before its search, wrenc_gpu_download_complexity, and include/wrenc_rate.h chooses its QPs -- one, or two
+// adjacent ones -- for a total of KBPS * 1000 / 8 / fps bytes per picture, parameter sets included; --qp stays the
+// parameter sets' QP; the bytes depend on the input and the options alone, not on --threads or timing, which is why
+// --ramp-down auto, decided by the clock, runs as never), --metrics PATH (PSNR and SSIM of every picture from sums the
 // device takes of the originals and the reconstruction it holds, wrenc_gpu_download_metrics: a JSON report in the shape of
 // the reference's evaluation harness, and one summary line on stderr), --verbose, --ramp-down auto|always|never, --tokens auto|on|off
 // (how a batch comes back.  auto and on: as the residual tokens the device makes of it, wrenc_gpu_download_tokens -- the
@@ -40,6 +44,7 @@
 #include "../../../include/wrenc_bitstream.h"
 #include "../../../include/wrenc_bitstream_qp.h"
 #include "../../../include/wrenc_gpu.h"
+#include "../../../include/wrenc_rate.h"
 
 namespace {
 
@@ -140,6 +145,7 @@ struct Options {
     std::vector<int> devices;
     std::vector<int> pic_qp; // --qp-file: the QP of every picture (empty: --qp for all)
     int min_qp = 26;         // the smallest QP of the run
+    double bitrate = 0, fps = 30; // --bitrate (kbit/s, 0: none) and --fps
 };
 
 // --qp-file: whitespace-separated integers 0..63, entry i the QP of picture i, at least one per picture
@@ -169,7 +175,7 @@ std::vector<int> read_qp_file(const char* path, long num_pictures) {
 
 Options parse_options(int argc, char** argv) {
     Options o;
-    const char *in_size = nullptr, *out_size = nullptr, *device_list = nullptr, *qp_file = nullptr;
+    const char *in_size = nullptr, *out_size = nullptr, *device_list = nullptr, *qp_file = nullptr, *bitrate = nullptr, *fps = nullptr;
     int device = 0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -185,6 +191,8 @@ Options parse_options(int argc, char** argv) {
         else if (a == "--num-pictures") o.num_pictures = atol(val());
         else if (a == "--qp") o.qp = atoi(val());
         else if (a == "--qp-file") qp_file = val();
+        else if (a == "--bitrate") bitrate = val();
+        else if (a == "--fps") fps = val();
         else if (a == "--max-split-depth") o.depth = atoi(val());
         else if (a == "--extra-params") o.extra = val();
         else if (a == "--batch") o.batch = atoi(val());
@@ -225,6 +233,17 @@ Options parse_options(int argc, char** argv) {
     if (o.w % 32 || o.h % 32) die("output-size must be a multiple of the 32x32 CTU (picture.rs:178-181): %dx%d", o.w, o.h);
     if (o.qp < 0 || o.qp > 63 || o.depth < 0 || o.depth > 3) die("qp must be 0..63, max-split-depth 0..3");
     o.min_qp = o.qp;
+    const auto positive = [](const char* text, double& v) { // a finite number > 0 and nothing after it
+        char* end = nullptr;
+        v = strtod(text, &end);
+        return end != text && !*end && std::isfinite(v) && v > 0;
+    };
+    if (fps && !positive(fps, o.fps)) die("Invalid fps: %s", fps);
+    if (bitrate) {
+        if (qp_file) die("--bitrate and --qp-file exclude each other: the QPs come from the rate control or from the file");
+        if (!positive(bitrate, o.bitrate)) die("Invalid bitrate: %s (kbit/s, a number above 0)", bitrate);
+        o.ramp_mode = 2; // (auto looks at the clock: the batches, and with them the QPs, must not depend on it)
+    }
     if (qp_file) {
         o.pic_qp = read_qp_file(qp_file, o.num_pictures);
         o.pic_qp.resize((size_t)o.num_pictures);
@@ -370,10 +389,50 @@ struct Run {
           seekable(fin != stdin && lseek(fileno(fin), 0, SEEK_CUR) != (off_t)-1),
           n_readers(seekable ? (o.n_threads < 8 ? o.n_threads : 8) : 1), pool(o.n_threads) {}
 
-    // --qp-file: the config of every QP of the file other than --qp (indexed by QP), built once by main()
+    // the config of every QP in use other than --qp (indexed by QP), resolved as the contexts' config was: --qp-file's by
+    // main(), --bitrate's when the rate control first chooses the QP
     std::vector<const wrenc_gpu_config*> qcfg = std::vector<const wrenc_gpu_config*>(64, nullptr);
+    std::vector<wrenc_gpu_config> qcfg_store;
 
-    int slice_qp(long picture) const { return o.pic_qp.empty() ? o.qp : o.pic_qp[(size_t)picture]; }
+    const wrenc_gpu_config* config_of(int q) {
+        if (q == o.qp || qcfg[(size_t)q]) return qcfg[(size_t)q];
+        if (qcfg_store.empty()) qcfg_store.resize(64);
+        wrenc_gpu_config& c = qcfg_store[(size_t)q];
+        if (wrenc_gpu_default_config(&c, o.w, o.h, q, o.depth)) fatal("%s", wrenc_gpu_last_error(nullptr));
+        if (o.extra && wrenc_gpu_config_extra_params(&c, o.extra)) fatal("%s", wrenc_gpu_last_error(nullptr));
+        return qcfg[(size_t)q] = &c;
+    }
+
+    // --bitrate: the controller, the QP it chose for every picture so far (sized once: the slice threads read it), and
+    // the batch whose slices are being written (flushed, and so reported, before the next batch's QPs are chosen)
+    wrenc_rate* rate = nullptr;
+    std::vector<int> rate_qp;
+    std::vector<wrenc_gpu_complexity> cplx;
+    std::vector<uint64_t> rate_words;
+    HostSet* pending = nullptr;
+
+    int slice_qp(long picture) const { return rate ? rate_qp[(size_t)picture] : (o.pic_qp.empty() ? o.qp : o.pic_qp[(size_t)picture]); }
+
+    // The QPs of the unit's uploaded batch: measured on the device while the other unit's search keeps it busy, chosen
+    // with every byte count known by now, set slot by slot.
+    void choose_qps(HostSet& s) {
+        cplx.assign((size_t)s.count, wrenc_gpu_complexity{});
+        gpu_check(s, wrenc_gpu_download_complexity(s.ctx, s.base, s.count, cplx.data()));
+        if (pending) {
+            flush(*pending);
+            pending = nullptr;
+        }
+        rate_words.resize((size_t)s.count * 3);
+        for (int k = 0; k < s.count; ++k)
+            for (int p = 0; p < 3; ++p) rate_words[(size_t)(3 * k + p)] = cplx[(size_t)k].satd[p];
+        std::vector<int32_t> qps((size_t)s.count);
+        if (wrenc_rate_choose(rate, s.count, rate_words.data(), qps.data())) fatal("rate control: choose failed");
+        for (int k = 0; k < s.count; ++k) {
+            rate_qp[(size_t)(poc + k)] = qps[(size_t)k];
+            gpu_check(s, wrenc_gpu_set_slot_qp(s.ctx, s.base + k, config_of(qps[(size_t)k])));
+        }
+        if (o.verbose) fprintf(stderr, "  batch at picture %ld: QP %d .. %d\n", poc, (int)qps.front(), (int)qps.back());
+    }
 
     void upload(HostSet& s, int k) {
         // the slot's QP first: the encode call of the batch reads it (NULL: the context's, --qp)
@@ -432,6 +491,7 @@ struct Run {
                 upload(s, k);
             }
         }
+        if (s.count && rate) choose_qps(s);
         if (s.count) gpu_check(s, wrenc_gpu_encode(s.ctx, s.base, s.count));
         poc += s.count;
     }
@@ -525,6 +585,10 @@ struct Run {
             bytes += s.len[(size_t)k];
             if (o.metrics) pic_bytes.push_back(s.len[(size_t)k]);
             if (frec) fwrite(s.rec + g.pic * k, 1, g.pic, frec); // main.rs:387-399
+        }
+        if (rate && s.bs_count > 0) { // the bytes of the batch's NAL units, in the order its QPs were chosen
+            rate_words.assign(s.len.begin(), s.len.begin() + s.bs_count);
+            if (wrenc_rate_report(rate, s.bs_count, rate_words.data())) fatal("rate control: report failed");
         }
         pictures += s.bs_count;
     }
@@ -631,20 +695,25 @@ int main(int argc, char** argv) {
 
     const auto t_start = std::chrono::steady_clock::now();
     Run run(o, g, fin, fout, frec, per_dev);
-    std::vector<wrenc_gpu_config> qcfgs(o.pic_qp.empty() ? 0 : 64); // --qp-file: resolved as the contexts' config was
-    for (int q : o.pic_qp) {
-        if (q == o.qp || run.qcfg[(size_t)q]) continue;
-        wrenc_gpu_config& c = qcfgs[(size_t)q];
-        if (wrenc_gpu_default_config(&c, o.w, o.h, q, o.depth)) fatal("%s", wrenc_gpu_last_error(nullptr));
-        if (o.extra && wrenc_gpu_config_extra_params(&c, o.extra)) fatal("%s", wrenc_gpu_last_error(nullptr));
-        run.qcfg[(size_t)q] = &c;
+    for (int q : o.pic_qp) run.config_of(q); // --qp-file: resolved as the contexts' config was
+    const double target_bytes = o.bitrate * 1000.0 / 8.0 / o.fps;
+    if (o.bitrate > 0 && o.num_pictures > 0) {
+        // --extra-params can push the quantiser's rate model out of the device's 32-bit range at high QPs (lambda_q grows
+        // with the QP: wrenc_gpu_set_slot_qp refuses those): the rate control stays below the first QP that does not fit
+        int qp_max = 63;
+        while (qp_max > o.qp && wrenc_gpu_set_slot_qp(ctxs[0], 0, run.config_of(qp_max)) == WRENC_GPU_EINVAL) --qp_max;
+        if (wrenc_gpu_set_slot_qp(ctxs[0], 0, nullptr)) fatal("%s", wrenc_gpu_last_error(ctxs[0]));
+        const wrenc_rate_config rcfg = {o.w, o.h, 0, qp_max, (int64_t)o.num_pictures, target_bytes, (double)hdr_bytes};
+        if (wrenc_rate_create(&rcfg, &run.rate)) fatal("rate control: bad configuration");
+        run.rate_qp.assign((size_t)o.num_pictures, o.qp);
+        if (o.verbose) fprintf(stderr, "rate control: %.1f kbit/s at %.3g pictures/s = %.1f bytes per picture, QP 0 .. %d\n", o.bitrate, o.fps, target_bytes, qp_max);
     }
     // Fill every unit, then go round: read the oldest batch back (waits for its search only), collect the
     // slices of the batch before it (written meanwhile), start this batch's slices, and give the unit the next
     // batch.  With --reconst the planes of a batch are written out before its unit is read back into again.
     for (HostSet& s : units)
         if (run.poc < o.num_pictures) run.submit(s);
-    HostSet* pending = nullptr;
+    HostSet*& pending = run.pending;
     // --verbose: where the main thread spends the run (waiting for slices, for the search + read-back, reading + uploading)
     double t_flush = 0, t_readback = 0, t_submit = 0;
     int n_token_batches = 0;
@@ -692,6 +761,12 @@ int main(int argc, char** argv) {
     if (frec) fclose(frec);
     if (fout != stdout) fclose(fout);
     if (o.metrics) write_metrics_report(run, o.metrics, run.bytes + hdr_bytes);
+    if (o.verbose && run.rate && run.pictures > 0) {
+        const double total = (double)(run.bytes + hdr_bytes), want = target_bytes * (double)run.pictures;
+        fprintf(stderr, "rate control: target %.1f kbit/s, achieved %.1f kbit/s (%.0f of %.0f bytes, ratio %.4f)\n", o.bitrate,
+                total / (double)run.pictures * 8.0 * o.fps / 1000.0, total, want, total / want);
+    }
+    wrenc_rate_destroy(run.rate);
     if (o.verbose) {
         const double dt = since(t_start);
         fprintf(stderr, "%ld pictures, %llu bytes, %.2f s, %.1f pictures/s (file to stream, %d GPU context(s), %d host threads)\n",

@@ -42,3 +42,4 @@
 #define WRENC_TOKENS_KERNEL_TU
 #include "dev_bins.h"
 #include "dev_metrics.h"
+#include "dev_complexity.h"

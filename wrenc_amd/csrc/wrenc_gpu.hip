@@ -680,6 +680,11 @@ struct wrenc_gpu_ctx {
     MetricsPartial* d_mpartial = nullptr;
     MetricsSums* d_msums = nullptr;
     int metrics_cap = 0; // pictures the scratch holds
+    // complexity read-back: the waves' triples, the pictures' totals and CTU maps of one call, for every slot at once
+    // (allocated on first use and never again: a later call must not free device memory under a search in flight)
+    ComplexityPartial* d_xpartial = nullptr;
+    ComplexityPartial* d_xsums = nullptr;
+    uint32_t* d_xmap = nullptr;
     int schedule = WRENC_GPU_SCHEDULE_AUTO;
     int last_schedule = WRENC_GPU_SCHEDULE_WAVE; // what the most recent encode call ran
     bool stats_valid = false;
@@ -1212,6 +1217,9 @@ void wrenc_gpu_destroy(wrenc_gpu_ctx* ctx) {
     if (ctx->d_ccount) (void)hipFree(ctx->d_ccount);
     if (ctx->d_mpartial) (void)hipFree(ctx->d_mpartial);
     if (ctx->d_msums) (void)hipFree(ctx->d_msums);
+    if (ctx->d_xpartial) (void)hipFree(ctx->d_xpartial);
+    if (ctx->d_xsums) (void)hipFree(ctx->d_xsums);
+    if (ctx->d_xmap) (void)hipFree(ctx->d_xmap);
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
     if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
@@ -1797,6 +1805,38 @@ int wrenc_gpu_download_metrics(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_
     HIP_TRY(ctx, hipMemcpyAsync(sums.data(), ctx->d_msums, (size_t)n * sizeof(MetricsSums), hipMemcpyDeviceToHost, cs));
     if (const int rc = read_overflow(ctx)) return rc;
     for (int k = 0; k < n; ++k) fill_metrics(c, sums[(size_t)k], out[k]);
+    return WRENC_GPU_OK;
+}
+
+int wrenc_gpu_download_complexity(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_gpu_complexity* out) {
+    if (!ctx || !out) return WRENC_GPU_EINVAL;
+    const wrenc_gpu_config& c = ctx->cfg;
+    if (first_slot < 0 || n < 1 || first_slot + n > c.n_slots) return fail(ctx, WRENC_GPU_EINVAL, "slot range out of bounds");
+    for (int s = first_slot; s < first_slot + n; ++s)
+        if (ctx->state[s] == 0) return fail(ctx, WRENC_GPU_ESTATE, "slot has no uploaded picture");
+    HIP_TRY(ctx, hipSetDevice(c.device));
+    const size_t per_pic = (size_t)cplx_waves(c.width, c.height), n_ctus = (size_t)ctx->ctu_cols * ctx->ctu_rows;
+    if (!ctx->d_xmap) {
+        HIP_TRY(ctx, realloc_scratch(ctx->d_xpartial, (size_t)c.n_slots * per_pic * sizeof(ComplexityPartial)));
+        HIP_TRY(ctx, realloc_scratch(ctx->d_xsums, (size_t)c.n_slots * sizeof(ComplexityPartial)));
+        HIP_TRY(ctx, realloc_scratch(ctx->d_xmap, (size_t)c.n_slots * n_ctus * sizeof(uint32_t)));
+    }
+    // on the copy stream: behind the slots' uploads (queued there) and behind no search -- the pass reads the originals only,
+    // which a search of the same slot reads too and nothing but an upload writes
+    hipStream_t cs = ctx->copy_stream;
+    const size_t waves = (size_t)n * per_pic;
+    hipLaunchKernelGGL(complexity_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, cs, ctx->d_slots, first_slot, n, c.width,
+                       c.height, ctx->d_xpartial, ctx->d_xmap);
+    hipLaunchKernelGGL(complexity_finish_kernel, dim3(n), dim3(64), 0, cs, ctx->d_xpartial, c.width, c.height, ctx->d_xsums);
+    HIP_TRY(ctx, hipGetLastError());
+    std::vector<ComplexityPartial> sums((size_t)n);
+    HIP_TRY(ctx, hipMemcpyAsync(sums.data(), ctx->d_xsums, (size_t)n * sizeof(ComplexityPartial), hipMemcpyDeviceToHost, cs));
+    for (int k = 0; k < n; ++k)
+        if (out[k].ctu_satd)
+            HIP_TRY(ctx, hipMemcpyAsync(out[k].ctu_satd, ctx->d_xmap + (size_t)k * n_ctus, n_ctus * sizeof(uint32_t), hipMemcpyDeviceToHost, cs));
+    HIP_TRY(ctx, hipStreamSynchronize(cs));
+    for (int k = 0; k < n; ++k)
+        for (int p = 0; p < 3; ++p) out[k].satd[p] = sums[(size_t)k].satd[p];
     return WRENC_GPU_OK;
 }
 

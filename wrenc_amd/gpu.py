@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("WRENC_GPU_LIB", os.path.join(_HERE, "csrc", "libwrenc
 
 EXPORTED_SYMBOLS = [
     "wrenc_gpu_default_config", "wrenc_gpu_config_extra_params", "wrenc_gpu_create", "wrenc_gpu_destroy", "wrenc_gpu_last_error",
-    "wrenc_gpu_upload", "wrenc_gpu_encode", "wrenc_gpu_set_slot_qp", "wrenc_gpu_sync", "wrenc_gpu_download", "wrenc_gpu_download_compact", "wrenc_gpu_compact_mask_words", "wrenc_gpu_expand_levels", "wrenc_gpu_download_tokens", "wrenc_gpu_download_metrics", "wrenc_gpu_metrics_values", "wrenc_gpu_test_metrics", "wrenc_gpu_test_load_record", "wrenc_gpu_device_info",
+    "wrenc_gpu_upload", "wrenc_gpu_encode", "wrenc_gpu_set_slot_qp", "wrenc_gpu_sync", "wrenc_gpu_download", "wrenc_gpu_download_compact", "wrenc_gpu_compact_mask_words", "wrenc_gpu_expand_levels", "wrenc_gpu_download_tokens", "wrenc_gpu_download_metrics", "wrenc_gpu_download_complexity", "wrenc_gpu_metrics_values", "wrenc_gpu_test_metrics", "wrenc_gpu_test_load_record", "wrenc_gpu_device_info",
     "wrenc_gpu_alloc_host", "wrenc_gpu_free_host", "wrenc_gpu_encode_picture", "wrenc_gpu_set_schedule", "wrenc_gpu_last_schedule", "wrenc_gpu_stats_enable", "wrenc_gpu_last_encode_stats", "wrenc_gpu_last_encode_kernel_stats", "wrenc_gpu_final_pass_mismatches",
     "wrenc_gpu_test_fwd_dct", "wrenc_gpu_test_inv_dct", "wrenc_gpu_test_quantize",
     "wrenc_gpu_test_dequantize", "wrenc_gpu_test_predict", "wrenc_gpu_test_fwd_dct32", "wrenc_gpu_test_inv_dct32", "wrenc_gpu_test_quantize_p16", "wrenc_gpu_test_quantize_pk", "wrenc_gpu_test_set_wave_slots", "wrenc_gpu_test_scratch_overflows", "wrenc_gpu_test_head_ranges", "wrenc_gpu_test_avail_tab",
@@ -62,6 +62,10 @@ TOKEN_PAGE = 64  # WRENC_GPU_TOKEN_PAGE
 
 class Metrics(C.Structure):
     _fields_ = [("sse", C.c_uint64 * 3), ("ssim_sum", C.c_double * 3), ("ssim_windows", C.c_uint32 * 3)]
+
+
+class Complexity(C.Structure):
+    _fields_ = [("satd", C.c_uint64 * 3), ("ctu_satd", C.c_void_p)]
 
 
 def metrics_values(width, height, m):
@@ -284,6 +288,17 @@ class Encoder:
         self.lib.wrenc_gpu_download_metrics.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         self._check(self.lib.wrenc_gpu_download_metrics(self.ctx, first_slot, n, outs))
         return [metrics_values(self.width, self.height, outs[k]) for k in range(n)]
+
+    def download_complexity(self, first_slot, n, ctu_map=True):
+        """Hadamard activity of n slots' originals (include/wrenc_gpu.h, wrenc_gpu_download_complexity), before or after
+        their search: per picture {"satd": [Y, Cb, Cr], "ctu_satd": (h/32, w/32) uint32 array or None}."""
+        outs = (Complexity * max(n, 1))()
+        maps = [np.zeros((self.height // 32, self.width // 32), np.uint32) if ctu_map else None for _ in range(max(n, 0))]
+        for k, m in enumerate(maps):
+            outs[k].ctu_satd = _p(m).value if m is not None else None
+        self.lib.wrenc_gpu_download_complexity.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        self._check(self.lib.wrenc_gpu_download_complexity(self.ctx, first_slot, n, outs))
+        return [{"satd": [int(v) for v in outs[k].satd], "ctu_satd": maps[k]} for k in range(n)]
 
     def test_metrics(self, org, rec, maps=False):
         """Test entry: the metrics kernel on two arbitrary pictures (y, cb, cr) of the context's size.  Returns the entry of
