@@ -55,7 +55,11 @@ enum wrenc_gpu_status {
  * keep a word of their own and never poison a context: wrenc_gpu_test_quantize / _quantize_p16 / _quantize_pk return
  * WRENC_GPU_ELEVEL from the call whose blocks raised it (the levels and costs they wrote are then those of table
  * indices clamped to 1023, not the reference's) and clear the word on every return path, so the next call on the
- * context starts clean. */
+ * context starts clean.
+ * Only a candidate that is evaluated can raise WRENC_GPU_ELEVEL.  The wave schedule does not evaluate what cannot change
+ * the result: the children of a split that has already lost, and, in a 4x4 luma leaf, the SAD search's candidates where
+ * their header bits alone already cost as much as the best of {planar, DC}.  A candidate whose levels would have reached
+ * 1024 and that is skipped this way raises nothing; the team schedule and the trace build evaluate everything. */
 
 /* Resolved configuration.  The RD-model constants are resolved on the host
  * (libm pow/powf, exactly as block_splitter.rs:29-53,187-375 and

@@ -30,6 +30,9 @@ CUTS = ["cut_leaf4", "cut_leafc4", "cut_node16", "cut_node8"]
 # ... and the cuts only the floors decided, the partial sum alone being <= the unsplit cost (split_floor_cut): inside an
 # 8x8 node's split, between the children of a 32x32 / 16x16 node
 FLOOR_CUTS = ["cut_floor_split8", "cut_floor_node"]
+# ... and the searched 4x4 luma leaves whose candidate floors skipped the SAD search and pack B / pack B alone
+# (dev_search.h, kCandidateCut; tools/candidate_floor_model.py gives the same two counts from the oracle's trace)
+CAND_CUTS = ["cut_leaf4_sad", "cut_leaf4_packB"]
 names = (["predict", "fdct", "q_pre", "q_back", "q_trace", "deq", "idct", "recon", "total", "ctrl", "refs", "skip", "nstep", "nfull"]
          + ["stages_t%d_c%d" % (4 << (i // 2), i % 2) for i in range(8)] + ["x"] + ["stages_n%d_c%d" % (4 << (i // 2), i % 2) for i in range(8)]
          + ["x2", "qb_pre", "qb_wait1", "qb_walk", "qb_wait2", "t_xchg", "copy"] + ["cb%d" % i for i in range(32)] + ["y"]
@@ -39,7 +42,7 @@ names = (["predict", "fdct", "q_pre", "q_back", "q_trace", "deq", "idct", "recon
          + ["leaf8_packA", "leaf8_sad", "leaf8_packB", "leaf8_cclm", "leaf16_packA", "leaf16_sad", "leaf16_packB", "leaf16_packC",
             "sad_tables", "sad_blocks", "sad_samples", "leaf8_cclm_sad", "sad_lines"] + ["y9"]
          + ["leaf4_stage", "leaf4_packA", "leaf4_sad", "leaf4_packB", "leafc4", "split8_other"] + ["y10"] + ["hist%d" % i for i in range(64)]
-         + ["y11"] + CUTS + FLOOR_CUTS)
+         + ["y11"] + CUTS + FLOOR_CUTS + CAND_CUTS)
 KINDS = ["sadlist", "full", "nop/copy", "sadsearch", "cclmsearch", "leaf4", "leafc4", "leaf8", "leaf16", "split8"] + ["?"] * 6
 N = len(names)
 out = (C.c_ulonglong * N)()
@@ -65,6 +68,9 @@ for i, n in enumerate(names):
         continue
     if n in FLOOR_CUTS:
         print("%-16s %10.2f per CTU (cuts the floors decided and the partial sum did not)" % (n, out[i] / nctu))
+        continue
+    if n in CAND_CUTS:
+        print("%-16s %10.2f per CTU (searched 4x4 luma leaves that skipped %s)" % (n, out[i] / nctu, "the SAD search and pack B" if n.endswith("sad") else "pack B alone"))
         continue
     if n.startswith("ev"):
         k = int(n[2:])

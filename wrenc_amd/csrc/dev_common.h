@@ -57,6 +57,12 @@ struct DevConst {
     // [0] a DUAL_TREE_LUMA 4x4 leaf, [1] the DUAL_TREE_CHROMA leaf, [2 + level] a node at tree level 0 .. 2 (32x32,
     // 16x16, 8x8).  All 0.0 where the tables prove nothing.
     float split_floor[5];
+    // Candidate floors of a 4x4 DUAL_TREE_LUMA leaf (dev_search.h, kCandidateCut; fill_split_floors): per mode class what a
+    // candidate of that class costs with no distortion and no levels, rd_cost(0, hb_luma[1][0][cls], lambda_rd), and the
+    // smallest of them over the classes 2 .. 66 (mpm_idx 1 .. 4 and every remainder, which only angular modes can have).
+    // All -inf where the tables prove nothing: a floor of -inf never reaches a cost.
+    float cand_floor[67];
+    float cand_floor_ang;
 };
 
 // Pointers that are loaded from memory (PicBufs) lose their address space; these casts tell the
@@ -463,7 +469,7 @@ __device__ __forceinline__ Ctx uni(Ctx c) {
 // Diagnostic build only (-DWRENC_PROFILE): per-phase cycle counters, summed per wave and
 // added to a global table at CTU end.  Never compiled into the product library.
 #ifdef WRENC_PROFILE
-enum { PH_PREDICT, PH_FDCT, PH_QPRE, PH_QBACK, PH_QTRACE, PH_DEQ, PH_IDCT, PH_RECON, PH_TOTAL, PH_CTRL, PH_REFS, PH_SKIP, PH_NSTEP, PH_NFULL, PH_PSZ, PH_PSZ_END = PH_PSZ + 8, PH_PCNT, PH_PCNT_END = PH_PCNT + 8, PH_QB_PRE, PH_QB_WAIT1, PH_QB_WALK, PH_QB_WAIT2, PH_XCHG, PH_COPY, PH_CB, PH_CB_END = PH_CB + 32, PH_CBN, PH_CBN_END = PH_CBN + 32, PH_MEM, PH_MEM_END = PH_MEM + 16, PH_ST, PH_ST_END = PH_ST + 48, PH_STN, PH_STN_END = PH_STN + 12, PH_EV, PH_EV_END = PH_EV + 64, PH_EVN, PH_EVN_END = PH_EVN + 64, PH_QZ, PH_QZ_END = PH_QZ + 4, PH_LEAF, PH_LEAF_END = PH_LEAF + 13, PH_L4, PH_L4_END = PH_L4 + 6, PH_HIST, PH_HIST_END = PH_HIST + 64, PH_CUT, PH_CUT_END = PH_CUT + 6, PH_COUNT }; // PH_HIST: CTU durations, buckets of 2^17 ticks; PH_CUT: children a split cut left unsearched (4x4 luma leaves, chroma leaves, 16x16 nodes, 8x8 nodes), then the cuts that only the floors decided, the partial sum alone being <= the unsplit cost (inside an 8x8 split, between nodes)
+enum { PH_PREDICT, PH_FDCT, PH_QPRE, PH_QBACK, PH_QTRACE, PH_DEQ, PH_IDCT, PH_RECON, PH_TOTAL, PH_CTRL, PH_REFS, PH_SKIP, PH_NSTEP, PH_NFULL, PH_PSZ, PH_PSZ_END = PH_PSZ + 8, PH_PCNT, PH_PCNT_END = PH_PCNT + 8, PH_QB_PRE, PH_QB_WAIT1, PH_QB_WALK, PH_QB_WAIT2, PH_XCHG, PH_COPY, PH_CB, PH_CB_END = PH_CB + 32, PH_CBN, PH_CBN_END = PH_CBN + 32, PH_MEM, PH_MEM_END = PH_MEM + 16, PH_ST, PH_ST_END = PH_ST + 48, PH_STN, PH_STN_END = PH_STN + 12, PH_EV, PH_EV_END = PH_EV + 64, PH_EVN, PH_EVN_END = PH_EVN + 64, PH_QZ, PH_QZ_END = PH_QZ + 4, PH_LEAF, PH_LEAF_END = PH_LEAF + 13, PH_L4, PH_L4_END = PH_L4 + 6, PH_HIST, PH_HIST_END = PH_HIST + 64, PH_CUT, PH_CUT_END = PH_CUT + 8, PH_COUNT }; // PH_HIST: CTU durations, buckets of 2^17 ticks; PH_CUT: children a split cut left unsearched (4x4 luma leaves, chroma leaves, 16x16 nodes, 8x8 nodes), then the cuts that only the floors decided, the partial sum alone being <= the unsplit cost (inside an 8x8 split, between nodes), then the 4x4 luma leaves whose candidate floors skipped the SAD search and pack B / pack B alone (kCandidateCut)
 __device__ unsigned long long g_prof[PH_COUNT];
 __shared__ unsigned long long s_prof[PH_COUNT];
 #define PROF_T0() const unsigned long long prof_t0_ = __builtin_readcyclecounter()

@@ -28,6 +28,21 @@ constexpr bool kSplitCut = false;
 constexpr bool kSplitCut = true;
 #endif
 
+// Candidate cut (wave schedule, leaf4_search): a full candidate of a 4x4 DUAL_TREE_LUMA leaf costs rd_cost(ssd, level cost
+// + hb_luma[1][0][cls], lambda) with ssd >= 0 and level cost >= 0, and its class is known from the MPM list before anything
+// is evaluated.  rd_cost is monotone in both integer arguments for lambda >= 0 (conversion to f32, the product and the
+// sum each are, contraction being off), so rd_cost(0, hb_luma[1][0][cls], lambda) -- DevConst::cand_floor, formed by the
+// host with the same operations -- is <= that candidate's cost.  The leaf takes the first minimum as a running
+// strict-less update, so a candidate whose floor is >= the running best cannot win: it is not evaluated, and the leaf
+// returns what it returns when that candidate loses.  Off in the trace build, which records every candidate, and with
+// -DWRENC_EXHAUSTIVE_CANDIDATES (A/B measurements, tools/README.md); the team and level schedules, whose members run
+// the two halves of a leaf at the same time, stay exhaustive.
+#if defined(WRENC_TRACE) || defined(WRENC_EXHAUSTIVE_CANDIDATES)
+constexpr bool kCandidateCut = false;
+#else
+constexpr bool kCandidateCut = true;
+#endif
+
 struct Req {
     int kind;       // K_SADLIST: predict + SAD of a list of modes (block_splitter.rs:64-108, 476-522);
                     // K_FULL: predict .. reconstruct (:146-185); K_SADSEARCH: the whole SAD part of a leaf search in
@@ -886,7 +901,20 @@ __device__ __forceinline__ Res leaf4_search(const Ctx& c, const Req& q, int* ove
         PROF_MARK(l4a1_);
         PROF_ADD2(PH_L4 + 1, l4a0_, l4a1_);
     }
-    if (q.n & 2) {
+    // Candidate cut (kCandidateCut): where this wave has pack A's best before the rest of the search starts.  Every
+    // angular candidate costs at least the smallest floor an angular mode's class can have under this MPM list: mpm_idx
+    // 1 .. 4 and the remainders always (cand_floor_ang), mpm_idx 0 where it is not DC, which pack A has evaluated.  With
+    // best <= that floor no later candidate is strictly cheaper: neither the SAD search nor pack B can change the leaf.
+    const bool cut_on_ = kCandidateCut && q.n == 3 && c.solo == 0;
+    bool cut_ = false;
+    if (cut_on_) {
+        float fa = c.k->cand_floor_ang;
+        const float f1 = c.k->cand_floor[1];
+        if (mpl_.k0 > DC && f1 < fa) fa = f1;
+        cut_ = uni((int)(best <= fa)) != 0; // (every lane holds the same scalars: a scalar branch)
+        if (cut_) PROF_ADD2(PH_CUT + 6, 0, 1);
+    }
+    if ((q.n & 2) && !cut_) {
         int cm;
         unsigned smin;
         PROF_MARK(l4s0_);
@@ -896,13 +924,23 @@ __device__ __forceinline__ Res leaf4_search(const Ctx& c, const Req& q, int* ove
         cm = uni(cm);
         // pack B: step_search(mode, 1, _, aux = false) on {cm, cm - 1, cm + 1} (:974)
         const int lo = !(cm < 3) ? cm - 1 : kNoMode, hi = !(cm + 1 > 66) ? cm + 1 : kNoMode;
-        const Pack4Out b = pack4_eval(c, q, 3, cm, lo, hi, overflow);
-        int win_ = -1;
-        LEAF4_CANDIDATE(b, 0, cm);
-        if (lo != kNoMode) LEAF4_CANDIDATE(b, 1, lo);
-        if (hi != kNoMode) LEAF4_CANDIDATE(b, 2, hi);
-        if (row == win_) rec_put(0, q.tx + x, q.ty + y, b.rec);
-        WSYNC();
+        // the same with the real classes of the three candidates: pack B runs unless every candidate it would evaluate
+        // has a floor >= best (a pack of two costs what a pack of three costs, so no part of a pack is cut)
+        if (cut_on_) {
+            const CONST_AS float* const cf = c.k->cand_floor;
+            cut_ = uni((int)(cf[mpm_class_of(mpl_, cm)] >= best && (lo == kNoMode || cf[mpm_class_of(mpl_, lo)] >= best) &&
+                             (hi == kNoMode || cf[mpm_class_of(mpl_, hi)] >= best))) != 0;
+            if (cut_) PROF_ADD2(PH_CUT + 7, 0, 1);
+        }
+        if (!cut_) {
+            const Pack4Out b = pack4_eval(c, q, 3, cm, lo, hi, overflow);
+            int win_ = -1;
+            LEAF4_CANDIDATE(b, 0, cm);
+            if (lo != kNoMode) LEAF4_CANDIDATE(b, 1, lo);
+            if (hi != kNoMode) LEAF4_CANDIDATE(b, 2, hi);
+            if (row == win_) rec_put(0, q.tx + x, q.ty + y, b.rec);
+            WSYNC();
+        }
         PROF_MARK(l4b1_);
         PROF_ADD2(PH_L4 + 3, l4s1_, l4b1_);
     }

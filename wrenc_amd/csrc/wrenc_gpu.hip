@@ -886,9 +886,14 @@ void fill_avail_tab(DevConst& k) {
 // hence min(the unsplit floor, the children's floors summed the same way); a node at max-split-depth is a leaf.
 // Where the tables prove nothing (a negative lv_table entry or header-bit minimum, a lambda that is not >= 0) every
 // floor is 0.0, which is the sibling rule's own premise that costs are >= 0.
+// DevConst::cand_floor (dev_search.h, kCandidateCut) under the same conditions: per mode class of a 4x4 DUAL_TREE_LUMA
+// leaf the expression of rd_cost itself over ssd = 0 and the class's header bits alone, and the smallest of them over
+// the classes only an angular mode can have; -inf where the tables prove nothing or a floor is not finite.
 void fill_split_floors(const wrenc_gpu_config& cfg, DevConst& k) {
 #pragma clang fp contract(off)
     for (float& f : k.split_floor) f = 0.0f;
+    for (float& f : k.cand_floor) f = -INFINITY;
+    k.cand_floor_ang = -INFINITY;
     for (int i = 0; i < 1024; ++i)
         if (cfg.lv_table[i] < 0) return;
     if (!(cfg.lambda_rd >= 0.0f) || !(cfg.lambda_rd_chroma >= 0.0f)) return;
@@ -915,6 +920,16 @@ void fill_split_floors(const wrenc_gpu_config& cfg, DevConst& k) {
             for (int i = 0; i < 4; ++i) sum = sum + k.split_floor[2 + level + 1];
         k.split_floor[2 + level] = level < cfg.max_split_depth ? std::min(fs, sum) : fs;
     }
+    float cand[67], ang = INFINITY;
+    for (int cls = 0; cls < 67; ++cls) {
+        const float lv = (float)cfg.header_bits_luma[1][0][cls] * (1.0f / 16384.0f); // (rd_cost, dev_search.h, term by term)
+        const float prod = cfg.lambda_rd * lv;
+        cand[cls] = (float)0ULL + prod;
+        if (!std::isfinite(cand[cls])) return;
+        if (cls >= 2) ang = std::min(ang, cand[cls]);
+    }
+    memcpy(k.cand_floor, cand, sizeof(cand));
+    k.cand_floor_ang = ang;
 }
 
 void fill_dev_const(const wrenc_gpu_config& cfg, DevConst& k) {
