@@ -54,6 +54,8 @@ size_t wrenc_bs_picture_bound(int width, int height);
  * 00 00 00 00 00 01 prefix).  *len = bytes written (or needed, on WRENC_BS_ENOSPC). */
 int wrenc_bs_write_parameter_sets(int width, int height, int qp, uint8_t* out, size_t cap, size_t* len);
 
+/* The parameter sets of a picture of any even size, coded with a conformance window: include/wrenc_bitstream_window.h. */
+
 /* Picture header NAL + one IDR_W_RADL slice NAL holding every CTU of picture `poc`. */
 int wrenc_bs_write_picture(int width, int height, int qp, int poc, const wrenc_bs_record* rec,
                            uint8_t* out, size_t cap, size_t* len);

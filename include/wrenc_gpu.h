@@ -135,6 +135,27 @@ const char* wrenc_gpu_last_error(const wrenc_gpu_ctx* ctx); /* ctx may be NULL: 
 int wrenc_gpu_upload(wrenc_gpu_ctx* ctx, int slot, const uint8_t* y, const uint8_t* cb,
                      const uint8_t* cr, size_t stride_y, size_t stride_c);
 
+/* Pictures of any even size.  The context's width x height stay the CODED size, whole 32x32 CTUs; a visible size says
+ * that the caller's pictures are vis_w x vis_h: wrenc_gpu_upload then takes planes of vis_w x vis_h and vis_w/2 x vis_h/2
+ * (the stride checks use those widths), copies them into the top-left corner of the slot's planes and a device kernel
+ * behind the copies replicates each plane's last visible column and row into the margin,
+ *     org(x, y) = org(min(x, vis - 1), min(y, vis - 1)) per plane,
+ * so the margin never crosses the bus.  Search, final pass, token pass, compact pass and complexity pass see an ordinary
+ * picture of the coded size: wrenc_gpu_download, _download_compact and _download_tokens keep returning CODED-size maps,
+ * levels and reconstruction (the caller crops the reconstruction), and wrenc_gpu_download_complexity stays over the coded
+ * picture, margin included -- the margin is coded and costs bits, and those figures are rate control's estimate of bits.
+ * wrenc_gpu_download_metrics reports the visible rectangle only (below).  The stream tells a decoder the visible size
+ * by a conformance window: wrenc_bs_write_parameter_sets_window (wrenc_bitstream_window.h).
+ * vis_w and vis_h: even, at least 16 (each chroma plane still holds one SSIM window), and the context's size exactly
+ * the round-up of each to a multiple of 32; else WRENC_GPU_EINVAL.  WRENC_GPU_ESTATE once any slot of the context has
+ * been uploaded into.  Passing the coded size itself puts the context back to the plain behaviour; a context on which
+ * no visible size is set launches nothing it did not launch before. */
+int wrenc_gpu_set_visible_size(wrenc_gpu_ctx* ctx, int vis_w, int vis_h);
+int wrenc_gpu_visible_size(const wrenc_gpu_ctx* ctx, int* w, int* h); /* the coded size when none is set */
+/* Test entry: the coded-size original planes a slot holds (width*height, then (width/2)*(height/2) twice), margin
+ * included.  Blocking, behind the copy stream.  WRENC_GPU_ESTATE for a slot never uploaded into. */
+int wrenc_gpu_test_download_originals(wrenc_gpu_ctx* ctx, int slot, uint8_t* y, uint8_t* cb, uint8_t* cr);
+
 /* Run search + final pass for slots [first_slot, first_slot + n_pictures) whose
  * planes are resident.  Asynchronous.  This is the call a C++ SliceEncoder::encode
  * makes in place of the per-CTU split_ct loop. */
@@ -240,7 +261,12 @@ typedef struct wrenc_gpu_metrics {
     uint32_t ssim_windows[3];  /* (w/4 - 1)(h/4 - 1) of the plane */
 } wrenc_gpu_metrics;
 
-/* n slots in one call; blocking; waits for the encode call that searched them and for nothing queued later.
+/* On a context with a visible size (wrenc_gpu_set_visible_size) the figures are those of the visible rectangle: per plane
+ * of visible size w x h (a chroma width such as 17 is legal), sse over the w x h samples and SSIM over the
+ * ((w >> 2) - 1)((h >> 2) - 1) windows of whole 4x4 blocks inside it -- a partial last block is dropped, as ffmpeg's filter
+ * drops it -- with ssim_windows that count; wrenc_gpu_metrics_values is then called with the visible size.  The order of
+ * summation is fixed there too.
+ * n slots in one call; blocking; waits for the encode call that searched them and for nothing queued later.
  * WRENC_GPU_ESTATE unless every slot is in the encoded state (an upload into a slot replaces its originals
  * and puts it back to "uploaded": ask before re-using the slot).  Changes nothing in the slot. */
 int wrenc_gpu_download_metrics(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_gpu_metrics* out);

@@ -15,6 +15,8 @@ EXPORTED_SYMBOLS = ("wrenc_bs_picture_bound", "wrenc_bs_write_parameter_sets", "
                     "wrenc_bs_write_picture_tokens", "wrenc_bs_last_slice_data_bits")
 # per-picture QP (include/wrenc_bitstream_qp.h)
 EXPORTED_QP_SYMBOLS = ("wrenc_bs_write_picture_qp", "wrenc_bs_write_picture_tokens_qp")
+# pictures of any even size (include/wrenc_bitstream_window.h)
+EXPORTED_WINDOW_SYMBOLS = ("wrenc_bs_write_parameter_sets_window",)
 # rate control (include/wrenc_rate.h; the Python mirror is wrenc_amd/rate.py)
 EXPORTED_RATE_SYMBOLS = ("wrenc_rate_prior", "wrenc_rate_create", "wrenc_rate_destroy", "wrenc_rate_choose", "wrenc_rate_report")
 
@@ -69,6 +71,20 @@ def write_parameter_sets(width, height, qp):
     rc = lib.wrenc_bs_write_parameter_sets(width, height, qp, buf.ctypes.data, buf.size, C.byref(n))
     if rc != OK:
         raise BitstreamError(rc, "wrenc_bs_write_parameter_sets")
+    return buf[:n.value].tobytes()
+
+
+def write_parameter_sets_window(coded_w, coded_h, vis_w, vis_h, qp):
+    """VPS + SPS + PPS of a vis_w x vis_h picture coded at coded_w x coded_h: the SPS carries the conformance window
+    (wrenc_bs_write_parameter_sets_window)."""
+    lib = load_library()
+    buf = np.zeros(4096, np.uint8)
+    n = C.c_size_t()
+    lib.wrenc_bs_write_parameter_sets_window.restype = C.c_int
+    lib.wrenc_bs_write_parameter_sets_window.argtypes = [C.c_int] * 5 + [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    rc = lib.wrenc_bs_write_parameter_sets_window(coded_w, coded_h, vis_w, vis_h, qp, buf.ctypes.data, buf.size, C.byref(n))
+    if rc != OK:
+        raise BitstreamError(rc, "wrenc_bs_write_parameter_sets_window")
     return buf[:n.value].tobytes()
 
 

@@ -14,6 +14,13 @@
 // are neighbours in one strip, so the second read of a row is a cache hit.
 // Every wave leaves one {squared error, sum of window values} pair in a scratch array at its own index and
 // metrics_finish_kernel adds a plane's pairs in index order: no atomics, the same bits in any slot and batch.
+//
+// Window (WIN; a context with a visible size, wrenc_gpu_set_visible_size): the planes keep the coded pitch and the pass
+// measures their top-left vw x vh rectangle, any even size: a chroma plane may be 17 wide.  The dealing is the same with
+// the plane's last group and last block row possibly partial: the 16-byte loads stay inside the coded plane (its pitch is
+// a multiple of 16, its height of 16), samples outside the rectangle are masked to zero in both pictures before the dot
+// products -- they add nothing to the squared error -- and a window counts only where its four blocks are whole.  On a
+// rectangle whose sides are multiples of 16 and 4 the masks are all ones and the sums are those of the plain pass.
 #pragma once
 
 namespace wrenc {
@@ -30,10 +37,12 @@ struct MetricsSums { // per picture: Y, Cb, Cr
     double ssim[3];
 };
 
-// how a plane (chroma = 0 luma, 1 Cb / Cr) of a W x H picture is dealt to waves
+// how a plane (chroma = 0 luma, 1 Cb / Cr) of a W x H picture is dealt to waves (W x H: the size that is measured, whole
+// CTUs or a visible size; the last group and the last block row of a plane may be partial)
 struct MetPlane {
     int pw, ph;    // samples
     int groups;    // 16-sample column groups
+    int brows;     // 4-sample block rows
     int strips, segs, waves;
     int windows;   // (pw / 4 - 1)(ph / 4 - 1)
 };
@@ -41,9 +50,10 @@ __host__ __device__ inline MetPlane met_plane(int W, int H, int chroma) {
     MetPlane m;
     m.pw = W >> chroma;
     m.ph = H >> chroma;
-    m.groups = m.pw >> 4;
+    m.groups = (m.pw + 15) >> 4;
+    m.brows = (m.ph + 3) >> 2;
     m.strips = (m.groups + kMetStripLanes - 1) / kMetStripLanes;
-    m.segs = ((m.ph >> 2) - 1 + kMetRows - 1) / kMetRows;
+    m.segs = (m.brows - 1 + kMetRows - 1) / kMetRows;
     m.waves = m.strips * m.segs;
     m.windows = ((m.pw >> 2) - 1) * ((m.ph >> 2) - 1);
     return m;
@@ -78,7 +88,7 @@ struct GroupRows {
     Dwords4 a[4], b[4];
 };
 typedef const __attribute__((address_space(1))) Dwords4* GlobalRow; // (a plane pointer read from PicBufs would give flat loads)
-__device__ __forceinline__ void load_group_rows(GroupRows& g, const uint8_t* org, const uint8_t* rec, size_t at, int pw) {
+__device__ __forceinline__ void load_group_rows(GroupRows& g, const uint8_t* org, const uint8_t* rec, size_t at, int pw) { // pw: the planes' pitch
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         g.a[r] = *(GlobalRow)(org + at + (size_t)r * pw);
@@ -87,11 +97,13 @@ __device__ __forceinline__ void load_group_rows(GroupRows& g, const uint8_t* org
 }
 
 // One wave per (picture, plane, strip, kMetRows window rows).  MAP (test entry): the windows' values also go to `maps`,
-// per picture Y | Cb | Cr, each plane in raster order of its windows.
-template <bool MAP>
+// per picture Y | Cb | Cr, each plane in raster order of its windows.  W x H: the planes' (coded) size; WIN: the pass
+// measures their top-left VW x VH (else VW x VH is not read).
+template <bool MAP, bool WIN>
 __global__ __launch_bounds__(256) void metrics_kernel(const PicBufs* __restrict__ slots, int first_slot, int n_pics, int W, int H,
-                                                      MetricsPartial* __restrict__ partials, float* __restrict__ maps) {
-    const MetPlane L = met_plane(W, H, 0), C = met_plane(W, H, 1);
+                                                      int VW, int VH, MetricsPartial* __restrict__ partials,
+                                                      float* __restrict__ maps) {
+    const MetPlane L = met_plane(WIN ? VW : W, WIN ? VH : H, 0), C = met_plane(WIN ? VW : W, WIN ? VH : H, 1);
     const int per_pic = L.waves + 2 * C.waves;
     const int id = uni((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
     if (id >= n_pics * per_pic) return; // (the whole wave)
@@ -115,12 +127,23 @@ __global__ __launch_bounds__(256) void metrics_kernel(const PicBufs* __restrict_
     const int grp = strip * kMetStripLanes + lane;
     const bool own = grp < P.groups && lane < kMetStripLanes; // the group exists, and its blocks and the windows that start in its first three are this lane's
     const bool own3 = own && grp + 1 < P.groups;        // ... and the window of its fourth block and the right neighbour's first
-    const int bh = P.ph >> 2, win_w = (P.pw >> 2) - 1;
+    const int bh = P.brows, win_w = (P.pw >> 2) - 1;
+    const int whole_rows = P.ph >> 2;                   // (WIN) block rows that lie inside the rectangle: bh or bh - 1
+    const int pitch = WIN ? W >> (plane ? 1 : 0) : P.pw;
     const int r0 = seg * kMetRows;
     const int r_end = min(r0 + kMetRows, bh - 1);       // block rows r0 .. r_end; r_end is the next wave's r0 unless it is the last
     const bool last_seg = r_end == bh - 1;
     // a lane beyond the plane's last group reads that group again (same addresses as its owner: no traffic) and owns nothing
     const size_t col = (size_t)16 * min(grp, P.groups - 1);
+    // (WIN) the bytes of the group's four dwords that lie inside the rectangle
+    uint32_t col_mask[4] = {~0u, ~0u, ~0u, ~0u};
+    if (WIN) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int valid = min(max(P.pw - (int)col - 4 * j, 0), 4);
+            col_mask[j] = valid >= 4 ? ~0u : (1u << (8 * valid)) - 1u;
+        }
+    }
     float* map = nullptr;
     if (MAP) map = maps + (size_t)pic * (L.windows + 2 * C.windows) + (plane ? L.windows + (plane - 1) * C.windows : 0);
 
@@ -135,7 +158,12 @@ __global__ __launch_bounds__(256) void metrics_kernel(const PicBufs* __restrict_
             uint32_t s1 = 0, s2 = 0, ss = 0, s12 = 0;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const uint32_t a = g.a[r][j], b = g.b[r][j];
+                uint32_t a = g.a[r][j], b = g.b[r][j];
+                if (WIN) {
+                    const uint32_t m = 4 * br + r < P.ph ? col_mask[j] : 0u;
+                    a &= m;
+                    b &= m;
+                }
                 s1 = __builtin_amdgcn_udot4(a, 0x01010101u, s1, false);
                 s2 = __builtin_amdgcn_udot4(b, 0x01010101u, s2, false);
                 ss = __builtin_amdgcn_udot4(a, a, ss, false);
@@ -154,7 +182,7 @@ __global__ __launch_bounds__(256) void metrics_kernel(const PicBufs* __restrict_
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float v = ssim_window(above[j] + pair[j]);
-                const bool mine = j < 3 ? own : own3;
+                const bool mine = WIN ? own && 4 * grp + j < win_w : (j < 3 ? own : own3);
                 ssim += mine ? (double)v : 0.0;
                 if (MAP && mine) map[(size_t)(br - 1) * win_w + 4 * grp + j] = v;
             }
@@ -163,14 +191,15 @@ __global__ __launch_bounds__(256) void metrics_kernel(const PicBufs* __restrict_
         for (int j = 0; j < 4; ++j) above[j] = pair[j];
     };
     GroupRows cur, nxt;
-    load_group_rows(cur, org, rec, (size_t)(4 * r0) * P.pw + col, P.pw);
+    load_group_rows(cur, org, rec, (size_t)(4 * r0) * pitch + col, pitch);
     for (int br = r0; br < r_end; ++br) {
         // the next block row is on its way while this one is summed
-        load_group_rows(nxt, org, rec, (size_t)(4 * br + 4) * P.pw + col, P.pw);
+        load_group_rows(nxt, org, rec, (size_t)(4 * br + 4) * pitch + col, pitch);
         block_row(cur, br, true, br > r0);
         cur = nxt;
     }
-    block_row(cur, r_end, last_seg, true); // (r_end > r0: every wave has a window row)
+    // (r_end > r0: every wave has a block row below its first; WIN: a partial last block row closes no windows)
+    block_row(cur, r_end, last_seg, WIN ? r_end < whole_rows : true);
     // the wave's pair: a fixed butterfly, so the same lanes' values are always added in the same order
     unsigned long long sse_w = sse;
 #pragma unroll

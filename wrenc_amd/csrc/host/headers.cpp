@@ -69,7 +69,10 @@ void write_vps(BitWriter& bw, int, int) {
 }
 
 // sps_encoder.rs:29-545, SequenceParameterSet::new(1, 8, w, h, 8) (main.rs:236)
-void write_sps(BitWriter& bw, int width, int height) {
+// vis_w x vis_h: the size a decoder outputs.  Smaller than the coded size, it is signalled as a conformance window
+// (H.266 7.3.2.4 / 7.4.3.4): offsets in chroma sample units (SubWidthC = SubHeightC = 2), the margin at the right and
+// at the bottom only.
+void write_sps(BitWriter& bw, int width, int height, int vis_w, int vis_h) {
     bw.put(1, 4); // sps id
     bw.put(8, 4); // vps id
     bw.put(0, 3); // max_sublayers - 1
@@ -81,7 +84,15 @@ void write_sps(BitWriter& bw, int width, int height) {
     bw.bit(0); // ref_pic_resampling_enabled_flag
     bw.ue((uint64_t)width);
     bw.ue((uint64_t)height);
-    bw.bit(0);    // conformance window
+    if (vis_w == width && vis_h == height) {
+        bw.bit(0); // conformance window
+    } else {
+        bw.bit(1);
+        bw.ue(0);                                  // sps_conf_win_left_offset
+        bw.ue((uint64_t)((width - vis_w) / 2));    // sps_conf_win_right_offset
+        bw.ue(0);                                  // sps_conf_win_top_offset
+        bw.ue((uint64_t)((height - vis_h) / 2));   // sps_conf_win_bottom_offset
+    }
     bw.bit(0);    // subpic info
     bw.ue(0);     // bitdepth - 8
     bw.bit(0);    // entropy_coding_sync_enabled_flag
@@ -170,7 +181,7 @@ void write_pps(BitWriter& bw, int width, int height, int qp) {
     bw.bit(0);    // mixed_nalu_types_in_pic_flag
     bw.ue((uint64_t)width);
     bw.ue((uint64_t)height);
-    bw.bit(0); // conformance window
+    bw.bit(0); // conformance window: the picture has the SPS's maximum size, so the SPS's window is inferred (7.4.3.5)
     bw.bit(0); // scaling_window_explicit_signalling_flag
     bw.bit(0); // output_flag_present_flag
     bw.bit(1); // no_pic_partition_flag

@@ -51,7 +51,7 @@ private:
 
 // Raw byte sequence payloads (headers.cpp)
 void write_vps(BitWriter& bw, int width, int height);
-void write_sps(BitWriter& bw, int width, int height);
+void write_sps(BitWriter& bw, int width, int height, int vis_w, int vis_h);
 void write_pps(BitWriter& bw, int width, int height, int qp);
 void write_picture_header(BitWriter& bw, int poc);
 void write_slice_header(BitWriter& bw, int slice_qp, int pps_qp);

@@ -1,5 +1,6 @@
-// wrenc_bitstream.cpp -- the C ABI of include/wrenc_bitstream.h and include/wrenc_bitstream_qp.h.
+// wrenc_bitstream.cpp -- the C ABI of include/wrenc_bitstream.h, include/wrenc_bitstream_qp.h and include/wrenc_bitstream_window.h.
 #include "../../../include/wrenc_bitstream_qp.h"
+#include "../../../include/wrenc_bitstream_window.h"
 #include "slice_data.h"
 
 #include <cstring>
@@ -13,6 +14,12 @@ thread_local long long g_last_slice_data_bits = 0;
 bool size_ok(int width, int height, int qp) {
     return width >= 32 && height >= 32 && width % 32 == 0 && height % 32 == 0 && width <= 16384 &&
            height <= 16384 && qp >= 0 && qp <= 63;
+}
+
+// a visible size the coded size is the round-up of: even, at least 16 x 16 (one SSIM window per chroma plane)
+bool window_ok(int width, int height, int vis_w, int vis_h) {
+    return vis_w >= 16 && vis_h >= 16 && vis_w % 2 == 0 && vis_h % 2 == 0 && width == (vis_w + 31) / 32 * 32 &&
+           height == (vis_h + 31) / 32 * 32;
 }
 
 int hand_over(const std::vector<uint8_t>& bytes, uint8_t* out, size_t cap, size_t* len) {
@@ -53,7 +60,13 @@ size_t wrenc_bs_picture_bound(int width, int height) {
 }
 
 int wrenc_bs_write_parameter_sets(int width, int height, int qp, uint8_t* out, size_t cap, size_t* len) {
+    return wrenc_bs_write_parameter_sets_window(width, height, width, height, qp, out, cap, len);
+}
+
+int wrenc_bs_write_parameter_sets_window(int width, int height, int vis_w, int vis_h, int qp, uint8_t* out, size_t cap,
+                                         size_t* len) {
     if (!size_ok(width, height, qp)) return WRENC_BS_EINVAL;
+    if ((vis_w != width || vis_h != height) && !window_ok(width, height, vis_w, vis_h)) return WRENC_BS_EINVAL;
     std::vector<uint8_t> stream;
     {
         BitWriter bw;
@@ -62,7 +75,7 @@ int wrenc_bs_write_parameter_sets(int width, int height, int qp, uint8_t* out, s
     }
     {
         BitWriter bw;
-        write_sps(bw, width, height);
+        write_sps(bw, width, height, vis_w, vis_h);
         append_nal(stream, 9, NAL_SPS, 0, bw.bytes()); // main.rs:245
     }
     {

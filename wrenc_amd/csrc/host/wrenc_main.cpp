@@ -19,12 +19,18 @@
 // parameter sets' QP; the bytes depend on the input and the options alone, not on --threads or timing, which is why
 // --ramp-down auto, decided by the clock, runs as never), --metrics PATH (PSNR and SSIM of every picture from sums the
 // device takes of the originals and the reconstruction it holds, wrenc_gpu_download_metrics: a JSON report in the shape of
-// the reference's evaluation harness, and one summary line on stderr), --verbose, --ramp-down auto|always|never, --tokens auto|on|off
+// the reference's evaluation harness, and one summary line on stderr), --pad (below), --verbose, --ramp-down auto|always|never, --tokens auto|on|off
 // (how a batch comes back.  auto and on: as the residual tokens the device makes of it, wrenc_gpu_download_tokens -- the
 // host then runs the CU-level syntax and the arithmetic coder only, 1.8x less host time per picture, 20x the bytes over
 // PCIe -- and as the compact level record, with residual_coding on the host, when they do not fit the token pool.  off,
 // or --no-tokens: always as the compact record.  Same bytes either way).  Links only against the two C ABIs: no HIP, no
 // Python.
+//
+// --pad: --output-size may be any even size of at least 16x16.  The input holds frames of that size.  The contexts are
+// created at the next multiple of the CTU size with that visible size (wrenc_gpu_set_visible_size: the device replicates
+// the last column and row into the margin), and the SPS carries the conformance window.  --reconst receives frames
+// cropped to --output-size and --metrics reports that rectangle.  --bitrate charges the parameter sets of the coded
+// size, so its QPs are those of the padded pictures coded plainly.
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -43,6 +49,7 @@
 
 #include "../../../include/wrenc_bitstream.h"
 #include "../../../include/wrenc_bitstream_qp.h"
+#include "../../../include/wrenc_bitstream_window.h"
 #include "../../../include/wrenc_gpu.h"
 #include "../../../include/wrenc_rate.h"
 
@@ -137,7 +144,9 @@ private:
 struct Options {
     const char *input = nullptr, *output = nullptr, *reconst = nullptr, *extra = nullptr, *metrics = nullptr;
     long num_pictures = -1;
-    int w = 0, h = 0, qp = 26; // ctu.rs:382 when --qp is absent
+    int w = 0, h = 0, qp = 26; // the coded size; ctu.rs:382 when --qp is absent
+    int vis_w = 0, vis_h = 0;  // --output-size: the size of the input's and of --reconst's frames; w x h unless --pad
+    bool pad = false;
     int depth = 3, batch = 64, n_threads = 8;
     bool verbose = false;
     bool tokens = true; // --tokens auto | on: batches come back as residual tokens; --tokens off, --no-tokens: as the compact record
@@ -201,6 +210,7 @@ Options parse_options(int argc, char** argv) {
         else if (a == "--devices") device_list = val();
         else if (a == "--metrics") o.metrics = val();
         else if (a == "--verbose") o.verbose = true;
+        else if (a == "--pad") o.pad = true;
         else if (a == "--no-tokens") o.tokens = false;
         else if (a == "--ramp-down") { // how a run ends: auto (smaller last batches when the host's tail is heavy), always, never
             const std::string v = val();
@@ -229,6 +239,13 @@ Options parse_options(int argc, char** argv) {
                 die("Invalid extra-params: %s", o.extra);
             pos = end + 1;
         }
+    }
+    o.vis_w = o.w;
+    o.vis_h = o.h;
+    if (o.pad) { // any even size: coded at the next multiple of the CTU size
+        if (o.w % 2 || o.h % 2 || o.w < 16 || o.h < 16) die("with --pad, output-size must be even and at least 16x16: %dx%d", o.w, o.h);
+        o.w = (o.w + 31) / 32 * 32;
+        o.h = (o.h + 31) / 32 * 32;
     }
     if (o.w % 32 || o.h % 32) die("output-size must be a multiple of the 32x32 CTU (picture.rs:178-181): %dx%d", o.w, o.h);
     if (o.qp < 0 || o.qp > 63 || o.depth < 0 || o.depth > 3) die("qp must be 0..63, max-split-depth 0..3");
@@ -268,12 +285,15 @@ Options parse_options(int argc, char** argv) {
 
 // sizes of one picture (8-bit 4:2:0) and of what is read back of it
 struct Geometry {
-    int w, h;
+    int w, h;               // the coded size
+    int vw, vh;             // the size of the frames in the input and in --reconst (--pad: smaller than the coded size)
     size_t ysz, csz, pic;   // bytes of luma, of one chroma plane, of the picture
+    size_t vysz, vcsz, vpic; // the same of a frame of the input
     size_t n4, maps;        // 4x4 luma blocks; bytes of cu_log2_size | luma_mode | chroma_mode
     size_t mask_words, level_blocks, n_ctus;
-    Geometry(int w_, int h_)
-        : w(w_), h(h_), ysz((size_t)w_ * h_), csz(ysz / 4), pic(ysz + 2 * csz), n4(ysz / 16), maps(2 * n4 + ysz / 64),
+    Geometry(int w_, int h_, int vw_, int vh_)
+        : w(w_), h(h_), vw(vw_), vh(vh_), ysz((size_t)w_ * h_), csz(ysz / 4), pic(ysz + 2 * csz), vysz((size_t)vw_ * vh_),
+          vcsz((size_t)(vw_ / 2) * (vh_ / 2)), vpic(vysz + 2 * vcsz), n4(ysz / 16), maps(2 * n4 + ysz / 64),
           mask_words(wrenc_gpu_compact_mask_words(w_, h_)), level_blocks(pic / 16), n_ctus((size_t)(w_ / 32) * (h_ / 32)) {}
 };
 
@@ -337,7 +357,7 @@ std::vector<HostSet> make_units(const Options& o, const Geometry& g, const std::
         HostSet& s = units[u];
         s.ctx = ctxs[u % n_dev];
         s.base = (int)(u / n_dev) * o.batch;
-        s.in = (uint8_t*)wrenc_gpu_alloc_host(s.ctx, g.pic * batch);
+        s.in = (uint8_t*)wrenc_gpu_alloc_host(s.ctx, g.vpic * batch);
         s.maps = (uint8_t*)wrenc_gpu_alloc_host(s.ctx, g.maps * batch);
         if (with_rec) s.rec = (uint8_t*)wrenc_gpu_alloc_host(s.ctx, g.pic * batch);
         if (!s.in || !s.maps || (with_rec && !s.rec)) fatal("%s", wrenc_gpu_last_error(s.ctx));
@@ -437,8 +457,8 @@ struct Run {
     void upload(HostSet& s, int k) {
         // the slot's QP first: the encode call of the batch reads it (NULL: the context's, --qp)
         if (!o.pic_qp.empty()) gpu_check(s, wrenc_gpu_set_slot_qp(s.ctx, s.base + k, qcfg[(size_t)slice_qp(poc + k)]));
-        uint8_t* p = s.in + g.pic * k;
-        gpu_check(s, wrenc_gpu_upload(s.ctx, s.base + k, p, p + g.ysz, p + g.ysz + g.csz, (size_t)g.w, (size_t)g.w / 2));
+        uint8_t* p = s.in + g.vpic * k;
+        gpu_check(s, wrenc_gpu_upload(s.ctx, s.base + k, p, p + g.vysz, p + g.vysz + g.vcsz, (size_t)g.vw, (size_t)g.vw / 2));
         ++s.count;
     }
 
@@ -462,15 +482,15 @@ struct Run {
             for (int t = 0; t < n_readers; ++t)
                 readers.emplace_back([&, t] {
                     for (int k = t; k < want; k += n_readers) {
-                        uint8_t* p = s.in + g.pic * k;
+                        uint8_t* p = s.in + g.vpic * k;
                         size_t got = 0;
-                        const off_t at = (off_t)((size_t)(poc + k) * g.pic);
-                        while (got < g.pic) {
-                            const ssize_t r = pread(fileno(fin), p + got, g.pic - got, at + (off_t)got);
+                        const off_t at = (off_t)((size_t)(poc + k) * g.vpic);
+                        while (got < g.vpic) {
+                            const ssize_t r = pread(fileno(fin), p + got, g.vpic - got, at + (off_t)got);
                             if (r <= 0) break;
                             got += (size_t)r;
                         }
-                        ready[(size_t)k].store(got == g.pic ? 1 : -1, std::memory_order_release);
+                        ready[(size_t)k].store(got == g.vpic ? 1 : -1, std::memory_order_release);
                     }
                 });
             int short_at = -1;
@@ -487,7 +507,7 @@ struct Run {
             if (short_at >= 0) die("input ended after %ld of %ld pictures", poc + short_at, o.num_pictures);
         } else {
             for (int k = 0; k < want; ++k) {
-                if (!read_exact(fin, s.in + g.pic * k, g.pic)) die("input ended after %ld of %ld pictures", poc + k, o.num_pictures);
+                if (!read_exact(fin, s.in + g.vpic * k, g.vpic)) die("input ended after %ld of %ld pictures", poc + k, o.num_pictures);
                 upload(s, k);
             }
         }
@@ -577,6 +597,19 @@ struct Run {
         pool.start(s.count, [this, &s](int k) { write_picture(s, k); });
     }
 
+    // a picture's reconstruction (coded size, as it is read back) to --reconst, cropped to the frames' size
+    void write_reconst(const uint8_t* rec) {
+        if (g.vw == g.w && g.vh == g.h) {
+            fwrite(rec, 1, g.pic, frec);
+            return;
+        }
+        for (int p = 0; p < 3; ++p) {
+            const size_t pitch = (size_t)(p ? g.w / 2 : g.w), cols = (size_t)(p ? g.vw / 2 : g.vw), rows = (size_t)(p ? g.vh / 2 : g.vh);
+            const uint8_t* plane = rec + (p ? g.ysz + (size_t)(p - 1) * g.csz : 0);
+            for (size_t r = 0; r < rows; ++r) fwrite(plane + r * pitch, 1, cols, frec);
+        }
+    }
+
     void flush(HostSet& s) {
         pool.wait();
         for (int k = 0; k < s.bs_count; ++k) {
@@ -584,7 +617,7 @@ struct Run {
             fwrite(s.nal[(size_t)k].data(), 1, s.len[(size_t)k], fout);
             bytes += s.len[(size_t)k];
             if (o.metrics) pic_bytes.push_back(s.len[(size_t)k]);
-            if (frec) fwrite(s.rec + g.pic * k, 1, g.pic, frec); // main.rs:387-399
+            if (frec) write_reconst(s.rec + g.pic * k); // main.rs:387-399
         }
         if (rate && s.bs_count > 0) { // the bytes of the batch's NAL units, in the order its QPs were chosen
             rate_words.assign(s.len.begin(), s.len.begin() + s.bs_count);
@@ -603,7 +636,7 @@ void write_metrics_report(const Run& run, const char* path, unsigned long long s
     std::vector<double> psnr(4 * n), ssim(4 * n);
     double mean[2][4] = {};
     for (size_t i = 0; i < n; ++i) {
-        wrenc_gpu_metrics_values(o.w, o.h, &run.pic_metrics[i], &psnr[4 * i], &ssim[4 * i]);
+        wrenc_gpu_metrics_values(o.vis_w, o.vis_h, &run.pic_metrics[i], &psnr[4 * i], &ssim[4 * i]);
         for (int a = 0; a < 4; ++a) {
             mean[0][a] += psnr[4 * i + a];
             mean[1][a] += ssim[4 * i + a];
@@ -621,7 +654,7 @@ void write_metrics_report(const Run& run, const char* path, unsigned long long s
         if (std::isinf(v)) fputs(v > 0 ? "Infinity" : "-Infinity", f);
         else fprintf(f, "%.17g", v);
     };
-    fprintf(f, "{\"width\": %d, \"height\": %d, \"frames\": %zu", o.w, o.h, n);
+    fprintf(f, "{\"width\": %d, \"height\": %d, \"frames\": %zu", o.vis_w, o.vis_h, n);
     for (int m = 0; m < 2; ++m) {
         const std::vector<double>& v = m ? ssim : psnr;
         fprintf(f, ",\n \"%s\": {\"summary\": {", m ? "SSIM" : "PSNR");
@@ -647,7 +680,7 @@ void write_metrics_report(const Run& run, const char* path, unsigned long long s
     fputs("]}\n", f);
     fclose(f);
     fprintf(stderr, "%llu bytes  %.4f bpp  PSNR Avg %.2f Y %.2f U %.2f V %.2f dB  SSIM All %.4f Y %.4f\n", stream_bytes,
-            n ? 8.0 * (double)stream_bytes / ((double)n * o.w * o.h) : 0.0, mean[0][0], mean[0][1], mean[0][2], mean[0][3], mean[1][0], mean[1][1]);
+            n ? 8.0 * (double)stream_bytes / ((double)n * o.vis_w * o.vis_h) : 0.0, mean[0][0], mean[0][1], mean[0][2], mean[0][3], mean[1][0], mean[1][1]);
 }
 
 double since(std::chrono::steady_clock::time_point t) {
@@ -680,17 +713,22 @@ int main(int argc, char** argv) {
         cfg.device = d;
         wrenc_gpu_ctx* ctx = nullptr;
         if (wrenc_gpu_create(&cfg, &ctx)) fatal("%s", wrenc_gpu_last_error(nullptr)); // no CPU path: fails without an MI355X
+        if (o.pad && wrenc_gpu_set_visible_size(ctx, o.vis_w, o.vis_h)) fatal("%s", wrenc_gpu_last_error(ctx));
         ctxs.push_back(ctx);
     }
-    const Geometry g(o.w, o.h);
+    const Geometry g(o.w, o.h, o.vis_w, o.vis_h);
     std::vector<HostSet> units = make_units(o, g, ctxs, per_dev, frec != nullptr);
-    size_t hdr_bytes = 0;
+    size_t hdr_bytes = 0, rate_hdr_bytes = 0;
     {
         uint8_t hdr[512];
         size_t n = 0;
-        if (wrenc_bs_write_parameter_sets(o.w, o.h, o.qp, hdr, sizeof(hdr), &n)) fatal("parameter sets do not fit");
+        // (the visible size equal to the coded one: the bytes of wrenc_bs_write_parameter_sets)
+        if (wrenc_bs_write_parameter_sets_window(o.w, o.h, o.vis_w, o.vis_h, o.qp, hdr, sizeof(hdr), &n)) fatal("parameter sets do not fit");
         fwrite(hdr, 1, n, fout);
         hdr_bytes = n;
+        // --bitrate charges the parameter sets of the coded size: the byte or two of the window fields stay outside the
+        // budget, so a padded run chooses exactly the QPs of a plain run over the padded pictures
+        if (wrenc_bs_write_parameter_sets(o.w, o.h, o.qp, hdr, sizeof(hdr), &rate_hdr_bytes)) fatal("parameter sets do not fit");
     }
 
     const auto t_start = std::chrono::steady_clock::now();
@@ -703,7 +741,7 @@ int main(int argc, char** argv) {
         int qp_max = 63;
         while (qp_max > o.qp && wrenc_gpu_set_slot_qp(ctxs[0], 0, run.config_of(qp_max)) == WRENC_GPU_EINVAL) --qp_max;
         if (wrenc_gpu_set_slot_qp(ctxs[0], 0, nullptr)) fatal("%s", wrenc_gpu_last_error(ctxs[0]));
-        const wrenc_rate_config rcfg = {o.w, o.h, 0, qp_max, (int64_t)o.num_pictures, target_bytes, (double)hdr_bytes};
+        const wrenc_rate_config rcfg = {o.w, o.h, 0, qp_max, (int64_t)o.num_pictures, target_bytes, (double)rate_hdr_bytes};
         if (wrenc_rate_create(&rcfg, &run.rate)) fatal("rate control: bad configuration");
         run.rate_qp.assign((size_t)o.num_pictures, o.qp);
         if (o.verbose) fprintf(stderr, "rate control: %.1f kbit/s at %.3g pictures/s = %.1f bytes per picture, QP 0 .. %d\n", o.bitrate, o.fps, target_bytes, qp_max);

@@ -43,3 +43,4 @@
 #include "dev_bins.h"
 #include "dev_metrics.h"
 #include "dev_complexity.h"
+#include "dev_pad.h"

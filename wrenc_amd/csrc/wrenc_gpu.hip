@@ -655,6 +655,9 @@ struct wrenc_gpu_ctx {
     PicBufs* d_slots = nullptr;
     std::vector<PicBufs> slots;
     std::vector<int> state; // 0 empty, 1 uploaded, 2 encoded
+    // the size of the caller's pictures (wrenc_gpu_set_visible_size); the coded size unless one is set
+    int vis_w = 0, vis_h = 0;
+    bool any_upload = false;
     unsigned long long* d_mismatch = nullptr;
     int* d_overflow = nullptr;
     uint8_t* d_pred_scratch = nullptr; // kScratchSlots x WPB x kWaveScratch: saved reconstructions (dev_search.h copy_block)
@@ -1288,6 +1291,8 @@ int wrenc_gpu_create(const wrenc_gpu_config* cfg, wrenc_gpu_ctx** out) {
     ctx->wave_slots = ctx->device_wave_slots = (long long)prop.multiProcessorCount * kWorkgroupsPerCU * WPB;
     ctx->ctu_cols = cfg->width / 32;
     ctx->ctu_rows = cfg->height / 32;
+    ctx->vis_w = cfg->width;
+    ctx->vis_h = cfg->height;
     auto bail = [&](int code, const std::string& msg) {
         g_create_error = msg;
         wrenc_gpu_destroy(ctx);
@@ -1382,21 +1387,67 @@ int wrenc_gpu_upload(wrenc_gpu_ctx* ctx, int slot, const uint8_t* y, const uint8
     if (!ctx) return WRENC_GPU_EINVAL;
     if (slot < 0 || slot >= ctx->cfg.n_slots || !y || !cb || !cr) return fail(ctx, WRENC_GPU_EINVAL, "bad slot or null plane");
     const size_t w = ctx->cfg.width, h = ctx->cfg.height;
-    if (stride_y < w || stride_c < w / 2) return fail(ctx, WRENC_GPU_EINVAL, "stride smaller than row");
+    const size_t vw = (size_t)ctx->vis_w, vh = (size_t)ctx->vis_h; // the caller's planes; w x h unless a visible size is set
+    if (stride_y < vw || stride_c < vw / 2) return fail(ctx, WRENC_GPU_EINVAL, "stride smaller than row");
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
     PicBufs& b = ctx->slots[slot];
     // the planes may still be read by a search in flight on this slot
     if (ctx->slot_event[slot]) HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->slot_event[slot], 0));
     hipStream_t cs = ctx->copy_stream;
-    HIP_TRY(ctx, hipMemcpy2DAsync((void*)b.org[0], w, y, stride_y, w, h, hipMemcpyHostToDevice, cs));
-    HIP_TRY(ctx, hipMemcpy2DAsync((void*)b.org[1], w / 2, cb, stride_c, w / 2, h / 2, hipMemcpyHostToDevice, cs));
-    HIP_TRY(ctx, hipMemcpy2DAsync((void*)b.org[2], w / 2, cr, stride_c, w / 2, h / 2, hipMemcpyHostToDevice, cs));
+    HIP_TRY(ctx, hipMemcpy2DAsync((void*)b.org[0], w, y, stride_y, vw, vh, hipMemcpyHostToDevice, cs));
+    HIP_TRY(ctx, hipMemcpy2DAsync((void*)b.org[1], w / 2, cb, stride_c, vw / 2, vh / 2, hipMemcpyHostToDevice, cs));
+    HIP_TRY(ctx, hipMemcpy2DAsync((void*)b.org[2], w / 2, cr, stride_c, vw / 2, vh / 2, hipMemcpyHostToDevice, cs));
+    // a picture smaller than the coded size: its last column and row replicated into the margin of the three planes
+    // (dev_pad.h), behind the copies and in front of the tiling
+    if (vw != w || vh != h) {
+        const int items = pad_items((int)w, (int)h, (int)vw, (int)vh);
+        hipLaunchKernelGGL(pad_edges_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, cs, (uint8_t*)b.org[0], (int)w, (int)h,
+                           (int)vw, (int)vh);
+    }
     // planar staging -> CTU tiles (what the search reads), behind the copies on the same stream
     hipLaunchKernelGGL(retile_kernel, dim3(ctx->ctu_cols * ctx->ctu_rows), dim3(64), 0, cs, b.org[0], (uint8_t*)b.org_t, (int)w,
                        (int)h, ctx->ctu_cols);
     HIP_TRY(ctx, hipGetLastError());
     ctx->uploads_pending = true;
+    ctx->any_upload = true;
     ctx->state[slot] = 1;
+    return WRENC_GPU_OK;
+}
+
+int wrenc_gpu_set_visible_size(wrenc_gpu_ctx* ctx, int vis_w, int vis_h) {
+    if (!ctx) return WRENC_GPU_EINVAL;
+    const wrenc_gpu_config& c = ctx->cfg;
+    if (vis_w != c.width || vis_h != c.height) {
+        if (vis_w < 16 || vis_h < 16 || (vis_w & 1) || (vis_h & 1))
+            return fail(ctx, WRENC_GPU_EINVAL, "the visible size must be even and at least 16x16");
+        if ((vis_w + 31) / 32 * 32 != c.width || (vis_h + 31) / 32 * 32 != c.height)
+            return fail(ctx, WRENC_GPU_EINVAL, "the context's size must be the visible size rounded up to a multiple of 32");
+    }
+    if (ctx->any_upload) return fail(ctx, WRENC_GPU_ESTATE, "the visible size must be set before the first upload");
+    ctx->vis_w = vis_w;
+    ctx->vis_h = vis_h;
+    ctx->metrics_cap = 0; // the metrics scratch is sized for the rectangle that is measured
+    return WRENC_GPU_OK;
+}
+
+int wrenc_gpu_visible_size(const wrenc_gpu_ctx* ctx, int* w, int* h) {
+    if (!ctx || !w || !h) return WRENC_GPU_EINVAL;
+    *w = ctx->vis_w;
+    *h = ctx->vis_h;
+    return WRENC_GPU_OK;
+}
+
+int wrenc_gpu_test_download_originals(wrenc_gpu_ctx* ctx, int slot, uint8_t* y, uint8_t* cb, uint8_t* cr) {
+    if (!ctx) return WRENC_GPU_EINVAL;
+    if (slot < 0 || slot >= ctx->cfg.n_slots || !y || !cb || !cr) return fail(ctx, WRENC_GPU_EINVAL, "bad slot or null plane");
+    if (ctx->state[slot] == 0) return fail(ctx, WRENC_GPU_ESTATE, "slot has no uploaded picture");
+    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+    const PicBufs& b = ctx->slots[slot];
+    uint8_t* out[3] = {y, cb, cr};
+    // behind the slot's upload on the copy stream; a search only reads the planes
+    for (int p = 0; p < 3; ++p)
+        HIP_TRY(ctx, hipMemcpyAsync(out[p], b.org[p], plane_bytes(ctx->cfg, p, 1), hipMemcpyDeviceToHost, ctx->copy_stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->copy_stream));
     return WRENC_GPU_OK;
 }
 
@@ -1779,24 +1830,28 @@ int wrenc_gpu_download_tokens(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_g
 
 // the metrics pass over n pictures of `slots` from `first` on, on `st`: the waves' partial sums, then the pictures' totals
 // (maps: the test entry's per-window values, else NULL)
-static hipError_t launch_metrics(const wrenc_gpu_config& c, hipStream_t st, const PicBufs* slots, int first, int n, MetricsPartial* partials,
-                                 MetricsSums* sums, float* maps) {
-    const int per_pic = met_plane(c.width, c.height, 0).waves + 2 * met_plane(c.width, c.height, 1).waves;
+// vw x vh: the rectangle that is measured, the coded size or a context's visible size (the window variant of the kernel)
+static hipError_t launch_metrics(const wrenc_gpu_config& c, int vw, int vh, hipStream_t st, const PicBufs* slots, int first, int n,
+                                 MetricsPartial* partials, MetricsSums* sums, float* maps) {
+    const int per_pic = met_plane(vw, vh, 0).waves + 2 * met_plane(vw, vh, 1).waves;
     const long long waves = (long long)n * per_pic;
     const dim3 grid((unsigned)((waves + 3) / 4));
-    if (maps)
-        hipLaunchKernelGGL(metrics_kernel<true>, grid, dim3(256), 0, st, slots, first, n, c.width, c.height, partials, maps);
+    if ((vw != c.width || vh != c.height) && maps) return hipErrorInvalidValue; // the window variant stores no maps
+    if (vw != c.width || vh != c.height)
+        hipLaunchKernelGGL((metrics_kernel<false, true>), grid, dim3(256), 0, st, slots, first, n, c.width, c.height, vw, vh, partials, maps);
+    else if (maps)
+        hipLaunchKernelGGL((metrics_kernel<true, false>), grid, dim3(256), 0, st, slots, first, n, c.width, c.height, vw, vh, partials, maps);
     else
-        hipLaunchKernelGGL(metrics_kernel<false>, grid, dim3(256), 0, st, slots, first, n, c.width, c.height, partials, maps);
-    hipLaunchKernelGGL(metrics_finish_kernel, dim3(n), dim3(64), 0, st, partials, c.width, c.height, sums);
+        hipLaunchKernelGGL((metrics_kernel<false, false>), grid, dim3(256), 0, st, slots, first, n, c.width, c.height, vw, vh, partials, maps);
+    hipLaunchKernelGGL(metrics_finish_kernel, dim3(n), dim3(64), 0, st, partials, vw, vh, sums);
     return hipGetLastError();
 }
 
-static void fill_metrics(const wrenc_gpu_config& c, const MetricsSums& s, wrenc_gpu_metrics& m) {
+static void fill_metrics(int vw, int vh, const MetricsSums& s, wrenc_gpu_metrics& m) {
     for (int p = 0; p < 3; ++p) {
         m.sse[p] = s.sse[p];
         m.ssim_sum[p] = s.ssim[p];
-        m.ssim_windows[p] = (uint32_t)met_plane(c.width, c.height, p ? 1 : 0).windows;
+        m.ssim_windows[p] = (uint32_t)met_plane(vw, vh, p ? 1 : 0).windows;
     }
 }
 
@@ -1805,7 +1860,9 @@ int wrenc_gpu_download_metrics(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_
     if (const int rc = check_encoded(ctx, first_slot, n, "slot range out of bounds")) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
     const wrenc_gpu_config& c = ctx->cfg;
-    const size_t per_pic = (size_t)met_plane(c.width, c.height, 0).waves + 2 * (size_t)met_plane(c.width, c.height, 1).waves;
+    // a context with a visible size reports that rectangle only
+    const int vw = ctx->vis_w, vh = ctx->vis_h;
+    const size_t per_pic = (size_t)met_plane(vw, vh, 0).waves + 2 * (size_t)met_plane(vw, vh, 1).waves;
     if (ctx->metrics_cap < n) {
         ctx->metrics_cap = 0;
         HIP_TRY(ctx, realloc_scratch(ctx->d_mpartial, (size_t)n * per_pic * sizeof(MetricsPartial)));
@@ -1815,11 +1872,11 @@ int wrenc_gpu_download_metrics(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_
     // on the copy stream, behind the encode call that searched these slots and nothing later
     hipStream_t cs = ctx->copy_stream;
     if (const int rc = wait_for_search(ctx, first_slot, n)) return rc;
-    HIP_TRY(ctx, launch_metrics(c, cs, ctx->d_slots, first_slot, n, ctx->d_mpartial, ctx->d_msums, nullptr));
+    HIP_TRY(ctx, launch_metrics(c, vw, vh, cs, ctx->d_slots, first_slot, n, ctx->d_mpartial, ctx->d_msums, nullptr));
     std::vector<MetricsSums> sums((size_t)n);
     HIP_TRY(ctx, hipMemcpyAsync(sums.data(), ctx->d_msums, (size_t)n * sizeof(MetricsSums), hipMemcpyDeviceToHost, cs));
     if (const int rc = read_overflow(ctx)) return rc;
-    for (int k = 0; k < n; ++k) fill_metrics(c, sums[(size_t)k], out[k]);
+    for (int k = 0; k < n; ++k) fill_metrics(vw, vh, sums[(size_t)k], out[k]);
     return WRENC_GPU_OK;
 }
 
@@ -1903,7 +1960,7 @@ int wrenc_gpu_test_metrics(wrenc_gpu_ctx* ctx, const uint8_t* const org[3], cons
         if (e == hipSuccess) e = hipMemcpy(d_pic, &pb, sizeof(pb), hipMemcpyHostToDevice);
     }
     if (e == hipSuccess)
-        e = launch_metrics(c, 0, d_pic, 0, 1, d_part, d_sums, d_map);
+        e = launch_metrics(c, c.width, c.height, 0, d_pic, 0, 1, d_part, d_sums, d_map);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(&sums, d_sums, sizeof(sums), hipMemcpyDeviceToHost);
     if (e == hipSuccess && ssim_map) e = hipMemcpy(map.data(), d_map, n_win * sizeof(float), hipMemcpyDeviceToHost);
@@ -1914,7 +1971,7 @@ int wrenc_gpu_test_metrics(wrenc_gpu_ctx* ctx, const uint8_t* const org[3], cons
     (void)hipFree(d_map);
     if (e != hipSuccess) (void)hipGetLastError();
     HIP_TRY(ctx, e);
-    fill_metrics(c, sums, *out);
+    fill_metrics(c.width, c.height, sums, *out);
     if (ssim_map) {
         const size_t at[3] = {0, (size_t)L.windows, (size_t)L.windows + (size_t)C.windows};
         for (int p = 0; p < 3; ++p)
@@ -1996,7 +2053,7 @@ void wrenc_gpu_free_host(wrenc_gpu_ctx* ctx, void* p) {
 int wrenc_gpu_encode_picture(wrenc_gpu_ctx* ctx, const uint8_t* y, const uint8_t* cb, const uint8_t* cr,
                              wrenc_gpu_picture* out) {
     if (!ctx) return WRENC_GPU_EINVAL;
-    int rc = wrenc_gpu_upload(ctx, 0, y, cb, cr, ctx->cfg.width, ctx->cfg.width / 2);
+    int rc = wrenc_gpu_upload(ctx, 0, y, cb, cr, ctx->vis_w, ctx->vis_w / 2);
     if (rc) return rc;
     rc = wrenc_gpu_encode(ctx, 0, 1);
     if (rc) return rc;

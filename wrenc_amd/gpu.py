@@ -23,6 +23,7 @@ EXPORTED_SYMBOLS = [
     "wrenc_gpu_alloc_host", "wrenc_gpu_free_host", "wrenc_gpu_encode_picture", "wrenc_gpu_set_schedule", "wrenc_gpu_last_schedule", "wrenc_gpu_stats_enable", "wrenc_gpu_last_encode_stats", "wrenc_gpu_last_encode_kernel_stats", "wrenc_gpu_final_pass_mismatches",
     "wrenc_gpu_test_fwd_dct", "wrenc_gpu_test_inv_dct", "wrenc_gpu_test_quantize",
     "wrenc_gpu_test_dequantize", "wrenc_gpu_test_predict", "wrenc_gpu_test_fwd_dct32", "wrenc_gpu_test_inv_dct32", "wrenc_gpu_test_quantize_p16", "wrenc_gpu_test_quantize_pk", "wrenc_gpu_test_set_wave_slots", "wrenc_gpu_test_scratch_overflows", "wrenc_gpu_test_head_ranges", "wrenc_gpu_test_avail_tab",
+    "wrenc_gpu_set_visible_size", "wrenc_gpu_visible_size", "wrenc_gpu_test_download_originals",
 ]
 
 
@@ -165,7 +166,10 @@ class Encoder:
     SliceEncoder::encode uses in place of the per-CTU split_ct loop."""
 
     def __init__(self, width, height, qp=26, max_split_depth=3, device=0, n_slots=1, config=None, extra_params=None,
-                 schedule=None):
+                 schedule=None, visible=None):
+        """width x height: the coded size, whole 32x32 CTUs.  visible=(w, h): the pictures are that size (even, at least
+        16x16, the coded size its round-up to multiples of 32): upload takes planes of it, the device replicates their last
+        column and row into the margin, and download_metrics reports that rectangle (wrenc_gpu_set_visible_size)."""
         self.lib = load_library()
         self.cfg = config if config is not None else default_config(width, height, qp, max_split_depth,
                                                                      device, n_slots, extra_params)
@@ -178,8 +182,15 @@ class Encoder:
             raise WrencGpuError(rc, self.lib.wrenc_gpu_last_error(None).decode())
         self._keep = {}
         self._pinned = []
+        self.vis_width, self.vis_height = self.width, self.height
         if schedule is not None:
             self.set_schedule(schedule)
+        if visible is not None:
+            try:
+                self.set_visible_size(*visible)
+            except WrencGpuError:
+                self.close()
+                raise
 
     def _check(self, rc):
         if rc:
@@ -205,9 +216,41 @@ class Encoder:
         y = np.ascontiguousarray(y, np.uint8)
         cb = np.ascontiguousarray(cb, np.uint8)
         cr = np.ascontiguousarray(cr, np.uint8)
-        assert y.shape == (self.height, self.width)
+        assert y.shape == (self.vis_height, self.vis_width)
+        assert cb.shape == cr.shape == (self.vis_height // 2, self.vis_width // 2)
         self._keep[slot] = (y, cb, cr)  # host buffers must outlive the async copy
-        self._check(self.lib.wrenc_gpu_upload(self.ctx, slot, _p(y), _p(cb), _p(cr), self.width, self.width // 2))
+        self._check(self.lib.wrenc_gpu_upload(self.ctx, slot, _p(y), _p(cb), _p(cr), self.vis_width, self.vis_width // 2))
+
+    def upload_strided(self, slot, y, cb, cr):
+        """upload of planes that are views into wider arrays (last axis contiguous): their row strides go to the C ABI."""
+        planes = [np.asarray(a) for a in (y, cb, cr)]
+        assert all(a.dtype == np.uint8 and a.strides[1] == 1 for a in planes)
+        assert planes[0].shape == (self.vis_height, self.vis_width) and planes[1].strides[0] == planes[2].strides[0]
+        assert planes[1].shape == planes[2].shape == (self.vis_height // 2, self.vis_width // 2)
+        self._keep[slot] = tuple(planes)
+        self._check(self.lib.wrenc_gpu_upload(self.ctx, slot, _p(planes[0]), _p(planes[1]), _p(planes[2]),
+                                              planes[0].strides[0], planes[1].strides[0]))
+
+    def set_visible_size(self, vis_w, vis_h):
+        """wrenc_gpu_set_visible_size: before the first upload; the coded size itself restores the plain behaviour."""
+        self.lib.wrenc_gpu_set_visible_size.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        self._check(self.lib.wrenc_gpu_set_visible_size(self.ctx, int(vis_w), int(vis_h)))
+        self.vis_width, self.vis_height = int(vis_w), int(vis_h)
+
+    def visible_size(self):
+        w, h = C.c_int(), C.c_int()
+        self.lib.wrenc_gpu_visible_size.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        self._check(self.lib.wrenc_gpu_visible_size(self.ctx, C.byref(w), C.byref(h)))
+        return w.value, h.value
+
+    def download_originals(self, slot):
+        """Test entry: the coded-size original planes (y, cb, cr) the slot holds, margin included."""
+        y = np.zeros((self.height, self.width), np.uint8)
+        cb = np.zeros((self.height // 2, self.width // 2), np.uint8)
+        cr = np.zeros_like(cb)
+        self.lib.wrenc_gpu_test_download_originals.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._check(self.lib.wrenc_gpu_test_download_originals(self.ctx, slot, _p(y), _p(cb), _p(cr)))
+        return y, cb, cr
 
     def encode(self, first_slot=0, n_pictures=1):
         self._check(self.lib.wrenc_gpu_encode(self.ctx, first_slot, n_pictures))
@@ -283,11 +326,12 @@ class Encoder:
 
     def download_metrics(self, first_slot, n):
         """PSNR / SSIM of n encoded slots from the device's sums (include/wrenc_gpu.h, wrenc_gpu_download_metrics): per
-        picture {"PSNR": {...}, "SSIM": {...}} as metrics.frame_metrics gives them, the raw sums under "_raw"."""
+        picture {"PSNR": {...}, "SSIM": {...}} as metrics.frame_metrics gives them, the raw sums under "_raw".  With a visible
+        size: of that rectangle."""
         outs = (Metrics * max(n, 1))()
         self.lib.wrenc_gpu_download_metrics.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         self._check(self.lib.wrenc_gpu_download_metrics(self.ctx, first_slot, n, outs))
-        return [metrics_values(self.width, self.height, outs[k]) for k in range(n)]
+        return [metrics_values(self.vis_width, self.vis_height, outs[k]) for k in range(n)]
 
     def download_complexity(self, first_slot, n, ctu_map=True):
         """Hadamard activity of n slots' originals (include/wrenc_gpu.h, wrenc_gpu_download_complexity), before or after
