@@ -119,6 +119,11 @@ __device__ __forceinline__ int lane_fresh() {
 }
 #define LANE lane_fresh()
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+// a 64-bit value, half by half
+__device__ __forceinline__ long long uni_i64(long long v) {
+    const unsigned long long x = (unsigned long long)v;
+    return (long long)(((unsigned long long)(unsigned)uni((int)(x >> 32)) << 32) | (unsigned)uni((int)x));
+}
 
 // SSD and level cost of the luma block and of the chroma pair of one evaluated candidate
 struct EvalParts {
@@ -134,8 +139,7 @@ struct UF {
     T v;
     __device__ __forceinline__ T get() const {
         if constexpr (sizeof(T) == 8) {
-            const unsigned long long x = (unsigned long long)v;
-            return (T)(((unsigned long long)(unsigned)uni((int)(x >> 32)) << 32) | (unsigned)uni((int)x));
+            return (T)uni_i64((long long)v);
         } else if constexpr (sizeof(T) == 4 && !(T(0.5f) == T(0))) {
             return __int_as_float(uni(__float_as_int((float)v)));
         } else {
@@ -190,18 +194,21 @@ struct EvalPartsU {
 struct LeafSt {
     UF<uint8_t> cont;                   // where to continue with the result of the pending request
     UF<uint8_t> op_ml, op_mc, op_act;   // modes / activity of the pending full evaluation
-    UF<uint8_t> tree, bx, by, lg;
+    uint8_t pad0_;                      // (every leaf is a SINGLE_TREE block; removed fields stay as padding: snap_leaf)
+    UF<uint8_t> bx, by, lg;
     UF<uint8_t> need_refs0, need_refs1; // reference samples of the block not built yet (luma / chroma pair)
     UF<uint8_t> need_org;               // originals of the block not staged in LDS yet (blocks <= 16x16)
-    UF<uint8_t> step;
-    UF<uint8_t> cur_mode, mode, cclm_mode, dm_mode;
+    uint8_t pad1_;
+    UF<uint8_t> cur_mode, mode, cclm_mode;
+    uint8_t pad2_;
     UF<uint8_t> holder, evalr;          // team schedule: the member whose slot 0 holds the best candidate / the CCLM evaluator
     UF<uint8_t> luma_mode, chroma_mode; // result
     UF<uint8_t> best_cls;               // header-bit class (mpm_class) of the best luma mode
     UF<uint8_t> need_save, tile_best;   // best candidate's reconstruction: not saved yet / still in the tile
     UF<uint8_t> slot;                   // the scratch slot the best candidate's reconstruction is saved to
     UF<float> best_cost;                // best of {planar, DC} so far / of {planar, DC, dir}
-    UF<float> cur_cost, c0;
+    UF<float> cur_cost;
+    uint32_t pad3_;
     UF<float> cost;                     // result
     EvalPartsU e_best;
 };
@@ -238,9 +245,9 @@ struct EvalPartsSF {
     }
 };
 struct LeafSF {
-    SF<uint8_t> cont, op_ml, op_mc, op_act, tree, bx, by, lg, need_refs0, need_refs1, need_org, step, cur_mode, mode,
-        cclm_mode, dm_mode, holder, evalr, luma_mode, chroma_mode, best_cls, need_save, tile_best, slot;
-    SF<float> best_cost, cur_cost, c0, cost;
+    SF<uint8_t> cont, op_ml, op_mc, op_act, bx, by, lg, need_refs0, need_refs1, need_org, cur_mode, mode,
+        cclm_mode, holder, evalr, luma_mode, chroma_mode, best_cls, need_save, tile_best, slot;
+    SF<float> best_cost, cur_cost, cost;
     EvalPartsSF e_best;
 };
 static_assert(sizeof(LeafSt) == 64, "snap_leaf reads the struct as 16 dwords");
@@ -255,11 +262,11 @@ __device__ __forceinline__ LeafSF snap_leaf(LeafSt& l) {
 #define SNAP_F32(f)                                                                       \
     s.f.v = __int_as_float(__builtin_amdgcn_readlane(w, (int)(offsetof(LeafSt, f) >> 2))); \
     s.f.p = &l.f
-    SNAP_U8(cont); SNAP_U8(op_ml); SNAP_U8(op_mc); SNAP_U8(op_act); SNAP_U8(tree); SNAP_U8(bx); SNAP_U8(by); SNAP_U8(lg);
-    SNAP_U8(need_refs0); SNAP_U8(need_refs1); SNAP_U8(need_org); SNAP_U8(step); SNAP_U8(cur_mode); SNAP_U8(mode);
-    SNAP_U8(cclm_mode); SNAP_U8(dm_mode); SNAP_U8(holder); SNAP_U8(evalr); SNAP_U8(luma_mode); SNAP_U8(chroma_mode);
+    SNAP_U8(cont); SNAP_U8(op_ml); SNAP_U8(op_mc); SNAP_U8(op_act); SNAP_U8(bx); SNAP_U8(by); SNAP_U8(lg);
+    SNAP_U8(need_refs0); SNAP_U8(need_refs1); SNAP_U8(need_org); SNAP_U8(cur_mode); SNAP_U8(mode);
+    SNAP_U8(cclm_mode); SNAP_U8(holder); SNAP_U8(evalr); SNAP_U8(luma_mode); SNAP_U8(chroma_mode);
     SNAP_U8(best_cls); SNAP_U8(need_save); SNAP_U8(tile_best); SNAP_U8(slot);
-    SNAP_F32(best_cost); SNAP_F32(cur_cost); SNAP_F32(c0); SNAP_F32(cost);
+    SNAP_F32(best_cost); SNAP_F32(cur_cost); SNAP_F32(cost);
 #undef SNAP_U8
 #undef SNAP_F32
     constexpr int eb = (int)(offsetof(LeafSt, e_best) >> 2);
@@ -286,7 +293,8 @@ __device__ __forceinline__ LeafSF snap_leaf(LeafSt& l) {
 struct CtuSt {
     UF<uint8_t> cont, in_leaf, xpar; // xpar: parity of the team's next exchange
     UF<uint8_t> level, bx, by, lg, max_depth;
-    UF<uint8_t> i8, z, rl, rc;       // 4x4 child index, final-pass z-order index, regen modes
+    uint8_t pad0_;
+    UF<uint8_t> z, rl, rc;           // final-pass z-order index, regen modes
     UF<uint8_t> rbx, rby, rlg;       // regen block
     UF<uint8_t> ns_luma_cur, ns_chroma_cur;
     UF<uint8_t> pend, pbx, pby, plg, pslot; // reconstruction save to attach to the next request
@@ -296,7 +304,9 @@ struct CtuSt {
     // level schedule (team kernel at max-split-depth 3, dev_search.h): on | this member's unit | end of its final-pass range
     UF<uint8_t> lvmode, lv_i, zend;
     UF<uint8_t> fz_on;               // the final pass has begun (Lds::lev_was / lev_now are loaded)
-    UF<float> ret, ns_cost_cur, split8, ctu_cost;
+    UF<float> ret, ns_cost_cur;
+    uint32_t pad1_;
+    UF<float> ctu_cost;
     UF<float> lv_acc0, lv_acc1; // level schedule: running split cost of the open 32x32 / 16x16 node
     LeafSt leaf;
 };
@@ -317,7 +327,7 @@ struct __attribute__((aligned(16))) Lds {
     // Transform working set, time-multiplexed through a full evaluation (dev_search.h):
     //   r1: residual -> coefficients -> Viterbi chunk costs / levels -> inverse-transform intermediate -> residual
     //   r2: stage-1 DCT output (i32, blocks up to 16x16; the 32x32 transform keeps it in MFMA accumulators) ->
-    //       scan-order coefficients (+ chroma chunk costs of the merged pass) -> dequantised^T
+    //       scan-order coefficients -> dequantised^T
     // Bytes [kOrgLeaf, 2048) of r2 hold the originals of a block of at most 16x16 for its whole leaf search
     // (dev_predict.h); no stage of a block that small reaches them.
     // 2 KB each: five workgroups of four waves per CU (LDS is what caps the waves in flight, and the kernel's

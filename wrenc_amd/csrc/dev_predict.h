@@ -286,7 +286,8 @@ __device__ __forceinline__ CclmParams cclm_params_all(const Ctx& c, int tx, int 
 constexpr int kOrgStage = 512;
 // Blocks of at most 16x16 luma samples keep their originals in LDS for the WHOLE leaf search (SAD lists and
 // full evaluations alike): 256 B luma + 2 x 64 B chroma in the last 384 bytes of r2, which no stage of a
-// block that small touches (forward DCT <= 1088 B, quantize3 ends at byte 1536, dequantise <= 512, the angular
+// block that small touches (forward DCT <= 1088 B, the scan-order coefficients of a pack of two 16x16 candidates
+// end at byte 1536 (quantize_pk<4>, the largest user), dequantise <= 512, the angular
 // table of a prediction at 1280..1488; SAD-list tables are in r1).  Staged once per leaf (stage_org_leaf); a
 // 32x32 block has no such room: its SAD lists stage per list (stage_org), its full evaluations read the picture.
 constexpr int kOrgLeaf = 1664;
@@ -559,7 +560,7 @@ __device__ __forceinline__ int predict(Ctx c, int comp, int tx, int ty, int tlg,
 }
 
 // Prediction of up to four CANDIDATES of one 4x4 luma block at once (the packed 4x4 leaf search, dev_search.h
-// K_LEAF4): candidate s = lanes 16 s .. 16 s + 15, lane = (s, sample); `mode` is the lane's candidate mode
+// leaf4_search): candidate s = lanes 16 s .. 16 s + 15, lane = (s, sample); `mode` is the lane's candidate mode
 // (PLANAR, DC or 2..66; kNoMode lanes compute nothing).  Same arithmetic as predict() for comp 0, tlg 2 (a block of
 // 16 samples never uses the filtered references); the projected main reference of an angular candidate is built
 // by the candidate's own 16 lanes into tab4 (16 bytes per candidate, in r2 below kOrgLeaf).  build_refs(c, 0, ..)

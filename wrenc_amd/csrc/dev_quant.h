@@ -522,219 +522,8 @@ __device__ __forceinline__ long long quantize_solo(Ctx c, int lg, int nb, int* o
     return sum;
 }
 
-// Dependent quantisation of the three transform blocks of one candidate in ONE pass: luma
-// n0 x n0 at r1[0, P0), Cb and Cr (n0/2)^2 at r1[P0, P0 + Pc) and r1[P0 + Pc, P0 + 2 Pc), n0 = 8 or
-// 16 (search only).  Same algorithm as quantize_solo without the head exit; the chroma chains are a quarter as
-// long as the luma chain, so a chunk is 64 luma + 16 + 16 chroma positions and the chroma blocks ride along for
-// free: the wave walks its three blocks in quads 0..2.  `active == false`: nothing to do.
-// Scratch: r2 = [scan-order coefficients | chroma chunk entries], r1 = luma chunk entries (the coefficients are
-// dead after the gather and every level is written at the end), decw.
-__device__ __forceinline__ void quantize3(Ctx c, int lg0, bool active, int* overflow, long long* lvl_y,
-                                          long long* lvl_c, bool* any_y, bool* any_c) {
-    c = uni(c);
-    lg0 = uni(lg0);
-    const CONST_AS DevConst* k = c.k;
-    const int lgc = lg0 - 1;
-    const int P0 = 1 << (2 * lg0), Pc = P0 >> 2, T = P0 + 2 * Pc;
-    const int sh0 = lg0 + 4, shc = lgc + 4; // 8 + lg - 5 + 1 (quantizer.rs:558-569)
-    const int lsc = k->lsc;
-    const CONST_AS uint16_t* scan0 = k->scan_idx[lg0 - 2];
-    const CONST_AS uint16_t* scanc = k->scan_idx[lgc - 2];
-    int16_t* tcs = (int16_t*)SH.r2;               // [T]: coefficient in reverse-scan order, block after block
-    constexpr int kCcByte = 768;                  // 2 * T <= 768 for T <= 384
-    int32_t* cc0 = (int32_t*)SH.r1;                     // chunk, luma: [64][6] ints
-    int32_t* cc1 = (int32_t*)((char*)SH.r2 + kCcByte);  // chunk, Cb | Cr: [32][6] ints (ends at byte 1536 < kOrgLeaf)
-    *lvl_y = 0;
-    *lvl_c = 0;
-    PROF_MARK(q0_);
-    int istar0 = P0, istar1 = Pc, istar2 = Pc;
-    bool any_nz = false;
-    *any_y = false;
-    *any_c = false;
-    if (active) {
-        int first0 = P0, first1 = Pc, first2 = Pc, nzl = 0;
-        for (int idx = LANE; idx < T; idx += 64) {
-            const int b = idx < P0 ? 0 : (idx < P0 + Pc ? 1 : 2);
-            const int boff = b == 0 ? 0 : (b == 1 ? P0 : P0 + Pc);
-            const int p = idx - boff;
-            const int sh = b == 0 ? sh0 : shc;
-            const int off = (1 << sh) >> 1;
-            const int tc = SH.r1[boff + (b == 0 ? scan0[p] : scanc[p])];
-            nzl |= tc;
-            const int qd = quotient(k, tc, sh, off);
-            tcs[idx] = (int16_t)tc;
-            if (tc != 0 && (qd >> 1) > 0) {
-                if (b == 0)
-                    first0 = min(first0, p);
-                else if (b == 1)
-                    first1 = min(first1, p);
-                else
-                    first2 = min(first2, p);
-            }
-        }
-        istar0 = wave_min_i32(first0);
-        istar1 = wave_min_i32(first1);
-        istar2 = wave_min_i32(first2);
-        any_nz = __ballot(nzl != 0) != 0ULL;
-    }
-    if (!any_nz) return; // three zero blocks (or an inactive call): nothing to walk
-    PROF_MARK(q1_);
-    PROF_ADD2(PH_QPRE, q0_, q1_);
-    const int ldq1 = (int)ldq_at(c, 1);
-    const int st = LANE & 3;
-    const int cls = st == 0 ? 0 : (st == 1 ? 1 : 2);
-    // walker quads: quad gq = LANE / 4 walks block kind gq (0 luma, 1 Cb, 2 Cr)
-    const int gq = LANE >> 2;
-    const int wb = min(gq, 2);
-    const bool walker = gq < 3;
-    const int32_t* wcc = wb == 0 ? (const int32_t*)SH.r1
-                                 : (const int32_t*)((const char*)SH.r2 + kCcByte) + (wb == 1 ? 0 : 16) * 6;
-    uint16_t* wdec = (uint16_t*)SH.decw + (wb == 0 ? 0 : (wb == 1 ? (P0 >> 2) : (P0 >> 2) + (Pc >> 2)));
-    const int wnsb = wb == 0 ? 4 : 1; // sub-blocks of the walker's block per chunk
-    int C = 0;
-    int ovf = 0;
-    const int nch = P0 >> 6;
-    for (int ch = 0; ch < nch; ++ch) {
-        const int base0 = P0 - 64 * (ch + 1), basec = Pc - 16 * (ch + 1);
-        PROF_MARK(qb0_);
-        WSYNC();
-        {
-#pragma unroll 1
-            for (int pass = 0; pass < 2; ++pass) {
-                const int e = LANE + 64 * pass;
-                const bool mine = e < 96;
-                const int b = e < 64 ? 0 : (e < 80 ? 1 : 2);
-                const int i = b == 0 ? e : ((e - 64) & 15);
-                const int p = (b == 0 ? base0 : basec) + i;
-                const int Pb = b == 0 ? P0 : Pc;
-                const int gidx = (b == 0 ? 0 : (b == 1 ? P0 : P0 + Pc)) + p;
-                int par0 = 0, par1 = 0, adj = 0;
-                if (mine) {
-                    const int sh = b == 0 ? sh0 : shc;
-                    const int tc = tcs[gidx];
-                    chunk_entry(c, b == 0 ? cc0 + e * 6 : cc1 + (e - 64) * 6, tc, quotient(k, tc, sh, (1 << sh) >> 1), p == Pb - 1,
-                                p <= (b == 0 ? istar0 : (b == 1 ? istar1 : istar2)), sh, (1 << sh) >> 1, lsc, ldq1, &par0,
-                                &par1, &adj, &ovf);
-                }
-                const unsigned long long b0 = __ballot(mine && par0), b1 = __ballot(mine && par1),
-                                         ba = __ballot(mine && adj);
-                if (mine && (LANE & 15) == 0) {
-                    // pass 0: luma sub-block LANE / 16; pass 1: lanes 0..15 Cb, 16..31 Cr (one sub-block each)
-                    uint16_t* pm = SH.q_pm[b][b == 0 ? (LANE >> 4) : 0];
-                    pm[0] = (uint16_t)(b0 >> LANE);
-                    pm[1] = (uint16_t)(b1 >> LANE);
-                    pm[2] = (uint16_t)((ba >> (LANE + 15)) & 1);
-                }
-            }
-        }
-        WSYNC();
-        PROF_MARK(qb1_);
-        if (walker) {
-            for (int sbi = wnsb - 1; sbi >= 0; --sbi) { // one 4x4 sub-block per iteration
-                const int g16 = sbi * 16;
-                const uint16_t* pm = SH.q_pm[wb][sbi];
-                const unsigned parmask = pm[st > 1 ? 1 : 0];
-                const bool adj = st == 0 && pm[2] != 0;
-                int2 cur[16];
-#pragma unroll
-                for (int kk = 0; kk < 16; ++kk) cur[kk] = *(const int2*)&wcc[(g16 + kk) * 6 + 2 * cls];
-                unsigned bits = 0;
-#pragma unroll
-                for (int kk = 15; kk >= 0; --kk) {
-                    const int2 en = cur[kk];
-                    const int KA = en.x + dpp_quad<0xD8>(C); // C[trans[s][0]]: quad_perm [0,2,1,3]
-                    const int KB = en.y + dpp_quad<0x72>(C); // C[trans[s][1]]: quad_perm [2,0,3,1]
-                    C = min(KA, KB) & ~1;
-                    bits = shift_in_less(bits, KB, KA);
-                    if (kk == 15) { // first position of a sub-block in coding order (:512-514)
-                        const bool choseB = KB < KA;
-                        const bool pick1 = choseB != (((parmask >> 15) & 1) != 0);
-                        if (!pick1 && adj) C -= 2 * ldq1;
-                    }
-                }
-                bits ^= parmask; // choseB -> pick1
-                int m = min(C, dpp_quad<0xB1>(C));
-                m = min(m, dpp_quad<0x4E>(m));
-                C -= m;
-                wdec[(((wb == 0 ? base0 : basec) + g16) >> 4) * 4 + st] = (uint16_t)bits;
-            }
-        }
-        PROF_MARK(qb3_);
-        PROF_ADD2(PH_QB_PRE, qb0_, qb1_);
-        PROF_ADD2(PH_QB_WALK, qb1_, qb3_);
-    }
-    WSYNC();
-    PROF_MARK(q2_);
-    PROF_ADD2(PH_QBACK, q1_, q2_);
-    // ---- forward trace + level cost: lanes 0..31 luma, 32..47 Cb, 48..63 Cr ----
-    const int b = LANE < 32 ? 0 : (LANE < 48 ? 1 : 2);
-    const int lane_in = b == 0 ? LANE : (LANE & 15);
-    const int Pb = b == 0 ? P0 : Pc;
-    const int per = b == 0 ? (P0 >> 5) : (Pc >> 4); // P0 / 32 = Pc / 16 * 2
-    const int boff = b == 0 ? 0 : (b == 1 ? P0 : P0 + Pc);
-    const int p0 = lane_in * per;
-    const int16_t* btcs = tcs + boff;
-    const int shb = b == 0 ? sh0 : shc, offb = (1 << shb) >> 1;
-    const uint16_t* bdec = (const uint16_t*)SH.decw + (b == 0 ? 0 : (b == 1 ? (P0 >> 2) : (P0 >> 2) + (Pc >> 2)));
-    int fmap = kMapId;
-    const DecMasks dm = dec_masks(bdec, p0); // a lane's positions lie in one sub-block (per divides 16)
-    for (int j = 0; j < per; ++j) {
-        const int p = p0 + j;
-        const int tc = btcs[p];
-        fmap = compose_map(position_map(tc, quotient(k, tc, shb, offb), p == Pb - 1, dec_nib(dm, p)), fmap);
-    }
-    int pre = fmap;
-    pre = compose_map(pre, __builtin_amdgcn_update_dpp(kMapId, pre, 0x111, 0xF, 0xF, false)); // row_shr:1
-    pre = compose_map(pre, __builtin_amdgcn_update_dpp(kMapId, pre, 0x112, 0xF, 0xF, false)); // row_shr:2
-    pre = compose_map(pre, __builtin_amdgcn_update_dpp(kMapId, pre, 0x114, 0xF, 0xF, false)); // row_shr:4
-    pre = compose_map(pre, __builtin_amdgcn_update_dpp(kMapId, pre, 0x118, 0xF, 0xF, false)); // row_shr:8
-    pre = compose_map(pre, __builtin_amdgcn_update_dpp(kMapId, pre, 0x142, 0x2, 0xF, false)); // row_bcast:15 -> row 1 (luma)
-    int entry = __builtin_amdgcn_update_dpp(0, pre, 0x138, 0xF, 0xF, false) & 3; // wave_shr:1
-    if (lane_in == 0) entry = 0;
-    long long sum_nz = 0;
-    unsigned zmask = 0;
-    int fnz = Pb;
-    {
-        int state = entry;
-        for (int j = 0; j < per; ++j) {
-            const int p = p0 + j;
-            const int tc = btcs[p];
-            SH.r1[boff + (b == 0 ? scan0[p] : scanc[p])] = (int16_t)emit_level(
-                c, tc, quotient(k, tc, shb, offb), p == Pb - 1, dec_nib(dm, p), p, j, state, zmask, sum_nz, fnz, ovf);
-        }
-    }
-    // zeros before a block's first non-zero level cost nothing: minimum per block (rows 0-1 | 2 | 3)
-    {
-        const int rm = row_min_i32(fnz);
-        const int m0 = min(__builtin_amdgcn_readlane(rm, 0), __builtin_amdgcn_readlane(rm, 16));
-        const int m1 = __builtin_amdgcn_readlane(rm, 32), m2 = __builtin_amdgcn_readlane(rm, 48);
-        const int pf = b == 0 ? m0 : (b == 1 ? m1 : m2);
-        sum_nz += (long long)__popc(zmask >> min(max(pf - p0 + 1, 0), 16)) * SHT.lv[0];
-        *any_y = m0 < P0;
-        *any_c = m1 < Pc || m2 < Pc;
-    }
-    // level cost of the luma block (rows 0-1) and of the chroma pair (rows 2-3), three limbs each
-    {
-        const long long hi = sum_nz >> 24;
-        const int ra = row_sum_i32((int)(sum_nz & 0xFFFFFF)), rb = row_sum_i32((int)(hi & 0xFFFFFF)),
-                  rc = row_sum_i32((int)(hi >> 24));
-        const long long ya = (long long)(unsigned)(__builtin_amdgcn_readlane(ra, 0) + __builtin_amdgcn_readlane(ra, 16));
-        const long long yb = (long long)(unsigned)(__builtin_amdgcn_readlane(rb, 0) + __builtin_amdgcn_readlane(rb, 16));
-        const long long yc = (long long)(__builtin_amdgcn_readlane(rc, 0) + __builtin_amdgcn_readlane(rc, 16));
-        const long long ca = (long long)(unsigned)(__builtin_amdgcn_readlane(ra, 32) + __builtin_amdgcn_readlane(ra, 48));
-        const long long cb = (long long)(unsigned)(__builtin_amdgcn_readlane(rb, 32) + __builtin_amdgcn_readlane(rb, 48));
-        const long long cc2 = (long long)(__builtin_amdgcn_readlane(rc, 32) + __builtin_amdgcn_readlane(rc, 48));
-        *lvl_y = ya + ((yb + (yc << 24)) << 24);
-        *lvl_c = ca + ((cb + (cc2 << 24)) << 24);
-    }
-    if (__ballot(ovf != 0) != 0ULL) *overflow = 1;
-    WSYNC();
-    PROF_MARK(q3_);
-    PROF_ADD2(PH_QTRACE, q2_, q3_);
-}
-
 // Dependent quantisation of nb <= 4 luma blocks of 4x4 at once (the candidates of a packed 4x4 leaf search,
-// dev_search.h K_LEAF4): block b = lanes 16 b .. 16 b + 15, one lane per position, one quad walks each block's
+// dev_search.h leaf4_search): block b = lanes 16 b .. 16 b + 15, one lane per position, one quad walks each block's
 // 16 positions (a single chunk: no barrier of any kind).  Same algorithm and arithmetic as quantize_solo; block b's
 // level cost (block_splitter.rs:436-458) comes back in lvl[b], "has a non-zero level" in bit b of *any_mask.
 // Coefficients r1[16 b ..] -> levels in place (a lane keeps its coefficient in a register).  Scratch: r1 chunk

@@ -9,7 +9,8 @@ namespace wrenc {
 // ---------------------------------------------------------------------------
 // Evaluation requests and the evaluator
 // ---------------------------------------------------------------------------
-enum { K_SADLIST = 0, K_FULL = 1, K_NOP = 2, K_SADSEARCH = 3, K_CCLMSEARCH = 4, K_LEAF4 = 5, K_LEAFC4 = 6, K_LEAF8 = 7, K_LEAF16 = 8, K_SPLIT8 = 9, K_SERVE4 = 10 };
+// (the numbers index the profile build's counters, tools/phase_profile.py: 6 stays free)
+enum { K_SADLIST = 0, K_FULL = 1, K_NOP = 2, K_SADSEARCH = 3, K_CCLMSEARCH = 4, K_SERVE8 = 5, K_LEAF8 = 7, K_LEAF16 = 8, K_SPLIT8 = 9, K_SERVE4 = 10 };
 enum { COPY_NONE = 0, COPY_SAVE = 1, COPY_RESTORE = 2, COPY_PULL = 3 };
 
 // Split cut (wave schedule): a node's children are searched only until their partial cost, summed in z-order in f32 from
@@ -36,7 +37,7 @@ constexpr bool kSplitCut = true;
 // strict-less update, so a candidate whose floor is >= the running best cannot win: it is not evaluated, and the leaf
 // returns what it returns when that candidate loses.  Off in the trace build, which records every candidate, and with
 // -DWRENC_EXHAUSTIVE_CANDIDATES (A/B measurements, tools/README.md); the team and level schedules, whose members run
-// the two halves of a leaf at the same time, stay exhaustive.
+// pack A may come from the pack-A server, stay exhaustive.
 #if defined(WRENC_TRACE) || defined(WRENC_EXHAUSTIVE_CANDIDATES)
 constexpr bool kCandidateCut = false;
 #else
@@ -44,26 +45,26 @@ constexpr bool kCandidateCut = true;
 #endif
 
 struct Req {
-    int kind;       // K_SADLIST: predict + SAD of a list of modes (block_splitter.rs:64-108, 476-522);
-                    // K_FULL: predict .. reconstruct (:146-185); K_SADSEARCH: the whole SAD part of a leaf search in
+    int kind;       // K_FULL: predict .. reconstruct (block_splitter.rs:146-185) of a 32x32 candidate or a final-pass block;
+                    // K_NOP: nothing but the pre_copy;
+                    // K_SADSEARCH: the whole SAD part of a 32x32 leaf search in
                     // one request -- the 13 directional candidates, their first minimum and the two step-search
                     // rounds around it (:899-973): returns the mode (Res::imin) and its SAD (Res::vmin);
-                    // K_CCLMSEARCH: the CCLM part of a leaf search in one request -- the SADs of LT / T / L_CCLM, the
+                    // K_CCLMSEARCH: the CCLM part of a 16x16 / 32x32 leaf search in one request -- the SADs of LT / T / L_CCLM, the
                     // pick (:847-854) and the full evaluation of the chroma pair with it: Res::imin = the mode, + parts;
-                    // K_LEAF4: the whole search of a 4x4 DUAL_TREE_LUMA leaf (:886-1078) in one request, its full candidates
-                    // evaluated side by side in the wave's four 16-lane rows (leaf4_search): Res::imin = the mode, vmin = its cost;
-                    // K_LEAFC4: the same for the DUAL_TREE_CHROMA leaf of a split 8x8 CU (:794-885; leafc4_search), mc = the DM mode
+                    // K_SADLIST: the SAD of the chroma pair under the one CCLM mode mc (:476-522; the team's 32x32
+                    // candidate at max-split-depth 0, a probe per member): Res::v0;
                     // K_LEAF8: the whole search of an 8x8 SINGLE_TREE leaf (:886-1078) in one request, its full candidates
                     // evaluated in packs of two and three (leaf8_search): Res::imin / imin2 = luma / chroma mode, vmin = the cost;
-                    // n = which parts run here (bit 0 pack {planar, DC}, bit 1 the SAD search + pack {cm, cm - 1, cm + 1},
-                    // bit 2 the CCLM part on the winner ml with DM chroma cost fcur)
+                    // K_SERVE8 / K_SERVE4 (team kernel, member 0): pack {planar, DC} of member 2's 8x8 leaf / member 3's 4x4
+                    // luma leaf at (tx, ty), results in this wave's LDS (serve_pack8 / serve_pack4);
                     // K_SPLIT8: the split candidate of an 8x8 CU in one request: its four DUAL_TREE_LUMA 4x4 leaf searches, then the
                     // DUAL_TREE_CHROMA one (split8_search); Res::vmin = the split cost (:1116-1123)
                     // K_LEAF16: the five full candidates of a 16x16 SINGLE_TREE leaf and its SAD search in one request, the
                     // candidates in packs of two (leaf16_search): Res::imin = the best luma mode, vmin = its cost, + its parts
     int comps;      // bit 0: luma block, bit 1: Cb+Cr pair
     int tx, ty, tlg;
-    int ml, mc;     // K_FULL: luma / chroma mode
+    int ml, mc;     // K_FULL: luma / chroma mode; K_SADLIST: mc = the CCLM mode
     bool active;    // false: the request computes nothing (a candidate the reference skips keeps its place in the sequence)
     bool refs0, refs1; // (re)build the luma / chroma reference samples of the block first
     bool final;     // final pass: store the levels, count reconstruction changes
@@ -73,26 +74,35 @@ struct Req {
     // xchg: the team exchanges results after this request
     int copy_from;
     bool xchg;
-    int n;          // K_SADLIST: number of entries
     int tree;       // tree type of the leaf that asks (diagnostic trace only)
     // before the evaluation: save the block's reconstruction to a slot / restore it from there
     // (the reference's cache_reconsts / restore_reconsts, block_splitter.rs:807-840, 1085-1145)
     int pre_copy, copy_comps, copy_slot, copy_tx, copy_ty, copy_tlg;
-    unsigned long long modes_lo, modes_hi; // K_SADLIST: one byte per entry (8 + 8), the same mode for luma and chroma
-    float fcur;     // K_LEAF8, part 4 alone (team schedule): the winner's DM chroma cost (:1040)
-                    // K_SPLIT8: the 8x8 node's unsplit cost, the search stops once the split's partial cost is greater
+    float fcur;     // K_SPLIT8: the 8x8 node's unsplit cost, the search stops once the split's partial cost is greater
                     // (kSplitCut; +inf = search every leaf)
 };
 
 struct Res {
-    // K_FULL: SSD and level cost of the luma block and of the chroma pair
+    // K_FULL, K_CCLMSEARCH, K_LEAF8, K_LEAF16: SSD and level cost of the luma block and of the chroma pair
     uint32_t ssd_y, ssd_c;
     long long lvl_y, lvl_c;
-    // K_SADLIST: costs of the first three entries, first minimum (strict <) and its index
-    float v0, v1, v2, vmin;
-    int imin;
+    float v0;       // K_SADLIST: the SAD
+    float vmin;     // K_SADSEARCH: the SAD of the mode found; the packed searches: the cost
+    int imin;       // the mode found (K_SADSEARCH, K_CCLMSEARCH) / the luma mode (K_LEAF8, K_LEAF16)
     int imin2;      // K_LEAF8: the chroma mode
 };
+// nothing evaluated: no parts, f32::MAX, PLANAR
+__device__ __forceinline__ Res res_none() {
+    Res r;
+    r.ssd_y = 0;
+    r.ssd_c = 0;
+    r.lvl_y = 0;
+    r.lvl_c = 0;
+    r.v0 = r.vmin = 3.40282347e+38f;
+    r.imin = 0;
+    r.imin2 = 0;
+    return r;
+}
 
 __device__ __forceinline__ float uni_f(float v) { return __int_as_float(uni(__float_as_int(v))); }
 
@@ -273,37 +283,6 @@ __device__ __forceinline__ void copy_block(const Ctx& c, int mode, int comps, in
     WSYNC();
 }
 
-// SADs of a list of n angular modes (one byte each in lo | hi; kNoMode = not evaluated, f32::MAX in the reference):
-// SADs of the first two entries, the first minimum (smallest (sad, index) pair) and its index; kNoSad where none
-struct ListOut {
-    unsigned s0, s1, s2, smin;
-    int imin;
-};
-__device__ __forceinline__ ListOut angular_list(const Ctx& c, const Req& q, int n, unsigned long long lo, unsigned long long hi) {
-    constexpr unsigned kNoSad = 0xFFFFFFFFu;
-    ListOut o;
-    o.s0 = o.s1 = o.s2 = o.smin = kNoSad;
-    o.imin = 0;
-    const unsigned acc = sad_list_angular(c, q.comps, q.tx, q.ty, q.tlg, n, lo, hi);
-    const int my_mode = LANE < n ? (int)(((LANE < 8 ? lo : hi) >> (8 * (LANE & 7))) & 255u) : kNoMode;
-    if (c.trace && my_mode != kNoMode)
-        TRACE_REC(c.ctu_x + q.tx, c.ctu_y + q.ty, q.tlg, q.tree, (q.comps & 1) ? 0 : 2, (q.comps & 1) ? my_mode : 0, my_mode,
-                  __float_as_int((float)acc));
-    // first minimum = smallest (sad, index) pair
-    const int key = my_mode != kNoMode ? (int)((acc << 4) | (unsigned)LANE) : 0x7FFFFFFF;
-    const int kmin = wave_min_i32(key);
-    if (kmin != 0x7FFFFFFF) {
-        o.smin = (unsigned)kmin >> 4;
-        o.imin = kmin & 15;
-    }
-    const unsigned a0 = (unsigned)__builtin_amdgcn_readlane((int)acc, 0), a1 = (unsigned)__builtin_amdgcn_readlane((int)acc, 1),
-                   a2 = (unsigned)__builtin_amdgcn_readlane((int)acc, 2);
-    if ((int)(lo & 255u) != kNoMode) o.s0 = a0;
-    if (n > 1 && (int)((lo >> 8) & 255u) != kNoMode) o.s1 = a1;
-    if (n > 2 && (int)((lo >> 16) & 255u) != kNoMode) o.s2 = a2;
-    return o;
-}
-
 // The SAD part of a luma / single-tree leaf search: the 13 directional candidates, their first minimum and the two
 // step-search rounds around it (block_splitter.rs:899-973).  cm: the mode found, smin: its SAD.
 // ONE copy of the list code (sad_list_angular is a couple of thousand instructions, inlined): the rounds are iterations
@@ -415,28 +394,20 @@ __device__ __forceinline__ void sad_search(const Ctx& c, const Req& q, int& cm_o
     smin_out = cur;
 }
 
-__device__ __forceinline__ Res leaf4_search(const Ctx& c, const Req& q, int* overflow); // below, after the cost functions
-__device__ __forceinline__ Res leafc4_search(const Ctx& c, const Req& q, int* overflow);
 __device__ __forceinline__ Res leaf8_search(const Ctx& c, const Req& q, int* overflow);
 __device__ __forceinline__ Res leaf16_search(const Ctx& c, const Req& q, int* overflow);
 __device__ __forceinline__ Res split8_search(const Ctx& c, const Req& q, int* overflow);
 __device__ __forceinline__ void serve_pack4(const Ctx& c, const Req& q, int* overflow);
+__device__ __forceinline__ void serve_pack8(const Ctx& c, const Req& q, int* overflow);
 
 // The evaluator: every block evaluation of the search, of the regeneration and of the final pass
 // goes through this one inlined copy (the search logic below is a state machine that hands out
 // evaluation requests; no function calls in the hot path).
 // D3: the kernel serves max-split-depth 3 (the only depth at which an 8x8 CU splits into 4x4 leaves): the kernels for
-// the smaller depths are built without that code.
-template <bool D3>
+// the smaller depths are built without that code.  TEAM: the team kernel, the only one with a pack-A server.
+template <bool TEAM, bool D3>
 __device__ __forceinline__ Res evaluate(const Ctx& c, const PicBufs& pb, const Req& q, int* overflow) {
-    Res r;
-    r.ssd_y = 0;
-    r.ssd_c = 0;
-    r.lvl_y = 0;
-    r.lvl_c = 0;
-    r.v0 = r.v1 = r.v2 = r.vmin = 3.40282347e+38f;
-    r.imin = 0;
-    r.imin2 = 0;
+    Res r = res_none();
     PROF_MARK(tcp0_);
     if (q.pre_copy != COPY_NONE)
         copy_block(c, q.pre_copy, q.copy_comps, q.copy_slot, q.copy_tx, q.copy_ty, q.copy_tlg, q.copy_from);
@@ -448,7 +419,11 @@ __device__ __forceinline__ Res evaluate(const Ctx& c, const PicBufs& pb, const R
     if (q.kind == K_LEAF8) return leaf8_search(c, q, overflow);
     if (q.kind == K_LEAF16) return leaf16_search(c, q, overflow);
     if (D3 && q.kind == K_SPLIT8) return split8_search(c, q, overflow);
-    if (D3 && q.kind == K_SERVE4) { // (team kernel, member 0 only)
+    if (TEAM && q.kind == K_SERVE8) { // (member 0 only)
+        serve_pack8(c, q, overflow);
+        return r;
+    }
+    if (TEAM && D3 && q.kind == K_SERVE4) { // (the same)
         serve_pack4(c, q, overflow);
         return r;
     }
@@ -470,37 +445,28 @@ __device__ __forceinline__ Res evaluate(const Ctx& c, const PicBufs& pb, const R
         cpick_ = cclm_pick(call_, 2 * cclm_mode_index(mc)); // the evaluation below predicts with these
     }
     if (q.kind == K_FULL || q.kind == K_CCLMSEARCH) {
-        // A candidate of the search with an 8x8 or 16x16 luma block quantises its three transform
-        // blocks in one pass (quantize3): both components go through the first half, then the pass, then
-        // both through the second half.  Everything else runs component by component (the two share r1 / r2).
-        // One copy of each stage either way.  Every trellis walk is the wave's own.
-        #ifdef WRENC_EXP_NO_MERGED
-        const bool merged = false;
-#else
-        const bool merged = !q.final && q.comps == 3 && q.tlg >= 3 && q.tlg <= 4;
-#endif
-        const int p0 = 1 << (2 * q.tlg);
-        const int rounds = merged ? 1 : 2;
+        // Component by component (the two share r1 / r2): a search candidate that gets here is a 32x32 block or a chroma
+        // pair alone, a final-pass block is evaluated once.  One copy of each stage.  Every trellis walk is the wave's own.
+        // (A round per component, the stages in loops over the round's components: the shape is kept for the register
+        // allocator's sake -- one flat loop cost the wave kernels 6 KB of reloaded scalars and 1 % of their speed)
 #pragma unroll 1
-        for (int round = 0; round < rounds; ++round) {
-            const int cset = merged ? 3 : (q.comps & (1 << round));
+        for (int round = 0; round < 2; ++round) {
+            const int cset = q.comps & (1 << round);
             if (!cset) continue;
             if (q.active) {
 #pragma unroll 1
                 for (int comp = 0; comp < 2; ++comp)
                     if ((cset >> comp) & 1) {
                         PROF_MARK(tf0_);
-                        full_front(c, q, comp, comp ? mc : q.ml, (merged && comp) ? p0 : 0, cpick_);
+                        full_front(c, q, comp, comp ? mc : q.ml, 0, cpick_);
                         PROF_MARK(tf1_);
-                        PROF_ADD2(PH_PSZ + ((q.tlg - 2) * 2 + comp), tf0_, tf1_); // stage passes by block size and component
+                        PROF_ADD2(PH_PSZ + ((q.tlg - 2) * 2 + comp), tf0_, tf1_);
                         PROF_ADD2(PH_PCNT + ((q.tlg - 2) * 2 + comp), 0, 1);
                     }
             }
             PROF_MARK(ts0_);
             bool any_y = false, any_c = false;
-            if (merged) {
-                quantize3(c, q.tlg, q.active, overflow, &r.lvl_y, &r.lvl_c, &any_y, &any_c);
-            } else {
+            {
                 bool any = false;
                 long long lvl = 0;
                 if (q.active)
@@ -515,7 +481,7 @@ __device__ __forceinline__ Res evaluate(const Ctx& c, const PicBufs& pb, const R
             }
             PROF_MARK(ts1_);
             PROF_ADD2(PH_QZ + ((q.tlg - 2) & 3), ts0_, ts1_);
-            if (!q.active) { // an inactive evaluation (a candidate the reference skips): nothing was computed
+            if (!q.active) {
                 PROF_ADD2(PH_SKIP, ts0_, ts1_);
                 continue;
             }
@@ -523,7 +489,7 @@ __device__ __forceinline__ Res evaluate(const Ctx& c, const PicBufs& pb, const R
             for (int comp = 0; comp < 2; ++comp) {
                 if (!((cset >> comp) & 1)) continue;
                 PROF_MARK(tb0_);
-                const uint32_t ssd = full_back(c, pb, q, comp, (merged && comp) ? p0 : 0, comp ? any_c : any_y);
+                const uint32_t ssd = full_back(c, pb, q, comp, 0, comp ? any_c : any_y);
                 PROF_MARK(tb1_);
                 PROF_ADD2(PH_PSZ + ((q.tlg - 2) * 2 + comp), tb0_, tb1_);
                 if (comp)
@@ -534,7 +500,7 @@ __device__ __forceinline__ Res evaluate(const Ctx& c, const PicBufs& pb, const R
         }
         return r;
     }
-    // K_SADLIST: get_intra_pred_aux_cost / get_chroma_intra_pred_aux_cost of each listed mode
+    // K_SADSEARCH / K_SADLIST: get_intra_pred_aux_cost / get_chroma_intra_pred_aux_cost
     PROF_MARK(tr0_);
     if (q.refs0 && (q.comps & 1)) build_refs(c, 0, q.tx, q.ty, q.tlg);
     if (q.refs1 && (q.comps & 2)) build_refs(c, 1, q.tx, q.ty, q.tlg);
@@ -542,75 +508,24 @@ __device__ __forceinline__ Res evaluate(const Ctx& c, const PicBufs& pb, const R
     PROF_MARK(t0_);
     PROF_ADD2(PH_REFS, tr0_, t0_);
     // SADs stay integers (< 2^20, so the f32 the reference compares is exact and ordered the same
-    // way); they become floats once, at the end.  An entry that is not evaluated costs f32::MAX.
-    constexpr unsigned kNoSad = 0xFFFFFFFFu;
-    unsigned s0 = kNoSad, s1 = kNoSad, s2 = kNoSad, smin = kNoSad;
-    const int m_first = (int)(q.modes_lo & 255u);
-    const int m_second = (int)((q.modes_lo >> 8) & 255u);
+    // way); they become floats once, at the end.
     if (q.kind == K_SADSEARCH) {
+        constexpr unsigned kNoSad = 0xFFFFFFFFu;
         int cm;
+        unsigned smin = kNoSad;
         sad_search(c, q, cm, smin);
         r.imin = uni(cm);
-    } else if ((m_first >= 2 && m_first <= 66) || (m_first == kNoMode && m_second <= 66)) {
-        // a list of angular modes (a step-search pair)
-        const ListOut l = angular_list(c, q, q.n, q.modes_lo, q.modes_hi);
-        s0 = l.s0;
-        s1 = l.s1;
-        s2 = l.s2;
-        smin = l.smin;
-        r.imin = l.imin;
-    } else if (q.comps == 2 && q.n == 3 && (unsigned)q.modes_lo == ((unsigned)LT_CCLM | ((unsigned)T_CCLM << 8) | ((unsigned)L_CCLM << 16))) {
-        // the three CCLM modes of a chroma pair, one sample pass
-        const unsigned acc = sad_list_cclm(c, q.tx, q.ty, q.tlg);
-        s0 = (unsigned)__builtin_amdgcn_readlane((int)acc, 0);
-        s1 = (unsigned)__builtin_amdgcn_readlane((int)acc, 1);
-        s2 = (unsigned)__builtin_amdgcn_readlane((int)acc, 2);
-        if (c.trace && LANE < 3)
-            TRACE_REC(c.ctu_x + q.tx, c.ctu_y + q.ty, q.tlg, q.tree, 2, 0, LANE == 0 ? LT_CCLM : (LANE == 1 ? T_CCLM : L_CCLM),
-                      __float_as_int((float)acc));
-        smin = s0;
-        r.imin = 0;
-        if (s1 < smin) {
-            smin = s1;
-            r.imin = 1;
-        }
-        if (s2 < smin) {
-            smin = s2;
-            r.imin = 2;
-        }
-    } else {
-#pragma unroll 1
-        for (int i = 0; i < q.n; ++i) {
-            const int m = (int)(((i < 8 ? q.modes_lo : q.modes_hi) >> (8 * (i & 7))) & 255u);
-            unsigned sad = kNoSad;
-            if (m != kNoMode) {
-                sad = 0;
-#pragma unroll 1
-                for (int comp = 0; comp < 2; ++comp) {
-                    if (!((q.comps >> comp) & 1)) continue;
-                    PROF_MARK(tp0_);
-                    sad += (unsigned)wave_sum_i32(predict<false>(c, comp, q.tx, q.ty, q.tlg, m));
-                    PROF_MARK(tp1_);
-                    PROF_ADD2(PH_PSZ + ((q.tlg - 2) * 2 + comp), tp0_, tp1_);
-                    PROF_ADD2(PH_PCNT + ((q.tlg - 2) * 2 + comp), 0, 1);
-                }
-            }
-            if (c.trace && LANE == 0 && m != kNoMode)
-                TRACE_REC(c.ctu_x + q.tx, c.ctu_y + q.ty, q.tlg, q.tree, (q.comps & 1) ? 0 : 2, (q.comps & 1) ? m : 0, m,
-                          __float_as_int((float)sad));
-            if (i == 0) s0 = sad;
-            if (i == 1) s1 = sad;
-            if (i == 2) s2 = sad;
-            if (sad < smin) { // first minimum
-                smin = sad;
-                r.imin = i;
-            }
-        }
+        r.vmin = smin == kNoSad ? 3.40282347e+38f : uni_f((float)smin);
+    } else { // K_SADLIST: the chroma pair under the CCLM mode q.mc
+        PROF_MARK(tp0_);
+        const unsigned sad = (unsigned)wave_sum_i32(predict<false>(c, 1, q.tx, q.ty, q.tlg, q.mc));
+        PROF_MARK(tp1_);
+        PROF_ADD2(PH_PSZ + ((q.tlg - 2) * 2 + 1), tp0_, tp1_);
+        PROF_ADD2(PH_PCNT + ((q.tlg - 2) * 2 + 1), 0, 1);
+        if (c.trace && LANE == 0)
+            TRACE_REC(c.ctu_x + q.tx, c.ctu_y + q.ty, q.tlg, q.tree, 2, 0, q.mc, __float_as_int((float)sad));
+        r.v0 = uni_f((float)sad);
     }
-    r.v0 = s0 == kNoSad ? 3.40282347e+38f : uni_f((float)s0);
-    r.v1 = s1 == kNoSad ? 3.40282347e+38f : uni_f((float)s1);
-    r.v2 = s2 == kNoSad ? 3.40282347e+38f : uni_f((float)s2);
-    r.vmin = smin == kNoSad ? 3.40282347e+38f : uni_f((float)smin);
     PROF_MARK(t1_);
     PROF_ADD2(PH_PREDICT, t0_, t1_);
     return r;
@@ -758,7 +673,7 @@ __device__ __forceinline__ int pick_cclm(float lt, float t, float l) {
 }
 
 // ---------------------------------------------------------------------------
-// K_LEAF4: the whole search of a 4x4 DUAL_TREE_LUMA leaf in one request (block_splitter.rs:886-1078 with 16 samples
+// leaf4_search: the whole search of a 4x4 DUAL_TREE_LUMA leaf in one go (block_splitter.rs:886-1078 with 16 samples
 // per candidate).  A full evaluation of a 4x4 block is a chain of fixed-latency stages that keeps 16 of the wave's
 // 64 lanes busy, and at max-split-depth 3 these leaves are 61 % of a CTU.  The full candidates of a leaf do not
 // depend on each other (they read only neighbours outside the block, :887-898, :974), so they are evaluated SIDE BY
@@ -843,12 +758,7 @@ __device__ __forceinline__ Pack4Out pack4_eval(const Ctx& c, const Req& q, int n
 }
 
 __device__ __forceinline__ Res leaf4_search(const Ctx& c, const Req& q, int* overflow) {
-    Res r;
-    r.ssd_y = 0;
-    r.ssd_c = 0;
-    r.lvl_y = 0;
-    r.lvl_c = 0;
-    r.v0 = r.v1 = r.v2 = 3.40282347e+38f;
+    Res r = res_none();
     const int lane = lane_fresh();
     if (q.refs0) build_refs(c, 0, q.tx, q.ty, 2);
     const int x = lane & 3, y = (lane >> 2) & 3, row = lane >> 4;
@@ -866,7 +776,7 @@ __device__ __forceinline__ Res leaf4_search(const Ctx& c, const Req& q, int* ove
         e_.lvl_c = 0;                                                                                                  \
         const int cls_ = mpm_class_of(mpl_, (M));                                                                      \
         const float val_ = uni_f(assemble_cost(c, TREE_DUAL_LUMA, cls_, (M), e_));                                     \
-        if (c.trace && lane == 0) /* (team schedule: each half is traced by the member that runs it) */                \
+        if (c.trace && lane == 0)                                                                                      \
             TRACE_REC(c.ctu_x + q.tx, c.ctu_y + q.ty, 2, TREE_DUAL_LUMA, 1, (M), (M), __float_as_int(val_));           \
         if (first_ || val_ < best) {                                                                                   \
             best = val_;                                                                                               \
@@ -876,11 +786,10 @@ __device__ __forceinline__ Res leaf4_search(const Ctx& c, const Req& q, int* ove
         first_ = false;                                                                                                \
     } while (0)
     bool first_ = true;
-    // q.n: which half runs here (team schedule: member 0 takes pack A, member 1 the SAD search and pack B; 3 = both)
     // level schedule (team kernel): member 3's 4x4 luma leaves get their pack A from member 0, the server (serve_pack4;
     // the same protocol as for member 2's 8x8 leaves, leaf8_search)
     constexpr int kSrv4Byte = 448; // in the server's decw: 2 x 16 reconstructed samples, then ssd[2] (u32), lvl[2] (i64)
-    const bool served = c.solo && c.member == 3 && q.n == 3 && lv_word(&SHT.lvb.srv_ready) != 0;
+    const bool served = c.solo && c.member == 3 && lv_word(&SHT.lvb.srv_ready) != 0;
     unsigned my_job = 0;
     if (served) {
         if (lane == 0) {
@@ -889,7 +798,7 @@ __device__ __forceinline__ Res leaf4_search(const Ctx& c, const Req& q, int* ove
         }
         my_job = uni((int)lv_word(&SHT.lvb.job4_posted)) + 1u;
         lv_word_add(&SHT.lvb.job4_posted);
-    } else if (q.n & 1) {
+    } else {
         // pack A: planar and DC (:887-898)
         PROF_MARK(l4a0_);
         const Pack4Out a = pack4_eval(c, q, 2, PLANAR, DC, kNoMode, overflow);
@@ -905,7 +814,7 @@ __device__ __forceinline__ Res leaf4_search(const Ctx& c, const Req& q, int* ove
     // angular candidate costs at least the smallest floor an angular mode's class can have under this MPM list: mpm_idx
     // 1 .. 4 and the remainders always (cand_floor_ang), mpm_idx 0 where it is not DC, which pack A has evaluated.  With
     // best <= that floor no later candidate is strictly cheaper: neither the SAD search nor pack B can change the leaf.
-    const bool cut_on_ = kCandidateCut && q.n == 3 && c.solo == 0;
+    const bool cut_on_ = kCandidateCut && c.solo == 0;
     bool cut_ = false;
     if (cut_on_) {
         float fa = c.k->cand_floor_ang;
@@ -914,7 +823,7 @@ __device__ __forceinline__ Res leaf4_search(const Ctx& c, const Req& q, int* ove
         cut_ = uni((int)(best <= fa)) != 0; // (every lane holds the same scalars: a scalar branch)
         if (cut_) PROF_ADD2(PH_CUT + 6, 0, 1);
     }
-    if ((q.n & 2) && !cut_) {
+    if (!cut_) {
         int cm;
         unsigned smin;
         PROF_MARK(l4s0_);
@@ -957,8 +866,7 @@ __device__ __forceinline__ Res leaf4_search(const Ctx& c, const Req& q, int* ove
 #pragma unroll
         for (int k2 = 0; k2 < 2; ++k2) {
             a.ssd[k2] = (uint32_t)uni((int)((const uint32_t*)(sv + 32))[k2]);
-            const unsigned long long lv = ((const unsigned long long*)(sv + 40))[k2];
-            a.lvl[k2] = (long long)(((unsigned long long)(unsigned)uni((int)(lv >> 32)) << 32) | (unsigned)uni((int)lv));
+            a.lvl[k2] = uni_i64(((const long long*)(sv + 40))[k2]);
         }
         first_ = true;
         int win_ = -1;
@@ -998,17 +906,12 @@ __device__ __forceinline__ void serve_pack4(const Ctx& c, const Req& q, int* ove
     lv_word_add(&SHT.lvb.job4_done);
 }
 
-// K_LEAFC4: the DUAL_TREE_CHROMA leaf of a split 8x8 CU (block_splitter.rs:794-885) in one request.  The three CCLM
+// leafc4_search: the DUAL_TREE_CHROMA leaf of a split 8x8 CU (block_splitter.rs:794-885) in one go.  The three CCLM
 // SADs and the pick (:847-854) as in K_CCLMSEARCH, then the picked CCLM mode and the DM mode (q.mc) are evaluated SIDE
 // BY SIDE: rows 0 / 1 = Cb / Cr of the CCLM candidate, rows 2 / 3 = Cb / Cr of the DM candidate, four 4x4 blocks
 // through the stages of pack4_eval.  The winner's rows (DM on a tie, :857-873) write their reconstruction to the tile.
 __device__ __forceinline__ Res leafc4_search(const Ctx& c, const Req& q, int* overflow) {
-    Res r;
-    r.ssd_y = 0;
-    r.ssd_c = 0;
-    r.lvl_y = 0;
-    r.lvl_c = 0;
-    r.v0 = r.v1 = r.v2 = 3.40282347e+38f;
+    Res r = res_none();
     const int lane = lane_fresh();
     const int dm = q.mc;
     // get_chroma_intra_pred_aux_cost of LT, T, L_CCLM in one sample pass, then the pick (SADs are integers < 2^20)
@@ -1204,14 +1107,7 @@ __device__ __forceinline__ void pack8_to_tile(const Req& q, int nc, int cd) {
 }
 
 __device__ __forceinline__ Res leaf8_search(const Ctx& c, const Req& q, int* overflow) {
-    Res r;
-    r.ssd_y = 0;
-    r.ssd_c = 0;
-    r.lvl_y = 0;
-    r.lvl_c = 0;
-    r.v0 = r.v1 = r.v2 = 3.40282347e+38f;
-    r.imin = PLANAR;
-    r.imin2 = PLANAR;
+    Res r = res_none();
     const int lane = lane_fresh();
     if (q.refs0) build_refs(c, 0, q.tx, q.ty, 3);
     if (q.refs1) build_refs(c, 1, q.tx, q.ty, 3);
@@ -1231,7 +1127,7 @@ __device__ __forceinline__ Res leaf8_search(const Ctx& c, const Req& q, int* ove
         e_.lvl_c = (P).lvl_c[B];                                                                                       \
         const int cls_ = mpm_class_of(mpl_, (M));                                                                      \
         const float val_ = uni_f(assemble_cost(c, TREE_SINGLE, cls_, (M), e_));                                        \
-        if (c.trace && lane == 0) /* (team schedule: each part is traced by the member that runs it) */                \
+        if (c.trace && lane == 0)                                                                                      \
             TRACE_REC(c.ctu_x + q.tx, c.ctu_y + q.ty, 3, TREE_SINGLE, 1, (M), (M), __float_as_int(val_));              \
         if (first_ || val_ < best) {                                                                                   \
             best = val_;                                                                                               \
@@ -1243,29 +1139,10 @@ __device__ __forceinline__ Res leaf8_search(const Ctx& c, const Req& q, int* ove
         first_ = false;                                                                                                \
     } while (0)
     // Level schedule (team kernel): member 0, idle once the CTU's 32x32 candidate is done, SERVES pack A of member 2's 8x8
-    // leaves.  q.n & 16: this is the server's request -- reference samples and originals of the block from member 2's
-    // LDS, pack {planar, DC}, the candidates' parts to xr[0 .. 1], their reconstructions stay in this wave's park.
-    if (q.n & 16) {
-        const Lds& own = team_lds(c, 2);
-        for (int w = lane; w < 98; w += 64) ((uint32_t*)SH.refs)[w] = ((const uint32_t*)own.refs)[w];
-        for (int w = lane; w < 96; w += 64) ((uint32_t*)SH.r2)[kOrgLeaf / 4 + w] = ((const uint32_t*)own.r2)[kOrgLeaf / 4 + w];
-        WSYNC();
-        const Pack8Out a = pack8_eval(c, q, 2, PLANAR, DC, kNoMode, overflow);
-        if (lane < 2) {
-            XRes x;
-            x.ssd_y = lane ? a.ssd_y[1] : a.ssd_y[0];
-            x.ssd_c = lane ? a.ssd_c[1] : a.ssd_c[0];
-            x.lvl_y = lane ? a.lvl_y[1] : a.lvl_y[0];
-            x.lvl_c = lane ? a.lvl_c[1] : a.lvl_c[0];
-            SH.xr[lane] = x;
-        }
-        WSYNC();
-        lv_word_add(&SHT.lvb.job_done);
-        return r;
-    }
-    // member 2 of a team in the level schedule, and the server is polling: post the job (the block's reference samples
-    // and originals are ready and stay untouched until the leaf is decided), skip pack A here, merge its results below
-    const bool served = c.solo && c.member == 2 && (q.n & 7) == 7 && lv_word(&SHT.lvb.srv_ready) != 0;
+    // leaves (serve_pack8).  Member 2 of a team in the level schedule, and the server is polling: post the job (the
+    // block's reference samples and originals are ready and stay untouched until the leaf is decided), skip pack A
+    // here, merge its results below
+    const bool served = c.solo && c.member == 2 && lv_word(&SHT.lvb.srv_ready) != 0;
     unsigned my_job = 0;
     if (served) {
         if (lane == 0) {
@@ -1274,7 +1151,7 @@ __device__ __forceinline__ Res leaf8_search(const Ctx& c, const Req& q, int* ove
         }
         my_job = uni((int)lv_word(&SHT.lvb.job_posted)) + 1u;
         lv_word_add(&SHT.lvb.job_posted);
-    } else if (q.n & 1) {
+    } else {
         // pack A: planar and DC (:887-898)
         PROF_MARK(la0_);
         const Pack8Out a = pack8_eval(c, q, 2, PLANAR, DC, kNoMode, overflow);
@@ -1285,7 +1162,7 @@ __device__ __forceinline__ Res leaf8_search(const Ctx& c, const Req& q, int* ove
         PROF_MARK(la1_);
         PROF_ADD2(PH_LEAF + 0, la0_, la1_);
     }
-    if (q.n & 2) {
+    {
         int cm;
         unsigned smin;
         PROF_MARK(ls0_);
@@ -1323,9 +1200,8 @@ __device__ __forceinline__ Res leaf8_search(const Ctx& c, const Req& q, int* ove
             const XRes& x = srv.xr[k2];
             a.ssd_y[k2] = (uint32_t)uni((int)x.ssd_y);
             a.ssd_c[k2] = (uint32_t)uni((int)x.ssd_c);
-            const unsigned long long ly = (unsigned long long)x.lvl_y, lc = (unsigned long long)x.lvl_c;
-            a.lvl_y[k2] = (long long)(((unsigned long long)(unsigned)uni((int)(ly >> 32)) << 32) | (unsigned)uni((int)ly));
-            a.lvl_c[k2] = (long long)(((unsigned long long)(unsigned)uni((int)(lc >> 32)) << 32) | (unsigned)uni((int)lc));
+            a.lvl_y[k2] = uni_i64(x.lvl_y);
+            a.lvl_c[k2] = uni_i64(x.lvl_c);
         }
         LEAF8_CANDIDATE(a, 0, PLANAR);
         LEAF8_CANDIDATE(a, 1, DC);
@@ -1353,17 +1229,11 @@ __device__ __forceinline__ Res leaf8_search(const Ctx& c, const Req& q, int* ove
     r.ssd_c = eb.ssd_c;
     r.lvl_y = eb.lvl_y;
     r.lvl_c = eb.lvl_c;
-    if (!(q.n & 4)) return r;
     // ---- the CCLM part on the winner, whose reconstruction is in the tile (:1040-1072) ----
-    float cur;
-    if (q.n & 3) {
-        // :1040 get_chroma_intra_pred_cost(mode) repeats the winner's chroma evaluation: its parts are at hand
-        cur = uni_f(assemble_chroma_cost(c, best_mode, eb));
-        if (c.trace && lane == 0)
-            TRACE_REC(c.ctu_x + q.tx, c.ctu_y + q.ty, 3, TREE_SINGLE, 3, 0, best_mode, __float_as_int(cur));
-    } else {
-        cur = q.fcur; // (team schedule: the team decided the winner, every member assembled this cost)
-    }
+    // :1040 get_chroma_intra_pred_cost(mode) repeats the winner's chroma evaluation: its parts are at hand
+    const float cur = uni_f(assemble_chroma_cost(c, best_mode, eb));
+    if (c.trace && lane == 0)
+        TRACE_REC(c.ctu_x + q.tx, c.ctu_y + q.ty, 3, TREE_SINGLE, 3, 0, best_mode, __float_as_int(cur));
     PROF_MARK(lc0_);
     CclmParams call_;
     const unsigned acc = sad_list_cclm(c, q.tx, q.ty, 3, &call_);
@@ -1415,16 +1285,31 @@ __device__ __forceinline__ Res leaf8_search(const Ctx& c, const Req& q, int* ove
     WSYNC();
     PROF_MARK(lc9_);
     PROF_ADD2(PH_LEAF + 3, lc0_, lc9_);
-    if (q.n & 3) {
-        r.vmin = dm_wins ? uni_f(assemble_cost(c, TREE_SINGLE, best_cls, best_mode, eb))
-                         : uni_f(assemble_cost(c, TREE_SINGLE, best_cls, cm, e));
-        r.imin2 = dm_wins ? best_mode : cm;
-    } else { // part 4 alone: the CCLM candidate's mode and chroma parts, the team assembles the rest
-        r.imin = cm;
-        r.ssd_c = e.ssd_c;
-        r.lvl_c = e.lvl_c;
-    }
+    r.vmin = dm_wins ? uni_f(assemble_cost(c, TREE_SINGLE, best_cls, best_mode, eb))
+                     : uni_f(assemble_cost(c, TREE_SINGLE, best_cls, cm, e));
+    r.imin2 = dm_wins ? best_mode : cm;
     return r;
+}
+
+// The server's side of an 8x8 leaf (level schedule, q.kind K_SERVE8): reference samples and originals of the block from
+// member 2's LDS, pack {planar, DC}, the candidates' parts to xr[0 .. 1], their reconstructions stay in this wave's park.
+__device__ __forceinline__ void serve_pack8(const Ctx& c, const Req& q, int* overflow) {
+    const int lane = lane_fresh();
+    const Lds& own = team_lds(c, 2);
+    for (int w = lane; w < 98; w += 64) ((uint32_t*)SH.refs)[w] = ((const uint32_t*)own.refs)[w];
+    for (int w = lane; w < 96; w += 64) ((uint32_t*)SH.r2)[kOrgLeaf / 4 + w] = ((const uint32_t*)own.r2)[kOrgLeaf / 4 + w];
+    WSYNC();
+    const Pack8Out a = pack8_eval(c, q, 2, PLANAR, DC, kNoMode, overflow);
+    if (lane < 2) {
+        XRes x;
+        x.ssd_y = lane ? a.ssd_y[1] : a.ssd_y[0];
+        x.ssd_c = lane ? a.ssd_c[1] : a.ssd_c[0];
+        x.lvl_y = lane ? a.lvl_y[1] : a.lvl_y[0];
+        x.lvl_c = lane ? a.lvl_c[1] : a.lvl_c[0];
+        SH.xr[lane] = x;
+    }
+    WSYNC();
+    lv_word_add(&SHT.lvb.job_done);
 }
 
 // ---------------------------------------------------------------------------
@@ -1538,8 +1423,7 @@ __device__ __forceinline__ void pack16_to_tile(const Ctx& c, const Req& q, int n
 }
 
 __device__ __forceinline__ Res leaf16_search(const Ctx& c, const Req& q, int* overflow) {
-    Res r;
-    r.v0 = r.v1 = r.v2 = 3.40282347e+38f;
+    Res r = res_none();
     const int lane = lane_fresh();
     if (q.refs0) build_refs(c, 0, q.tx, q.ty, 4);
     if (q.refs1) build_refs(c, 1, q.tx, q.ty, 4);
@@ -1668,26 +1552,17 @@ __device__ __forceinline__ bool split_floor_cut(const Ctx& c, float partial, int
 // (Only the kernels built for max-split-depth 3 contain it, D3 below: inlined into the one evaluator of a kernel that also
 // serves depth 2, which never splits an 8x8, it cost that depth 2.5 %; as an out-of-line function it cost both depths more.)
 __device__ __forceinline__ Res split8_search(const Ctx& c, const Req& q, int* overflow) {
-    Res r;
-    r.ssd_y = 0;
-    r.ssd_c = 0;
-    r.lvl_y = 0;
-    r.lvl_c = 0;
-    r.v0 = r.v1 = r.v2 = 3.40282347e+38f;
-    r.imin = 0;
-    r.imin2 = 0;
+    Res r = res_none();
     float split8 = 0.0f;
 #pragma unroll 1
     for (int i8 = 0; i8 < 4; ++i8) {
         Req ql = {}; // (only what leaf4_search reads: a copy of q would keep thirty scalars alive across the four searches)
-        ql.kind = K_LEAF4;
         ql.comps = 1;
         ql.tx = q.tx + (i8 & 1) * 4;
         ql.ty = q.ty + (i8 >> 1) * 4;
         ql.tlg = 2;
         ql.refs0 = true;
         ql.refs1 = false;
-        ql.n = 3;
         ql.tree = TREE_DUAL_LUMA;
         if (split_floor_cut(c, split8, 4 - i8, 0, true, q.fcur, &r.vmin)) { // (before the first leaf: the split is skipped whole)
             PROF_ADD2(PH_CUT + 0, 0, 4 - i8);
@@ -1709,7 +1584,6 @@ __device__ __forceinline__ Res split8_search(const Ctx& c, const Req& q, int* ov
         return r;
     }
     Req qc = {};
-    qc.kind = K_LEAFC4;
     qc.tx = q.tx;
     qc.ty = q.ty;
     qc.comps = 2;
@@ -1763,20 +1637,20 @@ __device__ __forceinline__ void req_copy(Req& q, int mode, int comps, int slot, 
     q.copy_from = -1;
 }
 
+// (the numbers index the profile build's counters, tools/phase_profile.py: the gaps are states that are gone)
 enum {
-    C_START = 0, C_PLANAR, C_DCM, C_LIST, C_PAIR_EMIT, C_PAIR, C_F0, C_F1, C_F2, C_WIN, C_CX, C_CCLM, C_DM,
-    C_DC_START, C_DC2, C_DC3, C_DC4, C_DC5, C_L4, C_LC4, C_L8, C_L16, C_WINNER
+    C_START = 0, C_PLANAR = 1, C_DCM = 2, C_LIST = 3, C_F0 = 6, C_F1 = 7, C_F2 = 8, C_CCLM = 11, C_DM = 12,
+    C_L8 = 20, C_L16 = 21, C_WINNER = 22
 };
 
 // slot: where the search keeps its best candidate's reconstruction (0 = the leaf's own slot; 1 + level when the wave
 // schedule goes on to test the block's split: the slot then already holds the unsplit candidate, see ctu_step)
-__device__ __forceinline__ void leaf_init(LeafSt& s, int tree, int bx, int by, int lg, int dm_mode, int slot = 0) {
-    s.cont = (uint8_t)(tree == TREE_DUAL_CHROMA ? C_DC_START : C_START);
-    s.tree = (uint8_t)tree;
+// Every leaf that is searched step by step is a SINGLE_TREE block; the leaves of an 8x8 split are searched inside K_SPLIT8.
+__device__ __forceinline__ void leaf_init(LeafSt& s, int bx, int by, int lg, int slot = 0) {
+    s.cont = C_START;
     s.bx = (uint8_t)bx;
     s.by = (uint8_t)by;
     s.lg = (uint8_t)lg;
-    s.dm_mode = (uint8_t)dm_mode;
     s.need_refs0 = 1;
     s.need_refs1 = 1;
     s.need_org = lg <= 4 ? 1 : 0;
@@ -1790,7 +1664,7 @@ __device__ __forceinline__ void leaf_init(LeafSt& s, int tree, int bx, int by, i
 __device__ __forceinline__ void leaf_attach_save(LeafSF& s, Req& q) {
     q.pre_copy = COPY_NONE;
     if (s.need_save) {
-        req_copy(q, COPY_SAVE, s.tree == TREE_SINGLE ? 3 : 1, s.slot, s.bx, s.by, s.lg);
+        req_copy(q, COPY_SAVE, 3, s.slot, s.bx, s.by, s.lg);
         s.need_save = 0;
     }
 }
@@ -1798,7 +1672,7 @@ __device__ __forceinline__ void leaf_attach_save(LeafSF& s, Req& q) {
 __device__ __forceinline__ void leaf_attach_org(LeafSF& s, Req& q) {
     q.stage = 0;
     if (s.need_org) {
-        q.stage = s.tree == TREE_SINGLE ? 3 : (s.tree == TREE_DUAL_LUMA ? 1 : 2);
+        q.stage = 3;
         s.need_org = 0;
     }
 }
@@ -1816,7 +1690,7 @@ __device__ __forceinline__ void leaf_full(LeafSF& s, Req& q, int comps, int ml, 
     const bool r0 = (comps & 1) && s.need_refs0 != 0;
     const bool r1 = (comps & 2) && mc < LT_CCLM && s.need_refs1 != 0;
     req_full(q, comps, s.bx, s.by, s.lg, ml, mc, act, r0, r1, false);
-    q.tree = s.tree;
+    q.tree = TREE_SINGLE;
     leaf_attach_org(s, q);
     leaf_attach_save(s, q);
     if (act) {
@@ -1829,23 +1703,18 @@ __device__ __forceinline__ void leaf_full(LeafSF& s, Req& q, int comps, int ml, 
     s.cont = (uint8_t)cont;
 }
 
-// SAD list (get_intra_pred_aux_cost / get_chroma_intra_pred_aux_cost) of n modes, one byte each
-__device__ __forceinline__ void leaf_sadlist(LeafSF& s, Req& q, int comps, int n, uint32_t m0, uint32_t m1, uint32_t m2,
-                                             uint32_t m3, bool chroma_refs, int cont) {
+// the SAD (get_chroma_intra_pred_aux_cost) of the chroma pair under one CCLM mode (K_SADLIST)
+__device__ __forceinline__ void leaf_sadlist(LeafSF& s, Req& q, int mc, int cont) {
     q.kind = K_SADLIST;
     q.xchg = false;
-    q.tree = s.tree;
-    q.comps = comps;
+    q.tree = TREE_SINGLE;
+    q.comps = 2;
     q.tx = s.bx;
     q.ty = s.by;
     q.tlg = s.lg;
-    q.n = n;
-    q.modes_lo = (unsigned long long)m0 | ((unsigned long long)m1 << 32);
-    q.modes_hi = (unsigned long long)m2 | ((unsigned long long)m3 << 32);
-    q.refs0 = (comps & 1) && s.need_refs0 != 0;
-    q.refs1 = (comps & 2) && chroma_refs && s.need_refs1 != 0;
-    if (q.refs0) s.need_refs0 = 0;
-    if (q.refs1) s.need_refs1 = 0;
+    q.mc = mc;
+    q.refs0 = false;
+    q.refs1 = false; // (a CCLM mode reads no reference samples)
     leaf_attach_org(s, q);
     leaf_attach_save(s, q);
     s.cont = (uint8_t)cont;
@@ -1857,34 +1726,29 @@ __device__ __forceinline__ void leaf_cclmsearch(LeafSF& s, Req& q, int cont) {
     q.kind = K_CCLMSEARCH;
 }
 
-// the whole SAD part of a luma / single-tree leaf search as one request (K_SADSEARCH)
-__device__ __forceinline__ void leaf_sadsearch(LeafSF& s, Req& q, int comps, int cont) {
-    leaf_sadlist(s, q, comps, 13, 0, 0, 0, 0, true, cont);
+// the whole SAD part of a leaf search as one request (K_SADSEARCH)
+__device__ __forceinline__ void leaf_sadsearch(LeafSF& s, Req& q, int cont) {
     q.kind = K_SADSEARCH;
-}
-
-// the whole search of a 4x4 DUAL_TREE_LUMA leaf as one request (K_LEAF4, leaf4_search)
-__device__ __forceinline__ bool leaf_is_leaf4(const LeafSF& s) { return s.tree == TREE_DUAL_LUMA && s.lg == 2; }
-__device__ __forceinline__ void leaf_leaf4(LeafSF& s, Req& q, int cont) {
-    req_full(q, 1, s.bx, s.by, s.lg, 0, 0, true, s.need_refs0 != 0, false, false);
-    q.kind = K_LEAF4;
-    q.n = 3;
-    q.tree = s.tree;
+    q.xchg = false;
+    q.tree = TREE_SINGLE;
+    q.comps = 3;
+    q.tx = s.bx;
+    q.ty = s.by;
+    q.tlg = s.lg;
+    q.refs0 = s.need_refs0 != 0;
+    q.refs1 = s.need_refs1 != 0;
+    if (q.refs0) s.need_refs0 = 0;
+    if (q.refs1) s.need_refs1 = 0;
     leaf_attach_org(s, q);
     leaf_attach_save(s, q);
-    s.need_refs0 = 0;
     s.cont = (uint8_t)cont;
 }
 
-// the whole search of an 8x8 SINGLE_TREE leaf as one request (K_LEAF8, leaf8_search); parts: bit 0 pack {planar, DC},
-// bit 1 SAD search + pack {cm, cm - 1, cm + 1}, bit 2 the CCLM part
-__device__ __forceinline__ bool leaf_is_leaf8(const LeafSF& s) { return s.tree == TREE_SINGLE && s.lg == 3; }
-__device__ __forceinline__ void leaf_leaf8(LeafSF& s, Req& q, int parts, int cont) {
+// the whole search of an 8x8 SINGLE_TREE leaf as one request (K_LEAF8, leaf8_search)
+__device__ __forceinline__ void leaf_leaf8(LeafSF& s, Req& q, int cont) {
     req_full(q, 3, s.bx, s.by, s.lg, 0, 0, true, s.need_refs0 != 0, s.need_refs1 != 0, false);
     q.kind = K_LEAF8;
-    q.n = parts;
-    q.tree = s.tree;
-    q.fcur = 0.0f;
+    q.tree = TREE_SINGLE;
     leaf_attach_org(s, q);
     leaf_attach_save(s, q);
     s.need_refs0 = 0;
@@ -1892,10 +1756,9 @@ __device__ __forceinline__ void leaf_leaf8(LeafSF& s, Req& q, int parts, int con
     s.cont = (uint8_t)cont;
 }
 
-// the full candidates of a 16x16 SINGLE_TREE leaf as one request (K_LEAF16, leaf16_search); wave schedule only
-__device__ __forceinline__ bool leaf_is_leaf16(const LeafSF& s) { return s.tree == TREE_SINGLE && s.lg == 4; }
+// the full candidates of a 16x16 SINGLE_TREE leaf as one request (K_LEAF16, leaf16_search)
 __device__ __forceinline__ void leaf_leaf16(LeafSF& s, Req& q, int cont) {
-    leaf_leaf8(s, q, 3, cont);
+    leaf_leaf8(s, q, cont);
     q.kind = K_LEAF16;
 }
 
@@ -1931,16 +1794,15 @@ __device__ __forceinline__ void put_parts(EvalPartsSF& d, const EvalParts& e) {
         }                                 \
     } while (0)
 
-// One step of a leaf search: SINGLE_TREE / DUAL_TREE_LUMA blocks (block_splitter.rs:886-1078) and
-// DUAL_TREE_CHROMA blocks (:794-885; lg = luma log2 = 3).  r is the result of the request the
+// One step of the search of a SINGLE_TREE leaf (block_splitter.rs:886-1078).  An 8x8 leaf is one request (C_L8), a 16x16
+// leaf one request and its CCLM part (C_L16, C_WINNER ..); the candidate-by-candidate states C_PLANAR .. C_F2 serve the
+// 32x32 leaf alone.  r is the result of the request the
 // previous step made (unused at the first step).  Returns false when the leaf is decided
 // (s.cost, s.luma_mode, s.chroma_mode).  The reference's "first minimum wins" selections are kept
 // as strict-less running updates in the reference's candidate order; a candidate = one request
 // (luma block and chroma pair together, SAD candidates as one list).
-template <bool D3>
 __device__ __forceinline__ bool leaf_step(const Ctx& c, LeafSF& s, const Res& r, Req& q) {
-    const int tree = s.tree;
-    const int both = tree == TREE_SINGLE ? 3 : 1;
+    constexpr int tree = TREE_SINGLE;
     int cont = s.cont;
     // RD cost of the full evaluation that just came back (candidates of C_PLANAR .. C_F2)
     float val = 0.0f;
@@ -1959,19 +1821,15 @@ __device__ __forceinline__ bool leaf_step(const Ctx& c, LeafSF& s, const Res& r,
     for (;;) {
         switch (cont) {
         case C_START: // candidates {0,1,2,7,13,18,23,29,34,39,45,50,55,60,66} (:887)
-            if (D3 && leaf_is_leaf4(s)) { // a 4x4 luma leaf: the whole search in one request
-                leaf_leaf4(s, q, C_L4);
+            if (s.lg == 3) { // an 8x8 leaf: the whole search in one request, candidates in packs
+                leaf_leaf8(s, q, C_L8);
                 return true;
             }
-            if (leaf_is_leaf8(s)) { // an 8x8 single-tree leaf: the whole search in one request, candidates in packs
-                leaf_leaf8(s, q, 7, C_L8);
-                return true;
-            }
-            if (leaf_is_leaf16(s)) { // a 16x16 leaf: its five full candidates and the SAD search in one request
+            if (s.lg == 4) { // a 16x16 leaf: its five full candidates and the SAD search in one request
                 leaf_leaf16(s, q, C_L16);
                 return true;
             }
-            leaf_full(s, q, both, PLANAR, PLANAR, true, C_PLANAR);
+            leaf_full(s, q, 3, PLANAR, PLANAR, true, C_PLANAR);
             return true;
         case C_L16: // the winner of [planar, DC, cm, cm - 1, cm + 1] is in the tile; it is saved by the next request
             s.best_cost = r.vmin;
@@ -1987,11 +1845,6 @@ __device__ __forceinline__ bool leaf_step(const Ctx& c, LeafSF& s, const Res& r,
             s.luma_mode = (uint8_t)r.imin;
             s.chroma_mode = (uint8_t)r.imin2;
             return false;
-        case C_L4:
-            s.cost = r.vmin;
-            s.luma_mode = (uint8_t)r.imin;
-            s.chroma_mode = (uint8_t)r.imin;
-            return false;
         case C_PLANAR:
             s.best_cost = val;
             put_parts(s.e_best, rp);
@@ -1999,13 +1852,13 @@ __device__ __forceinline__ bool leaf_step(const Ctx& c, LeafSF& s, const Res& r,
             s.best_cls = (uint8_t)cls;
             s.need_save = 1;
             s.tile_best = 1;
-            leaf_full(s, q, both, DC, DC, true, C_DCM);
+            leaf_full(s, q, 3, DC, DC, true, C_DCM);
             return true;
         case C_DCM:
             LEAF_CANDIDATE(DC);
             // the 13 directional candidates, their first minimum (:899-904) and step_search(mode, 2, cost, aux = true)
             // (:905-973) in ONE request: the evaluator runs the three lists back to back
-            leaf_sadsearch(s, q, both, C_LIST);
+            leaf_sadsearch(s, q, C_LIST);
             return true;
         case C_LIST: {
             // step_search(mode, 1, _, aux=false) (:974) on {cur, cur - 1, cur + 1}, then the minimum of
@@ -2014,19 +1867,19 @@ __device__ __forceinline__ bool leaf_step(const Ctx& c, LeafSF& s, const Res& r,
             const int cm = r.imin;
             s.cur_mode = (uint8_t)cm;
             s.cur_cost = r.vmin;
-            leaf_full(s, q, both, cm, cm, true, C_F0);
+            leaf_full(s, q, 3, cm, cm, true, C_F0);
             return true;
         }
         case C_F0: {
             const int cm = s.cur_mode;
             LEAF_CANDIDATE(cm);
-            leaf_full(s, q, both, cm - 1, cm - 1, !(cm < 3), C_F1);
+            leaf_full(s, q, 3, cm - 1, cm - 1, !(cm < 3), C_F1);
             return true;
         }
         case C_F1: {
             const int cm = s.cur_mode;
             LEAF_CANDIDATE(cm - 1);
-            leaf_full(s, q, both, cm + 1, cm + 1, !(cm + 1 > 66), C_F2);
+            leaf_full(s, q, 3, cm + 1, cm + 1, !(cm + 1 > 66), C_F2);
             return true;
         }
         case C_F2:
@@ -2041,13 +1894,6 @@ __device__ __forceinline__ bool leaf_step(const Ctx& c, LeafSF& s, const Res& r,
             // :989-1037 re-runs the winner's luma to have its reconstruction in the tile; here the
             // winner's reconstruction comes back from slot 0 unless it is still in the tile
             const bool in_tile = s.tile_best != 0;
-            if (tree == TREE_DUAL_LUMA) {
-                // :1073-1076 repeats the luma evaluation for planar / DC: same parts, same header bits,
-                // so the cost it assigns is the candidate's cost already in s.cost
-                if (in_tile) return false;
-                leaf_copy_only(s, q, COPY_RESTORE, 1, C_WIN);
-                return true;
-            }
             // :1040 get_chroma_intra_pred_cost(mode) repeats the winner's chroma evaluation: re-use it
             s.cur_cost = uni_f(assemble_chroma_cost(c, m, s.e_best.get()));
             if (c.trace && LANE == 0)
@@ -2057,8 +1903,6 @@ __device__ __forceinline__ bool leaf_step(const Ctx& c, LeafSF& s, const Res& r,
             if (!in_tile) req_copy(q, COPY_RESTORE, 1, s.slot, s.bx, s.by, s.lg); // (its save went out earlier)
             return true;
         }
-        case C_WIN:
-            return false;
         case C_CCLM: {
             // the CCLM candidate = the winner's luma parts + the chroma parts just evaluated
             s.cclm_mode = (uint8_t)r.imin;
@@ -2083,42 +1927,7 @@ __device__ __forceinline__ bool leaf_step(const Ctx& c, LeafSF& s, const Res& r,
             s.cost = uni_f(assemble_cost(c, tree, bcls, s.cclm_mode, e));
             return false;
         }
-        case C_DM:
-            return false;
-        // ---- DUAL_TREE_CHROMA leaf (:794-885) ----
-        case C_DC_START: // the whole chroma leaf in one request, CCLM and DM candidates side by side (K_LEAFC4)
-            leaf_full(s, q, 2, 0, s.dm_mode, true, C_LC4);
-            q.kind = K_LEAFC4;
-            return true;
-        case C_LC4:
-            s.luma_mode = 0;
-            s.cost = r.vmin;
-            s.chroma_mode = (uint8_t)r.imin;
-            return false;
-        case C_DC3:
-            s.cclm_mode = (uint8_t)r.imin;
-            s.c0 = uni_f(assemble_chroma_cost(c, s.cclm_mode, rp));
-            if (c.trace && LANE == 0)
-                TRACE_REC(c.ctu_x + s.bx, c.ctu_y + s.by, s.lg, tree, 3, 0, s.cclm_mode, __float_as_int((float)s.c0));
-            leaf_full(s, q, 2, 0, s.dm_mode, true, C_DC4);
-            req_copy(q, COPY_SAVE, 2, s.slot, s.bx, s.by, s.lg); // keep the CCLM reconstruction (:807-840)
-            return true;
-        case C_DC4: {
-            const float dm_cost = uni_f(assemble_chroma_cost(c, s.dm_mode, rp));
-            if (c.trace && LANE == 0)
-                TRACE_REC(c.ctu_x + s.bx, c.ctu_y + s.by, s.lg, tree, 3, 0, s.dm_mode, __float_as_int(dm_cost));
-            const float cost = fminf(s.c0, fminf(dm_cost, 3.40282347e+38f));
-            s.luma_mode = 0;
-            s.cost = cost;
-            if (dm_cost == cost) {
-                s.chroma_mode = s.dm_mode;
-                return false;
-            }
-            s.chroma_mode = s.cclm_mode;
-            leaf_copy_only(s, q, COPY_RESTORE, 2, C_DC5); // :869-873 restore_reconsts
-            return true;
-        }
-        default: // C_DC5
+        default: // C_DM: the DM chroma is back in the tile
             return false;
         }
     }
@@ -2144,27 +1953,19 @@ __device__ __forceinline__ EvalParts xparts(const Ctx& c, int par, int m) {
     EvalParts e;
     e.ssd_y = (uint32_t)uni((int)x.ssd_y);
     e.ssd_c = (uint32_t)uni((int)x.ssd_c);
-    const unsigned long long a = (unsigned long long)x.lvl_y, b = (unsigned long long)x.lvl_c;
-    e.lvl_y = (long long)(((unsigned long long)(unsigned)uni((int)(a >> 32)) << 32) | (unsigned)uni((int)a));
-    e.lvl_c = (long long)(((unsigned long long)(unsigned)uni((int)(b >> 32)) << 32) | (unsigned)uni((int)b));
+    e.lvl_y = uni_i64(x.lvl_y);
+    e.lvl_c = uni_i64(x.lvl_c);
     return e;
 }
-// SAD list results: first minimum (f32 bits in ssd_y), its index (ssd_c), the first entry's cost (lvl_y)
+// K_SADSEARCH: the SAD of the mode found (f32 bits in ssd_y), the mode (ssd_c); K_SADLIST: the SAD (lvl_y)
 __device__ __forceinline__ float xvmin(const Ctx& c, int par, int m) { return __int_as_float(uni((int)team_lds(c, m).xr[par].ssd_y)); }
 __device__ __forceinline__ int ximin(const Ctx& c, int par, int m) { return uni((int)team_lds(c, m).xr[par].ssd_c); }
 __device__ __forceinline__ float xv0(const Ctx& c, int par, int m) { return __int_as_float(uni((int)team_lds(c, m).xr[par].lvl_y)); }
 
 __device__ __forceinline__ void team_publish(const Req& q, const Res& r, int par) {
     XRes x;
-    if (q.kind == K_LEAF8) {
-        // a half of the packed search: its best candidate's parts, the mode in the top byte of ssd_y; the CCLM part:
-        // the picked mode in ssd_y, the CCLM candidate's chroma parts
-        x.ssd_y = (q.n & 4) ? (uint32_t)r.imin : (r.ssd_y | ((uint32_t)r.imin << 24));
-        x.ssd_c = r.ssd_c;
-        x.lvl_y = r.lvl_y;
-        x.lvl_c = r.lvl_c;
-    } else if (q.kind == K_FULL || q.kind == K_CCLMSEARCH) {
-        x.ssd_y = q.kind == K_CCLMSEARCH ? (uint32_t)r.imin : r.ssd_y; // a chroma-only request: the picked mode rides here
+    if (q.kind == K_FULL) {
+        x.ssd_y = r.ssd_y;
         x.ssd_c = r.ssd_c;
         x.lvl_y = r.lvl_y;
         x.lvl_c = r.lvl_c;
@@ -2177,7 +1978,7 @@ __device__ __forceinline__ void team_publish(const Req& q, const Res& r, int par
     if (LANE == 0) SH.xr[par] = x;
 }
 
-enum { TC_START = 0, TC_A, TC_D, TC_E, TC_F, TC_DONE, TC_DC_START };
+enum { TC_START = 0, TC_A = 1, TC_D = 2, TC_E = 3, TC_F = 4 };
 
 // a member with nothing to evaluate in a stage
 __device__ __forceinline__ void team_idle(Req& q) {
@@ -2198,22 +1999,22 @@ __device__ __forceinline__ void team_defer_pull(CtuSt& t, const LeafSF& s, int c
     t.dp0 = (uint8_t)(1 | (comps << 1) | (holder << 3) | ((s.lg - 2) << 5));
 }
 
-// One step of a leaf search in the team schedule; par = parity of the exchange that delivered the results
+// One step of the search of the CTU's 32x32 candidate in the team schedule (the level schedule takes over once it is
+// decided, see TC_D; the CCLM stages TC_E and TC_F run at max-split-depth 0 only); par = parity of the exchange that delivered the results
 // of the previous step's requests.  Same decisions, in the same order, as leaf_step.
 __device__ __forceinline__ bool leaf_step_team(const Ctx& c, CtuSt& t, LeafSF& s, Req& q, int par, const Res& r) {
-    const int tree = s.tree;
-    const int both = tree == TREE_SINGLE ? 3 : 1;
+    constexpr int tree = TREE_SINGLE;
     const int me = c.member;
     int cont = s.cont;
     for (;;) {
         switch (cont) {
         case TC_START: // stage A: planar | DC | the directional SAD search (:887-973)
             if (me == 0) {
-                leaf_full(s, q, both, PLANAR, PLANAR, true, TC_A);
+                leaf_full(s, q, 3, PLANAR, PLANAR, true, TC_A);
             } else if (me == 1) {
-                leaf_full(s, q, both, DC, DC, true, TC_A);
+                leaf_full(s, q, 3, DC, DC, true, TC_A);
             } else if (me == 2) {
-                leaf_sadsearch(s, q, both, TC_A); // the 13 directional SADs + both step-search rounds (K_SADSEARCH)
+                leaf_sadsearch(s, q, TC_A); // the 13 directional SADs + both step-search rounds (K_SADSEARCH)
             } else {
                 team_idle(q);
             }
@@ -2252,7 +2053,7 @@ __device__ __forceinline__ bool leaf_step_team(const Ctx& c, CtuSt& t, LeafSF& s
             const int mode = k == 0 ? cm : (k == 1 ? cm - 1 : cm + 1);
             const bool act = k == 0 || (k == 1 ? !(cm < 3) : !(cm + 1 > 66));
             if (me != holder && act) {
-                leaf_full(s, q, both, mode, mode, true, TC_D);
+                leaf_full(s, q, 3, mode, mode, true, TC_D);
             } else {
                 team_idle(q);
             }
@@ -2285,10 +2086,6 @@ __device__ __forceinline__ bool leaf_step_team(const Ctx& c, CtuSt& t, LeafSF& s
             const int m = s.mode, holder = s.holder;
             s.luma_mode = (uint8_t)m;
             s.chroma_mode = (uint8_t)m;
-            if (tree == TREE_DUAL_LUMA) { // every tile gets the winner's luma; nothing else to decide
-                team_defer_pull(t, s, 1, holder);
-                return false;
-            }
             if (s.lg == 5 && c.k->max_depth >= 1) {
                 // The CTU's 32x32 candidate, and the level schedule follows: its LUMA mode is all the other levels need
                 // (their MPM classes), and it is decided now.  Everybody pulls the winner (member 0 keeps
@@ -2312,7 +2109,7 @@ __device__ __forceinline__ bool leaf_step_team(const Ctx& c, CtuSt& t, LeafSF& s
             // the three CCLM probes side by side on the winner's luma, which everybody pulls first (one member doing
             // the three-mode pass and the evaluation in one request, as the wave schedule does, measured 3 % slower here)
             if (me < 3)
-                leaf_sadlist(s, q, 2, 1, (uint32_t)(me == 0 ? LT_CCLM : (me == 1 ? T_CCLM : L_CCLM)), 0, 0, 0, false, TC_E);
+                leaf_sadlist(s, q, me == 0 ? LT_CCLM : (me == 1 ? T_CCLM : L_CCLM), TC_E);
             else
                 team_idle(q);
             team_restore(c, s, q, 3, holder);
@@ -2356,9 +2153,6 @@ __device__ __forceinline__ bool leaf_step_team(const Ctx& c, CtuSt& t, LeafSF& s
             team_defer_pull(t, s, 2, ev);
             return false;
         }
-        case TC_DONE:
-            return false;
-        // ---- DUAL_TREE_CHROMA leaf (:794-885): the three CCLM probes and the DM evaluation side by side ----
         default:
             return false;
         }
@@ -2376,7 +2170,7 @@ __device__ __forceinline__ bool leaf_step_team(const Ctx& c, CtuSt& t, LeafSF& s
 // searched it and its children are decided; whoever lost copies the winner's reconstruction and decision maps from
 // the tile of the member that holds them (LDS to LDS), so every member's tile shows later blocks exactly the
 // neighbourhood the reference's depth-first search shows them.  Each member runs the ordinary one-wave leaf search
-// (leaf_step with the packed requests K_LEAF16 / K_LEAF8 / K_LEAF4 / K_LEAFC4), solo trellis walks throughout.
+// (leaf_step with the packed requests K_LEAF16 / K_LEAF8; member 3 issues K_SPLIT8), solo trellis walks throughout.
 // A decision has two meeting points (everybody arrived: the costs are posted; everybody has copied: tiles may be
 // written again); they are counters in LDS that the members of the decision poll -- a workgroup barrier would also
 // stop the members of other levels, who are in the middle of their own searches.  Same decisions, same f32 sums in
@@ -2502,8 +2296,9 @@ __device__ __forceinline__ void lv_post_split(int L, float sp) {
 // slots in global scratch they were saved to (copy_block): the reference's cache_reconsts /
 // restore_reconsts (block_splitter.rs:807-840, 1085-1145), with the saved planes kept in L2/HBM
 // instead of LDS.
-enum { T_START = 0, T_ENTER, T_NODE_LEAF, T_LEAF4_EMIT, T_LEAF4, T_LEAFC, T_REGEN_DONE, T_RETURN, T_FINAL_Z, T_FZ_TAIL, T_FZ_NEXT,
-       T_LV_UNIT, T_LV_LEAFDONE, T_LV_UP, T_SPLIT8, T_LV_SERVE };
+// (the numbers index the profile build's counters, tools/phase_profile.py: 3 .. 5 were the 4x4 leaf walk K_SPLIT8 replaced)
+enum { T_START = 0, T_ENTER = 1, T_NODE_LEAF = 2, T_REGEN_DONE = 6, T_RETURN = 7, T_FINAL_Z = 8, T_FZ_TAIL = 9, T_FZ_NEXT = 10,
+       T_LV_UNIT = 11, T_LV_LEAFDONE = 12, T_LV_UP = 13, T_SPLIT8 = 14, T_LV_SERVE = 15 };
 
 template <bool TEAM, bool D3>
 __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
@@ -2514,7 +2309,7 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
         if (in_leaf) {
             // team schedule: the results of the previous requests are in the members' XRes of parity xpar ^ 1
             LeafSF ls = snap_leaf(t.leaf);
-            if ((TEAM && !t.lvmode) ? leaf_step_team(c, t, ls, q, t.xpar ^ 1, r) : leaf_step<D3>(c, ls, r, q)) {
+            if ((TEAM && !t.lvmode) ? leaf_step_team(c, t, ls, q, t.xpar ^ 1, r) : leaf_step(c, ls, r, q)) {
                 if (t.pend) { // the first request of a node's first child saves the unsplit candidate
                     req_copy(q, COPY_SAVE, t.pend, t.pslot, t.pbx, t.pby, t.plg);
                     t.pend = 0;
@@ -2538,7 +2333,7 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
             t.lg = (uint8_t)lg;
             // wave schedule, a node whose split is tested next: the search saves its best candidate straight to the
             // node's slot 1 + level, which then holds the unsplit candidate without a save of its own (T_NODE_LEAF)
-            leaf_init(t.leaf, TREE_SINGLE, t.bx, t.by, lg, 0, (!TEAM && t.level < t.max_depth) ? 1 + t.level : 0);
+            leaf_init(t.leaf, t.bx, t.by, lg, (!TEAM && t.level < t.max_depth) ? 1 + t.level : 0);
             if (TEAM && !t.lvmode) t.leaf.cont = TC_START;
             in_leaf = true;
             cont = T_NODE_LEAF;
@@ -2574,10 +2369,11 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
                 cont = (c.member == 0 || c.member > t.max_depth) ? T_LV_UP : T_LV_UNIT;
                 break;
             }
-            // the unsplit candidate's reconstruction goes to slot 1 + level (cache_reconsts, :1085-1100).  Wave schedule:
+            // ---- wave schedule from here on ----
+            // the unsplit candidate's reconstruction goes to slot 1 + level (cache_reconsts, :1085-1100):
             // the search saved its winner there already (luma and DM chroma, leaf_init above), so all that is left to
             // save is the chroma pair when the CCLM candidate won; a packed 8x8 search (K_LEAF8) saved nothing.
-            t.pend = (uint8_t)((TEAM || lg == 3) ? 3 : (mc >= LT_CCLM ? 2 : 0));
+            t.pend = (uint8_t)(lg == 3 ? 3 : (mc >= LT_CCLM ? 2 : 0));
             t.pbx = t.bx;
             t.pby = t.by;
             t.plg = (uint8_t)lg;
@@ -2595,7 +2391,7 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
                 // lost before its first child.  No child has touched the tile or the maps, which hold the unsplit candidate
                 // as they do for a node at max-split-depth, so there is nothing to save or to restore
                 float bound;
-                if (!TEAM && split_floor_cut(c, 0.0f, 4, 2 + level + 1, false, ns, &bound)) {
+                if (split_floor_cut(c, 0.0f, 4, 2 + level + 1, false, ns, &bound)) {
                     PROF_ADD2(PH_CUT + 2 + level, 0, 4);
                     PROF_ADD2(PH_CUT + 5, 0, 1);
                     t.pend = 0;
@@ -2621,67 +2417,9 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
             return true;
         }
         case T_SPLIT8: {
-            if constexpr (D3) { // the split candidate of the 8x8 node came back: against the unsplit one, as T_LEAFC does
+            if constexpr (D3) { // the split candidate of the 8x8 node came back: against the unsplit one
                 const float split8 = r.vmin;
                 if (TEAM && t.lvmode) { // level schedule: member 3's unit is done
-                    lv_post_split(2, split8);
-                    cont = T_LV_UP;
-                    break;
-                }
-                if (split8 > t.ns_cost_cur) { // :1125-1145: the unsplit 8x8 wins, put it back
-                    t.rbx = t.bx;
-                    t.rby = t.by;
-                    t.rlg = t.lg;
-                    t.rl = t.ns_luma_cur;
-                    t.rc = t.ns_chroma_cur;
-                    q.kind = K_NOP;
-                    q.xchg = false;
-                    req_copy(q, COPY_RESTORE, 3, 1 + t.level, t.rbx, t.rby, t.rlg);
-                    t.cont = T_REGEN_DONE;
-                    return true;
-                }
-                t.ret = split8;
-                cont = T_RETURN;
-                break;
-            }
-            }
-            break;
-        case T_LEAF4_EMIT: {
-            if constexpr (D3) {
-                const int i8 = t.i8;
-                leaf_init(t.leaf, TREE_DUAL_LUMA, t.bx + (i8 & 1) * 4, t.by + (i8 >> 1) * 4, 2, 0);
-                if (TEAM && !t.lvmode) t.leaf.cont = TC_START;
-                in_leaf = true;
-                cont = T_LEAF4;
-                break;
-            }
-            }
-            break;
-        case T_LEAF4: {
-            if constexpr (D3) {
-                fill_maps(t.leaf.bx, t.leaf.by, 2, t.leaf.luma_mode, 0, true, false);
-                t.split8 = t.split8 + t.leaf.cost;
-                const int i8 = t.i8 + 1;
-                t.i8 = (uint8_t)i8;
-                if (i8 < 4) {
-                    cont = T_LEAF4_EMIT;
-                    break;
-                }
-                // DM = luma mode of the CU covering the parent's centre (block_splitter.rs:795-805)
-                const int bx = t.bx, by = t.by;
-                leaf_init(t.leaf, TREE_DUAL_CHROMA, bx, by, 3, uni((int)SH.luma_mode[((by + 4) >> 2) * 8 + ((bx + 4) >> 2)]));
-                if (TEAM && !t.lvmode) t.leaf.cont = TC_DC_START;
-                in_leaf = true;
-                cont = T_LEAFC;
-                break;
-            }
-            }
-            break;
-        case T_LEAFC: {
-            if constexpr (D3) {
-                fill_maps(t.bx, t.by, 3, 0, t.leaf.chroma_mode, false, true);
-                const float split8 = t.split8 + t.leaf.cost;
-                if (TEAM && t.lvmode) { // member 3's unit is done: the split candidate of 8x8 node lv_i
                     lv_post_split(2, split8);
                     cont = T_LV_UP;
                     break;
@@ -2795,7 +2533,7 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
                 }
                 const int lg = me == 1 ? 4 : 3;
                 t.lg = (uint8_t)lg;
-                leaf_init(t.leaf, TREE_SINGLE, bx, by, lg, 0);
+                leaf_init(t.leaf, bx, by, lg);
                 in_leaf = true;
                 cont = T_LV_LEAFDONE;
                 break;
@@ -2859,7 +2597,7 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
         case T_LV_SERVE: {
             if constexpr (TEAM) {
                 // Member 0 between its 32x32 candidate and the CTU's decision: pack {planar, DC} of member 2's 8x8 leaves
-                // (leaf8_search, q.n & 16), one job at a time: wait for a job or for "no more jobs", wait until the
+                // (K_SERVE8) and of member 3's 4x4 luma leaves (K_SERVE4), one job at a time: wait for a job or for "no more jobs", wait until the
                 // previous job's results have been taken, run it.
                 if (LANE == 0) SHT.lvb.srv_ready = 1;
                 const bool two = D3 && t.max_depth == 3; // member 3 posts jobs too
@@ -2901,7 +2639,6 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
                     lv_word_wait(&SHT.lvb.job4_ack, served4); // the previous results have been taken
                     req_full(q, 1, uni((int)SHT.lvb.job4_bx), uni((int)SHT.lvb.job4_by), 2, 0, 0, true, false, false, false);
                     q.kind = K_SERVE4;
-                    q.n = 1;
                     q.stage = 0;
                     q.tree = TREE_DUAL_LUMA;
                     t.cont = T_LV_SERVE;
@@ -2909,11 +2646,9 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
                 }
                 lv_word_wait(&SHT.lvb.job_ack, served8); // the previous job's reconstructions are still in this wave's park
                 req_full(q, 3, uni((int)SHT.lvb.job_bx), uni((int)SHT.lvb.job_by), 3, 0, 0, true, false, false, false);
-                q.kind = K_LEAF8;
-                q.n = 16;
+                q.kind = K_SERVE8;
                 q.stage = 0;
                 q.tree = TREE_SINGLE;
-                q.fcur = 0.0f;
                 t.cont = T_LV_SERVE;
                 return true;
             }
@@ -3077,7 +2812,7 @@ __device__ __forceinline__ void encode_ctu(Ctx& c, const PicBufs& pb, int ctu_co
         r = Res{};
 #else
         PROF_MARK(te0_);
-        r = evaluate<D3>(c, pb, q, overflow);
+        r = evaluate<TEAM, D3>(c, pb, q, overflow);
         PROF_MARK(te1_);
         PROF_ADDM(q.kind == K_NOP ? 3 : 1, te0_, te1_);
         PROF_ADD2(PH_EV + (((q.kind & 15) * 4 + ((q.kind == K_NOP ? q.copy_tlg : q.tlg) - 2)) & 63), te0_, te1_); // by request kind and block size

@@ -25,7 +25,7 @@
 // tools/build_exp.sh builds them with WRENC_EXPERIMENT_BUILD, which nothing else defines.
 #if !defined(WRENC_EXPERIMENT_BUILD) &&                                                                             \
     (defined(WRENC_EXP_CTRL_ONLY) || defined(WRENC_EXP_LDS_PAD) || defined(WRENC_EXP_NOINLINE_SAD) ||               \
-     defined(WRENC_EXP_NO_MERGED) || defined(WRENC_EXP_NO_ORG) || defined(WRENC_EXP_OLD_PDPC) ||                    \
+     defined(WRENC_EXP_NO_ORG) || defined(WRENC_EXP_OLD_PDPC) ||                                                    \
      defined(WRENC_EXP_SKIP_DCT) || defined(WRENC_EXP_SKIP_PRED) || defined(WRENC_EXP_SKIP_QUANT) ||                \
      defined(WRENC_EXP_SKIP_REFS) || defined(WRENC_EXP_SKIP_SAD))
 #error "a WRENC_EXP_* switch is set outside an experiment build: use tools/build_exp.sh"
