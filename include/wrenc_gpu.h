@@ -405,6 +405,12 @@ int wrenc_gpu_test_quantize_p16(wrenc_gpu_ctx* ctx, const int16_t* coef, int cou
                                 int64_t* level_cost);
 int wrenc_gpu_test_dequantize(wrenc_gpu_ctx* ctx, const int16_t* levels, int log2n, int count,
                               int16_t* deq);                            /* quantizer.rs:761 */
+/* The register transforms of the search's 4x4 passes (wrenc_amd/csrc/dev_transform.h fwd_dct4_reg / inv_dct4_reg): `count`
+ * 4x4 blocks, row-major int16, four per wavefront with one sample per lane, a last wavefront of fewer included.
+ * fwd: residuals -> coefficients (transformer.rs:2040).  inv: LEVELS -> residuals, dequantised in the lane at the
+ * context's QP (quantizer.rs:761) and inverted (transformer.rs:2380). */
+int wrenc_gpu_test_fwd_dct4_reg(wrenc_gpu_ctx* ctx, const int16_t* res, int count, int16_t* coef);
+int wrenc_gpu_test_inv_dct4_reg(wrenc_gpu_ctx* ctx, const int16_t* levels, int count, int16_t* res);
 
 /* Intra prediction of single blocks (intra_predictor.rs:56-144: reference-sample build :146-353, PLANAR
  * :759-1146, DC :1148-1285, ANGULAR 2..66 :1287-1602, PDPC :355-757, CCLM :1604-2055) in the environment of

@@ -678,9 +678,9 @@ __device__ __forceinline__ int pick_cclm(float lt, float t, float l) {
 // 64 lanes busy, and at max-split-depth 3 these leaves are 61 % of a CTU.  The full candidates of a leaf do not
 // depend on each other (they read only neighbours outside the block, :887-898, :974), so they are evaluated SIDE BY
 // SIDE, one candidate per 16-lane row: pack A = {planar, DC}, then the SAD search (sad_search), then pack B =
-// {cm, cm - 1, cm + 1}.  Every stage is the one the single evaluation uses, run over nb blocks (forward / inverse
-// transform, dequantisation) or written for rows (predict4_lane, quantize_p16).  The decisions are the reference's, in
-// its order: first minimum of [planar, DC, cm, cm - 1, cm + 1] as a running strict-less update; a candidate outside
+// {cm, cm - 1, cm + 1}.  Every stage computes what the single evaluation's computes, written for rows: a candidate's
+// block stays in its 16 lanes' registers from predict4_lane to the reconstruction (kRegDct4 below).  The decisions are
+// the reference's, in its order: first minimum of [planar, DC, cm, cm - 1, cm + 1] as a running strict-less update; a candidate outside
 // 2..66 is not evaluated (f32::MAX there).  The best candidate's reconstruction goes to the tile when its pack is
 // done (nothing reads the block's own area meanwhile: the reference samples are cached); no save / restore at all.
 // ---------------------------------------------------------------------------
@@ -710,6 +710,23 @@ __device__ __forceinline__ void lv_word_wait(const uint32_t* p, unsigned target)
     WSYNC();
 }
 
+// The 4x4 passes -- pack4_eval, leafc4_search, the chroma blocks of pack8_eval and the CCLM pair of leaf8_search -- keep
+// a block in registers from the prediction to the reconstruction: lane = (block, sample), fwd_dct4_reg, quantize_p16_reg
+// (quantize_pk for pack8_eval, which takes the coefficients from r1 and leaves the levels there), dequantize4_lane,
+// inv_dct4_reg.  -DWRENC_EXP_LDS_DCT4 (experiment builds) sends them through r1 / r2 with fwd_dct<2>, dequantize_t and
+// inv_dct<2> as before, for the A/B comparison; evaluate() and the final pass use those for every 4x4 block in any build.
+#ifdef WRENC_EXP_LDS_DCT4
+constexpr bool kRegDct4 = false;
+#else
+constexpr bool kRegDct4 = true;
+#endif
+// the lane's residual from its level; "no level of the pass is non-zero" (wave-uniform) gives zero without the transform
+__device__ __forceinline__ int residual4_reg(const Ctx& c, int level, bool any_level) {
+    int res = 0;
+    if (any_level) res = inv_dct4_reg(dequantize4_lane(c, level));
+    return res;
+}
+
 struct Pack4Out {
     uint32_t ssd[3];
     long long lvl[3];
@@ -724,24 +741,41 @@ __device__ __forceinline__ Pack4Out pack4_eval(const Ctx& c, const Req& q, int n
     PROF_MARK(t0_);
     const int v = predict4_lane(c, on ? mode : kNoMode);
     const int org = ((const uint8_t*)SH.r2)[kOrgLeaf + i];
-    if (s < nb) SH.r1[lane] = (int16_t)(on ? org - v : 0); // (a candidate that is not evaluated rides along as a zero block)
-    WSYNC();
+    const int res0 = on ? org - v : 0; // (a candidate that is not evaluated, and a row without one, ride along as zero blocks)
+    if (!kRegDct4) {
+        if (s < nb) SH.r1[lane] = (int16_t)res0;
+        WSYNC();
+    }
     PROF_MARK(t1_);
     PROF_ADD2(PH_PREDICT, t0_, t1_);
-    fwd_dct_lg(c, 2, nb, 0);
+    int coef = 0;
+    if (kRegDct4)
+        coef = fwd_dct4_reg(res0);
+    else
+        fwd_dct_lg(c, 2, nb, 0);
     PROF_MARK(t2_);
     PROF_ADD2(PH_FDCT, t1_, t2_);
     long long lvl[4];
     int any_mask = 0;
-    quantize_p16(c, nb, overflow, lvl, &any_mask);
+    int level = 0;
+    if (kRegDct4)
+        level = quantize_p16_reg(c, nb, coef, overflow, lvl, &any_mask);
+    else
+        quantize_p16(c, nb, overflow, lvl, &any_mask);
     PROF_MARK(t3_);
-    if (any_mask) { // (all levels zero: the residuals are zero too, and r1 already says so)
-        dequantize_t(c, 2, nb, 0);
-        inv_dct_lg(c, 2, nb, 0);
+    int res;
+    if (kRegDct4) {
+        res = residual4_reg(c, level, any_mask != 0);
+    } else {
+        if (any_mask) { // (all levels zero: the residuals are zero too, and r1 already says so)
+            dequantize_t(c, 2, nb, 0);
+            inv_dct_lg(c, 2, nb, 0);
+        }
+        res = (int)SH.r1[s < nb ? lane : 0];
     }
     PROF_MARK(t4_);
     PROF_ADD2(PH_IDCT, t3_, t4_);
-    int rec = (int16_t)(v + (int)SH.r1[s < nb ? lane : 0]); // pred as i16 + res, clamp (:178)
+    int rec = (int16_t)(v + res); // pred as i16 + res, clamp (:178)
     rec = min(max(rec, 0), 255);
     const int d = rec - org;
     const int row = row_sum_i32(on ? M24(d, d) : 0);
@@ -941,19 +975,28 @@ __device__ __forceinline__ Res leafc4_search(const Ctx& c, const Req& q, int* ov
         }
     }
     const int org = ((const uint8_t*)SH.r2)[kOrgLeaf + 256 + 16 * pl + i];
-    SH.r1[lane] = (int16_t)(org - v);
-    WSYNC();
+    if (!kRegDct4) {
+        SH.r1[lane] = (int16_t)(org - v);
+        WSYNC();
+    }
     PROF_MARK(t1_);
     PROF_ADD2(PH_PREDICT, t0_, t1_);
-    fwd_dct_lg(c, 2, 4, 0);
     long long lvl[4];
     int any_mask = 0;
-    quantize_p16(c, 4, overflow, lvl, &any_mask);
-    if (any_mask) {
-        dequantize_t(c, 2, 4, 0);
-        inv_dct_lg(c, 2, 4, 0);
+    int res;
+    if (kRegDct4) {
+        const int coef = fwd_dct4_reg(org - v);
+        res = residual4_reg(c, quantize_p16_reg(c, 4, coef, overflow, lvl, &any_mask), any_mask != 0);
+    } else {
+        fwd_dct_lg(c, 2, 4, 0);
+        quantize_p16(c, 4, overflow, lvl, &any_mask);
+        if (any_mask) {
+            dequantize_t(c, 2, 4, 0);
+            inv_dct_lg(c, 2, 4, 0);
+        }
+        res = (int)SH.r1[lane];
     }
-    int rec = (int16_t)(v + (int)SH.r1[lane]);
+    int rec = (int16_t)(v + res);
     rec = min(max(rec, 0), 255);
     const int d = rec - org;
     const int rs = row_sum_i32(M24(d, d));
@@ -986,7 +1029,8 @@ __device__ __forceinline__ Res leafc4_search(const Ctx& c, const Req& q, int* ov
 // walk per candidate between two workgroup barriers.  The full candidates of a leaf read only neighbours outside the
 // block (:887-898, :974), so they are evaluated in PACKS: pack A = {planar, DC}, then the SAD search, then pack B =
 // {cm, cm - 1, cm + 1}; a pack's candidates go through every stage together -- luma blocks one pass each, the 4x4
-// chroma blocks of all candidates four to a pass (predict4_lane), the transforms over nb blocks, and ONE trellis pass
+// chroma blocks of all candidates four to a pass (predict4_lane, transformed in registers: kRegDct4), the luma
+// transforms over nb blocks, and ONE trellis pass
 // for the pack's six or nine chains walked side by side by this wave alone (quantize_pk: no workgroup barrier).
 // Predictions and reconstructions of the pack are parked in LDS (PRED_PARK); the running best candidate's
 // reconstruction goes to the tile when its pack is done, so there is no save / restore through global scratch.
@@ -1027,8 +1071,12 @@ __device__ __forceinline__ Pack8Out pack8_eval(const Ctx& c, const Req& q, int n
         const bool in = blk < 2 * nc;
         const bool on = in && mode != kNoMode;
         const int v = predict4_lane(c, on ? mode : kNoMode, pl);
+        int rc = on ? (int)org[256 + 16 * pl + i16] - v : 0;
+        // the block's coefficients straight from the registers, to where quantize_pk takes them (every lane runs the
+        // transform; a row without a block carries zeros and stores nothing)
+        if (kRegDct4) rc = fwd_dct4_reg(rc);
         if (in) {
-            SH.r1[nL + 16 * blk + i16] = (int16_t)(on ? (int)org[256 + 16 * pl + i16] - v : 0);
+            SH.r1[nL + 16 * blk + i16] = (int16_t)rc;
             park[nL + 16 * blk + i16] = (uint8_t)v;
         }
         WSYNC();
@@ -1036,7 +1084,7 @@ __device__ __forceinline__ Pack8Out pack8_eval(const Ctx& c, const Req& q, int n
     PROF_MARK(t1_);
     PROF_ADD2(PH_PREDICT, t0_, t1_);
     fwd_dct_lg(c, 3, nc, 0);
-    fwd_dct_lg(c, 2, 2 * nc, nL);
+    if (!kRegDct4) fwd_dct_lg(c, 2, 2 * nc, nL);
     PROF_MARK(t2_);
     PROF_ADD2(PH_FDCT, t1_, t2_);
     bool any_y = false, any_c = false;
@@ -1046,7 +1094,7 @@ __device__ __forceinline__ Pack8Out pack8_eval(const Ctx& c, const Req& q, int n
         dequantize_t(c, 3, nc, 0);
         inv_dct_lg(c, 3, nc, 0);
     }
-    if (any_c) {
+    if (any_c && !kRegDct4) {
         dequantize_t(c, 2, 2 * nc, nL);
         inv_dct_lg(c, 2, 2 * nc, nL);
     }
@@ -1071,8 +1119,11 @@ __device__ __forceinline__ Pack8Out pack8_eval(const Ctx& c, const Req& q, int n
         const int blk = 4 * ps + row;
         const bool in = blk < 2 * nc;
         int dd = 0;
+        // r1 holds the block's residual, or (kRegDct4) its levels: the lane dequantises and inverts its own in registers
+        int res = in ? (int)SH.r1[nL + 16 * blk + i16] : 0;
+        if (kRegDct4) res = residual4_reg(c, res, any_c);
         if (in) {
-            int rec = (int16_t)((int)park[nL + 16 * blk + i16] + (int)SH.r1[nL + 16 * blk + i16]);
+            int rec = (int16_t)((int)park[nL + 16 * blk + i16] + res);
             rec = min(max(rec, 0), 255);
             park[nL + 16 * blk + i16] = (uint8_t)rec;
             const int d = rec - (int)org[256 + 16 * (blk & 1) + i16];
@@ -1258,19 +1309,28 @@ __device__ __forceinline__ Res leaf8_search(const Ctx& c, const Req& q, int* ove
         v = min(max(v, 0), 255);
     }
     const int org = ((const uint8_t*)SH.r2)[kOrgLeaf + 256 + 16 * pl + i];
-    if (mine) SH.r1[lane] = (int16_t)(org - v);
-    WSYNC();
+    if (!kRegDct4) {
+        if (mine) SH.r1[lane] = (int16_t)(org - v);
+        WSYNC();
+    }
     PROF_MARK(t1_);
     PROF_ADD2(PH_PREDICT, t0_, t1_);
-    fwd_dct_lg(c, 2, 2, 0);
     long long lvl[4];
     int any_mask = 0;
-    quantize_p16(c, 2, overflow, lvl, &any_mask);
-    if (any_mask) {
-        dequantize_t(c, 2, 2, 0);
-        inv_dct_lg(c, 2, 2, 0);
+    int res;
+    if (kRegDct4) {
+        const int coef = fwd_dct4_reg(mine ? org - v : 0); // (rows 2, 3 ride along as zero blocks)
+        res = residual4_reg(c, quantize_p16_reg(c, 2, coef, overflow, lvl, &any_mask), any_mask != 0);
+    } else {
+        fwd_dct_lg(c, 2, 2, 0);
+        quantize_p16(c, 2, overflow, lvl, &any_mask);
+        if (any_mask) {
+            dequantize_t(c, 2, 2, 0);
+            inv_dct_lg(c, 2, 2, 0);
+        }
+        res = (int)SH.r1[mine ? lane : 0];
     }
-    int rec = (int16_t)(v + (int)SH.r1[mine ? lane : 0]);
+    int rec = (int16_t)(v + res);
     rec = min(max(rec, 0), 255);
     const int d = rec - org;
     const int rs = row_sum_i32(mine ? M24(d, d) : 0);

@@ -254,6 +254,81 @@ __device__ __forceinline__ void inv_dct32_mfma(Ctx c, int o1) {
     WSYNC();
 }
 
+// ---------------------------------------------------------------------------
+// 4x4 blocks in registers (the packed 4x4 passes of the leaf searches, dev_search.h): four blocks per wave,
+// lane = (block LANE >> 4, sample LANE & 15, row-major), one value per lane in and out.  A 4x4 block lies inside one
+// 16-lane DPP row, so the two stages of a transform exchange their operands between lanes and nothing goes through LDS:
+//   the four lanes 4 y + 0..3 of a quad (one row of the block):  quad_perm broadcasts [k, k, k, k]
+//   the four lanes 4 i + x at stride 4 (one column of the block):  row_ror:4 k
+// The basis elements (64, 83, 36 and their signs) are the bytes of literals picked by the lane's x = LANE & 3 or
+// y = (LANE >> 2) & 3: no table, no load.  Same sums, offsets, shifts and casts as fwd_dct<2> / inv_dct<2>.
+// All 64 lanes must be enabled where these are called (a DPP read of a disabled lane is not that lane's value):
+// idle rows carry zeros, and no call sits under a lane-divergent branch.
+// ---------------------------------------------------------------------------
+constexpr int kT4[4][4] = {{64, 64, 64, 64}, {83, 36, -36, -83}, {64, -64, -64, 64}, {36, -83, 83, -36}}; // T_4[u][x]
+// row_ror:4 k hands lane j (of the stride-4 column) the value of lane (j - k) & 3 (the impulse cases of
+// tests/test_gpu_blocks4_registers.py pin this direction: with the other one every off-diagonal coefficient moves)
+constexpr int ror4_src(int j, int k) { return (j - k) & 3; }
+enum { T4_FWD1, T4_FWD2, T4_INV1, T4_INV2 };
+// the basis element that goes with operand k of a stage, for the lanes of index j = 0..3, as bytes j of one word
+constexpr uint32_t t4_word(int stage, int k) {
+    uint32_t w = 0;
+    for (int j = 0; j < 4; ++j) {
+        const int o = ror4_src(j, k);
+        const int t = stage == T4_FWD1   ? kT4[j][k]  // lane u = j, operand r[y][k]
+                      : stage == T4_FWD2 ? kT4[j][o]  // lane v = j, operand H[x][o]
+                      : stage == T4_INV1 ? kT4[o][j]  // lane y = j, operand d[o][x]
+                                         : kT4[k][j]; // lane x = j, operand V[y][k]
+        w |= (uint32_t)(t & 0xFF) << (8 * j);
+    }
+    return w;
+}
+template <int STAGE, int K>
+__device__ __forceinline__ int t4_sel(int shift8) { // shift8 = 8 * (the lane's index j)
+    constexpr uint32_t w = t4_word(STAGE, K);
+    return (int)(int8_t)(w >> shift8);
+}
+// the sum over the four operands of a stage: the lanes of the quad (QUAD) or of the stride-4 column
+template <int STAGE, bool QUAD>
+__device__ __forceinline__ int t4_stage(int v, int shift8) {
+    // |basis| <= 83 and |operand| < 2^23 (an i16, or stage 1 of the forward transform: <= 2 * 83 * 32768): exact in 24 bits
+    const int v0 = QUAD ? dpp_mov<0x00>(v) : v;
+    const int v1 = QUAD ? dpp_mov<0x55>(v) : dpp_mov<0x124>(v); // quad_perm [1,1,1,1] / row_ror:4
+    const int v2 = QUAD ? dpp_mov<0xAA>(v) : dpp_mov<0x128>(v); // quad_perm [2,2,2,2] / row_ror:8
+    const int v3 = QUAD ? dpp_mov<0xFF>(v) : dpp_mov<0x12C>(v); // quad_perm [3,3,3,3] / row_ror:12
+    const int t0 = t4_sel<STAGE, 0>(shift8), t1 = t4_sel<STAGE, 1>(shift8), t2 = t4_sel<STAGE, 2>(shift8), t3 = t4_sel<STAGE, 3>(shift8);
+    const int acc = M24(v0, t0) + M24(v1, t1) + M24(v2, t2) + M24(v3, t3);
+    return acc;
+}
+
+// forward (transformer.rs:2040-2378 at 4x4): the lane's residual r[y][x] -> the lane's coefficient C[y][x] (C[v][x] on
+// lane (v, x): the layout fwd_dct<2> leaves in r1)
+__device__ __forceinline__ int fwd_dct4_reg(int res) {
+#ifdef WRENC_EXP_SKIP_DCT
+    return res;
+#endif
+    const int lane = lane_fresh();
+    const int sx = 8 * (lane & 3), sy = 2 * (lane & 12);
+    // stage 1 on lane (y, u): H[u][y] = (sum_x T[u][x] r[y][x] + 1) >> 1
+    const int h = (t4_stage<T4_FWD1, true>(res, sx) + 1) >> 1;
+    // stage 2 on lane (v, x): C[v][x] = (sum_y T[v][y] H[x][y] + 128) >> 8, H[x][y] from lane (y, x)
+    return (int16_t)((t4_stage<T4_FWD2, false>(h, sy) + 128) >> 8);
+}
+
+// inverse (transformer.rs:2380-2737 at 4x4): the lane's dequantised coefficient d[y][x] -> the lane's residual r[y][x]
+__device__ __forceinline__ int inv_dct4_reg(int deq) {
+#ifdef WRENC_EXP_SKIP_DCT
+    return deq;
+#endif
+    const int lane = lane_fresh();
+    const int sx = 8 * (lane & 3), sy = 2 * (lane & 12);
+    // stage 1 on lane (y, x): V[y][x] = clamp16((sum_i T[i][y] d[i][x] + 64) >> 7)
+    int v = (t4_stage<T4_INV1, false>(deq, sy) + 64) >> 7;
+    v = min(max(v, -32768), 32767);
+    // stage 2 on lane (y, x): r[y][x] = (sum_i T[i][x] V[y][i] + 2048) >> 12
+    return (int16_t)((t4_stage<T4_INV2, true>(v, sx) + 2048) >> 12);
+}
+
 // o1: where the blocks start in r1 (i16 units, a multiple of 2)
 __device__ __forceinline__ void fwd_dct_lg(Ctx c, int lg, int nb, int o1 = 0) {
 #ifdef WRENC_EXP_SKIP_DCT // instruction-count experiment only: the residual stays where the coefficients should be

@@ -399,16 +399,36 @@ __global__ __launch_bounds__(64) void test_quantize_p16_kernel(const DevConst* _
     load_tables(c);
     const int first = 4 * blockIdx.x;
     const int nb = min(4, count - first);
-    if (threadIdx.x < 16 * nb) SH.r1[threadIdx.x] = in[(size_t)first * 16 + threadIdx.x];
-    WSYNC();
+    const bool mine = threadIdx.x < 16 * nb;
     int ovf = 0, any = 0;
     long long lvl[4];
-    quantize_p16(c, nb, &ovf, lvl, &any);
-    if (threadIdx.x < 16 * nb) out[(size_t)first * 16 + threadIdx.x] = SH.r1[threadIdx.x];
+    if (kRegDct4) { // the form the search runs: the lane's coefficient in, the lane's level out
+        const int level = quantize_p16_reg(c, nb, mine ? (int)in[(size_t)first * 16 + threadIdx.x] : 0, &ovf, lvl, &any);
+        if (mine) out[(size_t)first * 16 + threadIdx.x] = (int16_t)level;
+    } else {
+        if (mine) SH.r1[threadIdx.x] = in[(size_t)first * 16 + threadIdx.x];
+        WSYNC();
+        quantize_p16(c, nb, &ovf, lvl, &any);
+        if (mine) out[(size_t)first * 16 + threadIdx.x] = SH.r1[threadIdx.x];
+    }
     if (threadIdx.x == 0) {
         for (int b = 0; b < nb; ++b) cost[first + b] = lvl[b];
         if (ovf) atomicOr(overflow, 1);
     }
+}
+
+// The register transforms of the 4x4 passes (dev_transform.h): four consecutive 4x4 blocks per wave, lane = (block,
+// sample); forward: residuals -> fwd_dct4_reg; inverse: levels -> dequantize4_lane -> inv_dct4_reg.  Every lane runs the
+// transform (rows past the last block carry zeros) and only the lanes of a block load and store.
+__global__ __launch_bounds__(64) void test_dct4_reg_kernel(const DevConst* __restrict__ k, const int16_t* in, int count, int inverse,
+                                                           int16_t* out) {
+    Ctx c = {};
+    c.k = (const CONST_AS DevConst*)k;
+    const size_t at = (size_t)blockIdx.x * 64 + threadIdx.x;
+    const bool mine = at < (size_t)count * 16;
+    const int v = mine ? (int)in[at] : 0;
+    const int r = inverse ? inv_dct4_reg(dequantize4_lane(c, v)) : fwd_dct4_reg(v);
+    if (mine) out[at] = (int16_t)r;
 }
 
 // quantize_pk (the packed leaf searches' quantiser): one wave per pack of nc candidates
@@ -2285,6 +2305,16 @@ int wrenc_gpu_test_inv_dct32(wrenc_gpu_ctx* ctx, const int16_t* deq, int count, 
 int wrenc_gpu_test_inv_dct(wrenc_gpu_ctx* ctx, const int16_t* deq, int log2n, int count, int16_t* res) {
     return run_block_test(ctx, deq, log2n, count, res, [&](int16_t* i, int16_t* o) {
         hipLaunchKernelGGL(test_inv_dct_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const, i, log2n, o);
+    });
+}
+int wrenc_gpu_test_fwd_dct4_reg(wrenc_gpu_ctx* ctx, const int16_t* res, int count, int16_t* coef) {
+    return run_block_test(ctx, res, 2, count, coef, [&](int16_t* i, int16_t* o) {
+        hipLaunchKernelGGL(test_dct4_reg_kernel, dim3((count + 3) / 4), dim3(64), 0, ctx->stream, ctx->d_const, i, count, 0, o);
+    });
+}
+int wrenc_gpu_test_inv_dct4_reg(wrenc_gpu_ctx* ctx, const int16_t* levels, int count, int16_t* res) {
+    return run_block_test(ctx, levels, 2, count, res, [&](int16_t* i, int16_t* o) {
+        hipLaunchKernelGGL(test_dct4_reg_kernel, dim3((count + 3) / 4), dim3(64), 0, ctx->stream, ctx->d_const, i, count, 1, o);
     });
 }
 int wrenc_gpu_test_dequantize(wrenc_gpu_ctx* ctx, const int16_t* levels, int log2n, int count, int16_t* deq) {

@@ -22,7 +22,7 @@ EXPORTED_SYMBOLS = [
     "wrenc_gpu_upload", "wrenc_gpu_encode", "wrenc_gpu_set_slot_qp", "wrenc_gpu_sync", "wrenc_gpu_download", "wrenc_gpu_download_compact", "wrenc_gpu_compact_mask_words", "wrenc_gpu_expand_levels", "wrenc_gpu_download_tokens", "wrenc_gpu_download_metrics", "wrenc_gpu_download_complexity", "wrenc_gpu_metrics_values", "wrenc_gpu_test_metrics", "wrenc_gpu_test_load_record", "wrenc_gpu_device_info",
     "wrenc_gpu_alloc_host", "wrenc_gpu_free_host", "wrenc_gpu_encode_picture", "wrenc_gpu_set_schedule", "wrenc_gpu_last_schedule", "wrenc_gpu_stats_enable", "wrenc_gpu_last_encode_stats", "wrenc_gpu_last_encode_kernel_stats", "wrenc_gpu_final_pass_mismatches",
     "wrenc_gpu_test_fwd_dct", "wrenc_gpu_test_inv_dct", "wrenc_gpu_test_quantize",
-    "wrenc_gpu_test_dequantize", "wrenc_gpu_test_predict", "wrenc_gpu_test_fwd_dct32", "wrenc_gpu_test_inv_dct32", "wrenc_gpu_test_quantize_p16", "wrenc_gpu_test_quantize_pk", "wrenc_gpu_test_set_wave_slots", "wrenc_gpu_test_scratch_overflows", "wrenc_gpu_test_head_ranges", "wrenc_gpu_test_avail_tab",
+    "wrenc_gpu_test_dequantize", "wrenc_gpu_test_predict", "wrenc_gpu_test_fwd_dct32", "wrenc_gpu_test_inv_dct32", "wrenc_gpu_test_quantize_p16", "wrenc_gpu_test_quantize_pk", "wrenc_gpu_test_fwd_dct4_reg", "wrenc_gpu_test_inv_dct4_reg", "wrenc_gpu_test_set_wave_slots", "wrenc_gpu_test_scratch_overflows", "wrenc_gpu_test_head_ranges", "wrenc_gpu_test_avail_tab",
     "wrenc_gpu_set_visible_size", "wrenc_gpu_visible_size", "wrenc_gpu_test_download_originals",
 ]
 
@@ -516,6 +516,22 @@ class Encoder:
 
     def dequantize(self, blocks):
         return self._blocks(self.lib.wrenc_gpu_test_dequantize, blocks)
+
+    def _blocks4_reg(self, fn, blocks):
+        arr = np.ascontiguousarray(blocks, np.int16)
+        assert arr.shape[1:] == (4, 4)
+        out = np.zeros_like(arr)
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        self._check(fn(self.ctx, _p(arr), arr.shape[0], _p(out)))
+        return out
+
+    def fwd_dct4_reg(self, blocks):
+        """4x4 residual blocks through the register transform of the search's 4x4 passes (four blocks per wavefront)."""
+        return self._blocks4_reg(self.lib.wrenc_gpu_test_fwd_dct4_reg, blocks)
+
+    def inv_dct4_reg(self, levels):
+        """4x4 blocks of levels -> residuals: in-lane dequantisation at the context's QP + the register inverse transform."""
+        return self._blocks4_reg(self.lib.wrenc_gpu_test_inv_dct4_reg, levels)
 
     def predict_blocks(self, rec_y, rec_cb, rec_cr, items):
         """items: (n, 5) int32 {x, y, log2 luma size, comp (0 luma, 1 Cb+Cr pair, 2 luma 4x4 through the packed predictor
