@@ -526,14 +526,11 @@ __device__ __forceinline__ long long quantize_solo(Ctx c, int lg, int nb, int* o
 // dev_search.h leaf4_search): block b = lanes 16 b .. 16 b + 15, one lane per position, one quad walks each block's
 // 16 positions (a single chunk: no barrier of any kind).  Same algorithm and arithmetic as quantize_solo; block b's
 // level cost (block_splitter.rs:436-458) comes back in lvl[b], "has a non-zero level" in bit b of *any_mask.
-// REG (what the search runs): the lane's coefficient comes in a register, row-major (lane 16 b + 4 y + x of block b), and
-// the lane's level goes back the same way; nothing of either is kept in LDS.  The move to scan order and back (position
-// p of the row works on raster index scan[p]) is one ds_bpermute_b32 in and one ds_permute_b32 out: lane exchanges of the
-// LDS crossbar, no store, no bank access, and no wait between a store and its load.
-// !REG (the -DWRENC_EXP_LDS_DCT4 comparison build): coefficients r1[16 b ..] -> levels in place.
-// Scratch in both forms: r1 chunk entries, decw.
-template <bool REG>
-__device__ __forceinline__ int quantize_p16_impl(Ctx c, int nb, int coef, int* overflow, long long lvl[4], int* any_mask) {
+// The lane's coefficient comes in a register, row-major (lane 16 b + 4 y + x of block b), and the lane's level goes back
+// the same way; nothing of either is kept in LDS.  The move to scan order and back (position p of the row works on
+// raster index scan[p]) is one ds_bpermute_b32 in and one ds_permute_b32 out: lane exchanges of the LDS crossbar, no
+// store, no bank access, and no wait between a store and its load.  Scratch: r1 chunk entries, decw.
+__device__ __forceinline__ int quantize_p16_reg(Ctx c, int nb, int coef, int* overflow, long long lvl[4], int* any_mask) {
     c = uni(c);
     nb = uni(nb);
     const int lane = lane_fresh();
@@ -550,33 +547,20 @@ __device__ __forceinline__ int quantize_p16_impl(Ctx c, int nb, int coef, int* o
 #ifdef WRENC_EXP_SKIP_QUANT
     lvl[0] = lvl[1] = lvl[2] = lvl[3] = 0;
     *any_mask = 0;
-    if (!REG && lane < 16 * nb) SH.r1[lane] = 0;
     WSYNC();
     return 0;
 #endif
     const HeadT ht = head_ranges(k, 2);
     const int at = 16 * blk + (int)scan[p]; // the lane that holds this position's raster sample
-    int tc;
-    if (REG) {
-        tc = __builtin_amdgcn_ds_bpermute(4 * at, coef); // (every lane takes part, whatever its row holds)
-        if (!mine) tc = 0;
-    } else {
-        tc = mine ? (int)SH.r1[at] : 0;
-    }
+    int tc = __builtin_amdgcn_ds_bpermute(4 * at, coef); // (every lane takes part, whatever its row holds)
+    if (!mine) tc = 0;
     const int istar = row_min_i32(head_sig(tc, ht) ? p : P); // of this lane's block
     const unsigned long long nzb = __ballot(tc != 0);
     lvl[0] = lvl[1] = lvl[2] = lvl[3] = 0;
     *any_mask = 0;
-    if (nzb == 0ULL) return 0; // every block is zero: the levels are the zero coefficients (already in r1)
+    if (nzb == 0ULL) return 0; // every block is zero: the levels are the zero coefficients
     // every block's levels proven zero (the head proof over the whole block, head_alpha): nothing to walk or trace
-    if (__ballot(mine && head_bad(tc, p == P - 1, ht)) == 0ULL) {
-        if (!REG) {
-            WSYNC();
-            if (mine) SH.r1[at] = 0;
-            WSYNC();
-        }
-        return 0;
-    }
+    if (__ballot(mine && head_bad(tc, p == P - 1, ht)) == 0ULL) return 0;
     PROF_MARK(q1_);
     PROF_ADD2(PH_QPRE, q0_, q1_);
     WSYNC(); // every lane has its coefficient before the chunk entries overwrite r1
@@ -648,9 +632,8 @@ __device__ __forceinline__ int quantize_p16_impl(Ctx c, int nb, int coef, int* o
     if (mine) {
         int state = entry;
         level = (int16_t)emit_level(c, tc, qd, p == P - 1, nib, p, 0, state, zmask, sum_nz, fnz, ovf);
-        if (!REG) SH.r1[at] = (int16_t)level;
     }
-    if (REG) level = __builtin_amdgcn_ds_permute(4 * at, level); // scan position -> the raster sample's lane
+    level = __builtin_amdgcn_ds_permute(4 * at, level); // scan position -> the raster sample's lane
     const int pf = row_min_i32(fnz); // zeros before a block's first non-zero level cost nothing
     if (mine && (zmask & 1u) && p > pf) sum_nz += SHT.lv[0];
     {
@@ -670,22 +653,6 @@ __device__ __forceinline__ int quantize_p16_impl(Ctx c, int nb, int coef, int* o
     PROF_MARK(q3_);
     PROF_ADD2(PH_QTRACE, q2_, q3_);
     return level;
-}
-// the lane's coefficient -> the lane's level (row-major lanes, see above)
-__device__ __forceinline__ int quantize_p16_reg(Ctx c, int nb, int coef, int* overflow, long long lvl[4], int* any_mask) {
-#ifdef WRENC_EXP_P16_LDS_SCAN // comparison build: the move to scan order and back as a store + a load each
-    const int lane = lane_fresh();
-    if (lane < 16 * nb) SH.r1[lane] = (int16_t)coef;
-    WSYNC();
-    quantize_p16_impl<false>(c, nb, 0, overflow, lvl, any_mask);
-    return lane < 16 * nb ? (int)SH.r1[lane] : 0;
-#else
-    return quantize_p16_impl<true>(c, nb, coef, overflow, lvl, any_mask);
-#endif
-}
-// coefficients r1[16 b ..] -> levels in place
-__device__ __forceinline__ void quantize_p16(Ctx c, int nb, int* overflow, long long lvl[4], int* any_mask) {
-    quantize_p16_impl<false>(c, nb, 0, overflow, lvl, any_mask);
 }
 // in-lane dequantisation of a 4x4 block's level (quantizer.rs:761-1079; dequantize_t's arithmetic at lg = 2)
 __device__ __forceinline__ int dequantize4_lane(const Ctx& c, int level) {

@@ -400,6 +400,32 @@ __device__ __forceinline__ Res split8_search(const Ctx& c, const Req& q, int* ov
 __device__ __forceinline__ void serve_pack4(const Ctx& c, const Req& q, int* overflow);
 __device__ __forceinline__ void serve_pack8(const Ctx& c, const Req& q, int* overflow);
 
+// The CCLM probe of a block's chroma pair: get_chroma_intra_pred_aux_cost of LT, T, L_CCLM in one sample pass, their trace
+// records, then the pick of block_splitter.rs:847-854 (SADs are integers < 2^20: comparing them is comparing the
+// reference's f32 values).  Returns the picked mode; *all = the model parameters of the three modes (cclm_pick takes the
+// picked mode's from there).
+__device__ __forceinline__ int cclm_probe(const Ctx& c, int tx, int ty, int lg, int tree, CclmParams* all) {
+    const int lane = lane_fresh();
+    const unsigned acc = sad_list_cclm(c, tx, ty, lg, all);
+    const unsigned lt = (unsigned)__builtin_amdgcn_readlane((int)acc, 0), t = (unsigned)__builtin_amdgcn_readlane((int)acc, 1),
+                   l = (unsigned)__builtin_amdgcn_readlane((int)acc, 2);
+    if (c.trace && lane < 3)
+        TRACE_REC(c.ctu_x + tx, c.ctu_y + ty, lg, tree, 2, 0, lane == 0 ? LT_CCLM : (lane == 1 ? T_CCLM : L_CCLM),
+                  __float_as_int((float)acc));
+    return (lt <= t && lt <= l) ? LT_CCLM : (t <= l ? T_CCLM : L_CCLM);
+}
+
+// the CCLM prediction of sample (x, y) of plane pl of the 4x4 chroma pair of q's 8x8 block, in the lane's registers
+__device__ __forceinline__ int cclm_pred4_lane(const Ctx& c, const Req& q, const CclmPick& pick, int pl, int x, int y) {
+    int v = 128;
+    if (!pick.flat128) {
+        const int ds = cclm_ds6(c, q.tx, q.ty, 2 * y, 2 * x, pick.avail_l);
+        v = (M24(ds, pl ? pick.a1 : pick.a0) >> (pl ? pick.k1 : pick.k0)) + (pl ? pick.b1 : pick.b0);
+        v = min(max(v, 0), 255);
+    }
+    return v;
+}
+
 // The evaluator: every block evaluation of the search, of the regeneration and of the final pass
 // goes through this one inlined copy (the search logic below is a state machine that hands out
 // evaluation requests; no function calls in the hot path).
@@ -430,17 +456,10 @@ __device__ __forceinline__ Res evaluate(const Ctx& c, const PicBufs& pb, const R
     int mc = q.mc;
     CclmPick cpick_ = CclmPick{};
     if (q.kind == K_CCLMSEARCH) {
-        // get_chroma_intra_pred_aux_cost of LT, T, L_CCLM in one sample pass, then the pick of :847-854 (SADs are
-        // integers < 2^20: comparing them is comparing the reference's f32 values); the evaluation follows below
+        // the three CCLM probes and the pick (cclm_probe); the evaluation follows below
         if (q.tlg > 4) stage_org(c, 2, q.tx, q.ty, q.tlg);
         CclmParams call_;
-        const unsigned acc = sad_list_cclm(c, q.tx, q.ty, q.tlg, &call_);
-        const unsigned lt = (unsigned)__builtin_amdgcn_readlane((int)acc, 0), t = (unsigned)__builtin_amdgcn_readlane((int)acc, 1),
-                       l = (unsigned)__builtin_amdgcn_readlane((int)acc, 2);
-        if (c.trace && LANE < 3)
-            TRACE_REC(c.ctu_x + q.tx, c.ctu_y + q.ty, q.tlg, q.tree, 2, 0, LANE == 0 ? LT_CCLM : (LANE == 1 ? T_CCLM : L_CCLM),
-                      __float_as_int((float)acc));
-        mc = (lt <= t && lt <= l) ? LT_CCLM : (t <= l ? T_CCLM : L_CCLM);
+        mc = cclm_probe(c, q.tx, q.ty, q.tlg, q.tree, &call_);
         r.imin = mc;
         cpick_ = cclm_pick(call_, 2 * cclm_mode_index(mc)); // the evaluation below predicts with these
     }
@@ -679,7 +698,7 @@ __device__ __forceinline__ int pick_cclm(float lt, float t, float l) {
 // depend on each other (they read only neighbours outside the block, :887-898, :974), so they are evaluated SIDE BY
 // SIDE, one candidate per 16-lane row: pack A = {planar, DC}, then the SAD search (sad_search), then pack B =
 // {cm, cm - 1, cm + 1}.  Every stage computes what the single evaluation's computes, written for rows: a candidate's
-// block stays in its 16 lanes' registers from predict4_lane to the reconstruction (kRegDct4 below).  The decisions are
+// block stays in its 16 lanes' registers from predict4_lane to the reconstruction (pass4_reg below).  The decisions are
 // the reference's, in its order: first minimum of [planar, DC, cm, cm - 1, cm + 1] as a running strict-less update; a candidate outside
 // 2..66 is not evaluated (f32::MAX there).  The best candidate's reconstruction goes to the tile when its pack is
 // done (nothing reads the block's own area meanwhile: the reference samples are cached); no save / restore at all.
@@ -713,18 +732,43 @@ __device__ __forceinline__ void lv_word_wait(const uint32_t* p, unsigned target)
 // The 4x4 passes -- pack4_eval, leafc4_search, the chroma blocks of pack8_eval and the CCLM pair of leaf8_search -- keep
 // a block in registers from the prediction to the reconstruction: lane = (block, sample), fwd_dct4_reg, quantize_p16_reg
 // (quantize_pk for pack8_eval, which takes the coefficients from r1 and leaves the levels there), dequantize4_lane,
-// inv_dct4_reg.  -DWRENC_EXP_LDS_DCT4 (experiment builds) sends them through r1 / r2 with fwd_dct<2>, dequantize_t and
-// inv_dct<2> as before, for the A/B comparison; evaluate() and the final pass use those for every 4x4 block in any build.
-#ifdef WRENC_EXP_LDS_DCT4
-constexpr bool kRegDct4 = false;
-#else
-constexpr bool kRegDct4 = true;
-#endif
+// inv_dct4_reg.  All but pack8_eval's run the same function, pass4_reg; evaluate() and the final pass send every 4x4
+// block through r1 / r2 with fwd_dct<2>, dequantize_t and inv_dct<2>.
 // the lane's residual from its level; "no level of the pass is non-zero" (wave-uniform) gives zero without the transform
 __device__ __forceinline__ int residual4_reg(const Ctx& c, int level, bool any_level) {
     int res = 0;
     if (any_level) res = inv_dct4_reg(dequantize4_lane(c, level));
     return res;
+}
+
+// One pass of four 4x4 blocks, lane = (block LANE / 16, sample LANE % 16): v = the lane's prediction, org its original,
+// on = the lane's block is evaluated (a block that is not, and a row past nb, ride along as zero blocks and count no
+// error).  Residual, transform, quantisation of the nb blocks side by side, and back: the lane's reconstruction (pred as
+// i16 + res, clamp: :178), its block's SSD summed over the row, the blocks' level costs and "has a non-zero level" bits.
+struct Pass4Out {
+    int rec, row_ssd;
+    long long lvl[4];
+    int any_mask;
+};
+__device__ __forceinline__ Pass4Out pass4_reg(const Ctx& c, int nb, bool on, int v, int org, int* overflow) {
+    Pass4Out o;
+    PROF_MARK(t1_);
+    const int coef = fwd_dct4_reg(on ? org - v : 0);
+    PROF_MARK(t2_);
+    PROF_ADD2(PH_FDCT, t1_, t2_);
+    o.any_mask = 0;
+    const int level = quantize_p16_reg(c, nb, coef, overflow, o.lvl, &o.any_mask);
+    PROF_MARK(t3_);
+    const int res = residual4_reg(c, level, o.any_mask != 0);
+    PROF_MARK(t4_);
+    PROF_ADD2(PH_IDCT, t3_, t4_);
+    const int rec = min(max((int)(int16_t)(v + res), 0), 255);
+    const int d = rec - org;
+    o.rec = rec;
+    o.row_ssd = row_sum_i32(on ? M24(d, d) : 0);
+    PROF_MARK(t5_);
+    PROF_ADD2(PH_RECON, t4_, t5_);
+    return o;
 }
 
 struct Pack4Out {
@@ -741,54 +785,91 @@ __device__ __forceinline__ Pack4Out pack4_eval(const Ctx& c, const Req& q, int n
     PROF_MARK(t0_);
     const int v = predict4_lane(c, on ? mode : kNoMode);
     const int org = ((const uint8_t*)SH.r2)[kOrgLeaf + i];
-    const int res0 = on ? org - v : 0; // (a candidate that is not evaluated, and a row without one, ride along as zero blocks)
-    if (!kRegDct4) {
-        if (s < nb) SH.r1[lane] = (int16_t)res0;
-        WSYNC();
-    }
     PROF_MARK(t1_);
     PROF_ADD2(PH_PREDICT, t0_, t1_);
-    int coef = 0;
-    if (kRegDct4)
-        coef = fwd_dct4_reg(res0);
-    else
-        fwd_dct_lg(c, 2, nb, 0);
-    PROF_MARK(t2_);
-    PROF_ADD2(PH_FDCT, t1_, t2_);
-    long long lvl[4];
-    int any_mask = 0;
-    int level = 0;
-    if (kRegDct4)
-        level = quantize_p16_reg(c, nb, coef, overflow, lvl, &any_mask);
-    else
-        quantize_p16(c, nb, overflow, lvl, &any_mask);
-    PROF_MARK(t3_);
-    int res;
-    if (kRegDct4) {
-        res = residual4_reg(c, level, any_mask != 0);
-    } else {
-        if (any_mask) { // (all levels zero: the residuals are zero too, and r1 already says so)
-            dequantize_t(c, 2, nb, 0);
-            inv_dct_lg(c, 2, nb, 0);
-        }
-        res = (int)SH.r1[s < nb ? lane : 0];
-    }
-    PROF_MARK(t4_);
-    PROF_ADD2(PH_IDCT, t3_, t4_);
-    int rec = (int16_t)(v + res); // pred as i16 + res, clamp (:178)
-    rec = min(max(rec, 0), 255);
-    const int d = rec - org;
-    const int row = row_sum_i32(on ? M24(d, d) : 0);
+    const Pass4Out p = pass4_reg(c, nb, on, v, org, overflow);
+    PROF_MARK(t5_);
 #pragma unroll
     for (int b = 0; b < 3; ++b) {
-        o.ssd[b] = (uint32_t)__builtin_amdgcn_readlane(row, 16 * b);
-        o.lvl[b] = lvl[b];
+        o.ssd[b] = (uint32_t)__builtin_amdgcn_readlane(p.row_ssd, 16 * b);
+        o.lvl[b] = p.lvl[b];
     }
-    o.rec = rec;
+    o.rec = p.rec;
     WSYNC();
-    PROF_MARK(t5_);
-    PROF_ADD2(PH_RECON, t4_, t5_);
+    PROF_MARK(t6_);
+    PROF_ADD2(PH_RECON, t5_, t6_); // (the pass's PH_RECON ends at the row sums)
     return o;
+}
+
+// The end of a SINGLE_TREE leaf search (block_splitter.rs:1040-1072): the winner keeps its DM chroma unless the picked
+// CCLM mode is strictly cheaper (DM on a tie, :857-873 and :1062); cur / cclm_cost = get_chroma_intra_pred_cost of the two
+__device__ __forceinline__ bool dm_keeps(float cur, float cclm_cost) {
+    return cur == fminf(cclm_cost, fminf(cur, 3.40282347e+38f));
+}
+// ... and the final get_intra_pred_cost: the winner's luma (mode ml, class cls) with its own chroma (parts eb) or with
+// the CCLM chroma (mode cm, parts e = eb with the CCLM evaluation's chroma parts)
+struct ChromaFinal {
+    bool dm_wins;
+    float cost;
+    int mc;
+};
+__device__ __forceinline__ ChromaFinal chroma_final(const Ctx& c, float cur, float cclm_cost, const EvalParts& eb, const EvalParts& e,
+                                                    int cls, int ml, int cm) {
+    ChromaFinal f;
+    f.dm_wins = dm_keeps(cur, cclm_cost);
+    f.cost = f.dm_wins ? uni_f(assemble_cost(c, TREE_SINGLE, cls, ml, eb)) : uni_f(assemble_cost(c, TREE_SINGLE, cls, cm, e));
+    f.mc = f.dm_wins ? ml : cm;
+    return f;
+}
+
+// The running best of a leaf's full candidates: the reference's "first minimum wins" over [planar, DC, cm, cm - 1,
+// cm + 1], kept as a strict-less running update in that order.  win = the winner's index in the pack that is being
+// merged (-1: none of this pack so far); first = no candidate yet (the first one is taken whatever it costs).
+struct LeafBest {
+    float cost;
+    int mode, cls;
+    EvalParts e;
+    int win;
+    bool first;
+};
+__device__ __forceinline__ LeafBest leaf_best_init(int mode) {
+    LeafBest b;
+    b.cost = 3.40282347e+38f;
+    b.mode = mode;
+    b.cls = 0;
+    b.e.ssd_y = b.e.ssd_c = 0;
+    b.e.lvl_y = b.e.lvl_c = 0;
+    b.win = -1;
+    b.first = true;
+    return b;
+}
+// one candidate of a pack that has come back (index k in its pack, luma and chroma mode `mode`, parts e): its cost, the
+// trace record, the running first minimum; returns whether it is the new best
+__device__ __forceinline__ bool leaf_candidate(const Ctx& c, int bx, int by, int lg, int tree, const MpmList& mpl, LeafBest& b,
+                                               int k, int mode, const EvalParts& e) {
+    const int cls = mpm_class_of(mpl, mode);
+    const float val = uni_f(assemble_cost(c, tree, cls, mode, e));
+    if (c.trace && lane_fresh() == 0) TRACE_REC(c.ctu_x + bx, c.ctu_y + by, lg, tree, 1, mode, mode, __float_as_int(val));
+    const bool take = b.first || val < b.cost;
+    if (take) {
+        b.cost = val;
+        b.mode = mode;
+        b.cls = cls;
+        b.e = e;
+        b.win = k;
+    }
+    b.first = false;
+    return take;
+}
+
+// candidate k of a 4x4 luma pack as parts: no chroma (DUAL_TREE_LUMA)
+__device__ __forceinline__ EvalParts pack4_parts(const Pack4Out& p, int k) {
+    EvalParts e;
+    e.ssd_y = p.ssd[k];
+    e.ssd_c = 0;
+    e.lvl_y = p.lvl[k];
+    e.lvl_c = 0;
+    return e;
 }
 
 __device__ __forceinline__ Res leaf4_search(const Ctx& c, const Req& q, int* overflow) {
@@ -796,30 +877,8 @@ __device__ __forceinline__ Res leaf4_search(const Ctx& c, const Req& q, int* ove
     const int lane = lane_fresh();
     if (q.refs0) build_refs(c, 0, q.tx, q.ty, 2);
     const int x = lane & 3, y = (lane >> 2) & 3, row = lane >> 4;
-    float best = 3.40282347e+38f;
-    int best_mode = PLANAR;
-    // one candidate of a pack that has come back: its cost, the trace record, the running first minimum; returns
-    // whether it is the new best
+    LeafBest best = leaf_best_init(PLANAR);
     const MpmList mpl_ = mpm_list(c, q.tx, q.ty, 2);
-#define LEAF4_CANDIDATE(P, B, M)                                                                                       \
-    do {                                                                                                               \
-        EvalParts e_;                                                                                                  \
-        e_.ssd_y = (P).ssd[B];                                                                                         \
-        e_.ssd_c = 0;                                                                                                  \
-        e_.lvl_y = (P).lvl[B];                                                                                         \
-        e_.lvl_c = 0;                                                                                                  \
-        const int cls_ = mpm_class_of(mpl_, (M));                                                                      \
-        const float val_ = uni_f(assemble_cost(c, TREE_DUAL_LUMA, cls_, (M), e_));                                     \
-        if (c.trace && lane == 0)                                                                                      \
-            TRACE_REC(c.ctu_x + q.tx, c.ctu_y + q.ty, 2, TREE_DUAL_LUMA, 1, (M), (M), __float_as_int(val_));           \
-        if (first_ || val_ < best) {                                                                                   \
-            best = val_;                                                                                               \
-            best_mode = (M);                                                                                           \
-            win_ = (B);                                                                                                \
-        }                                                                                                              \
-        first_ = false;                                                                                                \
-    } while (0)
-    bool first_ = true;
     // level schedule (team kernel): member 3's 4x4 luma leaves get their pack A from member 0, the server (serve_pack4;
     // the same protocol as for member 2's 8x8 leaves, leaf8_search)
     constexpr int kSrv4Byte = 448; // in the server's decw: 2 x 16 reconstructed samples, then ssd[2] (u32), lvl[2] (i64)
@@ -836,10 +895,9 @@ __device__ __forceinline__ Res leaf4_search(const Ctx& c, const Req& q, int* ove
         // pack A: planar and DC (:887-898)
         PROF_MARK(l4a0_);
         const Pack4Out a = pack4_eval(c, q, 2, PLANAR, DC, kNoMode, overflow);
-        int win_ = -1;
-        LEAF4_CANDIDATE(a, 0, PLANAR);
-        LEAF4_CANDIDATE(a, 1, DC);
-        if (row == win_) rec_put(0, q.tx + x, q.ty + y, a.rec);
+        leaf_candidate(c, q.tx, q.ty, 2, TREE_DUAL_LUMA, mpl_, best, 0, PLANAR, pack4_parts(a, 0));
+        leaf_candidate(c, q.tx, q.ty, 2, TREE_DUAL_LUMA, mpl_, best, 1, DC, pack4_parts(a, 1));
+        if (row == best.win) rec_put(0, q.tx + x, q.ty + y, a.rec);
         WSYNC();
         PROF_MARK(l4a1_);
         PROF_ADD2(PH_L4 + 1, l4a0_, l4a1_);
@@ -854,7 +912,7 @@ __device__ __forceinline__ Res leaf4_search(const Ctx& c, const Req& q, int* ove
         float fa = c.k->cand_floor_ang;
         const float f1 = c.k->cand_floor[1];
         if (mpl_.k0 > DC && f1 < fa) fa = f1;
-        cut_ = uni((int)(best <= fa)) != 0; // (every lane holds the same scalars: a scalar branch)
+        cut_ = uni((int)(best.cost <= fa)) != 0; // (every lane holds the same scalars: a scalar branch)
         if (cut_) PROF_ADD2(PH_CUT + 6, 0, 1);
     }
     if (!cut_) {
@@ -871,17 +929,17 @@ __device__ __forceinline__ Res leaf4_search(const Ctx& c, const Req& q, int* ove
         // has a floor >= best (a pack of two costs what a pack of three costs, so no part of a pack is cut)
         if (cut_on_) {
             const CONST_AS float* const cf = c.k->cand_floor;
-            cut_ = uni((int)(cf[mpm_class_of(mpl_, cm)] >= best && (lo == kNoMode || cf[mpm_class_of(mpl_, lo)] >= best) &&
-                             (hi == kNoMode || cf[mpm_class_of(mpl_, hi)] >= best))) != 0;
+            cut_ = uni((int)(cf[mpm_class_of(mpl_, cm)] >= best.cost && (lo == kNoMode || cf[mpm_class_of(mpl_, lo)] >= best.cost) &&
+                             (hi == kNoMode || cf[mpm_class_of(mpl_, hi)] >= best.cost))) != 0;
             if (cut_) PROF_ADD2(PH_CUT + 7, 0, 1);
         }
         if (!cut_) {
             const Pack4Out b = pack4_eval(c, q, 3, cm, lo, hi, overflow);
-            int win_ = -1;
-            LEAF4_CANDIDATE(b, 0, cm);
-            if (lo != kNoMode) LEAF4_CANDIDATE(b, 1, lo);
-            if (hi != kNoMode) LEAF4_CANDIDATE(b, 2, hi);
-            if (row == win_) rec_put(0, q.tx + x, q.ty + y, b.rec);
+            best.win = -1;
+            leaf_candidate(c, q.tx, q.ty, 2, TREE_DUAL_LUMA, mpl_, best, 0, cm, pack4_parts(b, 0));
+            if (lo != kNoMode) leaf_candidate(c, q.tx, q.ty, 2, TREE_DUAL_LUMA, mpl_, best, 1, lo, pack4_parts(b, 1));
+            if (hi != kNoMode) leaf_candidate(c, q.tx, q.ty, 2, TREE_DUAL_LUMA, mpl_, best, 2, hi, pack4_parts(b, 2));
+            if (row == best.win) rec_put(0, q.tx + x, q.ty + y, b.rec);
             WSYNC();
         }
         PROF_MARK(l4b1_);
@@ -894,30 +952,26 @@ __device__ __forceinline__ Res leaf4_search(const Ctx& c, const Req& q, int* ove
         PROF_MARK(sw1_);
         PROF_ADDM(3, sw0_, sw1_); // (profile build: mem_nop_m3 = what member 3 waits for the server)
         const uint8_t* sv = (const uint8_t*)team_lds(c, 0).decw + kSrv4Byte;
-        const float bestB = best;
-        const int modeB = best_mode;
+        const LeafBest bestB = best;
         Pack4Out a;
 #pragma unroll
         for (int k2 = 0; k2 < 2; ++k2) {
             a.ssd[k2] = (uint32_t)uni((int)((const uint32_t*)(sv + 32))[k2]);
             a.lvl[k2] = uni_i64(((const long long*)(sv + 40))[k2]);
         }
-        first_ = true;
-        int win_ = -1;
-        LEAF4_CANDIDATE(a, 0, PLANAR);
-        LEAF4_CANDIDATE(a, 1, DC);
-        if (bestB < best) {
+        best.first = true;
+        leaf_candidate(c, q.tx, q.ty, 2, TREE_DUAL_LUMA, mpl_, best, 0, PLANAR, pack4_parts(a, 0));
+        leaf_candidate(c, q.tx, q.ty, 2, TREE_DUAL_LUMA, mpl_, best, 1, DC, pack4_parts(a, 1));
+        if (bestB.cost < best.cost) {
             best = bestB;
-            best_mode = modeB;
         } else {
-            if (lane < 16) rec_put(0, q.tx + x, q.ty + y, sv[16 * win_ + lane]);
+            if (lane < 16) rec_put(0, q.tx + x, q.ty + y, sv[16 * best.win + lane]);
             WSYNC();
         }
         lv_word_add(&SHT.lvb.job4_ack);
     }
-#undef LEAF4_CANDIDATE
-    r.vmin = best;
-    r.imin = best_mode;
+    r.vmin = best.cost;
+    r.imin = best.mode;
     return r;
 }
 
@@ -948,76 +1002,38 @@ __device__ __forceinline__ Res leafc4_search(const Ctx& c, const Req& q, int* ov
     Res r = res_none();
     const int lane = lane_fresh();
     const int dm = q.mc;
-    // get_chroma_intra_pred_aux_cost of LT, T, L_CCLM in one sample pass, then the pick (SADs are integers < 2^20)
     CclmParams call_;
-    const unsigned acc = sad_list_cclm(c, q.tx, q.ty, 3, &call_);
-    const unsigned lt = (unsigned)__builtin_amdgcn_readlane((int)acc, 0), t = (unsigned)__builtin_amdgcn_readlane((int)acc, 1),
-                   l = (unsigned)__builtin_amdgcn_readlane((int)acc, 2);
-    if (c.trace && lane < 3)
-        TRACE_REC(c.ctu_x + q.tx, c.ctu_y + q.ty, 3, q.tree, 2, 0, lane == 0 ? LT_CCLM : (lane == 1 ? T_CCLM : L_CCLM),
-                  __float_as_int((float)acc));
-    const int cm = (lt <= t && lt <= l) ? LT_CCLM : (t <= l ? T_CCLM : L_CCLM);
+    const int cm = cclm_probe(c, q.tx, q.ty, 3, q.tree, &call_);
     if (q.refs1) build_refs(c, 1, q.tx, q.ty, 3);
     PROF_MARK(t0_);
     // model parameters of both planes of the picked mode: derived with the SAD list's
     const CclmPick cpk_ = cclm_pick(call_, 2 * cclm_mode_index(cm));
-    const int a0 = cpk_.a0, a1 = cpk_.a1, k0 = cpk_.k0, k1 = cpk_.k1, b0 = cpk_.b0, b1 = cpk_.b1;
-    const bool flat128 = cpk_.flat128, avail_l = cpk_.avail_l;
     const int row = lane >> 4, i = lane & 15, x = i & 3, y = i >> 2;
     const int pl = row & 1;
     int v = predict4_lane(c, row >= 2 ? dm : kNoMode, pl); // rows 2, 3: the DM candidate (every lane passes the WSYNC inside)
-    if (row < 2) {
-        v = 128;
-        if (!flat128) {
-            const int ds = cclm_ds6(c, q.tx, q.ty, 2 * y, 2 * x, avail_l);
-            v = (M24(ds, pl ? a1 : a0) >> (pl ? k1 : k0)) + (pl ? b1 : b0);
-            v = min(max(v, 0), 255);
-        }
-    }
+    if (row < 2) v = cclm_pred4_lane(c, q, cpk_, pl, x, y);
     const int org = ((const uint8_t*)SH.r2)[kOrgLeaf + 256 + 16 * pl + i];
-    if (!kRegDct4) {
-        SH.r1[lane] = (int16_t)(org - v);
-        WSYNC();
-    }
     PROF_MARK(t1_);
     PROF_ADD2(PH_PREDICT, t0_, t1_);
-    long long lvl[4];
-    int any_mask = 0;
-    int res;
-    if (kRegDct4) {
-        const int coef = fwd_dct4_reg(org - v);
-        res = residual4_reg(c, quantize_p16_reg(c, 4, coef, overflow, lvl, &any_mask), any_mask != 0);
-    } else {
-        fwd_dct_lg(c, 2, 4, 0);
-        quantize_p16(c, 4, overflow, lvl, &any_mask);
-        if (any_mask) {
-            dequantize_t(c, 2, 4, 0);
-            inv_dct_lg(c, 2, 4, 0);
-        }
-        res = (int)SH.r1[lane];
-    }
-    int rec = (int16_t)(v + res);
-    rec = min(max(rec, 0), 255);
-    const int d = rec - org;
-    const int rs = row_sum_i32(M24(d, d));
+    const Pass4Out p = pass4_reg(c, 4, true, v, org, overflow);
     EvalParts ec, ed;
     ec.ssd_y = ed.ssd_y = 0;
     ec.lvl_y = ed.lvl_y = 0;
-    ec.ssd_c = (uint32_t)(__builtin_amdgcn_readlane(rs, 0) + __builtin_amdgcn_readlane(rs, 16));
-    ed.ssd_c = (uint32_t)(__builtin_amdgcn_readlane(rs, 32) + __builtin_amdgcn_readlane(rs, 48));
-    ec.lvl_c = lvl[0] + lvl[1];
-    ed.lvl_c = lvl[2] + lvl[3];
+    ec.ssd_c = (uint32_t)(__builtin_amdgcn_readlane(p.row_ssd, 0) + __builtin_amdgcn_readlane(p.row_ssd, 16));
+    ed.ssd_c = (uint32_t)(__builtin_amdgcn_readlane(p.row_ssd, 32) + __builtin_amdgcn_readlane(p.row_ssd, 48));
+    ec.lvl_c = p.lvl[0] + p.lvl[1];
+    ed.lvl_c = p.lvl[2] + p.lvl[3];
     const float c0 = uni_f(assemble_chroma_cost(c, cm, ec));
     const float dm_cost = uni_f(assemble_chroma_cost(c, dm, ed));
     if (c.trace && lane == 0) {
         TRACE_REC(c.ctu_x + q.tx, c.ctu_y + q.ty, 3, q.tree, 3, 0, cm, __float_as_int(c0));
         TRACE_REC(c.ctu_x + q.tx, c.ctu_y + q.ty, 3, q.tree, 3, 0, dm, __float_as_int(dm_cost));
     }
-    const float cost = fminf(c0, fminf(dm_cost, 3.40282347e+38f));
-    const bool dm_wins = dm_cost == cost;
-    if ((row >= 2) == dm_wins) rec_put(1 + pl, (q.tx >> 1) + x, (q.ty >> 1) + y, rec);
+    // (the leaf's cost is the chroma cost itself: only the tie rule of chroma_final fits here)
+    const bool dm_wins = dm_keeps(dm_cost, c0);
+    if ((row >= 2) == dm_wins) rec_put(1 + pl, (q.tx >> 1) + x, (q.ty >> 1) + y, p.rec);
     WSYNC();
-    r.vmin = cost;
+    r.vmin = dm_wins ? dm_cost : c0;
     r.imin = dm_wins ? dm : cm;
     return r;
 }
@@ -1029,7 +1045,7 @@ __device__ __forceinline__ Res leafc4_search(const Ctx& c, const Req& q, int* ov
 // walk per candidate between two workgroup barriers.  The full candidates of a leaf read only neighbours outside the
 // block (:887-898, :974), so they are evaluated in PACKS: pack A = {planar, DC}, then the SAD search, then pack B =
 // {cm, cm - 1, cm + 1}; a pack's candidates go through every stage together -- luma blocks one pass each, the 4x4
-// chroma blocks of all candidates four to a pass (predict4_lane, transformed in registers: kRegDct4), the luma
+// chroma blocks of all candidates four to a pass (predict4_lane, transformed in registers), the luma
 // transforms over nb blocks, and ONE trellis pass
 // for the pack's six or nine chains walked side by side by this wave alone (quantize_pk: no workgroup barrier).
 // Predictions and reconstructions of the pack are parked in LDS (PRED_PARK); the running best candidate's
@@ -1042,6 +1058,16 @@ struct Pack8Out {
     uint32_t ssd_y[3], ssd_c[3];
     long long lvl_y[3], lvl_c[3];
 };
+// candidate k of an 8x8 or 16x16 pack (Pack8Out, Pack16Out) as parts
+template <class P>
+__device__ __forceinline__ EvalParts pack_parts(const P& p, int k) {
+    EvalParts e;
+    e.ssd_y = p.ssd_y[k];
+    e.ssd_c = p.ssd_c[k];
+    e.lvl_y = p.lvl_y[k];
+    e.lvl_c = p.lvl_c[k];
+    return e;
+}
 __device__ __forceinline__ Pack8Out pack8_eval(const Ctx& c, const Req& q, int nc, int m0, int m1, int m2, int* overflow) {
     Pack8Out o;
     const int lane = lane_fresh();
@@ -1074,7 +1100,7 @@ __device__ __forceinline__ Pack8Out pack8_eval(const Ctx& c, const Req& q, int n
         int rc = on ? (int)org[256 + 16 * pl + i16] - v : 0;
         // the block's coefficients straight from the registers, to where quantize_pk takes them (every lane runs the
         // transform; a row without a block carries zeros and stores nothing)
-        if (kRegDct4) rc = fwd_dct4_reg(rc);
+        rc = fwd_dct4_reg(rc);
         if (in) {
             SH.r1[nL + 16 * blk + i16] = (int16_t)rc;
             park[nL + 16 * blk + i16] = (uint8_t)v;
@@ -1084,7 +1110,6 @@ __device__ __forceinline__ Pack8Out pack8_eval(const Ctx& c, const Req& q, int n
     PROF_MARK(t1_);
     PROF_ADD2(PH_PREDICT, t0_, t1_);
     fwd_dct_lg(c, 3, nc, 0);
-    if (!kRegDct4) fwd_dct_lg(c, 2, 2 * nc, nL);
     PROF_MARK(t2_);
     PROF_ADD2(PH_FDCT, t1_, t2_);
     bool any_y = false, any_c = false;
@@ -1093,10 +1118,6 @@ __device__ __forceinline__ Pack8Out pack8_eval(const Ctx& c, const Req& q, int n
     if (any_y) { // (all levels zero: the residuals are zero too, and r1 already says so)
         dequantize_t(c, 3, nc, 0);
         inv_dct_lg(c, 3, nc, 0);
-    }
-    if (any_c && !kRegDct4) {
-        dequantize_t(c, 2, 2 * nc, nL);
-        inv_dct_lg(c, 2, 2 * nc, nL);
     }
     PROF_MARK(t4_);
     PROF_ADD2(PH_IDCT, t3_, t4_);
@@ -1119,9 +1140,8 @@ __device__ __forceinline__ Pack8Out pack8_eval(const Ctx& c, const Req& q, int n
         const int blk = 4 * ps + row;
         const bool in = blk < 2 * nc;
         int dd = 0;
-        // r1 holds the block's residual, or (kRegDct4) its levels: the lane dequantises and inverts its own in registers
-        int res = in ? (int)SH.r1[nL + 16 * blk + i16] : 0;
-        if (kRegDct4) res = residual4_reg(c, res, any_c);
+        // r1 holds the block's levels: the lane dequantises and inverts its own in registers
+        const int res = residual4_reg(c, in ? (int)SH.r1[nL + 16 * blk + i16] : 0, any_c);
         if (in) {
             int rec = (int16_t)((int)park[nL + 16 * blk + i16] + res);
             rec = min(max(rec, 0), 255);
@@ -1145,10 +1165,10 @@ __device__ __forceinline__ Pack8Out pack8_eval(const Ctx& c, const Req& q, int n
     return o;
 }
 
-// a pack candidate's reconstruction from the park into the tile (luma 8x8, Cb and Cr 4x4)
-__device__ __forceinline__ void pack8_to_tile(const Req& q, int nc, int cd) {
+// candidate cd's reconstruction from the park of a pack of nc (this wave's or the server's) into the tile (luma 8x8, Cb
+// and Cr 4x4)
+__device__ __forceinline__ void pack8_to_tile(const Req& q, const uint8_t* park, int nc, int cd) {
     const int lane = lane_fresh();
-    const uint8_t* park = (const uint8_t*)SH.decw + kParkByte;
     rec_put(0, q.tx + (lane & 7), q.ty + (lane >> 3), park[64 * cd + lane]);
     if (lane < 32) {
         const int pl = lane >> 4, i = lane & 15;
@@ -1162,33 +1182,8 @@ __device__ __forceinline__ Res leaf8_search(const Ctx& c, const Req& q, int* ove
     const int lane = lane_fresh();
     if (q.refs0) build_refs(c, 0, q.tx, q.ty, 3);
     if (q.refs1) build_refs(c, 1, q.tx, q.ty, 3);
-    float best = 3.40282347e+38f;
-    int best_mode = q.ml, best_cls = 0;
-    EvalParts eb;
-    eb.ssd_y = eb.ssd_c = 0;
-    eb.lvl_y = eb.lvl_c = 0;
-    bool first_ = true;
+    LeafBest best = leaf_best_init(q.ml);
     const MpmList mpl_ = mpm_list(c, q.tx, q.ty, 3);
-#define LEAF8_CANDIDATE(P, B, M)                                                                                       \
-    do {                                                                                                               \
-        EvalParts e_;                                                                                                  \
-        e_.ssd_y = (P).ssd_y[B];                                                                                       \
-        e_.ssd_c = (P).ssd_c[B];                                                                                       \
-        e_.lvl_y = (P).lvl_y[B];                                                                                       \
-        e_.lvl_c = (P).lvl_c[B];                                                                                       \
-        const int cls_ = mpm_class_of(mpl_, (M));                                                                      \
-        const float val_ = uni_f(assemble_cost(c, TREE_SINGLE, cls_, (M), e_));                                        \
-        if (c.trace && lane == 0)                                                                                      \
-            TRACE_REC(c.ctu_x + q.tx, c.ctu_y + q.ty, 3, TREE_SINGLE, 1, (M), (M), __float_as_int(val_));              \
-        if (first_ || val_ < best) {                                                                                   \
-            best = val_;                                                                                               \
-            best_mode = (M);                                                                                           \
-            best_cls = cls_;                                                                                           \
-            eb = e_;                                                                                                   \
-            win_ = (B);                                                                                                \
-        }                                                                                                              \
-        first_ = false;                                                                                                \
-    } while (0)
     // Level schedule (team kernel): member 0, idle once the CTU's 32x32 candidate is done, SERVES pack A of member 2's 8x8
     // leaves (serve_pack8).  Member 2 of a team in the level schedule, and the server is polling: post the job (the
     // block's reference samples and originals are ready and stay untouched until the leaf is decided), skip pack A
@@ -1206,10 +1201,9 @@ __device__ __forceinline__ Res leaf8_search(const Ctx& c, const Req& q, int* ove
         // pack A: planar and DC (:887-898)
         PROF_MARK(la0_);
         const Pack8Out a = pack8_eval(c, q, 2, PLANAR, DC, kNoMode, overflow);
-        int win_ = -1;
-        LEAF8_CANDIDATE(a, 0, PLANAR);
-        LEAF8_CANDIDATE(a, 1, DC);
-        pack8_to_tile(q, 2, win_);
+        leaf_candidate(c, q.tx, q.ty, 3, TREE_SINGLE, mpl_, best, 0, PLANAR, pack_parts(a, 0));
+        leaf_candidate(c, q.tx, q.ty, 3, TREE_SINGLE, mpl_, best, 1, DC, pack_parts(a, 1));
+        pack8_to_tile(q, (const uint8_t*)SH.decw + kParkByte, 2, best.win);
         PROF_MARK(la1_);
         PROF_ADD2(PH_LEAF + 0, la0_, la1_);
     }
@@ -1224,11 +1218,11 @@ __device__ __forceinline__ Res leaf8_search(const Ctx& c, const Req& q, int* ove
         // pack B: step_search(mode, 1, _, aux = false) on {cm, cm - 1, cm + 1} (:974)
         const int lo = !(cm < 3) ? cm - 1 : kNoMode, hi = !(cm + 1 > 66) ? cm + 1 : kNoMode;
         const Pack8Out b = pack8_eval(c, q, 3, cm, lo, hi, overflow);
-        int win_ = -1;
-        LEAF8_CANDIDATE(b, 0, cm);
-        if (lo != kNoMode) LEAF8_CANDIDATE(b, 1, lo);
-        if (hi != kNoMode) LEAF8_CANDIDATE(b, 2, hi);
-        if (win_ >= 0) pack8_to_tile(q, 3, win_);
+        best.win = -1;
+        leaf_candidate(c, q.tx, q.ty, 3, TREE_SINGLE, mpl_, best, 0, cm, pack_parts(b, 0));
+        if (lo != kNoMode) leaf_candidate(c, q.tx, q.ty, 3, TREE_SINGLE, mpl_, best, 1, lo, pack_parts(b, 1));
+        if (hi != kNoMode) leaf_candidate(c, q.tx, q.ty, 3, TREE_SINGLE, mpl_, best, 2, hi, pack_parts(b, 2));
+        if (best.win >= 0) pack8_to_tile(q, (const uint8_t*)SH.decw + kParkByte, 3, best.win);
         PROF_MARK(lb1_);
         PROF_ADD2(PH_LEAF + 2, ls1_, lb1_);
     }
@@ -1240,11 +1234,8 @@ __device__ __forceinline__ Res leaf8_search(const Ctx& c, const Req& q, int* ove
         PROF_MARK(sw1_);
         PROF_ADDM(3, sw0_, sw1_); // (mem_nop_m2)
         const Lds& srv = team_lds(c, 0);
-        const float bestB = best;
-        const int modeB = best_mode, clsB = best_cls;
-        const EvalParts ebB = eb;
-        first_ = true;
-        int win_ = -1;
+        const LeafBest bestB = best;
+        best.first = true;
         Pack8Out a;
 #pragma unroll
         for (int k2 = 0; k2 < 2; ++k2) {
@@ -1254,28 +1245,17 @@ __device__ __forceinline__ Res leaf8_search(const Ctx& c, const Req& q, int* ove
             a.lvl_y[k2] = uni_i64(x.lvl_y);
             a.lvl_c[k2] = uni_i64(x.lvl_c);
         }
-        LEAF8_CANDIDATE(a, 0, PLANAR);
-        LEAF8_CANDIDATE(a, 1, DC);
-        if (bestB < best) { // pack B's best stays (its reconstruction is in the tile already)
+        leaf_candidate(c, q.tx, q.ty, 3, TREE_SINGLE, mpl_, best, 0, PLANAR, pack_parts(a, 0));
+        leaf_candidate(c, q.tx, q.ty, 3, TREE_SINGLE, mpl_, best, 1, DC, pack_parts(a, 1));
+        if (bestB.cost < best.cost) // pack B's best stays (its reconstruction is in the tile already)
             best = bestB;
-            best_mode = modeB;
-            best_cls = clsB;
-            eb = ebB;
-        } else {            // a candidate of pack A: its reconstruction from the server's park
-            const uint8_t* park = (const uint8_t*)srv.decw + kParkByte;
-            rec_put(0, q.tx + (lane & 7), q.ty + (lane >> 3), park[64 * win_ + lane]);
-            if (lane < 32) {
-                const int pl2 = lane >> 4, i2 = lane & 15;
-                rec_put(1 + pl2, (q.tx >> 1) + (i2 & 3), (q.ty >> 1) + (i2 >> 2), park[128 + 32 * win_ + lane]);
-            }
-            WSYNC();
-        }
+        else                        // a candidate of pack A: its reconstruction from the server's park
+            pack8_to_tile(q, (const uint8_t*)srv.decw + kParkByte, 2, best.win);
         lv_word_add(&SHT.lvb.job_ack);
     }
-#undef LEAF8_CANDIDATE
-    r.vmin = best;
+    const int best_mode = best.mode;
+    const EvalParts eb = best.e;
     r.imin = best_mode;
-    r.imin2 = best_mode;
     r.ssd_y = eb.ssd_y;
     r.ssd_c = eb.ssd_c;
     r.lvl_y = eb.lvl_y;
@@ -1287,67 +1267,32 @@ __device__ __forceinline__ Res leaf8_search(const Ctx& c, const Req& q, int* ove
         TRACE_REC(c.ctu_x + q.tx, c.ctu_y + q.ty, 3, TREE_SINGLE, 3, 0, best_mode, __float_as_int(cur));
     PROF_MARK(lc0_);
     CclmParams call_;
-    const unsigned acc = sad_list_cclm(c, q.tx, q.ty, 3, &call_);
-    const unsigned lt = (unsigned)__builtin_amdgcn_readlane((int)acc, 0), t = (unsigned)__builtin_amdgcn_readlane((int)acc, 1),
-                   l = (unsigned)__builtin_amdgcn_readlane((int)acc, 2);
-    if (c.trace && lane < 3)
-        TRACE_REC(c.ctu_x + q.tx, c.ctu_y + q.ty, 3, TREE_SINGLE, 2, 0, lane == 0 ? LT_CCLM : (lane == 1 ? T_CCLM : L_CCLM),
-                  __float_as_int((float)acc));
-    const int cm = (lt <= t && lt <= l) ? LT_CCLM : (t <= l ? T_CCLM : L_CCLM);
+    const int cm = cclm_probe(c, q.tx, q.ty, 3, TREE_SINGLE, &call_);
     PROF_MARK(t0_);
     PROF_ADD2(PH_LEAF + 11, lc0_, t0_);
     const CclmPick cpk_ = cclm_pick(call_, 2 * cclm_mode_index(cm)); // (derived with the SAD list's)
-    const int a0 = cpk_.a0, a1 = cpk_.a1, k0 = cpk_.k0, k1 = cpk_.k1, b0 = cpk_.b0, b1 = cpk_.b1;
-    const bool flat128 = cpk_.flat128, avail_l = cpk_.avail_l;
     const int row = lane >> 4, i = lane & 15, x = i & 3, y = i >> 2;
     const int pl = row & 1;
-    const bool mine = row < 2; // rows 0 / 1 = Cb / Cr
+    const bool mine = row < 2; // rows 0 / 1 = Cb / Cr; rows 2, 3 ride along as zero blocks
     int v = 128;
-    if (mine && !flat128) {
-        const int ds = cclm_ds6(c, q.tx, q.ty, 2 * y, 2 * x, avail_l);
-        v = (M24(ds, pl ? a1 : a0) >> (pl ? k1 : k0)) + (pl ? b1 : b0);
-        v = min(max(v, 0), 255);
-    }
+    if (mine) v = cclm_pred4_lane(c, q, cpk_, pl, x, y);
     const int org = ((const uint8_t*)SH.r2)[kOrgLeaf + 256 + 16 * pl + i];
-    if (!kRegDct4) {
-        if (mine) SH.r1[lane] = (int16_t)(org - v);
-        WSYNC();
-    }
     PROF_MARK(t1_);
     PROF_ADD2(PH_PREDICT, t0_, t1_);
-    long long lvl[4];
-    int any_mask = 0;
-    int res;
-    if (kRegDct4) {
-        const int coef = fwd_dct4_reg(mine ? org - v : 0); // (rows 2, 3 ride along as zero blocks)
-        res = residual4_reg(c, quantize_p16_reg(c, 2, coef, overflow, lvl, &any_mask), any_mask != 0);
-    } else {
-        fwd_dct_lg(c, 2, 2, 0);
-        quantize_p16(c, 2, overflow, lvl, &any_mask);
-        if (any_mask) {
-            dequantize_t(c, 2, 2, 0);
-            inv_dct_lg(c, 2, 2, 0);
-        }
-        res = (int)SH.r1[mine ? lane : 0];
-    }
-    int rec = (int16_t)(v + res);
-    rec = min(max(rec, 0), 255);
-    const int d = rec - org;
-    const int rs = row_sum_i32(mine ? M24(d, d) : 0);
+    const Pass4Out p = pass4_reg(c, 2, mine, v, org, overflow);
     EvalParts e = eb;
-    e.ssd_c = (uint32_t)(__builtin_amdgcn_readlane(rs, 0) + __builtin_amdgcn_readlane(rs, 16));
-    e.lvl_c = lvl[0] + lvl[1];
+    e.ssd_c = (uint32_t)(__builtin_amdgcn_readlane(p.row_ssd, 0) + __builtin_amdgcn_readlane(p.row_ssd, 16));
+    e.lvl_c = p.lvl[0] + p.lvl[1];
     const float cclm_cost = uni_f(assemble_chroma_cost(c, cm, e));
     if (c.trace && lane == 0) TRACE_REC(c.ctu_x + q.tx, c.ctu_y + q.ty, 3, TREE_SINGLE, 3, 0, cm, __float_as_int(cclm_cost));
-    const bool dm_wins = cur == fminf(cclm_cost, fminf(cur, 3.40282347e+38f));
     // :1062-1072 final get_intra_pred_cost: the winner's luma with the DM chroma (still in the tile) or the CCLM chroma
-    if (!dm_wins && mine) rec_put(1 + pl, (q.tx >> 1) + x, (q.ty >> 1) + y, rec);
+    const ChromaFinal f = chroma_final(c, cur, cclm_cost, eb, e, best.cls, best_mode, cm);
+    if (!f.dm_wins && mine) rec_put(1 + pl, (q.tx >> 1) + x, (q.ty >> 1) + y, p.rec);
     WSYNC();
     PROF_MARK(lc9_);
     PROF_ADD2(PH_LEAF + 3, lc0_, lc9_);
-    r.vmin = dm_wins ? uni_f(assemble_cost(c, TREE_SINGLE, best_cls, best_mode, eb))
-                     : uni_f(assemble_cost(c, TREE_SINGLE, best_cls, cm, e));
-    r.imin2 = dm_wins ? best_mode : cm;
+    r.vmin = f.cost;
+    r.imin2 = f.mc;
     return r;
 }
 
@@ -1487,40 +1432,15 @@ __device__ __forceinline__ Res leaf16_search(const Ctx& c, const Req& q, int* ov
     const int lane = lane_fresh();
     if (q.refs0) build_refs(c, 0, q.tx, q.ty, 4);
     if (q.refs1) build_refs(c, 1, q.tx, q.ty, 4);
-    float best = 3.40282347e+38f;
-    int best_mode = PLANAR;
-    EvalParts eb;
-    eb.ssd_y = eb.ssd_c = 0;
-    eb.lvl_y = eb.lvl_c = 0;
-    bool first_ = true;
+    LeafBest best = leaf_best_init(PLANAR);
     const MpmList mpl_ = mpm_list(c, q.tx, q.ty, 4);
-#define LEAF16_CANDIDATE(P, B, M)                                                                                      \
-    do {                                                                                                               \
-        EvalParts e_;                                                                                                  \
-        e_.ssd_y = (P).ssd_y[B];                                                                                       \
-        e_.ssd_c = (P).ssd_c[B];                                                                                       \
-        e_.lvl_y = (P).lvl_y[B];                                                                                       \
-        e_.lvl_c = (P).lvl_c[B];                                                                                       \
-        const int cls_ = mpm_class_of(mpl_, (M));                                                                      \
-        const float val_ = uni_f(assemble_cost(c, TREE_SINGLE, cls_, (M), e_));                                        \
-        if (c.trace && lane == 0)                                                                                      \
-            TRACE_REC(c.ctu_x + q.tx, c.ctu_y + q.ty, 4, TREE_SINGLE, 1, (M), (M), __float_as_int(val_));              \
-        if (first_ || val_ < best) {                                                                                   \
-            best = val_;                                                                                               \
-            best_mode = (M);                                                                                           \
-            eb = e_;                                                                                                   \
-            win_ = (B);                                                                                                \
-        }                                                                                                              \
-        first_ = false;                                                                                                \
-    } while (0)
     {
         // planar and DC (:887-898)
         PROF_MARK(la0_);
         const Pack16Out a = pack16_eval(c, q, 2, PLANAR, DC, overflow);
-        int win_ = -1;
-        LEAF16_CANDIDATE(a, 0, PLANAR);
-        LEAF16_CANDIDATE(a, 1, DC);
-        pack16_to_tile(c, q, 2, win_);
+        leaf_candidate(c, q.tx, q.ty, 4, TREE_SINGLE, mpl_, best, 0, PLANAR, pack_parts(a, 0));
+        leaf_candidate(c, q.tx, q.ty, 4, TREE_SINGLE, mpl_, best, 1, DC, pack_parts(a, 1));
+        pack16_to_tile(c, q, 2, best.win);
         PROF_MARK(la1_);
         PROF_ADD2(PH_LEAF + 4, la0_, la1_);
     }
@@ -1535,29 +1455,28 @@ __device__ __forceinline__ Res leaf16_search(const Ctx& c, const Req& q, int* ov
     const int lo = !(cm < 3) ? cm - 1 : kNoMode, hi = !(cm + 1 > 66) ? cm + 1 : kNoMode;
     {
         const Pack16Out b = pack16_eval(c, q, 2, cm, lo, overflow);
-        int win_ = -1;
-        LEAF16_CANDIDATE(b, 0, cm);
-        if (lo != kNoMode) LEAF16_CANDIDATE(b, 1, lo);
-        if (win_ >= 0) pack16_to_tile(c, q, 2, win_);
+        best.win = -1;
+        leaf_candidate(c, q.tx, q.ty, 4, TREE_SINGLE, mpl_, best, 0, cm, pack_parts(b, 0));
+        if (lo != kNoMode) leaf_candidate(c, q.tx, q.ty, 4, TREE_SINGLE, mpl_, best, 1, lo, pack_parts(b, 1));
+        if (best.win >= 0) pack16_to_tile(c, q, 2, best.win);
     }
     PROF_MARK(lb1_);
     PROF_ADD2(PH_LEAF + 6, ls1_, lb1_);
     if (hi != kNoMode) {
         const Pack16Out b = pack16_eval(c, q, 1, hi, kNoMode, overflow);
-        int win_ = -1;
-        LEAF16_CANDIDATE(b, 0, hi);
-        if (win_ >= 0) pack16_to_tile(c, q, 1, win_);
+        best.win = -1;
+        leaf_candidate(c, q.tx, q.ty, 4, TREE_SINGLE, mpl_, best, 0, hi, pack_parts(b, 0));
+        if (best.win >= 0) pack16_to_tile(c, q, 1, best.win);
     }
     PROF_MARK(lc1_);
     PROF_ADD2(PH_LEAF + 7, lb1_, lc1_);
-#undef LEAF16_CANDIDATE
-    r.vmin = best;
-    r.imin = best_mode;
-    r.imin2 = best_mode;
-    r.ssd_y = eb.ssd_y;
-    r.ssd_c = eb.ssd_c;
-    r.lvl_y = eb.lvl_y;
-    r.lvl_c = eb.lvl_c;
+    r.vmin = best.cost;
+    r.imin = best.mode;
+    r.imin2 = best.mode;
+    r.ssd_y = best.e.ssd_y;
+    r.ssd_c = best.e.ssd_c;
+    r.lvl_y = best.e.lvl_y;
+    r.lvl_c = best.e.lvl_c;
     return r;
 }
 
@@ -1837,22 +1756,25 @@ __device__ __forceinline__ void put_parts(EvalPartsSF& d, const EvalParts& e) {
     d.lvl_c = e.lvl_c;
 }
 
-// result of a full candidate with luma mode M: running first minimum over the candidates in the
-// reference's order; a new best is saved by the next request, any other active candidate has
-// overwritten the tile
-#define LEAF_CANDIDATE(M)                 \
-    do {                                  \
-        if (val < s.best_cost) {          \
-            s.best_cost = val;            \
-            put_parts(s.e_best, rp);      \
-            s.mode = (uint8_t)(M);        \
-            s.best_cls = (uint8_t)cls;    \
-            s.need_save = 1;              \
-            s.tile_best = 1;              \
-        } else if (s.op_act) {            \
-            s.tile_best = 0;              \
-        }                                 \
-    } while (0)
+// the step machines' running best takes a candidate: cost, parts, luma mode and its MPM class.  Where the winner's
+// reconstruction then is stays with the caller: the wave schedule sets need_save / tile_best, the team schedule holder.
+__device__ __forceinline__ void leaf_take(LeafSF& s, float val, const EvalParts& parts, int mode, int cls) {
+    s.best_cost = val;
+    put_parts(s.e_best, parts);
+    s.mode = (uint8_t)mode;
+    s.best_cls = (uint8_t)cls;
+}
+// wave schedule, result of a full candidate: running first minimum over the candidates in the reference's order; a new
+// best is saved by the next request, any other active candidate has overwritten the tile
+__device__ __forceinline__ void leaf_offer(LeafSF& s, float val, const EvalParts& parts, int mode, int cls) {
+    if (val < s.best_cost) {
+        leaf_take(s, val, parts, mode, cls);
+        s.need_save = 1;
+        s.tile_best = 1;
+    } else if (s.op_act) {
+        s.tile_best = 0;
+    }
+}
 
 // One step of the search of a SINGLE_TREE leaf (block_splitter.rs:886-1078).  An 8x8 leaf is one request (C_L8), a 16x16
 // leaf one request and its CCLM part (C_L16, C_WINNER ..); the candidate-by-candidate states C_PLANAR .. C_F2 serve the
@@ -1892,10 +1814,7 @@ __device__ __forceinline__ bool leaf_step(const Ctx& c, LeafSF& s, const Res& r,
             leaf_full(s, q, 3, PLANAR, PLANAR, true, C_PLANAR);
             return true;
         case C_L16: // the winner of [planar, DC, cm, cm - 1, cm + 1] is in the tile; it is saved by the next request
-            s.best_cost = r.vmin;
-            put_parts(s.e_best, rp);
-            s.mode = (uint8_t)r.imin;
-            s.best_cls = (uint8_t)mpm_class(c, s.bx, s.by, s.lg, r.imin);
+            leaf_take(s, r.vmin, rp, r.imin, mpm_class(c, s.bx, s.by, s.lg, r.imin));
             s.need_save = 1;
             s.tile_best = 1;
             cont = C_WINNER;
@@ -1906,16 +1825,13 @@ __device__ __forceinline__ bool leaf_step(const Ctx& c, LeafSF& s, const Res& r,
             s.chroma_mode = (uint8_t)r.imin2;
             return false;
         case C_PLANAR:
-            s.best_cost = val;
-            put_parts(s.e_best, rp);
-            s.mode = PLANAR;
-            s.best_cls = (uint8_t)cls;
+            leaf_take(s, val, rp, PLANAR, cls);
             s.need_save = 1;
             s.tile_best = 1;
             leaf_full(s, q, 3, DC, DC, true, C_DCM);
             return true;
         case C_DCM:
-            LEAF_CANDIDATE(DC);
+            leaf_offer(s, val, rp, DC, cls);
             // the 13 directional candidates, their first minimum (:899-904) and step_search(mode, 2, cost, aux = true)
             // (:905-973) in ONE request: the evaluator runs the three lists back to back
             leaf_sadsearch(s, q, C_LIST);
@@ -1932,18 +1848,18 @@ __device__ __forceinline__ bool leaf_step(const Ctx& c, LeafSF& s, const Res& r,
         }
         case C_F0: {
             const int cm = s.cur_mode;
-            LEAF_CANDIDATE(cm);
+            leaf_offer(s, val, rp, cm, cls);
             leaf_full(s, q, 3, cm - 1, cm - 1, !(cm < 3), C_F1);
             return true;
         }
         case C_F1: {
             const int cm = s.cur_mode;
-            LEAF_CANDIDATE(cm - 1);
+            leaf_offer(s, val, rp, cm - 1, cls);
             leaf_full(s, q, 3, cm + 1, cm + 1, !(cm + 1 > 66), C_F2);
             return true;
         }
         case C_F2:
-            LEAF_CANDIDATE(s.cur_mode + 1);
+            leaf_offer(s, val, rp, s.cur_mode + 1, cls);
             cont = C_WINNER;
             break;
         case C_WINNER: {
@@ -1972,13 +1888,12 @@ __device__ __forceinline__ bool leaf_step(const Ctx& c, LeafSF& s, const Res& r,
             const float cclm_cost = uni_f(assemble_chroma_cost(c, s.cclm_mode, e));
             if (c.trace && LANE == 0)
                 TRACE_REC(c.ctu_x + s.bx, c.ctu_y + s.by, s.lg, tree, 3, 0, s.cclm_mode, __float_as_int(cclm_cost));
-            const float cur = s.cur_cost;
-            const bool dm_wins = cur == fminf(cclm_cost, fminf(cur, 3.40282347e+38f));
-            // :1062-1072 final get_intra_pred_cost: luma = the winner; the chroma pair is the DM
-            // evaluation (its reconstruction comes back from slot 0) or the CCLM evaluation just made
+            // :1062-1072 final get_intra_pred_cost: luma = the winner (its mpm_class from its candidate evaluation); the
+            // chroma pair is the DM evaluation (its reconstruction comes back from slot 0) or the CCLM evaluation just made.
+            // (chroma_final's decision spelt out: called here, in any of five shapes, it cost the wave kernels 2 VGPRs)
             const int m = s.mode;
             const int bcls = s.best_cls; // mpm_class of the winner, from its candidate evaluation
-            if (dm_wins) {
+            if (dm_keeps(s.cur_cost, cclm_cost)) {
                 s.cost = uni_f(assemble_cost(c, tree, bcls, m, s.e_best.get()));
                 leaf_copy_only(s, q, COPY_RESTORE, 2, C_DM);
                 return true;
@@ -2091,16 +2006,10 @@ __device__ __forceinline__ bool leaf_step_team(const Ctx& c, CtuSt& t, LeafSF& s
                 TRACE_REC(c.ctu_x + s.bx, c.ctu_y + s.by, s.lg, tree, 1, DC, DC, __float_as_int(v1));
             }
             if (v1 < v0) { // first minimum of [planar, DC, ...] as a running strict-less update
-                s.best_cost = v1;
-                put_parts(s.e_best, e1);
-                s.mode = DC;
-                s.best_cls = (uint8_t)cls1;
+                leaf_take(s, v1, e1, DC, cls1);
                 s.holder = 1;
             } else {
-                s.best_cost = v0;
-                put_parts(s.e_best, e0);
-                s.mode = PLANAR;
-                s.best_cls = 0;
+                leaf_take(s, v0, e0, PLANAR, 0);
                 s.holder = 0;
             }
             // member 2 searched the directional modes (K_SADSEARCH): its winner and its SAD
@@ -2135,10 +2044,7 @@ __device__ __forceinline__ bool leaf_step_team(const Ctx& c, CtuSt& t, LeafSF& s
                 if (c.write && LANE == 0)
                     TRACE_REC(c.ctu_x + s.bx, c.ctu_y + s.by, s.lg, tree, 1, mode, mode, __float_as_int(val));
                 if (val < s.best_cost) {
-                    s.best_cost = val;
-                    put_parts(s.e_best, e);
-                    s.mode = (uint8_t)mode;
-                    s.best_cls = (uint8_t)cls;
+                    leaf_take(s, val, e, mode, cls);
                     s.holder = (uint8_t)mem;
                 }
             }
@@ -2200,17 +2106,11 @@ __device__ __forceinline__ bool leaf_step_team(const Ctx& c, CtuSt& t, LeafSF& s
             const float cclm_cost = uni_f(assemble_chroma_cost(c, s.cclm_mode, e));
             if (c.write && LANE == 0)
                 TRACE_REC(c.ctu_x + s.bx, c.ctu_y + s.by, s.lg, tree, 3, 0, s.cclm_mode, __float_as_int(cclm_cost));
-            const float cur = s.cur_cost;
-            const bool dm_wins = cur == fminf(cclm_cost, fminf(cur, 3.40282347e+38f));
-            const int m = s.mode, bcls = s.best_cls;
-            if (dm_wins) { // only the evaluator's tile holds the CCLM chroma: it takes the DM chroma back
-                s.cost = uni_f(assemble_cost(c, tree, bcls, m, s.e_best.get()));
-                team_defer_pull(t, s, 2, holder);
-                return false;
-            }
-            s.chroma_mode = s.cclm_mode;
-            s.cost = uni_f(assemble_cost(c, tree, bcls, s.cclm_mode, e));
-            team_defer_pull(t, s, 2, ev);
+            const ChromaFinal f = chroma_final(c, s.cur_cost, cclm_cost, s.e_best.get(), e, s.best_cls, s.mode, s.cclm_mode);
+            s.cost = f.cost;
+            if (!f.dm_wins) s.chroma_mode = s.cclm_mode;
+            // DM wins: only the evaluator's tile holds the CCLM chroma, it takes the DM chroma back
+            team_defer_pull(t, s, 2, f.dm_wins ? holder : ev);
             return false;
         }
         default:

@@ -24,10 +24,10 @@
 // The WRENC_EXP_* switches are measurement builds (tools/README.md); several of them give wrong results on purpose.
 // tools/build_exp.sh builds them with WRENC_EXPERIMENT_BUILD, which nothing else defines.
 #if !defined(WRENC_EXPERIMENT_BUILD) &&                                                                             \
-    (defined(WRENC_EXP_CTRL_ONLY) || defined(WRENC_EXP_LDS_DCT4) || defined(WRENC_EXP_LDS_PAD) ||                   \
-     defined(WRENC_EXP_NOINLINE_SAD) || defined(WRENC_EXP_NO_ORG) || defined(WRENC_EXP_OLD_PDPC) ||                 \
-     defined(WRENC_EXP_P16_LDS_SCAN) || defined(WRENC_EXP_SKIP_DCT) || defined(WRENC_EXP_SKIP_PRED) ||              \
-     defined(WRENC_EXP_SKIP_QUANT) || defined(WRENC_EXP_SKIP_REFS) || defined(WRENC_EXP_SKIP_SAD))
+    (defined(WRENC_EXP_CTRL_ONLY) || defined(WRENC_EXP_LDS_PAD) || defined(WRENC_EXP_NOINLINE_SAD) ||               \
+     defined(WRENC_EXP_NO_ORG) || defined(WRENC_EXP_OLD_PDPC) || defined(WRENC_EXP_SKIP_DCT) ||                     \
+     defined(WRENC_EXP_SKIP_PRED) || defined(WRENC_EXP_SKIP_QUANT) || defined(WRENC_EXP_SKIP_REFS) ||               \
+     defined(WRENC_EXP_SKIP_SAD))
 #error "a WRENC_EXP_* switch is set outside an experiment build: use tools/build_exp.sh"
 #endif
 

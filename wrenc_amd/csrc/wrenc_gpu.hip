@@ -391,7 +391,7 @@ __global__ __launch_bounds__(64) void test_avail_tab_kernel(const DevConst* __re
     if (nb_avail(c, gx, gy, tn, gx, gy - 1, false, false) != (((m >> 3) & 1) != 0)) atomicAdd(out, 1);
 }
 
-// quantize_p16 (the packed 4x4 leaf search's quantiser): each wave takes up to four consecutive 4x4 blocks
+// quantize_p16_reg (the packed 4x4 leaf search's quantiser): each wave takes up to four consecutive 4x4 blocks
 __global__ __launch_bounds__(64) void test_quantize_p16_kernel(const DevConst* __restrict__ k, const int16_t* in, int count,
                                                                int16_t* out, long long* cost, int* overflow) {
     Ctx c = {};
@@ -402,15 +402,9 @@ __global__ __launch_bounds__(64) void test_quantize_p16_kernel(const DevConst* _
     const bool mine = threadIdx.x < 16 * nb;
     int ovf = 0, any = 0;
     long long lvl[4];
-    if (kRegDct4) { // the form the search runs: the lane's coefficient in, the lane's level out
-        const int level = quantize_p16_reg(c, nb, mine ? (int)in[(size_t)first * 16 + threadIdx.x] : 0, &ovf, lvl, &any);
-        if (mine) out[(size_t)first * 16 + threadIdx.x] = (int16_t)level;
-    } else {
-        if (mine) SH.r1[threadIdx.x] = in[(size_t)first * 16 + threadIdx.x];
-        WSYNC();
-        quantize_p16(c, nb, &ovf, lvl, &any);
-        if (mine) out[(size_t)first * 16 + threadIdx.x] = SH.r1[threadIdx.x];
-    }
+    // the lane's coefficient in, the lane's level out
+    const int level = quantize_p16_reg(c, nb, mine ? (int)in[(size_t)first * 16 + threadIdx.x] : 0, &ovf, lvl, &any);
+    if (mine) out[(size_t)first * 16 + threadIdx.x] = (int16_t)level;
     if (threadIdx.x == 0) {
         for (int b = 0; b < nb; ++b) cost[first + b] = lvl[b];
         if (ovf) atomicOr(overflow, 1);
