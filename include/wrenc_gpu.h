@@ -152,6 +152,28 @@ int wrenc_gpu_upload(wrenc_gpu_ctx* ctx, int slot, const uint8_t* y, const uint8
  * no visible size is set launches nothing it did not launch before. */
 int wrenc_gpu_set_visible_size(wrenc_gpu_ctx* ctx, int vis_w, int vis_h);
 int wrenc_gpu_visible_size(const wrenc_gpu_ctx* ctx, int* w, int* h); /* the coded size when none is set */
+/* Scaling on the device.  A source size says that the caller's pictures are src_w x src_h and are resampled to the
+ * context's visible size (the coded size unless one is set): wrenc_gpu_upload then takes planes of src_w x src_h and
+ * src_w/2 x src_h/2 (the stride checks use those widths; wrenc_gpu_encode_picture follows), copies them into staging planes
+ * on the device -- one set per context; copies, scaler, pad and retile of every upload run in order on one stream -- and a
+ * kernel behind the copies writes the visible rectangle of the slot's planes; the margin of a padded context is filled
+ * from the scaled picture as before.  The filter is defined in wrenc_scale.h, in integers: separable Catmull-Rom,
+ * stretched by the ratio when shrinking, centre-aligned samples, edge samples repeated; the device meets it bit for bit.
+ * Everything behind the upload sees the scaled picture as the slot's originals: search, final pass, token and compact
+ * pass, wrenc_gpu_download_complexity, and wrenc_gpu_download_metrics -- which therefore measures the codec against the
+ * SCALED originals, not the scaling itself.
+ * src_w and src_h: even, at least 16, and per dimension within a factor of 4 of the visible size, in either direction;
+ * else WRENC_GPU_EINVAL.  WRENC_GPU_ESTATE once any slot of the context has been uploaded into.  Passing the visible size
+ * itself puts the context back to the plain behaviour; a context on which no source size is set launches and allocates
+ * nothing it did not before.  While a source size is set wrenc_gpu_set_visible_size returns WRENC_GPU_ESTATE: set the
+ * visible size first, then the source size. */
+int wrenc_gpu_set_source_size(wrenc_gpu_ctx* ctx, int src_w, int src_h);
+int wrenc_gpu_source_size(const wrenc_gpu_ctx* ctx, int* w, int* h); /* the visible size when none is set */
+/* Host only: the taps of output sample o of one axis n_in -> n_out (wrenc_scale_taps of wrenc_scale.h): *first the input
+ * index of coef[0] -- it may lie outside [0, n_in - 1], where the edge sample is read -- and *n_taps their number (at most
+ * 16); the coefficients sum to 4096.  WRENC_GPU_EINVAL outside the limits (n_out <= 4 n_in, n_in <= 4 n_out, both 1 ..
+ * 16384, 0 <= o < n_out) or for a null pointer. */
+int wrenc_gpu_scale_taps(int n_in, int n_out, int o, int* first, int* n_taps, int16_t coef[17]);
 /* Test entry: the coded-size original planes a slot holds (width*height, then (width/2)*(height/2) twice), margin
  * included.  Blocking, behind the copy stream.  WRENC_GPU_ESTATE for a slot never uploaded into. */
 int wrenc_gpu_test_download_originals(wrenc_gpu_ctx* ctx, int slot, uint8_t* y, uint8_t* cb, uint8_t* cr);

@@ -25,4 +25,8 @@ g++ -O1 -g -std=c++17 -ffp-contract=off -fsanitize=address,undefined -fno-omit-f
 g++ -O1 -g -std=c++17 -ffp-contract=off -mavx2 -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined \
     -o "$T/oracle_search" "$R/tools/sanitize/oracle_search.cpp" "$R/oracle/wrenc_oracle.cpp" "$R/oracle/vvc_parse.cpp"
 "$T/oracle_search"
+# the scaling filter's tap derivation (include/wrenc_scale.h), 64-bit intermediates at the largest sizes included
+g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined \
+    -o "$T/scale_taps" "$R/tools/sanitize/scale_taps.cpp"
+"$T/scale_taps"
 rm -rf "$T"

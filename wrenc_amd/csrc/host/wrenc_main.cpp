@@ -19,7 +19,7 @@
 // parameter sets' QP; the bytes depend on the input and the options alone, not on --threads or timing, which is why
 // --ramp-down auto, decided by the clock, runs as never), --metrics PATH (PSNR and SSIM of every picture from sums the
 // device takes of the originals and the reconstruction it holds, wrenc_gpu_download_metrics: a JSON report in the shape of
-// the reference's evaluation harness, and one summary line on stderr), --pad (below), --verbose, --ramp-down auto|always|never, --tokens auto|on|off
+// the reference's evaluation harness, and one summary line on stderr), --pad and --scale (below), --verbose, --ramp-down auto|always|never, --tokens auto|on|off
 // (how a batch comes back.  auto and on: as the residual tokens the device makes of it, wrenc_gpu_download_tokens -- the
 // host then runs the CU-level syntax and the arithmetic coder only, 1.8x less host time per picture, 20x the bytes over
 // PCIe -- and as the compact level record, with residual_coding on the host, when they do not fit the token pool.  off,
@@ -31,6 +31,13 @@
 // the last column and row into the margin), and the SPS carries the conformance window.  --reconst receives frames
 // cropped to --output-size and --metrics reports that rectangle.  --bitrate charges the parameter sets of the coded
 // size, so its QPs are those of the padded pictures coded plainly.
+//
+// --scale: the input holds frames of --input-size (even, at least 16x16, within a factor of 4 of --output-size in each
+// dimension) and the device resamples every picture to --output-size behind its upload (wrenc_gpu_set_source_size; the
+// filter is include/wrenc_scale.h's).  Everything else is the run on the scaled pictures: --reconst receives frames of
+// --output-size, --metrics reports that size and compares the reconstruction with the SCALED originals, --pad pads the
+// scaled picture, --bitrate measures it.  Without --scale, --input-size is parsed and not used, as in the reference
+// (main.rs:164-174).  --scale with equal sizes changes nothing.
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -147,6 +154,8 @@ struct Options {
     int w = 0, h = 0, qp = 26; // the coded size; ctu.rs:382 when --qp is absent
     int vis_w = 0, vis_h = 0;  // --output-size: the size of the input's and of --reconst's frames; w x h unless --pad
     bool pad = false;
+    bool scale = false;
+    int in_w = 0, in_h = 0;    // the size of the input's frames: --input-size with --scale, else vis_w x vis_h
     int depth = 3, batch = 64, n_threads = 8;
     bool verbose = false;
     bool tokens = true; // --tokens auto | on: batches come back as residual tokens; --tokens off, --no-tokens: as the compact record
@@ -211,6 +220,7 @@ Options parse_options(int argc, char** argv) {
         else if (a == "--metrics") o.metrics = val();
         else if (a == "--verbose") o.verbose = true;
         else if (a == "--pad") o.pad = true;
+        else if (a == "--scale") o.scale = true;
         else if (a == "--no-tokens") o.tokens = false;
         else if (a == "--ramp-down") { // how a run ends: auto (smaller last batches when the host's tail is heavy), always, never
             const std::string v = val();
@@ -227,7 +237,7 @@ Options parse_options(int argc, char** argv) {
     if (!o.input || !o.output || !in_size || !out_size || o.num_pictures < 0)
         die("the following options are required: --input --output --input-size --output-size --num-pictures");
     int iw = 0, ih = 0;
-    if (!parse_size(in_size, iw, ih)) die("Invalid input-size: %s", in_size); // parsed, otherwise unused (main.rs:164-174)
+    if (!parse_size(in_size, iw, ih)) die("Invalid input-size: %s", in_size); // used with --scale only (below); otherwise parsed and unused, as in main.rs:164-174
     if (!parse_size(out_size, o.w, o.h)) die("Invalid output-size: %s", out_size);
     if (o.extra) {
         const std::string e = o.extra;
@@ -248,6 +258,15 @@ Options parse_options(int argc, char** argv) {
         o.h = (o.h + 31) / 32 * 32;
     }
     if (o.w % 32 || o.h % 32) die("output-size must be a multiple of the 32x32 CTU (picture.rs:178-181): %dx%d", o.w, o.h);
+    o.in_w = o.vis_w;
+    o.in_h = o.vis_h;
+    if (o.scale) { // the input's frames are --input-size; the device resamples them to --output-size
+        if (iw % 2 || ih % 2 || iw < 16 || ih < 16) die("with --scale, input-size must be even and at least 16x16: %dx%d", iw, ih);
+        if (iw > 4 * o.vis_w || o.vis_w > 4 * iw || ih > 4 * o.vis_h || o.vis_h > 4 * ih)
+            die("with --scale, input-size and output-size must be within a factor of 4 of each other: %dx%d to %dx%d", iw, ih, o.vis_w, o.vis_h);
+        o.in_w = iw;
+        o.in_h = ih;
+    }
     if (o.qp < 0 || o.qp > 63 || o.depth < 0 || o.depth > 3) die("qp must be 0..63, max-split-depth 0..3");
     o.min_qp = o.qp;
     const auto positive = [](const char* text, double& v) { // a finite number > 0 and nothing after it
@@ -286,14 +305,15 @@ Options parse_options(int argc, char** argv) {
 // sizes of one picture (8-bit 4:2:0) and of what is read back of it
 struct Geometry {
     int w, h;               // the coded size
-    int vw, vh;             // the size of the frames in the input and in --reconst (--pad: smaller than the coded size)
+    int vw, vh;             // the size of the frames in --reconst (--pad: smaller than the coded size)
+    int iw, ih;             // the size of the frames in the input (--scale: --input-size; else vw x vh)
     size_t ysz, csz, pic;   // bytes of luma, of one chroma plane, of the picture
-    size_t vysz, vcsz, vpic; // the same of a frame of the input
+    size_t iysz, icsz, ipic; // the same of a frame of the input
     size_t n4, maps;        // 4x4 luma blocks; bytes of cu_log2_size | luma_mode | chroma_mode
     size_t mask_words, level_blocks, n_ctus;
-    Geometry(int w_, int h_, int vw_, int vh_)
-        : w(w_), h(h_), vw(vw_), vh(vh_), ysz((size_t)w_ * h_), csz(ysz / 4), pic(ysz + 2 * csz), vysz((size_t)vw_ * vh_),
-          vcsz((size_t)(vw_ / 2) * (vh_ / 2)), vpic(vysz + 2 * vcsz), n4(ysz / 16), maps(2 * n4 + ysz / 64),
+    Geometry(int w_, int h_, int vw_, int vh_, int iw_, int ih_)
+        : w(w_), h(h_), vw(vw_), vh(vh_), iw(iw_), ih(ih_), ysz((size_t)w_ * h_), csz(ysz / 4), pic(ysz + 2 * csz), iysz((size_t)iw_ * ih_),
+          icsz((size_t)(iw_ / 2) * (ih_ / 2)), ipic(iysz + 2 * icsz), n4(ysz / 16), maps(2 * n4 + ysz / 64),
           mask_words(wrenc_gpu_compact_mask_words(w_, h_)), level_blocks(pic / 16), n_ctus((size_t)(w_ / 32) * (h_ / 32)) {}
 };
 
@@ -357,7 +377,7 @@ std::vector<HostSet> make_units(const Options& o, const Geometry& g, const std::
         HostSet& s = units[u];
         s.ctx = ctxs[u % n_dev];
         s.base = (int)(u / n_dev) * o.batch;
-        s.in = (uint8_t*)wrenc_gpu_alloc_host(s.ctx, g.vpic * batch);
+        s.in = (uint8_t*)wrenc_gpu_alloc_host(s.ctx, g.ipic * batch);
         s.maps = (uint8_t*)wrenc_gpu_alloc_host(s.ctx, g.maps * batch);
         if (with_rec) s.rec = (uint8_t*)wrenc_gpu_alloc_host(s.ctx, g.pic * batch);
         if (!s.in || !s.maps || (with_rec && !s.rec)) fatal("%s", wrenc_gpu_last_error(s.ctx));
@@ -457,8 +477,8 @@ struct Run {
     void upload(HostSet& s, int k) {
         // the slot's QP first: the encode call of the batch reads it (NULL: the context's, --qp)
         if (!o.pic_qp.empty()) gpu_check(s, wrenc_gpu_set_slot_qp(s.ctx, s.base + k, qcfg[(size_t)slice_qp(poc + k)]));
-        uint8_t* p = s.in + g.vpic * k;
-        gpu_check(s, wrenc_gpu_upload(s.ctx, s.base + k, p, p + g.vysz, p + g.vysz + g.vcsz, (size_t)g.vw, (size_t)g.vw / 2));
+        uint8_t* p = s.in + g.ipic * k;
+        gpu_check(s, wrenc_gpu_upload(s.ctx, s.base + k, p, p + g.iysz, p + g.iysz + g.icsz, (size_t)g.iw, (size_t)g.iw / 2));
         ++s.count;
     }
 
@@ -482,15 +502,15 @@ struct Run {
             for (int t = 0; t < n_readers; ++t)
                 readers.emplace_back([&, t] {
                     for (int k = t; k < want; k += n_readers) {
-                        uint8_t* p = s.in + g.vpic * k;
+                        uint8_t* p = s.in + g.ipic * k;
                         size_t got = 0;
-                        const off_t at = (off_t)((size_t)(poc + k) * g.vpic);
-                        while (got < g.vpic) {
-                            const ssize_t r = pread(fileno(fin), p + got, g.vpic - got, at + (off_t)got);
+                        const off_t at = (off_t)((size_t)(poc + k) * g.ipic);
+                        while (got < g.ipic) {
+                            const ssize_t r = pread(fileno(fin), p + got, g.ipic - got, at + (off_t)got);
                             if (r <= 0) break;
                             got += (size_t)r;
                         }
-                        ready[(size_t)k].store(got == g.vpic ? 1 : -1, std::memory_order_release);
+                        ready[(size_t)k].store(got == g.ipic ? 1 : -1, std::memory_order_release);
                     }
                 });
             int short_at = -1;
@@ -507,7 +527,7 @@ struct Run {
             if (short_at >= 0) die("input ended after %ld of %ld pictures", poc + short_at, o.num_pictures);
         } else {
             for (int k = 0; k < want; ++k) {
-                if (!read_exact(fin, s.in + g.vpic * k, g.vpic)) die("input ended after %ld of %ld pictures", poc + k, o.num_pictures);
+                if (!read_exact(fin, s.in + g.ipic * k, g.ipic)) die("input ended after %ld of %ld pictures", poc + k, o.num_pictures);
                 upload(s, k);
             }
         }
@@ -714,9 +734,10 @@ int main(int argc, char** argv) {
         wrenc_gpu_ctx* ctx = nullptr;
         if (wrenc_gpu_create(&cfg, &ctx)) fatal("%s", wrenc_gpu_last_error(nullptr)); // no CPU path: fails without an MI355X
         if (o.pad && wrenc_gpu_set_visible_size(ctx, o.vis_w, o.vis_h)) fatal("%s", wrenc_gpu_last_error(ctx));
+        if (o.scale && wrenc_gpu_set_source_size(ctx, o.in_w, o.in_h)) fatal("%s", wrenc_gpu_last_error(ctx)); // after the visible size
         ctxs.push_back(ctx);
     }
-    const Geometry g(o.w, o.h, o.vis_w, o.vis_h);
+    const Geometry g(o.w, o.h, o.vis_w, o.vis_h, o.in_w, o.in_h);
     std::vector<HostSet> units = make_units(o, g, ctxs, per_dev, frec != nullptr);
     size_t hdr_bytes = 0, rate_hdr_bytes = 0;
     {

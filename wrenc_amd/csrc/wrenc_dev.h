@@ -19,6 +19,7 @@
 //   dev_search.h     block_splitter.rs:64-1154, ctu_encoder.rs:1421-1461
 //   dev_bins.h       ctu_encoder.rs:1786-2269       residual_coding as a token stream for the host's arithmetic coder
 //   dev_metrics.h    (the evaluation harness)       PSNR / SSIM sums of originals against the reconstruction
+//   dev_scale.h      (no counterpart)               resampling of an uploaded picture to the visible size
 #pragma once
 
 // The WRENC_EXP_* switches are measurement builds (tools/README.md); several of them give wrong results on purpose.
@@ -44,3 +45,4 @@
 #include "dev_metrics.h"
 #include "dev_complexity.h"
 #include "dev_pad.h"
+#include "dev_scale.h"

@@ -10,6 +10,7 @@
 // wait is a workgroup's acquire of a scratch region from a bitmap that always has
 // more regions than workgroups can be resident, see ctu_search_kernel.)
 #include "../../include/wrenc_gpu.h"
+#include "../../include/wrenc_scale.h"
 #include "wrenc_dev.h"
 
 #include <hip/hip_runtime.h>
@@ -672,6 +673,14 @@ struct wrenc_gpu_ctx {
     // the size of the caller's pictures (wrenc_gpu_set_visible_size); the coded size unless one is set
     int vis_w = 0, vis_h = 0;
     bool any_upload = false;
+    // a scaling context (wrenc_gpu_set_source_size): the size of the caller's pictures (0: none set, the visible size), the
+    // staging planes the upload copies them into (one set per context: copies, scaler, pad and retile of every slot run
+    // on copy_stream, in order, so a picture is scaled out of them before the next one is copied in), the filter's tables
+    // (one allocation) and the kernel's arguments but for the slot
+    int src_w = 0, src_h = 0;
+    uint8_t* d_stage = nullptr;
+    void* d_scale_tab = nullptr;
+    ScaleArgs scale_args = {};
     unsigned long long* d_mismatch = nullptr;
     int* d_overflow = nullptr;
     uint8_t* d_pred_scratch = nullptr; // kScratchSlots x WPB x kWaveScratch: saved reconstructions (dev_search.h copy_block)
@@ -1252,6 +1261,8 @@ void wrenc_gpu_destroy(wrenc_gpu_ctx* ctx) {
     if (ctx->d_xpartial) (void)hipFree(ctx->d_xpartial);
     if (ctx->d_xsums) (void)hipFree(ctx->d_xsums);
     if (ctx->d_xmap) (void)hipFree(ctx->d_xmap);
+    if (ctx->d_stage) (void)hipFree(ctx->d_stage);
+    if (ctx->d_scale_tab) (void)hipFree(ctx->d_scale_tab);
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
     if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
@@ -1401,16 +1412,31 @@ int wrenc_gpu_upload(wrenc_gpu_ctx* ctx, int slot, const uint8_t* y, const uint8
     if (!ctx) return WRENC_GPU_EINVAL;
     if (slot < 0 || slot >= ctx->cfg.n_slots || !y || !cb || !cr) return fail(ctx, WRENC_GPU_EINVAL, "bad slot or null plane");
     const size_t w = ctx->cfg.width, h = ctx->cfg.height;
-    const size_t vw = (size_t)ctx->vis_w, vh = (size_t)ctx->vis_h; // the caller's planes; w x h unless a visible size is set
-    if (stride_y < vw || stride_c < vw / 2) return fail(ctx, WRENC_GPU_EINVAL, "stride smaller than row");
+    const size_t vw = (size_t)ctx->vis_w, vh = (size_t)ctx->vis_h; // the slot's picture; w x h unless a visible size is set
+    const bool scaling = ctx->src_w != 0;
+    const size_t sw = scaling ? (size_t)ctx->src_w : vw, sh = scaling ? (size_t)ctx->src_h : vh; // the caller's planes
+    if (stride_y < sw || stride_c < sw / 2) return fail(ctx, WRENC_GPU_EINVAL, "stride smaller than row");
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
     PicBufs& b = ctx->slots[slot];
     // the planes may still be read by a search in flight on this slot
     if (ctx->slot_event[slot]) HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->slot_event[slot], 0));
     hipStream_t cs = ctx->copy_stream;
-    HIP_TRY(ctx, hipMemcpy2DAsync((void*)b.org[0], w, y, stride_y, vw, vh, hipMemcpyHostToDevice, cs));
-    HIP_TRY(ctx, hipMemcpy2DAsync((void*)b.org[1], w / 2, cb, stride_c, vw / 2, vh / 2, hipMemcpyHostToDevice, cs));
-    HIP_TRY(ctx, hipMemcpy2DAsync((void*)b.org[2], w / 2, cr, stride_c, vw / 2, vh / 2, hipMemcpyHostToDevice, cs));
+    if (scaling) {
+        // Source-size planes into the context's staging planes, then the scaler (dev_scale.h) writes the visible
+        // rectangle of the slot's planes.  Copies, scaler, pad and retile all run on copy_stream, in order: the one set of
+        // staging planes is read out before the next upload's copies reach it, whichever slot that one is for.
+        ScaleArgs a = ctx->scale_args;
+        const uint8_t* const from[3] = {y, cb, cr};
+        for (int p = 0; p < 3; ++p)
+            HIP_TRY(ctx, hipMemcpy2DAsync((void*)a.src[p], (size_t)a.src_pitch[p ? 1 : 0], from[p], p ? stride_c : stride_y,
+                                          p ? sw / 2 : sw, p ? sh / 2 : sh, hipMemcpyHostToDevice, cs));
+        a.dst = (uint8_t*)b.org[0];
+        hipLaunchKernelGGL(scale_kernel, dim3((unsigned)(a.tiles[0] + 2 * a.tiles[1])), dim3(256), 0, cs, a);
+    } else {
+        HIP_TRY(ctx, hipMemcpy2DAsync((void*)b.org[0], w, y, stride_y, vw, vh, hipMemcpyHostToDevice, cs));
+        HIP_TRY(ctx, hipMemcpy2DAsync((void*)b.org[1], w / 2, cb, stride_c, vw / 2, vh / 2, hipMemcpyHostToDevice, cs));
+        HIP_TRY(ctx, hipMemcpy2DAsync((void*)b.org[2], w / 2, cr, stride_c, vw / 2, vh / 2, hipMemcpyHostToDevice, cs));
+    }
     // a picture smaller than the coded size: its last column and row replicated into the margin of the three planes
     // (dev_pad.h), behind the copies and in front of the tiling
     if (vw != w || vh != h) {
@@ -1438,6 +1464,7 @@ int wrenc_gpu_set_visible_size(wrenc_gpu_ctx* ctx, int vis_w, int vis_h) {
             return fail(ctx, WRENC_GPU_EINVAL, "the context's size must be the visible size rounded up to a multiple of 32");
     }
     if (ctx->any_upload) return fail(ctx, WRENC_GPU_ESTATE, "the visible size must be set before the first upload");
+    if (ctx->src_w) return fail(ctx, WRENC_GPU_ESTATE, "a source size is set: the visible size comes first, then the source size");
     ctx->vis_w = vis_w;
     ctx->vis_h = vis_h;
     ctx->metrics_cap = 0; // the metrics scratch is sized for the rectangle that is measured
@@ -1448,6 +1475,140 @@ int wrenc_gpu_visible_size(const wrenc_gpu_ctx* ctx, int* w, int* h) {
     if (!ctx || !w || !h) return WRENC_GPU_EINVAL;
     *w = ctx->vis_w;
     *h = ctx->vis_h;
+    return WRENC_GPU_OK;
+}
+
+int wrenc_gpu_scale_taps(int n_in, int n_out, int o, int* first, int* n_taps, int16_t coef[WRENC_SCALE_MAX_TAPS]) {
+    return wrenc_scale_taps(n_in, n_out, o, first, n_taps, coef) ? WRENC_GPU_EINVAL : WRENC_GPU_OK;
+}
+
+namespace {
+
+// the tables of one axis (dev_scale.h: ScaleAxis) as they go to the device
+struct ScaleAxisHost {
+    std::vector<int> first, tile_base;
+    std::vector<int16_t> coef;
+    int n_in = 0, n_out = 0, taps = 0, span = 0;
+};
+
+// tile: output samples per tile of this axis; align4: tile_base rounded down to a multiple of 4 (the x axis: dword loads)
+bool build_scale_axis(int n_in, int n_out, int tile, bool align4, ScaleAxisHost& h) {
+    h.n_in = n_in;
+    h.n_out = n_out;
+    h.first.assign((size_t)n_out, 0);
+    h.coef.assign((size_t)n_out * kScaleCoefs, 0);
+    h.taps = 0;
+    for (int o = 0; o < n_out; ++o) {
+        int16_t k[WRENC_SCALE_MAX_TAPS];
+        int n = 0;
+        if (wrenc_scale_taps(n_in, n_out, o, &h.first[(size_t)o], &n, k) || n > kScaleCoefs) return false;
+        for (int j = 0; j < n; ++j) h.coef[(size_t)o * kScaleCoefs + j] = k[j];
+        h.taps = n > h.taps ? n : h.taps;
+    }
+    h.taps = (h.taps + 1) & ~1;
+    const int tiles = (n_out + tile - 1) / tile;
+    h.tile_base.assign((size_t)tiles, 0);
+    h.span = 0;
+    for (int t = 0; t < tiles; ++t) {
+        int lo = h.first[(size_t)t * tile], hi = lo;
+        for (int o = t * tile; o < n_out && o < (t + 1) * tile; ++o) {
+            lo = h.first[(size_t)o] < lo ? h.first[(size_t)o] : lo;
+            hi = h.first[(size_t)o] > hi ? h.first[(size_t)o] : hi;
+        }
+        if (align4) lo &= ~3;
+        h.tile_base[(size_t)t] = lo;
+        h.span = hi + h.taps - lo > h.span ? hi + h.taps - lo : h.span;
+    }
+    return true;
+}
+
+} // namespace
+
+int wrenc_gpu_set_source_size(wrenc_gpu_ctx* ctx, int src_w, int src_h) {
+    if (!ctx) return WRENC_GPU_EINVAL;
+    const int vw = ctx->vis_w, vh = ctx->vis_h;
+    const bool plain = src_w == vw && src_h == vh;
+    if (!plain) {
+        if (src_w < 16 || src_h < 16 || (src_w & 1) || (src_h & 1))
+            return fail(ctx, WRENC_GPU_EINVAL, "the source size must be even and at least 16x16");
+        if (src_w > 4 * vw || vw > 4 * src_w || src_h > 4 * vh || vh > 4 * src_h || src_w > WRENC_SCALE_MAX_SIZE ||
+            src_h > WRENC_SCALE_MAX_SIZE)
+            return fail(ctx, WRENC_GPU_EINVAL, "the source size must be within a factor of 4 of the visible size in each dimension");
+    }
+    if (ctx->any_upload) return fail(ctx, WRENC_GPU_ESTATE, "the source size must be set before the first upload");
+    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+    if (ctx->d_stage) (void)hipFree(ctx->d_stage);
+    if (ctx->d_scale_tab) (void)hipFree(ctx->d_scale_tab);
+    ctx->d_stage = nullptr;
+    ctx->d_scale_tab = nullptr;
+    ctx->src_w = ctx->src_h = 0;
+    if (plain) return WRENC_GPU_OK;
+    // the four tables: x and y of luma, x and y of chroma; every piece starts on a 16-byte boundary of one allocation
+    ScaleAxisHost ax[4];
+    const int n_in[4] = {src_w, src_h, src_w / 2, src_h / 2}, n_out[4] = {vw, vh, vw / 2, vh / 2};
+    size_t at = 0, off[4][3];
+    for (int i = 0; i < 4; ++i) {
+        const bool is_x = !(i & 1);
+        if (!build_scale_axis(n_in[i], n_out[i], is_x ? kScaleTileW : kScaleTileH, is_x, ax[i]) ||
+            ax[i].span > (is_x ? kScaleSpanX : kScaleSpanY))
+            return fail(ctx, WRENC_GPU_EINVAL, "the scaler's tables do not fit its tile");
+        const size_t bytes[3] = {ax[i].first.size() * sizeof(int), ax[i].coef.size() * sizeof(int16_t), ax[i].tile_base.size() * sizeof(int)};
+        for (int k = 0; k < 3; ++k) {
+            off[i][k] = at;
+            at += (bytes[k] + 15) & ~(size_t)15;
+        }
+    }
+    std::vector<uint8_t> tab(at, 0);
+    for (int i = 0; i < 4; ++i) {
+        memcpy(&tab[off[i][0]], ax[i].first.data(), ax[i].first.size() * sizeof(int));
+        memcpy(&tab[off[i][1]], ax[i].coef.data(), ax[i].coef.size() * sizeof(int16_t));
+        memcpy(&tab[off[i][2]], ax[i].tile_base.data(), ax[i].tile_base.size() * sizeof(int));
+    }
+    const size_t pitch_y = ((size_t)src_w + 15) & ~(size_t)15, pitch_c = ((size_t)src_w / 2 + 15) & ~(size_t)15;
+    const size_t stage_y = pitch_y * (size_t)src_h, stage_c = pitch_c * (size_t)(src_h / 2);
+    hipError_t e = hipMalloc((void**)&ctx->d_scale_tab, at);
+    if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_stage, stage_y + 2 * stage_c);
+    if (e == hipSuccess) e = hipMemcpy(ctx->d_scale_tab, tab.data(), at, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (ctx->d_stage) (void)hipFree(ctx->d_stage);
+        if (ctx->d_scale_tab) (void)hipFree(ctx->d_scale_tab);
+        ctx->d_stage = nullptr;
+        ctx->d_scale_tab = nullptr;
+        return fail(ctx, e == hipErrorOutOfMemory ? WRENC_GPU_ENOMEM : WRENC_GPU_EHIP, std::string("scaler buffers: ") + hipGetErrorString(e));
+    }
+    ScaleArgs& a = ctx->scale_args;
+    a = ScaleArgs{};
+    const uint8_t* base = (const uint8_t*)ctx->d_scale_tab;
+    for (int i = 0; i < 4; ++i) {
+        ScaleAxis& d = (i & 1) ? a.y[i >> 1] : a.x[i >> 1];
+        d.first = (const int*)(base + off[i][0]);
+        d.coef = (const int16_t*)(base + off[i][1]);
+        d.tile_base = (const int*)(base + off[i][2]);
+        d.n_in = ax[i].n_in;
+        d.n_out = ax[i].n_out;
+        d.taps = ax[i].taps;
+        d.span = ax[i].span;
+    }
+    a.src[0] = ctx->d_stage;
+    a.src[1] = ctx->d_stage + stage_y;
+    a.src[2] = ctx->d_stage + stage_y + stage_c;
+    a.src_pitch[0] = (int)pitch_y;
+    a.src_pitch[1] = (int)pitch_c;
+    a.W = ctx->cfg.width;
+    a.H = ctx->cfg.height;
+    for (int c = 0; c < 2; ++c) {
+        a.tiles_x[c] = (int)ax[2 * c].tile_base.size();
+        a.tiles[c] = a.tiles_x[c] * (int)ax[2 * c + 1].tile_base.size();
+    }
+    ctx->src_w = src_w;
+    ctx->src_h = src_h;
+    return WRENC_GPU_OK;
+}
+
+int wrenc_gpu_source_size(const wrenc_gpu_ctx* ctx, int* w, int* h) {
+    if (!ctx || !w || !h) return WRENC_GPU_EINVAL;
+    *w = ctx->src_w ? ctx->src_w : ctx->vis_w;
+    *h = ctx->src_w ? ctx->src_h : ctx->vis_h;
     return WRENC_GPU_OK;
 }
 
@@ -2067,7 +2228,8 @@ void wrenc_gpu_free_host(wrenc_gpu_ctx* ctx, void* p) {
 int wrenc_gpu_encode_picture(wrenc_gpu_ctx* ctx, const uint8_t* y, const uint8_t* cb, const uint8_t* cr,
                              wrenc_gpu_picture* out) {
     if (!ctx) return WRENC_GPU_EINVAL;
-    int rc = wrenc_gpu_upload(ctx, 0, y, cb, cr, ctx->vis_w, ctx->vis_w / 2);
+    const int row = ctx->src_w ? ctx->src_w : ctx->vis_w;
+    int rc = wrenc_gpu_upload(ctx, 0, y, cb, cr, (size_t)row, (size_t)row / 2);
     if (rc) return rc;
     rc = wrenc_gpu_encode(ctx, 0, 1);
     if (rc) return rc;

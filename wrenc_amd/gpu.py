@@ -24,6 +24,7 @@ EXPORTED_SYMBOLS = [
     "wrenc_gpu_test_fwd_dct", "wrenc_gpu_test_inv_dct", "wrenc_gpu_test_quantize",
     "wrenc_gpu_test_dequantize", "wrenc_gpu_test_predict", "wrenc_gpu_test_fwd_dct32", "wrenc_gpu_test_inv_dct32", "wrenc_gpu_test_quantize_p16", "wrenc_gpu_test_quantize_pk", "wrenc_gpu_test_fwd_dct4_reg", "wrenc_gpu_test_inv_dct4_reg", "wrenc_gpu_test_set_wave_slots", "wrenc_gpu_test_scratch_overflows", "wrenc_gpu_test_head_ranges", "wrenc_gpu_test_avail_tab",
     "wrenc_gpu_set_visible_size", "wrenc_gpu_visible_size", "wrenc_gpu_test_download_originals",
+    "wrenc_gpu_set_source_size", "wrenc_gpu_source_size", "wrenc_gpu_scale_taps",
 ]
 
 
@@ -80,6 +81,19 @@ def metrics_values(width, height, m):
     names = ("Avg", "Y", "U", "V")
     return {"PSNR": dict(zip(names, psnr)), "SSIM": dict(zip(names, ssim)),
             "_raw": {"sse": list(m.sse), "ssim_sum": list(m.ssim_sum), "ssim_windows": list(m.ssim_windows), "bytes": bytes(m)}}
+
+
+def scale_taps(n_in, n_out, o):
+    """wrenc_gpu_scale_taps (host only): (first input index, [coefficients]) of output sample o of one axis n_in -> n_out
+    of the scaling filter (include/wrenc_scale.h); WrencGpuError outside the limits."""
+    lib = load_library()
+    first, n = C.c_int(), C.c_int()
+    coef = (C.c_int16 * 17)()
+    lib.wrenc_gpu_scale_taps.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    rc = lib.wrenc_gpu_scale_taps(int(n_in), int(n_out), int(o), C.byref(first), C.byref(n), coef)
+    if rc:
+        raise WrencGpuError(rc, "scale_taps(%d, %d, %d)" % (n_in, n_out, o))
+    return first.value, list(coef[:n.value])
 
 
 class WrencGpuError(RuntimeError):
@@ -166,10 +180,12 @@ class Encoder:
     SliceEncoder::encode uses in place of the per-CTU split_ct loop."""
 
     def __init__(self, width, height, qp=26, max_split_depth=3, device=0, n_slots=1, config=None, extra_params=None,
-                 schedule=None, visible=None):
+                 schedule=None, visible=None, source=None):
         """width x height: the coded size, whole 32x32 CTUs.  visible=(w, h): the pictures are that size (even, at least
         16x16, the coded size its round-up to multiples of 32): upload takes planes of it, the device replicates their last
-        column and row into the margin, and download_metrics reports that rectangle (wrenc_gpu_set_visible_size)."""
+        column and row into the margin, and download_metrics reports that rectangle (wrenc_gpu_set_visible_size).
+        source=(w, h): the pictures are THAT size and the device resamples them to the visible size (the coded size when
+        none is given) in front of everything else (wrenc_gpu_set_source_size)."""
         self.lib = load_library()
         self.cfg = config if config is not None else default_config(width, height, qp, max_split_depth,
                                                                      device, n_slots, extra_params)
@@ -183,11 +199,18 @@ class Encoder:
         self._keep = {}
         self._pinned = []
         self.vis_width, self.vis_height = self.width, self.height
+        self.src_width, self.src_height = self.width, self.height
         if schedule is not None:
             self.set_schedule(schedule)
         if visible is not None:
             try:
                 self.set_visible_size(*visible)
+            except WrencGpuError:
+                self.close()
+                raise
+        if source is not None:
+            try:
+                self.set_source_size(*source)
             except WrencGpuError:
                 self.close()
                 raise
@@ -216,17 +239,17 @@ class Encoder:
         y = np.ascontiguousarray(y, np.uint8)
         cb = np.ascontiguousarray(cb, np.uint8)
         cr = np.ascontiguousarray(cr, np.uint8)
-        assert y.shape == (self.vis_height, self.vis_width)
-        assert cb.shape == cr.shape == (self.vis_height // 2, self.vis_width // 2)
+        assert y.shape == (self.src_height, self.src_width)
+        assert cb.shape == cr.shape == (self.src_height // 2, self.src_width // 2)
         self._keep[slot] = (y, cb, cr)  # host buffers must outlive the async copy
-        self._check(self.lib.wrenc_gpu_upload(self.ctx, slot, _p(y), _p(cb), _p(cr), self.vis_width, self.vis_width // 2))
+        self._check(self.lib.wrenc_gpu_upload(self.ctx, slot, _p(y), _p(cb), _p(cr), self.src_width, self.src_width // 2))
 
     def upload_strided(self, slot, y, cb, cr):
         """upload of planes that are views into wider arrays (last axis contiguous): their row strides go to the C ABI."""
         planes = [np.asarray(a) for a in (y, cb, cr)]
         assert all(a.dtype == np.uint8 and a.strides[1] == 1 for a in planes)
-        assert planes[0].shape == (self.vis_height, self.vis_width) and planes[1].strides[0] == planes[2].strides[0]
-        assert planes[1].shape == planes[2].shape == (self.vis_height // 2, self.vis_width // 2)
+        assert planes[0].shape == (self.src_height, self.src_width) and planes[1].strides[0] == planes[2].strides[0]
+        assert planes[1].shape == planes[2].shape == (self.src_height // 2, self.src_width // 2)
         self._keep[slot] = tuple(planes)
         self._check(self.lib.wrenc_gpu_upload(self.ctx, slot, _p(planes[0]), _p(planes[1]), _p(planes[2]),
                                               planes[0].strides[0], planes[1].strides[0]))
@@ -236,6 +259,20 @@ class Encoder:
         self.lib.wrenc_gpu_set_visible_size.argtypes = [C.c_void_p, C.c_int, C.c_int]
         self._check(self.lib.wrenc_gpu_set_visible_size(self.ctx, int(vis_w), int(vis_h)))
         self.vis_width, self.vis_height = int(vis_w), int(vis_h)
+        self.src_width, self.src_height = self.source_size()
+
+    def set_source_size(self, src_w, src_h):
+        """wrenc_gpu_set_source_size: upload takes planes of this size and the device scales them to the visible size; before
+        the first upload and after any set_visible_size; the visible size itself restores the plain behaviour."""
+        self.lib.wrenc_gpu_set_source_size.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        self._check(self.lib.wrenc_gpu_set_source_size(self.ctx, int(src_w), int(src_h)))
+        self.src_width, self.src_height = int(src_w), int(src_h)
+
+    def source_size(self):
+        w, h = C.c_int(), C.c_int()
+        self.lib.wrenc_gpu_source_size.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        self._check(self.lib.wrenc_gpu_source_size(self.ctx, C.byref(w), C.byref(h)))
+        return w.value, h.value
 
     def visible_size(self):
         w, h = C.c_int(), C.c_int()
