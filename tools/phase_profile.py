@@ -43,7 +43,7 @@ names = (["predict", "fdct", "q_pre", "q_back", "q_trace", "deq", "idct", "recon
             "sad_tables", "sad_blocks", "sad_samples", "leaf8_cclm_sad", "sad_lines"] + ["y9"]
          + ["leaf4_stage", "leaf4_packA", "leaf4_sad", "leaf4_packB", "leafc4", "split8_other"] + ["y10"] + ["hist%d" % i for i in range(64)]
          + ["y11"] + CUTS + FLOOR_CUTS + CAND_CUTS)
-KINDS = ["sadlist", "full", "nop/copy", "sadsearch", "cclmsearch", "serve8", "?", "leaf8", "leaf16", "split8", "serve4"] + ["?"] * 5
+KINDS = ["sadlist", "full", "nop/copy", "sadsearch", "cclmsearch", "serve8", "?", "leaf8", "leaf16", "split8", "serve4", "node8"] + ["?"] * 4
 N = len(names)
 out = (C.c_ulonglong * N)()
 enc.lib.wrenc_gpu_prof_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int]

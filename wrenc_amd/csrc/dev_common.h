@@ -296,7 +296,7 @@ struct CtuSt {
     uint8_t pad0_;
     UF<uint8_t> z, rl, rc;           // final-pass z-order index, regen modes
     UF<uint8_t> rbx, rby, rlg;       // regen block
-    UF<uint8_t> ns_luma_cur, ns_chroma_cur;
+    uint8_t pad2_[2];
     UF<uint8_t> pend, pbx, pby, plg, pslot; // reconstruction save to attach to the next request
     // team schedule: a decided leaf's winner still to be pulled into every member's tile, done by the driver loop
     // before the next evaluation.  dp0 = on | comps << 1 | from << 3 | (lg - 2) << 5, dp1 = bx / 4 | (by / 4) << 3
@@ -304,7 +304,8 @@ struct CtuSt {
     // level schedule (team kernel at max-split-depth 3, dev_search.h): on | this member's unit | end of its final-pass range
     UF<uint8_t> lvmode, lv_i, zend;
     UF<uint8_t> fz_on;               // the final pass has begun (Lds::lev_was / lev_now are loaded)
-    UF<float> ret, ns_cost_cur;
+    UF<float> ret;
+    uint32_t pad3_;
     uint32_t pad1_;
     UF<float> ctu_cost;
     UF<float> lv_acc0, lv_acc1; // level schedule: running split cost of the open 32x32 / 16x16 node

@@ -10,7 +10,8 @@ namespace wrenc {
 // Evaluation requests and the evaluator
 // ---------------------------------------------------------------------------
 // (the numbers index the profile build's counters, tools/phase_profile.py: 6 stays free)
-enum { K_SADLIST = 0, K_FULL = 1, K_NOP = 2, K_SADSEARCH = 3, K_CCLMSEARCH = 4, K_SERVE8 = 5, K_LEAF8 = 7, K_LEAF16 = 8, K_SPLIT8 = 9, K_SERVE4 = 10 };
+enum { K_SADLIST = 0, K_FULL = 1, K_NOP = 2, K_SADSEARCH = 3, K_CCLMSEARCH = 4, K_SERVE8 = 5, K_LEAF8 = 7, K_LEAF16 = 8, K_SPLIT8 = 9, K_SERVE4 = 10,
+       K_NODE8 = 11 };
 enum { COPY_NONE = 0, COPY_SAVE = 1, COPY_RESTORE = 2, COPY_PULL = 3 };
 
 // Split cut (wave schedule): a node's children are searched only until their partial cost, summed in z-order in f32 from
@@ -62,6 +63,8 @@ struct Req {
                     // DUAL_TREE_CHROMA one (split8_search); Res::vmin = the split cost (:1116-1123)
                     // K_LEAF16: the five full candidates of a 16x16 SINGLE_TREE leaf and its SAD search in one request, the
                     // candidates in packs of two (leaf16_search): Res::imin = the best luma mode, vmin = its cost, + its parts
+                    // K_NODE8 (wave kernel at max-split-depth 3): one 8x8 node decided inside the request -- its unsplit
+                    // candidate, its split, the comparison and the restore (node8_search): Res::vmin = the node's cost
     int comps;      // bit 0: luma block, bit 1: Cb+Cr pair
     int tx, ty, tlg;
     int ml, mc;     // K_FULL: luma / chroma mode; K_SADLIST: mc = the CCLM mode
@@ -396,7 +399,8 @@ __device__ __forceinline__ void sad_search(const Ctx& c, const Req& q, int& cm_o
 
 __device__ __forceinline__ Res leaf8_search(const Ctx& c, const Req& q, int* overflow);
 __device__ __forceinline__ Res leaf16_search(const Ctx& c, const Req& q, int* overflow);
-__device__ __forceinline__ Res split8_search(const Ctx& c, const Req& q, int* overflow);
+__device__ __forceinline__ Res split8_search(const Ctx& c, const Req& q, int* overflow, int* leaves = nullptr);
+__device__ __forceinline__ void fill_maps(int bx, int by, int lg, int luma_mode, int chroma_mode, bool luma, bool chroma);
 __device__ __forceinline__ void serve_pack4(const Ctx& c, const Req& q, int* overflow);
 __device__ __forceinline__ void serve_pack8(const Ctx& c, const Req& q, int* overflow);
 
@@ -426,6 +430,47 @@ __device__ __forceinline__ int cclm_pred4_lane(const Ctx& c, const Req& q, const
     return v;
 }
 
+// One 8x8 node of the wave schedule at max-split-depth 3, decided without leaving the request (K_NODE8): the
+// SINGLE_TREE leaf search, whose winner with its final DM-or-CCLM chroma is then in the tile; the maps of the unsplit
+// candidate; the split's search against the unsplit cost (split8_search, its cuts and floors as they are); the comparison
+// of :1125-1145.  The unsplit candidate's reconstruction waits in ONE register per lane meanwhile -- luma sample
+// (lane & 7, lane >> 3), and in lanes 0..31 the Cb / Cr sample of the 4x4 pair -- where the walk used to save it to a slot
+// in global scratch in front of K_SPLIT8 and to fetch it back with a request of its own: 96 bytes out and in, two
+// requests and three control steps per node.  A split that is cut before its first leaf has touched neither the tile
+// nor the maps, so nothing is put back.  Returns the node's cost.
+__device__ __forceinline__ float node8_search(const Ctx& c, int tx, int ty, int* overflow) {
+    Req qn = {}; // (only what the two searches read)
+    qn.comps = 3;
+    qn.tx = tx;
+    qn.ty = ty;
+    qn.tlg = 3;
+    qn.refs0 = true;
+    qn.refs1 = true;
+    qn.tree = TREE_SINGLE;
+    stage_org_leaf(c, 3, tx, ty, 3);
+    const Res ru = leaf8_search(c, qn, overflow);
+    const float ns = ru.vmin;
+    const int ml = ru.imin, mc = ru.imin2;
+    fill_maps(tx, ty, 3, ml, mc, true, true);
+    unsigned kept;
+    {
+        const int lane = lane_fresh();
+        kept = (unsigned)rec_get(0, tx + (lane & 7), ty + (lane >> 3));
+        if (lane < 32) kept |= (unsigned)rec_get(1 + (lane >> 4), (tx >> 1) + (lane & 3), (ty >> 1) + ((lane & 15) >> 2)) << 8;
+    }
+    qn.fcur = ns; // (kSplitCut)
+    int leaves = 0;
+    const float split8 = split8_search(c, qn, overflow, &leaves).vmin;
+    if (!(split8 > ns)) return split8; // (a tie is a split)
+    if (leaves) { // :1125-1145: the unsplit 8x8 wins, put it back
+        const int lane = lane_fresh();
+        rec_put(0, tx + (lane & 7), ty + (lane >> 3), (int)(kept & 255u));
+        if (lane < 32) rec_put(1 + (lane >> 4), (tx >> 1) + (lane & 3), (ty >> 1) + ((lane & 15) >> 2), (int)(kept >> 8));
+        fill_maps(tx, ty, 3, ml, mc, true, true); // (ends in a WSYNC)
+    }
+    return ns;
+}
+
 // The evaluator: every block evaluation of the search, of the regeneration and of the final pass
 // goes through this one inlined copy (the search logic below is a state machine that hands out
 // evaluation requests; no function calls in the hot path).
@@ -442,9 +487,16 @@ __device__ __forceinline__ Res evaluate(const Ctx& c, const PicBufs& pb, const R
     if (q.kind == K_NOP) return r;
     if (q.stage) stage_org_leaf(c, q.stage, q.tx, q.ty, q.tlg);
     // (4x4 leaves are searched inside K_SPLIT8 only: nothing asks for one by itself)
-    if (q.kind == K_LEAF8) return leaf8_search(c, q, overflow);
+    // The wave kernel at max-split-depth 3 searches an 8x8 block only as a node that may split (K_NODE8): its one copy
+    // of leaf8_search and its one copy of split8_search are node8_search's
+    constexpr bool kNodes = !TEAM && D3;
+    if (kNodes && q.kind == K_NODE8) {
+        r.vmin = node8_search(c, q.tx, q.ty, overflow);
+        return r;
+    }
+    if (!kNodes && q.kind == K_LEAF8) return leaf8_search(c, q, overflow);
     if (q.kind == K_LEAF16) return leaf16_search(c, q, overflow);
-    if (D3 && q.kind == K_SPLIT8) return split8_search(c, q, overflow);
+    if (TEAM && D3 && q.kind == K_SPLIT8) return split8_search(c, q, overflow);
     if (TEAM && q.kind == K_SERVE8) { // (member 0 only)
         serve_pack8(c, q, overflow);
         return r;
@@ -1530,7 +1582,8 @@ __device__ __forceinline__ bool split_floor_cut(const Ctx& c, float partial, int
 // The check runs before every leaf, the first one included, with the leaves still to come at their floors (split_floor_cut).
 // (Only the kernels built for max-split-depth 3 contain it, D3 below: inlined into the one evaluator of a kernel that also
 // serves depth 2, which never splits an 8x8, it cost that depth 2.5 %; as an out-of-line function it cost both depths more.)
-__device__ __forceinline__ Res split8_search(const Ctx& c, const Req& q, int* overflow) {
+// *leaves (where asked for): 0 when the split was cut before its first leaf, so that nothing has touched the tile or the maps
+__device__ __forceinline__ Res split8_search(const Ctx& c, const Req& q, int* overflow, int* leaves) {
     Res r = res_none();
     float split8 = 0.0f;
 #pragma unroll 1
@@ -1549,6 +1602,7 @@ __device__ __forceinline__ Res split8_search(const Ctx& c, const Req& q, int* ov
             PROF_ADD2(PH_CUT + 4, 0, split8 > q.fcur ? 0 : 1);
             return r;
         }
+        if (leaves) *leaves = 1;
         PROF_MARK(l4g0_);
         stage_org_leaf(c, 1, ql.tx, ql.ty, 2);
         PROF_MARK(l4g1_);
@@ -2256,8 +2310,8 @@ __device__ __forceinline__ void lv_post_split(int L, float sp) {
 // slots in global scratch they were saved to (copy_block): the reference's cache_reconsts /
 // restore_reconsts (block_splitter.rs:807-840, 1085-1145), with the saved planes kept in L2/HBM
 // instead of LDS.
-// (the numbers index the profile build's counters, tools/phase_profile.py: 3 .. 5 were the 4x4 leaf walk K_SPLIT8 replaced)
-enum { T_START = 0, T_ENTER = 1, T_NODE_LEAF = 2, T_REGEN_DONE = 6, T_RETURN = 7, T_FINAL_Z = 8, T_FZ_TAIL = 9, T_FZ_NEXT = 10,
+// (the numbers index the profile build's counters, tools/phase_profile.py: 4 and 5 were states of the 4x4 leaf walk K_SPLIT8 replaced)
+enum { T_START = 0, T_ENTER = 1, T_NODE_LEAF = 2, T_NODE8 = 3, T_REGEN_DONE = 6, T_RETURN = 7, T_FINAL_Z = 8, T_FZ_TAIL = 9, T_FZ_NEXT = 10,
        T_LV_UNIT = 11, T_LV_LEAFDONE = 12, T_LV_UP = 13, T_SPLIT8 = 14, T_LV_SERVE = 15 };
 
 template <bool TEAM, bool D3>
@@ -2291,6 +2345,19 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
         case T_ENTER: { // enter node (bx, by) at `level`: the unsplit candidate
             const int lg = 5 - t.level;
             t.lg = (uint8_t)lg;
+            if (!TEAM && D3 && lg == 3) {
+                // max-split-depth 3: an 8x8 node is decided against its split inside ONE request (K_NODE8, node8_search);
+                // the pending save of the parent's unsplit candidate rides on it as on any first request of a first child
+                req_full(q, 3, t.bx, t.by, 3, 0, 0, true, false, false, false);
+                q.kind = K_NODE8;
+                q.tree = TREE_SINGLE;
+                if (t.pend) {
+                    req_copy(q, COPY_SAVE, t.pend, t.pslot, t.pbx, t.pby, t.plg);
+                    t.pend = 0;
+                }
+                t.cont = T_NODE8;
+                return true;
+            }
             // wave schedule, a node whose split is tested next: the search saves its best candidate straight to the
             // node's slot 1 + level, which then holds the unsplit candidate without a save of its own (T_NODE_LEAF)
             leaf_init(t.leaf, t.bx, t.by, lg, (!TEAM && t.level < t.max_depth) ? 1 + t.level : 0);
@@ -2303,9 +2370,6 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
             const float ns = t.leaf.cost;
             const int ml = t.leaf.luma_mode, mc = t.leaf.chroma_mode;
             const int level = t.level, lg = t.lg;
-            t.ns_cost_cur = ns;
-            t.ns_luma_cur = (uint8_t)ml;
-            t.ns_chroma_cur = (uint8_t)mc;
             fill_maps(t.bx, t.by, lg, ml, mc, true, true);
             if (level == 0) c.cu32_mode = ml;
             if (t.max_depth - level == 0) {
@@ -2332,8 +2396,9 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
             // ---- wave schedule from here on ----
             // the unsplit candidate's reconstruction goes to slot 1 + level (cache_reconsts, :1085-1100):
             // the search saved its winner there already (luma and DM chroma, leaf_init above), so all that is left to
-            // save is the chroma pair when the CCLM candidate won; a packed 8x8 search (K_LEAF8) saved nothing.
-            t.pend = (uint8_t)(lg == 3 ? 3 : (mc >= LT_CCLM ? 2 : 0));
+            // save is the chroma pair when the CCLM candidate won.  (An 8x8 node is never here: below max-split-depth 3 it
+            // is a leaf, at depth 3 it is decided inside K_NODE8.)
+            t.pend = (uint8_t)(mc >= LT_CCLM ? 2 : 0);
             t.pbx = t.bx;
             t.pby = t.by;
             t.plg = (uint8_t)lg;
@@ -2346,58 +2411,34 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
                 SH.child[level] = 0;
             }
             WSYNC();
-            if (lg > 3 || !D3) { // (an 8x8 node splits at max-split-depth 3 only)
-                // four children at their floors already cost more than the unsplit candidate (split_floor_cut): the split has
-                // lost before its first child.  No child has touched the tile or the maps, which hold the unsplit candidate
-                // as they do for a node at max-split-depth, so there is nothing to save or to restore
-                float bound;
-                if (split_floor_cut(c, 0.0f, 4, 2 + level + 1, false, ns, &bound)) {
-                    PROF_ADD2(PH_CUT + 2 + level, 0, 4);
-                    PROF_ADD2(PH_CUT + 5, 0, 1);
-                    t.pend = 0;
-                    t.ret = ns;
-                    cont = T_RETURN;
-                    break;
-                }
-                t.level = (uint8_t)(level + 1); // descend into child 0 (same top-left corner)
-                cont = T_ENTER;
+            // four children at their floors already cost more than the unsplit candidate (split_floor_cut): the split has
+            // lost before its first child.  No child has touched the tile or the maps, which hold the unsplit candidate
+            // as they do for a node at max-split-depth, so there is nothing to save or to restore
+            float bound;
+            if (split_floor_cut(c, 0.0f, 4, 2 + level + 1, false, ns, &bound)) {
+                PROF_ADD2(PH_CUT + 2 + level, 0, 4);
+                PROF_ADD2(PH_CUT + 5, 0, 1);
+                t.pend = 0;
+                t.ret = ns;
+                cont = T_RETURN;
                 break;
             }
-            // 8x8: four DUAL_TREE_LUMA 4x4 leaves, then the DUAL_TREE_CHROMA leaf, as one request (K_SPLIT8)
-            req_full(q, 3, t.bx, t.by, 3, 0, 0, true, false, false, false);
-            q.kind = K_SPLIT8;
-            q.stage = 0;
-            q.tree = TREE_DUAL_LUMA;
-            q.fcur = ns; // (kSplitCut)
-            if (t.pend) { // the unsplit 8x8 candidate is saved first
-                req_copy(q, COPY_SAVE, t.pend, t.pslot, t.pbx, t.pby, t.plg);
-                t.pend = 0;
-            }
-            t.cont = T_SPLIT8;
-            return true;
+            t.level = (uint8_t)(level + 1); // descend into child 0 (same top-left corner)
+            cont = T_ENTER;
+            break;
         }
-        case T_SPLIT8: {
-            if constexpr (D3) { // the split candidate of the 8x8 node came back: against the unsplit one
-                const float split8 = r.vmin;
-                if (TEAM && t.lvmode) { // level schedule: member 3's unit is done
-                    lv_post_split(2, split8);
-                    cont = T_LV_UP;
-                    break;
-                }
-                if (split8 > t.ns_cost_cur) { // :1125-1145: the unsplit 8x8 wins, put it back
-                    t.rbx = t.bx;
-                    t.rby = t.by;
-                    t.rlg = t.lg;
-                    t.rl = t.ns_luma_cur;
-                    t.rc = t.ns_chroma_cur;
-                    q.kind = K_NOP;
-                    q.xchg = false;
-                    req_copy(q, COPY_RESTORE, 3, 1 + t.level, t.rbx, t.rby, t.rlg);
-                    t.cont = T_REGEN_DONE;
-                    return true;
-                }
-                t.ret = split8;
+        case T_NODE8: {
+            if constexpr (!TEAM && D3) { // the 8x8 node's cost came back
+                t.ret = r.vmin;
                 cont = T_RETURN;
+                break;
+            }
+            }
+            break;
+        case T_SPLIT8: {
+            if constexpr (TEAM && D3) { // level schedule: member 3's unit is done
+                lv_post_split(2, r.vmin);
+                cont = T_LV_UP;
                 break;
             }
             }
