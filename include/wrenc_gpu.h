@@ -446,7 +446,15 @@ int wrenc_gpu_test_inv_dct4_reg(wrenc_gpu_ctx* ctx, const int16_t* levels, int c
  * originals: mode = first mode (2..66) | entries (1..16) << 8 | stride (1..64) << 16, entry j = first mode + j * stride (an
  * entry beyond 66 is not evaluated and reads 0).  comp 7 (log2 size >= 3, mode 0): the CCLM SAD list of the chroma pair,
  * entries LT_CCLM, T_CCLM, L_CCLM (get_chroma_intra_pred_aux_cost, :476-522).  A list item's output is 16 uint32 (64 bytes):
- * the SAD of entry j at index j. */
+ * the SAD of entry j at index j.
+ * comp 8 / 9: the search's FULL-candidate predictor on the luma block / the Cb+Cr pair (log2 size >= 3; mode as for comp 0 /
+ * 1) into the recon tile, with the block's own samples in the planes as originals (staged as the search stages them).
+ * comp 10 (log2 size 3): the luma blocks of an 8x8 pack of 1..3 candidates, predicted side by side into the pack's LDS
+ * park; comp 11 (log2 size 4): a 16x16 pack of 1..2 candidates, luma block and chroma pair, into its park; their mode =
+ * m0 | m1 << 8 | m2 << 16 | candidates << 24, each m 0..66 or 255 (a candidate that is not evaluated and rides along as
+ * zeros).  Output of 8..11: the prediction bytes read back from the destination (comp 10: [candidate][64]; comp 11: luma
+ * [candidate][256], then chroma [candidate][Cb | Cr][64]), then as many int16 residuals (original - prediction) in the
+ * same order: 3 bytes per sample. */
 int wrenc_gpu_test_predict(wrenc_gpu_ctx* ctx, const uint8_t* rec_y, const uint8_t* rec_cb,
                            const uint8_t* rec_cr, int n_items, const int32_t* items, uint8_t* out,
                            size_t out_bytes);

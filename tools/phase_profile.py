@@ -33,6 +33,12 @@ FLOOR_CUTS = ["cut_floor_split8", "cut_floor_node"]
 # ... and the searched 4x4 luma leaves whose candidate floors skipped the SAD search and pack B / pack B alone
 # (dev_search.h, kCandidateCut; tools/candidate_floor_model.py gives the same two counts from the oracle's trace)
 CAND_CUTS = ["cut_leaf4_sad", "cut_leaf4_packB"]
+# "predict" and "recon" by caller (dev_common.h, PH_PRED / PH_REC): the full candidates of full_front by block size, of
+# the packs, the predict4_lane passes (4x4 blocks, four to a pass), the CCLM predictions, the SAD requests counted
+# under "predict"; the reconstruction loops of full_back, the packs and the 4x4 register pass
+PRED_BY = ["predict_front32", "predict_front16", "predict_pack16", "predict_pack8_luma", "predict_lane4", "predict_cclm",
+           "predict_front_le8", "predict_sad_requests"]
+RECON_BY = ["recon_full_back", "recon_pack16", "recon_pack8", "recon_pass4"]
 names = (["predict", "fdct", "q_pre", "q_back", "q_trace", "deq", "idct", "recon", "total", "ctrl", "refs", "skip", "nstep", "nfull"]
          + ["stages_t%d_c%d" % (4 << (i // 2), i % 2) for i in range(8)] + ["x"] + ["stages_n%d_c%d" % (4 << (i // 2), i % 2) for i in range(8)]
          + ["x2", "qb_pre", "qb_wait1", "qb_walk", "qb_wait2", "t_xchg", "copy"] + ["cb%d" % i for i in range(32)] + ["y"]
@@ -42,7 +48,7 @@ names = (["predict", "fdct", "q_pre", "q_back", "q_trace", "deq", "idct", "recon
          + ["leaf8_packA", "leaf8_sad", "leaf8_packB", "leaf8_cclm", "leaf16_packA", "leaf16_sad", "leaf16_packB", "leaf16_packC",
             "sad_tables", "sad_blocks", "sad_samples", "leaf8_cclm_sad", "sad_lines"] + ["y9"]
          + ["leaf4_stage", "leaf4_packA", "leaf4_sad", "leaf4_packB", "leafc4", "split8_other"] + ["y10"] + ["hist%d" % i for i in range(64)]
-         + ["y11"] + CUTS + FLOOR_CUTS + CAND_CUTS)
+         + ["y11"] + CUTS + FLOOR_CUTS + CAND_CUTS + ["y12"] + PRED_BY + ["y13"] + RECON_BY)
 KINDS = ["sadlist", "full", "nop/copy", "sadsearch", "cclmsearch", "serve8", "?", "leaf8", "leaf16", "split8", "serve4", "node8"] + ["?"] * 4
 N = len(names)
 out = (C.c_ulonglong * N)()

@@ -389,7 +389,7 @@ struct Ctx {
     const CONST_AS DevConst* k;         // constant address space: uniform reads become scalar loads
     const GLOBAL_AS uint8_t* org;       // originals of THIS CTU: the kOrgTile bytes of its tile in PicBufs::org_t (read-only)
     int W, WH;                          // luma width, luma plane size
-    uint8_t* pred_scratch;              // building-block test kernel only (PRED_SCRATCH): where predict() puts its bytes
+    uint8_t* pred_scratch;              // building-block test kernel only (PRED_SCRATCH): where predict_full puts its bytes
     GLOBAL_AS uint8_t* slots;           // kReconSlots saved reconstructions of this wave (see copy_block)
     unsigned long long* mismatch;
     int ctu_x, ctu_y; // luma, picture coordinates
@@ -480,7 +480,10 @@ __device__ __forceinline__ Ctx uni(Ctx c) {
 // Diagnostic build only (-DWRENC_PROFILE): per-phase cycle counters, summed per wave and
 // added to a global table at CTU end.  Never compiled into the product library.
 #ifdef WRENC_PROFILE
-enum { PH_PREDICT, PH_FDCT, PH_QPRE, PH_QBACK, PH_QTRACE, PH_DEQ, PH_IDCT, PH_RECON, PH_TOTAL, PH_CTRL, PH_REFS, PH_SKIP, PH_NSTEP, PH_NFULL, PH_PSZ, PH_PSZ_END = PH_PSZ + 8, PH_PCNT, PH_PCNT_END = PH_PCNT + 8, PH_QB_PRE, PH_QB_WAIT1, PH_QB_WALK, PH_QB_WAIT2, PH_XCHG, PH_COPY, PH_CB, PH_CB_END = PH_CB + 32, PH_CBN, PH_CBN_END = PH_CBN + 32, PH_MEM, PH_MEM_END = PH_MEM + 16, PH_ST, PH_ST_END = PH_ST + 48, PH_STN, PH_STN_END = PH_STN + 12, PH_EV, PH_EV_END = PH_EV + 64, PH_EVN, PH_EVN_END = PH_EVN + 64, PH_QZ, PH_QZ_END = PH_QZ + 4, PH_LEAF, PH_LEAF_END = PH_LEAF + 13, PH_L4, PH_L4_END = PH_L4 + 6, PH_HIST, PH_HIST_END = PH_HIST + 64, PH_CUT, PH_CUT_END = PH_CUT + 8, PH_COUNT }; // PH_HIST: CTU durations, buckets of 2^17 ticks; PH_CUT: children a split cut left unsearched (4x4 luma leaves, chroma leaves, 16x16 nodes, 8x8 nodes), then the cuts that only the floors decided, the partial sum alone being <= the unsplit cost (inside an 8x8 split, between nodes), then the 4x4 luma leaves whose candidate floors skipped the SAD search and pack B / pack B alone (kCandidateCut)
+enum { PH_PREDICT, PH_FDCT, PH_QPRE, PH_QBACK, PH_QTRACE, PH_DEQ, PH_IDCT, PH_RECON, PH_TOTAL, PH_CTRL, PH_REFS, PH_SKIP, PH_NSTEP, PH_NFULL, PH_PSZ, PH_PSZ_END = PH_PSZ + 8, PH_PCNT, PH_PCNT_END = PH_PCNT + 8, PH_QB_PRE, PH_QB_WAIT1, PH_QB_WALK, PH_QB_WAIT2, PH_XCHG, PH_COPY, PH_CB, PH_CB_END = PH_CB + 32, PH_CBN, PH_CBN_END = PH_CBN + 32, PH_MEM, PH_MEM_END = PH_MEM + 16, PH_ST, PH_ST_END = PH_ST + 48, PH_STN, PH_STN_END = PH_STN + 12, PH_EV, PH_EV_END = PH_EV + 64, PH_EVN, PH_EVN_END = PH_EVN + 64, PH_QZ, PH_QZ_END = PH_QZ + 4, PH_LEAF, PH_LEAF_END = PH_LEAF + 13, PH_L4, PH_L4_END = PH_L4 + 6, PH_HIST, PH_HIST_END = PH_HIST + 64, PH_CUT, PH_CUT_END = PH_CUT + 8, PH_PRED, PH_PRED_END = PH_PRED + 8, PH_REC, PH_REC_END = PH_REC + 4, PH_COUNT }; // PH_HIST: CTU durations, buckets of 2^17 ticks; PH_CUT: children a split cut left unsearched (4x4 luma leaves, chroma leaves, 16x16 nodes, 8x8 nodes), then the cuts that only the floors decided, the partial sum alone being <= the unsplit cost (inside an 8x8 split, between nodes), then the 4x4 luma leaves whose candidate floors skipped the SAD search and pack B / pack B alone (kCandidateCut)
+// PH_PRED: PH_PREDICT by caller -- full_front at 32x32, at 16x16, pack16_eval, the luma part of pack8_eval, the predict4_lane
+// passes, the CCLM predictions, full_front of blocks up to 8x8 (the final pass), the SAD requests; PH_REC: PH_RECON by
+// caller -- full_back, pack16_eval, pack8_eval, pass4_reg
 __device__ unsigned long long g_prof[PH_COUNT];
 __shared__ unsigned long long s_prof[PH_COUNT];
 #define PROF_T0() const unsigned long long prof_t0_ = __builtin_readcyclecounter()
@@ -595,6 +598,17 @@ __device__ __forceinline__ void rec_put(int c, int x, int y, int v) {
         SH.recY[y * 36 + x + 4] = (uint8_t)v;
     else
         SH.recC[c - 1][y * 20 + x + 4] = (uint8_t)v;
+}
+// four samples of a row as one dword (x a multiple of 4, y >= 0: the rows' x offset 4 and strides 36 / 20 keep it aligned)
+__device__ __forceinline__ uint32_t rec_get4(int c, int x, int y) {
+    if (c == 0) return *(const uint32_t*)&SH.recY[y * 36 + x + 4];
+    return *(const uint32_t*)&SH.recC[c - 1][y * 20 + x + 4];
+}
+__device__ __forceinline__ void rec_put4(int c, int x, int y, uint32_t v) {
+    if (c == 0)
+        *(uint32_t*)&SH.recY[y * 36 + x + 4] = v;
+    else
+        *(uint32_t*)&SH.recC[c - 1][y * 20 + x + 4] = v;
 }
 // original sample at CTU-local component coordinates (global load; the planes are read-only
 // for the whole launch, so the loads are cacheable and need no ordering)

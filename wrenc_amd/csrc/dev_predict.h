@@ -116,6 +116,8 @@ __device__ __forceinline__ void build_refs(Ctx c, int comp, int tx, int ty, int 
     }
 }
 
+constexpr int kNoMode = 255; // list entry / pack candidate that is not evaluated (cost f32::MAX)
+
 // CCLM model parameters (intra_predictor.rs:1604-2031); uniform across the wave
 struct CclmParams {
     int a, k, b;
@@ -139,7 +141,7 @@ __device__ __forceinline__ int cclm_ds6(Ctx c, int tx, int ty, int sy, int sx, b
 struct CclmPick {
     int a0, a1, k0, k1, b0, b1;
     bool flat128, avail_l;
-    bool have; // (false: nothing at hand, predict() derives the parameters itself.  Passed BY VALUE: a pointer to a pick
+    bool have; // (false: nothing at hand, the predictor derives the parameters itself.  Passed BY VALUE: a pointer to a pick
                // that is only sometimes there kept the struct in scratch memory, 1.6 KB stored and re-read per request)
 };
 __device__ __forceinline__ CclmPick cclm_pick(const CclmParams& v, int s0) {
@@ -295,13 +297,6 @@ constexpr int kOrgLeaf = 1664;
 __device__ __forceinline__ int org_byte(int comp, int tlg) {
     return tlg <= 4 ? kOrgLeaf + (comp ? 256 : 0) : kOrgStage + (comp ? 1024 : 0);
 }
-// original of sample i of the block (plane pc, component coordinates x, y); lds: the block's originals are
-// staged at byte obyte of r2
-template <bool full>
-__device__ __forceinline__ int pred_org(const Ctx& c, int pc, int x, int y, int obyte, int i, bool lds) {
-    if (full && !lds) return org_get(c, pc, x, y);
-    return ((const uint8_t*)SH.r2)[obyte + i];
-}
 __device__ __forceinline__ void stage_org(const Ctx& c, int comps, int tx, int ty, int tlg, int lbyte = kOrgStage,
                                           int cword = 256) {
     uint32_t* dst = (uint32_t*)((char*)SH.r2 + lbyte);
@@ -335,7 +330,7 @@ __device__ __forceinline__ void stage_org_leaf(const Ctx& c, int comps, int tx, 
     stage_org(c, comps, tx, ty, tlg, kOrgLeaf, 64);
 }
 
-// one predicted sample: accumulate |org - pred|; `full` also stores residual and prediction
+// Where a full candidate's prediction goes (predict_full, emit_row4).
 // The prediction itself is parked in the block's own area of the reconstruction tile until the
 // residual is added to it (nothing reads that area in between: the reference samples are cached, and
 // CCLM reads the luma plane while it writes chroma).  Only the final pass, which compares its
@@ -356,39 +351,22 @@ __device__ __forceinline__ uint8_t* park16(int i, int nl) {
     const int j = i - nl;
     return j < 128 ? (uint8_t*)SH.r2 + 1536 + j : (uint8_t*)SH.decw + 384 + (j - 128);
 }
-template <bool full>
-__device__ __forceinline__ int emit_sample(const Ctx& c, int o, int i, int v, int pc, int x, int y, int to_tile, int nl = 0) {
+__device__ __forceinline__ int abs_diff(int o, int v) {
     const int d = o - v;
-    if (full) { // i already includes the block's base in r1 / the prediction scratch
-        SH.r1[i] = (int16_t)d;
-        if (to_tile == PRED_TILE)
-            rec_put(pc, x, y, v);
-        else if (to_tile == PRED_PARK)
-            ((uint8_t*)SH.decw)[kParkByte + i] = (uint8_t)v;
-        else if (to_tile == PRED_PARK16)
-            *park16(i, nl) = (uint8_t)v;
-        else
-            c.pred_scratch[i] = (uint8_t)v;
-    }
     return d < 0 ? -d : d;
 }
 
-// Prediction of one luma block (comp 0) or of the Cb+Cr pair (comp 1) from the cached reference
-// samples (build_refs must have run for this block; CCLM reads the reconstructed luma instead).
+// SAD of ONE mode of one luma block (comp 0) or of the Cb+Cr pair (comp 1), one sample per lane and iteration, from the
+// cached reference samples (build_refs must have run for this block; CCLM reads the reconstructed luma instead)
+// against the originals staged in r2 (stage_org / stage_org_leaf).  The full candidates go through predict_full below,
+// lists of modes through sad_list_angular / sad_list_cclm.
 // Sample index i runs over nb*n*n: block blk = i / (n*n), then row-major inside the block.
-// full: the residual org - pred goes to r1[i] and the prediction byte to this wave's scratch
-//       (each lane later re-reads exactly the bytes it wrote).
 // Returns the lane's partial sum of |org - pred| (the SAD of block_splitter.rs:96-104).
-template <bool full>
-__device__ __forceinline__ int predict(Ctx c, int comp, int tx, int ty, int tlg, int mode, int rbase = 0,
-                                       int to_tile = PRED_TILE, int nl = 0, CclmPick pick = CclmPick{}) {
+__device__ __forceinline__ int predict_sad(Ctx c, int comp, int tx, int ty, int tlg, int mode, CclmPick pick = CclmPick{}) {
 #ifdef WRENC_EXP_SKIP_PRED // instruction-count experiment only (profiles/r04_issue_model.md): nothing predicted
     return 0;
 #endif
     c = uni(c);
-    rbase = uni(rbase);
-    to_tile = uni(to_tile);
-    nl = uni(nl);
     comp = uni(comp);
     tx = uni(tx);
     ty = uni(ty);
@@ -398,10 +376,8 @@ __device__ __forceinline__ int predict(Ctx c, int comp, int tx, int ty, int tlg,
     const int nb = comp ? 2 : 1;
     const int lg = tlg - cs;
     const int n = 1 << lg;
-    const int cx = tx >> cs, cy = ty >> cs;
     const int nn = n * n;
-    const int obyte = org_byte(comp, tlg);
-    const bool olds = tlg <= 4;
+    const uint8_t* org = (const uint8_t*)SH.r2 + org_byte(comp, tlg);
     int sad = 0;
     if (mode >= LT_CCLM) {
         // model parameters of both planes in one pass: odd lanes derive Cr, even lanes Cb
@@ -414,7 +390,7 @@ __device__ __forceinline__ int predict(Ctx c, int comp, int tx, int ty, int tlg,
             const int blk = i >> (2 * lg);
             const int ii = i & (nn - 1);
             const int x = ii & (n - 1), y = ii >> lg;
-            const int o = pred_org<full>(c, comp + blk, cx + x, cy + y, obyte, i, olds); // issued early
+            const int o = org[i]; // issued early
             int v;
             if (flat128) {
                 v = 128;
@@ -423,7 +399,7 @@ __device__ __forceinline__ int predict(Ctx c, int comp, int tx, int ty, int tlg,
                 v = (M24(ds, blk ? a1 : a0) >> (blk ? k1 : k0)) + (blk ? b1 : b0);
                 v = min(max(v, 0), 255);
             }
-            sad += emit_sample<full>(c, o, rbase + i, v, comp + blk, cx + x, cy + y, to_tile, nl);
+            sad += abs_diff(o, v);
         }
         WSYNC();
         return sad;
@@ -450,7 +426,7 @@ __device__ __forceinline__ int predict(Ctx c, int comp, int tx, int ty, int tlg,
             const int blk = i >> (2 * lg);
             const int ii = i & (nn - 1);
             const int x = ii & (n - 1), y = ii >> lg;
-            const int o = pred_org<full>(c, comp + blk, cx + x, cy + y, obyte, i, olds); // issued early
+            const int o = org[i]; // issued early
             const ref_t* L = SH.refs + (blk ? R_LC1 : oL0);
             const ref_t* A = SH.refs + (blk ? R_AC1 : oA0);
             int v;
@@ -464,7 +440,7 @@ __device__ __forceinline__ int predict(Ctx c, int comp, int tx, int ty, int tlg,
             const int wl = pdpc_w(n_scale, x), wt = pdpc_w(n_scale, y);
             v = (int16_t)(M24(L[y + 1], wl) + M24(A[x], wt) + M24(64 - wt - wl, v) + 32) >> 6;
             v = min(max(v, 0), 255);
-            sad += emit_sample<full>(c, o, rbase + i, v, comp + blk, cx + x, cy + y, to_tile, nl);
+            sad += abs_diff(o, v);
         }
         WSYNC();
         return sad;
@@ -513,7 +489,7 @@ __device__ __forceinline__ int predict(Ctx c, int comp, int tx, int ty, int tlg,
         const int blk = i >> (2 * lg);
         const int ii = i & (nn - 1);
         const int x = ii & (n - 1), y = ii >> lg;
-        const int o = pred_org<full>(c, comp + blk, cx + x, cy + y, obyte, i, olds); // issued early
+        const int o = org[i]; // issued early
         const ref_t* L = SH.refs + (blk ? R_LC1 : oL0);
         const ref_t* A = SH.refs + (blk ? R_AC1 : oA0);
         int v;
@@ -553,15 +529,356 @@ __device__ __forceinline__ int predict(Ctx c, int comp, int tx, int ty, int tlg,
             v = (int16_t)(M24(rl, wl) + M24(rt, wt) + M24(64 - wt - wl, v) + 32) >> 6;
             v = min(max(v, 0), 255);
         }
-        sad += emit_sample<full>(c, o, rbase + i, v, comp + blk, cx + x, cy + y, to_tile, nl);
+        sad += abs_diff(o, v);
     }
     WSYNC();
     return sad;
 }
 
+// ---------------------------------------------------------------------------
+// Full candidates, four samples per lane (predict_full below; predict_sad above is the SAD form, one sample per lane).
+// ---------------------------------------------------------------------------
+// Every destination of a prediction takes four bytes of a row as one dword, and r1 four residuals as eight bytes:
+// block corners are multiples of 4 samples in their plane, the tile's rows keep that (x offset 4, strides 36 / 20),
+// kParkByte is a multiple of 16, the three pieces of park16 break at multiples of 128, and every rbase a caller
+// passes is a multiple of 64.
+static_assert(offsetof(Lds, r1) % 8 == 0 && offsetof(Lds, r2) % 4 == 0 && offsetof(Lds, refs) % 4 == 0 &&
+              offsetof(Lds, decw) % 4 == 0, "Lds: r1 takes 8-byte stores, r2 / refs / decw dword accesses");
+static_assert(offsetof(Lds, recY) % 4 == 0 && offsetof(Lds, recC) % 4 == 0 && 36 % 4 == 0 && 20 % 4 == 0 &&
+              sizeof(((Lds*)0)->recC[0]) % 4 == 0, "recon tile: a row of four samples at x % 4 == 0 is one aligned dword");
+static_assert(kOrgLeaf % 4 == 0 && kOrgStage % 4 == 0, "staged originals are read a dword per row");
+static_assert(1536 % 128 == 0 && 384 % 128 == 0, "park16: a dword never straddles two of its pieces");
+
+// four bytes at byte offset `at` of the reference arrays (any alignment): two aligned dwords and one v_alignbyte
+__device__ __forceinline__ uint32_t refs_load4(int at) {
+    const uint32_t* p = (const uint32_t*)(SH.refs + (at & ~3));
+    return __builtin_amdgcn_alignbyte(p[1], p[0], at & 3);
+}
+__device__ __forceinline__ uint32_t pack4(const int (&v)[4]) {
+    return (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16) | ((uint32_t)v[3] << 24);
+}
+// The four lanes of a quad hold a 4x4 block of bytes by columns (lane j: column j, byte k = row k); returns it by rows
+// (lane j: row j, byte k = column k).  DPP quad broadcasts, no LDS.  All four lanes of the quad must be active.
+__device__ __forceinline__ uint32_t quad_transpose_bytes(uint32_t p, int j) {
+    const uint32_t b0 = (uint32_t)dpp_mov<0x00>((int)p), b1 = (uint32_t)dpp_mov<0x55>((int)p);
+    const uint32_t b2 = (uint32_t)dpp_mov<0xAA>((int)p), b3 = (uint32_t)dpp_mov<0xFF>((int)p);
+    const uint32_t sel = 0x0C0C0400u + (uint32_t)j * 0x0101u; // byte j of the second | of the first operand
+    return __builtin_amdgcn_perm(__builtin_amdgcn_perm(b3, b2, sel), __builtin_amdgcn_perm(b1, b0, sel), 0x05040100u);
+}
+// the originals of four samples of a row (plane index blk of the component, component coordinates; x % 4 == 0):
+// from the staged copy in r2 (blocks <= 16x16), else from the CTU's tile of originals, whose rows are contiguous
+__device__ __forceinline__ uint32_t org_row4(const Ctx& c, int comp, int blk, int x, int y, int obyte, int i, bool lds) {
+    if (lds) return *(const uint32_t*)((const uint8_t*)SH.r2 + obyte + i);
+#ifdef WRENC_EXP_NO_ORG
+    return 0x50607080u + (uint32_t)i;
+#endif
+    return *(const GLOBAL_AS uint32_t*)&c.org[comp == 0 ? y * 32 + x : 1024 + blk * 256 + y * 16 + x];
+}
+// prediction and residual of four samples of a row: i = the first one's index in the layout (block base included)
+__device__ __forceinline__ void emit_row4(const Ctx& c, uint32_t org, uint32_t pred, int i, int pc, int x, int y,
+                                          int to_tile, int nl) {
+    const int d0 = (int)(org & 255u) - (int)(pred & 255u), d1 = (int)((org >> 8) & 255u) - (int)((pred >> 8) & 255u);
+    const int d2 = (int)((org >> 16) & 255u) - (int)((pred >> 16) & 255u), d3 = (int)(org >> 24) - (int)(pred >> 24);
+    uint2 res;
+    res.x = ((uint32_t)d0 & 0xFFFFu) | ((uint32_t)d1 << 16);
+    res.y = ((uint32_t)d2 & 0xFFFFu) | ((uint32_t)d3 << 16);
+    *(uint2*)&SH.r1[i] = res;
+    if (to_tile == PRED_TILE) {
+        rec_put4(pc, x, y, pred);
+    } else if (to_tile == PRED_PARK) {
+        *(uint32_t*)((uint8_t*)SH.decw + kParkByte + i) = pred;
+    } else if (to_tile == PRED_PARK16) {
+        *(uint32_t*)park16(i, nl) = pred;
+    } else {
+        *(uint32_t*)(c.pred_scratch + i) = pred;
+    }
+}
+
+// reconstruction of four samples of a row: pred as i16 + res, clamp (:178); rec[] also gets the samples one by one, and
+// ssd the squared error against the originals added to it
+__device__ __forceinline__ uint32_t recon_row4(uint32_t pred, uint2 res, uint32_t org, int (&rec)[4], unsigned& ssd) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t rw = k < 2 ? res.x : res.y;
+        const int rs = (k & 1) ? (int)rw >> 16 : (int)(int16_t)(rw & 0xFFFFu);
+        int v = (int16_t)((int)((pred >> (8 * k)) & 255u) + rs);
+        v = min(max(v, 0), 255);
+        rec[k] = v;
+        const int d = v - (int)((org >> (8 * k)) & 255u);
+        ssd += (unsigned)M24(d, d);
+    }
+    return pack4(rec);
+}
+
+// What a mode asks of an angular prediction (intra_predictor.rs:1287-1310, 355-372); lg = log2 size of the block
+struct AngPar {
+    int angle, inv_angle;
+    int kind;         // PDPC variant (intra_predictor.rs:355-757): 0 none, 1 mode 18 / 50, 2 mode < 18, 3 mode > 50
+    int n_scale;
+    bool filter_flag; // luma: the smoothing filter instead of the cubic one
+    bool vertical;
+};
+__device__ __forceinline__ AngPar ang_params(const Ctx& c, int mode, int lg) {
+    AngPar p;
+    const int at = c.k->ang_tab[mode];
+    p.angle = (int)(int16_t)(at & 0xFFFF);
+    p.inv_angle = at >> 16;
+    p.vertical = mode >= 34;
+    p.filter_flag = false;
+    if (!(mode == 2 || mode == 34 || mode == 66)) {
+        const int md = min(abs(mode - 50), abs(mode - 18));
+        const int thr = lg == 2 ? 24 : (lg == 3 ? 14 : (lg == 4 ? 2 : 0));
+        p.filter_flag = md > thr;
+    }
+    if (mode > 50 || mode < 18)
+        p.n_scale = min(lg - ilog2i(3 * p.inv_angle - 2) + 8, 2);
+    else
+        p.n_scale = (2 * lg - 2) >> 2;
+    p.kind = 0;
+    if (mode == 18 || mode == 50)
+        p.kind = 1;
+    else if (mode < 18 && p.n_scale >= 0)
+        p.kind = 2;
+    else if (mode > 50 && p.n_scale >= 0)
+        p.kind = 3;
+    return p;
+}
+// Entry ee of a block's projected main reference (intra_predictor.rs:1311-1420): entry idx = ee - n in [-n, 2n + 3] =
+// ref[idx] of the reference's refx / refy arrays: idx >= 0 reads the main side (0 = corner, k = sample k - 1, clamped to
+// 2n), idx < 0 the side array at the inverse-angle projection.  As a byte XOR 0x80 (ref - 128 as a signed byte): the
+// filters run as one v_dot4_i32_i8 over four packed taps, see sad_list_angular.  oL / oA: the block's left (index 0 =
+// corner) and above references in Lds::refs.
+__device__ __forceinline__ uint8_t ang_table_entry(const AngPar& p, int n, int ee, int oL, int oA) {
+    const int idx = ee - n;
+    const int k = idx >= 0 ? min(idx, 2 * n) : max(min((M24(idx, p.inv_angle) + 256) >> 9, n), 0);
+    const bool from_above = (idx >= 0) == p.vertical;
+    // k == 0 is the corner (L[0]); above sample k - 1 = A[k - 1], left sample k - 1 = L[k]
+    return (uint8_t)(SH.refs[k == 0 ? oL : (from_above ? oA + k - 1 : oL + k)] ^ 0x80);
+}
+// Four angular samples next to each other ACROSS the prediction direction, packed: line `along` (a row y for the
+// vertical modes, a column x for the horizontal ones), samples c0 .. c0 + 3 of it.  tab: the block's projected main
+// reference (dword-aligned).  The four share the projection (i_idx, i_fact), the filter word and one 7-byte window of the
+// table.  PDPC weighs by the position across the direction and is over after 3 << n_scale samples; its reference runs
+// along it: left[] = L + 1 for the vertical modes, above[] = A (as rows_per_lane of sad_list_angular).
+__device__ __forceinline__ uint32_t ang_row4(const AngPar& p, bool luma, const uint8_t* tab, int n, int oL, int oA,
+                                             int along, int c0) {
+    const int pr = M24(along + 1, p.angle);
+    const int i_idx = pr >> 5, i_fact = pr & 31;
+    const int ta = n + c0 + i_idx; // the four samples' taps = ref[ta + k + 0..3]
+    const uint32_t* tp = (const uint32_t*)(tab + (ta & ~3));
+    const uint32_t w0 = tp[0], w1 = tp[1], w2 = tp[2];
+    const uint32_t lo = __builtin_amdgcn_alignbyte(w1, w0, ta & 3), hi = __builtin_amdgcn_alignbyte(w2, w1, ta & 3);
+    const int wgt = luma ? (p.filter_flag ? 0x00102010 + (i_fact >> 1) * 0x0100FEFF : *(const int*)&SHT.fc[i_fact][0])
+                         : (((32 - i_fact) << 8) | (i_fact << 16));
+    int v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int taps = (int)(k == 0 ? lo : __builtin_amdgcn_alignbyte(hi, lo, k));
+        if (luma) // (chroma: i_fact == 0 gives the second tap itself; a convex combination of 8-bit samples needs no clamp)
+            v[k] = min(max(__builtin_amdgcn_sdot4(wgt, taps, 8192 + 32, false) >> 6, 0), 255);
+        else
+            v[k] = __builtin_amdgcn_sdot4(wgt, taps, 4096 + 16, false) >> 5;
+    }
+    if (p.kind != 0) {
+        const bool pdpc = c0 < (3 << p.n_scale);
+        const int side = p.vertical ? oL + 1 : oA;
+        const int alrs = SH.refs[oL];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int wp = pdpc ? pdpc_w(p.n_scale, c0 + k) : 0;
+            const int dk = p.kind == 1 ? 0 : ((M24(c0 + k + 1, p.inv_angle) + 256) >> 9);
+            const int sv = SH.refs[side + (pdpc ? along + dk : 0)];
+            const int rs = p.kind == 1 ? (int)(int16_t)(sv - alrs + v[k]) : sv;
+            const int pv = (int16_t)(M24(rs, wp) + M24(64 - wp, v[k]) + 32) >> 6;
+            v[k] = min(max(pv, 0), 255);
+        }
+    }
+    return pack4(v);
+}
+// Four PLANAR or DC samples of row y, x0 .. x0 + 3, packed (dcv: the block's DC value): A[x0 .. x0 + 3] as one dword,
+// L[y + 1] once for the row
+__device__ __forceinline__ uint32_t planar_dc_row4(int mode, int lg, int oL, int oA, int x0, int y, int dcv) {
+    const int n = 1 << lg;
+    const int n_scale = (2 * lg - 2) >> 2;
+    const uint32_t a4 = refs_load4(oA + x0);
+    const int ly = SH.refs[oL + y + 1];
+    const int lb = SH.refs[oL + n + 1], an = SH.refs[oA + n];
+    const int wt = pdpc_w(n_scale, y);
+    int v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int x = x0 + k;
+        const int ax = (int)((a4 >> (8 * k)) & 255u);
+        int p = dcv;
+        if (mode == PLANAR) {
+            const int pv = M24(n - 1 - y, ax) + M24(y + 1, lb);
+            const int ph = M24(n - 1 - x, ly) + M24(x + 1, an);
+            p = ((pv + ph + n) >> (lg + 1)) & 0xFF;
+        }
+        const int wl = pdpc_w(n_scale, x);
+        p = (int16_t)(M24(ly, wl) + M24(ax, wt) + M24(64 - wt - wl, p) + 32) >> 6;
+        v[k] = min(max(p, 0), 255);
+    }
+    return pack4(v);
+}
+
+// Prediction of a FULL candidate: one luma block (comp 0) or the Cb+Cr pair (comp 1), the arithmetic and the results of
+// predict_sad(), organised as the SAD lists' rows_per_lane: a lane takes four samples that lie next to each other ACROSS
+// the prediction direction, so i_idx / i_fact, the filter word, one 7-byte window of the projected references and the
+// PDPC weights are derived once for the four.  The four lanes of a quad hold one 4x4 block of samples: lane j its row j
+// for the vertical modes (and PLANAR, DC, CCLM), its COLUMN j for the horizontal ones, which the quad then transposes
+// in registers (quad_transpose_bytes) -- so every lane ends with a row: one dword of originals in, one dword of
+// prediction and eight bytes of residual out (emit_row4), row-major where fwd_dct_lg reads them.
+// nb n^2 / 4 rows: one pass of the wave up to a 16x16 luma block, two for the 16x16 chroma pair, four for 32x32 luma.
+constexpr int kAngTabByte = 1280, kAngTabStride = 104; // the projected main reference: byte offset in r2 (below kOrgLeaf), stride per block
+__device__ __forceinline__ void predict_full(Ctx c, int comp, int tx, int ty, int tlg, int mode, int rbase = 0,
+                                             int to_tile = PRED_TILE, int nl = 0, CclmPick pick = CclmPick{}) {
+#ifdef WRENC_EXP_SKIP_PRED // instruction-count experiment only (profiles/r04_issue_model.md): nothing predicted
+    return;
+#endif
+    c = uni(c);
+    rbase = uni(rbase);
+    to_tile = uni(to_tile);
+    nl = uni(nl);
+    comp = uni(comp);
+    tx = uni(tx);
+    ty = uni(ty);
+    tlg = uni(tlg);
+    mode = uni(mode);
+    const int cs = comp ? 1 : 0;
+    const int nb = comp ? 2 : 1;
+    const int lg = tlg - cs;
+    const int n = 1 << lg;
+    const int cx = tx >> cs, cy = ty >> cs;
+    const int obyte = org_byte(comp, tlg);
+    const bool olds = tlg <= 4;
+    const int lgb = lg - 2;              // 4x4 blocks per side, log2
+    const int rows = nb << (2 * lg - 2); // rows of four (a power of two, at least 4: quads are whole)
+    const int lane = LANE;
+    const int j = lane & 3;
+    const bool cclm = mode >= LT_CCLM;
+    const bool ang = mode >= 2 && !cclm;
+    // luma blocks of more than 32 samples use the filtered references for modes 0, 2, 34, 66
+    const bool filt = comp == 0 && n * n > 32 && (mode == 0 || mode == 2 || mode == 34 || mode == 66);
+    const int oL0 = comp == 0 ? (filt ? R_LF : R_L0) : R_LC0; // index 0 = corner
+    const int oA0 = comp == 0 ? (filt ? R_AF : R_A0) : R_AC0;
+    // ---- per mode, in front of the rows ----
+    CclmPick cp = pick;
+    int dcv0 = 0, dcv1 = 0;
+    AngPar ap = {};
+    uint8_t* rm = (uint8_t*)SH.r2 + kAngTabByte;
+    if (cclm) {
+        // (pick: the parameters are at hand from the block's CCLM SAD list, sad_list_cclm)
+        if (!pick.have) cp = cclm_pick(cclm_params(c, tx, ty, tlg, mode), 0);
+    } else if (mode == DC) {
+        int part0 = 0, part1 = 0;
+        for (int t = lane; t < 2 * n; t += 64) {
+            part0 += t < n ? SH.refs[oA0 + t] : SH.refs[oL0 + t - n + 1];
+            if (nb == 2) part1 += t < n ? SH.refs[R_AC1 + t] : SH.refs[R_LC1 + t - n + 1];
+        }
+        dcv0 = ((wave_sum_i32(part0) + n) >> (lg + 1)) & 0xFF; // `as u8`
+        if (nb == 2) dcv1 = ((wave_sum_i32(part1) + n) >> (lg + 1)) & 0xFF;
+    } else if (ang) {
+        // angular 2..66 (intra_predictor.rs:1287-1602), square blocks: the main reference of the mode, projected once.  It
+        // lives in r2 (no transform runs during a prediction), so a row's taps are consecutive LDS reads with no selects.
+        ap = ang_params(c, mode, lg);
+        const int ne = 3 * n + 4;
+        for (int e = lane; e < nb * ne; e += 64) {
+            const int blk = e >= ne ? 1 : 0;
+            const int ee = e - blk * ne;
+            rm[blk * kAngTabStride + ee] = ang_table_entry(ap, n, ee, blk ? R_LC1 : oL0, blk ? R_AC1 : oA0);
+        }
+        WSYNC();
+    }
+    const bool vertical = !ang || ap.vertical;
+    // ---- the rows ----
+#pragma unroll 1
+    for (int base = 0; base < rows; base += 64) {
+        const bool on = base + lane < rows;
+        const int t = (base + lane) & (rows - 1); // (a lane beyond the rows repeats one of them and stores nothing)
+        const int blk = t >> (2 * lg - 2);
+        const int bq = (t >> 2) & ((1 << (2 * lgb)) - 1);
+        const int x0 = 4 * (bq & ((1 << lgb) - 1)), y0 = 4 * (bq >> lgb);
+        const int y = y0 + j;                        // the row this lane stores: samples x0 .. x0 + 3 of it
+        const int i = (blk << (2 * lg)) + (y << lg) + x0;
+        const uint32_t org = org_row4(c, comp, blk, cx + x0, cy + y, obyte, i, olds); // issued early
+        const int oL = blk ? R_LC1 : oL0, oA = blk ? R_AC1 : oA0;
+        uint32_t packed;
+        if (cclm) {
+            int v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (cp.flat128) {
+                    v[k] = 128;
+                } else {
+                    const int ds = cclm_ds6(c, tx, ty, 2 * y, 2 * (x0 + k), cp.avail_l);
+                    const int m = (M24(ds, blk ? cp.a1 : cp.a0) >> (blk ? cp.k1 : cp.k0)) + (blk ? cp.b1 : cp.b0);
+                    v[k] = min(max(m, 0), 255);
+                }
+            }
+            packed = pack4(v);
+        } else if (!ang) {
+            packed = planar_dc_row4(mode, lg, oL, oA, x0, y, blk ? dcv1 : dcv0);
+        } else {
+            // along / across the prediction direction: this lane's line is `along`, its samples c0 .. c0 + 3 of it
+            packed = ang_row4(ap, comp == 0, rm + blk * kAngTabStride, n, oL, oA, (vertical ? y0 : x0) + j, vertical ? x0 : y0);
+            if (!vertical) packed = quad_transpose_bytes(packed, j);
+        }
+        if (on) emit_row4(c, org, packed, rbase + i, comp + blk, cx + x0, cy + y, to_tile, nl);
+    }
+    WSYNC();
+}
+
+// The luma blocks of an 8x8 pack's candidates SIDE BY SIDE (dev_search.h, pack8_eval): candidate cd = lanes 16 cd ..
+// 16 cd + 15, the mode per lane (PLANAR, DC or 2..66; a candidate of kNoMode rides along as zeros), each lane one row of
+// four samples exactly as in predict_full -- a block of 64 samples is 16 rows, so one candidate alone would leave
+// three quarters of the wave idle.  Prediction bytes to the pack's park (PRED_PARK), residuals against the leaf's staged
+// originals to r1[64 cd ..]; the projected main reference of an angular candidate is built by the candidate's own 16
+// lanes (28 bytes, stride 32, where predict_full keeps its table).  build_refs(c, 0, ..) must have run.
+static_assert(kAngTabByte % 4 == 0 && kAngTabByte + 4 * 32 <= kOrgLeaf, "the tables of a pack's candidates end below the leaf's originals");
+__device__ __forceinline__ void predict_pack8_luma(const Ctx& c, int nc, int m0, int m1, int m2) {
+#ifdef WRENC_EXP_SKIP_PRED
+    return;
+#endif
+    constexpr int lg = 3, n = 8;
+    const int lane = LANE;
+    const int cd = lane >> 4, t = lane & 15, j = lane & 3;
+    const int mode = cd == 0 ? m0 : (cd == 1 ? m1 : (cd == 2 ? m2 : kNoMode));
+    const bool in = cd < nc;
+    const bool on = in && mode != kNoMode;
+    const bool ang = on && mode >= 2;
+    // a block of 64 samples uses the filtered references for modes 0, 2, 34, 66
+    const bool filt = mode == 0 || mode == 2 || mode == 34 || mode == 66;
+    const int oL = filt ? R_LF : R_L0, oA = filt ? R_AF : R_A0;
+    uint8_t* rm = (uint8_t*)SH.r2 + kAngTabByte + 32 * cd;
+    AngPar ap = ang_params(c, ang ? mode : 2, lg);
+    if (ang) {
+        rm[t] = ang_table_entry(ap, n, t, oL, oA);
+        if (t < 3 * n + 4 - 16) rm[16 + t] = ang_table_entry(ap, n, 16 + t, oL, oA);
+    }
+    WSYNC();
+    // DC value of the candidate: its 16 lanes read the 8 samples above and the 8 to the left, one each
+    const int dcv = ((row_sum_i32(SH.refs[t < n ? oA + t : oL + t - n + 1]) + n) >> (lg + 1)) & 0xFF; // `as u8`
+    const int bq = t >> 2;
+    const int x0 = 4 * (bq & 1), y0 = 4 * (bq >> 1);
+    const int y = y0 + j;
+    const int i = (y << lg) + x0;
+    const uint32_t org = *(const uint32_t*)((const uint8_t*)SH.r2 + kOrgLeaf + i);
+    const bool vertical = !ang || ap.vertical;
+    uint32_t packed = 0;
+    if (ang)
+        packed = ang_row4(ap, true, rm, n, oL, oA, (vertical ? y0 : x0) + j, vertical ? x0 : y0);
+    else if (on)
+        packed = planar_dc_row4(mode, lg, oL, oA, x0, y, dcv);
+    const uint32_t turned = quad_transpose_bytes(packed, j); // (every lane: the four lanes of a quad share their candidate)
+    if (!vertical) packed = turned;
+    if (in) emit_row4(c, on ? org : 0u, packed, 64 * cd + i, 0, 0, 0, PRED_PARK, 0);
+    WSYNC();
+}
+
 // Prediction of up to four CANDIDATES of one 4x4 luma block at once (the packed 4x4 leaf search, dev_search.h
 // leaf4_search): candidate s = lanes 16 s .. 16 s + 15, lane = (s, sample); `mode` is the lane's candidate mode
-// (PLANAR, DC or 2..66; kNoMode lanes compute nothing).  Same arithmetic as predict() for comp 0, tlg 2 (a block of
+// (PLANAR, DC or 2..66; kNoMode lanes compute nothing).  Same arithmetic as predict_full for comp 0, tlg 2 (a block of
 // 16 samples never uses the filtered references); the projected main reference of an angular candidate is built
 // by the candidate's own 16 lanes into tab4 (16 bytes per candidate, in r2 below kOrgLeaf).  build_refs(c, 0, ..)
 // must have run.  Returns the predicted sample.
@@ -587,7 +904,7 @@ __device__ __forceinline__ int predict4_lane(const Ctx& c, int mode, int pl = -1
         angle = (int)(int16_t)(at & 0xFFFF);
         inv_angle = at >> 16;
         vertical = mode >= 34;
-        // entry ee of the candidate's table = ref[ee - n] (intra_predictor.rs:1311-1420), see predict()
+        // entry ee of the candidate's table = ref[ee - n] (intra_predictor.rs:1311-1420), see predict_full
         const int idx = i - n;
         const int k = idx >= 0 ? min(idx, 2 * n) : max(min((M24(idx, inv_angle) + 256) >> 9, n), 0);
         const bool from_above = (idx >= 0) == vertical;
@@ -710,10 +1027,8 @@ __device__ __forceinline__ unsigned sad_list_cclm(const Ctx& c, int tx, int ty, 
     return LANE == 0 ? t0 : (LANE == 1 ? t1 : (LANE == 2 ? t2 : 0u));
 }
 
-constexpr int kNoMode = 255; // list entry that is not evaluated (cost f32::MAX)
-
 // SADs of a LIST of angular modes (2..66) of one block: get_intra_pred_aux_cost of each entry
-// (block_splitter.rs:64-108), luma block and/or chroma pair.  Same arithmetic as predict<false>,
+// (block_splitter.rs:64-108), luma block and/or chroma pair.  Same arithmetic as predict_sad,
 // organised so that the per-mode fixed work is done once per list:
 //   * lane mi derives the parameters of entry mi (angle, inverse angle, filter / PDPC variant);
 //     the uniform loop over the entries fetches them with v_readlane;

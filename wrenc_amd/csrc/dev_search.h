@@ -119,9 +119,11 @@ __device__ __forceinline__ unsigned checksum_weight(int i) { return (2u * (unsig
 __device__ __forceinline__ unsigned tile_checksum(int comp, int cx, int cy, int lg) {
     const int n = 1 << lg, nn = n * n, nb = comp ? 2 : 1;
     unsigned h = 0;
-    for (int i = LANE; i < nb * nn; i += 64) {
+    for (int i = 4 * LANE; i < nb * nn; i += 256) { // a row of four samples per lane: one dword of the tile
         const int blk = i >> (2 * lg), ii = i & (nn - 1);
-        h += (unsigned)rec_get(comp + blk, cx + (ii & (n - 1)), cy + (ii >> lg)) * checksum_weight(i);
+        const uint32_t w = rec_get4(comp + blk, cx + (ii & (n - 1)), cy + (ii >> lg));
+#pragma unroll
+        for (int k = 0; k < 4; ++k) h += ((w >> (8 * k)) & 255u) * checksum_weight(i + k);
     }
     return (unsigned)wave_sum_i32((int)h);
 }
@@ -143,9 +145,10 @@ __device__ __forceinline__ void full_front(const Ctx& c, const Req& q, int comp,
     }
     PROF_MARK(t0_);
     PROF_ADD2(PH_REFS, tr0_, t0_);
-    predict<true>(c, comp, q.tx, q.ty, q.tlg, mode, rbase, PRED_TILE, 0, pick);
+    predict_full(c, comp, q.tx, q.ty, q.tlg, mode, rbase, PRED_TILE, 0, pick);
     PROF_MARK(t1_);
     PROF_ADD2(PH_PREDICT, t0_, t1_);
+    PROF_ADD2(PH_PRED + (mode >= LT_CCLM ? 5 : (q.tlg == 5 ? 0 : (q.tlg == 4 ? 1 : 6))), t0_, t1_);
     fwd_dct_lg(c, lg, nb, rbase);
     PROF_MARK(t2_);
     PROF_ADD2(PH_FDCT, t1_, t2_);
@@ -202,17 +205,18 @@ __device__ __forceinline__ uint32_t full_back(const Ctx& c, const PicBufs& pb, c
     PROF_ADD2(PH_IDCT, t4_, t5_);
     unsigned int part = 0;
     unsigned hs = 0;
-    for (int i = LANE; i < nb * nn; i += 64) {
+    for (int i = 4 * LANE; i < nb * nn; i += 256) { // a row of four samples per lane (recon_row4)
         const int blk = i >> (2 * lg), ii = i & (nn - 1);
         const int x = ii & (n - 1), y = ii >> lg;
         const int pc = comp + blk;
-        const int pred = rec_get(pc, cx + x, cy + y);
-        int v = (int16_t)(pred + (int)SH.r1[rbase + i]); // pred as i16 + res, clamp (:178)
-        v = min(max(v, 0), 255);
-        if (q.final) hs += (unsigned)v * checksum_weight(i);
-        rec_put(pc, cx + x, cy + y, v);
-        const int d = v - (olds ? (int)((const uint8_t*)SH.r2)[obyte + i] : org_get(c, pc, cx + x, cy + y));
-        part += (unsigned)M24(d, d);
+        const uint32_t org = org_row4(c, comp, blk, cx + x, cy + y, obyte, i, olds);
+        int v[4];
+        const uint32_t rec = recon_row4(rec_get4(pc, cx + x, cy + y), *(const uint2*)&SH.r1[rbase + i], org, v, part);
+        if (q.final) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) hs += (unsigned)v[k] * checksum_weight(i + k);
+        }
+        rec_put4(pc, cx + x, cy + y, rec);
     }
     const uint32_t ssd = (uint32_t)wave_sum_i32((int)part); // <= 1024 * 255^2: fits 32 bits
     if (q.final) { // the block's reconstruction must be what the search left in the tile (tile_checksum, full_front)
@@ -222,6 +226,7 @@ __device__ __forceinline__ uint32_t full_back(const Ctx& c, const PicBufs& pb, c
     WSYNC();
     PROF_MARK(t6_);
     PROF_ADD2(PH_RECON, t5_, t6_);
+    PROF_ADD2(PH_REC + 0, t5_, t6_);
     return ssd;
 }
 
@@ -589,7 +594,7 @@ __device__ __forceinline__ Res evaluate(const Ctx& c, const PicBufs& pb, const R
         r.vmin = smin == kNoSad ? 3.40282347e+38f : uni_f((float)smin);
     } else { // K_SADLIST: the chroma pair under the CCLM mode q.mc
         PROF_MARK(tp0_);
-        const unsigned sad = (unsigned)wave_sum_i32(predict<false>(c, 1, q.tx, q.ty, q.tlg, q.mc));
+        const unsigned sad = (unsigned)wave_sum_i32(predict_sad(c, 1, q.tx, q.ty, q.tlg, q.mc));
         PROF_MARK(tp1_);
         PROF_ADD2(PH_PSZ + ((q.tlg - 2) * 2 + 1), tp0_, tp1_);
         PROF_ADD2(PH_PCNT + ((q.tlg - 2) * 2 + 1), 0, 1);
@@ -599,6 +604,7 @@ __device__ __forceinline__ Res evaluate(const Ctx& c, const PicBufs& pb, const R
     }
     PROF_MARK(t1_);
     PROF_ADD2(PH_PREDICT, t0_, t1_);
+    PROF_ADD2(PH_PRED + 7, t0_, t1_);
     return r;
 }
 
@@ -820,6 +826,7 @@ __device__ __forceinline__ Pass4Out pass4_reg(const Ctx& c, int nb, bool on, int
     o.row_ssd = row_sum_i32(on ? M24(d, d) : 0);
     PROF_MARK(t5_);
     PROF_ADD2(PH_RECON, t4_, t5_);
+    PROF_ADD2(PH_REC + 3, t4_, t5_);
     return o;
 }
 
@@ -839,6 +846,7 @@ __device__ __forceinline__ Pack4Out pack4_eval(const Ctx& c, const Req& q, int n
     const int org = ((const uint8_t*)SH.r2)[kOrgLeaf + i];
     PROF_MARK(t1_);
     PROF_ADD2(PH_PREDICT, t0_, t1_);
+    PROF_ADD2(PH_PRED + 4, t0_, t1_);
     const Pass4Out p = pass4_reg(c, nb, on, v, org, overflow);
     PROF_MARK(t5_);
 #pragma unroll
@@ -850,6 +858,7 @@ __device__ __forceinline__ Pack4Out pack4_eval(const Ctx& c, const Req& q, int n
     WSYNC();
     PROF_MARK(t6_);
     PROF_ADD2(PH_RECON, t5_, t6_); // (the pass's PH_RECON ends at the row sums)
+    PROF_ADD2(PH_REC + 3, t5_, t6_);
     return o;
 }
 
@@ -1067,6 +1076,7 @@ __device__ __forceinline__ Res leafc4_search(const Ctx& c, const Req& q, int* ov
     const int org = ((const uint8_t*)SH.r2)[kOrgLeaf + 256 + 16 * pl + i];
     PROF_MARK(t1_);
     PROF_ADD2(PH_PREDICT, t0_, t1_);
+    PROF_ADD2(PH_PRED + 5, t0_, t1_);
     const Pass4Out p = pass4_reg(c, 4, true, v, org, overflow);
     EvalParts ec, ed;
     ec.ssd_y = ed.ssd_y = 0;
@@ -1128,17 +1138,8 @@ __device__ __forceinline__ Pack8Out pack8_eval(const Ctx& c, const Req& q, int n
     uint8_t* park = (uint8_t*)SH.decw + kParkByte;
     const uint8_t* org = (const uint8_t*)SH.r2 + kOrgLeaf;
     PROF_MARK(t0_);
-    // luma: one pass per candidate (a candidate outside 2..66 rides along as a zero block)
-#pragma unroll 1
-    for (int cd = 0; cd < nc; ++cd) {
-        const int mode = cd == 0 ? m0 : (cd == 1 ? m1 : m2);
-        if (mode != kNoMode) {
-            predict<true>(c, 0, q.tx, q.ty, 3, mode, 64 * cd, PRED_PARK);
-        } else {
-            SH.r1[64 * cd + lane] = 0;
-            park[64 * cd + lane] = 0;
-        }
-    }
+    predict_pack8_luma(c, nc, m0, m1, m2); // luma: the candidates side by side, one pass
+    PROF_MARK(tl_);
     // chroma: the 4x4 blocks of all candidates, four to a pass (row = block 2 cand + plane)
 #pragma unroll 1
     for (int ps = 0; ps < 2; ++ps) {
@@ -1161,6 +1162,8 @@ __device__ __forceinline__ Pack8Out pack8_eval(const Ctx& c, const Req& q, int n
     }
     PROF_MARK(t1_);
     PROF_ADD2(PH_PREDICT, t0_, t1_);
+    PROF_ADD2(PH_PRED + 3, t0_, tl_);
+    PROF_ADD2(PH_PRED + 4, tl_, t1_);
     fwd_dct_lg(c, 3, nc, 0);
     PROF_MARK(t2_);
     PROF_ADD2(PH_FDCT, t1_, t2_);
@@ -1214,6 +1217,7 @@ __device__ __forceinline__ Pack8Out pack8_eval(const Ctx& c, const Req& q, int n
     WSYNC();
     PROF_MARK(t5_);
     PROF_ADD2(PH_RECON, t4_, t5_);
+    PROF_ADD2(PH_REC + 2, t4_, t5_);
     return o;
 }
 
@@ -1331,6 +1335,7 @@ __device__ __forceinline__ Res leaf8_search(const Ctx& c, const Req& q, int* ove
     const int org = ((const uint8_t*)SH.r2)[kOrgLeaf + 256 + 16 * pl + i];
     PROF_MARK(t1_);
     PROF_ADD2(PH_PREDICT, t0_, t1_);
+    PROF_ADD2(PH_PRED + 5, t0_, t1_);
     const Pass4Out p = pass4_reg(c, 2, mine, v, org, overflow);
     EvalParts e = eb;
     e.ssd_c = (uint32_t)(__builtin_amdgcn_readlane(p.row_ssd, 0) + __builtin_amdgcn_readlane(p.row_ssd, 16));
@@ -1384,18 +1389,17 @@ struct Pack16Out {
     uint32_t ssd_y[2], ssd_c[2];
     long long lvl_y[3], lvl_c[3];
 };
-__device__ __forceinline__ Pack16Out pack16_eval(const Ctx& c, const Req& q, int nc, int m0, int m1, int* overflow) {
-    Pack16Out o;
+// predictions and residuals of the pack's nc candidates, luma block and chroma pair: prediction bytes to park16,
+// residuals to r1 in the same layout (luma [cand][256], then chroma [cand][Cb | Cr][64])
+__device__ __forceinline__ void pack16_predict(const Ctx& c, int tx, int ty, int nc, int m0, int m1) {
     const int lane = lane_fresh();
     const int nL = 256 * nc;
-    const uint8_t* org = (const uint8_t*)SH.r2 + kOrgLeaf; // luma 256 | Cb 64 | Cr 64
-    PROF_MARK(t0_);
 #pragma unroll 1
     for (int cd = 0; cd < nc; ++cd) {
         const int mode = cd == 0 ? m0 : m1;
         if (mode != kNoMode) {
-            predict<true>(c, 0, q.tx, q.ty, 4, mode, 256 * cd, PRED_PARK16, nL);
-            predict<true>(c, 1, q.tx, q.ty, 4, mode, nL + 128 * cd, PRED_PARK16, nL);
+            predict_full(c, 0, tx, ty, 4, mode, 256 * cd, PRED_PARK16, nL);
+            predict_full(c, 1, tx, ty, 4, mode, nL + 128 * cd, PRED_PARK16, nL);
         } else { // a candidate outside 2..66 rides along as a zero block
             for (int i = lane; i < 256; i += 64) {
                 SH.r1[256 * cd + i] = 0;
@@ -1408,8 +1412,17 @@ __device__ __forceinline__ Pack16Out pack16_eval(const Ctx& c, const Req& q, int
             WSYNC();
         }
     }
+}
+__device__ __forceinline__ Pack16Out pack16_eval(const Ctx& c, const Req& q, int nc, int m0, int m1, int* overflow) {
+    Pack16Out o;
+    const int lane = lane_fresh();
+    const int nL = 256 * nc;
+    const uint8_t* org = (const uint8_t*)SH.r2 + kOrgLeaf; // luma 256 | Cb 64 | Cr 64
+    PROF_MARK(t0_);
+    pack16_predict(c, q.tx, q.ty, nc, m0, m1);
     PROF_MARK(t1_);
     PROF_ADD2(PH_PREDICT, t0_, t1_);
+    PROF_ADD2(PH_PRED + 2, t0_, t1_);
     fwd_dct_lg(c, 4, nc, 0);
     fwd_dct_lg(c, 3, 2 * nc, nL);
     PROF_MARK(t2_);
@@ -1432,34 +1445,27 @@ __device__ __forceinline__ Pack16Out pack16_eval(const Ctx& c, const Req& q, int
         o.ssd_y[cd] = 0;
         o.ssd_c[cd] = 0;
         if (cd < nc) {
-            int py = 0, pc = 0;
-#pragma unroll
-            for (int kq = 0; kq < 4; ++kq) {
-                const int i = lane + 64 * kq;
-                uint8_t* pk = park16(256 * cd + i, nL);
-                int rec = (int16_t)((int)*pk + (int)SH.r1[256 * cd + i]); // pred as i16 + res, clamp (:178)
-                rec = min(max(rec, 0), 255);
-                *pk = (uint8_t)rec;
-                const int d = rec - (int)org[i];
-                py += M24(d, d);
+            // a row of four samples per lane (recon_row4): the luma block is one pass of the wave, the chroma pair half of one
+            unsigned py = 0, pc = 0;
+            int v[4];
+            {
+                const int i = 4 * lane;
+                uint32_t* pk = (uint32_t*)park16(256 * cd + i, nL);
+                *pk = recon_row4(*pk, *(const uint2*)&SH.r1[256 * cd + i], *(const uint32_t*)(org + i), v, py);
             }
-#pragma unroll
-            for (int kq = 0; kq < 2; ++kq) {
-                const int i = lane + 64 * kq;
-                uint8_t* pk = park16(nL + 128 * cd + i, nL);
-                int rec = (int16_t)((int)*pk + (int)SH.r1[nL + 128 * cd + i]);
-                rec = min(max(rec, 0), 255);
-                *pk = (uint8_t)rec;
-                const int d = rec - (int)org[256 + i];
-                pc += M24(d, d);
+            if (lane < 32) {
+                const int i = 4 * lane;
+                uint32_t* pk = (uint32_t*)park16(nL + 128 * cd + i, nL);
+                *pk = recon_row4(*pk, *(const uint2*)&SH.r1[nL + 128 * cd + i], *(const uint32_t*)(org + 256 + i), v, pc);
             }
-            o.ssd_y[cd] = (uint32_t)wave_sum_i32(py);
-            o.ssd_c[cd] = (uint32_t)wave_sum_i32(pc);
+            o.ssd_y[cd] = (uint32_t)wave_sum_i32((int)py);
+            o.ssd_c[cd] = (uint32_t)wave_sum_i32((int)pc);
         }
     }
     WSYNC();
     PROF_MARK(t5_);
     PROF_ADD2(PH_RECON, t4_, t5_);
+    PROF_ADD2(PH_REC + 1, t4_, t5_);
     return o;
 }
 

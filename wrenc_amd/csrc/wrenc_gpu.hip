@@ -471,6 +471,13 @@ __global__ __launch_bounds__(64) void test_dequantize_kernel(const DevConst* __r
 // comp 3 + comps (comps: bit 0 luma, bit 1 the chroma pair): a SAD LIST (sad_list_angular) of the block against its own samples
 // in the planes as "originals"; mode = m0 | entries << 8 | stride << 16, entry j = m0 + j * stride (kNoMode beyond 66); the
 // output is the 16 accumulators of lanes 0..15 (u32 each); comp 7: the CCLM SAD list of the chroma pair (mode 0), same output
+// comp 8 / 9: a FULL candidate (predict_full) of the luma block / the chroma pair into the recon tile, residuals against the
+// block's own samples in the planes as originals (a CTU tile of originals is staged for c.org, and stage_org_leaf runs for
+// blocks <= 16x16, as in the search); comp 10: the luma part of an 8x8 pack (predict_pack8_luma) into PRED_PARK, mode =
+// m0 | m1 << 8 | m2 << 16 | candidates << 24; comp 11: a 16x16 pack, luma and chroma pair (pack16_predict), into
+// PRED_PARK16, mode = m0 | m1 << 8 | candidates << 24 (a candidate mode of 255 = kNoMode rides along as zeros).  The output
+// is the prediction bytes read back from the destination, in the layout of the destination, then the i16 residuals of r1.
+constexpr int kTestPredictScratch = 1024 + kOrgTile; // per item: PRED_SCRATCH | the CTU's tile of originals
 __global__ __launch_bounds__(64) void test_predict_kernel(const DevConst* __restrict__ k, const uint8_t* planes,
                                                           const int* items, uint8_t* scratch, uint8_t* out) {
     const int* it = items + 6 * blockIdx.x;
@@ -480,7 +487,7 @@ __global__ __launch_bounds__(64) void test_predict_kernel(const DevConst* __rest
     c.org = (const GLOBAL_AS uint8_t*)planes; // residuals are computed against these and ignored
     c.W = k->W;
     c.WH = k->W * k->H;
-    c.pred_scratch = scratch + (size_t)blockIdx.x * 1024;
+    c.pred_scratch = scratch + (size_t)blockIdx.x * kTestPredictScratch;
     c.ctu_x = x & ~31;
     c.ctu_y = y & ~31;
     c.write = 1;
@@ -529,7 +536,7 @@ __global__ __launch_bounds__(64) void test_predict_kernel(const DevConst* __rest
         if (LANE < 16) ((uint32_t*)(out + it[5]))[LANE] = acc;
         return;
     }
-    if (comp >= 4) {
+    if (comp >= 4 && comp < 8) {
         const int comps = comp - 3, m0 = mode & 255, nm = (mode >> 8) & 255, stride = mode >> 16;
         // the originals where a SAD list reads them (stage_org / stage_org_leaf's layout): luma, then Cb | Cr
         uint8_t* ol = (uint8_t*)SH.r2 + org_byte(0, tlg);
@@ -554,8 +561,59 @@ __global__ __launch_bounds__(64) void test_predict_kernel(const DevConst* __rest
         if (LANE < 16) ((uint32_t*)(out + it[5]))[LANE] = acc;
         return;
     }
+    if (comp >= 8) {
+        // the CTU's originals as retile_kernel lays them out: Y 32x32 | Cb 16x16 | Cr 16x16 (samples outside the picture: 0)
+        uint8_t* tile = c.pred_scratch + 1024;
+        for (int i = LANE; i < kOrgTile; i += 64) {
+            const int pc = i < 1024 ? 0 : 1 + ((i - 1024) >> 8);
+            const int ii = pc ? (i - 1024) & 255 : i;
+            const int lgw = pc ? 4 : 5;
+            const int gx = (pc ? c.ctu_x >> 1 : c.ctu_x) + (ii & ((1 << lgw) - 1)), gy = (pc ? c.ctu_y >> 1 : c.ctu_y) + (ii >> lgw);
+            const int pw = pc ? Wc : W, ph = pc ? k->H >> 1 : k->H;
+            tile[i] = (gx < pw && gy < ph) ? rec[plane_off(c, pc) + (size_t)gy * pw + gx] : 0;
+        }
+        __threadfence_block();
+        WSYNC();
+        c.org = (const GLOBAL_AS uint8_t*)tile;
+        const int comps = comp == 8 ? 1 : (comp == 9 ? 2 : (comp == 10 ? 1 : 3));
+        if (tlg <= 4) stage_org_leaf(c, comps, tx, ty, tlg);
+        uint8_t* op = out + it[5];
+        if (comp <= 9) {
+            const int cmp = comp - 8;
+            if (mode < LT_CCLM) build_refs(c, cmp, tx, ty, tlg);
+            predict_full(c, cmp, tx, ty, tlg, mode, 0, PRED_TILE);
+            const int lg = tlg - cmp, n = 1 << lg, total = (cmp ? 2 : 1) * n * n;
+            for (int i = LANE; i < total; i += 64) {
+                const int blk = i >> (2 * lg), ii = i & (n * n - 1);
+                op[i] = (uint8_t)rec_get(cmp + blk, (tx >> cmp) + (ii & (n - 1)), (ty >> cmp) + (ii >> lg));
+                ((int16_t*)(op + total))[i] = SH.r1[i];
+            }
+            return;
+        }
+        const int nc = mode >> 24, m0 = mode & 255, m1 = (mode >> 8) & 255, m2 = (mode >> 16) & 255;
+        if (comp == 10) {
+            build_refs(c, 0, tx, ty, 3);
+            predict_pack8_luma(c, nc, m0, m1, m2);
+            WSYNC();
+            const uint8_t* park = (const uint8_t*)SH.decw + kParkByte;
+            for (int i = LANE; i < 64 * nc; i += 64) {
+                op[i] = park[i];
+                ((int16_t*)(op + 64 * nc))[i] = SH.r1[i];
+            }
+            return;
+        }
+        build_refs(c, 0, tx, ty, 4);
+        build_refs(c, 1, tx, ty, 4);
+        pack16_predict(c, tx, ty, nc, m0, m1);
+        WSYNC();
+        for (int i = LANE; i < 384 * nc; i += 64) {
+            op[i] = *park16(i, 256 * nc);
+            ((int16_t*)(op + 384 * nc))[i] = SH.r1[i];
+        }
+        return;
+    }
     if (mode < LT_CCLM) build_refs(c, comp, tx, ty, tlg);
-    predict<true>(c, comp, tx, ty, tlg, mode, 0, false);
+    predict_full(c, comp, tx, ty, tlg, mode, 0, PRED_SCRATCH);
     const int n = 1 << (tlg - (comp ? 1 : 0));
     const int total = (comp ? 2 : 1) * n * n;
     __threadfence_block();
@@ -2555,15 +2613,30 @@ int wrenc_gpu_test_predict(wrenc_gpu_ctx* ctx, const uint8_t* rec_y, const uint8
         const int n = 1 << lg;
         const bool list = comp >= 4 && comp <= 6; // a SAD list: mode = m0 | entries << 8 | stride << 16
         const int m0 = mode & 255, nm = (mode >> 8) & 255, stride = mode >> 16;
-        const bool ok = lg >= 2 && lg <= 5 && x >= 0 && y >= 0 && x + n <= W && y + n <= H && !(x & (n - 1)) && !(y & (n - 1)) &&
-                        (comp == 0 || (comp == 1 && lg >= 3) || (comp == 2 && lg == 2) || (comp == 4) || (list && lg >= 3) ||
-                         (comp == 7 && lg >= 3)) &&
-                        (comp == 7 ? mode == 0 : list ? (mode >= 0 && m0 >= 2 && m0 <= 66 && nm >= 1 && nm <= 16 && stride >= 1 && stride <= 64)
-                              : ((mode >= 0 && mode <= 66) || (comp == 1 && mode >= LT_CCLM && mode <= T_CCLM)));
+        bool ok = lg >= 2 && lg <= 5 && x >= 0 && y >= 0 && x + n <= W && y + n <= H && !(x & (n - 1)) && !(y & (n - 1));
+        const bool pack = comp == 10 || comp == 11; // mode = m0 | m1 << 8 | m2 << 16 | candidates << 24, 255 = kNoMode
+        const int pk_nc = mode >> 24;
+        if (pack) {
+            ok = ok && mode >= 0 && lg == (comp == 10 ? 3 : 4) && pk_nc >= 1 && pk_nc <= (comp == 10 ? 3 : 2);
+            for (int j = 0; ok && j < pk_nc; ++j) {
+                const int m = (mode >> (8 * j)) & 255;
+                ok = m <= 66 || m == kNoMode;
+            }
+        } else if (comp == 8 || comp == 9) {
+            ok = ok && (comp == 8 || lg >= 3) && ((mode >= 0 && mode <= 66) || (comp == 9 && mode >= LT_CCLM && mode <= T_CCLM));
+        } else {
+            ok = ok && (comp == 0 || (comp == 1 && lg >= 3) || (comp == 2 && lg == 2) || (comp == 4) || (list && lg >= 3) ||
+                        (comp == 7 && lg >= 3)) &&
+                 (comp == 7 ? mode == 0 : list ? (mode >= 0 && m0 >= 2 && m0 <= 66 && nm >= 1 && nm <= 16 && stride >= 1 && stride <= 64)
+                       : ((mode >= 0 && mode <= 66) || (comp == 1 && mode >= LT_CCLM && mode <= T_CCLM)));
+        }
         if (!ok) return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_test_predict: bad item");
         int* d = &dev_items[(size_t)i * 6];
         d[0] = x; d[1] = y; d[2] = lg; d[3] = comp; d[4] = mode; d[5] = (int)total;
-        total += (list || comp == 7) ? 64 : (comp == 1 ? (size_t)n * n / 2 : (size_t)n * n);
+        // (the full-candidate items: prediction bytes, then as many i16 residuals)
+        total += (list || comp == 7) ? 64 : comp == 8 ? 3 * (size_t)n * n : comp == 9 ? 3 * (size_t)n * n / 2
+                 : comp == 10 ? 3 * 64 * (size_t)pk_nc : comp == 11 ? 3 * 384 * (size_t)pk_nc
+                 : (comp == 1 ? (size_t)n * n / 2 : (size_t)n * n);
     }
     if (total != out_bytes) return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_test_predict: output size does not match the items");
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
@@ -2571,7 +2644,7 @@ int wrenc_gpu_test_predict(wrenc_gpu_ctx* ctx, const uint8_t* rec_y, const uint8
     uint8_t *d_planes = nullptr, *d_scratch = nullptr, *d_out = nullptr;
     int* d_items = nullptr;
     hipError_t e = hipMalloc((void**)&d_planes, wh + wh / 2);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_scratch, (size_t)n_items * 1024);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_scratch, (size_t)n_items * kTestPredictScratch);
     if (e == hipSuccess) e = hipMalloc((void**)&d_out, total);
     if (e == hipSuccess) e = hipMalloc((void**)&d_items, dev_items.size() * sizeof(int));
     if (e == hipSuccess) e = hipMemcpy(d_planes, rec_y, wh, hipMemcpyHostToDevice);

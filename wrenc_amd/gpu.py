@@ -590,6 +590,55 @@ class Encoder:
             at += sz
         return res
 
+    NO_MODE = 255   # a pack candidate that is not evaluated (dev_predict.h, kNoMode): rides along as zeros
+
+    @staticmethod
+    def pack_modes(modes):
+        """The mode word of a pack item of predict_full_blocks: up to three candidate modes (0..66 or NO_MODE)."""
+        word = len(modes) << 24
+        for j, m in enumerate(modes):
+            word |= int(m) << (8 * j)
+        return word
+
+    def predict_full_blocks(self, rec_y, rec_cb, rec_cr, items):
+        """The search's full-candidate predictor (predict_full: four samples per lane) into each of its destinations, with
+        the block's own samples in the planes as originals.  items: (n, 5) int32 {x, y, log2 luma size, kind, mode}:
+        kind 8: a luma block into the recon tile; 9: the Cb+Cr pair into the tile (mode 0..66 or a CCLM mode);
+        kind 10: the luma blocks of an 8x8 pack of 1..3 candidates into its LDS park, mode = pack_modes([...]);
+        kind 11: a 16x16 pack of 1..2 candidates, luma and chroma pair, into its park.
+        Returns per item (prediction, residual) as read back from the destination and from the residual buffer: uint8 /
+        int16 arrays of shape (n, n) (kind 8), (2, n/2, n/2) (9), (candidates, 8, 8) (10); kind 11: each a pair
+        (luma (candidates, 16, 16), chroma (candidates, 2, 8, 8))."""
+        items = np.ascontiguousarray(items, np.int32).reshape(-1, 5)
+        sizes = []
+        for q in items:
+            nn, kind, nc = (1 << int(q[2])) ** 2, int(q[3]), int(q[4]) >> 24
+            assert kind in (8, 9, 10, 11)
+            sizes.append({8: nn, 9: nn // 2, 10: 64 * nc, 11: 384 * nc}[kind])
+        out = np.zeros(3 * int(sum(sizes)), np.uint8)
+        planes = [np.ascontiguousarray(a, np.uint8) for a in (rec_y, rec_cb, rec_cr)]
+        assert planes[0].shape == (self.height, self.width)
+        self.lib.wrenc_gpu_test_predict.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                    C.c_void_p, C.c_size_t]
+        self._check(self.lib.wrenc_gpu_test_predict(self.ctx, _p(planes[0]), _p(planes[1]), _p(planes[2]), len(items),
+                                                    _p(items), _p(out), out.size))
+        res, at = [], 0
+        for q, sz in zip(items, sizes):
+            n, kind, nc = 1 << int(q[2]), int(q[3]), int(q[4]) >> 24
+            pair = []
+            for arr in (out[at:at + sz], out[at + sz:at + 3 * sz].view(np.int16)):
+                if kind == 8:
+                    pair.append(arr.reshape(n, n))
+                elif kind == 9:
+                    pair.append(arr.reshape(2, n // 2, n // 2))
+                elif kind == 10:
+                    pair.append(arr.reshape(nc, 8, 8))
+                else:
+                    pair.append((arr[:256 * nc].reshape(nc, 16, 16), arr[256 * nc:].reshape(nc, 2, 8, 8)))
+            res.append(tuple(pair))
+            at += 3 * sz
+        return res
+
     def sad_lists(self, rec_y, rec_cb, rec_cr, items):
         """SAD lists (the search's sad_list_angular) of blocks against their own samples in the planes as originals.
         items: (n, 7) {x, y, log2 luma size, comps (1 luma, 2 chroma pair, 3 both), first mode, entries (<= 16), stride};
