@@ -24,6 +24,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "wrenc_format.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -174,6 +176,36 @@ int wrenc_gpu_source_size(const wrenc_gpu_ctx* ctx, int* w, int* h); /* the visi
  * 16); the coefficients sum to 4096.  WRENC_GPU_EINVAL outside the limits (n_out <= 4 n_in, n_in <= 4 n_out, both 1 ..
  * 16384, 0 <= o < n_out) or for a null pointer. */
 int wrenc_gpu_scale_taps(int n_in, int n_out, int o, int* first, int* n_taps, int16_t coef[17]);
+/* Source formats.  A source format says how the caller's pictures lie in memory (wrenc_format.h names the six: yuv420p = 0
+ * the plain behaviour, nv12, yuv420p10le, p010le, yuv422p, yuv422p10le) and wrenc_gpu_upload_planes takes them as they
+ * are: it copies the RAW planes -- 16-bit words, interleaved CbCr, 4:2:2 rows; a 10-bit picture crosses the bus once -- into
+ * raw staging planes on the device (one set per context, pitch a multiple of 32 bytes; allocated when the format is set, or
+ * at the first upload when a size was set after it: WRENC_GPU_ENOMEM from that call when it fails) and a kernel behind the
+ * copies writes planar 8-bit 4:2:0 by the rules of wrenc_format.h, in integers, bit for bit: into the scaler's staging
+ * planes when a source size is set -- conversion comes BEFORE scaling -- else into the visible rectangle of the slot's
+ * planes.  Scaler, padding and everything behind the upload then run as always, on the converted picture: search and
+ * parameter sets stay 8-bit 4:2:0, and wrenc_gpu_download_metrics measures the codec against the CONVERTED (and scaled)
+ * originals, not the conversion.  The planes are those of the context's source size (wrenc_gpu_source_size).
+ * wrenc_gpu_set_source_format: any order with wrenc_gpu_set_visible_size / _set_source_size.  WRENC_GPU_EINVAL for an
+ * unknown format, WRENC_GPU_ESTATE once any slot of the context has been uploaded into.  Format 0 puts the context back to
+ * the plain behaviour; a context on which no format is set launches and allocates nothing it did not before.
+ * wrenc_gpu_upload_planes: plane[p] and stride_bytes[p] as wrenc_gpu_format_layout numbers the planes; a two-plane format
+ * does not read plane[2] and stride_bytes[2].  With format 0 it is wrenc_gpu_upload (which has one stride for both chroma
+ * planes: WRENC_GPU_EINVAL when stride_bytes[1] != stride_bytes[2]).  WRENC_GPU_EINVAL for a null plane that the format
+ * reads, a stride smaller than the plane's row_bytes, and an odd pointer or odd stride with a 16-bit format.  The host
+ * buffers must stay valid as for wrenc_gpu_upload.
+ * While the format is not 0, wrenc_gpu_upload and wrenc_gpu_encode_picture return WRENC_GPU_ESTATE: their uint8_t*
+ * signature cannot say what is meant. */
+int wrenc_gpu_set_source_format(wrenc_gpu_ctx* ctx, int format);
+int wrenc_gpu_source_format(const wrenc_gpu_ctx* ctx); /* the id; 0 when none is set */
+int wrenc_gpu_upload_planes(wrenc_gpu_ctx* ctx, int slot, const void* const plane[3], const size_t stride_bytes[3]);
+/* Host only, callable without a device.  The id of a format's name (as ffmpeg names it) or WRENC_GPU_EINVAL; the name of an
+ * id or NULL; and the layout of a tightly packed w x h frame as it lies in a raw file: planes, bytes per sample, per plane
+ * row_bytes, rows and offset, and frame_bytes.  WRENC_GPU_EINVAL for an unknown format, an odd w or h, w or h below 16, or
+ * a null pointer. */
+int wrenc_gpu_format_from_name(const char* name);
+const char* wrenc_gpu_format_name(int format);
+int wrenc_gpu_format_layout(int format, int w, int h, struct wrenc_gpu_format_layout* out);
 /* Test entry: the coded-size original planes a slot holds (width*height, then (width/2)*(height/2) twice), margin
  * included.  Blocking, behind the copy stream.  WRENC_GPU_ESTATE for a slot never uploaded into. */
 int wrenc_gpu_test_download_originals(wrenc_gpu_ctx* ctx, int slot, uint8_t* y, uint8_t* cb, uint8_t* cr);

@@ -29,4 +29,9 @@ g++ -O1 -g -std=c++17 -ffp-contract=off -mavx2 -fsanitize=address,undefined -fno
 g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined \
     -o "$T/scale_taps" "$R/tools/sanitize/scale_taps.cpp"
 "$T/scale_taps"
+# the source-format converter's kernel body on the host (wrenc_amd/csrc/dev_format.h against include/wrenc_format.h); clang++
+# for the vector types the kernel is written with
+${CLANGXX:-/opt/rocm/lib/llvm/bin/clang++} -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined \
+    -o "$T/format_convert" "$R/tools/sanitize/format_convert.cpp"
+"$T/format_convert"
 rm -rf "$T"

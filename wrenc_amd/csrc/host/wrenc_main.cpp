@@ -19,7 +19,7 @@
 // parameter sets' QP; the bytes depend on the input and the options alone, not on --threads or timing, which is why
 // --ramp-down auto, decided by the clock, runs as never), --metrics PATH (PSNR and SSIM of every picture from sums the
 // device takes of the originals and the reconstruction it holds, wrenc_gpu_download_metrics: a JSON report in the shape of
-// the reference's evaluation harness, and one summary line on stderr), --pad and --scale (below), --verbose, --ramp-down auto|always|never, --tokens auto|on|off
+// the reference's evaluation harness, and one summary line on stderr), --pad, --scale and --input-format (below), --verbose, --ramp-down auto|always|never, --tokens auto|on|off
 // (how a batch comes back.  auto and on: as the residual tokens the device makes of it, wrenc_gpu_download_tokens -- the
 // host then runs the CU-level syntax and the arithmetic coder only, 1.8x less host time per picture, 20x the bytes over
 // PCIe -- and as the compact level record, with residual_coding on the host, when they do not fit the token pool.  off,
@@ -38,6 +38,12 @@
 // --output-size, --metrics reports that size and compares the reconstruction with the SCALED originals, --pad pads the
 // scaled picture, --bitrate measures it.  Without --scale, --input-size is parsed and not used, as in the reference
 // (main.rs:164-174).  --scale with equal sizes changes nothing.
+//
+// --input-format NAME: how the input's frames lie in the file, named as ffmpeg names them (include/wrenc_format.h): yuv420p
+// (the default), nv12, yuv420p10le, p010le, yuv422p, yuv422p10le.  A frame is read as it is -- its size and its planes come
+// from wrenc_gpu_format_layout -- and uploaded as it is (wrenc_gpu_upload_planes); the device converts it to 8-bit 4:2:0
+// behind the copy and in front of the scaler.  Everything else is the run on the converted pictures: --reconst stays 8-bit
+// 4:2:0 of --output-size and --metrics compares the reconstruction with the CONVERTED (and scaled) originals.
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -156,6 +162,7 @@ struct Options {
     bool pad = false;
     bool scale = false;
     int in_w = 0, in_h = 0;    // the size of the input's frames: --input-size with --scale, else vis_w x vis_h
+    int format = 0;            // --input-format: their pixel format (wrenc_format.h), yuv420p unless given
     int depth = 3, batch = 64, n_threads = 8;
     bool verbose = false;
     bool tokens = true; // --tokens auto | on: batches come back as residual tokens; --tokens off, --no-tokens: as the compact record
@@ -221,6 +228,11 @@ Options parse_options(int argc, char** argv) {
         else if (a == "--verbose") o.verbose = true;
         else if (a == "--pad") o.pad = true;
         else if (a == "--scale") o.scale = true;
+        else if (a == "--input-format") {
+            const char* v = val();
+            o.format = wrenc_gpu_format_from_name(v);
+            if (o.format < 0) die("Invalid input-format: %s (yuv420p, nv12, yuv420p10le, p010le, yuv422p, yuv422p10le)", v);
+        }
         else if (a == "--no-tokens") o.tokens = false;
         else if (a == "--ramp-down") { // how a run ends: auto (smaller last batches when the host's tail is heavy), always, never
             const std::string v = val();
@@ -302,19 +314,23 @@ Options parse_options(int argc, char** argv) {
     return o;
 }
 
-// sizes of one picture (8-bit 4:2:0) and of what is read back of it
+// sizes of one picture (8-bit 4:2:0), of a frame of the input (in its own format) and of what is read back of a picture
 struct Geometry {
     int w, h;               // the coded size
     int vw, vh;             // the size of the frames in --reconst (--pad: smaller than the coded size)
     int iw, ih;             // the size of the frames in the input (--scale: --input-size; else vw x vh)
     size_t ysz, csz, pic;   // bytes of luma, of one chroma plane, of the picture
-    size_t iysz, icsz, ipic; // the same of a frame of the input
+    struct wrenc_gpu_format_layout in; // the planes of a frame of the input as it lies in the file (wrenc_gpu_format_layout)
+    size_t ipic;            // ... and its bytes
     size_t n4, maps;        // 4x4 luma blocks; bytes of cu_log2_size | luma_mode | chroma_mode
     size_t mask_words, level_blocks, n_ctus;
-    Geometry(int w_, int h_, int vw_, int vh_, int iw_, int ih_)
-        : w(w_), h(h_), vw(vw_), vh(vh_), iw(iw_), ih(ih_), ysz((size_t)w_ * h_), csz(ysz / 4), pic(ysz + 2 * csz), iysz((size_t)iw_ * ih_),
-          icsz((size_t)(iw_ / 2) * (ih_ / 2)), ipic(iysz + 2 * icsz), n4(ysz / 16), maps(2 * n4 + ysz / 64),
-          mask_words(wrenc_gpu_compact_mask_words(w_, h_)), level_blocks(pic / 16), n_ctus((size_t)(w_ / 32) * (h_ / 32)) {}
+    Geometry(int w_, int h_, int vw_, int vh_, int iw_, int ih_, int format)
+        : w(w_), h(h_), vw(vw_), vh(vh_), iw(iw_), ih(ih_), ysz((size_t)w_ * h_), csz(ysz / 4), pic(ysz + 2 * csz), in(), ipic(0),
+          n4(ysz / 16), maps(2 * n4 + ysz / 64), mask_words(wrenc_gpu_compact_mask_words(w_, h_)), level_blocks(pic / 16),
+          n_ctus((size_t)(w_ / 32) * (h_ / 32)) {
+        if (wrenc_gpu_format_layout(format, iw_, ih_, &in)) die("input frames must be of an even size, at least 16x16: %dx%d", iw_, ih_);
+        ipic = in.frame_bytes;
+    }
 };
 
 struct HostSet { // one (device, slot set) unit: page-locked planes of one batch
@@ -477,8 +493,9 @@ struct Run {
     void upload(HostSet& s, int k) {
         // the slot's QP first: the encode call of the batch reads it (NULL: the context's, --qp)
         if (!o.pic_qp.empty()) gpu_check(s, wrenc_gpu_set_slot_qp(s.ctx, s.base + k, qcfg[(size_t)slice_qp(poc + k)]));
-        uint8_t* p = s.in + g.ipic * k;
-        gpu_check(s, wrenc_gpu_upload(s.ctx, s.base + k, p, p + g.iysz, p + g.iysz + g.icsz, (size_t)g.iw, (size_t)g.iw / 2));
+        const uint8_t* p = s.in + g.ipic * k;
+        const void* const plane[3] = {p + g.in.offset[0], p + g.in.offset[1], p + g.in.offset[2]};
+        gpu_check(s, wrenc_gpu_upload_planes(s.ctx, s.base + k, plane, g.in.row_bytes));
         ++s.count;
     }
 
@@ -735,9 +752,10 @@ int main(int argc, char** argv) {
         if (wrenc_gpu_create(&cfg, &ctx)) fatal("%s", wrenc_gpu_last_error(nullptr)); // no CPU path: fails without an MI355X
         if (o.pad && wrenc_gpu_set_visible_size(ctx, o.vis_w, o.vis_h)) fatal("%s", wrenc_gpu_last_error(ctx));
         if (o.scale && wrenc_gpu_set_source_size(ctx, o.in_w, o.in_h)) fatal("%s", wrenc_gpu_last_error(ctx)); // after the visible size
+        if (o.format && wrenc_gpu_set_source_format(ctx, o.format)) fatal("%s", wrenc_gpu_last_error(ctx));
         ctxs.push_back(ctx);
     }
-    const Geometry g(o.w, o.h, o.vis_w, o.vis_h, o.in_w, o.in_h);
+    const Geometry g(o.w, o.h, o.vis_w, o.vis_h, o.in_w, o.in_h, o.format);
     std::vector<HostSet> units = make_units(o, g, ctxs, per_dev, frec != nullptr);
     size_t hdr_bytes = 0, rate_hdr_bytes = 0;
     {

@@ -11,6 +11,7 @@
 // more regions than workgroups can be resident, see ctu_search_kernel.)
 #include "../../include/wrenc_gpu.h"
 #include "../../include/wrenc_scale.h"
+#include "../../include/wrenc_format.h"
 #include "wrenc_dev.h"
 
 #include <hip/hip_runtime.h>
@@ -739,6 +740,12 @@ struct wrenc_gpu_ctx {
     uint8_t* d_stage = nullptr;
     void* d_scale_tab = nullptr;
     ScaleArgs scale_args = {};
+    // the format of the caller's pictures (wrenc_gpu_set_source_format; 0: planar 8-bit 4:2:0, the plain upload) and the raw
+    // staging planes wrenc_gpu_upload_planes copies them into as they come: one set per context, like the scaler's and by
+    // the same argument, allocated for d_raw_bytes when the format is set or, where the sizes came later, at the first upload
+    int src_format = 0;
+    uint8_t* d_raw = nullptr;
+    size_t d_raw_bytes = 0;
     unsigned long long* d_mismatch = nullptr;
     int* d_overflow = nullptr;
     uint8_t* d_pred_scratch = nullptr; // kScratchSlots x WPB x kWaveScratch: saved reconstructions (dev_search.h copy_block)
@@ -1321,6 +1328,7 @@ void wrenc_gpu_destroy(wrenc_gpu_ctx* ctx) {
     if (ctx->d_xmap) (void)hipFree(ctx->d_xmap);
     if (ctx->d_stage) (void)hipFree(ctx->d_stage);
     if (ctx->d_scale_tab) (void)hipFree(ctx->d_scale_tab);
+    if (ctx->d_raw) (void)hipFree(ctx->d_raw);
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
     if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
@@ -1465,36 +1473,11 @@ int wrenc_gpu_create(const wrenc_gpu_config* cfg, wrenc_gpu_ctx** out) {
     return WRENC_GPU_OK;
 }
 
-int wrenc_gpu_upload(wrenc_gpu_ctx* ctx, int slot, const uint8_t* y, const uint8_t* cb, const uint8_t* cr,
-                     size_t stride_y, size_t stride_c) {
-    if (!ctx) return WRENC_GPU_EINVAL;
-    if (slot < 0 || slot >= ctx->cfg.n_slots || !y || !cb || !cr) return fail(ctx, WRENC_GPU_EINVAL, "bad slot or null plane");
-    const size_t w = ctx->cfg.width, h = ctx->cfg.height;
-    const size_t vw = (size_t)ctx->vis_w, vh = (size_t)ctx->vis_h; // the slot's picture; w x h unless a visible size is set
-    const bool scaling = ctx->src_w != 0;
-    const size_t sw = scaling ? (size_t)ctx->src_w : vw, sh = scaling ? (size_t)ctx->src_h : vh; // the caller's planes
-    if (stride_y < sw || stride_c < sw / 2) return fail(ctx, WRENC_GPU_EINVAL, "stride smaller than row");
-    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+// what every upload ends with, on copy_stream behind whatever wrote the visible rectangle of the slot's planes
+static int finish_upload(wrenc_gpu_ctx* ctx, int slot) {
+    const size_t w = ctx->cfg.width, h = ctx->cfg.height, vw = (size_t)ctx->vis_w, vh = (size_t)ctx->vis_h;
     PicBufs& b = ctx->slots[slot];
-    // the planes may still be read by a search in flight on this slot
-    if (ctx->slot_event[slot]) HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->slot_event[slot], 0));
     hipStream_t cs = ctx->copy_stream;
-    if (scaling) {
-        // Source-size planes into the context's staging planes, then the scaler (dev_scale.h) writes the visible
-        // rectangle of the slot's planes.  Copies, scaler, pad and retile all run on copy_stream, in order: the one set of
-        // staging planes is read out before the next upload's copies reach it, whichever slot that one is for.
-        ScaleArgs a = ctx->scale_args;
-        const uint8_t* const from[3] = {y, cb, cr};
-        for (int p = 0; p < 3; ++p)
-            HIP_TRY(ctx, hipMemcpy2DAsync((void*)a.src[p], (size_t)a.src_pitch[p ? 1 : 0], from[p], p ? stride_c : stride_y,
-                                          p ? sw / 2 : sw, p ? sh / 2 : sh, hipMemcpyHostToDevice, cs));
-        a.dst = (uint8_t*)b.org[0];
-        hipLaunchKernelGGL(scale_kernel, dim3((unsigned)(a.tiles[0] + 2 * a.tiles[1])), dim3(256), 0, cs, a);
-    } else {
-        HIP_TRY(ctx, hipMemcpy2DAsync((void*)b.org[0], w, y, stride_y, vw, vh, hipMemcpyHostToDevice, cs));
-        HIP_TRY(ctx, hipMemcpy2DAsync((void*)b.org[1], w / 2, cb, stride_c, vw / 2, vh / 2, hipMemcpyHostToDevice, cs));
-        HIP_TRY(ctx, hipMemcpy2DAsync((void*)b.org[2], w / 2, cr, stride_c, vw / 2, vh / 2, hipMemcpyHostToDevice, cs));
-    }
     // a picture smaller than the coded size: its last column and row replicated into the margin of the three planes
     // (dev_pad.h), behind the copies and in front of the tiling
     if (vw != w || vh != h) {
@@ -1510,6 +1493,44 @@ int wrenc_gpu_upload(wrenc_gpu_ctx* ctx, int slot, const uint8_t* y, const uint8
     ctx->any_upload = true;
     ctx->state[slot] = 1;
     return WRENC_GPU_OK;
+}
+
+int wrenc_gpu_upload(wrenc_gpu_ctx* ctx, int slot, const uint8_t* y, const uint8_t* cb, const uint8_t* cr,
+                     size_t stride_y, size_t stride_c) {
+    if (!ctx) return WRENC_GPU_EINVAL;
+    if (slot < 0 || slot >= ctx->cfg.n_slots || !y || !cb || !cr) return fail(ctx, WRENC_GPU_EINVAL, "bad slot or null plane");
+    if (ctx->src_format) return fail(ctx, WRENC_GPU_ESTATE, "a source format is set: the planes go through wrenc_gpu_upload_planes");
+    const size_t w = ctx->cfg.width, h = ctx->cfg.height;
+    const size_t vw = (size_t)ctx->vis_w, vh = (size_t)ctx->vis_h; // the slot's picture; w x h unless a visible size is set
+    const bool scaling = ctx->src_w != 0;
+    const size_t sw = scaling ? (size_t)ctx->src_w : vw, sh = scaling ? (size_t)ctx->src_h : vh; // the caller's planes
+    if (stride_y < sw || stride_c < sw / 2) return fail(ctx, WRENC_GPU_EINVAL, "stride smaller than row");
+    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+    PicBufs& b = ctx->slots[slot];
+    // the planes may still be read by a search in flight on this slot
+    if (ctx->slot_event[slot]) HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->slot_event[slot], 0));
+    hipStream_t cs = ctx->copy_stream;
+    if (scaling) {
+        // Source-size planes into the context's staging planes, then the scaler (dev_scale.h) writes the visible
+        // rectangle of the slot's planes.  Copies, scaler, pad and retile all run on copy_stream, in order: the one set of
+        // staging planes is read out before the next upload's copies reach it, whichever slot that one is for.  The
+        // same holds one step earlier on a context with a source format (wrenc_gpu_upload_planes below): raw copies,
+        // converter, scaler, pad and retile are one chain on this stream, so the one set of raw staging planes has been
+        // converted out of, and the scaler's planes -- which the converter then writes in place of the copies -- scaled
+        // out of, before the next upload's first copy starts.
+        ScaleArgs a = ctx->scale_args;
+        const uint8_t* const from[3] = {y, cb, cr};
+        for (int p = 0; p < 3; ++p)
+            HIP_TRY(ctx, hipMemcpy2DAsync((void*)a.src[p], (size_t)a.src_pitch[p ? 1 : 0], from[p], p ? stride_c : stride_y,
+                                          p ? sw / 2 : sw, p ? sh / 2 : sh, hipMemcpyHostToDevice, cs));
+        a.dst = (uint8_t*)b.org[0];
+        hipLaunchKernelGGL(scale_kernel, dim3((unsigned)(a.tiles[0] + 2 * a.tiles[1])), dim3(256), 0, cs, a);
+    } else {
+        HIP_TRY(ctx, hipMemcpy2DAsync((void*)b.org[0], w, y, stride_y, vw, vh, hipMemcpyHostToDevice, cs));
+        HIP_TRY(ctx, hipMemcpy2DAsync((void*)b.org[1], w / 2, cb, stride_c, vw / 2, vh / 2, hipMemcpyHostToDevice, cs));
+        HIP_TRY(ctx, hipMemcpy2DAsync((void*)b.org[2], w / 2, cr, stride_c, vw / 2, vh / 2, hipMemcpyHostToDevice, cs));
+    }
+    return finish_upload(ctx, slot);
 }
 
 int wrenc_gpu_set_visible_size(wrenc_gpu_ctx* ctx, int vis_w, int vis_h) {
@@ -1668,6 +1689,148 @@ int wrenc_gpu_source_size(const wrenc_gpu_ctx* ctx, int* w, int* h) {
     *w = ctx->src_w ? ctx->src_w : ctx->vis_w;
     *h = ctx->src_w ? ctx->src_h : ctx->vis_h;
     return WRENC_GPU_OK;
+}
+
+int wrenc_gpu_format_from_name(const char* name) {
+    const int f = wrenc_format_from_name(name);
+    return f < 0 ? WRENC_GPU_EINVAL : f;
+}
+
+const char* wrenc_gpu_format_name(int format) { return wrenc_format_name(format); }
+
+int wrenc_gpu_format_layout(int format, int w, int h, struct wrenc_gpu_format_layout* out) {
+    return wrenc_format_layout(format, w, h, out) ? WRENC_GPU_EINVAL : WRENC_GPU_OK;
+}
+
+namespace {
+
+// the raw staging planes of the context's format at its source size: pitches, offsets and the bytes of the allocation
+struct RawStage {
+    struct wrenc_gpu_format_layout lay;
+    size_t pitch[3], off[3], bytes;
+};
+
+bool raw_stage(const wrenc_gpu_ctx* ctx, int format, RawStage& r) {
+    const int sw = ctx->src_w ? ctx->src_w : ctx->vis_w, sh = ctx->src_w ? ctx->src_h : ctx->vis_h;
+    if (wrenc_format_layout(format, sw, sh, &r.lay)) return false;
+    r.bytes = 0;
+    for (int p = 0; p < 3; ++p) {
+        r.pitch[p] = format_raw_pitch(r.lay.row_bytes[p]);
+        r.off[p] = r.bytes;
+        r.bytes += r.pitch[p] * r.lay.rows[p];
+    }
+    return true;
+}
+
+// d_raw holds r.bytes: allocated here when it does not (the format, or a size, has changed since)
+int ensure_raw_stage(wrenc_gpu_ctx* ctx, const RawStage& r) {
+    if (ctx->d_raw && ctx->d_raw_bytes == r.bytes) return WRENC_GPU_OK;
+    if (ctx->d_raw) (void)hipFree(ctx->d_raw);
+    ctx->d_raw = nullptr;
+    ctx->d_raw_bytes = 0;
+    const hipError_t e = hipMalloc((void**)&ctx->d_raw, r.bytes);
+    if (e != hipSuccess) {
+        ctx->d_raw = nullptr;
+        return fail(ctx, e == hipErrorOutOfMemory ? WRENC_GPU_ENOMEM : WRENC_GPU_EHIP, std::string("raw staging planes: ") + hipGetErrorString(e));
+    }
+    ctx->d_raw_bytes = r.bytes;
+    return WRENC_GPU_OK;
+}
+
+} // namespace
+
+int wrenc_gpu_set_source_format(wrenc_gpu_ctx* ctx, int format) {
+    if (!ctx) return WRENC_GPU_EINVAL;
+    if (!wrenc_format_valid(format)) return fail(ctx, WRENC_GPU_EINVAL, "unknown source format");
+    if (ctx->any_upload) return fail(ctx, WRENC_GPU_ESTATE, "the source format must be set before the first upload");
+    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+    if (format == WRENC_FORMAT_YUV420P) {
+        if (ctx->d_raw) (void)hipFree(ctx->d_raw);
+        ctx->d_raw = nullptr;
+        ctx->d_raw_bytes = 0;
+        ctx->src_format = 0;
+        return WRENC_GPU_OK;
+    }
+    RawStage r;
+    if (!raw_stage(ctx, format, r)) return fail(ctx, WRENC_GPU_EINVAL, "the source format needs pictures of an even size, at least 16x16");
+    const int rc = ensure_raw_stage(ctx, r);
+    if (rc) return rc;
+    ctx->src_format = format;
+    return WRENC_GPU_OK;
+}
+
+int wrenc_gpu_source_format(const wrenc_gpu_ctx* ctx) { return ctx ? ctx->src_format : WRENC_GPU_EINVAL; }
+
+int wrenc_gpu_upload_planes(wrenc_gpu_ctx* ctx, int slot, const void* const plane[3], const size_t stride_bytes[3]) {
+    if (!ctx) return WRENC_GPU_EINVAL;
+    if (!plane || !stride_bytes) return fail(ctx, WRENC_GPU_EINVAL, "null plane or stride list");
+    const int format = ctx->src_format;
+    if (format == WRENC_FORMAT_YUV420P) {
+        if (stride_bytes[1] != stride_bytes[2]) return fail(ctx, WRENC_GPU_EINVAL, "yuv420p: the two chroma planes share one stride");
+        return wrenc_gpu_upload(ctx, slot, (const uint8_t*)plane[0], (const uint8_t*)plane[1], (const uint8_t*)plane[2], stride_bytes[0],
+                                stride_bytes[1]);
+    }
+    if (slot < 0 || slot >= ctx->cfg.n_slots) return fail(ctx, WRENC_GPU_EINVAL, "bad slot or null plane");
+    RawStage r;
+    if (!raw_stage(ctx, format, r)) return fail(ctx, WRENC_GPU_EINVAL, "the source format needs pictures of an even size, at least 16x16");
+    for (int p = 0; p < r.lay.n_planes; ++p) {
+        if (!plane[p]) return fail(ctx, WRENC_GPU_EINVAL, "bad slot or null plane");
+        if (stride_bytes[p] < r.lay.row_bytes[p]) return fail(ctx, WRENC_GPU_EINVAL, "stride smaller than row");
+        if (r.lay.bytes_per_sample == 2 && (((uintptr_t)plane[p] | stride_bytes[p]) & 1))
+            return fail(ctx, WRENC_GPU_EINVAL, "a 16-bit format needs even plane addresses and strides");
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+    const int rc = ensure_raw_stage(ctx, r);
+    if (rc) return rc;
+    const bool scaling = ctx->src_w != 0;
+    const size_t w = ctx->cfg.width, h = ctx->cfg.height;
+    PicBufs& b = ctx->slots[slot];
+    // the planes may still be read by a search in flight on this slot
+    if (ctx->slot_event[slot]) HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->slot_event[slot], 0));
+    hipStream_t cs = ctx->copy_stream;
+    // the caller's bytes as they are -- a 10-bit picture crosses the bus once -- and behind them the converter (dev_format.h)
+    FormatArgs a = {};
+    a.raw = ctx->d_raw;
+    for (int p = 0; p < r.lay.n_planes; ++p) {
+        HIP_TRY(ctx, hipMemcpy2DAsync((void*)(ctx->d_raw + r.off[p]), r.pitch[p], plane[p], stride_bytes[p], r.lay.row_bytes[p], r.lay.rows[p],
+                                      hipMemcpyHostToDevice, cs));
+        a.raw_off[p] = r.off[p];
+        a.raw_pitch[p] = (int)r.pitch[p];
+    }
+    if (scaling) { // into the scaler's staging planes, in the place of wrenc_gpu_upload's copies
+        const ScaleArgs& s = ctx->scale_args;
+        a.dst = ctx->d_stage;
+        for (int p = 0; p < 3; ++p) a.dst_off[p] = (size_t)(s.src[p] - s.src[0]);
+        a.dst_pitch[0] = s.src_pitch[0];
+        a.dst_pitch[1] = s.src_pitch[1];
+        a.w = ctx->src_w;
+        a.h = ctx->src_h;
+    } else { // into the visible rectangle of the slot's planes
+        a.dst = (uint8_t*)b.org[0];
+        a.dst_off[1] = w * h;
+        a.dst_off[2] = w * h + w * h / 4;
+        a.dst_pitch[0] = (int)w;
+        a.dst_pitch[1] = (int)(w / 2);
+        a.w = ctx->vis_w;
+        a.h = ctx->vis_h;
+    }
+    a.row_blocks[0] = (a.h + kFormatRows - 1) / kFormatRows;
+    a.row_blocks[1] = (a.h / 2 + kFormatRows - 1) / kFormatRows;
+    const dim3 grid((unsigned)((a.w + 64 * kFormatGroup - 1) / (64 * kFormatGroup)),
+                    (unsigned)(a.row_blocks[0] + (r.lay.n_planes == 2 ? 1 : 2) * a.row_blocks[1])), block(64, kFormatRows);
+    switch (format) {
+    case WRENC_FORMAT_NV12: hipLaunchKernelGGL(convert_format_kernel<WRENC_FORMAT_NV12>, grid, block, 0, cs, a); break;
+    case WRENC_FORMAT_YUV420P10LE: hipLaunchKernelGGL(convert_format_kernel<WRENC_FORMAT_YUV420P10LE>, grid, block, 0, cs, a); break;
+    case WRENC_FORMAT_P010LE: hipLaunchKernelGGL(convert_format_kernel<WRENC_FORMAT_P010LE>, grid, block, 0, cs, a); break;
+    case WRENC_FORMAT_YUV422P: hipLaunchKernelGGL(convert_format_kernel<WRENC_FORMAT_YUV422P>, grid, block, 0, cs, a); break;
+    default: hipLaunchKernelGGL(convert_format_kernel<WRENC_FORMAT_YUV422P10LE>, grid, block, 0, cs, a); break;
+    }
+    if (scaling) {
+        ScaleArgs s = ctx->scale_args;
+        s.dst = (uint8_t*)b.org[0];
+        hipLaunchKernelGGL(scale_kernel, dim3((unsigned)(s.tiles[0] + 2 * s.tiles[1])), dim3(256), 0, cs, s);
+    }
+    return finish_upload(ctx, slot);
 }
 
 int wrenc_gpu_test_download_originals(wrenc_gpu_ctx* ctx, int slot, uint8_t* y, uint8_t* cb, uint8_t* cr) {

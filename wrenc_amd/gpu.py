@@ -25,6 +25,8 @@ EXPORTED_SYMBOLS = [
     "wrenc_gpu_test_dequantize", "wrenc_gpu_test_predict", "wrenc_gpu_test_fwd_dct32", "wrenc_gpu_test_inv_dct32", "wrenc_gpu_test_quantize_p16", "wrenc_gpu_test_quantize_pk", "wrenc_gpu_test_fwd_dct4_reg", "wrenc_gpu_test_inv_dct4_reg", "wrenc_gpu_test_set_wave_slots", "wrenc_gpu_test_scratch_overflows", "wrenc_gpu_test_head_ranges", "wrenc_gpu_test_avail_tab",
     "wrenc_gpu_set_visible_size", "wrenc_gpu_visible_size", "wrenc_gpu_test_download_originals",
     "wrenc_gpu_set_source_size", "wrenc_gpu_source_size", "wrenc_gpu_scale_taps",
+    "wrenc_gpu_set_source_format", "wrenc_gpu_source_format", "wrenc_gpu_upload_planes",
+    "wrenc_gpu_format_from_name", "wrenc_gpu_format_name", "wrenc_gpu_format_layout",
 ]
 
 
@@ -94,6 +96,49 @@ def scale_taps(n_in, n_out, o):
     if rc:
         raise WrencGpuError(rc, "scale_taps(%d, %d, %d)" % (n_in, n_out, o))
     return first.value, list(coef[:n.value])
+
+
+class FormatLayout(C.Structure):
+    _fields_ = [("n_planes", C.c_int), ("bytes_per_sample", C.c_int), ("row_bytes", C.c_size_t * 3), ("rows", C.c_size_t * 3),
+                ("offset", C.c_size_t * 3), ("frame_bytes", C.c_size_t)]
+
+
+def format_from_name(name):
+    """wrenc_gpu_format_from_name (host only): the id of a source format named as ffmpeg names it (include/wrenc_format.h);
+    WrencGpuError for an unknown name."""
+    lib = load_library()
+    lib.wrenc_gpu_format_from_name.argtypes = [C.c_char_p]
+    rc = lib.wrenc_gpu_format_from_name(name.encode() if name is not None else None)
+    if rc < 0:
+        raise WrencGpuError(rc, "format_from_name(%r)" % (name,))
+    return rc
+
+
+def format_name(fmt):
+    """wrenc_gpu_format_name (host only): the name of a format id, None for an unknown one."""
+    lib = load_library()
+    lib.wrenc_gpu_format_name.argtypes = [C.c_int]
+    lib.wrenc_gpu_format_name.restype = C.c_char_p
+    name = lib.wrenc_gpu_format_name(int(fmt))
+    return name.decode() if name is not None else None
+
+
+def _format_id(fmt):
+    return format_from_name(fmt) if isinstance(fmt, str) else int(fmt)
+
+
+def format_layout(fmt, w, h):
+    """wrenc_gpu_format_layout (host only): a tightly packed w x h frame of format `fmt` (an id or a name) as it lies in a raw
+    file: {"n_planes", "bytes_per_sample", "row_bytes", "rows", "offset" (a list per plane), "frame_bytes"}."""
+    lib = load_library()
+    out = FormatLayout()
+    lib.wrenc_gpu_format_layout.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
+    rc = lib.wrenc_gpu_format_layout(_format_id(fmt), int(w), int(h), C.byref(out))
+    if rc:
+        raise WrencGpuError(rc, "format_layout(%r, %d, %d)" % (fmt, w, h))
+    n = out.n_planes
+    return {"n_planes": n, "bytes_per_sample": out.bytes_per_sample, "row_bytes": list(out.row_bytes[:n]), "rows": list(out.rows[:n]),
+            "offset": list(out.offset[:n]), "frame_bytes": out.frame_bytes}
 
 
 class WrencGpuError(RuntimeError):
@@ -180,12 +225,14 @@ class Encoder:
     SliceEncoder::encode uses in place of the per-CTU split_ct loop."""
 
     def __init__(self, width, height, qp=26, max_split_depth=3, device=0, n_slots=1, config=None, extra_params=None,
-                 schedule=None, visible=None, source=None):
+                 schedule=None, visible=None, source=None, source_format=None):
         """width x height: the coded size, whole 32x32 CTUs.  visible=(w, h): the pictures are that size (even, at least
         16x16, the coded size its round-up to multiples of 32): upload takes planes of it, the device replicates their last
         column and row into the margin, and download_metrics reports that rectangle (wrenc_gpu_set_visible_size).
         source=(w, h): the pictures are THAT size and the device resamples them to the visible size (the coded size when
-        none is given) in front of everything else (wrenc_gpu_set_source_size)."""
+        none is given) in front of everything else (wrenc_gpu_set_source_size).
+        source_format: an id or a name of include/wrenc_format.h; the pictures come in that format through upload_planes and
+        the device converts them to 8-bit 4:2:0 first of all (wrenc_gpu_set_source_format)."""
         self.lib = load_library()
         self.cfg = config if config is not None else default_config(width, height, qp, max_split_depth,
                                                                      device, n_slots, extra_params)
@@ -211,6 +258,12 @@ class Encoder:
         if source is not None:
             try:
                 self.set_source_size(*source)
+            except WrencGpuError:
+                self.close()
+                raise
+        if source_format is not None:
+            try:
+                self.set_source_format(source_format)
             except WrencGpuError:
                 self.close()
                 raise
@@ -253,6 +306,27 @@ class Encoder:
         self._keep[slot] = tuple(planes)
         self._check(self.lib.wrenc_gpu_upload(self.ctx, slot, _p(planes[0]), _p(planes[1]), _p(planes[2]),
                                               planes[0].strides[0], planes[1].strides[0]))
+
+    def set_source_format(self, fmt):
+        """wrenc_gpu_set_source_format (an id or a name): before the first upload; 0 / "yuv420p" restores the plain behaviour."""
+        self.lib.wrenc_gpu_set_source_format.argtypes = [C.c_void_p, C.c_int]
+        self._check(self.lib.wrenc_gpu_set_source_format(self.ctx, _format_id(fmt)))
+
+    def source_format(self):
+        self.lib.wrenc_gpu_source_format.argtypes = [C.c_void_p]
+        return self.lib.wrenc_gpu_source_format(self.ctx)
+
+    def upload_planes(self, slot, planes):
+        """wrenc_gpu_upload_planes: the planes of the context's source format at its source size, numpy uint8 / uint16 arrays
+        (rows x samples; an interleaved CbCr plane rows x 2 * pairs), possibly views into wider arrays (last axis
+        contiguous): their own row strides go to the C ABI."""
+        planes = tuple(np.asarray(a) for a in planes)
+        assert 2 <= len(planes) <= 3 and all(a.ndim == 2 and a.dtype in (np.uint8, np.uint16) and a.strides[1] == a.itemsize for a in planes)
+        self._keep[slot] = planes  # host buffers must outlive the async copy
+        ptr = (C.c_void_p * 3)(*[a.ctypes.data for a in planes])
+        stride = (C.c_size_t * 3)(*[a.strides[0] for a in planes])
+        self.lib.wrenc_gpu_upload_planes.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        self._check(self.lib.wrenc_gpu_upload_planes(self.ctx, slot, ptr, stride))
 
     def set_visible_size(self, vis_w, vis_h):
         """wrenc_gpu_set_visible_size: before the first upload; the coded size itself restores the plain behaviour."""
