@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "wrenc_format.h"
+#include "wrenc_hash.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -350,6 +351,27 @@ void wrenc_gpu_metrics_values(int width, int height, const wrenc_gpu_metrics* m,
  * ssim_map[p] (may be NULL) receives the plane's per-window f32 values in raster order. */
 int wrenc_gpu_test_metrics(wrenc_gpu_ctx* ctx, const uint8_t* const org[3], const uint8_t* const rec[3],
                            wrenc_gpu_metrics* out, float* const ssim_map[3]);
+
+/* Hash read-back: the decoded picture hash (H.274 decoded picture hash SEI; the three definitions are in wrenc_hash.h) of
+ * what the search made of a slot, without the planes crossing the bus: 48 bytes a picture.  A device pass behind the
+ * search reads the slot's reconstruction once -- the coded planes, margin included on a context with a visible size, as a
+ * decoder hashes the picture before the conformance window crops it -- and leaves the three components' values as the SEI
+ * carries them (include/wrenc_bitstream_hash.h frames the message).  hash_type: WRENC_HASH_MD5, _CRC or _CHECKSUM.
+ * Checksum and CRC are parallel passes at about memory rate; MD5 is a serial chain per plane and runs as one lane per
+ * (picture, plane): it takes as long as the largest plane needs, however many pictures the call has.
+ * n slots in one call; blocking; runs on a stream of its own (made at the first call) behind the encode call that searched
+ * the slots and nothing queued later, so it delays neither the search of other slots nor uploads.  WRENC_GPU_ESTATE
+ * unless every slot is in the encoded state, WRENC_GPU_EINVAL for a bad range or an unknown hash_type.  Changes nothing in
+ * the slot.  The same planes give the same bytes in any slot, any batch size and any run. */
+int wrenc_gpu_download_hashes(wrenc_gpu_ctx* ctx, int first_slot, int n, int hash_type, wrenc_picture_hash* out);
+
+/* Measurement: the device time of the kernels of the last wrenc_gpu_download_hashes call, from HIP events around them on
+ * the pass's stream.  Taken only in measurement mode (wrenc_gpu_stats_enable); WRENC_GPU_ESTATE when the last call was
+ * not timed. */
+int wrenc_gpu_last_hash_ms(wrenc_gpu_ctx* ctx, float* ms);
+
+/* Test entry: the same kernels on an arbitrary picture of the context's size (host planes Y, Cb, Cr), no search involved. */
+int wrenc_gpu_test_hash(wrenc_gpu_ctx* ctx, const uint8_t* const rec[3], int hash_type, wrenc_picture_hash* out);
 
 /* Page-locked host memory for the planes handed to wrenc_gpu_upload / wrenc_gpu_download: transfers from
  * and to it run at PCIe rate and truly asynchronously (pageable buffers are staged by the runtime at a

@@ -19,8 +19,13 @@ EXPORTED_QP_SYMBOLS = ("wrenc_bs_write_picture_qp", "wrenc_bs_write_picture_toke
 EXPORTED_WINDOW_SYMBOLS = ("wrenc_bs_write_parameter_sets_window",)
 # rate control (include/wrenc_rate.h; the Python mirror is wrenc_amd/rate.py)
 EXPORTED_RATE_SYMBOLS = ("wrenc_rate_prior", "wrenc_rate_create", "wrenc_rate_destroy", "wrenc_rate_choose", "wrenc_rate_report")
+# decoded picture hash SEI (include/wrenc_bitstream_hash.h)
+EXPORTED_HASH_SYMBOLS = ("wrenc_bs_picture_hash", "wrenc_bs_write_hash_sei")
 
 OK, EINVAL, ENOSPC, EDATA = 0, -1, -2, -3
+HASH_MD5, HASH_CRC, HASH_CHECKSUM = 0, 1, 2   # include/wrenc_hash.h
+HASH_TYPES = {"md5": HASH_MD5, "crc": HASH_CRC, "checksum": HASH_CHECKSUM}
+HASH_VALUE_BYTES = {HASH_MD5: 16, HASH_CRC: 2, HASH_CHECKSUM: 4}
 
 
 class BitstreamError(RuntimeError):
@@ -161,6 +166,54 @@ def write_picture_tokens_qp(width, height, pps_qp, slice_qp, poc, pool, pic):
     w, h = int(width), int(height)
     t, _keep = _tokens(w, h, pool, pic)
     return _write("wrenc_bs_write_picture_tokens_qp", (pps_qp, slice_qp), w, h, poc, t, _Tokens)
+
+
+def _hash_id(hash_type):
+    return HASH_TYPES[hash_type] if isinstance(hash_type, str) else int(hash_type)
+
+
+def picture_hash(width, height, hash_type, y, cb, cr):
+    """wrenc_bs_picture_hash: the decoded picture hash of planes in host memory (the coded size), as the three components'
+    values [Y, Cb, Cr], each the bytes the SEI carries (MD5 16, CRC 2, checksum 4, big-endian).  hash_type: an id of
+    include/wrenc_hash.h or "md5" / "crc" / "checksum"."""
+    lib = load_library()
+    w, h, t = int(width), int(height), _hash_id(hash_type)
+    planes = [np.ascontiguousarray(a, np.uint8) for a in (y, cb, cr)]
+    if w > 0 and h > 0 and [a.shape for a in planes] != [(h, w), (h // 2, w // 2), (h // 2, w // 2)]:
+        raise ValueError("planes of %r do not make a %dx%d picture" % ([a.shape for a in planes], w, h))
+    out = (C.c_uint8 * 48)()
+    lib.wrenc_bs_picture_hash.restype = C.c_int
+    lib.wrenc_bs_picture_hash.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    rc = lib.wrenc_bs_picture_hash(w, h, t, planes[0].ctypes.data, planes[1].ctypes.data, planes[2].ctypes.data, out)
+    if rc != OK:
+        raise BitstreamError(rc, "wrenc_bs_picture_hash")
+    raw = bytes(out)
+    assert not any(raw[16 * p + HASH_VALUE_BYTES[t]:16 * p + 16].strip(b"\x00") for p in range(3))
+    return [raw[16 * p:16 * p + HASH_VALUE_BYTES[t]] for p in range(3)]
+
+
+def write_hash_sei(hash_type, values):
+    """wrenc_bs_write_hash_sei: the SUFFIX_SEI NAL unit (bytes) that carries the three components' values [Y, Cb, Cr] (as
+    picture_hash returns them, or a 48-byte wrenc_picture_hash such as gpu.PictureHash); it goes directly behind the
+    picture's slice NAL unit."""
+    lib = load_library()
+    t = _hash_id(hash_type)
+    rec = (C.c_uint8 * 48)()
+    if isinstance(values, (list, tuple)):
+        for p, v in enumerate(values):
+            if len(v) > 16:
+                raise ValueError("a component's value has at most 16 bytes")
+            rec[16 * p:16 * p + len(v)] = list(v)
+    else:
+        rec[:] = list(bytes(values))
+    lib.wrenc_bs_write_hash_sei.restype = C.c_int
+    lib.wrenc_bs_write_hash_sei.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    buf = np.zeros(128, np.uint8)
+    n = C.c_size_t()
+    rc = lib.wrenc_bs_write_hash_sei(t, rec, buf.ctypes.data, buf.size, C.byref(n))
+    if rc != OK:
+        raise BitstreamError(rc, "wrenc_bs_write_hash_sei")
+    return buf[:n.value].tobytes()
 
 
 def last_slice_data_bits():

@@ -56,7 +56,7 @@ void write_pps(BitWriter& bw, int width, int height, int qp);
 void write_picture_header(BitWriter& bw, int poc);
 void write_slice_header(BitWriter& bw, int slice_qp, int pps_qp);
 
-enum NalType { NAL_IDR_W_RADL = 7, NAL_VPS = 14, NAL_SPS = 15, NAL_PPS = 16, NAL_PH = 19 };
+enum NalType { NAL_IDR_W_RADL = 7, NAL_VPS = 14, NAL_SPS = 15, NAL_PPS = 16, NAL_PH = 19, NAL_SUFFIX_SEI = 24 };
 
 // nal.rs:186-298: 00 00 00 00 00 01, two header bytes, payload with the reference's emulation prevention
 void append_nal(std::vector<uint8_t>& out, int layer_id, NalType type, int temporal_id,

@@ -19,7 +19,7 @@
 // parameter sets' QP; the bytes depend on the input and the options alone, not on --threads or timing, which is why
 // --ramp-down auto, decided by the clock, runs as never), --metrics PATH (PSNR and SSIM of every picture from sums the
 // device takes of the originals and the reconstruction it holds, wrenc_gpu_download_metrics: a JSON report in the shape of
-// the reference's evaluation harness, and one summary line on stderr), --pad, --scale and --input-format (below), --verbose, --ramp-down auto|always|never, --tokens auto|on|off
+// the reference's evaluation harness, and one summary line on stderr), --pad, --scale, --input-format and --hash (below), --verbose, --ramp-down auto|always|never, --tokens auto|on|off
 // (how a batch comes back.  auto and on: as the residual tokens the device makes of it, wrenc_gpu_download_tokens -- the
 // host then runs the CU-level syntax and the arithmetic coder only, 1.8x less host time per picture, 20x the bytes over
 // PCIe -- and as the compact level record, with residual_coding on the host, when they do not fit the token pool.  off,
@@ -44,6 +44,12 @@
 // from wrenc_gpu_format_layout -- and uploaded as it is (wrenc_gpu_upload_planes); the device converts it to 8-bit 4:2:0
 // behind the copy and in front of the scaler.  Everything else is the run on the converted pictures: --reconst stays 8-bit
 // 4:2:0 of --output-size and --metrics compares the reconstruction with the CONVERTED (and scaled) originals.
+//
+// --hash md5|crc|checksum: every picture's slice is followed by a decoded picture hash SEI (H.274; include/wrenc_hash.h), so
+// that any conforming decoder checks what it decodes against what this encoder reconstructed.  The device takes the hash
+// of the reconstruction it holds (wrenc_gpu_download_hashes: the coded planes, --pad's margin included, as a decoder
+// hashes them; 48 bytes a picture over the bus) and the SEI's NAL unit (wrenc_bs_write_hash_sei) is part of the picture's
+// bytes: --bitrate charges it and --metrics' frame_bytes include it.  Without the option nothing is launched or written.
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -61,6 +67,7 @@
 #include <unistd.h>
 
 #include "../../../include/wrenc_bitstream.h"
+#include "../../../include/wrenc_bitstream_hash.h"
 #include "../../../include/wrenc_bitstream_qp.h"
 #include "../../../include/wrenc_bitstream_window.h"
 #include "../../../include/wrenc_gpu.h"
@@ -163,6 +170,7 @@ struct Options {
     bool scale = false;
     int in_w = 0, in_h = 0;    // the size of the input's frames: --input-size with --scale, else vis_w x vis_h
     int format = 0;            // --input-format: their pixel format (wrenc_format.h), yuv420p unless given
+    int hash = -1;             // --hash: the type of the decoded picture hash SEI behind every slice (wrenc_hash.h), -1: none
     int depth = 3, batch = 64, n_threads = 8;
     bool verbose = false;
     bool tokens = true; // --tokens auto | on: batches come back as residual tokens; --tokens off, --no-tokens: as the compact record
@@ -232,6 +240,11 @@ Options parse_options(int argc, char** argv) {
             const char* v = val();
             o.format = wrenc_gpu_format_from_name(v);
             if (o.format < 0) die("Invalid input-format: %s (yuv420p, nv12, yuv420p10le, p010le, yuv422p, yuv422p10le)", v);
+        }
+        else if (a == "--hash") {
+            const std::string v = val();
+            o.hash = v == "md5" ? WRENC_HASH_MD5 : (v == "crc" ? WRENC_HASH_CRC : (v == "checksum" ? WRENC_HASH_CHECKSUM : -1));
+            if (o.hash < 0) die("Invalid hash: %s (md5, crc, checksum)", v.c_str());
         }
         else if (a == "--no-tokens") o.tokens = false;
         else if (a == "--ramp-down") { // how a run ends: auto (smaller last batches when the host's tail is heavy), always, never
@@ -352,6 +365,7 @@ struct HostSet { // one (device, slot set) unit: page-locked planes of one batch
     std::vector<int> status;
     std::vector<size_t> len;
     std::vector<wrenc_gpu_metrics> metrics; // --metrics: the batch's sums
+    std::vector<wrenc_picture_hash> hashes; // --hash: the batch's hashes, until its slices are written
     int count = 0, first_poc = 0;       // the batch being searched / read back in this set
     int bs_count = 0, bs_first_poc = 0; // the batch whose slices are being written from this set
 };
@@ -416,6 +430,7 @@ std::vector<HostSet> make_units(const Options& o, const Geometry& g, const std::
         s.status.assign(batch, 0);
         s.len.assign(batch, 0);
         if (o.metrics) s.metrics.resize(batch);
+        if (o.hash >= 0) s.hashes.resize(batch);
     }
     return units;
 }
@@ -563,6 +578,8 @@ struct Run {
             if (pic_metrics.size() < (size_t)(s.first_poc + s.count)) pic_metrics.resize((size_t)(s.first_poc + s.count));
             for (int k = 0; k < s.count; ++k) pic_metrics[(size_t)(s.first_poc + k)] = s.metrics[(size_t)k];
         }
+        // --hash: of the reconstruction where it lies, 48 bytes a picture (the unit's slices of the batch before are out)
+        if (o.hash >= 0) gpu_check(s, wrenc_gpu_download_hashes(s.ctx, s.base, s.count, o.hash, s.hashes.data()));
         if (s.tok_pool) {
             for (int k = 0; k < s.count; ++k) {
                 uint8_t* m = s.maps + g.maps * k;
@@ -619,6 +636,15 @@ struct Run {
         if (rc == WRENC_BS_ENOSPC) {
             out.resize(n);
             rc = write(&n);
+        }
+        if (!rc && o.hash >= 0) { // the decoded picture hash SEI directly behind the slice: part of the picture's bytes
+            size_t sei = 0;
+            rc = wrenc_bs_write_hash_sei(o.hash, &s.hashes[(size_t)k], out.data() + n, out.size() - n, &sei);
+            if (rc == WRENC_BS_ENOSPC) {
+                out.resize(n + sei);
+                rc = wrenc_bs_write_hash_sei(o.hash, &s.hashes[(size_t)k], out.data() + n, out.size() - n, &sei);
+            }
+            n += sei;
         }
         s.status[(size_t)k] = rc;
         s.len[(size_t)k] = rc ? 0 : n;

@@ -19,6 +19,7 @@
 //   dev_search.h     block_splitter.rs:64-1154, ctu_encoder.rs:1421-1461
 //   dev_bins.h       ctu_encoder.rs:1786-2269       residual_coding as a token stream for the host's arithmetic coder
 //   dev_metrics.h    (the evaluation harness)       PSNR / SSIM sums of originals against the reconstruction
+//   dev_hash.h       (no counterpart)               decoded picture hash (MD5, CRC, checksum) of the reconstruction
 //   dev_scale.h      (no counterpart)               resampling of an uploaded picture to the visible size
 //   dev_format.h     (no counterpart)               10-bit, NV12 / P010 and 4:2:2 uploads to the 8-bit 4:2:0 planes
 #pragma once
@@ -44,6 +45,7 @@
 #define WRENC_TOKENS_KERNEL_TU
 #include "dev_bins.h"
 #include "dev_metrics.h"
+#include "dev_hash.h"
 #include "dev_complexity.h"
 #include "dev_pad.h"
 #include "dev_scale.h"

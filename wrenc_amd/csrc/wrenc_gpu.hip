@@ -771,6 +771,16 @@ struct wrenc_gpu_ctx {
     MetricsPartial* d_mpartial = nullptr;
     MetricsSums* d_msums = nullptr;
     int metrics_cap = 0; // pictures the scratch holds
+    // hash read-back (made on first use: a context that never asks launches and allocates what it always did): a stream
+    // of its own -- an MD5 pass is long, and on the copy stream it would stand in front of the next batch's uploads --,
+    // the CRC's tables, the waves' partials of one call and the pictures' values, grown on demand
+    hipStream_t hash_stream = nullptr;
+    HashTables* d_htables = nullptr;
+    uint32_t* d_hpartial = nullptr;
+    wrenc_picture_hash* d_hvalues = nullptr;
+    int hash_cap = 0; // pictures the scratch holds
+    hipEvent_t hash_ev[2] = {nullptr, nullptr}; // measurement mode (stats_enabled): around the last hash pass
+    bool hash_timed = false;
     // complexity read-back: the waves' triples, the pictures' totals and CTU maps of one call, for every slot at once
     // (allocated on first use and never again: a later call must not free device memory under a search in flight)
     ComplexityPartial* d_xpartial = nullptr;
@@ -815,10 +825,10 @@ int check_encoded(wrenc_gpu_ctx* ctx, int first, int n, const char* range_msg) {
     return WRENC_GPU_OK;
 }
 
-// the copy stream waits for the encode calls that searched these slots and for nothing queued after them (the slots of
-// one read-back usually share one call's event: each event is waited for once)
-int wait_for_search(wrenc_gpu_ctx* ctx, int first, int n) {
-    hipStream_t cs = ctx->copy_stream;
+// the copy stream (or `st`) waits for the encode calls that searched these slots and for nothing queued after them (the
+// slots of one read-back usually share one call's event: each event is waited for once)
+int wait_for_search(wrenc_gpu_ctx* ctx, int first, int n, hipStream_t st = nullptr) {
+    hipStream_t cs = st ? st : ctx->copy_stream;
     hipEvent_t last = nullptr;
     for (int s = first; s < first + n; ++s)
         if (ctx->slot_event[s] && ctx->slot_event[s] != last) {
@@ -828,11 +838,12 @@ int wait_for_search(wrenc_gpu_ctx* ctx, int first, int n) {
     return WRENC_GPU_OK;
 }
 
-// the encode calls' sticky overflow word, read on the copy stream behind what is queued there, as a status
-int read_overflow(wrenc_gpu_ctx* ctx) {
+// the encode calls' sticky overflow word, read on the copy stream (or `st`) behind what is queued there, as a status
+int read_overflow(wrenc_gpu_ctx* ctx, hipStream_t st = nullptr) {
+    hipStream_t cs = st ? st : ctx->copy_stream;
     int ovf = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&ovf, ctx->d_overflow, sizeof(int), hipMemcpyDeviceToHost, ctx->copy_stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->copy_stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&ovf, ctx->d_overflow, sizeof(int), hipMemcpyDeviceToHost, cs));
+    HIP_TRY(ctx, hipStreamSynchronize(cs));
     if (ovf & 2) return fail(ctx, WRENC_GPU_EHIP, "internal: a team member never reached a meeting point of the level schedule");
     if (ovf) return fail(ctx, WRENC_GPU_ELEVEL, "a quantised level reached 1024 (reference panics: block_splitter.rs:453)");
     return WRENC_GPU_OK;
@@ -1288,6 +1299,7 @@ void wrenc_gpu_destroy(wrenc_gpu_ctx* ctx) {
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     for (hipStream_t st : ctx->lanes) (void)hipStreamSynchronize(st);
     if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
+    if (ctx->hash_stream) (void)hipStreamSynchronize(ctx->hash_stream);
     for (PicBufs& b : ctx->slots) {
         // planes 1 and 2 point into plane 0's slab
         if (b.org[0]) (void)hipFree((void*)b.org[0]);
@@ -1323,6 +1335,9 @@ void wrenc_gpu_destroy(wrenc_gpu_ctx* ctx) {
     if (ctx->d_ccount) (void)hipFree(ctx->d_ccount);
     if (ctx->d_mpartial) (void)hipFree(ctx->d_mpartial);
     if (ctx->d_msums) (void)hipFree(ctx->d_msums);
+    if (ctx->d_htables) (void)hipFree(ctx->d_htables);
+    if (ctx->d_hpartial) (void)hipFree(ctx->d_hpartial);
+    if (ctx->d_hvalues) (void)hipFree(ctx->d_hvalues);
     if (ctx->d_xpartial) (void)hipFree(ctx->d_xpartial);
     if (ctx->d_xsums) (void)hipFree(ctx->d_xsums);
     if (ctx->d_xmap) (void)hipFree(ctx->d_xmap);
@@ -1337,6 +1352,9 @@ void wrenc_gpu_destroy(wrenc_gpu_ctx* ctx) {
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_uploaded) (void)hipEventDestroy(ctx->ev_uploaded);
     for (hipEvent_t e : ctx->enc_events) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ctx->hash_ev)
+        if (e) (void)hipEventDestroy(e);
+    if (ctx->hash_stream) (void)hipStreamDestroy(ctx->hash_stream);
     if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -2373,6 +2391,135 @@ int wrenc_gpu_test_metrics(wrenc_gpu_ctx* ctx, const uint8_t* const org[3], cons
         for (int p = 0; p < 3; ++p)
             if (ssim_map[p]) memcpy(ssim_map[p], map.data() + at[p], (size_t)(p ? C.windows : L.windows) * sizeof(float));
     }
+    return WRENC_GPU_OK;
+}
+
+// the hash pass over n pictures of `slots` from `first` on, on `st` (dev_hash.h): an MD5 lane per plane, or the waves'
+// partials and the finish; `tables` is read by the CRC only
+static hipError_t launch_hashes(const wrenc_gpu_config& c, hipStream_t st, const PicBufs* slots, int first, int n, int hash_type,
+                                const HashTables* tables, uint32_t* partials, wrenc_picture_hash* values) {
+    if (hash_type == WRENC_HASH_MD5) {
+        hipLaunchKernelGGL(hash_md5_kernel, dim3((unsigned)md5_waves(n)), dim3(64), 0, st, slots, first, n, c.width, c.height, values);
+        return hipGetLastError();
+    }
+    const HashPlane L = hash_plane(c.width, c.height, 0), C = hash_plane(c.width, c.height, 1);
+    const long long waves = (long long)n * (L.pieces + 2 * C.pieces);
+    // a workgroup of the CRC pass copies the tables to LDS first: few enough workgroups that each takes many pieces
+    const long long groups = (waves + 3) / 4;
+    const dim3 grid((unsigned)(groups < 2048 ? groups : 2048));
+    const uint32_t start_l = hash_crc_start_term(L.bytes), start_c = hash_crc_start_term(C.bytes);
+    if (hash_type == WRENC_HASH_CRC) {
+        hipLaunchKernelGGL(hash_piece_kernel<true>, grid, dim3(256), 0, st, slots, first, n, c.width, c.height, tables, partials);
+        hipLaunchKernelGGL(hash_finish_kernel<true>, dim3((unsigned)n, 3), dim3(64), 0, st, partials, c.width, c.height, tables, start_l, start_c, values);
+    } else {
+        hipLaunchKernelGGL(hash_piece_kernel<false>, grid, dim3(256), 0, st, slots, first, n, c.width, c.height, tables, partials);
+        hipLaunchKernelGGL(hash_finish_kernel<false>, dim3((unsigned)n, 3), dim3(64), 0, st, partials, c.width, c.height, tables, start_l, start_c, values);
+    }
+    return hipGetLastError();
+}
+
+static size_t hash_partials(const wrenc_gpu_config& c) {
+    return (size_t)hash_plane(c.width, c.height, 0).pieces + 2 * (size_t)hash_plane(c.width, c.height, 1).pieces;
+}
+
+// the CRC's tables, in place before anything queued on `st` after this call reads them
+static hipError_t upload_hash_tables(HashTables* d_tables, hipStream_t st) {
+    HashTables t;
+    hash_fill_tables(t);
+    const hipError_t e = hipMemcpyAsync(d_tables, &t, sizeof(t), hipMemcpyHostToDevice, st);
+    return e != hipSuccess ? e : hipStreamSynchronize(st);
+}
+
+int wrenc_gpu_download_hashes(wrenc_gpu_ctx* ctx, int first_slot, int n, int hash_type, wrenc_picture_hash* out) {
+    if (!ctx || !out) return WRENC_GPU_EINVAL;
+    if (hash_type != WRENC_HASH_MD5 && hash_type != WRENC_HASH_CRC && hash_type != WRENC_HASH_CHECKSUM)
+        return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_download_hashes: unknown hash type");
+    if (const int rc = check_encoded(ctx, first_slot, n, "slot range out of bounds")) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+    const wrenc_gpu_config& c = ctx->cfg;
+    if (!ctx->hash_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->hash_stream, hipStreamNonBlocking));
+    if (!ctx->d_htables) {
+        HashTables* t = nullptr;
+        HIP_TRY(ctx, realloc_scratch(t, sizeof(HashTables)));
+        const hipError_t e = upload_hash_tables(t, ctx->hash_stream);
+        if (e != hipSuccess) (void)hipFree(t);
+        HIP_TRY(ctx, e);
+        ctx->d_htables = t;
+    }
+    if (ctx->hash_cap < n) {
+        ctx->hash_cap = 0;
+        HIP_TRY(ctx, realloc_scratch(ctx->d_hpartial, (size_t)n * hash_partials(c) * sizeof(uint32_t)));
+        HIP_TRY(ctx, realloc_scratch(ctx->d_hvalues, (size_t)n * sizeof(wrenc_picture_hash)));
+        ctx->hash_cap = n;
+    }
+    // on the hash stream, behind the encode call that searched these slots and nothing later; the search of other slots
+    // and the copy stream's uploads go on meanwhile
+    hipStream_t hs = ctx->hash_stream;
+    if (const int rc = wait_for_search(ctx, first_slot, n, hs)) return rc;
+    ctx->hash_timed = false;
+    if (ctx->stats_enabled) {
+        for (hipEvent_t& e : ctx->hash_ev)
+            if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+        HIP_TRY(ctx, hipEventRecord(ctx->hash_ev[0], hs));
+    }
+    HIP_TRY(ctx, launch_hashes(c, hs, ctx->d_slots, first_slot, n, hash_type, ctx->d_htables, ctx->d_hpartial, ctx->d_hvalues));
+    if (ctx->stats_enabled) {
+        HIP_TRY(ctx, hipEventRecord(ctx->hash_ev[1], hs));
+        ctx->hash_timed = true;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_hvalues, (size_t)n * sizeof(wrenc_picture_hash), hipMemcpyDeviceToHost, hs));
+    return read_overflow(ctx, hs); // (synchronises the stream)
+}
+
+int wrenc_gpu_last_hash_ms(wrenc_gpu_ctx* ctx, float* ms) {
+    if (!ctx || !ms) return WRENC_GPU_EINVAL;
+    if (!ctx->hash_timed) return fail(ctx, WRENC_GPU_ESTATE, "no timed hash pass: wrenc_gpu_stats_enable, then wrenc_gpu_download_hashes");
+    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+    HIP_TRY(ctx, hipEventElapsedTime(ms, ctx->hash_ev[0], ctx->hash_ev[1]));
+    return WRENC_GPU_OK;
+}
+
+int wrenc_gpu_test_hash(wrenc_gpu_ctx* ctx, const uint8_t* const rec[3], int hash_type, wrenc_picture_hash* out) {
+    if (!ctx || !rec || !out) return WRENC_GPU_EINVAL;
+    if (hash_type != WRENC_HASH_MD5 && hash_type != WRENC_HASH_CRC && hash_type != WRENC_HASH_CHECKSUM)
+        return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_test_hash: unknown hash type");
+    for (int p = 0; p < 3; ++p)
+        if (!rec[p]) return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_test_hash: null plane");
+    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+    const wrenc_gpu_config& c = ctx->cfg;
+    const size_t wh = (size_t)c.width * c.height;
+    // a picture of its own (planes as one slab, like a slot's), never a slot of the context
+    uint8_t* d_planes = nullptr;
+    PicBufs* d_pic = nullptr;
+    HashTables* d_tables = nullptr;
+    uint32_t* d_part = nullptr;
+    wrenc_picture_hash* d_values = nullptr;
+    hipError_t e = hipMalloc((void**)&d_planes, wh + wh / 2);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_pic, sizeof(PicBufs));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_tables, sizeof(HashTables));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_part, hash_partials(c) * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_values, sizeof(wrenc_picture_hash));
+    if (e == hipSuccess) e = upload_hash_tables(d_tables, 0);
+    if (e == hipSuccess) {
+        PicBufs pb = {};
+        uint8_t* at = d_planes;
+        for (int p = 0; p < 3 && e == hipSuccess; ++p) {
+            pb.rec[p] = at;
+            e = hipMemcpy(at, rec[p], plane_bytes(c, p, 1), hipMemcpyHostToDevice);
+            at += plane_bytes(c, p, 1);
+        }
+        if (e == hipSuccess) e = hipMemcpy(d_pic, &pb, sizeof(pb), hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = launch_hashes(c, 0, d_pic, 0, 1, hash_type, d_tables, d_part, d_values);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, d_values, sizeof(*out), hipMemcpyDeviceToHost);
+    (void)hipFree(d_planes);
+    (void)hipFree(d_pic);
+    (void)hipFree(d_tables);
+    (void)hipFree(d_part);
+    (void)hipFree(d_values);
+    if (e != hipSuccess) (void)hipGetLastError();
+    HIP_TRY(ctx, e);
     return WRENC_GPU_OK;
 }
 

@@ -27,6 +27,7 @@ EXPORTED_SYMBOLS = [
     "wrenc_gpu_set_source_size", "wrenc_gpu_source_size", "wrenc_gpu_scale_taps",
     "wrenc_gpu_set_source_format", "wrenc_gpu_source_format", "wrenc_gpu_upload_planes",
     "wrenc_gpu_format_from_name", "wrenc_gpu_format_name", "wrenc_gpu_format_layout",
+    "wrenc_gpu_download_hashes", "wrenc_gpu_test_hash", "wrenc_gpu_last_hash_ms",
 ]
 
 
@@ -66,6 +67,24 @@ TOKEN_PAGE = 64  # WRENC_GPU_TOKEN_PAGE
 
 class Metrics(C.Structure):
     _fields_ = [("sse", C.c_uint64 * 3), ("ssim_sum", C.c_double * 3), ("ssim_windows", C.c_uint32 * 3)]
+
+
+HASH_MD5, HASH_CRC, HASH_CHECKSUM = 0, 1, 2   # include/wrenc_hash.h
+HASH_TYPES = {"md5": HASH_MD5, "crc": HASH_CRC, "checksum": HASH_CHECKSUM}
+
+
+class PictureHash(C.Structure):
+    """wrenc_picture_hash: Y, Cb, Cr, each the bytes the SEI carries (MD5 16, CRC 2, checksum 4), zeros behind."""
+    _fields_ = [("value", (C.c_uint8 * 16) * 3)]
+
+    def values(self, hash_type):
+        """The three components' values as bytes of the type's length."""
+        n = {HASH_MD5: 16, HASH_CRC: 2, HASH_CHECKSUM: 4}[_hash_id(hash_type)]
+        return [bytes(self.value[p])[:n] for p in range(3)]
+
+
+def _hash_id(hash_type):
+    return HASH_TYPES[hash_type] if isinstance(hash_type, str) else int(hash_type)
 
 
 class Complexity(C.Structure):
@@ -470,6 +489,31 @@ class Encoder:
                                                     (C.c_void_p * 3)(*[_p(a).value for a in wins]) if maps else None))
         m = metrics_values(self.width, self.height, out)
         return (m, wins) if maps else m
+
+    def download_hashes(self, first_slot, n, hash_type):
+        """The decoded picture hash of n encoded slots' reconstruction (include/wrenc_gpu.h, wrenc_gpu_download_hashes):
+        per picture a PictureHash; hash_type an id of include/wrenc_hash.h or "md5" / "crc" / "checksum"."""
+        outs = (PictureHash * max(n, 1))()
+        self.lib.wrenc_gpu_download_hashes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        self._check(self.lib.wrenc_gpu_download_hashes(self.ctx, first_slot, n, _hash_id(hash_type), outs))
+        return [outs[k] for k in range(n)]
+
+    def last_hash_ms(self):
+        """Device time of the last download_hashes call's kernels (HIP events; after stats_enable())."""
+        ms = C.c_float()
+        self.lib.wrenc_gpu_last_hash_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        self._check(self.lib.wrenc_gpu_last_hash_ms(self.ctx, C.byref(ms)))
+        return ms.value
+
+    def test_hash(self, rec, hash_type):
+        """Test entry: the hash kernels on an arbitrary picture (y, cb, cr) of the context's size; a PictureHash."""
+        r = [np.ascontiguousarray(a, np.uint8) for a in rec]
+        assert [a.shape for a in r] == [(self.height, self.width)] + [(self.height // 2, self.width // 2)] * 2
+        out = PictureHash()
+        self.lib.wrenc_gpu_test_hash.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        self._check(self.lib.wrenc_gpu_test_hash(self.ctx, (C.c_void_p * 3)(*[_p(a).value for a in r]), _hash_id(hash_type),
+                                                 C.byref(out)))
+        return out
 
     def device_info(self):
         """(wavefronts of the search kernel the device holds at once, HIP streams an encode call uses)."""
