@@ -26,6 +26,7 @@
 
 #include "wrenc_format.h"
 #include "wrenc_hash.h"
+#include "wrenc_ratecurve.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -341,6 +342,23 @@ typedef struct wrenc_gpu_complexity {
     uint32_t* ctu_satd;      /* (width/32)*(height/32) entries, may be NULL */
 } wrenc_gpu_complexity;
 int wrenc_gpu_download_complexity(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_gpu_complexity* out);
+
+/* Rate histogram read-back: the distribution of a slot's residual coefficient magnitudes, from its originals alone, BEFORE
+ * any search -- what sets the slope of the picture's bytes-at-QP curve (include/wrenc_rate.h: wrenc_rate_choose_vbv).  The
+ * definition, in exact integers, is include/wrenc_ratecurve.h: per picture-aligned 8x8 block of every plane of the CODED
+ * picture (a padded context's margin included) the best of the DC, V and H predictions from the neighbours' originals, the
+ * 8x8 Hadamard transform of the residual, and per plane the count of coefficients in each of 57 log-magnitude bins.
+ * QP-independent; 1536 bytes a picture over the bus; the same planes give the same table in any slot, batch and run.
+ * The calling rules are wrenc_gpu_download_complexity's: n slots in one call, blocking, on the copy stream behind the slots'
+ * uploads and behind no search; every slot that holds originals; WRENC_GPU_ESTATE for a slot never uploaded into,
+ * WRENC_GPU_EINVAL for a bad range; changes nothing in the slot.  Its scratch is allocated on the first call: a context
+ * that never calls it launches and allocates nothing it did not before. */
+int wrenc_gpu_download_rate_hist(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_rate_hist* out);
+/* Host only, no device: the bin of a coefficient magnitude 0 .. 16,320 (WRENC_GPU_EINVAL outside), and the table of a
+ * picture of width x height (multiples of 16, at least 16; tightly packed planes) by wrenc_ratecurve.h itself
+ * (WRENC_GPU_EINVAL for a bad size or a null pointer). */
+int wrenc_gpu_rate_hist_bin(int magnitude);
+int wrenc_gpu_rate_hist_host(int width, int height, const uint8_t* y, const uint8_t* cb, const uint8_t* cr, wrenc_rate_hist* out);
 
 /* Host only, no device: PSNR (dB) and SSIM as {Avg, Y, U, V} in wrenc_amd/metrics.py's definitions:
  * plane PSNR 10 log10(255^2 n / sse) (+infinity for sse 0), Avg from the MSE over all samples of the frame,

@@ -5,6 +5,10 @@
         17..47, 352x288 and a few 1920x1088 pictures, the bytes of every picture's NAL units against its complexity;
         least squares of ln bytes = ln a + ln N + b ln(C / N) - qp ln 2 / s, and the residuals.  --oracle: the same
         pictures through the CPU oracle (bit-exact with the device, so the same bytes; 352x288 only, on every core)
+    python3 tools/rc_probe.py curve FIT.json [OUT.json]
+        the buffer model's predictor on the rows of a `fit --oracle` run: every picture's rate
+        histogram (tests/ratecurve_ref.py), bytes ~ a P(q) + c CTUs with the library's curve and c and ONE global a (least
+        squares in ln bytes), the residuals per content, and the complexity model's on the same rows
     rocprofv3 --kernel-trace --stats -d DIR --output-format csv -- python3 tools/rc_probe.py kernel [WxH=1920x1088] [N=256] [REPS=4]
     python3 tools/rc_probe.py stats DIR/.../*_kernel_stats.csv [WxH] [N]
         complexity_kernel next to metrics_kernel (which reads twice the bytes: originals and reconstruction)
@@ -103,6 +107,34 @@ def fit(argv):
         json.dump(out, open(argv[0], "w"))
 
 
+def curve(argv):
+    import ratecurve_ref
+    from wrenc_amd import rate
+    fitted = json.load(open(argv[0]))
+    rows = [r for r in fitted["rows"] if (r[1], r[2]) == (352, 288)]
+    curves = {name: rate.curve(ratecurve_ref.rate_hist(*p)) for name, p in _pictures(352, 288, True)}
+    _, c = rate.curve_prior()
+    ctus = 11 * 9
+    got = np.array([r[5] for r in rows], np.float64)
+    unit = np.array([curves[r[0]][r[3]] for r in rows])
+    best = None
+    for ln_a in np.linspace(-7.0, 1.0, 8001):          # one global a: least squares of ln bytes - ln(a P + c CTUs)
+        res = np.log(got) - np.log(np.exp(ln_a) * unit + c * ctus)
+        rms = float(np.sqrt(np.mean(res * res)))
+        if best is None or rms < best[0]:
+            best = (rms, float(np.exp(ln_a)), res)
+    rms, a, res = best
+    out = {"a": a, "c": c, "pictures": len(rows), "residual_rms_ln": rms, "residual_max_ln": float(np.max(np.abs(res))),
+           "complexity_model": {"residual_rms_ln": fitted["residual_rms_ln"], "residual_max_ln": fitted["residual_max_ln"]}, "by_content": {}}
+    for name in sorted(curves):
+        sel = np.array([r[0] == name for r in rows])
+        out["by_content"][name] = {"mean_ln": float(np.mean(res[sel])), "rms_ln": float(np.sqrt(np.mean(res[sel] ** 2))),
+                                   "max_ln": float(np.max(np.abs(res[sel])))}
+    print(json.dumps(out, indent=1))
+    if len(argv) > 1:
+        json.dump(out, open(argv[1], "w"), indent=1)
+
+
 def _args(argv):
     w, h = [int(v) for v in (argv[0] if argv else "1920x1088").split("x")]
     return w, h, int(argv[1]) if len(argv) > 1 else 256, int(argv[2]) if len(argv) > 2 else 4
@@ -120,7 +152,8 @@ def kernel(argv):
     for rep in range(reps + 1):      # the first round warms up
         m = enc.download_metrics(0, n)
         c = enc.download_complexity(0, n, ctu_map=False)
-        print("%dx%d, %d pictures: PSNR Y %.3f dB, satd %s" % (w, h, n, m[0]["PSNR"]["Y"], c[0]["satd"]), flush=True)
+        r = enc.download_rate_hist(0, n)
+        print("%dx%d, %d pictures: PSNR Y %.3f dB, satd %s, zero coefficients %s" % (w, h, n, m[0]["PSNR"]["Y"], c[0]["satd"], r[0, :, 0].tolist()), flush=True)
     enc.close()
 
 
@@ -128,7 +161,7 @@ def stats(argv):
     w, h, n, _ = _args(argv[1:])
     for row in csv.DictReader(open(argv[0])):
         name = row["Name"]
-        for key, per_sample in (("complexity_kernel", 1.5), ("metrics_kernel", 3.0)):
+        for key, per_sample in (("complexity_kernel", 1.5), ("rate_hist_kernel", 1.5), ("metrics_kernel", 3.0)):
             if key in name:
                 avg_ns = float(row["AverageNs"])
                 print("%-24s %3d calls  avg %9.1f us  min %9.1f  max %9.1f  %.3f TB/s (%.1f B x %d x %d samples per call)" % (
@@ -137,4 +170,4 @@ def stats(argv):
 
 
 if __name__ == "__main__":
-    {"fit": fit, "kernel": kernel, "stats": stats}[sys.argv[1]](sys.argv[2:])
+    {"fit": fit, "curve": curve, "kernel": kernel, "stats": stats}[sys.argv[1]](sys.argv[2:])

@@ -34,4 +34,9 @@ g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -fno-
 ${CLANGXX:-/opt/rocm/lib/llvm/bin/clang++} -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined \
     -o "$T/format_convert" "$R/tools/sanitize/format_convert.cpp"
 "$T/format_convert"
+# the buffer model's host code: the rate histogram's definition (include/wrenc_ratecurve.h) and the controller's chooser,
+# bucket and re-encode step (include/wrenc_rate_vbv.h) over random histograms and sizes
+g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined \
+    -o "$T/rate_vbv" "$R/tools/sanitize/rate_vbv.cpp" $H0/rate_control.cpp
+"$T/rate_vbv"
 rm -rf "$T"

@@ -19,6 +19,9 @@ EXPORTED_QP_SYMBOLS = ("wrenc_bs_write_picture_qp", "wrenc_bs_write_picture_toke
 EXPORTED_WINDOW_SYMBOLS = ("wrenc_bs_write_parameter_sets_window",)
 # rate control (include/wrenc_rate.h; the Python mirror is wrenc_amd/rate.py)
 EXPORTED_RATE_SYMBOLS = ("wrenc_rate_prior", "wrenc_rate_create", "wrenc_rate_destroy", "wrenc_rate_choose", "wrenc_rate_report")
+# its buffer model (include/wrenc_rate_vbv.h)
+EXPORTED_RATE_VBV_SYMBOLS = ("wrenc_rate_curve", "wrenc_rate_curve_prior", "wrenc_rate_enable_vbv", "wrenc_rate_choose_vbv",
+                             "wrenc_rate_vbv_allowance", "wrenc_rate_recode")
 # decoded picture hash SEI (include/wrenc_bitstream_hash.h)
 EXPORTED_HASH_SYMBOLS = ("wrenc_bs_picture_hash", "wrenc_bs_write_hash_sei")
 

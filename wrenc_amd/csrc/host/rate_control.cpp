@@ -1,5 +1,6 @@
 // rate_control.cpp -- include/wrenc_rate.h: the QPs of a batch from its pictures' complexities, a bytes-at-QP model
-// whose scale follows the bytes reported so far.  Plain doubles and libm, one thread, no state outside the object: the
+// whose scale follows the bytes reported so far; and the buffer model: a leaky bucket, a curve per picture from its rate
+// histogram, a QP per picture, the QP to code a picture again at.  Plain doubles and libm, one thread, no state outside the object: the
 // same calls give the same QPs.
 #include <cmath>
 #include <deque>
@@ -20,6 +21,26 @@ constexpr double kPriorS = 6.872;
 // batch's budget costs three batches where spending a quarter of it costs three quarters of one.
 constexpr double kSteepS = 3.0;
 
+// The buffer model's prior, bytes ~ a P(q) + c CTUs: the same searches through the pictures' rate histograms
+// (tools/rc_probe.py curve).
+constexpr double kCurveA = 0.1370;
+constexpr double kCurveC = 4.8;
+
+// the middle of a bin's magnitudes (bins that hold nothing -- 2, 3, 4, 6, 8 -- never count)
+double bin_rep(int bin) {
+    if (bin <= 0) return 0.0;
+    const int lo = wrenc_ratecurve_bin_floor(bin);
+    int next = bin + 1;
+    while (next <= WRENC_RATECURVE_TOP_BIN && wrenc_ratecurve_bin_floor(next) <= lo) ++next;
+    const int hi = next <= WRENC_RATECURVE_TOP_BIN ? wrenc_ratecurve_bin_floor(next) : WRENC_RATECURVE_MAX_MAGNITUDE + 1;
+    return 0.5 * (double)(lo + hi - 1);
+}
+
+double level_bits(double l) {
+    if (l < WRENC_RATE_CURVE_DEAD) return WRENC_RATE_CURVE_TAIL * l / WRENC_RATE_CURVE_DEAD;
+    return WRENC_RATE_CURVE_BITS0 + WRENC_RATE_CURVE_BITS1 * std::log2(l / WRENC_RATE_CURVE_DEAD);
+}
+
 } // namespace
 
 struct wrenc_rate {
@@ -28,6 +49,7 @@ struct wrenc_rate {
     struct picture {
         double base; // what a = 1 predicts for it at QP 0
         int qp;
+        std::vector<double> curve; // the buffer model: P(q) of the picture, q = 0 .. 63
     };
     std::deque<picture> pending; // chosen, not yet reported
     long long chosen = 0;       // pictures chosen so far
@@ -36,6 +58,21 @@ struct wrenc_rate {
     // fit_qp / fit_n, and fit_base for the slope between them and the next report
     double fit_bytes = 0, fit_unit = 0, fit_base = 0, fit_qp = 0, fit_n = 0;
     double s_down = kSteepS;    // the slope below the reported QPs
+    // the buffer model: off while bufsize is 0; the bucket after every reported picture; the reports behind a
+    bool vbv = false;
+    double bufsize = 0, fullness = 0;
+    long long reported = 0;
+    double curve_bytes = 0, curve_unit = 0;
+    double ctus = 0;
+
+    double curve_a() const { return curve_unit > 0 && curve_bytes > 0 ? curve_bytes / curve_unit : kCurveA; }
+    double predict(const picture& p, int q) const { return curve_a() * p.curve[(size_t)q] + kCurveC * ctus; }
+    double arrive() const { return 8.0 * cfg.target_bytes; } // R
+    // the bucket after a picture of `bytes`, the `index`-th of the run (picture 0 carries the parameter sets)
+    double drain(double f, double bytes, long long index) const {
+        const double bits = 8.0 * (bytes + (index == 0 ? cfg.header_bytes : 0.0));
+        return std::fmin(bufsize, f - bits + arrive());
+    }
 
     // the model's 2^(-QP / s): the prior's slope, and s_down below the mean QP of the reports
     double scale(double q) const {
@@ -60,6 +97,7 @@ int wrenc_rate_create(const wrenc_rate_config* cfg, wrenc_rate** out) {
     if (!rc) return WRENC_RATE_EINVAL;
     rc->cfg = *cfg;
     rc->samples = (double)cfg->width * cfg->height;
+    rc->ctus = (double)((cfg->width + 31) / 32) * (double)((cfg->height + 31) / 32);
     *out = rc;
     return WRENC_RATE_OK;
 }
@@ -67,7 +105,7 @@ int wrenc_rate_create(const wrenc_rate_config* cfg, wrenc_rate** out) {
 void wrenc_rate_destroy(wrenc_rate* rc) { delete rc; }
 
 int wrenc_rate_choose(wrenc_rate* rc, int n, const uint64_t* satd, int32_t* qp) {
-    if (!rc || n < 1 || !satd || !qp) return WRENC_RATE_EINVAL;
+    if (!rc || n < 1 || !satd || !qp || rc->vbv) return WRENC_RATE_EINVAL;
     const wrenc_rate_config& c = rc->cfg;
     // what a = 1 predicts for every picture at QP 0 (a flat picture still costs its CU syntax: one activity unit per block)
     std::vector<double> base((size_t)n);
@@ -105,7 +143,7 @@ int wrenc_rate_choose(wrenc_rate* rc, int n, const uint64_t* satd, int32_t* qp) 
     }
     for (int k = 0; k < n; ++k) {
         qp[k] = k < split ? q : q + 1;
-        rc->pending.push_back({base[(size_t)k], qp[k]});
+        rc->pending.push_back({base[(size_t)k], qp[k], {}});
     }
     rc->chosen += n;
     return WRENC_RATE_OK;
@@ -113,6 +151,19 @@ int wrenc_rate_choose(wrenc_rate* rc, int n, const uint64_t* satd, int32_t* qp) 
 
 int wrenc_rate_report(wrenc_rate* rc, int n, const uint64_t* bytes) {
     if (!rc || n < 1 || !bytes || (size_t)n > rc->pending.size()) return WRENC_RATE_EINVAL;
+    if (rc->vbv) {
+        for (int k = 0; k < n; ++k) {
+            const wrenc_rate::picture p = rc->pending.front();
+            rc->pending.pop_front();
+            // a from the bytes beyond the constant; a picture smaller than the constant says nothing about a
+            rc->curve_bytes = WRENC_RATE_VBV_DECAY * rc->curve_bytes + std::fmax((double)bytes[k] - kCurveC * rc->ctus, 0.0);
+            rc->curve_unit = WRENC_RATE_VBV_DECAY * rc->curve_unit + p.curve[(size_t)p.qp];
+            rc->fullness = rc->drain(rc->fullness, (double)bytes[k], rc->reported);
+            rc->reported_bytes += (double)bytes[k];
+            ++rc->reported;
+        }
+        return WRENC_RATE_OK;
+    }
     double got = 0, base = 0, qp = 0;
     for (int k = 0; k < n; ++k) {
         got += (double)bytes[k];
@@ -142,5 +193,86 @@ int wrenc_rate_report(wrenc_rate* rc, int n, const uint64_t* bytes) {
         rc->fit_n += 1;
         rc->reported_bytes += (double)bytes[k];
     }
+    return WRENC_RATE_OK;
+}
+
+int wrenc_rate_curve(const wrenc_rate_hist* hist, double p[64]) {
+    if (!hist || !p) return WRENC_RATE_EINVAL;
+    double rep[WRENC_RATECURVE_BINS] = {};
+    for (int b = 1; b <= WRENC_RATECURVE_TOP_BIN; ++b) rep[b] = bin_rep(b);
+    for (int q = 0; q < 64; ++q) {
+        const double scale = 1.0 / (8.0 * std::exp2((q - 4) / 6.0));
+        double sum = 0;
+        for (int b = 1; b <= WRENC_RATECURVE_TOP_BIN; ++b) {
+            const double n = (double)hist->count[0][b] + WRENC_RATE_CURVE_CHROMA_WEIGHT * ((double)hist->count[1][b] + (double)hist->count[2][b]);
+            if (n > 0) sum += n * level_bits(rep[b] * scale);
+        }
+        p[q] = sum;
+    }
+    return WRENC_RATE_OK;
+}
+
+void wrenc_rate_curve_prior(double* a, double* c) {
+    if (a) *a = kCurveA;
+    if (c) *c = kCurveC;
+}
+
+int wrenc_rate_enable_vbv(wrenc_rate* rc, double bufsize_bits) {
+    if (!rc || rc->chosen > 0 || !std::isfinite(bufsize_bits) || bufsize_bits < rc->arrive() || !(bufsize_bits > 8.0 * rc->cfg.header_bytes))
+        return WRENC_RATE_EINVAL;
+    rc->vbv = true;
+    rc->bufsize = rc->fullness = bufsize_bits;
+    return WRENC_RATE_OK;
+}
+
+int wrenc_rate_choose_vbv(wrenc_rate* rc, int n, const wrenc_rate_hist* hist, int32_t* qp, double* allowance_bits) {
+    if (!rc || n < 1 || !hist || !qp || !rc->vbv) return WRENC_RATE_EINVAL;
+    const wrenc_rate_config& c = rc->cfg;
+    // the bucket and the bytes spent, walked from the reports over the predictions of the pictures in flight
+    double f = rc->fullness, in_flight = 0;
+    long long index = rc->reported;
+    for (const wrenc_rate::picture& p : rc->pending) {
+        const double bytes = rc->predict(p, p.qp);
+        in_flight += bytes;
+        f = rc->drain(f, bytes, index++);
+    }
+    // the batch's budget as wrenc_rate_choose draws it, an n-th of it for every picture
+    const double spent = c.header_bytes + rc->reported_bytes + in_flight;
+    const double error = c.target_bytes * (double)rc->chosen - spent;
+    long long window = c.num_pictures - rc->chosen;
+    if (window > WRENC_RATE_WINDOW) window = WRENC_RATE_WINDOW;
+    if (window < n) window = n;
+    const double share = c.target_bytes + error / (double)window;
+    for (int k = 0; k < n; ++k, ++index) {
+        wrenc_rate::picture p{0.0, c.qp_min, std::vector<double>(64)};
+        wrenc_rate_curve(hist + k, p.curve.data());
+        const double allowed = f - (index == 0 ? 8.0 * c.header_bytes : 0.0);
+        const double cap = std::fmin(share, WRENC_RATE_VBV_SAFETY * allowed / 8.0);
+        while (p.qp < c.qp_max && rc->predict(p, p.qp) > cap) ++p.qp;
+        if (allowance_bits) allowance_bits[k] = allowed;
+        qp[k] = p.qp;
+        f = rc->drain(f, rc->predict(p, p.qp), index);
+        rc->pending.push_back(std::move(p));
+    }
+    rc->chosen += n;
+    return WRENC_RATE_OK;
+}
+
+int wrenc_rate_vbv_allowance(const wrenc_rate* rc, double* allowance_bits, double* bufsize_bits, double* fullness_bits) {
+    if (!rc || !rc->vbv) return WRENC_RATE_EINVAL;
+    if (allowance_bits) *allowance_bits = rc->fullness - (rc->reported == 0 ? 8.0 * rc->cfg.header_bytes : 0.0);
+    if (bufsize_bits) *bufsize_bits = rc->bufsize;
+    if (fullness_bits) *fullness_bits = rc->fullness;
+    return WRENC_RATE_OK;
+}
+
+int wrenc_rate_recode(wrenc_rate* rc, uint64_t actual_bytes, double allowance_bits, int32_t* qp) {
+    if (!rc || !rc->vbv || !qp || rc->pending.empty() || actual_bytes < 1 || !std::isfinite(allowance_bits)) return WRENC_RATE_EINVAL;
+    wrenc_rate::picture& p = rc->pending.front();
+    const double ratio = (double)actual_bytes / rc->predict(p, p.qp);
+    const double cap = WRENC_RATE_VBV_SAFETY * allowance_bits / 8.0;
+    int q = p.qp < rc->cfg.qp_max ? p.qp + 1 : rc->cfg.qp_max;
+    while (q < rc->cfg.qp_max && ratio * rc->predict(p, q) > cap) ++q;
+    *qp = p.qp = q;
     return WRENC_RATE_OK;
 }

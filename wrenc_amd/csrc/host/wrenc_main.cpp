@@ -50,6 +50,16 @@
 // of the reconstruction it holds (wrenc_gpu_download_hashes: the coded planes, --pad's margin included, as a decoder
 // hashes them; 48 bytes a picture over the bus) and the SEI's NAL unit (wrenc_bs_write_hash_sei) is part of the picture's
 // bytes: --bitrate charges it and --metrics' frame_bytes include it.  Without the option nothing is launched or written.
+//
+// --vbv-bufsize KBIT (with --bitrate): every picture's size is bounded by a leaky bucket of KBIT * 1000 bits that fills by
+// bitrate / fps bits per picture and starts full (include/wrenc_rate.h: the buffer model; the parameter sets are charged to
+// picture 0, the hash SEI to its picture).  Every batch is measured by wrenc_gpu_download_rate_hist, not by its complexity,
+// and every picture gets a QP of its own.  A unit's batch is flushed BEFORE that unit uploads again, so that its slots still
+// hold the originals when its bytes are known: the flush walks the batch in picture order, and a picture over its
+// allowance is searched again at the QP wrenc_rate_recode returns (wrenc_gpu_set_slot_qp, wrenc_gpu_encode of that one
+// slot), read back and written again, up to the largest QP; one that does not fit even there is written as it is and
+// counted as a violation.  Metrics, hash and --reconst of such a picture are those of its last coding.  Only the cap is
+// enforced: no filler data, no HRD syntax -- the parameter sets are byte for byte what they are without the option.
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -179,6 +189,7 @@ struct Options {
     std::vector<int> pic_qp; // --qp-file: the QP of every picture (empty: --qp for all)
     int min_qp = 26;         // the smallest QP of the run
     double bitrate = 0, fps = 30; // --bitrate (kbit/s, 0: none) and --fps
+    double vbv_bits = 0;          // --vbv-bufsize in bits (0: no buffer model)
 };
 
 // --qp-file: whitespace-separated integers 0..63, entry i the QP of picture i, at least one per picture
@@ -208,7 +219,7 @@ std::vector<int> read_qp_file(const char* path, long num_pictures) {
 
 Options parse_options(int argc, char** argv) {
     Options o;
-    const char *in_size = nullptr, *out_size = nullptr, *device_list = nullptr, *qp_file = nullptr, *bitrate = nullptr, *fps = nullptr;
+    const char *in_size = nullptr, *out_size = nullptr, *device_list = nullptr, *qp_file = nullptr, *bitrate = nullptr, *fps = nullptr, *vbv = nullptr;
     int device = 0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -226,6 +237,7 @@ Options parse_options(int argc, char** argv) {
         else if (a == "--qp-file") qp_file = val();
         else if (a == "--bitrate") bitrate = val();
         else if (a == "--fps") fps = val();
+        else if (a == "--vbv-bufsize") vbv = val();
         else if (a == "--max-split-depth") o.depth = atoi(val());
         else if (a == "--extra-params") o.extra = val();
         else if (a == "--batch") o.batch = atoi(val());
@@ -304,6 +316,15 @@ Options parse_options(int argc, char** argv) {
         if (qp_file) die("--bitrate and --qp-file exclude each other: the QPs come from the rate control or from the file");
         if (!positive(bitrate, o.bitrate)) die("Invalid bitrate: %s (kbit/s, a number above 0)", bitrate);
         o.ramp_mode = 2; // (auto looks at the clock: the batches, and with them the QPs, must not depend on it)
+    }
+    if (vbv) {
+        if (qp_file) die("--vbv-bufsize and --qp-file exclude each other: the buffer model chooses the QPs");
+        if (!bitrate) die("--vbv-bufsize needs --bitrate: the buffer fills at that rate");
+        double kbit = 0;
+        if (!positive(vbv, kbit)) die("Invalid vbv-bufsize: %s (kbit, a number above 0)", vbv);
+        o.vbv_bits = kbit * 1000.0;
+        if (o.vbv_bits < o.bitrate * 1000.0 / o.fps)
+            die("vbv-bufsize %s kbit is smaller than one picture's share of the bitrate, %.3f kbit", vbv, o.bitrate / o.fps);
     }
     if (qp_file) {
         o.pic_qp = read_qp_file(qp_file, o.num_pictures);
@@ -481,12 +502,33 @@ struct Run {
     std::vector<wrenc_gpu_complexity> cplx;
     std::vector<uint64_t> rate_words;
     HostSet* pending = nullptr;
+    // --vbv-bufsize: the batch's histograms; per picture the bits left in the bucket once it is taken out (negative: a
+    // violation) and how often it was coded again; the run's counts
+    std::vector<wrenc_rate_hist> hists;
+    std::vector<double> vbv_left;
+    std::vector<int> vbv_recodes;
+    long vbv_reencoded = 0, vbv_violations = 0;
 
     int slice_qp(long picture) const { return rate ? rate_qp[(size_t)picture] : (o.pic_qp.empty() ? o.qp : o.pic_qp[(size_t)picture]); }
 
     // The QPs of the unit's uploaded batch: measured on the device while the other unit's search keeps it busy, chosen
     // with every byte count known by now, set slot by slot.
     void choose_qps(HostSet& s) {
+        if (o.vbv_bits > 0) { // the unit's previous batch is out already (main): nothing to flush here
+            hists.resize((size_t)s.count);
+            gpu_check(s, wrenc_gpu_download_rate_hist(s.ctx, s.base, s.count, hists.data()));
+            std::vector<int32_t> qps((size_t)s.count);
+            if (wrenc_rate_choose_vbv(rate, s.count, hists.data(), qps.data(), nullptr)) fatal("rate control: choose failed");
+            int lo = 63, hi = 0;
+            for (int k = 0; k < s.count; ++k) {
+                rate_qp[(size_t)(poc + k)] = qps[(size_t)k];
+                gpu_check(s, wrenc_gpu_set_slot_qp(s.ctx, s.base + k, config_of(qps[(size_t)k])));
+                lo = qps[(size_t)k] < lo ? qps[(size_t)k] : lo;
+                hi = qps[(size_t)k] > hi ? qps[(size_t)k] : hi;
+            }
+            if (o.verbose) fprintf(stderr, "  batch at picture %ld: QP %d .. %d (a QP per picture)\n", poc, lo, hi);
+            return;
+        }
         cplx.assign((size_t)s.count, wrenc_gpu_complexity{});
         gpu_check(s, wrenc_gpu_download_complexity(s.ctx, s.base, s.count, cplx.data()));
         if (pending) {
@@ -572,34 +614,38 @@ struct Run {
     // (other buffers): the residual tokens the device made of it -- the pass costs the device about 2 % of the search's
     // time and the host writes a picture 1.8 .. 2.1x faster from them -- or, when they do not fit the pool or the unit has
     // none, the compact level record (mask of coded 4x4 blocks + those blocks); either way with the maps.  True: tokens.
-    bool read_back(HostSet& s) {
+    bool read_back(HostSet& s) { return read_back(s, 0, s.count, s.first_poc); }
+
+    // ... pictures k0 .. k0 + n - 1 of the unit's batch, which starts at picture first_poc (the whole batch, or the one
+    // picture --vbv-bufsize has searched again: the token pool is free then, the batch's slices are written)
+    bool read_back(HostSet& s, int k0, int n, int first_poc) {
         if (o.metrics) { // the slots still hold the batch's originals next to its reconstruction: their sums, 60 bytes a picture
-            gpu_check(s, wrenc_gpu_download_metrics(s.ctx, s.base, s.count, s.metrics.data()));
-            if (pic_metrics.size() < (size_t)(s.first_poc + s.count)) pic_metrics.resize((size_t)(s.first_poc + s.count));
-            for (int k = 0; k < s.count; ++k) pic_metrics[(size_t)(s.first_poc + k)] = s.metrics[(size_t)k];
+            gpu_check(s, wrenc_gpu_download_metrics(s.ctx, s.base + k0, n, s.metrics.data() + k0));
+            if (pic_metrics.size() < (size_t)(first_poc + k0 + n)) pic_metrics.resize((size_t)(first_poc + k0 + n));
+            for (int k = k0; k < k0 + n; ++k) pic_metrics[(size_t)(first_poc + k)] = s.metrics[(size_t)k];
         }
         // --hash: of the reconstruction where it lies, 48 bytes a picture (the unit's slices of the batch before are out)
-        if (o.hash >= 0) gpu_check(s, wrenc_gpu_download_hashes(s.ctx, s.base, s.count, o.hash, s.hashes.data()));
+        if (o.hash >= 0) gpu_check(s, wrenc_gpu_download_hashes(s.ctx, s.base + k0, n, o.hash, s.hashes.data() + k0));
         if (s.tok_pool) {
-            for (int k = 0; k < s.count; ++k) {
+            for (int k = k0; k < k0 + n; ++k) {
                 uint8_t* m = s.maps + g.maps * k;
                 uint8_t* r = frec ? s.rec + g.pic * k : nullptr;
                 s.tks[(size_t)k] = wrenc_gpu_tokens{s.tok_first + g.n_ctus * k, m, m + g.n4, m + 2 * g.n4, r, r ? r + g.ysz : nullptr, r ? r + g.ysz + g.csz : nullptr};
             }
-            const int rc = wrenc_gpu_download_tokens(s.ctx, s.base, s.count, s.tks.data(), s.tok_pool, s.tok_cap, &s.tok_used);
+            const int rc = wrenc_gpu_download_tokens(s.ctx, s.base + k0, n, s.tks.data() + k0, s.tok_pool, s.tok_cap, &s.tok_used);
             if (rc == WRENC_GPU_OK) return true;
             if (rc != WRENC_GPU_ENOMEM) gpu_check(s, rc);
             if (o.verbose)
-                fprintf(stderr, "batch at picture %d: more tokens than the pool holds, read back as the compact level record\n", s.first_poc);
+                fprintf(stderr, "batch at picture %d: more tokens than the pool holds, read back as the compact level record\n", first_poc + k0);
             prepare_compact(s, g, o.batch);
         }
-        for (int k = 0; k < s.count; ++k) {
+        for (int k = k0; k < k0 + n; ++k) {
             uint8_t* m = s.maps + g.maps * k;
             uint8_t* r = frec ? s.rec + g.pic * k : nullptr;
             s.cps[(size_t)k] = wrenc_gpu_compact{s.mask + g.mask_words * k, s.lev + g.pic * k, g.level_blocks, 0, m, m + g.n4, m + 2 * g.n4,
                                                  r, r ? r + g.ysz : nullptr, r ? r + g.ysz + g.csz : nullptr};
         }
-        gpu_check(s, wrenc_gpu_download_compact(s.ctx, s.base, s.count, s.cps.data()));
+        gpu_check(s, wrenc_gpu_download_compact(s.ctx, s.base + k0, n, s.cps.data() + k0));
         return false;
     }
 
@@ -673,16 +719,49 @@ struct Run {
         }
     }
 
+    // --vbv-bufsize: picture k of the batch being flushed against the bucket.  Over its allowance it is searched again at
+    // the controller's QP while its slot still holds the originals, read back and written again on this thread, until it
+    // fits or the QP is the largest; then it is reported, which moves the bucket on.
+    void enforce_vbv(HostSet& s, int k) {
+        const size_t picture = (size_t)(s.bs_first_poc + k);
+        double allowance = 0;
+        if (wrenc_rate_vbv_allowance(rate, &allowance, nullptr, nullptr)) fatal("rate control: no buffer model");
+        while (!s.status[(size_t)k] && 8.0 * (double)s.len[(size_t)k] > allowance) {
+            int32_t q = 0;
+            if (wrenc_rate_recode(rate, s.len[(size_t)k], allowance, &q)) fatal("rate control: recode failed");
+            if (q == rate_qp[picture]) break; // the largest QP already: written as it is
+            rate_qp[picture] = q;
+            ++vbv_recodes[picture];
+            gpu_check(s, wrenc_gpu_set_slot_qp(s.ctx, s.base + k, config_of(q)));
+            gpu_check(s, wrenc_gpu_encode(s.ctx, s.base + k, 1));
+            const bool batch_tokens = s.bs_tokens;
+            s.bs_tokens = read_back(s, k, 1, s.bs_first_poc);
+            write_picture(s, k);
+            s.bs_tokens = batch_tokens;
+        }
+        if (s.status[(size_t)k]) return; // (flush reports the failure)
+        vbv_left[picture] = allowance - 8.0 * (double)s.len[(size_t)k];
+        vbv_reencoded += vbv_recodes[picture] > 0;
+        vbv_violations += vbv_left[picture] < 0;
+        const uint64_t bytes_k = s.len[(size_t)k];
+        if (wrenc_rate_report(rate, 1, &bytes_k)) fatal("rate control: report failed");
+    }
+
     void flush(HostSet& s) {
         pool.wait();
+        const long reenc0 = vbv_reencoded, viol0 = vbv_violations;
         for (int k = 0; k < s.bs_count; ++k) {
+            if (o.vbv_bits > 0) enforce_vbv(s, k);
             if (s.status[(size_t)k]) fatal("wrenc_bs_write_picture failed with %d on picture %d", s.status[(size_t)k], s.bs_first_poc + k);
             fwrite(s.nal[(size_t)k].data(), 1, s.len[(size_t)k], fout);
             bytes += s.len[(size_t)k];
             if (o.metrics) pic_bytes.push_back(s.len[(size_t)k]);
             if (frec) write_reconst(s.rec + g.pic * k); // main.rs:387-399
         }
-        if (rate && s.bs_count > 0) { // the bytes of the batch's NAL units, in the order its QPs were chosen
+        if (o.vbv_bits > 0) { // (reported picture by picture, above)
+            if (o.verbose && s.bs_count > 0)
+                fprintf(stderr, "  vbv: batch at picture %d: %ld re-encoded, %ld violations\n", s.bs_first_poc, vbv_reencoded - reenc0, vbv_violations - viol0);
+        } else if (rate && s.bs_count > 0) { // the bytes of the batch's NAL units, in the order its QPs were chosen
             rate_words.assign(s.len.begin(), s.len.begin() + s.bs_count);
             if (wrenc_rate_report(rate, s.bs_count, rate_words.data())) fatal("rate control: report failed");
         }
@@ -740,7 +819,13 @@ void write_metrics_report(const Run& run, const char* path, unsigned long long s
     for (size_t i = 0; i < run.pic_bytes.size(); ++i) fprintf(f, "%s%zu", i ? ", " : "", run.pic_bytes[i]);
     fputs("],\n \"frame_qp\": [", f);
     for (size_t i = 0; i < n; ++i) fprintf(f, "%s%d", i ? ", " : "", run.slice_qp((long)i));
-    fputs("]}\n", f);
+    fputc(']', f);
+    if (o.vbv_bits > 0) { // fullness: the bits left in the bucket once the picture is taken out, negative for a violation
+        fprintf(f, ",\n \"vbv\": {\"bufsize_bits\": %.17g, \"reencoded\": %ld, \"violations\": %ld, \"fullness\": [", o.vbv_bits, run.vbv_reencoded, run.vbv_violations);
+        for (size_t i = 0; i < n; ++i) fprintf(f, "%s%.17g", i ? ", " : "", run.vbv_left[i]);
+        fputs("]}", f);
+    }
+    fputs("}\n", f);
     fclose(f);
     fprintf(stderr, "%llu bytes  %.4f bpp  PSNR Avg %.2f Y %.2f U %.2f V %.2f dB  SSIM All %.4f Y %.4f\n", stream_bytes,
             n ? 8.0 * (double)stream_bytes / ((double)n * o.vis_w * o.vis_h) : 0.0, mean[0][0], mean[0][1], mean[0][2], mean[0][3], mean[1][0], mean[1][1]);
@@ -806,8 +891,14 @@ int main(int argc, char** argv) {
         int qp_max = 63;
         while (qp_max > o.qp && wrenc_gpu_set_slot_qp(ctxs[0], 0, run.config_of(qp_max)) == WRENC_GPU_EINVAL) --qp_max;
         if (wrenc_gpu_set_slot_qp(ctxs[0], 0, nullptr)) fatal("%s", wrenc_gpu_last_error(ctxs[0]));
-        const wrenc_rate_config rcfg = {o.w, o.h, 0, qp_max, (int64_t)o.num_pictures, target_bytes, (double)rate_hdr_bytes};
+        // (the buffer model charges the parameter sets as they are written, window fields included: its cap is on real bits)
+        const wrenc_rate_config rcfg = {o.w, o.h, 0, qp_max, (int64_t)o.num_pictures, target_bytes, (double)(o.vbv_bits > 0 ? hdr_bytes : rate_hdr_bytes)};
         if (wrenc_rate_create(&rcfg, &run.rate)) fatal("rate control: bad configuration");
+        if (o.vbv_bits > 0) {
+            if (wrenc_rate_enable_vbv(run.rate, o.vbv_bits)) die("vbv-bufsize %.0f bits does not hold the parameter sets (%zu bytes)", o.vbv_bits, hdr_bytes);
+            run.vbv_left.assign((size_t)o.num_pictures, 0.0);
+            run.vbv_recodes.assign((size_t)o.num_pictures, 0);
+        }
         run.rate_qp.assign((size_t)o.num_pictures, o.qp);
         if (o.verbose) fprintf(stderr, "rate control: %.1f kbit/s at %.3g pictures/s = %.1f bytes per picture, QP 0 .. %d\n", o.bitrate, o.fps, target_bytes, qp_max);
     }
@@ -842,8 +933,14 @@ int main(int argc, char** argv) {
         run.start_slices(s, tokens);
         pending = &s;
         s.count = 0;
+        if (o.vbv_bits > 0) { // the unit's batch out, and enforced, while its slots still hold the originals
+            const auto tf = std::chrono::steady_clock::now();
+            run.flush(s);
+            pending = nullptr;
+            t_flush += since(tf);
+        }
         if (run.poc < o.num_pictures) {
-            if (units.size() == 1) { // a single unit: its slices must be out before its buffers are refilled
+            if (units.size() == 1 && pending) { // a single unit: its slices must be out before its buffers are refilled
                 run.flush(s);
                 pending = nullptr;
             }
@@ -864,6 +961,7 @@ int main(int argc, char** argv) {
     if (frec) fclose(frec);
     if (fout != stdout) fclose(fout);
     if (o.metrics) write_metrics_report(run, o.metrics, run.bytes + hdr_bytes);
+    if (o.vbv_bits > 0) fprintf(stderr, "vbv: %ld re-encoded, %ld violations\n", run.vbv_reencoded, run.vbv_violations);
     if (o.verbose && run.rate && run.pictures > 0) {
         const double total = (double)(run.bytes + hdr_bytes), want = target_bytes * (double)run.pictures;
         fprintf(stderr, "rate control: target %.1f kbit/s, achieved %.1f kbit/s (%.0f of %.0f bytes, ratio %.4f)\n", o.bitrate,

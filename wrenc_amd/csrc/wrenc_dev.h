@@ -20,6 +20,7 @@
 //   dev_bins.h       ctu_encoder.rs:1786-2269       residual_coding as a token stream for the host's arithmetic coder
 //   dev_metrics.h    (the evaluation harness)       PSNR / SSIM sums of originals against the reconstruction
 //   dev_hash.h       (no counterpart)               decoded picture hash (MD5, CRC, checksum) of the reconstruction
+//   dev_ratecurve.h  (no counterpart)               rate histogram of the originals (prediction, Hadamard, magnitude bins)
 //   dev_scale.h      (no counterpart)               resampling of an uploaded picture to the visible size
 //   dev_format.h     (no counterpart)               10-bit, NV12 / P010 and 4:2:2 uploads to the 8-bit 4:2:0 planes
 #pragma once
@@ -47,6 +48,7 @@
 #include "dev_metrics.h"
 #include "dev_hash.h"
 #include "dev_complexity.h"
+#include "dev_ratecurve.h"
 #include "dev_pad.h"
 #include "dev_scale.h"
 #include "dev_format.h"

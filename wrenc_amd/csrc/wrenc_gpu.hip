@@ -12,6 +12,7 @@
 #include "../../include/wrenc_gpu.h"
 #include "../../include/wrenc_scale.h"
 #include "../../include/wrenc_format.h"
+#include "../../include/wrenc_ratecurve.h"
 #include "wrenc_dev.h"
 
 #include <hip/hip_runtime.h>
@@ -786,6 +787,10 @@ struct wrenc_gpu_ctx {
     ComplexityPartial* d_xpartial = nullptr;
     ComplexityPartial* d_xsums = nullptr;
     uint32_t* d_xmap = nullptr;
+    // rate histogram read-back: the waves' counts of one call and the pictures' tables, for every slot at once (allocated
+    // on first use and never again, as the complexity scratch)
+    RateHistPartial* d_rpartial = nullptr;
+    RateHistCounts* d_rsums = nullptr;
     int schedule = WRENC_GPU_SCHEDULE_AUTO;
     int last_schedule = WRENC_GPU_SCHEDULE_WAVE; // what the most recent encode call ran
     bool stats_valid = false;
@@ -1341,6 +1346,8 @@ void wrenc_gpu_destroy(wrenc_gpu_ctx* ctx) {
     if (ctx->d_xpartial) (void)hipFree(ctx->d_xpartial);
     if (ctx->d_xsums) (void)hipFree(ctx->d_xsums);
     if (ctx->d_xmap) (void)hipFree(ctx->d_xmap);
+    if (ctx->d_rpartial) (void)hipFree(ctx->d_rpartial);
+    if (ctx->d_rsums) (void)hipFree(ctx->d_rsums);
     if (ctx->d_stage) (void)hipFree(ctx->d_stage);
     if (ctx->d_scale_tab) (void)hipFree(ctx->d_scale_tab);
     if (ctx->d_raw) (void)hipFree(ctx->d_raw);
@@ -2324,6 +2331,40 @@ int wrenc_gpu_download_complexity(wrenc_gpu_ctx* ctx, int first_slot, int n, wre
     for (int k = 0; k < n; ++k)
         for (int p = 0; p < 3; ++p) out[k].satd[p] = sums[(size_t)k].satd[p];
     return WRENC_GPU_OK;
+}
+
+int wrenc_gpu_download_rate_hist(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_rate_hist* out) {
+    if (!ctx || !out) return WRENC_GPU_EINVAL;
+    const wrenc_gpu_config& c = ctx->cfg;
+    if (first_slot < 0 || n < 1 || first_slot + n > c.n_slots) return fail(ctx, WRENC_GPU_EINVAL, "slot range out of bounds");
+    for (int s = first_slot; s < first_slot + n; ++s)
+        if (ctx->state[s] == 0) return fail(ctx, WRENC_GPU_ESTATE, "slot has no uploaded picture");
+    HIP_TRY(ctx, hipSetDevice(c.device));
+    static_assert(sizeof(RateHistCounts) == sizeof(wrenc_rate_hist), "the device's table is the ABI's");
+    const size_t per_pic = (size_t)cplx_waves(c.width, c.height);
+    if (!ctx->d_rsums) {
+        HIP_TRY(ctx, realloc_scratch(ctx->d_rpartial, (size_t)c.n_slots * per_pic * sizeof(RateHistPartial)));
+        HIP_TRY(ctx, realloc_scratch(ctx->d_rsums, (size_t)c.n_slots * sizeof(RateHistCounts)));
+    }
+    // on the copy stream: behind the slots' uploads and behind no search, as the complexity pass
+    hipStream_t cs = ctx->copy_stream;
+    const size_t waves = (size_t)n * per_pic;
+    hipLaunchKernelGGL(rate_hist_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, cs, ctx->d_slots, first_slot, n, c.width, c.height,
+                       ctx->d_rpartial);
+    hipLaunchKernelGGL(rate_hist_finish_kernel, dim3(n), dim3(192), 0, cs, ctx->d_rpartial, c.width, c.height, ctx->d_rsums);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_rsums, (size_t)n * sizeof(wrenc_rate_hist), hipMemcpyDeviceToHost, cs));
+    HIP_TRY(ctx, hipStreamSynchronize(cs));
+    return WRENC_GPU_OK;
+}
+
+int wrenc_gpu_rate_hist_bin(int magnitude) {
+    if (magnitude < 0 || magnitude > WRENC_RATECURVE_MAX_MAGNITUDE) return WRENC_GPU_EINVAL;
+    return wrenc_ratecurve_bin(magnitude);
+}
+
+int wrenc_gpu_rate_hist_host(int width, int height, const uint8_t* y, const uint8_t* cb, const uint8_t* cr, wrenc_rate_hist* out) {
+    return wrenc_ratecurve_picture(y, cb, cr, width, height, out) ? WRENC_GPU_EINVAL : WRENC_GPU_OK;
 }
 
 void wrenc_gpu_metrics_values(int width, int height, const wrenc_gpu_metrics* m, double psnr[4], double ssim[4]) {

@@ -28,6 +28,7 @@ EXPORTED_SYMBOLS = [
     "wrenc_gpu_set_source_format", "wrenc_gpu_source_format", "wrenc_gpu_upload_planes",
     "wrenc_gpu_format_from_name", "wrenc_gpu_format_name", "wrenc_gpu_format_layout",
     "wrenc_gpu_download_hashes", "wrenc_gpu_test_hash", "wrenc_gpu_last_hash_ms",
+    "wrenc_gpu_download_rate_hist", "wrenc_gpu_rate_hist_bin", "wrenc_gpu_rate_hist_host",
 ]
 
 
@@ -89,6 +90,45 @@ def _hash_id(hash_type):
 
 class Complexity(C.Structure):
     _fields_ = [("satd", C.c_uint64 * 3), ("ctu_satd", C.c_void_p)]
+
+
+RATE_HIST_BINS, RATE_HIST_TOP_BIN = 64, 56    # include/wrenc_ratecurve.h
+
+
+class RateHist(C.Structure):
+    """wrenc_rate_hist: count[plane][bin], Y, Cb, Cr."""
+    _fields_ = [("count", (C.c_uint64 * RATE_HIST_BINS) * 3)]
+
+
+def _hist_array(hists, n):
+    return np.frombuffer(hists, np.uint64).reshape(-1, 3, RATE_HIST_BINS)[:n].copy()
+
+
+def rate_hist_bin(magnitude):
+    """wrenc_gpu_rate_hist_bin (host only): the bin of a coefficient magnitude 0 .. 16,320 (include/wrenc_ratecurve.h);
+    WrencGpuError outside."""
+    lib = load_library()
+    lib.wrenc_gpu_rate_hist_bin.argtypes = [C.c_int]
+    rc = lib.wrenc_gpu_rate_hist_bin(int(magnitude))
+    if rc < 0:
+        raise WrencGpuError(rc, "rate_hist_bin(%d)" % magnitude)
+    return rc
+
+
+def rate_hist_host(y, cb, cr):
+    """wrenc_gpu_rate_hist_host (host only): the rate histogram of a picture by include/wrenc_ratecurve.h itself, a (3, 64)
+    uint64 array; WrencGpuError for planes that are not h x w, h/2 x w/2, h/2 x w/2 with w and h multiples of 16."""
+    planes = [np.ascontiguousarray(p, np.uint8) for p in (y, cb, cr)]
+    h, w = planes[0].shape if planes[0].ndim == 2 else (0, 0)
+    if any(p.ndim != 2 for p in planes) or planes[1].shape != (h // 2, w // 2) or planes[2].shape != (h // 2, w // 2):
+        raise WrencGpuError(-1, "rate_hist_host: planes of %s" % ([p.shape for p in planes],))
+    lib = load_library()
+    out = (RateHist * 1)()
+    lib.wrenc_gpu_rate_hist_host.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    rc = lib.wrenc_gpu_rate_hist_host(w, h, _p(planes[0]), _p(planes[1]), _p(planes[2]), out)
+    if rc:
+        raise WrencGpuError(rc, "rate_hist_host(%d x %d)" % (w, h))
+    return _hist_array(out, 1)[0]
 
 
 def metrics_values(width, height, m):
@@ -473,6 +513,14 @@ class Encoder:
         self.lib.wrenc_gpu_download_complexity.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         self._check(self.lib.wrenc_gpu_download_complexity(self.ctx, first_slot, n, outs))
         return [{"satd": [int(v) for v in outs[k].satd], "ctu_satd": maps[k]} for k in range(n)]
+
+    def download_rate_hist(self, first_slot, n):
+        """The rate histograms of n slots' originals (include/wrenc_gpu.h, wrenc_gpu_download_rate_hist), before or after
+        their search: an (n, 3, 64) uint64 array, count[picture][plane][bin]."""
+        outs = (RateHist * max(n, 1))()
+        self.lib.wrenc_gpu_download_rate_hist.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        self._check(self.lib.wrenc_gpu_download_rate_hist(self.ctx, first_slot, n, outs))
+        return _hist_array(outs, n)
 
     def test_metrics(self, org, rec, maps=False):
         """Test entry: the metrics kernel on two arbitrary pictures (y, cb, cr) of the context's size.  Returns the entry of

@@ -7,6 +7,9 @@ from . import bitstream
 
 CHROMA_WEIGHT = 1.0   # WRENC_RATE_CHROMA_WEIGHT
 WINDOW = 64           # WRENC_RATE_WINDOW
+# the buffer model's curve: WRENC_RATE_CURVE_DEAD, _TAIL, _BITS0, _BITS1, _CHROMA_WEIGHT; WRENC_RATE_VBV_SAFETY, _DECAY
+CURVE_DEAD, CURVE_TAIL, CURVE_BITS0, CURVE_BITS1, CURVE_CHROMA_WEIGHT = 0.7, 0.125, 2.3, 0.87, 0.5
+VBV_SAFETY, VBV_DECAY = 0.85, 0.9
 
 
 class Config(C.Structure):
@@ -23,6 +26,13 @@ def _lib():
     lib.wrenc_rate_destroy.argtypes = [C.c_void_p]
     lib.wrenc_rate_choose.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.wrenc_rate_report.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.wrenc_rate_curve.argtypes = [C.c_void_p, C.c_void_p]
+    lib.wrenc_rate_curve_prior.restype = None
+    lib.wrenc_rate_curve_prior.argtypes = [C.c_void_p, C.c_void_p]
+    lib.wrenc_rate_enable_vbv.argtypes = [C.c_void_p, C.c_double]
+    lib.wrenc_rate_choose_vbv.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.wrenc_rate_vbv_allowance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.wrenc_rate_recode.argtypes = [C.c_void_p, C.c_uint64, C.c_double, C.c_void_p]
     return lib
 
 
@@ -35,6 +45,31 @@ def prior():
 
 class RateError(RuntimeError):
     pass
+
+
+def _hists(hist):
+    hist = np.ascontiguousarray(hist, np.uint64)
+    if hist.ndim < 2 or hist.shape[-2:] != (3, 64):
+        raise RateError("a rate histogram is (3, 64) counts")
+    return hist.reshape(-1, 3, 64)
+
+
+def curve(hist):
+    """wrenc_rate_curve: P(q), q = 0 .. 63, of one (3, 64) rate histogram (wrenc_amd.gpu download_rate_hist)."""
+    hist = _hists(hist)
+    if len(hist) != 1:
+        raise RateError("curve: one histogram")
+    p = np.zeros(64, np.float64)
+    if _lib().wrenc_rate_curve(hist.ctypes.data, p.ctypes.data):
+        raise RateError("wrenc_rate_curve")
+    return p
+
+
+def curve_prior():
+    """(a, c) of bytes ~ a P(q) + c CTUs."""
+    a, c = C.c_double(), C.c_double()
+    _lib().wrenc_rate_curve_prior(C.byref(a), C.byref(c))
+    return a.value, c.value
 
 
 class Controller:
@@ -57,6 +92,35 @@ class Controller:
         nbytes = np.ascontiguousarray(nbytes, np.uint64).reshape(-1)
         if self.lib.wrenc_rate_report(self.rc, len(nbytes), nbytes.ctypes.data):
             raise RateError("wrenc_rate_report: more pictures than are outstanding")
+
+    # the buffer model
+    def enable_vbv(self, bufsize_bits):
+        if self.lib.wrenc_rate_enable_vbv(self.rc, float(bufsize_bits)):
+            raise RateError("wrenc_rate_enable_vbv: a buffer below one picture's bits or the parameter sets', or pictures already chosen")
+
+    def choose_vbv(self, hist, allowances=False):
+        """hist: (n, 3, 64) rate histograms of the next n pictures; returns their QPs (and, asked for, the bits the walk
+        expects the bucket to allow each)."""
+        hist = _hists(hist)
+        qp = np.zeros(len(hist), np.int32)
+        allow = np.zeros(len(hist), np.float64)
+        if self.lib.wrenc_rate_choose_vbv(self.rc, len(hist), hist.ctypes.data, qp.ctypes.data, allow.ctypes.data):
+            raise RateError("wrenc_rate_choose_vbv: no buffer model enabled")
+        return ([int(q) for q in qp], allow.tolist()) if allowances else [int(q) for q in qp]
+
+    def vbv_allowance(self):
+        """{"allowance", "bufsize", "fullness"} in bits, for the oldest outstanding picture."""
+        a, b, f = C.c_double(), C.c_double(), C.c_double()
+        if self.lib.wrenc_rate_vbv_allowance(self.rc, C.byref(a), C.byref(b), C.byref(f)):
+            raise RateError("wrenc_rate_vbv_allowance: no buffer model enabled")
+        return {"allowance": a.value, "bufsize": b.value, "fullness": f.value}
+
+    def recode(self, actual_bytes, allowance_bits):
+        """The QP to code the oldest outstanding picture again at."""
+        q = C.c_int32()
+        if self.lib.wrenc_rate_recode(self.rc, int(actual_bytes), float(allowance_bits), C.byref(q)):
+            raise RateError("wrenc_rate_recode")
+        return q.value
 
     def close(self):
         if self.rc:
