@@ -294,6 +294,45 @@ __device__ __forceinline__ bool head_test(int C, int st, int amin) {
     return (m - c0) + 2 * amin >= 0;                   // |m - c0| < 2^30 (see kNoBranch), amin <= 2^28
 }
 
+// quantize_solo's first pass over block blk of side 1 << LG: the coefficients r1 ([y][x]) into scan order (tcs), the first
+// significant position, and how far down the head is provably zero (head_batch).  Position 64 T + LANE of batch T is
+// position LANE & 15 of sub-block 4 T + (LANE >> 4): the offset inside the sub-block is the same in every batch and the
+// sub-blocks' origins are a literal per batch (dev_scan.h), so no address waits for a load -- the LDS reads of up to four
+// batches (a block of 256 positions and more; smaller blocks are one batch) are issued before the first ballot, then the
+// batches go through the head search in order.
+template <int LG>
+__device__ __forceinline__ void solo_gather(int blk, int16_t* tcs, const HeadK& hk, const HeadT& ht, int& nzl, int& first, bool& open,
+                                            int& arun, int& sb) {
+    constexpr int P = 1 << (2 * LG), NB = (P + 63) / 64, G = 4;
+    const int lane = LANE;
+    const int row = lane >> 4;
+    const int in4 = blk * P + scan_nib_offset(LG, scan_nib(lane & 15));
+#pragma unroll
+    for (int g = 0; g < NB; g += G) {
+        int tcb[G];
+#pragma unroll
+        for (int t = 0; t < G; ++t) {
+            if (g + t >= NB) continue;
+            const int p = 64 * (g + t) + lane;
+            tcb[t] = p < P ? (int)SH.r1[scan_word_origin(scan_batch_word(LG, g + t), row) + in4] : 0;
+        }
+#pragma unroll
+        for (int t = 0; t < G; ++t) {
+            if (g + t >= NB) continue;
+            const int p0 = 64 * (g + t), p = p0 + lane;
+            const bool valid = p < P;
+            const int tc = tcb[t];
+            nzl |= tc;
+            if (valid) tcs[blk * P + p] = (int16_t)tc;
+            if (first == P) {
+                const unsigned long long sig = __ballot(head_sig(tc, ht));
+                if (sig != 0ULL) first = p0 + (int)__builtin_ctzll(sig);
+            }
+            head_batch(tc, p, P, valid, hk, ht, open, arun, sb);
+        }
+    }
+}
+
 // Dependent quantisation of nb transform blocks of side n (nb = 1 luma, 2 = Cb+Cr pair) by one wave:
 // coefficients r1 ([blk][y][x]) -> levels in place; returns the summed level cost
 // (block_splitter.rs:436-458).  Scratch: r2, decw.  `*overflow` is set when a level needs a table
@@ -320,7 +359,6 @@ __device__ __forceinline__ long long quantize_solo(Ctx c, int lg, int nb, int* o
     const int sh = 8 + lg - 5 + 1; // quantizer.rs:558-569
     const int off = (1 << sh) >> 1;
     const int lsc = k->lsc;
-    const CONST_AS uint16_t* scan = k->scan_idx[lg - 2];
     int16_t* tcs = (int16_t*)SH.r2;          // [blk][p]: coefficient in reverse-scan order (all of r2 for a 32x32 block)
     int32_t* cc = (int32_t*)SH.r1;           // chunk: [blk][CH][6] ints (coefficients are dead after the gather)
     uint16_t* dec16 = (uint16_t*)SH.decw;    // decisions: [blk][sub-block][state] 16-bit masks
@@ -340,18 +378,11 @@ __device__ __forceinline__ long long quantize_solo(Ctx c, int lg, int nb, int* o
     for (int blk = 0; blk < nb; ++blk) {
         int first = P, arun = kAlphaInf, sb = nsb - 1; // (first: uniform)
         bool open = true;
-#pragma unroll 1
-        for (int p0 = 0; p0 < P; p0 += 64) {
-            const int p = p0 + LANE;
-            const bool valid = p < P;
-            const int tc = valid ? (int)SH.r1[blk * P + scan[valid ? p : 0]] : 0;
-            nzl |= tc;
-            if (valid) tcs[blk * P + p] = (int16_t)tc;
-            if (first == P) {
-                const unsigned long long sig = __ballot(head_sig(tc, ht));
-                if (sig != 0ULL) first = p0 + (int)__builtin_ctzll(sig);
-            }
-            head_batch(tc, p, P, valid, hk, ht, open, arun, sb);
+        switch (lg) { // (uniform) the scan is arithmetic on the block size: a literal per batch once the size is a constant
+        case 2: solo_gather<2>(blk, tcs, hk, ht, nzl, first, open, arun, sb); break;
+        case 3: solo_gather<3>(blk, tcs, hk, ht, nzl, first, open, arun, sb); break;
+        case 4: solo_gather<4>(blk, tcs, hk, ht, nzl, first, open, arun, sb); break;
+        default: solo_gather<5>(blk, tcs, hk, ht, nzl, first, open, arun, sb); break;
         }
         sb = head_sb(open, sb, nsb);
         if (sb > 0 && sb < nsb) arun = wave_min_i32(arun);
@@ -482,6 +513,7 @@ __device__ __forceinline__ long long quantize_solo(Ctx c, int lg, int nb, int* o
     const uint16_t* bdec = dec16 + blk * (P >> 2);
     int fmap = kMapId;
     const DecMasks dm = dec_masks(bdec, act ? p0 : 0); // a lane's positions lie in one sub-block (per divides 16)
+    const int org = blk * P + scan_sb_origin(lg, act ? p0 >> 4 : 0); // ... whose levels go to raster org + the position's offset
     if (act) {
         for (int j = 0; j < per; ++j) {
             const int p = p0 + j;
@@ -503,11 +535,12 @@ __device__ __forceinline__ long long quantize_solo(Ctx c, int lg, int nb, int* o
     int fnz = P;
     if (act) {
         int state = entry;
-        for (int j = 0; j < per; ++j) {
+        unsigned long long nibs = scan_nibs_from(p0 & 15);
+        for (int j = 0; j < per; ++j, nibs >>= 4) {
             const int p = p0 + j;
             const int tc = btcs[p];
-            SH.r1[blk * P + scan[p]] = (int16_t)emit_level(c, tc, quotient(k, tc, sh, off), p == P - 1, dec_nib(dm, p), p, j,
-                                                           state, zmask, sum_nz, fnz, ovf);
+            SH.r1[org + scan_nib_offset(lg, (int)nibs & 15)] = (int16_t)emit_level(c, tc, quotient(k, tc, sh, off), p == P - 1, dec_nib(dm, p), p, j,
+                                                                                  state, zmask, sum_nz, fnz, ovf);
         }
     }
     const int pf = group_min_i32(fnz, half); // zeros before a block's first non-zero level cost nothing
@@ -528,7 +561,7 @@ __device__ __forceinline__ long long quantize_solo(Ctx c, int lg, int nb, int* o
 // level cost (block_splitter.rs:436-458) comes back in lvl[b], "has a non-zero level" in bit b of *any_mask.
 // The lane's coefficient comes in a register, row-major (lane 16 b + 4 y + x of block b), and the lane's level goes back
 // the same way; nothing of either is kept in LDS.  The move to scan order and back (position p of the row works on
-// raster index scan[p]) is one ds_bpermute_b32 in and one ds_permute_b32 out: lane exchanges of the LDS crossbar, no
+// raster index scan_nib(p), dev_scan.h) is one ds_bpermute_b32 in and one ds_permute_b32 out: lane exchanges of the LDS crossbar, no
 // store, no bank access, and no wait between a store and its load.  Scratch: r1 chunk entries, decw.
 __device__ __forceinline__ int quantize_p16_reg(Ctx c, int nb, int coef, int* overflow, long long lvl[4], int* any_mask) {
     c = uni(c);
@@ -539,7 +572,6 @@ __device__ __forceinline__ int quantize_p16_reg(Ctx c, int nb, int coef, int* ov
     constexpr int sh = 8 + lg - 5 + 1; // quantizer.rs:558-569
     constexpr int off = (1 << sh) >> 1;
     const int lsc = k->lsc;
-    const CONST_AS uint16_t* scan = k->scan_idx[0];
     int32_t* cc = (int32_t*)SH.r1;
     PROF_MARK(q0_);
     const int blk = lane >> 4, p = lane & 15;
@@ -551,7 +583,7 @@ __device__ __forceinline__ int quantize_p16_reg(Ctx c, int nb, int coef, int* ov
     return 0;
 #endif
     const HeadT ht = head_ranges(k, 2);
-    const int at = 16 * blk + (int)scan[p]; // the lane that holds this position's raster sample
+    const int at = 16 * blk + scan_nib(p); // the lane that holds this position's raster sample
     int tc = __builtin_amdgcn_ds_bpermute(4 * at, coef); // (every lane takes part, whatever its row holds)
     if (!mine) tc = 0;
     const int istar = row_min_i32(head_sig(tc, ht) ? p : P); // of this lane's block
@@ -680,11 +712,10 @@ __device__ __forceinline__ int dequantize4_lane(const Ctx& c, int level) {
 // ---------------------------------------------------------------------------
 
 // forward trace + level cost of up to four blocks of 64 positions, block b = row b (16 lanes, four consecutive
-// positions per lane: they lie in one sub-block); levels to r1[rbase + 64 b + scan[p]]; per block the level cost and
-// "has a non-zero level"
+// positions per lane: they lie in one sub-block); levels to r1[rbase + 64 b + scan_raster(3, p)]; per block the level
+// cost and "has a non-zero level"
 __device__ __forceinline__ void trace_rows64(const Ctx& c, int nblk, const int16_t* tcs, const uint16_t* dec16, int rbase,
-                                             const CONST_AS uint16_t* scan, int sh, int off, long long lvl[4], bool any[4], int& ovf,
-                                             int start = 0) {
+                                             int sh, int off, long long lvl[4], bool any[4], int& ovf, int start = 0) {
     // start (per row: a multiple of 16): the positions before it are proven zero (their levels are zero already, the
     // trace reaches `start` in state 0); the row's lanes share what is left, 1, 2 or 4 consecutive positions each
     const int lane = lane_fresh();
@@ -696,6 +727,7 @@ __device__ __forceinline__ void trace_rows64(const Ctx& c, int nblk, const int16
     const int b = row < nblk ? row : 0;
     const int16_t* btcs = tcs + b * 64;
     const DecMasks dm = dec_masks(dec16 + b * 16, act ? p0 : 0);
+    const int org = rbase + b * 64 + scan_sb_origin_ct<3>(act ? p0 >> 4 : 0);
     int fmap = kMapId;
     if (act) {
         for (int j = 0; j < per; ++j) {
@@ -716,11 +748,12 @@ __device__ __forceinline__ void trace_rows64(const Ctx& c, int nblk, const int16
     int fnz = 64;
     if (act) {
         int state = entry;
-        for (int j = 0; j < per; ++j) {
+        unsigned long long nibs = scan_nibs_from(p0 & 15);
+        for (int j = 0; j < per; ++j, nibs >>= 4) {
             const int p = p0 + j;
             const int tc = btcs[p];
-            SH.r1[rbase + b * 64 + scan[p]] = (int16_t)emit_level(c, tc, quotient(k, tc, sh, off), p == 63, dec_nib(dm, p), p, j, state,
-                                                                  zmask, sum_nz, fnz, ovf);
+            SH.r1[org + scan_nib_offset(3, (int)nibs & 15)] = (int16_t)emit_level(c, tc, quotient(k, tc, sh, off), p == 63, dec_nib(dm, p), p, j,
+                                                                                 state, zmask, sum_nz, fnz, ovf);
         }
     }
     const int pf = row_min_i32(fnz); // zeros before a block's first non-zero level cost nothing
@@ -739,7 +772,7 @@ __device__ __forceinline__ void trace_rows64(const Ctx& c, int nblk, const int16
 
 // the same for up to four blocks of 16 positions, one position per lane (as quantize_p16)
 __device__ __forceinline__ void trace_rows16(const Ctx& c, int nblk, const int16_t* tcs, const uint16_t* dec16, int rbase,
-                                             const CONST_AS uint16_t* scan, int sh, int off, long long lvl[4], bool any[4], int& ovf) {
+                                             int sh, int off, long long lvl[4], bool any[4], int& ovf) {
     const int lane = lane_fresh();
     const int row = lane >> 4, i16 = lane & 15;
     const CONST_AS DevConst* k = c.k;
@@ -761,7 +794,7 @@ __device__ __forceinline__ void trace_rows16(const Ctx& c, int nblk, const int16
     int fnz = 16;
     if (mine) {
         int state = entry;
-        SH.r1[rbase + bb * 16 + scan[i16]] = (int16_t)emit_level(c, tc, qd, i16 == 15, nib, i16, 0, state, zmask, sum_nz, fnz, ovf);
+        SH.r1[rbase + bb * 16 + scan_nib(i16)] = (int16_t)emit_level(c, tc, qd, i16 == 15, nib, i16, 0, state, zmask, sum_nz, fnz, ovf);
     }
     const int pf = row_min_i32(fnz);
     if (mine && (zmask & 1u) && i16 > pf) sum_nz += SHT.lv[0];
@@ -779,8 +812,7 @@ __device__ __forceinline__ void trace_rows16(const Ctx& c, int nblk, const int16
 
 // the same for ONE block of 256 positions over the whole wave (four consecutive positions per lane), as quantize_solo
 __device__ __forceinline__ void trace_wave256(const Ctx& c, const int16_t* tcs, const uint16_t* dec16, int rbase,
-                                              const CONST_AS uint16_t* scan, int sh, int off, long long* lvl, bool* any, int& ovf,
-                                              int start = 0) {
+                                              int sh, int off, long long* lvl, bool* any, int& ovf, int start = 0) {
     // start (uniform, a multiple of 16): see trace_rows64; the wave's lanes share the positions from there on
     const int lane = lane_fresh();
     const CONST_AS DevConst* k = c.k;
@@ -788,6 +820,7 @@ __device__ __forceinline__ void trace_wave256(const Ctx& c, const int16_t* tcs, 
     const int p0 = start + lane * per;
     const bool act = p0 < 256;
     const DecMasks dm = dec_masks(dec16, act ? p0 : 0);
+    const int org = rbase + scan_sb_origin_ct<4>(act ? p0 >> 4 : 0);
     int fmap = kMapId;
     if (act) {
         for (int j = 0; j < per; ++j) {
@@ -810,11 +843,12 @@ __device__ __forceinline__ void trace_wave256(const Ctx& c, const int16_t* tcs, 
     int fnz = 256;
     if (act) {
         int state = entry;
-        for (int j = 0; j < per; ++j) {
+        unsigned long long nibs = scan_nibs_from(p0 & 15);
+        for (int j = 0; j < per; ++j, nibs >>= 4) {
             const int p = p0 + j;
             const int tc = tcs[p];
-            SH.r1[rbase + scan[p]] = (int16_t)emit_level(c, tc, quotient(k, tc, sh, off), p == 255, dec_nib(dm, p), p, j, state, zmask,
-                                                         sum_nz, fnz, ovf);
+            SH.r1[org + scan_nib_offset(4, (int)nibs & 15)] = (int16_t)emit_level(c, tc, quotient(k, tc, sh, off), p == 255, dec_nib(dm, p), p, j,
+                                                                                 state, zmask, sum_nz, fnz, ovf);
         }
     }
     const int pf = wave_min_i32(fnz);
@@ -836,8 +870,6 @@ __device__ __forceinline__ void quantize_pk(Ctx c, int nc, int* overflow, long l
     constexpr int shl = 8 + LGL - 5 + 1, offl = (1 << shl) >> 1; // quantizer.rs:558-569
     constexpr int shc = shl - 1, offc = (1 << shc) >> 1;
     const int lsc = k->lsc;
-    const CONST_AS uint16_t* scanl = k->scan_idx[LGL - 2];
-    const CONST_AS uint16_t* scanc = k->scan_idx[LGL - 3];
     int16_t* tcs = (int16_t*)SH.r2;
     int32_t* cc = (int32_t*)SH.r1;
     uint16_t* dec16 = (uint16_t*)SH.decw;  // luma candidate c: [4 SBL c + 4 sb + state]; chroma chain b: [4 SBL nc + 4 SBC b + 4 sb + state]
@@ -861,13 +893,15 @@ __device__ __forceinline__ void quantize_pk(Ctx c, int nc, int* overflow, long l
     int v_low = 0, v_amin = kAlphaInf;
     const HeadK hkl = head_consts(shl, offl, lsc);
     const HeadT htl = head_ranges(k, LGL), htc = head_ranges(k, LGL - 1);
+    const int nib = scan_nib(i16); // the lane's place inside its sub-block: the same in every gather below (dev_scan.h)
 #pragma unroll 1
     for (int cd = 0; cd < nc; ++cd) {
         int first = PL, arun = kAlphaInf, sb = SBL - 1; // (first: uniform)
         bool open = true;
 #pragma unroll
-        for (int p = lane; p < PL; p += 64) {
-            const int tc = SH.r1[cd * PL + scanl[p]];
+        for (int t = 0; t < PL / 64; ++t) {
+            const int p = lane + 64 * t;
+            const int tc = SH.r1[cd * PL + scan_word_origin(scan_batch_word(LGL, t), row) + scan_nib_offset(LGL, nib)];
             nzl |= tc;
             tcs[cd * PL + p] = (int16_t)tc;
             if (first == PL) {
@@ -891,7 +925,7 @@ __device__ __forceinline__ void quantize_pk(Ctx c, int nc, int* overflow, long l
             const bool mine = blk < nch;
             int tc = 0;
             if (mine) {
-                tc = SH.r1[nL + blk * 16 + scanc[i16]];
+                tc = SH.r1[nL + blk * 16 + nib];
                 nzl |= tc;
                 tcs[nL + blk * 16 + i16] = (int16_t)tc;
             }
@@ -906,7 +940,7 @@ __device__ __forceinline__ void quantize_pk(Ctx c, int nc, int* overflow, long l
         const HeadK hkc = head_consts(shc, offc, lsc);
 #pragma unroll 1
         for (int b = 0; b < nch; ++b) {
-            const int tc = SH.r1[nL + b * PC + scanc[lane]];
+            const int tc = SH.r1[nL + b * PC + scan_word_origin(scan_batch_word(LGL - 1, 0), row) + scan_nib_offset(LGL - 1, nib)];
             nzl |= tc;
             tcs[nL + b * PC + lane] = (int16_t)tc;
             const unsigned long long sig = __ballot(head_sig(tc, htc));
@@ -1076,7 +1110,7 @@ __device__ __forceinline__ void quantize_pk(Ctx c, int nc, int* overflow, long l
         bool a4[4];
         const int s0_ = 16 * __builtin_amdgcn_readlane(v_low, 0), s1_ = 16 * __builtin_amdgcn_readlane(v_low, 1),
                   s2_ = 16 * __builtin_amdgcn_readlane(v_low, 2);
-        trace_rows64(c, nc, tcs, dec16, 0, scanl, shl, offl, l4, a4, ovf, row == 0 ? s0_ : (row == 1 ? s1_ : (row == 2 ? s2_ : 0)));
+        trace_rows64(c, nc, tcs, dec16, 0, shl, offl, l4, a4, ovf, row == 0 ? s0_ : (row == 1 ? s1_ : (row == 2 ? s2_ : 0)));
 #pragma unroll
         for (int b = 0; b < 3; ++b)
             if (b < nc) {
@@ -1086,7 +1120,7 @@ __device__ __forceinline__ void quantize_pk(Ctx c, int nc, int* overflow, long l
 #pragma unroll
         for (int ps = 0; ps < 2; ++ps) {
             if (4 * ps >= nch) continue; // (uniform)
-            trace_rows16(c, min(4, nch - 4 * ps), tcs + nL + 64 * ps, dec16 + 4 * SBL * nc + 16 * ps, nL + 64 * ps, scanc, shc, offc, l4, a4, ovf);
+            trace_rows16(c, min(4, nch - 4 * ps), tcs + nL + 64 * ps, dec16 + 4 * SBL * nc + 16 * ps, nL + 64 * ps, shc, offc, l4, a4, ovf);
 #pragma unroll
             for (int b = 0; b < 4; ++b)
                 if (4 * ps + b < nch) {
@@ -1099,7 +1133,7 @@ __device__ __forceinline__ void quantize_pk(Ctx c, int nc, int* overflow, long l
         for (int cd = 0; cd < nc; ++cd) {
             long long l1;
             bool a1;
-            trace_wave256(c, tcs + cd * PL, dec16 + 4 * SBL * cd, cd * PL, scanl, shl, offl, &l1, &a1, ovf,
+            trace_wave256(c, tcs + cd * PL, dec16 + 4 * SBL * cd, cd * PL, shl, offl, &l1, &a1, ovf,
                           16 * __builtin_amdgcn_readlane(v_low, cd));
             if (cd == 0)
                 lvl_y[0] = l1;
@@ -1111,7 +1145,7 @@ __device__ __forceinline__ void quantize_pk(Ctx c, int nc, int* overflow, long l
         bool a4[4];
         const int s4_ = 16 * __builtin_amdgcn_readlane(v_low, 4), s5_ = 16 * __builtin_amdgcn_readlane(v_low, 5),
                   s6_ = 16 * __builtin_amdgcn_readlane(v_low, 6), s7_ = 16 * __builtin_amdgcn_readlane(v_low, 7);
-        trace_rows64(c, nch, tcs + nL, dec16 + 4 * SBL * nc, nL, scanc, shc, offc, l4, a4, ovf,
+        trace_rows64(c, nch, tcs + nL, dec16 + 4 * SBL * nc, nL, shc, offc, l4, a4, ovf,
                      row == 0 ? s4_ : (row == 1 ? s5_ : (row == 2 ? s6_ : s7_))); // four 8x8 chroma blocks at most
 #pragma unroll
         for (int b = 0; b < 4; ++b)

@@ -41,6 +41,7 @@
 #include "dev_common.h"
 #include "dev_predict.h"
 #include "dev_transform.h"
+#include "dev_scan.h"
 #include "dev_quant.h"
 #include "dev_search.h"
 #define WRENC_TOKENS_KERNEL_TU

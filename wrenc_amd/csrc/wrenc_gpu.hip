@@ -675,7 +675,7 @@ const int8_t kFC[32][4] = {
     {-2, 16, 54, -4}, {-2, 15, 55, -4}, {-2, 14, 56, -4}, {-2, 12, 57, -3}, {-2, 10, 58, -2}, {-1, 7, 60, -2},
     {0, 4, 62, -2},   {0, 2, 63, -1}};
 
-void diag_scan(int lw, int lh, uint8_t (*out)[2]) { // ctu.rs:54-77
+constexpr void diag_scan(int lw, int lh, uint8_t (*out)[2]) { // ctu.rs:54-77
     const int bw = 1 << lw, bh = 1 << lh;
     int i = 0, x = 0, y = 0;
     bool stop = false;
@@ -694,6 +694,31 @@ void diag_scan(int lw, int lh, uint8_t (*out)[2]) { // ctu.rs:54-77
         if (i >= bw * bh) stop = true;
     }
 }
+
+// The quantisers compute the scan (dev_scan.h) where wrenc_gpu_config below fills DevConst::scan_idx for everyone else:
+// the closed form against that construction -- diag_scan and the fill loop, as a constant expression -- for every
+// position of every block size.  A wrong formula does not build.
+constexpr bool scan_closed_form_holds() {
+    for (int idx = 0; idx < 4; ++idx) {
+        const int lg = idx + 2, n = 1 << lg, nsb = 1 << (2 * lg - 4);
+        uint8_t d4[16][2] = {}, dsb[64][2] = {};
+        diag_scan(2, 2, d4);
+        diag_scan(idx, idx, dsb);
+        for (int p = 0; p < n * n; ++p) {
+            const int sb = nsb - 1 - (p >> 4), sp = 15 - (p & 15);
+            const int x = (dsb[sb][0] << 2) + d4[sp][0];
+            const int y = (dsb[sb][1] << 2) + d4[sp][1];
+            if (wrenc::scan_raster(lg, p) != y * n + x) return false;
+            if (wrenc::scan_sb_origin(lg, p >> 4) + wrenc::scan_nib_offset(lg, (int)wrenc::scan_nibs_from(p & 15) & 15) != y * n + x) return false;
+            const int org = wrenc::scan_sb_origin(lg, p >> 4); // ... and the forms the quantisers take the origin in
+            if (wrenc::scan_word_origin(wrenc::scan_batch_word(lg, p >> 6), (p >> 4) & 3) != org) return false;
+            if (lg == 3 && wrenc::scan_sb_origin_ct<3>(p >> 4) != org) return false;
+            if (lg == 4 && wrenc::scan_sb_origin_ct<4>(p >> 4) != org) return false;
+        }
+    }
+    return true;
+}
+static_assert(scan_closed_form_holds(), "dev_scan.h: the closed form differs from the scan table's construction");
 
 } // namespace
 
