@@ -39,6 +39,13 @@ CAND_CUTS = ["cut_leaf4_sad", "cut_leaf4_packB"]
 PRED_BY = ["predict_front32", "predict_front16", "predict_pack16", "predict_pack8_luma", "predict_lane4", "predict_cclm",
            "predict_front_le8", "predict_sad_requests"]
 RECON_BY = ["recon_full_back", "recon_pack16", "recon_pack8", "recon_pass4"]
+# counts of the packed leaf searches (dev_common.h, PH_SPARSE): quantize_pk calls that reach the forward trace; trace passes
+# and, after each, those among them whose chains are all proven zero (not traced); packs with a level among their luma /
+# chroma blocks and, after each, the blocks of those packs that have none (not dequantised, not transformed back)
+SPARSE = ["pk_trace_calls", "pk8_luma_passes", "pk8_luma_passes_proven", "pk8_chroma_passes", "pk8_chroma_passes_proven",
+          "pk16_luma_traces", "pk16_luma_traces_proven", "pk16_chroma_passes", "pk16_chroma_passes_proven",
+          "pack8_luma_packs_with_level", "pack8_luma_blocks_without", "pack16_luma_packs_with_level", "pack16_luma_blocks_without",
+          "pack16_chroma_packs_with_level", "pack16_chroma_blocks_without", "sparse_spare"]
 names = (["predict", "fdct", "q_pre", "q_back", "q_trace", "deq", "idct", "recon", "total", "ctrl", "refs", "skip", "nstep", "nfull"]
          + ["stages_t%d_c%d" % (4 << (i // 2), i % 2) for i in range(8)] + ["x"] + ["stages_n%d_c%d" % (4 << (i // 2), i % 2) for i in range(8)]
          + ["x2", "qb_pre", "qb_wait1", "qb_walk", "qb_wait2", "t_xchg", "copy"] + ["cb%d" % i for i in range(32)] + ["y"]
@@ -48,7 +55,7 @@ names = (["predict", "fdct", "q_pre", "q_back", "q_trace", "deq", "idct", "recon
          + ["leaf8_packA", "leaf8_sad", "leaf8_packB", "leaf8_cclm", "leaf16_packA", "leaf16_sad", "leaf16_packB", "leaf16_packC",
             "sad_tables", "sad_blocks", "sad_samples", "leaf8_cclm_sad", "sad_lines"] + ["y9"]
          + ["leaf4_stage", "leaf4_packA", "leaf4_sad", "leaf4_packB", "leafc4", "split8_other"] + ["y10"] + ["hist%d" % i for i in range(64)]
-         + ["y11"] + CUTS + FLOOR_CUTS + CAND_CUTS + ["y12"] + PRED_BY + ["y13"] + RECON_BY)
+         + ["y11"] + CUTS + FLOOR_CUTS + CAND_CUTS + ["y12"] + PRED_BY + ["y13"] + RECON_BY + ["y14"] + SPARSE)
 KINDS = ["sadlist", "full", "nop/copy", "sadsearch", "cclmsearch", "serve8", "?", "leaf8", "leaf16", "split8", "serve4", "node8"] + ["?"] * 4
 N = len(names)
 out = (C.c_ulonglong * N)()
@@ -74,6 +81,9 @@ for i, n in enumerate(names):
         continue
     if n in FLOOR_CUTS:
         print("%-16s %10.2f per CTU (cuts the floors decided and the partial sum did not)" % (n, out[i] / nctu))
+        continue
+    if n in SPARSE:
+        print("%-32s %10.2f per CTU (count)" % (n, out[i] / nctu))
         continue
     if n in CAND_CUTS:
         print("%-16s %10.2f per CTU (searched 4x4 luma leaves that skipped %s)" % (n, out[i] / nctu, "the SAD search and pack B" if n.endswith("sad") else "pack B alone"))

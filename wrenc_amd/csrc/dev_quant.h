@@ -707,7 +707,8 @@ __device__ __forceinline__ int dequantize4_lane(const Ctx& c, int level) {
 // candidate between two workgroup barriers per 64 positions.  Same arithmetic as quantize_solo: chunk_entry, the
 // one-compare walk, the forward trace by composed state maps, emit_level.  Levels in place; per candidate the level
 // cost of the luma block and of the chroma pair (block_splitter.rs:436-458) and whether any level of the pack's luma /
-// chroma blocks is non-zero.
+// chroma blocks is non-zero.  A chroma trace pass runs only where one of its chains has something to trace: a chain
+// proven zero from end to end keeps the zeros of the zero-fill, costs nothing and has no level.
 // Scratch: r2[0, 3 PL nc) scan-order coefficients, r1 chunk entries, decw decisions (72 / 192 u16), q_pm.
 // ---------------------------------------------------------------------------
 
@@ -1105,9 +1106,19 @@ __device__ __forceinline__ void quantize_pk(Ctx c, int nc, int* overflow, long l
     //      the levels before that are zero: the chunk entries in r1 are dead, zero all of the pack's levels first ----
     for (int i = lane; i < (nL + nch * PC) / 8; i += 64) *(uint4*)&SH.r1[8 * i] = make_uint4(0u, 0u, 0u, 0u);
     WSYNC();
+    // The chains that still have something to trace (uniform; bit = lane of v_low).  A chain proven zero from end to end
+    // has the zero levels just written, level cost 0 (pf = the block length: the lv[0] term never fires) and no level;
+    // a chain that failed its head test has v_low = 0 again and is traced from its first position.  The chroma passes
+    // are skipped where none of their chains is live (nine in ten of them on the bench's content); the luma traces are
+    // not looked at: a pack gets here because of a luma chain nearly always.
+    const unsigned live = (unsigned)__ballot(lane < 12 && (lane < nc || (lane >= 4 && lane < 4 + nch)) && v_low < (lane < 4 ? SBL : SBC));
+    PROF_CNT(PH_SPARSE + 0, 1);
+    int n_with = 0; // (profile build: the blocks of a kind that have a level)
     if constexpr (LGL == 3) {
         long long l4[4];
         bool a4[4];
+        PROF_CNT(PH_SPARSE + 1, 1);
+        PROF_CNT(PH_SPARSE + 2, (live & 0x7u) == 0);
         const int s0_ = 16 * __builtin_amdgcn_readlane(v_low, 0), s1_ = 16 * __builtin_amdgcn_readlane(v_low, 1),
                   s2_ = 16 * __builtin_amdgcn_readlane(v_low, 2);
         trace_rows64(c, nc, tcs, dec16, 0, shl, offl, l4, a4, ovf, row == 0 ? s0_ : (row == 1 ? s1_ : (row == 2 ? s2_ : 0)));
@@ -1116,10 +1127,18 @@ __device__ __forceinline__ void quantize_pk(Ctx c, int nc, int* overflow, long l
             if (b < nc) {
                 lvl_y[b] = l4[b];
                 if (a4[b]) *any_y = true;
+                n_with += a4[b];
             }
+        PROF_CNT(PH_SPARSE + 9, n_with != 0);
+        PROF_CNT(PH_SPARSE + 10, n_with ? nc - n_with : 0);
 #pragma unroll
         for (int ps = 0; ps < 2; ++ps) {
             if (4 * ps >= nch) continue; // (uniform)
+            PROF_CNT(PH_SPARSE + 3, 1);
+            if (!(live & (0xF0u << (4 * ps)))) { // (uniform) every chain of the pass is proven zero
+                PROF_CNT(PH_SPARSE + 4, 1);
+                continue;
+            }
             trace_rows16(c, min(4, nch - 4 * ps), tcs + nL + 64 * ps, dec16 + 4 * SBL * nc + 16 * ps, nL + 64 * ps, shc, offc, l4, a4, ovf);
 #pragma unroll
             for (int b = 0; b < 4; ++b)
@@ -1133,6 +1152,8 @@ __device__ __forceinline__ void quantize_pk(Ctx c, int nc, int* overflow, long l
         for (int cd = 0; cd < nc; ++cd) {
             long long l1;
             bool a1;
+            PROF_CNT(PH_SPARSE + 5, 1);
+            PROF_CNT(PH_SPARSE + 6, ((live >> cd) & 1u) == 0);
             trace_wave256(c, tcs + cd * PL, dec16 + 4 * SBL * cd, cd * PL, shl, offl, &l1, &a1, ovf,
                           16 * __builtin_amdgcn_readlane(v_low, cd));
             if (cd == 0)
@@ -1140,20 +1161,33 @@ __device__ __forceinline__ void quantize_pk(Ctx c, int nc, int* overflow, long l
             else
                 lvl_y[1] = l1;
             if (a1) *any_y = true;
+            n_with += a1;
         }
-        long long l4[4];
-        bool a4[4];
-        const int s4_ = 16 * __builtin_amdgcn_readlane(v_low, 4), s5_ = 16 * __builtin_amdgcn_readlane(v_low, 5),
-                  s6_ = 16 * __builtin_amdgcn_readlane(v_low, 6), s7_ = 16 * __builtin_amdgcn_readlane(v_low, 7);
-        trace_rows64(c, nch, tcs + nL, dec16 + 4 * SBL * nc, nL, shc, offc, l4, a4, ovf,
-                     row == 0 ? s4_ : (row == 1 ? s5_ : (row == 2 ? s6_ : s7_))); // four 8x8 chroma blocks at most
+        PROF_CNT(PH_SPARSE + 11, n_with != 0);
+        PROF_CNT(PH_SPARSE + 12, n_with ? nc - n_with : 0);
+        PROF_CNT(PH_SPARSE + 7, 1);
+        if (live & 0xF0u) { // (uniform)
+            long long l4[4];
+            bool a4[4];
+            const int s4_ = 16 * __builtin_amdgcn_readlane(v_low, 4), s5_ = 16 * __builtin_amdgcn_readlane(v_low, 5),
+                      s6_ = 16 * __builtin_amdgcn_readlane(v_low, 6), s7_ = 16 * __builtin_amdgcn_readlane(v_low, 7);
+            trace_rows64(c, nch, tcs + nL, dec16 + 4 * SBL * nc, nL, shc, offc, l4, a4, ovf,
+                         row == 0 ? s4_ : (row == 1 ? s5_ : (row == 2 ? s6_ : s7_))); // four 8x8 chroma blocks at most
+            n_with = 0;
 #pragma unroll
-        for (int b = 0; b < 4; ++b)
-            if (b < nch) {
-                lvl_c[b >> 1] += l4[b];
-                if (a4[b]) *any_c = true;
-            }
+            for (int b = 0; b < 4; ++b)
+                if (b < nch) {
+                    lvl_c[b >> 1] += l4[b];
+                    if (a4[b]) *any_c = true;
+                    n_with += a4[b];
+                }
+            PROF_CNT(PH_SPARSE + 13, n_with != 0);
+            PROF_CNT(PH_SPARSE + 14, n_with ? nch - n_with : 0);
+        } else { // every chroma chain is proven zero
+            PROF_CNT(PH_SPARSE + 8, 1);
+        }
     }
+    (void)n_with;
     if (__ballot(ovf != 0) != 0ULL) *overflow = 1;
     WSYNC();
     PROF_MARK(q3_);
