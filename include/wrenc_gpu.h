@@ -499,6 +499,26 @@ int wrenc_gpu_test_quantize_p16(wrenc_gpu_ctx* ctx, const int16_t* coef, int cou
                                 int64_t* level_cost);
 int wrenc_gpu_test_dequantize(wrenc_gpu_ctx* ctx, const int16_t* levels, int log2n, int count,
                               int16_t* deq);                            /* quantizer.rs:761 */
+/* The same device functions as the search calls them: on GROUPS of blocks.  Each entry runs `count` groups, one wavefront
+ * per group; a group is `nb` blocks of side 1 << log2n back to back, [blk][y][x] row-major int16, and the outputs have the
+ * same layout.  The one-block entries above are these with nb = 1, o1 = 0 (one kernel per device function).
+ *   _quantize_nb: nb = 1 (a luma block) or 2 (the Cb + Cr pair of a CU: quantize_solo's two-block path) at r1[0 ..];
+ *       level_cost[g]: the summed level cost of group g's blocks, any_level[g]: 1 where the device function reported a
+ *       non-zero level in the group (what decides whether its caller dequantises and inverts at all), else 0; may be null.
+ *       Its own overflow word, WRENC_GPU_ELEVEL and the clean next call exactly as wrenc_gpu_test_quantize.
+ *   _fwd_dct_nb / _inv_dct_nb / _dequantize_nb: the group's blocks sit at r1[o1 ..] (i16 units), where the search puts a
+ *       pack's chroma behind its luma; the inverse transform's input goes to r2 transposed block by block, and the
+ *       dequantiser's output is read back from there the same way.
+ * Refused with WRENC_GPU_EINVAL before anything is launched -- the device functions are not written for these, or the
+ * group would leave the wavefront's buffers (r1 and r2: 1024 int16 each): nb < 1, nb > 2 for the quantiser; log2n = 5
+ * with nb > 1; o1 odd or negative; o1 + nb * 4^log2n > 1024; nb * 4^log2n > 1024; and a 32x32 residual outside +-255
+ * for the forward transform. */
+int wrenc_gpu_test_quantize_nb(wrenc_gpu_ctx* ctx, const int16_t* coef, int log2n, int nb, int count, int16_t* levels,
+                               int64_t* level_cost, int32_t* any_level);
+int wrenc_gpu_test_fwd_dct_nb(wrenc_gpu_ctx* ctx, const int16_t* res, int log2n, int nb, int o1, int count, int16_t* coef);
+int wrenc_gpu_test_inv_dct_nb(wrenc_gpu_ctx* ctx, const int16_t* deq, int log2n, int nb, int o1, int count, int16_t* res);
+int wrenc_gpu_test_dequantize_nb(wrenc_gpu_ctx* ctx, const int16_t* levels, int log2n, int nb, int o1, int count,
+                                 int16_t* deq);
 /* The register transforms of the search's 4x4 passes (wrenc_amd/csrc/dev_transform.h fwd_dct4_reg / inv_dct4_reg): `count`
  * 4x4 blocks, row-major int16, four per wavefront with one sample per lane, a last wavefront of fewer included.
  * fwd: residuals -> coefficients (transformer.rs:2040).  inv: LEVELS -> residuals, dequantised in the lane at the

@@ -269,16 +269,18 @@ __global__ __launch_bounds__(64 * WPB, 5) void ctu_search_team_kernel(const DevC
     release_scratch(slot_map, scratch_slot);
 }
 
-// building-block kernels: one wave per block of side 1 << lg
+// building-block kernels: one wave per group of nb blocks of side 1 << lg, laid out [blk][y][x]; the transforms and the
+// dequantiser work on r1[o1 ..], where the search puts a pack's chroma behind its luma (the host entries check that the
+// group fits r1 and r2)
 __global__ __launch_bounds__(64) void test_fwd_dct_kernel(const DevConst* __restrict__ k,
-                                                          const int16_t* in, int lg, int16_t* out) {
+                                                          const int16_t* in, int lg, int nb, int o1, int16_t* out) {
     Ctx c = {};
     c.k = (const CONST_AS DevConst*)k;
-    const int nn = 1 << (2 * lg);
-    for (int i = threadIdx.x; i < nn; i += 64) SH.r1[i] = in[(size_t)blockIdx.x * nn + i];
+    const int total = nb << (2 * lg);
+    for (int i = threadIdx.x; i < total; i += 64) SH.r1[o1 + i] = in[(size_t)blockIdx.x * total + i];
     WSYNC();
-    fwd_dct_lg(c, lg, 1);
-    for (int i = threadIdx.x; i < nn; i += 64) out[(size_t)blockIdx.x * nn + i] = SH.r1[i];
+    fwd_dct_lg(c, lg, nb, o1);
+    for (int i = threadIdx.x; i < total; i += 64) out[(size_t)blockIdx.x * total + i] = SH.r1[o1 + i];
 }
 
 // MFMA experiment: the 32x32 forward transform as i8 MFMAs (dev_transform.h); `reps` repeats the transform
@@ -317,32 +319,37 @@ __global__ __launch_bounds__(64) void test_inv_dct32_kernel(const DevConst* __re
 }
 
 __global__ __launch_bounds__(64) void test_inv_dct_kernel(const DevConst* __restrict__ k,
-                                                          const int16_t* in, int lg, int16_t* out) {
+                                                          const int16_t* in, int lg, int nb, int o1, int16_t* out) {
     Ctx c = {};
     c.k = (const CONST_AS DevConst*)k;
-    const int n = 1 << lg, nn = n * n;
-    for (int i = threadIdx.x; i < nn; i += 64) // transposed load: dT[x][i] = d[i][x]
-        ((int16_t*)SH.r2)[(i & (n - 1)) * n + (i >> lg)] = in[(size_t)blockIdx.x * nn + i];
+    const int n = 1 << lg, nn = n * n, total = nb * nn;
+    for (int i = threadIdx.x; i < total; i += 64) { // transposed load, block by block: dT[blk][x][i] = d[blk][i][x]
+        const int ii = i & (nn - 1);
+        ((int16_t*)SH.r2)[(i - ii) + (ii & (n - 1)) * n + (ii >> lg)] = in[(size_t)blockIdx.x * total + i];
+    }
     WSYNC();
-    inv_dct_lg(c, lg, 1);
-    for (int i = threadIdx.x; i < nn; i += 64) out[(size_t)blockIdx.x * nn + i] = SH.r1[i];
+    inv_dct_lg(c, lg, nb, o1);
+    for (int i = threadIdx.x; i < total; i += 64) out[(size_t)blockIdx.x * total + i] = SH.r1[o1 + i];
 }
 
+// quantize_solo: nb = 1 (a luma block) or 2 (the Cb + Cr pair) blocks at r1[0 ..]; per group the summed level cost and the
+// *any_level the function reported
 __global__ __launch_bounds__(64) void test_quantize_kernel(const DevConst* __restrict__ k,
-                                                           const int16_t* in, int lg, int16_t* out,
-                                                           long long* cost, int* overflow) {
+                                                           const int16_t* in, int lg, int nb, int16_t* out,
+                                                           long long* cost, int* any_level, int* overflow) {
     Ctx c = {};
     c.k = (const CONST_AS DevConst*)k;
     load_tables(c);
-    const int nn = 1 << (2 * lg);
-    for (int i = threadIdx.x; i < nn; i += 64) SH.r1[i] = in[(size_t)blockIdx.x * nn + i];
+    const int total = nb << (2 * lg);
+    for (int i = threadIdx.x; i < total; i += 64) SH.r1[i] = in[(size_t)blockIdx.x * total + i];
     WSYNC();
     int ovf = 0;
     bool any = false;
-    const long long lc = quantize_solo(c, lg, 1, &ovf, &any);
-    for (int i = threadIdx.x; i < nn; i += 64) out[(size_t)blockIdx.x * nn + i] = SH.r1[i];
+    const long long lc = quantize_solo(c, lg, nb, &ovf, &any);
+    for (int i = threadIdx.x; i < total; i += 64) out[(size_t)blockIdx.x * total + i] = SH.r1[i];
     if (threadIdx.x == 0) {
         cost[blockIdx.x] = lc;
+        any_level[blockIdx.x] = any ? 1 : 0;
         if (ovf) atomicOr(overflow, 1);
     }
 }
@@ -455,15 +462,17 @@ __global__ __launch_bounds__(64) void test_quantize_pk_kernel(const DevConst* __
 }
 
 __global__ __launch_bounds__(64) void test_dequantize_kernel(const DevConst* __restrict__ k,
-                                                             const int16_t* in, int lg, int16_t* out) {
+                                                             const int16_t* in, int lg, int nb, int o1, int16_t* out) {
     Ctx c = {};
     c.k = (const CONST_AS DevConst*)k;
-    const int n = 1 << lg, nn = n * n;
-    for (int i = threadIdx.x; i < nn; i += 64) SH.r1[i] = in[(size_t)blockIdx.x * nn + i];
+    const int n = 1 << lg, nn = n * n, total = nb * nn;
+    for (int i = threadIdx.x; i < total; i += 64) SH.r1[o1 + i] = in[(size_t)blockIdx.x * total + i];
     WSYNC();
-    dequantize_t(c, lg, 1);
-    for (int i = threadIdx.x; i < nn; i += 64) // undo the transpose
-        out[(size_t)blockIdx.x * nn + i] = ((const int16_t*)SH.r2)[(i & (n - 1)) * n + (i >> lg)];
+    dequantize_t(c, lg, nb, o1);
+    for (int i = threadIdx.x; i < total; i += 64) { // undo the transpose, block by block
+        const int ii = i & (nn - 1);
+        out[(size_t)blockIdx.x * total + i] = ((const int16_t*)SH.r2)[(i - ii) + (ii & (n - 1)) * n + (ii >> lg)];
+    }
 }
 
 // Prediction of single blocks in the environment of given reconstruction planes (one wave per item):
@@ -1153,11 +1162,11 @@ void fill_dev_const(const wrenc_gpu_config& cfg, DevConst& k) {
 
 namespace {
 template <class Launch>
-int run_block_test(wrenc_gpu_ctx* ctx, const int16_t* in, int log2n, int count, int16_t* out, Launch launch) {
+int run_block_test(wrenc_gpu_ctx* ctx, const int16_t* in, int log2n, int count, int16_t* out, Launch launch, int nb = 1) {
     if (!ctx || !in || !out) return WRENC_GPU_EINVAL;
-    if (log2n < 2 || log2n > 5 || count < 1) return fail(ctx, WRENC_GPU_EINVAL, "log2n must be 2..5 and count >= 1");
+    if (log2n < 2 || log2n > 5 || count < 1 || nb < 1) return fail(ctx, WRENC_GPU_EINVAL, "log2n must be 2..5 and count >= 1");
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-    const size_t bytes = (size_t)count * sizeof(int16_t) << (2 * log2n);
+    const size_t bytes = (size_t)count * nb * sizeof(int16_t) << (2 * log2n);
     int16_t *d_in = nullptr, *d_out = nullptr;
     HIP_TRY(ctx, hipMalloc((void**)&d_in, bytes));
     hipError_t e = hipMalloc((void**)&d_out, bytes);
@@ -2841,12 +2850,31 @@ static bool residuals_fit_9_bits(const int16_t* res, size_t n) {
     return true;
 }
 
-int wrenc_gpu_test_fwd_dct(wrenc_gpu_ctx* ctx, const int16_t* res, int log2n, int count, int16_t* coef) {
-    if (ctx && res && log2n == 5 && count >= 1 && !residuals_fit_9_bits(res, (size_t)count * 1024))
+// What the group entries refuse, before anything is allocated or launched: a group the device functions are not written
+// for or that does not fit the wave's buffers (r1: 1024 i16 from o1 on; r2: the 1024 i16 of the scan-order or transposed
+// blocks).  nb_max: 2 for the quantiser (a luma block or the Cb + Cr pair).  nullptr = fine.
+static const char* group_shape_error(int log2n, int nb, int o1, int nb_max) {
+    if (log2n < 2 || log2n > 5) return "log2n must be 2..5";
+    if (nb < 1 || nb > nb_max) return "nb outside what the device function takes";
+    if (log2n == 5 && nb > 1) return "a 32x32 block is always alone";
+    if (o1 < 0 || (o1 & 1)) return "o1 must be even and >= 0";
+    if ((nb << (2 * log2n)) > 1024) return "the group does not fit r2";
+    if (o1 + (nb << (2 * log2n)) > 1024) return "the group does not fit r1 behind o1";
+    return nullptr;
+}
+constexpr int kGroupMaxBlocks = 64; // (1024 / 16: group_shape_error's size rules are what bounds a transform group)
+
+int wrenc_gpu_test_fwd_dct_nb(wrenc_gpu_ctx* ctx, const int16_t* res, int log2n, int nb, int o1, int count, int16_t* coef) {
+    if (!ctx || !res || !coef) return WRENC_GPU_EINVAL;
+    if (const char* why = group_shape_error(log2n, nb, o1, kGroupMaxBlocks)) return fail(ctx, WRENC_GPU_EINVAL, why);
+    if (log2n == 5 && count >= 1 && !residuals_fit_9_bits(res, (size_t)count * 1024))
         return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_test_fwd_dct: a 32x32 residual lies outside +-255");
     return run_block_test(ctx, res, log2n, count, coef, [&](int16_t* i, int16_t* o) {
-        hipLaunchKernelGGL(test_fwd_dct_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const, i, log2n, o);
-    });
+        hipLaunchKernelGGL(test_fwd_dct_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const, i, log2n, nb, o1, o);
+    }, nb);
+}
+int wrenc_gpu_test_fwd_dct(wrenc_gpu_ctx* ctx, const int16_t* res, int log2n, int count, int16_t* coef) {
+    return wrenc_gpu_test_fwd_dct_nb(ctx, res, log2n, 1, 0, count, coef);
 }
 // a 32x32 transform micro-benchmark: `count` blocks, `reps` repetitions each, HIP-event duration of the one kernel
 static int run_dct32_bench(wrenc_gpu_ctx* ctx, const int16_t* in, int count, int16_t* out, int use_mfma, int reps,
@@ -2892,10 +2920,15 @@ int wrenc_gpu_test_inv_dct32(wrenc_gpu_ctx* ctx, const int16_t* deq, int count, 
                              float* kernel_ms) {
     return run_dct32_bench(ctx, deq, count, res, use_mfma, reps, kernel_ms, true);
 }
-int wrenc_gpu_test_inv_dct(wrenc_gpu_ctx* ctx, const int16_t* deq, int log2n, int count, int16_t* res) {
+int wrenc_gpu_test_inv_dct_nb(wrenc_gpu_ctx* ctx, const int16_t* deq, int log2n, int nb, int o1, int count, int16_t* res) {
+    if (!ctx || !deq || !res) return WRENC_GPU_EINVAL;
+    if (const char* why = group_shape_error(log2n, nb, o1, kGroupMaxBlocks)) return fail(ctx, WRENC_GPU_EINVAL, why);
     return run_block_test(ctx, deq, log2n, count, res, [&](int16_t* i, int16_t* o) {
-        hipLaunchKernelGGL(test_inv_dct_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const, i, log2n, o);
-    });
+        hipLaunchKernelGGL(test_inv_dct_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const, i, log2n, nb, o1, o);
+    }, nb);
+}
+int wrenc_gpu_test_inv_dct(wrenc_gpu_ctx* ctx, const int16_t* deq, int log2n, int count, int16_t* res) {
+    return wrenc_gpu_test_inv_dct_nb(ctx, deq, log2n, 1, 0, count, res);
 }
 int wrenc_gpu_test_fwd_dct4_reg(wrenc_gpu_ctx* ctx, const int16_t* res, int count, int16_t* coef) {
     return run_block_test(ctx, res, 2, count, coef, [&](int16_t* i, int16_t* o) {
@@ -2907,28 +2940,47 @@ int wrenc_gpu_test_inv_dct4_reg(wrenc_gpu_ctx* ctx, const int16_t* levels, int c
         hipLaunchKernelGGL(test_dct4_reg_kernel, dim3((count + 3) / 4), dim3(64), 0, ctx->stream, ctx->d_const, i, count, 1, o);
     });
 }
-int wrenc_gpu_test_dequantize(wrenc_gpu_ctx* ctx, const int16_t* levels, int log2n, int count, int16_t* deq) {
+int wrenc_gpu_test_dequantize_nb(wrenc_gpu_ctx* ctx, const int16_t* levels, int log2n, int nb, int o1, int count, int16_t* deq) {
+    if (!ctx || !levels || !deq) return WRENC_GPU_EINVAL;
+    if (const char* why = group_shape_error(log2n, nb, o1, kGroupMaxBlocks)) return fail(ctx, WRENC_GPU_EINVAL, why);
     return run_block_test(ctx, levels, log2n, count, deq, [&](int16_t* i, int16_t* o) {
-        hipLaunchKernelGGL(test_dequantize_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const, i, log2n, o);
-    });
+        hipLaunchKernelGGL(test_dequantize_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const, i, log2n, nb, o1, o);
+    }, nb);
 }
-int wrenc_gpu_test_quantize(wrenc_gpu_ctx* ctx, const int16_t* coef, int log2n, int count, int16_t* levels,
-                            int64_t* level_cost) {
-    if (!ctx || !level_cost) return WRENC_GPU_EINVAL;
+int wrenc_gpu_test_dequantize(wrenc_gpu_ctx* ctx, const int16_t* levels, int log2n, int count, int16_t* deq) {
+    return wrenc_gpu_test_dequantize_nb(ctx, levels, log2n, 1, 0, count, deq);
+}
+// (any_level may be null: the one-block entry does not hand it on)
+int wrenc_gpu_test_quantize_nb(wrenc_gpu_ctx* ctx, const int16_t* coef, int log2n, int nb, int count, int16_t* levels,
+                               int64_t* level_cost, int32_t* any_level) {
+    if (!ctx || !coef || !levels || !level_cost) return WRENC_GPU_EINVAL;
+    if (const char* why = group_shape_error(log2n, nb, 0, 2)) return fail(ctx, WRENC_GPU_EINVAL, why);
     if (count < 1) return fail(ctx, WRENC_GPU_EINVAL, "count must be >= 1");
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
     long long* d_cost = nullptr;
+    int* d_any = nullptr;
     HIP_TRY(ctx, hipMalloc((void**)&d_cost, sizeof(long long) * count));
+    hipError_t ea = hipMalloc((void**)&d_any, sizeof(int) * count);
+    if (ea != hipSuccess) {
+        (void)hipFree(d_cost);
+        return fail(ctx, WRENC_GPU_EHIP, hipGetErrorString(ea));
+    }
     int rc = run_block_test(ctx, coef, log2n, count, levels, [&](int16_t* i, int16_t* o) {
-        hipLaunchKernelGGL(test_quantize_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const, i, log2n, o,
-                           d_cost, ctx->d_overflow + 1);
-    });
+        hipLaunchKernelGGL(test_quantize_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const, i, log2n, nb, o,
+                           d_cost, d_any, ctx->d_overflow + 1);
+    }, nb);
     if (rc == WRENC_GPU_OK) {
         hipError_t e = hipMemcpy(level_cost, d_cost, sizeof(long long) * count, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && any_level) e = hipMemcpy(any_level, d_any, sizeof(int) * count, hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(ctx, WRENC_GPU_EHIP, hipGetErrorString(e));
     }
     (void)hipFree(d_cost);
+    (void)hipFree(d_any);
     return take_test_overflow(ctx, rc);
+}
+int wrenc_gpu_test_quantize(wrenc_gpu_ctx* ctx, const int16_t* coef, int log2n, int count, int16_t* levels,
+                            int64_t* level_cost) {
+    return wrenc_gpu_test_quantize_nb(ctx, coef, log2n, 1, count, levels, level_cost, nullptr);
 }
 
 int wrenc_gpu_test_quantize_p16(wrenc_gpu_ctx* ctx, const int16_t* coef, int count, int16_t* levels, int64_t* level_cost) {

@@ -22,7 +22,8 @@ EXPORTED_SYMBOLS = [
     "wrenc_gpu_upload", "wrenc_gpu_encode", "wrenc_gpu_set_slot_qp", "wrenc_gpu_sync", "wrenc_gpu_download", "wrenc_gpu_download_compact", "wrenc_gpu_compact_mask_words", "wrenc_gpu_expand_levels", "wrenc_gpu_download_tokens", "wrenc_gpu_download_metrics", "wrenc_gpu_download_complexity", "wrenc_gpu_metrics_values", "wrenc_gpu_test_metrics", "wrenc_gpu_test_load_record", "wrenc_gpu_device_info",
     "wrenc_gpu_alloc_host", "wrenc_gpu_free_host", "wrenc_gpu_encode_picture", "wrenc_gpu_set_schedule", "wrenc_gpu_last_schedule", "wrenc_gpu_stats_enable", "wrenc_gpu_last_encode_stats", "wrenc_gpu_last_encode_kernel_stats", "wrenc_gpu_final_pass_mismatches",
     "wrenc_gpu_test_fwd_dct", "wrenc_gpu_test_inv_dct", "wrenc_gpu_test_quantize",
-    "wrenc_gpu_test_dequantize", "wrenc_gpu_test_predict", "wrenc_gpu_test_fwd_dct32", "wrenc_gpu_test_inv_dct32", "wrenc_gpu_test_quantize_p16", "wrenc_gpu_test_quantize_pk", "wrenc_gpu_test_fwd_dct4_reg", "wrenc_gpu_test_inv_dct4_reg", "wrenc_gpu_test_set_wave_slots", "wrenc_gpu_test_scratch_overflows", "wrenc_gpu_test_head_ranges", "wrenc_gpu_test_avail_tab",
+    "wrenc_gpu_test_fwd_dct_nb", "wrenc_gpu_test_inv_dct_nb", "wrenc_gpu_test_quantize_nb", "wrenc_gpu_test_dequantize_nb",
+    "wrenc_gpu_test_dequantize","wrenc_gpu_test_predict", "wrenc_gpu_test_fwd_dct32", "wrenc_gpu_test_inv_dct32", "wrenc_gpu_test_quantize_p16", "wrenc_gpu_test_quantize_pk", "wrenc_gpu_test_fwd_dct4_reg", "wrenc_gpu_test_inv_dct4_reg", "wrenc_gpu_test_set_wave_slots", "wrenc_gpu_test_scratch_overflows", "wrenc_gpu_test_head_ranges", "wrenc_gpu_test_avail_tab",
     "wrenc_gpu_set_visible_size", "wrenc_gpu_visible_size", "wrenc_gpu_test_download_originals",
     "wrenc_gpu_set_source_size", "wrenc_gpu_source_size", "wrenc_gpu_scale_taps",
     "wrenc_gpu_set_source_format", "wrenc_gpu_source_format", "wrenc_gpu_upload_planes",
@@ -237,6 +238,11 @@ def load_library():
                                                                C.c_void_p]
         lib.wrenc_gpu_test_quantize.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                                 C.c_void_p]
+        for name in ("fwd_dct_nb", "inv_dct_nb", "dequantize_nb"):   # (ctx, in, log2n, nb, o1, count, out)
+            getattr(lib, "wrenc_gpu_test_" + name).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                               C.c_void_p]
+        lib.wrenc_gpu_test_quantize_nb.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p]
         _lib = lib
     return _lib
 
@@ -719,6 +725,37 @@ class Encoder:
 
     def dequantize(self, blocks):
         return self._blocks(self.lib.wrenc_gpu_test_dequantize, blocks)
+
+    # ---- the same device functions on groups of blocks, as the search calls them ----
+    def _groups(self, fn, groups, o1):
+        arr = np.ascontiguousarray(groups, np.int16)
+        count, nb, n, _ = arr.shape
+        out = np.zeros_like(arr)
+        self._check(fn(self.ctx, _p(arr), int(n).bit_length() - 1, nb, int(o1), count, _p(out)))
+        return out
+
+    def fwd_dct_groups(self, groups, o1=0):
+        """groups: (count, nb, n, n) residuals, a group's blocks at r1[o1 ..] of its wavefront; coefficients, same shape."""
+        return self._groups(self.lib.wrenc_gpu_test_fwd_dct_nb, groups, o1)
+
+    def inv_dct_groups(self, groups, o1=0):
+        return self._groups(self.lib.wrenc_gpu_test_inv_dct_nb, groups, o1)
+
+    def dequantize_groups(self, groups, o1=0):
+        return self._groups(self.lib.wrenc_gpu_test_dequantize_nb, groups, o1)
+
+    def quantize_groups(self, groups):
+        """groups: (count, nb, n, n) coefficients, nb = 1 or 2 (the Cb + Cr pair through quantize_solo's two-block path).
+        Returns (levels, summed level cost per group, whether the device function reported a level per group)."""
+        arr = np.ascontiguousarray(groups, np.int16)
+        count, nb, n, _ = arr.shape
+        out = np.zeros_like(arr)
+        cost = np.zeros(count, np.int64)
+        any_level = np.full(count, -1, np.int32)
+        self._check(self.lib.wrenc_gpu_test_quantize_nb(self.ctx, _p(arr), int(n).bit_length() - 1, nb, count, _p(out),
+                                                        _p(cost), _p(any_level)))
+        assert np.isin(any_level, (0, 1)).all(), "a group's any_level was not written"
+        return out, cost, any_level == 1
 
     def _blocks4_reg(self, fn, blocks):
         arr = np.ascontiguousarray(blocks, np.int16)
