@@ -1,0 +1,56 @@
+// host_mem.h -- device memory with an owner (host code only).  The one place that allocates and frees device memory:
+// what a context or a test entry holds in a DevBuf is freed when the holder goes, on every path.
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+namespace wrenc {
+
+// `count` elements of T on the current device, or nothing.  Movable, not copyable; the destructor frees.
+template <class T>
+class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr, o.n_ = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            reset();
+            p_ = o.p_, n_ = o.n_;
+            o.p_ = nullptr, o.n_ = 0;
+        }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+
+    // replaces what is held by `count` elements (contents dropped).  On failure nothing is held and HIP's last error is
+    // cleared, so that the next launch check (hipGetLastError) does not report the failed allocation as its own.
+    hipError_t alloc(size_t count) {
+        reset();
+        void* p = nullptr;
+        const hipError_t e = hipMalloc(&p, count * sizeof(T));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return e;
+        }
+        p_ = static_cast<T*>(p);
+        n_ = count;
+        return hipSuccess;
+    }
+    // at least `count` elements: what is held stays where it is enough, else alloc
+    hipError_t grow(size_t count) { return p_ && n_ >= count ? hipSuccess : alloc(count); }
+    void reset() {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+        n_ = 0;
+    }
+    T* get() const { return p_; }
+    size_t count() const { return n_; }
+    explicit operator bool() const { return p_ != nullptr; }
+
+private:
+    T* p_ = nullptr;
+    size_t n_ = 0;
+};
+
+} // namespace wrenc

@@ -17,9 +17,12 @@
 
 #include <hip/hip_runtime.h>
 
+#include "host_mem.h"
+
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -746,22 +749,31 @@ struct wrenc_gpu_ctx {
     std::vector<hipEvent_t> lane_done;
     hipEvent_t ev_fork = nullptr;
     hipEvent_t last_done = nullptr;            // completion event of the most recent encode call
-    DevConst* d_const = nullptr;
+    // Device memory belongs to DevBuf members (host_mem.h): `delete ctx` frees it, wrenc_gpu_destroy lists none of it.
+    DevBuf<DevConst> d_const;
     // per-picture QP (wrenc_gpu_set_slot_qp): one constant block per QP in use, built on first use and kept until destroy
     // (a call in flight may read it); the QP of every slot (-1: the context's); per encode call in flight (ring of
-    // enc_events), the call's picture list and its groups, host copy kept until the call is done
-    DevConst* d_qconst[64] = {};
-    wrenc_gpu_config* qcfg[64] = {};           // the per-QP config a block was built from (its lambdas are the QP's)
+    // enc_events), the call's picture list and its groups (grown on demand), host copy kept until the call is done
+    DevBuf<DevConst> d_qconst[64];
+    std::unique_ptr<wrenc_gpu_config> qcfg[64]; // the per-QP config a block was built from (its lambdas are the QP's)
     std::vector<int> slot_qp;
     struct CallList {
-        PicBufs* d_pics = nullptr;
-        CallGroup* d_groups = nullptr;
-        int cap = 0;                            // entries of d_pics (d_groups: cap / WPB)
+        DevBuf<PicBufs> d_pics;
+        DevBuf<CallGroup> d_groups;             // (one per WPB entries of d_pics)
         std::vector<PicBufs> pics;
         std::vector<CallGroup> groups;
     };
     std::vector<CallList> call_lists;
-    PicBufs* d_slots = nullptr;
+    // what a slot's PicBufs points into: Y | Cb | Cr as one slab each for originals, reconstruction and levels
+    struct SlotMem {
+        DevBuf<uint8_t> org, org_t, border, rec;
+        DevBuf<int16_t> lev;
+        DevBuf<uint32_t> lev_dirty;
+        DevBuf<uint8_t> cu_log2, luma_mode, chroma_mode;
+        DevBuf<float> ctu_cost;
+    };
+    std::vector<SlotMem> slot_mem;
+    DevBuf<PicBufs> d_slots;
     std::vector<PicBufs> slots;
     std::vector<int> state; // 0 empty, 1 uploaded, 2 encoded
     // the size of the caller's pictures (wrenc_gpu_set_visible_size); the coded size unless one is set
@@ -772,59 +784,54 @@ struct wrenc_gpu_ctx {
     // on copy_stream, in order, so a picture is scaled out of them before the next one is copied in), the filter's tables
     // (one allocation) and the kernel's arguments but for the slot
     int src_w = 0, src_h = 0;
-    uint8_t* d_stage = nullptr;
-    void* d_scale_tab = nullptr;
+    DevBuf<uint8_t> d_stage, d_scale_tab;
     ScaleArgs scale_args = {};
     // the format of the caller's pictures (wrenc_gpu_set_source_format; 0: planar 8-bit 4:2:0, the plain upload) and the raw
     // staging planes wrenc_gpu_upload_planes copies them into as they come: one set per context, like the scaler's and by
-    // the same argument, allocated for d_raw_bytes when the format is set or, where the sizes came later, at the first upload
+    // the same argument, allocated when the format is set or, where the sizes came later, at the first upload
     int src_format = 0;
-    uint8_t* d_raw = nullptr;
-    size_t d_raw_bytes = 0;
-    unsigned long long* d_mismatch = nullptr;
-    int* d_overflow = nullptr;
-    uint8_t* d_pred_scratch = nullptr; // kScratchSlots x WPB x kWaveScratch: saved reconstructions (dev_search.h copy_block)
-    unsigned long long* d_slot_map = nullptr; // kScratchSlots bits: scratch regions in use
+    DevBuf<uint8_t> d_raw;
+    DevBuf<unsigned long long> d_mismatch;
+    DevBuf<int> d_overflow;
+    // made by the first encode call, both or neither:
+    DevBuf<uint8_t> d_pred_scratch; // kScratchSlots x WPB x kWaveScratch: saved reconstructions (dev_search.h copy_block)
+    DevBuf<unsigned long long> d_slot_map; // kScratchSlots bits: scratch regions in use
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     std::vector<hipEvent_t> ev_pool;
     int last_launches = 0;
     std::vector<char> launch_team;             // per launch of the last call: the team kernel?
     std::vector<long long> launch_ctus;        // ... and the CTU-pictures it searched
     bool stats_enabled = false; // per-launch timing events: bench / profiling only (wrenc_gpu_stats_enable)
-    // compact read-back: device scratch for one call (masks, payloads with room for every block, counts), grown on demand
-    uint32_t* d_cmask = nullptr;
-    int16_t* d_cpayload = nullptr;
-    unsigned* d_ccount = nullptr;
-    int compact_cap = 0; // pictures the scratch holds
+    // Per-call scratch of the read-backs that wait for the search, grown on demand: each call asks its buffers for what
+    // its pictures need (DevBuf::grow), and a buffer that is large enough stays.
+    // compact read-back: masks, payloads with room for every block, counts
+    DevBuf<uint32_t> d_cmask;
+    DevBuf<int16_t> d_cpayload;
+    DevBuf<unsigned> d_ccount;
     // token read-back: the page pool of one call, its allocation counter, the CTUs' first pages
-    uint32_t* d_tok_pool = nullptr;
-    size_t tok_pool_words = 0;
-    unsigned* d_tok_counter = nullptr;
-    uint32_t* d_tok_first = nullptr;
-    int tok_first_cap = 0;
-    // metrics read-back: the waves' partial sums of one call and the pictures' totals, grown on demand
-    MetricsPartial* d_mpartial = nullptr;
-    MetricsSums* d_msums = nullptr;
-    int metrics_cap = 0; // pictures the scratch holds
+    DevBuf<uint32_t> d_tok_pool;
+    DevBuf<unsigned> d_tok_counter;
+    DevBuf<uint32_t> d_tok_first;
+    // metrics read-back: the waves' partial sums of one call and the pictures' totals
+    DevBuf<MetricsPartial> d_mpartial;
+    DevBuf<MetricsSums> d_msums;
     // hash read-back (made on first use: a context that never asks launches and allocates what it always did): a stream
     // of its own -- an MD5 pass is long, and on the copy stream it would stand in front of the next batch's uploads --,
     // the CRC's tables, the waves' partials of one call and the pictures' values, grown on demand
     hipStream_t hash_stream = nullptr;
-    HashTables* d_htables = nullptr;
-    uint32_t* d_hpartial = nullptr;
-    wrenc_picture_hash* d_hvalues = nullptr;
-    int hash_cap = 0; // pictures the scratch holds
+    DevBuf<HashTables> d_htables;
+    DevBuf<uint32_t> d_hpartial;
+    DevBuf<wrenc_picture_hash> d_hvalues;
     hipEvent_t hash_ev[2] = {nullptr, nullptr}; // measurement mode (stats_enabled): around the last hash pass
     bool hash_timed = false;
     // complexity read-back: the waves' triples, the pictures' totals and CTU maps of one call, for every slot at once
     // (allocated on first use and never again: a later call must not free device memory under a search in flight)
-    ComplexityPartial* d_xpartial = nullptr;
-    ComplexityPartial* d_xsums = nullptr;
-    uint32_t* d_xmap = nullptr;
+    DevBuf<ComplexityPartial> d_xpartial, d_xsums;
+    DevBuf<uint32_t> d_xmap;
     // rate histogram read-back: the waves' counts of one call and the pictures' tables, for every slot at once (allocated
     // on first use and never again, as the complexity scratch)
-    RateHistPartial* d_rpartial = nullptr;
-    RateHistCounts* d_rsums = nullptr;
+    DevBuf<RateHistPartial> d_rpartial;
+    DevBuf<RateHistCounts> d_rsums;
     int schedule = WRENC_GPU_SCHEDULE_AUTO;
     int last_schedule = WRENC_GPU_SCHEDULE_WAVE; // what the most recent encode call ran
     bool stats_valid = false;
@@ -842,11 +849,15 @@ int fail(wrenc_gpu_ctx* ctx, int code, const std::string& msg) {
     return code;
 }
 
+// returns WRENC_GPU_EHIP where `expr` fails.  HIP's last error is cleared then, so that the next call's launch check
+// (hipGetLastError) does not report this failure as its own; what the caller holds in DevBufs is freed by the return.
 #define HIP_TRY(ctx, expr)                                                                        \
     do {                                                                                          \
         hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess)                                                                     \
+        if (e_ != hipSuccess) {                                                                   \
+            (void)hipGetLastError();                                                              \
             return fail(ctx, WRENC_GPU_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+        }                                                                                         \
     } while (0)
 
 size_t plane_bytes(const wrenc_gpu_config& c, int comp, size_t elem) {
@@ -856,11 +867,13 @@ size_t plane_bytes(const wrenc_gpu_config& c, int comp, size_t elem) {
 
 // ---- the steps the read-back entry points share (wrenc_gpu_sync, wrenc_gpu_download, _download_compact, _download_tokens) ----
 
-// slots first .. first + n - 1 exist (else WRENC_GPU_EINVAL with `range_msg`) and have been searched
-int check_encoded(wrenc_gpu_ctx* ctx, int first, int n, const char* range_msg) {
+// slots first .. first + n - 1 exist (else WRENC_GPU_EINVAL with `range_msg`) and are in state `min_state` at least:
+// 1 uploaded, 2 searched
+int check_slots(wrenc_gpu_ctx* ctx, int first, int n, int min_state, const char* range_msg) {
     if (first < 0 || n < 1 || first + n > ctx->cfg.n_slots) return fail(ctx, WRENC_GPU_EINVAL, range_msg);
     for (int s = first; s < first + n; ++s)
-        if (ctx->state[s] != 2) return fail(ctx, WRENC_GPU_ESTATE, "slot has not been encoded");
+        if (ctx->state[s] < min_state)
+            return fail(ctx, WRENC_GPU_ESTATE, min_state == 2 ? "slot has not been encoded" : "slot has no uploaded picture");
     return WRENC_GPU_OK;
 }
 
@@ -881,7 +894,7 @@ int wait_for_search(wrenc_gpu_ctx* ctx, int first, int n, hipStream_t st = nullp
 int read_overflow(wrenc_gpu_ctx* ctx, hipStream_t st = nullptr) {
     hipStream_t cs = st ? st : ctx->copy_stream;
     int ovf = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&ovf, ctx->d_overflow, sizeof(int), hipMemcpyDeviceToHost, cs));
+    HIP_TRY(ctx, hipMemcpyAsync(&ovf, ctx->d_overflow.get(), sizeof(int), hipMemcpyDeviceToHost, cs));
     HIP_TRY(ctx, hipStreamSynchronize(cs));
     if (ovf & 2) return fail(ctx, WRENC_GPU_EHIP, "internal: a team member never reached a meeting point of the level schedule");
     if (ovf) return fail(ctx, WRENC_GPU_ELEVEL, "a quantised level reached 1024 (reference panics: block_splitter.rs:453)");
@@ -902,20 +915,6 @@ int copy_maps(wrenc_gpu_ctx* ctx, int slot, uint8_t* cu_log2_size, uint8_t* luma
     for (int p = 0; p < 3; ++p)
         if (rec[p]) HIP_TRY(ctx, hipMemcpyAsync(rec[p], b.rec[p], plane_bytes(c, p, 1), hipMemcpyDeviceToHost, cs));
     return WRENC_GPU_OK;
-}
-
-// replaces a device scratch buffer by one of `bytes` (contents dropped).  On failure it is NULL and HIP's last error is
-// cleared, so that the next launch check (hipGetLastError) does not report the failed allocation as its own.
-template <class T>
-hipError_t realloc_scratch(T*& p, size_t bytes) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    const hipError_t e = hipMalloc((void**)&p, bytes);
-    if (e != hipSuccess) {
-        p = nullptr;
-        (void)hipGetLastError();
-    }
-    return e;
 }
 
 // DevConst::head_rng: the coefficients that do not end the head proof's region, and those with a quotient below 2, as one
@@ -1161,25 +1160,60 @@ void fill_dev_const(const wrenc_gpu_config& cfg, DevConst& k) {
 } // namespace
 
 namespace {
+// `count` groups of `nb` blocks to the device, launch(d_in, d_out) on the context's stream, as many blocks back.
+// kernel_ms: NULL, or where the HIP-event duration of what `launch` queued goes (the 32x32 micro-benchmark)
 template <class Launch>
-int run_block_test(wrenc_gpu_ctx* ctx, const int16_t* in, int log2n, int count, int16_t* out, Launch launch, int nb = 1) {
+int run_block_test(wrenc_gpu_ctx* ctx, const int16_t* in, int log2n, int count, int16_t* out, Launch launch, int nb = 1,
+                   float* kernel_ms = nullptr) {
     if (!ctx || !in || !out) return WRENC_GPU_EINVAL;
     if (log2n < 2 || log2n > 5 || count < 1 || nb < 1) return fail(ctx, WRENC_GPU_EINVAL, "log2n must be 2..5 and count >= 1");
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-    const size_t bytes = (size_t)count * nb * sizeof(int16_t) << (2 * log2n);
-    int16_t *d_in = nullptr, *d_out = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&d_in, bytes));
-    hipError_t e = hipMalloc((void**)&d_out, bytes);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in, in, bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        launch(d_in, d_out);
-        e = hipGetLastError();
+    const size_t n = (size_t)count * nb << (2 * log2n);
+    struct Event {
+        hipEvent_t e = nullptr;
+        ~Event() {
+            if (e) (void)hipEventDestroy(e);
+        }
+    } e0, e1;
+    DevBuf<int16_t> d_in, d_out;
+    HIP_TRY(ctx, d_in.alloc(n));
+    HIP_TRY(ctx, d_out.alloc(n));
+    if (kernel_ms) {
+        *kernel_ms = 0.f;
+        HIP_TRY(ctx, hipEventCreate(&e0.e));
+        HIP_TRY(ctx, hipEventCreate(&e1.e));
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (e != hipSuccess) return fail(ctx, WRENC_GPU_EHIP, hipGetErrorString(e));
+    HIP_TRY(ctx, hipMemcpyAsync(d_in.get(), in, n * sizeof(int16_t), hipMemcpyHostToDevice, ctx->stream));
+    if (kernel_ms) HIP_TRY(ctx, hipEventRecord(e0.e, ctx->stream));
+    launch(d_in.get(), d_out.get());
+    HIP_TRY(ctx, hipGetLastError());
+    if (kernel_ms) HIP_TRY(ctx, hipEventRecord(e1.e, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out, d_out.get(), n * sizeof(int16_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (kernel_ms) HIP_TRY(ctx, hipEventElapsedTime(kernel_ms, e0.e, e1.e));
+    return WRENC_GPU_OK;
+}
+
+// A picture of a test entry's own (never a slot of the context): up to two sets of three planes of the context's size, Y |
+// Cb | Cr as one slab each like a slot's, in `slab`.  `pic`: NULL, or where the device's PicBufs of it goes.
+int load_test_picture(wrenc_gpu_ctx* ctx, const uint8_t* const org[3], const uint8_t* const rec[3], DevBuf<uint8_t>& slab,
+                      DevBuf<PicBufs>* pic) {
+    const wrenc_gpu_config& c = ctx->cfg;
+    const size_t wh = (size_t)c.width * c.height;
+    HIP_TRY(ctx, slab.alloc(((org ? 1 : 0) + (rec ? 1 : 0)) * (wh + wh / 2)));
+    PicBufs pb = {};
+    uint8_t* at = slab.get();
+    for (int p = 0; p < 6; ++p) {
+        const uint8_t* const* from = p < 3 ? org : rec;
+        if (!from) continue;
+        const int comp = p % 3;
+        if (p < 3) pb.org[comp] = at; else pb.rec[comp] = at;
+        HIP_TRY(ctx, hipMemcpy(at, from[comp], plane_bytes(c, comp, 1), hipMemcpyHostToDevice));
+        at += plane_bytes(c, comp, 1);
+    }
+    if (!pic) return WRENC_GPU_OK;
+    HIP_TRY(ctx, pic->alloc(1));
+    HIP_TRY(ctx, hipMemcpy(pic->get(), &pb, sizeof(pb), hipMemcpyHostToDevice));
     return WRENC_GPU_OK;
 }
 
@@ -1189,8 +1223,8 @@ int run_block_test(wrenc_gpu_ctx* ctx, const int16_t* in, int log2n, int count, 
 // (include/wrenc_gpu.h: "keep a word of their own and never poison a context")
 int take_test_overflow(wrenc_gpu_ctx* ctx, int rc) {
     int ovf = 0;
-    hipError_t e = hipMemcpyAsync(&ovf, ctx->d_overflow + 1, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(ctx->d_overflow + 1, 0, sizeof(int), ctx->stream);
+    hipError_t e = hipMemcpyAsync(&ovf, ctx->d_overflow.get() + 1, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(ctx->d_overflow.get() + 1, 0, sizeof(int), ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (rc != WRENC_GPU_OK) return rc;
     if (e != hipSuccess) return fail(ctx, WRENC_GPU_EHIP, hipGetErrorString(e));
@@ -1339,52 +1373,6 @@ void wrenc_gpu_destroy(wrenc_gpu_ctx* ctx) {
     for (hipStream_t st : ctx->lanes) (void)hipStreamSynchronize(st);
     if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
     if (ctx->hash_stream) (void)hipStreamSynchronize(ctx->hash_stream);
-    for (PicBufs& b : ctx->slots) {
-        // planes 1 and 2 point into plane 0's slab
-        if (b.org[0]) (void)hipFree((void*)b.org[0]);
-        if (b.org_t) (void)hipFree((void*)b.org_t);
-        if (b.border) (void)hipFree(b.border);
-        if (b.rec[0]) (void)hipFree(b.rec[0]);
-        if (b.lev[0]) (void)hipFree(b.lev[0]);
-        if (b.lev_dirty) (void)hipFree(b.lev_dirty);
-        if (b.cu_log2) (void)hipFree(b.cu_log2);
-        if (b.luma_mode) (void)hipFree(b.luma_mode);
-        if (b.chroma_mode) (void)hipFree(b.chroma_mode);
-        if (b.ctu_cost) (void)hipFree(b.ctu_cost);
-    }
-    if (ctx->d_const) (void)hipFree(ctx->d_const);
-    for (int q = 0; q < 64; ++q) {
-        if (ctx->d_qconst[q]) (void)hipFree(ctx->d_qconst[q]);
-        delete ctx->qcfg[q];
-    }
-    for (auto& cl : ctx->call_lists) {
-        if (cl.d_pics) (void)hipFree(cl.d_pics);
-        if (cl.d_groups) (void)hipFree(cl.d_groups);
-    }
-    if (ctx->d_slots) (void)hipFree(ctx->d_slots);
-    if (ctx->d_mismatch) (void)hipFree(ctx->d_mismatch);
-    if (ctx->d_overflow) (void)hipFree(ctx->d_overflow);
-    if (ctx->d_tok_pool) (void)hipFree(ctx->d_tok_pool);
-    if (ctx->d_tok_counter) (void)hipFree(ctx->d_tok_counter);
-    if (ctx->d_tok_first) (void)hipFree(ctx->d_tok_first);
-    if (ctx->d_pred_scratch) (void)hipFree(ctx->d_pred_scratch);
-    if (ctx->d_slot_map) (void)hipFree(ctx->d_slot_map);
-    if (ctx->d_cmask) (void)hipFree(ctx->d_cmask);
-    if (ctx->d_cpayload) (void)hipFree(ctx->d_cpayload);
-    if (ctx->d_ccount) (void)hipFree(ctx->d_ccount);
-    if (ctx->d_mpartial) (void)hipFree(ctx->d_mpartial);
-    if (ctx->d_msums) (void)hipFree(ctx->d_msums);
-    if (ctx->d_htables) (void)hipFree(ctx->d_htables);
-    if (ctx->d_hpartial) (void)hipFree(ctx->d_hpartial);
-    if (ctx->d_hvalues) (void)hipFree(ctx->d_hvalues);
-    if (ctx->d_xpartial) (void)hipFree(ctx->d_xpartial);
-    if (ctx->d_xsums) (void)hipFree(ctx->d_xsums);
-    if (ctx->d_xmap) (void)hipFree(ctx->d_xmap);
-    if (ctx->d_rpartial) (void)hipFree(ctx->d_rpartial);
-    if (ctx->d_rsums) (void)hipFree(ctx->d_rsums);
-    if (ctx->d_stage) (void)hipFree(ctx->d_stage);
-    if (ctx->d_scale_tab) (void)hipFree(ctx->d_scale_tab);
-    if (ctx->d_raw) (void)hipFree(ctx->d_raw);
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
     if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
@@ -1398,7 +1386,7 @@ void wrenc_gpu_destroy(wrenc_gpu_ctx* ctx) {
     if (ctx->hash_stream) (void)hipStreamDestroy(ctx->hash_stream);
     if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx; // (frees the device memory: every stream has been synchronised above)
 }
 
 // The trellis keeps path costs in 32 bits (dev_quant.h, above kNoBranch): exact as long as one step costs less than 2^25,
@@ -1483,49 +1471,57 @@ int wrenc_gpu_create(const wrenc_gpu_config* cfg, wrenc_gpu_ctx** out) {
         DevConst* hk = new (std::nothrow) DevConst();
         if (!hk) return bail(WRENC_GPU_ENOMEM, "out of host memory");
         fill_dev_const(*cfg, *hk);
-        hipError_t e = hipMalloc((void**)&ctx->d_const, sizeof(DevConst));
-        if (e == hipSuccess) e = hipMemcpy(ctx->d_const, hk, sizeof(DevConst), hipMemcpyHostToDevice);
+        hipError_t e = ctx->d_const.alloc(1);
+        if (e == hipSuccess) e = hipMemcpy(ctx->d_const.get(), hk, sizeof(DevConst), hipMemcpyHostToDevice);
         delete hk;
         CREATE_TRY(e);
     }
-    CREATE_TRY(hipMalloc((void**)&ctx->d_mismatch, sizeof(unsigned long long)));
-    CREATE_TRY(hipMemset(ctx->d_mismatch, 0, sizeof(unsigned long long)));
-    CREATE_TRY(hipMalloc((void**)&ctx->d_overflow, 2 * sizeof(int))); // [0]: encode calls (sticky), [1]: the building-block test entries
-    CREATE_TRY(hipMemset(ctx->d_overflow, 0, 2 * sizeof(int)));
+    CREATE_TRY(ctx->d_mismatch.alloc(1));
+    CREATE_TRY(hipMemset(ctx->d_mismatch.get(), 0, sizeof(unsigned long long)));
+    CREATE_TRY(ctx->d_overflow.alloc(2)); // [0]: encode calls (sticky), [1]: the building-block test entries
+    CREATE_TRY(hipMemset(ctx->d_overflow.get(), 0, 2 * sizeof(int)));
     ctx->slots.assign(cfg->n_slots, PicBufs{});
+    ctx->slot_mem.resize((size_t)cfg->n_slots);
     ctx->state.assign(cfg->n_slots, 0);
     ctx->slot_qp.assign(cfg->n_slots, -1);
     ctx->call_lists.resize(ctx->enc_events.size());
     for (int s = 0; s < cfg->n_slots; ++s) {
         PicBufs& b = ctx->slots[s];
+        wrenc_gpu_ctx::SlotMem& m = ctx->slot_mem[(size_t)s];
         // Y | Cb | Cr of a picture are one slab each for originals, reconstruction and levels: the
         // kernel addresses a plane by an element offset, never by selecting a pointer per lane
         const size_t wh = (size_t)cfg->width * cfg->height;
-        uint8_t* org_slab = nullptr;
-        CREATE_TRY(hipMalloc((void**)&org_slab, wh + wh / 2));
-        b.org[0] = org_slab;
-        b.org[1] = org_slab + wh;
-        b.org[2] = org_slab + wh + wh / 4;
         const size_t n_ctus = (size_t)ctx->ctu_cols * ctx->ctu_rows;
-        CREATE_TRY(hipMalloc((void**)&b.org_t, n_ctus * kOrgTile));
-        CREATE_TRY(hipMalloc((void**)&b.border, n_ctus * kBorderBytes));
-        CREATE_TRY(hipMalloc((void**)&b.rec[0], wh + wh / 2));
-        b.rec[1] = b.rec[0] + wh;
-        b.rec[2] = b.rec[0] + wh + wh / 4;
-        CREATE_TRY(hipMalloc((void**)&b.lev[0], (wh + wh / 2) * sizeof(int16_t)));
-        b.lev[1] = b.lev[0] + wh;
-        b.lev[2] = b.lev[0] + wh + wh / 4;
+        const size_t n4 = (size_t)(cfg->width / 4) * (cfg->height / 4), n8 = (size_t)(cfg->width / 8) * (cfg->height / 8);
+        CREATE_TRY(m.org.alloc(wh + wh / 2));
+        CREATE_TRY(m.org_t.alloc(n_ctus * kOrgTile));
+        CREATE_TRY(m.border.alloc(n_ctus * kBorderBytes));
+        CREATE_TRY(m.rec.alloc(wh + wh / 2));
+        CREATE_TRY(m.lev.alloc(wh + wh / 2));
+        CREATE_TRY(m.lev_dirty.alloc(n_ctus * 4));
+        CREATE_TRY(m.cu_log2.alloc(n4));
+        CREATE_TRY(m.luma_mode.alloc(n4));
+        CREATE_TRY(m.chroma_mode.alloc(n8));
+        CREATE_TRY(m.ctu_cost.alloc(n_ctus));
+        const size_t plane_at[3] = {0, wh, wh + wh / 4};
+        for (int p = 0; p < 3; ++p) {
+            b.org[p] = m.org.get() + plane_at[p];
+            b.rec[p] = m.rec.get() + plane_at[p];
+            b.lev[p] = m.lev.get() + plane_at[p];
+        }
+        b.org_t = m.org_t.get();
+        b.border = m.border.get();
+        b.lev_dirty = m.lev_dirty.get();
+        b.cu_log2 = m.cu_log2.get();
+        b.luma_mode = m.luma_mode.get();
+        b.chroma_mode = m.chroma_mode.get();
+        b.ctu_cost = m.ctu_cost.get();
         // the planes start zeroed, with no block marked as holding levels (PicBufs::lev_dirty)
         CREATE_TRY(hipMemsetAsync(b.lev[0], 0, (wh + wh / 2) * sizeof(int16_t), ctx->stream));
-        CREATE_TRY(hipMalloc((void**)&b.lev_dirty, n_ctus * 4 * sizeof(uint32_t)));
         CREATE_TRY(hipMemsetAsync(b.lev_dirty, 0, n_ctus * 4 * sizeof(uint32_t), ctx->stream));
-        CREATE_TRY(hipMalloc((void**)&b.cu_log2, (size_t)(cfg->width / 4) * (cfg->height / 4)));
-        CREATE_TRY(hipMalloc((void**)&b.luma_mode, (size_t)(cfg->width / 4) * (cfg->height / 4)));
-        CREATE_TRY(hipMalloc((void**)&b.chroma_mode, (size_t)(cfg->width / 8) * (cfg->height / 8)));
-        CREATE_TRY(hipMalloc((void**)&b.ctu_cost, sizeof(float) * ctx->ctu_cols * ctx->ctu_rows));
     }
-    CREATE_TRY(hipMalloc((void**)&ctx->d_slots, sizeof(PicBufs) * cfg->n_slots));
-    CREATE_TRY(hipMemcpy(ctx->d_slots, ctx->slots.data(), sizeof(PicBufs) * cfg->n_slots, hipMemcpyHostToDevice));
+    CREATE_TRY(ctx->d_slots.alloc((size_t)cfg->n_slots));
+    CREATE_TRY(hipMemcpy(ctx->d_slots.get(), ctx->slots.data(), sizeof(PicBufs) * cfg->n_slots, hipMemcpyHostToDevice));
     CREATE_TRY(hipStreamSynchronize(ctx->stream)); // the level planes are zero before anything can reach them
 #undef CREATE_TRY
     *out = ctx;
@@ -1605,7 +1601,6 @@ int wrenc_gpu_set_visible_size(wrenc_gpu_ctx* ctx, int vis_w, int vis_h) {
     if (ctx->src_w) return fail(ctx, WRENC_GPU_ESTATE, "a source size is set: the visible size comes first, then the source size");
     ctx->vis_w = vis_w;
     ctx->vis_h = vis_h;
-    ctx->metrics_cap = 0; // the metrics scratch is sized for the rectangle that is measured
     return WRENC_GPU_OK;
 }
 
@@ -1675,10 +1670,8 @@ int wrenc_gpu_set_source_size(wrenc_gpu_ctx* ctx, int src_w, int src_h) {
     }
     if (ctx->any_upload) return fail(ctx, WRENC_GPU_ESTATE, "the source size must be set before the first upload");
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-    if (ctx->d_stage) (void)hipFree(ctx->d_stage);
-    if (ctx->d_scale_tab) (void)hipFree(ctx->d_scale_tab);
-    ctx->d_stage = nullptr;
-    ctx->d_scale_tab = nullptr;
+    ctx->d_stage.reset();
+    ctx->d_scale_tab.reset();
     ctx->src_w = ctx->src_h = 0;
     if (plain) return WRENC_GPU_OK;
     // the four tables: x and y of luma, x and y of chroma; every piece starts on a 16-byte boundary of one allocation
@@ -1704,19 +1697,17 @@ int wrenc_gpu_set_source_size(wrenc_gpu_ctx* ctx, int src_w, int src_h) {
     }
     const size_t pitch_y = ((size_t)src_w + 15) & ~(size_t)15, pitch_c = ((size_t)src_w / 2 + 15) & ~(size_t)15;
     const size_t stage_y = pitch_y * (size_t)src_h, stage_c = pitch_c * (size_t)(src_h / 2);
-    hipError_t e = hipMalloc((void**)&ctx->d_scale_tab, at);
-    if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_stage, stage_y + 2 * stage_c);
-    if (e == hipSuccess) e = hipMemcpy(ctx->d_scale_tab, tab.data(), at, hipMemcpyHostToDevice);
+    hipError_t e = ctx->d_scale_tab.alloc(at);
+    if (e == hipSuccess) e = ctx->d_stage.alloc(stage_y + 2 * stage_c);
+    if (e == hipSuccess) e = hipMemcpy(ctx->d_scale_tab.get(), tab.data(), at, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
-        if (ctx->d_stage) (void)hipFree(ctx->d_stage);
-        if (ctx->d_scale_tab) (void)hipFree(ctx->d_scale_tab);
-        ctx->d_stage = nullptr;
-        ctx->d_scale_tab = nullptr;
+        ctx->d_stage.reset();
+        ctx->d_scale_tab.reset();
         return fail(ctx, e == hipErrorOutOfMemory ? WRENC_GPU_ENOMEM : WRENC_GPU_EHIP, std::string("scaler buffers: ") + hipGetErrorString(e));
     }
     ScaleArgs& a = ctx->scale_args;
     a = ScaleArgs{};
-    const uint8_t* base = (const uint8_t*)ctx->d_scale_tab;
+    const uint8_t* base = ctx->d_scale_tab.get();
     for (int i = 0; i < 4; ++i) {
         ScaleAxis& d = (i & 1) ? a.y[i >> 1] : a.x[i >> 1];
         d.first = (const int*)(base + off[i][0]);
@@ -1727,9 +1718,9 @@ int wrenc_gpu_set_source_size(wrenc_gpu_ctx* ctx, int src_w, int src_h) {
         d.taps = ax[i].taps;
         d.span = ax[i].span;
     }
-    a.src[0] = ctx->d_stage;
-    a.src[1] = ctx->d_stage + stage_y;
-    a.src[2] = ctx->d_stage + stage_y + stage_c;
+    a.src[0] = ctx->d_stage.get();
+    a.src[1] = ctx->d_stage.get() + stage_y;
+    a.src[2] = ctx->d_stage.get() + stage_y + stage_c;
     a.src_pitch[0] = (int)pitch_y;
     a.src_pitch[1] = (int)pitch_c;
     a.W = ctx->cfg.width;
@@ -1783,16 +1774,10 @@ bool raw_stage(const wrenc_gpu_ctx* ctx, int format, RawStage& r) {
 
 // d_raw holds r.bytes: allocated here when it does not (the format, or a size, has changed since)
 int ensure_raw_stage(wrenc_gpu_ctx* ctx, const RawStage& r) {
-    if (ctx->d_raw && ctx->d_raw_bytes == r.bytes) return WRENC_GPU_OK;
-    if (ctx->d_raw) (void)hipFree(ctx->d_raw);
-    ctx->d_raw = nullptr;
-    ctx->d_raw_bytes = 0;
-    const hipError_t e = hipMalloc((void**)&ctx->d_raw, r.bytes);
-    if (e != hipSuccess) {
-        ctx->d_raw = nullptr;
+    if (ctx->d_raw && ctx->d_raw.count() == r.bytes) return WRENC_GPU_OK;
+    const hipError_t e = ctx->d_raw.alloc(r.bytes);
+    if (e != hipSuccess)
         return fail(ctx, e == hipErrorOutOfMemory ? WRENC_GPU_ENOMEM : WRENC_GPU_EHIP, std::string("raw staging planes: ") + hipGetErrorString(e));
-    }
-    ctx->d_raw_bytes = r.bytes;
     return WRENC_GPU_OK;
 }
 
@@ -1804,9 +1789,7 @@ int wrenc_gpu_set_source_format(wrenc_gpu_ctx* ctx, int format) {
     if (ctx->any_upload) return fail(ctx, WRENC_GPU_ESTATE, "the source format must be set before the first upload");
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
     if (format == WRENC_FORMAT_YUV420P) {
-        if (ctx->d_raw) (void)hipFree(ctx->d_raw);
-        ctx->d_raw = nullptr;
-        ctx->d_raw_bytes = 0;
+        ctx->d_raw.reset();
         ctx->src_format = 0;
         return WRENC_GPU_OK;
     }
@@ -1849,16 +1832,16 @@ int wrenc_gpu_upload_planes(wrenc_gpu_ctx* ctx, int slot, const void* const plan
     hipStream_t cs = ctx->copy_stream;
     // the caller's bytes as they are -- a 10-bit picture crosses the bus once -- and behind them the converter (dev_format.h)
     FormatArgs a = {};
-    a.raw = ctx->d_raw;
+    a.raw = ctx->d_raw.get();
     for (int p = 0; p < r.lay.n_planes; ++p) {
-        HIP_TRY(ctx, hipMemcpy2DAsync((void*)(ctx->d_raw + r.off[p]), r.pitch[p], plane[p], stride_bytes[p], r.lay.row_bytes[p], r.lay.rows[p],
+        HIP_TRY(ctx, hipMemcpy2DAsync((void*)(ctx->d_raw.get() + r.off[p]), r.pitch[p], plane[p], stride_bytes[p], r.lay.row_bytes[p], r.lay.rows[p],
                                       hipMemcpyHostToDevice, cs));
         a.raw_off[p] = r.off[p];
         a.raw_pitch[p] = (int)r.pitch[p];
     }
     if (scaling) { // into the scaler's staging planes, in the place of wrenc_gpu_upload's copies
         const ScaleArgs& s = ctx->scale_args;
-        a.dst = ctx->d_stage;
+        a.dst = ctx->d_stage.get();
         for (int p = 0; p < 3; ++p) a.dst_off[p] = (size_t)(s.src[p] - s.src[0]);
         a.dst_pitch[0] = s.src_pitch[0];
         a.dst_pitch[1] = s.src_pitch[1];
@@ -1926,7 +1909,7 @@ int wrenc_gpu_set_slot_qp(wrenc_gpu_ctx* ctx, int slot, const wrenc_gpu_config* 
                !memcmp(&a.lambda_rd_chroma, &b.lambda_rd_chroma, sizeof(float));
     };
     const int q = qcfg->qp;
-    const wrenc_gpu_config* known = q == c.qp ? &c : ctx->qcfg[q];
+    const wrenc_gpu_config* known = q == c.qp ? &c : ctx->qcfg[q].get();
     if (known) {
         if (!same_lambdas(*qcfg, *known)) return fail(ctx, WRENC_GPU_EINVAL, "the context has another lambda set for this QP");
         ctx->slot_qp[slot] = q == c.qp ? -1 : q;
@@ -1936,40 +1919,34 @@ int wrenc_gpu_set_slot_qp(wrenc_gpu_ctx* ctx, int slot, const wrenc_gpu_config* 
     // the QP's constant block, built once: it is never changed or freed while the context lives, so a call in flight
     // that reads it is not disturbed
     HIP_TRY(ctx, hipSetDevice(c.device));
-    DevConst* hk = new (std::nothrow) DevConst();
-    wrenc_gpu_config* kept = new (std::nothrow) wrenc_gpu_config(*qcfg);
-    DevConst* d = nullptr;
+    std::unique_ptr<DevConst> hk(new (std::nothrow) DevConst());
+    std::unique_ptr<wrenc_gpu_config> kept(new (std::nothrow) wrenc_gpu_config(*qcfg));
+    DevBuf<DevConst> d;
     hipError_t e = hipErrorOutOfMemory;
     if (hk && kept) {
         fill_dev_const(*qcfg, *hk);
-        e = hipMalloc((void**)&d, sizeof(DevConst));
-        if (e == hipSuccess) e = hipMemcpy(d, hk, sizeof(DevConst), hipMemcpyHostToDevice);
+        e = d.alloc(1);
+        if (e == hipSuccess) e = hipMemcpy(d.get(), hk.get(), sizeof(DevConst), hipMemcpyHostToDevice);
     }
-    delete hk;
     if (e != hipSuccess) {
-        delete kept;
-        if (d) (void)hipFree(d);
         (void)hipGetLastError();
         return fail(ctx, e == hipErrorOutOfMemory ? WRENC_GPU_ENOMEM : WRENC_GPU_EHIP,
                     std::string("constant block of a QP: ") + hipGetErrorString(e));
     }
-    ctx->d_qconst[q] = d;
-    ctx->qcfg[q] = kept;
+    ctx->d_qconst[q] = std::move(d);
+    ctx->qcfg[q] = std::move(kept);
     ctx->slot_qp[slot] = q;
     return WRENC_GPU_OK;
 }
 
 int wrenc_gpu_encode(wrenc_gpu_ctx* ctx, int first_slot, int n_pictures) {
     if (!ctx) return WRENC_GPU_EINVAL;
-    if (first_slot < 0 || n_pictures < 1 || first_slot + n_pictures > ctx->cfg.n_slots)
-        return fail(ctx, WRENC_GPU_EINVAL, "slot range out of bounds");
-    for (int s = first_slot; s < first_slot + n_pictures; ++s)
-        if (ctx->state[s] == 0) return fail(ctx, WRENC_GPU_ESTATE, "slot has no uploaded picture");
+    if (const int rc = check_slots(ctx, first_slot, n_pictures, 1, "slot range out of bounds")) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
     // The pictures' QPs are read now: a later wrenc_gpu_set_slot_qp does not change this call.  A call at one QP runs its
     // slots in place with that QP's constant block; a mixed one from a list of its own (CallGroup, above the kernels).
-    const DevConst* d_k = ctx->d_const;
-    const PicBufs* d_pics = ctx->d_slots;
+    const DevConst* d_k = ctx->d_const.get();
+    const PicBufs* d_pics = ctx->d_slots.get();
     const CallGroup* d_groups = nullptr;
     wrenc_gpu_ctx::CallList* cl = nullptr;
     int list_first = first_slot, n_entries = n_pictures;
@@ -1977,7 +1954,7 @@ int wrenc_gpu_encode(wrenc_gpu_ctx* ctx, int first_slot, int n_pictures) {
         const int q0 = ctx->slot_qp[first_slot];
         bool mixed = false;
         for (int s = first_slot; s < first_slot + n_pictures; ++s) mixed |= ctx->slot_qp[s] != q0;
-        if (!mixed && q0 >= 0) d_k = ctx->d_qconst[q0];
+        if (!mixed && q0 >= 0) d_k = ctx->d_qconst[q0].get();
         if (mixed) {
             // this call's list: the ring entry of the completion event it will record, last used by the call that recorded
             // that event before -- which must be done before the list is rewritten
@@ -1996,22 +1973,17 @@ int wrenc_gpu_encode(wrenc_gpu_ctx* ctx, int first_slot, int n_pictures) {
                     }
                 if (!n_q) continue;
                 while (cl->pics.size() % WPB) cl->pics.push_back(cl->pics.back());
-                const DevConst* kq = q == ctx->cfg.qp ? ctx->d_const : ctx->d_qconst[q];
+                const DevConst* kq = q == ctx->cfg.qp ? ctx->d_const.get() : ctx->d_qconst[q].get();
                 for (int g = 0; g * WPB < n_q; ++g) cl->groups.push_back(CallGroup{kq, n_q - g * WPB < WPB ? n_q - g * WPB : WPB});
             }
             n_entries = (int)cl->pics.size();
-            if (cl->cap < n_entries) {
-                cl->cap = 0;
-                if (realloc_scratch(cl->d_pics, sizeof(PicBufs) * n_entries) != hipSuccess ||
-                    realloc_scratch(cl->d_groups, sizeof(CallGroup) * (n_entries / WPB)) != hipSuccess)
-                    return fail(ctx, WRENC_GPU_ENOMEM, "no device memory for the picture list of a mixed-QP call");
-                cl->cap = n_entries;
-            }
-            HIP_TRY(ctx, hipMemcpyAsync(cl->d_pics, cl->pics.data(), sizeof(PicBufs) * n_entries, hipMemcpyHostToDevice, ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(cl->d_groups, cl->groups.data(), sizeof(CallGroup) * cl->groups.size(), hipMemcpyHostToDevice,
+            if (cl->d_pics.grow((size_t)n_entries) != hipSuccess || cl->d_groups.grow((size_t)n_entries / WPB) != hipSuccess)
+                return fail(ctx, WRENC_GPU_ENOMEM, "no device memory for the picture list of a mixed-QP call");
+            HIP_TRY(ctx, hipMemcpyAsync(cl->d_pics.get(), cl->pics.data(), sizeof(PicBufs) * n_entries, hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(cl->d_groups.get(), cl->groups.data(), sizeof(CallGroup) * cl->groups.size(), hipMemcpyHostToDevice,
                                         ctx->stream));
-            d_pics = cl->d_pics;
-            d_groups = cl->d_groups;
+            d_pics = cl->d_pics.get();
+            d_groups = cl->d_groups.get();
             list_first = 0;
         }
     }
@@ -2027,10 +1999,14 @@ int wrenc_gpu_encode(wrenc_gpu_ctx* ctx, int first_slot, int n_pictures) {
     const int total_groups = (n_entries + per_group - 1) / per_group;
     int n_team_diags = 0, n_wave_diags = 0;
     const int n_lanes = total_groups < kEncodeLanes ? total_groups : kEncodeLanes;
-    if (!ctx->d_pred_scratch) {
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_pred_scratch, (size_t)kScratchSlots * WPB * kWaveScratch));
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_slot_map, kSlotMapWords * 8));
-        HIP_TRY(ctx, hipMemset(ctx->d_slot_map, 0, kSlotMapWords * 8));
+    if (!ctx->d_pred_scratch) { // into locals first: a call that fails here leaves the context with neither
+        DevBuf<uint8_t> scratch;
+        DevBuf<unsigned long long> map;
+        HIP_TRY(ctx, scratch.alloc((size_t)kScratchSlots * WPB * kWaveScratch));
+        HIP_TRY(ctx, map.alloc(kSlotMapWords));
+        HIP_TRY(ctx, hipMemset(map.get(), 0, kSlotMapWords * 8));
+        ctx->d_pred_scratch = std::move(scratch);
+        ctx->d_slot_map = std::move(map);
     }
     const bool timed = ctx->stats_enabled;
     if (timed) {
@@ -2046,7 +2022,7 @@ int wrenc_gpu_encode(wrenc_gpu_ctx* ctx, int first_slot, int n_pictures) {
     // end).  A kernel that was aborted would leave its bits set for good, so the map is cleared whenever no
     // encode call is in flight (the last call's completion event has been reached).
     if (ctx->last_done == nullptr || hipEventQuery(ctx->last_done) == hipSuccess)
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_slot_map, 0, kScratchSlots / 8, ctx->stream)); // (not the overflow counter)
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_slot_map.get(), 0, kScratchSlots / 8, ctx->stream)); // (not the overflow counter)
     if (ctx->uploads_pending) {
         HIP_TRY(ctx, hipEventRecord(ctx->ev_uploaded, ctx->copy_stream));
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_uploaded, 0));
@@ -2095,7 +2071,7 @@ int wrenc_gpu_encode(wrenc_gpu_ctx* ctx, int first_slot, int n_pictures) {
                     const dim3 grid(count * ((n + kTeamsPerGroup - 1) / kTeamsPerGroup));
 #define WRENC_LAUNCH(KERNEL)                                                                                                   \
     hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL), grid, dim3(64 * WPB), 0, st, kq, d_pics, first, n, d, r_min, count,             \
-                       ctx->d_pred_scratch, ctx->d_slot_map, ctx->d_mismatch, ctx->d_overflow)
+                       ctx->d_pred_scratch.get(), ctx->d_slot_map.get(), ctx->d_mismatch.get(), ctx->d_overflow.get())
                     if (d3)
                         WRENC_LAUNCH(ctu_search_team_kernel<true>);
                     else
@@ -2108,7 +2084,7 @@ int wrenc_gpu_encode(wrenc_gpu_ctx* ctx, int first_slot, int n_pictures) {
                 const dim3 grid(count * (g1 - g0));
 #define WRENC_LAUNCH(KERNEL)                                                                                                   \
     hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL), grid, dim3(64 * WPB), 0, st, d_k, d_pics, lane_first, lane_pics, d, r_min, count, \
-                       ctx->d_pred_scratch, ctx->d_slot_map, ctx->d_mismatch, ctx->d_overflow, lane_groups)
+                       ctx->d_pred_scratch.get(), ctx->d_slot_map.get(), ctx->d_mismatch.get(), ctx->d_overflow.get(), lane_groups)
                 if (d3)
                     WRENC_LAUNCH(ctu_search_kernel<true>);
                 else
@@ -2157,7 +2133,7 @@ int wrenc_gpu_sync(wrenc_gpu_ctx* ctx) {
 
 int wrenc_gpu_download(wrenc_gpu_ctx* ctx, int slot, wrenc_gpu_picture* out) {
     if (!ctx || !out) return WRENC_GPU_EINVAL;
-    if (const int rc = check_encoded(ctx, slot, 1, "bad slot")) return rc;
+    if (const int rc = check_slots(ctx, slot, 1, 2, "bad slot")) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
     const PicBufs& b = ctx->slots[slot];
     const wrenc_gpu_config& c = ctx->cfg;
@@ -2182,35 +2158,31 @@ size_t wrenc_gpu_compact_mask_words(int width, int height) {
 
 int wrenc_gpu_download_compact(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_gpu_compact* out) {
     if (!ctx || !out) return WRENC_GPU_EINVAL;
-    if (const int rc = check_encoded(ctx, first_slot, n, "slot range out of bounds")) return rc;
+    if (const int rc = check_slots(ctx, first_slot, n, 2, "slot range out of bounds")) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
     const wrenc_gpu_config& c = ctx->cfg;
     const size_t mask_words = wrenc_gpu_compact_mask_words(c.width, c.height);
     const size_t blocks = (size_t)(c.width / 4) * (c.height / 4) * 3 / 2;
-    if (ctx->compact_cap < n) {
-        ctx->compact_cap = 0;
-        HIP_TRY(ctx, realloc_scratch(ctx->d_cmask, (size_t)n * mask_words * sizeof(uint32_t)));
-        HIP_TRY(ctx, realloc_scratch(ctx->d_cpayload, (size_t)n * blocks * 16 * sizeof(int16_t)));
-        HIP_TRY(ctx, realloc_scratch(ctx->d_ccount, (size_t)n * sizeof(unsigned)));
-        ctx->compact_cap = n;
-    }
+    HIP_TRY(ctx, ctx->d_cmask.grow((size_t)n * mask_words));
+    HIP_TRY(ctx, ctx->d_cpayload.grow((size_t)n * blocks * 16));
+    HIP_TRY(ctx, ctx->d_ccount.grow((size_t)n));
     hipStream_t cs = ctx->copy_stream;
     if (const int rc = wait_for_search(ctx, first_slot, n)) return rc;
-    hipLaunchKernelGGL(compact_levels_kernel, dim3(n), dim3(1024), 0, cs, ctx->d_slots, first_slot, c.width, c.height, ctx->d_cmask,
-                       mask_words, ctx->d_cpayload, blocks, ctx->d_ccount);
+    hipLaunchKernelGGL(compact_levels_kernel, dim3(n), dim3(1024), 0, cs, ctx->d_slots.get(), first_slot, c.width, c.height, ctx->d_cmask.get(),
+                       mask_words, ctx->d_cpayload.get(), blocks, ctx->d_ccount.get());
     HIP_TRY(ctx, hipGetLastError());
     std::vector<unsigned> counts((size_t)n);
-    HIP_TRY(ctx, hipMemcpyAsync(counts.data(), ctx->d_ccount, (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost, cs));
+    HIP_TRY(ctx, hipMemcpyAsync(counts.data(), ctx->d_ccount.get(), (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost, cs));
     if (const int rc = read_overflow(ctx)) return rc;
     bool short_buf = false;
     for (int k = 0; k < n; ++k) {
         wrenc_gpu_compact& o = out[k];
         o.n_blocks = counts[(size_t)k];
-        if (o.mask) HIP_TRY(ctx, hipMemcpyAsync(o.mask, ctx->d_cmask + (size_t)k * mask_words, mask_words * sizeof(uint32_t), hipMemcpyDeviceToHost, cs));
+        if (o.mask) HIP_TRY(ctx, hipMemcpyAsync(o.mask, ctx->d_cmask.get() + (size_t)k * mask_words, mask_words * sizeof(uint32_t), hipMemcpyDeviceToHost, cs));
         if (o.n_blocks > o.payload_cap || (o.n_blocks && !o.payload)) {
             short_buf = true;
         } else if (o.n_blocks) {
-            HIP_TRY(ctx, hipMemcpyAsync(o.payload, ctx->d_cpayload + (size_t)k * blocks * 16, o.n_blocks * 16 * sizeof(int16_t),
+            HIP_TRY(ctx, hipMemcpyAsync(o.payload, ctx->d_cpayload.get() + (size_t)k * blocks * 16, o.n_blocks * 16 * sizeof(int16_t),
                                         hipMemcpyDeviceToHost, cs));
         }
         if (const int rc = copy_maps(ctx, first_slot + k, o.cu_log2_size, o.luma_mode, o.chroma_mode, o.rec_y, o.rec_cb, o.rec_cr))
@@ -2224,7 +2196,7 @@ int wrenc_gpu_download_compact(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_
 int wrenc_gpu_download_tokens(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_gpu_tokens* out, uint32_t* pool, size_t pool_cap_words,
                               size_t* pool_words_used) {
     if (!ctx || !out || !pool || !pool_words_used || n < 1) return WRENC_GPU_EINVAL;
-    if (const int rc = check_encoded(ctx, first_slot, n, "bad slot range")) return rc;
+    if (const int rc = check_slots(ctx, first_slot, n, 2, "bad slot range")) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
     const int ctus = ctx->ctu_cols * ctx->ctu_rows;
     const size_t pages = pool_cap_words / kTokPage;
@@ -2235,31 +2207,22 @@ int wrenc_gpu_download_tokens(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_g
         *pool_words_used = 0;
         return fail(ctx, WRENC_GPU_ENOMEM, std::string("wrenc_gpu_download_tokens: device scratch: ") + hipGetErrorString(e));
     };
-    if (ctx->tok_pool_words < pages * kTokPage) {
-        ctx->tok_pool_words = 0;
-        if (const hipError_t e = realloc_scratch(ctx->d_tok_pool, pages * kTokPage * sizeof(uint32_t))) return no_room(e);
-        ctx->tok_pool_words = pages * kTokPage;
-    }
-    if (!ctx->d_tok_counter)
-        if (const hipError_t e = realloc_scratch(ctx->d_tok_counter, kCounterWords * sizeof(unsigned))) return no_room(e);
-    if (ctx->tok_first_cap < n) {
-        ctx->tok_first_cap = 0;
-        if (const hipError_t e = realloc_scratch(ctx->d_tok_first, (size_t)n * ctus * sizeof(uint32_t))) return no_room(e);
-        ctx->tok_first_cap = n;
-    }
+    if (const hipError_t e = ctx->d_tok_pool.grow(pages * kTokPage)) return no_room(e);
+    if (const hipError_t e = ctx->d_tok_counter.grow(kCounterWords)) return no_room(e);
+    if (const hipError_t e = ctx->d_tok_first.grow((size_t)n * ctus)) return no_room(e);
     hipStream_t cs = ctx->copy_stream;
     if (const int rc = wait_for_search(ctx, first_slot, n)) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_tok_counter, 0, kCounterWords * sizeof(unsigned), cs));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_tok_counter.get(), 0, kCounterWords * sizeof(unsigned), cs));
     const int waves = n * ctus;
     // sub-pools: enough CTUs in each (16 or more) that they fill evenly; one for a handful of CTUs
     int n_pools = 1;
     while (n_pools < kTokPools && n_pools * 32 <= waves) n_pools *= 2;
     const size_t sub = pages / (size_t)n_pools; // pages per sub-pool
-    hipLaunchKernelGGL(residual_tokens_kernel, dim3((waves + 3) / 4), dim3(256), 0, cs, ctx->d_const, ctx->d_slots, first_slot, n,
-                       ctx->d_tok_pool, (unsigned)sub, n_pools - 1, ctx->d_tok_counter, ctx->d_tok_first, (int*)(ctx->d_tok_counter + kCounterWords - 1));
+    hipLaunchKernelGGL(residual_tokens_kernel, dim3((waves + 3) / 4), dim3(256), 0, cs, ctx->d_const.get(), ctx->d_slots.get(), first_slot, n,
+                       ctx->d_tok_pool.get(), (unsigned)sub, n_pools - 1, ctx->d_tok_counter.get(), ctx->d_tok_first.get(), (int*)(ctx->d_tok_counter.get() + kCounterWords - 1));
     HIP_TRY(ctx, hipGetLastError());
     std::vector<unsigned> cnt((size_t)kCounterWords);
-    HIP_TRY(ctx, hipMemcpyAsync(cnt.data(), ctx->d_tok_counter, kCounterWords * sizeof(unsigned), hipMemcpyDeviceToHost, cs));
+    HIP_TRY(ctx, hipMemcpyAsync(cnt.data(), ctx->d_tok_counter.get(), kCounterWords * sizeof(unsigned), hipMemcpyDeviceToHost, cs));
     if (const int rc = read_overflow(ctx)) return rc;
     size_t asked = 0;
     bool short_of = cnt[(size_t)kCounterWords - 1] != 0;
@@ -2271,11 +2234,11 @@ int wrenc_gpu_download_tokens(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_g
     if (short_of) return fail(ctx, WRENC_GPU_ENOMEM, "wrenc_gpu_download_tokens: the token pool is too small for these pictures");
     for (int p = 0; p < n_pools; ++p) // every sub-pool's pages in use, to the same place in the caller's pool
         if (cnt[(size_t)p * kTokCounterStride])
-            HIP_TRY(ctx, hipMemcpyAsync(pool + (size_t)p * sub * kTokPage, ctx->d_tok_pool + (size_t)p * sub * kTokPage,
+            HIP_TRY(ctx, hipMemcpyAsync(pool + (size_t)p * sub * kTokPage, ctx->d_tok_pool.get() + (size_t)p * sub * kTokPage,
                                         (size_t)cnt[(size_t)p * kTokCounterStride] * kTokPage * sizeof(uint32_t), hipMemcpyDeviceToHost, cs));
     for (int k = 0; k < n; ++k) {
         wrenc_gpu_tokens& o = out[k];
-        if (o.first_page) HIP_TRY(ctx, hipMemcpyAsync(o.first_page, ctx->d_tok_first + (size_t)k * ctus, (size_t)ctus * sizeof(uint32_t), hipMemcpyDeviceToHost, cs));
+        if (o.first_page) HIP_TRY(ctx, hipMemcpyAsync(o.first_page, ctx->d_tok_first.get() + (size_t)k * ctus, (size_t)ctus * sizeof(uint32_t), hipMemcpyDeviceToHost, cs));
         if (const int rc = copy_maps(ctx, first_slot + k, o.cu_log2_size, o.luma_mode, o.chroma_mode, o.rec_y, o.rec_cb, o.rec_cr))
             return rc;
     }
@@ -2312,24 +2275,20 @@ static void fill_metrics(int vw, int vh, const MetricsSums& s, wrenc_gpu_metrics
 
 int wrenc_gpu_download_metrics(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_gpu_metrics* out) {
     if (!ctx || !out) return WRENC_GPU_EINVAL;
-    if (const int rc = check_encoded(ctx, first_slot, n, "slot range out of bounds")) return rc;
+    if (const int rc = check_slots(ctx, first_slot, n, 2, "slot range out of bounds")) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
     const wrenc_gpu_config& c = ctx->cfg;
     // a context with a visible size reports that rectangle only
     const int vw = ctx->vis_w, vh = ctx->vis_h;
     const size_t per_pic = (size_t)met_plane(vw, vh, 0).waves + 2 * (size_t)met_plane(vw, vh, 1).waves;
-    if (ctx->metrics_cap < n) {
-        ctx->metrics_cap = 0;
-        HIP_TRY(ctx, realloc_scratch(ctx->d_mpartial, (size_t)n * per_pic * sizeof(MetricsPartial)));
-        HIP_TRY(ctx, realloc_scratch(ctx->d_msums, (size_t)n * sizeof(MetricsSums)));
-        ctx->metrics_cap = n;
-    }
+    HIP_TRY(ctx, ctx->d_mpartial.grow((size_t)n * per_pic));
+    HIP_TRY(ctx, ctx->d_msums.grow((size_t)n));
     // on the copy stream, behind the encode call that searched these slots and nothing later
     hipStream_t cs = ctx->copy_stream;
     if (const int rc = wait_for_search(ctx, first_slot, n)) return rc;
-    HIP_TRY(ctx, launch_metrics(c, vw, vh, cs, ctx->d_slots, first_slot, n, ctx->d_mpartial, ctx->d_msums, nullptr));
+    HIP_TRY(ctx, launch_metrics(c, vw, vh, cs, ctx->d_slots.get(), first_slot, n, ctx->d_mpartial.get(), ctx->d_msums.get(), nullptr));
     std::vector<MetricsSums> sums((size_t)n);
-    HIP_TRY(ctx, hipMemcpyAsync(sums.data(), ctx->d_msums, (size_t)n * sizeof(MetricsSums), hipMemcpyDeviceToHost, cs));
+    HIP_TRY(ctx, hipMemcpyAsync(sums.data(), ctx->d_msums.get(), (size_t)n * sizeof(MetricsSums), hipMemcpyDeviceToHost, cs));
     if (const int rc = read_overflow(ctx)) return rc;
     for (int k = 0; k < n; ++k) fill_metrics(vw, vh, sums[(size_t)k], out[k]);
     return WRENC_GPU_OK;
@@ -2338,29 +2297,25 @@ int wrenc_gpu_download_metrics(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_
 int wrenc_gpu_download_complexity(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_gpu_complexity* out) {
     if (!ctx || !out) return WRENC_GPU_EINVAL;
     const wrenc_gpu_config& c = ctx->cfg;
-    if (first_slot < 0 || n < 1 || first_slot + n > c.n_slots) return fail(ctx, WRENC_GPU_EINVAL, "slot range out of bounds");
-    for (int s = first_slot; s < first_slot + n; ++s)
-        if (ctx->state[s] == 0) return fail(ctx, WRENC_GPU_ESTATE, "slot has no uploaded picture");
+    if (const int rc = check_slots(ctx, first_slot, n, 1, "slot range out of bounds")) return rc;
     HIP_TRY(ctx, hipSetDevice(c.device));
     const size_t per_pic = (size_t)cplx_waves(c.width, c.height), n_ctus = (size_t)ctx->ctu_cols * ctx->ctu_rows;
-    if (!ctx->d_xmap) {
-        HIP_TRY(ctx, realloc_scratch(ctx->d_xpartial, (size_t)c.n_slots * per_pic * sizeof(ComplexityPartial)));
-        HIP_TRY(ctx, realloc_scratch(ctx->d_xsums, (size_t)c.n_slots * sizeof(ComplexityPartial)));
-        HIP_TRY(ctx, realloc_scratch(ctx->d_xmap, (size_t)c.n_slots * n_ctus * sizeof(uint32_t)));
-    }
+    if (!ctx->d_xpartial) HIP_TRY(ctx, ctx->d_xpartial.alloc((size_t)c.n_slots * per_pic));
+    if (!ctx->d_xsums) HIP_TRY(ctx, ctx->d_xsums.alloc((size_t)c.n_slots));
+    if (!ctx->d_xmap) HIP_TRY(ctx, ctx->d_xmap.alloc((size_t)c.n_slots * n_ctus));
     // on the copy stream: behind the slots' uploads (queued there) and behind no search -- the pass reads the originals only,
     // which a search of the same slot reads too and nothing but an upload writes
     hipStream_t cs = ctx->copy_stream;
     const size_t waves = (size_t)n * per_pic;
-    hipLaunchKernelGGL(complexity_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, cs, ctx->d_slots, first_slot, n, c.width,
-                       c.height, ctx->d_xpartial, ctx->d_xmap);
-    hipLaunchKernelGGL(complexity_finish_kernel, dim3(n), dim3(64), 0, cs, ctx->d_xpartial, c.width, c.height, ctx->d_xsums);
+    hipLaunchKernelGGL(complexity_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, cs, ctx->d_slots.get(), first_slot, n, c.width,
+                       c.height, ctx->d_xpartial.get(), ctx->d_xmap.get());
+    hipLaunchKernelGGL(complexity_finish_kernel, dim3(n), dim3(64), 0, cs, ctx->d_xpartial.get(), c.width, c.height, ctx->d_xsums.get());
     HIP_TRY(ctx, hipGetLastError());
     std::vector<ComplexityPartial> sums((size_t)n);
-    HIP_TRY(ctx, hipMemcpyAsync(sums.data(), ctx->d_xsums, (size_t)n * sizeof(ComplexityPartial), hipMemcpyDeviceToHost, cs));
+    HIP_TRY(ctx, hipMemcpyAsync(sums.data(), ctx->d_xsums.get(), (size_t)n * sizeof(ComplexityPartial), hipMemcpyDeviceToHost, cs));
     for (int k = 0; k < n; ++k)
         if (out[k].ctu_satd)
-            HIP_TRY(ctx, hipMemcpyAsync(out[k].ctu_satd, ctx->d_xmap + (size_t)k * n_ctus, n_ctus * sizeof(uint32_t), hipMemcpyDeviceToHost, cs));
+            HIP_TRY(ctx, hipMemcpyAsync(out[k].ctu_satd, ctx->d_xmap.get() + (size_t)k * n_ctus, n_ctus * sizeof(uint32_t), hipMemcpyDeviceToHost, cs));
     HIP_TRY(ctx, hipStreamSynchronize(cs));
     for (int k = 0; k < n; ++k)
         for (int p = 0; p < 3; ++p) out[k].satd[p] = sums[(size_t)k].satd[p];
@@ -2370,24 +2325,20 @@ int wrenc_gpu_download_complexity(wrenc_gpu_ctx* ctx, int first_slot, int n, wre
 int wrenc_gpu_download_rate_hist(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_rate_hist* out) {
     if (!ctx || !out) return WRENC_GPU_EINVAL;
     const wrenc_gpu_config& c = ctx->cfg;
-    if (first_slot < 0 || n < 1 || first_slot + n > c.n_slots) return fail(ctx, WRENC_GPU_EINVAL, "slot range out of bounds");
-    for (int s = first_slot; s < first_slot + n; ++s)
-        if (ctx->state[s] == 0) return fail(ctx, WRENC_GPU_ESTATE, "slot has no uploaded picture");
+    if (const int rc = check_slots(ctx, first_slot, n, 1, "slot range out of bounds")) return rc;
     HIP_TRY(ctx, hipSetDevice(c.device));
     static_assert(sizeof(RateHistCounts) == sizeof(wrenc_rate_hist), "the device's table is the ABI's");
     const size_t per_pic = (size_t)cplx_waves(c.width, c.height);
-    if (!ctx->d_rsums) {
-        HIP_TRY(ctx, realloc_scratch(ctx->d_rpartial, (size_t)c.n_slots * per_pic * sizeof(RateHistPartial)));
-        HIP_TRY(ctx, realloc_scratch(ctx->d_rsums, (size_t)c.n_slots * sizeof(RateHistCounts)));
-    }
+    if (!ctx->d_rpartial) HIP_TRY(ctx, ctx->d_rpartial.alloc((size_t)c.n_slots * per_pic));
+    if (!ctx->d_rsums) HIP_TRY(ctx, ctx->d_rsums.alloc((size_t)c.n_slots));
     // on the copy stream: behind the slots' uploads and behind no search, as the complexity pass
     hipStream_t cs = ctx->copy_stream;
     const size_t waves = (size_t)n * per_pic;
-    hipLaunchKernelGGL(rate_hist_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, cs, ctx->d_slots, first_slot, n, c.width, c.height,
-                       ctx->d_rpartial);
-    hipLaunchKernelGGL(rate_hist_finish_kernel, dim3(n), dim3(192), 0, cs, ctx->d_rpartial, c.width, c.height, ctx->d_rsums);
+    hipLaunchKernelGGL(rate_hist_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, cs, ctx->d_slots.get(), first_slot, n, c.width, c.height,
+                       ctx->d_rpartial.get());
+    hipLaunchKernelGGL(rate_hist_finish_kernel, dim3(n), dim3(192), 0, cs, ctx->d_rpartial.get(), c.width, c.height, ctx->d_rsums.get());
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_rsums, (size_t)n * sizeof(wrenc_rate_hist), hipMemcpyDeviceToHost, cs));
+    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_rsums.get(), (size_t)n * sizeof(wrenc_rate_hist), hipMemcpyDeviceToHost, cs));
     HIP_TRY(ctx, hipStreamSynchronize(cs));
     return WRENC_GPU_OK;
 }
@@ -2423,43 +2374,22 @@ int wrenc_gpu_test_metrics(wrenc_gpu_ctx* ctx, const uint8_t* const org[3], cons
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
     const wrenc_gpu_config& c = ctx->cfg;
     const MetPlane L = met_plane(c.width, c.height, 0), C = met_plane(c.width, c.height, 1);
-    const size_t wh = (size_t)c.width * c.height, n_win = (size_t)L.windows + 2 * (size_t)C.windows;
-    // two pictures of its own (planes as one slab each, like a slot's), never a slot of the context
-    uint8_t* d_planes = nullptr;
-    PicBufs* d_pic = nullptr;
-    MetricsPartial* d_part = nullptr;
-    MetricsSums* d_sums = nullptr;
-    float* d_map = nullptr;
+    const size_t n_win = (size_t)L.windows + 2 * (size_t)C.windows;
+    DevBuf<uint8_t> d_planes;
+    DevBuf<PicBufs> d_pic;
+    DevBuf<MetricsPartial> d_part;
+    DevBuf<MetricsSums> d_sums;
+    DevBuf<float> d_map;
     MetricsSums sums = {};
     std::vector<float> map(ssim_map ? n_win : 0);
-    hipError_t e = hipMalloc((void**)&d_planes, 2 * (wh + wh / 2));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_pic, sizeof(PicBufs));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_part, (size_t)(L.waves + 2 * C.waves) * sizeof(MetricsPartial));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_sums, sizeof(MetricsSums));
-    if (e == hipSuccess && ssim_map) e = hipMalloc((void**)&d_map, n_win * sizeof(float));
-    if (e == hipSuccess) {
-        PicBufs pb = {};
-        uint8_t* at = d_planes;
-        for (int p = 0; p < 6 && e == hipSuccess; ++p) { // Y | Cb | Cr of the originals, then of the reconstruction
-            const int comp = p % 3;
-            if (p < 3) pb.org[comp] = at; else pb.rec[comp] = at;
-            e = hipMemcpy(at, p < 3 ? org[comp] : rec[comp], plane_bytes(c, comp, 1), hipMemcpyHostToDevice);
-            at += plane_bytes(c, comp, 1);
-        }
-        if (e == hipSuccess) e = hipMemcpy(d_pic, &pb, sizeof(pb), hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess)
-        e = launch_metrics(c, c.width, c.height, 0, d_pic, 0, 1, d_part, d_sums, d_map);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(&sums, d_sums, sizeof(sums), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && ssim_map) e = hipMemcpy(map.data(), d_map, n_win * sizeof(float), hipMemcpyDeviceToHost);
-    (void)hipFree(d_planes);
-    (void)hipFree(d_pic);
-    (void)hipFree(d_part);
-    (void)hipFree(d_sums);
-    (void)hipFree(d_map);
-    if (e != hipSuccess) (void)hipGetLastError();
-    HIP_TRY(ctx, e);
+    if (const int rc = load_test_picture(ctx, org, rec, d_planes, &d_pic)) return rc;
+    HIP_TRY(ctx, d_part.alloc((size_t)(L.waves + 2 * C.waves)));
+    HIP_TRY(ctx, d_sums.alloc(1));
+    if (ssim_map) HIP_TRY(ctx, d_map.alloc(n_win));
+    HIP_TRY(ctx, launch_metrics(c, c.width, c.height, 0, d_pic.get(), 0, 1, d_part.get(), d_sums.get(), d_map.get()));
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    HIP_TRY(ctx, hipMemcpy(&sums, d_sums.get(), sizeof(sums), hipMemcpyDeviceToHost));
+    if (ssim_map) HIP_TRY(ctx, hipMemcpy(map.data(), d_map.get(), n_win * sizeof(float), hipMemcpyDeviceToHost));
     fill_metrics(c.width, c.height, sums, *out);
     if (ssim_map) {
         const size_t at[3] = {0, (size_t)L.windows, (size_t)L.windows + (size_t)C.windows};
@@ -2509,24 +2439,18 @@ int wrenc_gpu_download_hashes(wrenc_gpu_ctx* ctx, int first_slot, int n, int has
     if (!ctx || !out) return WRENC_GPU_EINVAL;
     if (hash_type != WRENC_HASH_MD5 && hash_type != WRENC_HASH_CRC && hash_type != WRENC_HASH_CHECKSUM)
         return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_download_hashes: unknown hash type");
-    if (const int rc = check_encoded(ctx, first_slot, n, "slot range out of bounds")) return rc;
+    if (const int rc = check_slots(ctx, first_slot, n, 2, "slot range out of bounds")) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
     const wrenc_gpu_config& c = ctx->cfg;
     if (!ctx->hash_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->hash_stream, hipStreamNonBlocking));
-    if (!ctx->d_htables) {
-        HashTables* t = nullptr;
-        HIP_TRY(ctx, realloc_scratch(t, sizeof(HashTables)));
-        const hipError_t e = upload_hash_tables(t, ctx->hash_stream);
-        if (e != hipSuccess) (void)hipFree(t);
-        HIP_TRY(ctx, e);
-        ctx->d_htables = t;
+    if (!ctx->d_htables) { // held by the context once they are filled
+        DevBuf<HashTables> t;
+        HIP_TRY(ctx, t.alloc(1));
+        HIP_TRY(ctx, upload_hash_tables(t.get(), ctx->hash_stream));
+        ctx->d_htables = std::move(t);
     }
-    if (ctx->hash_cap < n) {
-        ctx->hash_cap = 0;
-        HIP_TRY(ctx, realloc_scratch(ctx->d_hpartial, (size_t)n * hash_partials(c) * sizeof(uint32_t)));
-        HIP_TRY(ctx, realloc_scratch(ctx->d_hvalues, (size_t)n * sizeof(wrenc_picture_hash)));
-        ctx->hash_cap = n;
-    }
+    HIP_TRY(ctx, ctx->d_hpartial.grow((size_t)n * hash_partials(c)));
+    HIP_TRY(ctx, ctx->d_hvalues.grow((size_t)n));
     // on the hash stream, behind the encode call that searched these slots and nothing later; the search of other slots
     // and the copy stream's uploads go on meanwhile
     hipStream_t hs = ctx->hash_stream;
@@ -2537,12 +2461,12 @@ int wrenc_gpu_download_hashes(wrenc_gpu_ctx* ctx, int first_slot, int n, int has
             if (!e) HIP_TRY(ctx, hipEventCreate(&e));
         HIP_TRY(ctx, hipEventRecord(ctx->hash_ev[0], hs));
     }
-    HIP_TRY(ctx, launch_hashes(c, hs, ctx->d_slots, first_slot, n, hash_type, ctx->d_htables, ctx->d_hpartial, ctx->d_hvalues));
+    HIP_TRY(ctx, launch_hashes(c, hs, ctx->d_slots.get(), first_slot, n, hash_type, ctx->d_htables.get(), ctx->d_hpartial.get(), ctx->d_hvalues.get()));
     if (ctx->stats_enabled) {
         HIP_TRY(ctx, hipEventRecord(ctx->hash_ev[1], hs));
         ctx->hash_timed = true;
     }
-    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_hvalues, (size_t)n * sizeof(wrenc_picture_hash), hipMemcpyDeviceToHost, hs));
+    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_hvalues.get(), (size_t)n * sizeof(wrenc_picture_hash), hipMemcpyDeviceToHost, hs));
     return read_overflow(ctx, hs); // (synchronises the stream)
 }
 
@@ -2562,39 +2486,19 @@ int wrenc_gpu_test_hash(wrenc_gpu_ctx* ctx, const uint8_t* const rec[3], int has
         if (!rec[p]) return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_test_hash: null plane");
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
     const wrenc_gpu_config& c = ctx->cfg;
-    const size_t wh = (size_t)c.width * c.height;
-    // a picture of its own (planes as one slab, like a slot's), never a slot of the context
-    uint8_t* d_planes = nullptr;
-    PicBufs* d_pic = nullptr;
-    HashTables* d_tables = nullptr;
-    uint32_t* d_part = nullptr;
-    wrenc_picture_hash* d_values = nullptr;
-    hipError_t e = hipMalloc((void**)&d_planes, wh + wh / 2);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_pic, sizeof(PicBufs));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_tables, sizeof(HashTables));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_part, hash_partials(c) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_values, sizeof(wrenc_picture_hash));
-    if (e == hipSuccess) e = upload_hash_tables(d_tables, 0);
-    if (e == hipSuccess) {
-        PicBufs pb = {};
-        uint8_t* at = d_planes;
-        for (int p = 0; p < 3 && e == hipSuccess; ++p) {
-            pb.rec[p] = at;
-            e = hipMemcpy(at, rec[p], plane_bytes(c, p, 1), hipMemcpyHostToDevice);
-            at += plane_bytes(c, p, 1);
-        }
-        if (e == hipSuccess) e = hipMemcpy(d_pic, &pb, sizeof(pb), hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess) e = launch_hashes(c, 0, d_pic, 0, 1, hash_type, d_tables, d_part, d_values);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(out, d_values, sizeof(*out), hipMemcpyDeviceToHost);
-    (void)hipFree(d_planes);
-    (void)hipFree(d_pic);
-    (void)hipFree(d_tables);
-    (void)hipFree(d_part);
-    (void)hipFree(d_values);
-    if (e != hipSuccess) (void)hipGetLastError();
-    HIP_TRY(ctx, e);
+    DevBuf<uint8_t> d_planes;
+    DevBuf<PicBufs> d_pic;
+    DevBuf<HashTables> d_tables;
+    DevBuf<uint32_t> d_part;
+    DevBuf<wrenc_picture_hash> d_values;
+    if (const int rc = load_test_picture(ctx, nullptr, rec, d_planes, &d_pic)) return rc;
+    HIP_TRY(ctx, d_tables.alloc(1));
+    HIP_TRY(ctx, d_part.alloc(hash_partials(c)));
+    HIP_TRY(ctx, d_values.alloc(1));
+    HIP_TRY(ctx, upload_hash_tables(d_tables.get(), 0));
+    HIP_TRY(ctx, launch_hashes(c, 0, d_pic.get(), 0, 1, hash_type, d_tables.get(), d_part.get(), d_values.get()));
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    HIP_TRY(ctx, hipMemcpy(out, d_values.get(), sizeof(*out), hipMemcpyDeviceToHost));
     return WRENC_GPU_OK;
 }
 
@@ -2743,17 +2647,13 @@ int wrenc_gpu_test_set_wave_slots(wrenc_gpu_ctx* ctx, long long slots) {
 int wrenc_gpu_test_head_ranges(wrenc_gpu_ctx* ctx, int counts[4], int ranges[24]) {
     if (!ctx || !counts) return WRENC_GPU_EINVAL;
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-    int* d = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&d, 4 * sizeof(int)));
-    hipError_t e = hipMemset(d, 0, 4 * sizeof(int));
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(test_head_ranges_kernel, dim3(1024, 8), dim3(64), 0, 0, ctx->d_const, d);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(counts, d, 4 * sizeof(int), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    HIP_TRY(ctx, e);
+    DevBuf<int> d;
+    HIP_TRY(ctx, d.alloc(4));
+    HIP_TRY(ctx, hipMemset(d.get(), 0, 4 * sizeof(int)));
+    hipLaunchKernelGGL(test_head_ranges_kernel, dim3(1024, 8), dim3(64), 0, 0, ctx->d_const.get(), d.get());
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    HIP_TRY(ctx, hipMemcpy(counts, d.get(), 4 * sizeof(int), hipMemcpyDeviceToHost));
     if (ranges) {
         DevConst* hk = new DevConst;
         fill_dev_const(ctx->cfg, *hk);
@@ -2766,17 +2666,13 @@ int wrenc_gpu_test_head_ranges(wrenc_gpu_ctx* ctx, int counts[4], int ranges[24]
 int wrenc_gpu_test_avail_tab(wrenc_gpu_ctx* ctx, int* differences) {
     if (!ctx || !differences) return WRENC_GPU_EINVAL;
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-    int* d = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&d, sizeof(int)));
-    hipError_t e = hipMemset(d, 0, sizeof(int));
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(test_avail_tab_kernel, dim3(ctx->ctu_cols * ctx->ctu_rows, 4), dim3(64), 0, 0, ctx->d_const, d);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(differences, d, sizeof(int), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    HIP_TRY(ctx, e);
+    DevBuf<int> d;
+    HIP_TRY(ctx, d.alloc(1));
+    HIP_TRY(ctx, hipMemset(d.get(), 0, sizeof(int)));
+    hipLaunchKernelGGL(test_avail_tab_kernel, dim3(ctx->ctu_cols * ctx->ctu_rows, 4), dim3(64), 0, 0, ctx->d_const.get(), d.get());
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    HIP_TRY(ctx, hipMemcpy(differences, d.get(), sizeof(int), hipMemcpyDeviceToHost));
     return WRENC_GPU_OK;
 }
 
@@ -2787,7 +2683,7 @@ int wrenc_gpu_test_scratch_overflows(wrenc_gpu_ctx* ctx, long long* count) {
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
     HIP_TRY(ctx, hipDeviceSynchronize());
     unsigned long long v = 0;
-    HIP_TRY(ctx, hipMemcpy(&v, ctx->d_slot_map + kScratchSlots / 64, sizeof(v), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(&v, ctx->d_slot_map.get() + kScratchSlots / 64, sizeof(v), hipMemcpyDeviceToHost));
     *count = (long long)v;
     return WRENC_GPU_OK;
 }
@@ -2804,7 +2700,7 @@ int wrenc_gpu_final_pass_mismatches(wrenc_gpu_ctx* ctx, long long* count) {
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     unsigned long long v = 0;
-    HIP_TRY(ctx, hipMemcpy(&v, ctx->d_mismatch, sizeof(v), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(&v, ctx->d_mismatch.get(), sizeof(v), hipMemcpyDeviceToHost));
     *count = (long long)v;
     return WRENC_GPU_OK;
 }
@@ -2870,7 +2766,7 @@ int wrenc_gpu_test_fwd_dct_nb(wrenc_gpu_ctx* ctx, const int16_t* res, int log2n,
     if (log2n == 5 && count >= 1 && !residuals_fit_9_bits(res, (size_t)count * 1024))
         return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_test_fwd_dct: a 32x32 residual lies outside +-255");
     return run_block_test(ctx, res, log2n, count, coef, [&](int16_t* i, int16_t* o) {
-        hipLaunchKernelGGL(test_fwd_dct_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const, i, log2n, nb, o1, o);
+        hipLaunchKernelGGL(test_fwd_dct_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const.get(), i, log2n, nb, o1, o);
     }, nb);
 }
 int wrenc_gpu_test_fwd_dct(wrenc_gpu_ctx* ctx, const int16_t* res, int log2n, int count, int16_t* coef) {
@@ -2882,35 +2778,15 @@ static int run_dct32_bench(wrenc_gpu_ctx* ctx, const int16_t* in, int count, int
     if (!ctx || !in || !out || count < 1 || reps < 1) return WRENC_GPU_EINVAL;
     if (!inverse && use_mfma && !residuals_fit_9_bits(in, (size_t)count * 1024))
         return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_test_fwd_dct32: a residual lies outside +-255 (MFMA path)");
-    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-    const size_t bytes = (size_t)count * 1024 * sizeof(int16_t);
-    int16_t *d_in = nullptr, *d_out = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&d_in, bytes));
-    hipError_t e = hipMalloc((void**)&d_out, bytes);
-    if (e == hipSuccess) e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipMemcpy(d_in, in, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipEventRecord(e0, ctx->stream);
-    if (e == hipSuccess) {
-        if (inverse)
-            hipLaunchKernelGGL(test_inv_dct32_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const, d_in, d_out, use_mfma, reps);
-        else
-            hipLaunchKernelGGL(test_fwd_dct32_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const, d_in, d_out, use_mfma, reps);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(e1, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     float ms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    if (e == hipSuccess) e = hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost);
+    const int rc = run_block_test(ctx, in, 5, count, out, [&](int16_t* i, int16_t* o) {
+        if (inverse)
+            hipLaunchKernelGGL(test_inv_dct32_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const.get(), i, o, use_mfma, reps);
+        else
+            hipLaunchKernelGGL(test_fwd_dct32_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const.get(), i, o, use_mfma, reps);
+    }, 1, &ms);
     if (kernel_ms) *kernel_ms = ms;
-    (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (e != hipSuccess) return fail(ctx, WRENC_GPU_EHIP, hipGetErrorString(e));
-    return WRENC_GPU_OK;
+    return rc;
 }
 int wrenc_gpu_test_fwd_dct32(wrenc_gpu_ctx* ctx, const int16_t* res, int count, int16_t* coef, int use_mfma, int reps,
                              float* kernel_ms) {
@@ -2924,7 +2800,7 @@ int wrenc_gpu_test_inv_dct_nb(wrenc_gpu_ctx* ctx, const int16_t* deq, int log2n,
     if (!ctx || !deq || !res) return WRENC_GPU_EINVAL;
     if (const char* why = group_shape_error(log2n, nb, o1, kGroupMaxBlocks)) return fail(ctx, WRENC_GPU_EINVAL, why);
     return run_block_test(ctx, deq, log2n, count, res, [&](int16_t* i, int16_t* o) {
-        hipLaunchKernelGGL(test_inv_dct_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const, i, log2n, nb, o1, o);
+        hipLaunchKernelGGL(test_inv_dct_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const.get(), i, log2n, nb, o1, o);
     }, nb);
 }
 int wrenc_gpu_test_inv_dct(wrenc_gpu_ctx* ctx, const int16_t* deq, int log2n, int count, int16_t* res) {
@@ -2932,19 +2808,19 @@ int wrenc_gpu_test_inv_dct(wrenc_gpu_ctx* ctx, const int16_t* deq, int log2n, in
 }
 int wrenc_gpu_test_fwd_dct4_reg(wrenc_gpu_ctx* ctx, const int16_t* res, int count, int16_t* coef) {
     return run_block_test(ctx, res, 2, count, coef, [&](int16_t* i, int16_t* o) {
-        hipLaunchKernelGGL(test_dct4_reg_kernel, dim3((count + 3) / 4), dim3(64), 0, ctx->stream, ctx->d_const, i, count, 0, o);
+        hipLaunchKernelGGL(test_dct4_reg_kernel, dim3((count + 3) / 4), dim3(64), 0, ctx->stream, ctx->d_const.get(), i, count, 0, o);
     });
 }
 int wrenc_gpu_test_inv_dct4_reg(wrenc_gpu_ctx* ctx, const int16_t* levels, int count, int16_t* res) {
     return run_block_test(ctx, levels, 2, count, res, [&](int16_t* i, int16_t* o) {
-        hipLaunchKernelGGL(test_dct4_reg_kernel, dim3((count + 3) / 4), dim3(64), 0, ctx->stream, ctx->d_const, i, count, 1, o);
+        hipLaunchKernelGGL(test_dct4_reg_kernel, dim3((count + 3) / 4), dim3(64), 0, ctx->stream, ctx->d_const.get(), i, count, 1, o);
     });
 }
 int wrenc_gpu_test_dequantize_nb(wrenc_gpu_ctx* ctx, const int16_t* levels, int log2n, int nb, int o1, int count, int16_t* deq) {
     if (!ctx || !levels || !deq) return WRENC_GPU_EINVAL;
     if (const char* why = group_shape_error(log2n, nb, o1, kGroupMaxBlocks)) return fail(ctx, WRENC_GPU_EINVAL, why);
     return run_block_test(ctx, levels, log2n, count, deq, [&](int16_t* i, int16_t* o) {
-        hipLaunchKernelGGL(test_dequantize_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const, i, log2n, nb, o1, o);
+        hipLaunchKernelGGL(test_dequantize_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const.get(), i, log2n, nb, o1, o);
     }, nb);
 }
 int wrenc_gpu_test_dequantize(wrenc_gpu_ctx* ctx, const int16_t* levels, int log2n, int count, int16_t* deq) {
@@ -2957,26 +2833,20 @@ int wrenc_gpu_test_quantize_nb(wrenc_gpu_ctx* ctx, const int16_t* coef, int log2
     if (const char* why = group_shape_error(log2n, nb, 0, 2)) return fail(ctx, WRENC_GPU_EINVAL, why);
     if (count < 1) return fail(ctx, WRENC_GPU_EINVAL, "count must be >= 1");
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-    long long* d_cost = nullptr;
-    int* d_any = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&d_cost, sizeof(long long) * count));
-    hipError_t ea = hipMalloc((void**)&d_any, sizeof(int) * count);
-    if (ea != hipSuccess) {
-        (void)hipFree(d_cost);
-        return fail(ctx, WRENC_GPU_EHIP, hipGetErrorString(ea));
-    }
-    int rc = run_block_test(ctx, coef, log2n, count, levels, [&](int16_t* i, int16_t* o) {
-        hipLaunchKernelGGL(test_quantize_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const, i, log2n, nb, o,
-                           d_cost, d_any, ctx->d_overflow + 1);
-    }, nb);
-    if (rc == WRENC_GPU_OK) {
-        hipError_t e = hipMemcpy(level_cost, d_cost, sizeof(long long) * count, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && any_level) e = hipMemcpy(any_level, d_any, sizeof(int) * count, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(ctx, WRENC_GPU_EHIP, hipGetErrorString(e));
-    }
-    (void)hipFree(d_cost);
-    (void)hipFree(d_any);
-    return take_test_overflow(ctx, rc);
+    DevBuf<long long> d_cost;
+    DevBuf<int> d_any;
+    return take_test_overflow(ctx, [&]() -> int {
+        HIP_TRY(ctx, d_cost.alloc((size_t)count));
+        HIP_TRY(ctx, d_any.alloc((size_t)count));
+        const int rc = run_block_test(ctx, coef, log2n, count, levels, [&](int16_t* i, int16_t* o) {
+            hipLaunchKernelGGL(test_quantize_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const.get(), i, log2n, nb, o,
+                               d_cost.get(), d_any.get(), ctx->d_overflow.get() + 1);
+        }, nb);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemcpy(level_cost, d_cost.get(), sizeof(long long) * count, hipMemcpyDeviceToHost));
+        if (any_level) HIP_TRY(ctx, hipMemcpy(any_level, d_any.get(), sizeof(int) * count, hipMemcpyDeviceToHost));
+        return WRENC_GPU_OK;
+    }());
 }
 int wrenc_gpu_test_quantize(wrenc_gpu_ctx* ctx, const int16_t* coef, int log2n, int count, int16_t* levels,
                             int64_t* level_cost) {
@@ -2987,18 +2857,17 @@ int wrenc_gpu_test_quantize_p16(wrenc_gpu_ctx* ctx, const int16_t* coef, int cou
     if (!ctx || !level_cost) return WRENC_GPU_EINVAL;
     if (count < 1) return fail(ctx, WRENC_GPU_EINVAL, "count must be >= 1");
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-    long long* d_cost = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&d_cost, sizeof(long long) * count));
-    int rc = run_block_test(ctx, coef, 2, count, levels, [&](int16_t* i, int16_t* o) {
-        hipLaunchKernelGGL(test_quantize_p16_kernel, dim3((count + 3) / 4), dim3(64), 0, ctx->stream, ctx->d_const, i, count, o,
-                           d_cost, ctx->d_overflow + 1);
-    });
-    if (rc == WRENC_GPU_OK) {
-        hipError_t e = hipMemcpy(level_cost, d_cost, sizeof(long long) * count, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(ctx, WRENC_GPU_EHIP, hipGetErrorString(e));
-    }
-    (void)hipFree(d_cost);
-    return take_test_overflow(ctx, rc);
+    DevBuf<long long> d_cost;
+    return take_test_overflow(ctx, [&]() -> int {
+        HIP_TRY(ctx, d_cost.alloc((size_t)count));
+        const int rc = run_block_test(ctx, coef, 2, count, levels, [&](int16_t* i, int16_t* o) {
+            hipLaunchKernelGGL(test_quantize_p16_kernel, dim3((count + 3) / 4), dim3(64), 0, ctx->stream, ctx->d_const.get(), i, count, o,
+                               d_cost.get(), ctx->d_overflow.get() + 1);
+        });
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemcpy(level_cost, d_cost.get(), sizeof(long long) * count, hipMemcpyDeviceToHost));
+        return WRENC_GPU_OK;
+    }());
 }
 
 int wrenc_gpu_test_quantize_pk(wrenc_gpu_ctx* ctx, const int16_t* coef, int log2n, int nc, int n_packs, int16_t* levels,
@@ -3008,24 +2877,22 @@ int wrenc_gpu_test_quantize_pk(wrenc_gpu_ctx* ctx, const int16_t* coef, int log2
         return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_test_quantize_pk: log2n 3 with nc 1..3 or log2n 4 with nc 1..2");
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
     const size_t total = (size_t)n_packs * nc * 3 * ((size_t)1 << (2 * log2n)) / 2;
-    int16_t *d_in = nullptr, *d_out = nullptr;
-    long long* d_cost = nullptr;
-    hipError_t e = hipMalloc((void**)&d_in, total * sizeof(int16_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_out, total * sizeof(int16_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_cost, sizeof(long long) * 2 * nc * n_packs);
-    if (e == hipSuccess) e = hipMemcpy(d_in, coef, total * sizeof(int16_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(test_quantize_pk_kernel, dim3(n_packs), dim3(64), 0, ctx->stream, ctx->d_const, d_in, log2n, nc, d_out,
-                           d_cost, ctx->d_overflow + 1);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = hipMemcpy(levels, d_out, total * sizeof(int16_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(level_cost, d_cost, sizeof(long long) * 2 * nc * n_packs, hipMemcpyDeviceToHost);
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (d_cost) (void)hipFree(d_cost);
-    return take_test_overflow(ctx, e != hipSuccess ? fail(ctx, WRENC_GPU_EHIP, hipGetErrorString(e)) : WRENC_GPU_OK);
+    const size_t n_costs = (size_t)2 * nc * n_packs;
+    DevBuf<int16_t> d_in, d_out;
+    DevBuf<long long> d_cost;
+    return take_test_overflow(ctx, [&]() -> int {
+        HIP_TRY(ctx, d_in.alloc(total));
+        HIP_TRY(ctx, d_out.alloc(total));
+        HIP_TRY(ctx, d_cost.alloc(n_costs));
+        HIP_TRY(ctx, hipMemcpy(d_in.get(), coef, total * sizeof(int16_t), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(test_quantize_pk_kernel, dim3(n_packs), dim3(64), 0, ctx->stream, ctx->d_const.get(), d_in.get(), log2n, nc,
+                           d_out.get(), d_cost.get(), ctx->d_overflow.get() + 1);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, hipMemcpy(levels, d_out.get(), total * sizeof(int16_t), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(level_cost, d_cost.get(), sizeof(long long) * n_costs, hipMemcpyDeviceToHost));
+        return WRENC_GPU_OK;
+    }());
 }
 
 int wrenc_gpu_test_predict(wrenc_gpu_ctx* ctx, const uint8_t* rec_y, const uint8_t* rec_cb, const uint8_t* rec_cr,
@@ -3068,29 +2935,19 @@ int wrenc_gpu_test_predict(wrenc_gpu_ctx* ctx, const uint8_t* rec_y, const uint8
     }
     if (total != out_bytes) return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_test_predict: output size does not match the items");
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-    const size_t wh = (size_t)W * H;
-    uint8_t *d_planes = nullptr, *d_scratch = nullptr, *d_out = nullptr;
-    int* d_items = nullptr;
-    hipError_t e = hipMalloc((void**)&d_planes, wh + wh / 2);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_scratch, (size_t)n_items * kTestPredictScratch);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_out, total);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_items, dev_items.size() * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(d_planes, rec_y, wh, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_planes + wh, rec_cb, wh / 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_planes + wh + wh / 4, rec_cr, wh / 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_items, dev_items.data(), dev_items.size() * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(test_predict_kernel, dim3(n_items), dim3(64), 0, ctx->stream, ctx->d_const, d_planes, d_items,
-                           d_scratch, d_out);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = hipMemcpy(out, d_out, total, hipMemcpyDeviceToHost);
-    if (d_planes) (void)hipFree(d_planes);
-    if (d_scratch) (void)hipFree(d_scratch);
-    if (d_out) (void)hipFree(d_out);
-    if (d_items) (void)hipFree(d_items);
-    if (e != hipSuccess) return fail(ctx, WRENC_GPU_EHIP, hipGetErrorString(e));
+    const uint8_t* const rec[3] = {rec_y, rec_cb, rec_cr};
+    DevBuf<uint8_t> d_planes, d_scratch, d_out;
+    DevBuf<int> d_items;
+    if (const int rc = load_test_picture(ctx, nullptr, rec, d_planes, nullptr)) return rc;
+    HIP_TRY(ctx, d_scratch.alloc((size_t)n_items * kTestPredictScratch));
+    HIP_TRY(ctx, d_out.alloc(total));
+    HIP_TRY(ctx, d_items.alloc(dev_items.size()));
+    HIP_TRY(ctx, hipMemcpy(d_items.get(), dev_items.data(), dev_items.size() * sizeof(int), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(test_predict_kernel, dim3(n_items), dim3(64), 0, ctx->stream, ctx->d_const.get(), d_planes.get(), d_items.get(),
+                       d_scratch.get(), d_out.get());
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy(out, d_out.get(), total, hipMemcpyDeviceToHost));
     return WRENC_GPU_OK;
 }
 
