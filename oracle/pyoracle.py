@@ -173,8 +173,22 @@ def spec_trans_matrix():
     return m
 
 
+# wro_debug_perturb codes 11..17: one tie rule of split_ct taken the other way (oracle/wrenc_oracle.h)
+TIE_R1_COARSE_LAST_MIN = 11     # the last minimum of the 13 coarse SADs
+TIE_R2_STEP_NEIGHBOUR = 12      # step search: a neighbour takes a tie against the current mode
+TIE_R3_STEP_UP_FIRST = 13       # step search: mode + step before mode - step
+TIE_R4_FINAL_LAST_MIN = 14      # the last minimum of [planar, DC, directional]
+TIE_R5_CCLM_STRICT = 15         # the CCLM pick on < instead of <=
+TIE_R6_CCLM_TAKES_TIE = 16      # CCLM takes a tie against the derived chroma mode
+TIE_R7_TIE_UNSPLIT = 17         # split_cost >= no_split_cost: a tie goes to the unsplit node
+TIE_RULES = {"R1": TIE_R1_COARSE_LAST_MIN, "R2": TIE_R2_STEP_NEIGHBOUR, "R3": TIE_R3_STEP_UP_FIRST,
+             "R4": TIE_R4_FINAL_LAST_MIN, "R5": TIE_R5_CCLM_STRICT, "R6": TIE_R6_CCLM_TAKES_TIE,
+             "R7": TIE_R7_TIE_UNSPLIT}
+
+
 def debug_perturb(which):
-    """Deliberate misreading of one constant inside the oracle (wro_debug_perturb); 0 switches it off."""
+    """wro_debug_perturb: 1..4 a deliberate misreading of one constant inside the oracle, 11..17 (TIE_RULES) one tie
+    rule of the search taken the other way; 0 switches it off."""
     lib().wro_debug_perturb(int(which))
 
 

@@ -50,9 +50,23 @@ static inline size_t tbl(size_t i) {
     return i;
 }
 static bool g_tables_ready = false;
-// Test hook (wro_debug_perturb): a deliberate misreading of one constant, to prove that the independent
-// spec decoder notices what the oracle + GPU pair cannot notice about themselves.  0 = none.
+// Test hook (wro_debug_perturb).  0 = none.
+//   1..4: a deliberate misreading of one constant, to prove that the independent spec decoder notices what the
+//         oracle + GPU pair cannot notice about themselves.
+//   11..17: one tie rule of split_ct taken the other way (kTieR1..kTieR7 below; R5 and R6 at both of their sites).
+//         These leave every stream valid and decodable, so the spec decoder cannot and must not notice them.  They
+//         are there to prove that a set of pictures can tell the two sides of a tie apart: a case list under which
+//         a flipped rule changes no record says nothing about the side the device takes (tests/tie_cases.py).
 static int g_perturb = 0;
+enum {
+    kTieR1 = 11, // the LAST minimum of the 13 coarse directional SADs, not the first
+    kTieR2 = 12, // step search: a neighbour takes a tie against the current mode
+    kTieR3 = 13, // step search: mode + step before mode - step on a tie
+    kTieR4 = 14, // the LAST minimum of [planar, DC, directional]
+    kTieR5 = 15, // CCLM pick on < instead of <= (LT against T and L, then T against L)
+    kTieR6 = 16, // CCLM takes a tie against the derived (DM) chroma mode
+    kTieR7 = 17, // split_cost >= no_split_cost: a tie goes to the unsplit node
+};
 
 // intraPredAngle for predModeIntra -14..80 (H.266 Table 24; common.rs:145)
 static const int kIntraAngle[95] = {
@@ -2018,6 +2032,19 @@ struct Splitter {
             if (v[i] == m) return i;
         abort();
     }
+    // first_eq, or the last equal entry under the tie switch `flip` (g_perturb)
+    static int pick_eq(const float* v, int n, float m, int flip) {
+        if (g_perturb != flip) return first_eq(v, n, m);
+        for (int i = n - 1; i >= 0; --i)
+            if (v[i] == m) return i;
+        abort();
+    }
+    // the CCLM mode of the smallest SAD (block_splitter.rs:847-854)
+    static int pick_cclm(float lt, float t, float l) {
+        if (g_perturb == kTieR5) return lt < t && lt < l ? LT_CCLM : t < l ? T_CCLM : L_CCLM;
+        if (lt <= t && lt <= l) return LT_CCLM;
+        return t <= l ? T_CCLM : L_CCLM;
+    }
 
     // ctu.rs:1960-2064 (SPLIT_QT only)
     void split(Node* self) {
@@ -2071,20 +2098,14 @@ struct Splitter {
                 const float cclm_lt = get_chroma_intra_pred_aux_cost(LT_CCLM, ct);
                 const float cclm_t = get_chroma_intra_pred_aux_cost(T_CCLM, ct);
                 const float cclm_l = get_chroma_intra_pred_aux_cost(L_CCLM, ct);
-                int cclm_mode;
-                if (cclm_lt <= cclm_t && cclm_lt <= cclm_l)
-                    cclm_mode = LT_CCLM;
-                else if (cclm_t <= cclm_l)
-                    cclm_mode = T_CCLM;
-                else
-                    cclm_mode = L_CCLM;
+                const int cclm_mode = pick_cclm(cclm_lt, cclm_t, cclm_l);
                 const float cclm_cost = get_chroma_intra_pred_cost(cclm_mode, ct);
                 std::vector<uint8_t> cache[3];
                 cache_reconsts(ct, 1, 3, cache);
                 const float current_cost = get_chroma_intra_pred_cost(chroma_pred_mode, ct);
                 const float cands[2] = {current_cost, cclm_cost};
                 const float mn = fmin_fold(cands, 2);
-                const int idx = first_eq(cands, 2, mn);
+                const int idx = pick_eq(cands, 2, mn, kTieR6);
                 if (idx == 1) {
                     const int m3[3] = {cclm_mode, cclm_mode, cclm_mode};
                     ct->cus[0]->set_intra_pred_mode(m3);
@@ -2100,7 +2121,7 @@ struct Splitter {
                                                    : get_intra_pred_aux_cost(m3, ct);
             }
             const float min_dir_cost = fmin_fold(cand_costs + 2, 13);
-            const int min_dir_idx = first_eq(cand_costs + 2, 13, min_dir_cost) + 2;
+            const int min_dir_idx = pick_eq(cand_costs + 2, 13, min_dir_cost, kTieR1) + 2;
             auto step_search = [&](int current_mode, int step, float current_cost, bool aux,
                                    float& out_cost) -> int {
                 if (!aux) {
@@ -2124,8 +2145,9 @@ struct Splitter {
                         cost1 = aux ? get_intra_pred_aux_cost(m3, ct) : get_intra_pred_cost(m3, ct);
                     }
                     const float min_cost = std::fmin(std::fmin(current_cost, cost0), cost1);
-                    if (current_cost == min_cost) {
-                    } else if (cost0 == min_cost) {
+                    const bool down_first = g_perturb != kTieR3 || cost0 != cost1;
+                    if (current_cost == min_cost && !(g_perturb == kTieR2 && (cost0 == min_cost || cost1 == min_cost))) {
+                    } else if (cost0 == min_cost && down_first) {
                         current_mode = current_mode - step;
                         current_cost = cost0;
                     } else {
@@ -2143,7 +2165,7 @@ struct Splitter {
             const int cand_modes[3] = {0, 1, dir_mode};
             const float cc[3] = {cand_costs[0], cand_costs[1], dir_cost};
             float min_cost = fmin_fold(cc, 3);
-            const int min_idx = first_eq(cc, 3, min_cost);
+            const int min_idx = pick_eq(cc, 3, min_cost, kTieR4);
             CU* cu = ct->cus[0];
             const int mode = cand_modes[min_idx];
             {
@@ -2159,17 +2181,11 @@ struct Splitter {
                 const float cclm_lt = get_chroma_intra_pred_aux_cost(LT_CCLM, ct);
                 const float cclm_t = get_chroma_intra_pred_aux_cost(T_CCLM, ct);
                 const float cclm_l = get_chroma_intra_pred_aux_cost(L_CCLM, ct);
-                int cclm_mode;
-                if (cclm_lt <= cclm_t && cclm_lt <= cclm_l)
-                    cclm_mode = LT_CCLM;
-                else if (cclm_t <= cclm_l)
-                    cclm_mode = T_CCLM;
-                else
-                    cclm_mode = L_CCLM;
+                const int cclm_mode = pick_cclm(cclm_lt, cclm_t, cclm_l);
                 const float cclm_cost = get_chroma_intra_pred_cost(cclm_mode, ct);
                 const float cands[2] = {current_cost, cclm_cost};
                 const float mn = fmin_fold(cands, 2);
-                const int idx = first_eq(cands, 2, mn);
+                const int idx = pick_eq(cands, 2, mn, kTieR6);
                 if (idx == 0) {
                     const int m3[3] = {mode, mode, mode};
                     cu->set_intra_pred_mode(m3);
@@ -2197,7 +2213,7 @@ struct Splitter {
         const size_t n = sct->cts.size();
         float split_cost = 0.0f;
         for (size_t i = 0; i < n; ++i) split_cost += split_ct(sct->cts[i], max_depth - 1);
-        if (split_cost > no_split_cost) {
+        if (g_perturb == kTieR7 ? split_cost >= no_split_cost : split_cost > no_split_cost) {
             restore_reconsts(ct, c0, c1, no_split);
             return no_split_cost;
         }

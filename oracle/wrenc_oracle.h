@@ -122,6 +122,12 @@ float wro_lambda_rd_chroma(int qp);
 // quantizer.rs:8,617-622; 4 inverse-transform first-stage offset 64 -> 63, transformer.rs:2569-2580).  The
 // perturbed oracle stays self-consistent (its own decoder-side reconstruction still agrees with it); the
 // independent spec decoder (spec_decoder.cpp) must disagree.  tests/test_spec_decoder.py.
+// 11..17: ONE tie rule of split_ct taken the other way (block_splitter.rs): 11 the last minimum of the 13 coarse
+// SADs; 12 step search, a neighbour takes a tie against the current mode; 13 step search, mode + step before
+// mode - step; 14 the last minimum of [planar, DC, directional]; 15 the CCLM pick on < instead of <=; 16 CCLM takes
+// a tie against the derived chroma mode; 17 split_cost >= no_split_cost, a tie goes to the unsplit node.  Every
+// stream stays valid, so the spec decoder has nothing to notice; they prove that a list of pictures can tell the
+// two sides of a tie apart (tests/tie_cases.py, tests/test_tie_cases.py).
 void wro_debug_perturb(int which);
 
 // Trace of every candidate evaluation of the search (block_splitter.rs:64-108, 110-474, 476-522,

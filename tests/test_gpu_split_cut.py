@@ -79,11 +79,11 @@ def test_records_equal_the_oracle(built, kind, qp, depth):
     enc.close()
 
 
-def _encode_with(gpu, path, frames, w, h, qp, depth):
+def _encode_with(gpu, path, frames, w, h, qp, depth, extra_params=None):
     saved = (gpu._lib, gpu.LIB_PATH)
     gpu._lib, gpu.LIB_PATH = None, path
     try:
-        enc = gpu.Encoder(w, h, qp=qp, max_split_depth=depth, n_slots=len(frames), schedule=1)
+        enc = gpu.Encoder(w, h, qp=qp, max_split_depth=depth, n_slots=len(frames), schedule=1, extra_params=extra_params)
         for s, f in enumerate(frames):
             enc.upload(s, *f)
         enc.encode(0, len(frames))

@@ -27,9 +27,9 @@ def trace_gpu(built):
         gpu._lib, gpu.LIB_PATH = saved
 
 
-def _gpu_trace(gpu, y, cb, cr, qp, depth, schedule):
+def _gpu_trace(gpu, y, cb, cr, qp, depth, schedule, extra_params=None):
     h, w = y.shape
-    enc = gpu.Encoder(w, h, qp=qp, max_split_depth=depth, schedule=schedule)
+    enc = gpu.Encoder(w, h, qp=qp, max_split_depth=depth, schedule=schedule, extra_params=extra_params)
     fn = enc.lib.wrenc_gpu_trace_read
     fn.restype = C.c_long
     fn.argtypes = [C.c_void_p, C.c_void_p, C.c_long]
