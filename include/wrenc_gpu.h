@@ -519,6 +519,20 @@ int wrenc_gpu_test_fwd_dct_nb(wrenc_gpu_ctx* ctx, const int16_t* res, int log2n,
 int wrenc_gpu_test_inv_dct_nb(wrenc_gpu_ctx* ctx, const int16_t* deq, int log2n, int nb, int o1, int count, int16_t* res);
 int wrenc_gpu_test_dequantize_nb(wrenc_gpu_ctx* ctx, const int16_t* levels, int log2n, int nb, int o1, int count,
                                  int16_t* deq);
+/* The 16x16 transforms (log2n = 4) run as i8 MFMAs in the search (wrenc_amd/csrc/dev_transform.h fwd_dct_mfma /
+ * inv_dct_mfma): exact for forward residuals within +-255 and any int16 inverse input, with the group at an o1 that is a
+ * multiple of 8 -- all of which the search has by construction.  The same code exists for 8x8 (log2n = 3), where the
+ * search keeps the v_dot2 templates.  wrenc_gpu_test_fwd_dct(_nb) and _inv_dct(_nb) inspect the group on the host before
+ * the launch: a 16x16 forward group with a residual outside +-255, or a 16x16 group at another o1, runs the retained
+ * v_dot2 templates and still returns the reference's answer; every other group runs the code the search runs.  The two
+ * entries below choose the arm themselves at log2n = 3 or 4, for the parity tests and tools/dct_bench.py: arguments of
+ * _fwd_dct_nb / _inv_dct_nb, then use_mfma (1: the MFMA version, WRENC_GPU_EINVAL where the group does not meet the
+ * preconditions above; 0: the v_dot2 templates), reps >= 1 (the transform of the same group repeated in place of
+ * itself; the last repetition's result comes back) and kernel_ms (may be null: HIP-event duration of the kernel). */
+int wrenc_gpu_test_fwd_dct_mfma(wrenc_gpu_ctx* ctx, const int16_t* res, int log2n, int nb, int o1, int count, int16_t* coef,
+                                int use_mfma, int reps, float* kernel_ms);
+int wrenc_gpu_test_inv_dct_mfma(wrenc_gpu_ctx* ctx, const int16_t* deq, int log2n, int nb, int o1, int count, int16_t* res,
+                                int use_mfma, int reps, float* kernel_ms);
 /* The register transforms of the search's 4x4 passes (wrenc_amd/csrc/dev_transform.h fwd_dct4_reg / inv_dct4_reg): `count`
  * 4x4 blocks, row-major int16, four per wavefront with one sample per lane, a last wavefront of fewer included.
  * fwd: residuals -> coefficients (transformer.rs:2040).  inv: LEVELS -> residuals, dequantised in the lane at the

@@ -1,6 +1,7 @@
-"""Micro-benchmark of north_star's MFMA question: kernel time of the 32x32 forward and inverse DCT-2 for N blocks x
-REPS repetitions, v_dot2 / v_mad_i24 code (what the search kernel ran) against the i8-MFMA versions it runs now
-(wrenc_amd/csrc/dev_transform.h: fwd_dct32_mfma, inv_dct32_mfma).  One wave per block, both bit-exact against each other.
+"""Micro-benchmark of north_star's MFMA question: kernel time of the forward and inverse DCT-2 for N groups x REPS
+repetitions, v_dot2 / v_mad_i24 code (what the search kernel ran) against the i8-MFMA versions it runs now
+(wrenc_amd/csrc/dev_transform.h: fwd_dct32_mfma, inv_dct32_mfma at 32x32; fwd_dct_mfma, inv_dct_mfma at 8x8 and 16x16,
+groups of 1, 2, 3 and 4 blocks as the leaf packs hand them over).  One wave per group, both bit-exact against each other.
     python tools/dct_bench.py [N=16384] [REPS=64]"""
 import json
 import os
@@ -27,5 +28,18 @@ for direction, fn, data in (("forward", enc.fwd_dct32, blocks),
         res[name] = {"kernel_ms": best, "ns_per_transform": best * 1e6 / (n * reps), "out": out}
     same = bool(np.array_equal(res["vdot2"].pop("out"), res["mfma_i8"].pop("out")))
     doc[direction] = {"outputs_equal": same, **res, "speedup_mfma": res["vdot2"]["kernel_ms"] / res["mfma_i8"]["kernel_ms"]}
+for lg in (3, 4):
+    side = 1 << lg
+    for nb in (1, 2, 3, 4):
+        for direction, fn, lim in (("forward", enc.fwd_dct_groups_arm, 255), ("inverse", enc.inv_dct_groups_arm, 4000)):
+            data = rng.integers(-lim, lim + 1, (n, nb, side, side)).astype(np.int16)
+            res = {}
+            for name, flag in (("vdot2", 0), ("mfma_i8", 1)):
+                out, _ = fn(data, flag, 0, 1)
+                best = min(fn(data, flag, 0, reps)[1] for _ in range(3))
+                res[name] = {"kernel_ms": best, "ns_per_group": best * 1e6 / (n * reps), "out": out}
+            same = bool(np.array_equal(res["vdot2"].pop("out"), res["mfma_i8"].pop("out")))
+            doc["%s_%dx%d_nb%d" % (direction, side, side, nb)] = {
+                "outputs_equal": same, **res, "speedup_mfma": res["vdot2"]["kernel_ms"] / res["mfma_i8"]["kernel_ms"]}
 print(json.dumps(doc))
 enc.close()

@@ -43,6 +43,26 @@ struct DevConst {
     int8_t idct32_p[32][2][16];
     int32_t idct32_k1[32];
     int32_t idct32_k2[2][16];
+    // The 8x8 and 16x16 transforms as i8 MFMAs (dev_transform.h, fwd_dct_mfma / inv_dct_mfma), T = T_N, N = 8 << idx;
+    // [n][h][j]: byte j of the operand of lane n + 32 h; column n = (block n / N, index n % N); yk(j, h) = 8 (j / 4) + 4 h
+    // + j % 4 is the accumulator row of register j in lane half h.
+    //   fdct_b[idx]: block-diagonal T[u][x] (N = 16: block h, x = j; N = 8: block 2 h + j / 8, x = j % 8), else 0
+    //   fdct16_p:    rows m < 16: T[m][yk(j, h)], rows 16..31: 0 (three chained digit products)
+    //   fdct8_p:     rows m = 8 a + v, a < 3: T[v][4 h + j % 4] where j / 4 == a, else 0 (digit a of slot group j / 4)
+    //   idct_b[idx]: block-diagonal T[i][y], as fdct_b with (u, x) -> (y, i)
+    //   idct16_p:    rows m = 16 b + x: T[yk(j % 8, h)][x] where j / 8 == b, else 0
+    //   idct8_p:     rows m = 16 b + x, x < 8: T[4 h + j % 4][x] where j / 4 == b, else 0
+    //   idct_k1[idx][n] = 128 S[n % N] + 64, idct16_k2[h][w] = 128 S[yk(w, h)] + 2048, idct8_k2[h][w] = 128 S[4 h + w] + 2048,
+    //   S[n] = sum_i T[i][n]
+    alignas(16) int8_t fdct_b[2][32][2][16];
+    alignas(16) int8_t fdct16_p[32][2][8];
+    alignas(16) int8_t fdct8_p[32][2][16];
+    alignas(16) int8_t idct_b[2][32][2][16];
+    alignas(16) int8_t idct16_p[32][2][16];
+    alignas(16) int8_t idct8_p[32][2][8];
+    alignas(16) int32_t idct_k1[2][32];
+    alignas(16) int32_t idct16_k2[2][8];
+    alignas(16) int32_t idct8_k2[2][4];
     // The head proof's per-coefficient conditions (dev_quant.h, head_alpha) as range tests, per block size lg - 2: a coefficient tc
     // (a) does not end the region  <=>  (unsigned)(tc + r[0]) < (unsigned)r[1];  (b) the same at the DC position with r[2], r[3];
     // (c) has a quotient below 2  <=>  (unsigned)(tc + r[4]) < (unsigned)r[5].  Filled by the host from the same formulas
@@ -327,7 +347,8 @@ typedef uint8_t ref_t; // a reference sample (reconstructed or [1 2 1]-filtered:
 struct __attribute__((aligned(16))) Lds {
     // Transform working set, time-multiplexed through a full evaluation (dev_search.h):
     //   r1: residual -> coefficients -> Viterbi chunk costs / levels -> inverse-transform intermediate -> residual
-    //   r2: stage-1 DCT output (i32, blocks up to 16x16; the 32x32 transform keeps it in MFMA accumulators) ->
+    //   r2: stage-1 DCT output of the v_dot2 templates (i32: 8x8 blocks, 288 B each, and 4x4 blocks outside the packed
+    //       passes, which keep theirs in registers through DPP; 16x16 and 32x32 blocks keep it in MFMA accumulators) ->
     //       scan-order coefficients -> dequantised^T
     // Bytes [kOrgLeaf, 2048) of r2 hold the originals of a block of at most 16x16 for its whole leaf search
     // (dev_predict.h); no stage of a block that small reaches them.

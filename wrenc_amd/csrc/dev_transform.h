@@ -255,6 +255,194 @@ __device__ __forceinline__ void inv_dct32_mfma(Ctx c, int o1) {
 }
 
 // ---------------------------------------------------------------------------
+// 8x8 and 16x16 blocks the same way (the transforms of the leaf packs): 32 / N blocks share every MFMA, the basis
+// operand of a first stage is block-diagonal over them, and the digits (forward) or bytes (inverse) of the data operand
+// sit in the M dimension at rows m and m + 16, which are accumulators w and w + 8 of ONE lane, so they recombine without
+// any lane exchange.  Lane (n = LANE & 31, h = LANE >> 5) of an accumulator holds column n, rows 8 (w / 4) + 4 h + w % 4;
+// column n is (block n / N, index n % N).  What a first stage leaves in a lane is exactly that lane's share of the
+// second stage's data operand, so nothing goes through LDS in between (r2 is not touched by the forward transforms).
+// Cross products of different blocks meet zeros of the block-diagonal operand; rows that no block owns (N = 8: rows
+// 8..15 and 24..31 of a first stage) repeat rows 0..7 and are not stored.  Blocks past nb carry zeros (a zero byte
+// selector) and read a live block's address.  All 64 lanes run the operand gathers and the MFMAs under wave-uniform
+// control; only the final stores sit under a lane predicate (the block of the lane's column exists).
+//
+// Bounds, S = max_u sum_x |T_N[u][x]| = 64 N (row 0), N <= 16 (tests/test_dct_mfma_model.py asserts them on the model):
+//   forward, |r| <= 255: digits d0 in [-128, 127], d1 in [-1, 1]; per-digit sums <= 128 S = 131,072;
+//     H = (sum + d) >> (LG - 1): |H| <= 255 * 64 N / (N / 2) = 32,640 (three digits: d0, d1 in [-128, 127], |d2| <= 1);
+//     stage 2 per-digit sums <= 131,072; the recombined sum, and the chained accumulator before its last digit's product
+//     (the sum less that product), <= 32,640 * 1024 + 131,072 + 2^10 < 2^25.1
+//   inverse, any i16: bytes in [-128, 127]; per-byte sums <= 131,072; recombined (hi << 8) + lo + k <= 32,768 * 1024
+//     + 128 * 1024 + 2048 < 2^25.1 in either stage; the clamp to i16 after stage 1 is the reference's
+// ---------------------------------------------------------------------------
+typedef int v2i_t __attribute__((ext_vector_type(2)));
+constexpr uint32_t kSelLo = 0x06040200u, kSelHi = 0x07050301u, kSelZero = 0x0C0C0C0Cu; // v_perm: bytes 0 / 1 of four i16, zeros
+static_assert(255 * 64 * 16 / 8 <= 32640 && 32640 + 128 + 32768 < (1 << 23), "H takes three balanced digits, the top one in [-1, 1]");
+static_assert(32640ll * 1024 + (1 << 10) < (1ll << 31) && 32768ll * 1024 + 128 * 1024 + 2048 < (1ll << 31), "recombined sums stay in i32");
+
+__device__ __forceinline__ uint32_t pk_add16(uint32_t p, uint32_t q) { // per i16 half, wrapping
+    s2_t a, b;
+    a.x = (short)(p & 0xFFFF);
+    a.y = (short)(p >> 16);
+    b.x = (short)(q & 0xFFFF);
+    b.y = (short)(q >> 16);
+    a = a + b;
+    return (uint32_t)(unsigned short)a.x | ((uint32_t)(unsigned short)a.y << 16);
+}
+__device__ __forceinline__ long pack_i64(uint32_t lo, uint32_t hi) { return (long)(((unsigned long)hi << 32) | lo); }
+
+// The data operand of a first stage: the lane's row (n % N) of the 32 / N blocks of its half, 16 samples of 16 bits, as
+// the 16 bytes `sel` picks (kSelLo / kSelHi; a block past nb: zeros).  N = 16: block b0 + h; N = 8: blocks b0 + 2 h, + 1.
+// src: [blk][row][col] i16.  add: added to each i16 before the pick (the forward transform's second digit), xm: xor'ed
+// to the picked bytes of a live block (the inverse's "low byte minus 128").
+template <int LG>
+__device__ __forceinline__ v4i_t mfma_rows(const int16_t* src, int b0, int nb, int n, int h, uint32_t sel, uint32_t add,
+                                           uint32_t xm) {
+    constexpr int N = 1 << LG, NN = N * N;
+    const int row = n & (N - 1), last = nb - 1;
+    const int ba = b0 + (LG == 4 ? h : 2 * h), bb = LG == 4 ? ba : ba + 1;
+    const uint4 q0 = *(const uint4*)&src[min(ba, last) * NN + row * N];
+    const uint4 q1 = *(const uint4*)&src[min(bb, last) * NN + row * N + (LG == 4 ? 8 : 0)];
+    const uint32_t sa = ba <= last ? sel : kSelZero, sb = bb <= last ? sel : kSelZero;
+    const uint32_t xa = ba <= last ? xm : 0u, xb = bb <= last ? xm : 0u;
+    v4i_t a;
+    a[0] = (int)(__builtin_amdgcn_perm(pk_add16(q0.y, add), pk_add16(q0.x, add), sa) ^ xa);
+    a[1] = (int)(__builtin_amdgcn_perm(pk_add16(q0.w, add), pk_add16(q0.z, add), sa) ^ xa);
+    a[2] = (int)(__builtin_amdgcn_perm(pk_add16(q1.y, add), pk_add16(q1.x, add), sb) ^ xb);
+    a[3] = (int)(__builtin_amdgcn_perm(pk_add16(q1.w, add), pk_add16(q1.z, add), sb) ^ xb);
+    return a;
+}
+
+// forward (transformer.rs:2040-2378), LG = 3, 4: nb residual blocks in r1[o1 ..] ([blk][y][x] i16, |r| <= 255) ->
+// coefficients in place ([blk][v][u]: the layout fwd_dct leaves).
+//   stage 1: Ht[(d, y)][(blk, u)] = sum_x digit_d(R_blk[y][x]) T[u][x]     A = digits of R, rows 16 d + y; B = diag(T)
+//   stage 2: C[v][(blk, u)] = sum_y T[v][y] H_blk[y][u]                    A = T in accumulator k order, B = digits of H
+//     N = 16: three v_mfma_i32_32x32x16_i8 (k = the lane's 8 values of y), digit after digit from the top as at 32x32
+//     N = 8: one v_mfma_i32_32x32x32_i8, k = (digit a, the lane's 4 values of y), rows 8 a + v: the three digit
+//            products land in accumulators w, w + 4, w + 8
+template <int LG>
+__device__ __forceinline__ void fwd_dct_mfma(Ctx c, int nb, int o1) {
+    static_assert(LG == 3 || LG == 4, "the 8x8 and 16x16 transforms");
+    constexpr int N = 1 << LG, NN = N * N, PER = 32 / N, NH = N / 2;
+    const int lane = LANE;
+    const int n = lane & 31, h = lane >> 5;
+    const v4i_t tB = *(const CONST_AS v4i_t*)&c.k->fdct_b[LG - 3][n][h][0];
+    const int d = n >> 4;
+    const v16i_t z = {};
+#pragma unroll 1
+    for (int b0 = 0; b0 < nb; b0 += PER) {
+        // ---- stage 1: d0 = byte 0 of r (signed), d1 = byte 1 of r + 128 ----
+        const v4i_t a = mfma_rows<LG>(&SH.r1[o1], b0, nb, n, h, d ? kSelHi : kSelLo, d ? 0x00800080u : 0u, 0u);
+        v16i_t acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, tB, z, 0, 0, 0);
+        uint32_t H[NH]; // Ht_blk[y(w, h)][u], y(w, h) = 8 (w / 4) + 4 h + w % 4
+#pragma unroll
+        for (int w = 0; w < NH; ++w) H[w] = (uint32_t)(((acc[w + 8] << 8) + acc[w] + (1 << (LG - 2))) >> (LG - 1)); // (:2201-2209)
+        // ---- stage 2: digits of H straight from the registers ----
+        if constexpr (LG == 4) {
+            const long tP = *(const CONST_AS long*)&c.k->fdct16_p[n][h][0];
+            const long d0 = pack_i64(gather_byte(H[0], H[1], H[2], H[3], 0), gather_byte(H[4], H[5], H[6], H[7], 0));
+            const long d1 = pack_i64(gather_byte(H[0] + 128u, H[1] + 128u, H[2] + 128u, H[3] + 128u, 1),
+                                     gather_byte(H[4] + 128u, H[5] + 128u, H[6] + 128u, H[7] + 128u, 1));
+            const long d2 = pack_i64(gather_byte(H[0] + 32896u, H[1] + 32896u, H[2] + 32896u, H[3] + 32896u, 2),
+                                     gather_byte(H[4] + 32896u, H[5] + 32896u, H[6] + 32896u, H[7] + 32896u, 2));
+            acc = __builtin_amdgcn_mfma_i32_32x32x16_i8(tP, d2, z, 0, 0, 0); // (rows 16..31 of tP are zero: acc[8..15] stay 0)
+#pragma unroll
+            for (int w = 0; w < NH; ++w) acc[w] <<= 8;
+            acc = __builtin_amdgcn_mfma_i32_32x32x16_i8(tP, d1, acc, 0, 0, 0);
+#pragma unroll
+            for (int w = 0; w < NH; ++w) acc[w] = (acc[w] << 8) + (1 << (LG + 5)); // (+ (1 << (LG + 5))) >> (LG + 6) (:2309-2316)
+            acc = __builtin_amdgcn_mfma_i32_32x32x16_i8(tP, d0, acc, 0, 0, 0);
+        } else {
+            const v4i_t tP = *(const CONST_AS v4i_t*)&c.k->fdct8_p[n][h][0];
+            v4i_t b;
+            b[0] = (int)gather_byte(H[0], H[1], H[2], H[3], 0);
+            b[1] = (int)gather_byte(H[0] + 128u, H[1] + 128u, H[2] + 128u, H[3] + 128u, 1);
+            b[2] = (int)gather_byte(H[0] + 32896u, H[1] + 32896u, H[2] + 32896u, H[3] + 32896u, 2);
+            b[3] = 0;
+            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(tP, b, z, 0, 0, 0);
+#pragma unroll
+            for (int w = 0; w < NH; ++w) acc[w] = (((acc[w + 8] << 8) + acc[w + 4]) << 8) + acc[w] + (1 << (LG + 5));
+        }
+        WSYNC(); // every lane has read its residuals before the coefficients overwrite them
+        if (b0 + (n >> LG) < nb) {
+            int16_t* out = &SH.r1[o1 + (b0 + (n >> LG)) * NN + (n & (N - 1))];
+#pragma unroll
+            for (int w = 0; w < NH; ++w) out[(8 * (w >> 2) + 4 * h + (w & 3)) * N] = (int16_t)(acc[w] >> (LG + 6));
+        }
+        WSYNC();
+    }
+}
+
+// inverse (transformer.rs:2380-2737), LG = 3, 4: nb transposed dequantised blocks in r2 ([blk][x][i], any i16) ->
+// residuals r1[o1 ..] ([blk][y][x]).  Bytes as in inv_dct32_mfma: v = 256 hi + (lo - 128) + 128.
+//   stage 1: Vt[(b, x)][(blk, y)] = sum_i byte_b(dT_blk[x][i]) T[i][y]     A = bytes of dT, rows 16 b + x; B = diag(T)
+//            V = clamp16(((hi << 8) + lo + 128 S[y] + 64) >> 7)            (idct_k1, S[y] = sum_i T[i][y])
+//   stage 2: Rt[(b, x)][(blk, y)] = sum_i T[i][x] byte_b(V_blk[y][i])      A = T, k = (byte b, the lane's values of i),
+//            rows 16 b + x; B = the lane's bytes of V; C = 128 S[x] + 2048 in rows b = 0 (idct16_k2 / idct8_k2)
+//            N = 16: v_mfma_i32_32x32x32_i8 (8 values, 16 bytes); N = 8: v_mfma_i32_32x32x16_i8 (4 values, 8 bytes)
+template <int LG>
+__device__ __forceinline__ void inv_dct_mfma(Ctx c, int nb, int o1) {
+    static_assert(LG == 3 || LG == 4, "the 8x8 and 16x16 transforms");
+    constexpr int N = 1 << LG, NN = N * N, PER = 32 / N, NH = N / 2;
+    const int lane = LANE;
+    const int n = lane & 31, h = lane >> 5;
+    const v4i_t tB = *(const CONST_AS v4i_t*)&c.k->idct_b[LG - 3][n][h][0];
+    const int k1 = c.k->idct_k1[LG - 3][n];
+    const int b = n >> 4;
+    const v16i_t z = {};
+    v16i_t k2 = {};
+    if constexpr (LG == 4) {
+        const v4i_t ka = *(const CONST_AS v4i_t*)&c.k->idct16_k2[h][0], kb = *(const CONST_AS v4i_t*)&c.k->idct16_k2[h][4];
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            k2[w] = ka[w];
+            k2[4 + w] = kb[w];
+        }
+    } else {
+        const v4i_t ka = *(const CONST_AS v4i_t*)&c.k->idct8_k2[h][0];
+#pragma unroll
+        for (int w = 0; w < 4; ++w) k2[w] = ka[w];
+    }
+#pragma unroll 1
+    for (int b0 = 0; b0 < nb; b0 += PER) {
+        // ---- stage 1 ----
+        const v4i_t a = mfma_rows<LG>((const int16_t*)SH.r2, b0, nb, n, h, b ? kSelHi : kSelLo, 0u, b ? 0u : 0x80808080u);
+        v16i_t acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, tB, z, 0, 0, 0);
+        uint32_t V[NH]; // V_blk[y][x(w, h)], x(w, h) = 8 (w / 4) + 4 h + w % 4
+#pragma unroll
+        for (int w = 0; w < NH; ++w) V[w] = (uint32_t)min(max(((acc[w + 8] << 8) + acc[w] + k1) >> 7, -32768), 32767); // (:2499-2543)
+        // ---- stage 2: bytes of V straight from the registers ----
+        if constexpr (LG == 4) {
+            const v4i_t tP = *(const CONST_AS v4i_t*)&c.k->idct16_p[n][h][0];
+            v4i_t bv;
+            bv[0] = (int)(gather_byte(V[0], V[1], V[2], V[3], 0) ^ 0x80808080u);
+            bv[1] = (int)(gather_byte(V[4], V[5], V[6], V[7], 0) ^ 0x80808080u);
+            bv[2] = (int)gather_byte(V[0], V[1], V[2], V[3], 1);
+            bv[3] = (int)gather_byte(V[4], V[5], V[6], V[7], 1);
+            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(tP, bv, k2, 0, 0, 0);
+        } else {
+            const long tP = *(const CONST_AS long*)&c.k->idct8_p[n][h][0];
+            const long bv = pack_i64(gather_byte(V[0], V[1], V[2], V[3], 0) ^ 0x80808080u, gather_byte(V[0], V[1], V[2], V[3], 1));
+            acc = __builtin_amdgcn_mfma_i32_32x32x16_i8(tP, bv, k2, 0, 0, 0);
+        }
+        // lane ((blk, y), h): residuals at x = 8 q + 4 h + 0..3 (:2680-2737)
+        if (b0 + (n >> LG) < nb) {
+            int16_t* out = &SH.r1[o1 + (b0 + (n >> LG)) * NN + (n & (N - 1)) * N + 4 * h];
+#pragma unroll
+            for (int q = 0; q < NH / 4; ++q) {
+                int r[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) r[j] = ((acc[4 * q + j + 8] << 8) + acc[4 * q + j]) >> 12;
+                uint2 v;
+                v.x = ((uint32_t)r[0] & 0xFFFFu) | ((uint32_t)r[1] << 16);
+                v.y = ((uint32_t)r[2] & 0xFFFFu) | ((uint32_t)r[3] << 16);
+                *(uint2*)&out[8 * q] = v;
+            }
+        }
+        WSYNC();
+    }
+}
+
+// ---------------------------------------------------------------------------
 // 4x4 blocks in registers (the packed 4x4 passes of the leaf searches, dev_search.h): four blocks per wave,
 // lane = (block LANE >> 4, sample LANE & 15, row-major), one value per lane in and out.  A 4x4 block lies inside one
 // 16-lane DPP row, so the two stages of a transform exchange their operands between lanes and nothing goes through LDS:
@@ -329,7 +517,17 @@ __device__ __forceinline__ int inv_dct4_reg(int deq) {
     return (int16_t)((t4_stage<T4_INV2, true>(v, sx) + 2048) >> 12);
 }
 
-// o1: where the blocks start in r1 (i16 units, a multiple of 2)
+// o1: where the blocks start in r1 (i16 units, a multiple of 2; of 8 for the MFMA versions' 16-byte row reads, which is
+// what the search has: blocks start at multiples of 64).
+// Which code runs at 8x8 and 16x16 (ARM, a literal: the branches fold away).  DCT_SEARCH, what every caller in the search
+// passes: 16x16 as i8 MFMAs (fwd_dct_mfma / inv_dct_mfma, +3.0 % frames/s on the headline workload), 8x8 through the v_dot2
+// templates -- the MFMA version of that size is exact, but faster in the micro-benchmark only from three blocks per
+// group up, and its gain in the search (+0.2 %) did not clear the project's margin.  DCT_VDOT2 / DCT_MFMA: the building-block kernels (wrenc_gpu.hip)
+// name the arm, for groups the digit scheme does not take (a residual outside +-255, an o1 that is no multiple of 8),
+// for the parity tests of both versions at both sizes and for the micro-benchmark (tools/dct_bench.py).
+enum { DCT_SEARCH, DCT_VDOT2, DCT_MFMA };
+constexpr bool dct_runs_mfma(int arm, int lg) { return arm == DCT_MFMA || (arm == DCT_SEARCH && lg == 4); }
+template <int ARM = DCT_SEARCH>
 __device__ __forceinline__ void fwd_dct_lg(Ctx c, int lg, int nb, int o1 = 0) {
 #ifdef WRENC_EXP_SKIP_DCT // instruction-count experiment only: the residual stays where the coefficients should be
     return;
@@ -342,8 +540,18 @@ __device__ __forceinline__ void fwd_dct_lg(Ctx c, int lg, int nb, int o1 = 0) {
     constexpr int HB = (int)sizeof(SH.r2);
     switch (lg) {
     case 2: fwd_dct<2, HB>(c, nb, o1, h); break;
-    case 3: fwd_dct<3, HB>(c, nb, o1, h); break;
-    case 4: fwd_dct<4, HB>(c, nb, o1, h); break;
+    case 3:
+        if (!dct_runs_mfma(ARM, 3))
+            fwd_dct<3, HB>(c, nb, o1, h);
+        else
+            fwd_dct_mfma<3>(c, nb, o1);
+        break;
+    case 4:
+        if (!dct_runs_mfma(ARM, 4))
+            fwd_dct<4, HB>(c, nb, o1, h);
+        else
+            fwd_dct_mfma<4>(c, nb, o1);
+        break;
     default:
         // 32x32 (always a single luma block): the i8-MFMA version, kept on measurement (3.6x in the
         // micro-benchmark, +5.6 % frames/s at max-split-depth 0, +0.9 % at depth 2); its intermediate stays in the
@@ -352,6 +560,7 @@ __device__ __forceinline__ void fwd_dct_lg(Ctx c, int lg, int nb, int o1 = 0) {
         break;
     }
 }
+template <int ARM = DCT_SEARCH>
 __device__ __forceinline__ void inv_dct_lg(Ctx c, int lg, int nb, int o1 = 0) {
 #ifdef WRENC_EXP_SKIP_DCT
     return;
@@ -362,8 +571,18 @@ __device__ __forceinline__ void inv_dct_lg(Ctx c, int lg, int nb, int o1 = 0) {
     o1 = uni(o1);
     switch (lg) {
     case 2: inv_dct<2>(c, nb, o1); break;
-    case 3: inv_dct<3>(c, nb, o1); break;
-    case 4: inv_dct<4>(c, nb, o1); break;
+    case 3:
+        if (!dct_runs_mfma(ARM, 3))
+            inv_dct<3>(c, nb, o1);
+        else
+            inv_dct_mfma<3>(c, nb, o1);
+        break;
+    case 4:
+        if (!dct_runs_mfma(ARM, 4))
+            inv_dct<4>(c, nb, o1);
+        else
+            inv_dct_mfma<4>(c, nb, o1);
+        break;
     default:
 #ifdef WRENC_IDCT32_VDOT2
         inv_dct<5>(c, nb, o1); // the comparison arm of the micro-benchmark (tools/dct_bench.py)

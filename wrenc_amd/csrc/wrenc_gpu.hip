@@ -276,13 +276,23 @@ __global__ __launch_bounds__(64 * WPB, 5) void ctu_search_team_kernel(const DevC
 // dequantiser work on r1[o1 ..], where the search puts a pack's chroma behind its luma (the host entries check that the
 // group fits r1 and r2)
 __global__ __launch_bounds__(64) void test_fwd_dct_kernel(const DevConst* __restrict__ k,
-                                                          const int16_t* in, int lg, int nb, int o1, int16_t* out) {
+                                                          const int16_t* in, int lg, int nb, int o1, int16_t* out,
+                                                          int arm, int reps) {
     Ctx c = {};
     c.k = (const CONST_AS DevConst*)k;
     const int total = nb << (2 * lg);
-    for (int i = threadIdx.x; i < total; i += 64) SH.r1[o1 + i] = in[(size_t)blockIdx.x * total + i];
-    WSYNC();
-    fwd_dct_lg(c, lg, nb, o1);
+    // arm: DCT_SEARCH, or the version of the 8x8 / 16x16 transforms the host names (dev_transform.h); reps repeats the
+    // transform of the same group for the micro-benchmark
+    for (int rep = 0; rep < reps; ++rep) {
+        for (int i = threadIdx.x; i < total; i += 64) SH.r1[o1 + i] = in[(size_t)blockIdx.x * total + i];
+        WSYNC();
+        if (arm == DCT_VDOT2)
+            fwd_dct_lg<DCT_VDOT2>(c, lg, nb, o1);
+        else if (arm == DCT_MFMA)
+            fwd_dct_lg<DCT_MFMA>(c, lg, nb, o1);
+        else
+            fwd_dct_lg(c, lg, nb, o1);
+    }
     for (int i = threadIdx.x; i < total; i += 64) out[(size_t)blockIdx.x * total + i] = SH.r1[o1 + i];
 }
 
@@ -322,16 +332,24 @@ __global__ __launch_bounds__(64) void test_inv_dct32_kernel(const DevConst* __re
 }
 
 __global__ __launch_bounds__(64) void test_inv_dct_kernel(const DevConst* __restrict__ k,
-                                                          const int16_t* in, int lg, int nb, int o1, int16_t* out) {
+                                                          const int16_t* in, int lg, int nb, int o1, int16_t* out,
+                                                          int arm, int reps) {
     Ctx c = {};
     c.k = (const CONST_AS DevConst*)k;
     const int n = 1 << lg, nn = n * n, total = nb * nn;
-    for (int i = threadIdx.x; i < total; i += 64) { // transposed load, block by block: dT[blk][x][i] = d[blk][i][x]
-        const int ii = i & (nn - 1);
-        ((int16_t*)SH.r2)[(i - ii) + (ii & (n - 1)) * n + (ii >> lg)] = in[(size_t)blockIdx.x * total + i];
+    for (int rep = 0; rep < reps; ++rep) {
+        for (int i = threadIdx.x; i < total; i += 64) { // transposed load, block by block: dT[blk][x][i] = d[blk][i][x]
+            const int ii = i & (nn - 1);
+            ((int16_t*)SH.r2)[(i - ii) + (ii & (n - 1)) * n + (ii >> lg)] = in[(size_t)blockIdx.x * total + i];
+        }
+        WSYNC();
+        if (arm == DCT_VDOT2)
+            inv_dct_lg<DCT_VDOT2>(c, lg, nb, o1);
+        else if (arm == DCT_MFMA)
+            inv_dct_lg<DCT_MFMA>(c, lg, nb, o1);
+        else
+            inv_dct_lg(c, lg, nb, o1);
     }
-    WSYNC();
-    inv_dct_lg(c, lg, nb, o1);
     for (int i = threadIdx.x; i < total; i += 64) out[(size_t)blockIdx.x * total + i] = SH.r1[o1 + i];
 }
 
@@ -1153,6 +1171,43 @@ void fill_dev_const(const wrenc_gpu_config& cfg, DevConst& k) {
             for (int j = 0; j < 16; ++j) k.idct32_p[x][h][j] = (int8_t)dct64((8 * (j / 4) + 4 * h + j % 4) * 2, x);
     for (int h = 0; h < 2; ++h)
         for (int w = 0; w < 16; ++w) k.idct32_k2[h][w] = 128 * colsum[8 * (w / 4) + 4 * h + w % 4] + 2048;
+    // the 8x8 and 16x16 transforms as i8 MFMAs (DevConst::fdct_b ...)
+    memset(k.fdct_b, 0, sizeof(k.fdct_b));
+    memset(k.fdct16_p, 0, sizeof(k.fdct16_p));
+    memset(k.fdct8_p, 0, sizeof(k.fdct8_p));
+    memset(k.idct_b, 0, sizeof(k.idct_b));
+    memset(k.idct16_p, 0, sizeof(k.idct16_p));
+    memset(k.idct8_p, 0, sizeof(k.idct8_p));
+    for (int idx = 0; idx < 2; ++idx) {
+        const int n = 8 << idx, step = 64 / n;
+        auto T = [&](int u, int x) { return dct64(u * step, x); };
+        auto yk = [](int j, int h) { return 8 * (j / 4) + 4 * h + j % 4; };
+        int s[16];
+        for (int y = 0; y < n; ++y) {
+            s[y] = 0;
+            for (int i = 0; i < n; ++i) s[y] += T(i, y);
+        }
+        for (int m = 0; m < 32; ++m)
+            for (int h = 0; h < 2; ++h) {
+                for (int j = 0; j < 16; ++j) {
+                    const int blk = n == 16 ? h : 2 * h + j / 8, x = j % n;
+                    if (m / n == blk) {
+                        k.fdct_b[idx][m][h][j] = (int8_t)T(m % n, x);
+                        k.idct_b[idx][m][h][j] = (int8_t)T(x, m % n);
+                    }
+                    if (n == 16) {
+                        if (j < 8 && m < 16) k.fdct16_p[m][h][j] = (int8_t)T(m, yk(j, h));
+                        if (j / 8 == m / 16) k.idct16_p[m][h][j] = (int8_t)T(yk(j % 8, h), m % 16);
+                    } else {
+                        if (j / 4 == m / 8 && m / 8 < 3) k.fdct8_p[m][h][j] = (int8_t)T(m % 8, 4 * h + j % 4);
+                        if (j < 8 && j / 4 == m / 16 && m % 16 < 8) k.idct8_p[m][h][j] = (int8_t)T(4 * h + j % 4, m % 16);
+                    }
+                }
+                for (int w = 0; w < n / 2; ++w)
+                    (n == 16 ? k.idct16_k2[h][w] : k.idct8_k2[h][w]) = 128 * s[yk(w, h)] + 2048;
+            }
+        for (int m = 0; m < 32; ++m) k.idct_k1[idx][m] = 128 * s[m % n] + 64;
+    }
     fill_head_ranges(k);
     fill_avail_tab(k);
 }
@@ -2760,14 +2815,53 @@ static const char* group_shape_error(int log2n, int nb, int o1, int nb_max) {
 }
 constexpr int kGroupMaxBlocks = 64; // (1024 / 16: group_shape_error's size rules are what bounds a transform group)
 
-int wrenc_gpu_test_fwd_dct_nb(wrenc_gpu_ctx* ctx, const int16_t* res, int log2n, int nb, int o1, int count, int16_t* coef) {
-    if (!ctx || !res || !coef) return WRENC_GPU_EINVAL;
+// The 8x8 and 16x16 transforms exist as i8 MFMAs too (fwd_dct_mfma / inv_dct_mfma; the search runs them at 16x16):
+// 16-byte row reads, so o1 a multiple of 8, and for the forward transform |residual| <= 255.  The search has both by
+// construction; a test group that has not runs the retained v_dot2 templates (the host decides before the launch: no
+// data-dependent branch on the device).
+static bool group_takes_mfma(const int16_t* res, int log2n, int nb, int o1, int count, bool inverse) {
+    if (o1 & 7) return false;
+    return inverse || count < 1 || residuals_fit_9_bits(res, (size_t)count * ((size_t)nb << (2 * log2n)));
+}
+// use_mfma: -1 = the plain entries: what the search runs at this size where the group meets its preconditions, else the
+// v_dot2 templates; 0 = the v_dot2 templates; 1 = the MFMA versions, or EINVAL
+static int run_dct_group(wrenc_gpu_ctx* ctx, const int16_t* in, int log2n, int nb, int o1, int count, int16_t* out,
+                         int use_mfma, int reps, float* kernel_ms, bool inverse) {
+    if (!ctx || !in || !out || reps < 1) return WRENC_GPU_EINVAL;
     if (const char* why = group_shape_error(log2n, nb, o1, kGroupMaxBlocks)) return fail(ctx, WRENC_GPU_EINVAL, why);
-    if (log2n == 5 && count >= 1 && !residuals_fit_9_bits(res, (size_t)count * 1024))
+    if (!inverse && log2n == 5 && count >= 1 && !residuals_fit_9_bits(in, (size_t)count * 1024))
         return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_test_fwd_dct: a 32x32 residual lies outside +-255");
-    return run_block_test(ctx, res, log2n, count, coef, [&](int16_t* i, int16_t* o) {
-        hipLaunchKernelGGL(test_fwd_dct_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const.get(), i, log2n, nb, o1, o);
-    }, nb);
+    int arm = DCT_SEARCH; // (4x4 and 32x32: nothing to choose)
+    if (log2n == 3 || log2n == 4) {
+        const bool takes = group_takes_mfma(in, log2n, nb, o1, count, inverse);
+        if (use_mfma == 1 && !takes)
+            return fail(ctx, WRENC_GPU_EINVAL, "the MFMA transforms take residuals within +-255 and an o1 that is a multiple of 8");
+        arm = use_mfma == 1 ? DCT_MFMA : (use_mfma == 0 || !takes ? DCT_VDOT2 : DCT_SEARCH);
+    }
+    float ms = 0.f;
+    const int rc = run_block_test(ctx, in, log2n, count, out, [&](int16_t* i, int16_t* o) {
+        if (inverse)
+            hipLaunchKernelGGL(test_inv_dct_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const.get(), i, log2n, nb, o1, o, arm, reps);
+        else
+            hipLaunchKernelGGL(test_fwd_dct_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const.get(), i, log2n, nb, o1, o, arm, reps);
+    }, nb, kernel_ms ? &ms : nullptr);
+    if (kernel_ms) *kernel_ms = ms;
+    return rc;
+}
+int wrenc_gpu_test_fwd_dct_nb(wrenc_gpu_ctx* ctx, const int16_t* res, int log2n, int nb, int o1, int count, int16_t* coef) {
+    return run_dct_group(ctx, res, log2n, nb, o1, count, coef, -1, 1, nullptr, false);
+}
+int wrenc_gpu_test_fwd_dct_mfma(wrenc_gpu_ctx* ctx, const int16_t* res, int log2n, int nb, int o1, int count, int16_t* coef,
+                                int use_mfma, int reps, float* kernel_ms) {
+    if (!ctx) return WRENC_GPU_EINVAL;
+    if (log2n != 3 && log2n != 4) return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_test_fwd_dct_mfma: log2n must be 3 or 4");
+    return run_dct_group(ctx, res, log2n, nb, o1, count, coef, use_mfma ? 1 : 0, reps, kernel_ms, false);
+}
+int wrenc_gpu_test_inv_dct_mfma(wrenc_gpu_ctx* ctx, const int16_t* deq, int log2n, int nb, int o1, int count, int16_t* res,
+                                int use_mfma, int reps, float* kernel_ms) {
+    if (!ctx) return WRENC_GPU_EINVAL;
+    if (log2n != 3 && log2n != 4) return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_test_inv_dct_mfma: log2n must be 3 or 4");
+    return run_dct_group(ctx, deq, log2n, nb, o1, count, res, use_mfma ? 1 : 0, reps, kernel_ms, true);
 }
 int wrenc_gpu_test_fwd_dct(wrenc_gpu_ctx* ctx, const int16_t* res, int log2n, int count, int16_t* coef) {
     return wrenc_gpu_test_fwd_dct_nb(ctx, res, log2n, 1, 0, count, coef);
@@ -2797,11 +2891,7 @@ int wrenc_gpu_test_inv_dct32(wrenc_gpu_ctx* ctx, const int16_t* deq, int count, 
     return run_dct32_bench(ctx, deq, count, res, use_mfma, reps, kernel_ms, true);
 }
 int wrenc_gpu_test_inv_dct_nb(wrenc_gpu_ctx* ctx, const int16_t* deq, int log2n, int nb, int o1, int count, int16_t* res) {
-    if (!ctx || !deq || !res) return WRENC_GPU_EINVAL;
-    if (const char* why = group_shape_error(log2n, nb, o1, kGroupMaxBlocks)) return fail(ctx, WRENC_GPU_EINVAL, why);
-    return run_block_test(ctx, deq, log2n, count, res, [&](int16_t* i, int16_t* o) {
-        hipLaunchKernelGGL(test_inv_dct_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const.get(), i, log2n, nb, o1, o);
-    }, nb);
+    return run_dct_group(ctx, deq, log2n, nb, o1, count, res, -1, 1, nullptr, true);
 }
 int wrenc_gpu_test_inv_dct(wrenc_gpu_ctx* ctx, const int16_t* deq, int log2n, int count, int16_t* res) {
     return wrenc_gpu_test_inv_dct_nb(ctx, deq, log2n, 1, 0, count, res);

@@ -22,7 +22,7 @@ EXPORTED_SYMBOLS = [
     "wrenc_gpu_upload", "wrenc_gpu_encode", "wrenc_gpu_set_slot_qp", "wrenc_gpu_sync", "wrenc_gpu_download", "wrenc_gpu_download_compact", "wrenc_gpu_compact_mask_words", "wrenc_gpu_expand_levels", "wrenc_gpu_download_tokens", "wrenc_gpu_download_metrics", "wrenc_gpu_download_complexity", "wrenc_gpu_metrics_values", "wrenc_gpu_test_metrics", "wrenc_gpu_test_load_record", "wrenc_gpu_device_info",
     "wrenc_gpu_alloc_host", "wrenc_gpu_free_host", "wrenc_gpu_encode_picture", "wrenc_gpu_set_schedule", "wrenc_gpu_last_schedule", "wrenc_gpu_stats_enable", "wrenc_gpu_last_encode_stats", "wrenc_gpu_last_encode_kernel_stats", "wrenc_gpu_final_pass_mismatches",
     "wrenc_gpu_test_fwd_dct", "wrenc_gpu_test_inv_dct", "wrenc_gpu_test_quantize",
-    "wrenc_gpu_test_fwd_dct_nb", "wrenc_gpu_test_inv_dct_nb", "wrenc_gpu_test_quantize_nb", "wrenc_gpu_test_dequantize_nb",
+    "wrenc_gpu_test_fwd_dct_nb", "wrenc_gpu_test_inv_dct_nb", "wrenc_gpu_test_fwd_dct_mfma", "wrenc_gpu_test_inv_dct_mfma", "wrenc_gpu_test_quantize_nb", "wrenc_gpu_test_dequantize_nb",
     "wrenc_gpu_test_dequantize","wrenc_gpu_test_predict", "wrenc_gpu_test_fwd_dct32", "wrenc_gpu_test_inv_dct32", "wrenc_gpu_test_quantize_p16", "wrenc_gpu_test_quantize_pk", "wrenc_gpu_test_fwd_dct4_reg", "wrenc_gpu_test_inv_dct4_reg", "wrenc_gpu_test_set_wave_slots", "wrenc_gpu_test_scratch_overflows", "wrenc_gpu_test_head_ranges", "wrenc_gpu_test_avail_tab",
     "wrenc_gpu_set_visible_size", "wrenc_gpu_visible_size", "wrenc_gpu_test_download_originals",
     "wrenc_gpu_set_source_size", "wrenc_gpu_source_size", "wrenc_gpu_scale_taps",
@@ -740,6 +740,26 @@ class Encoder:
 
     def inv_dct_groups(self, groups, o1=0):
         return self._groups(self.lib.wrenc_gpu_test_inv_dct_nb, groups, o1)
+
+    def _groups_arm(self, fn, groups, o1, use_mfma, reps):
+        arr = np.ascontiguousarray(groups, np.int16)
+        count, nb, n, _ = arr.shape
+        out = np.zeros_like(arr)
+        ms = C.c_float()
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                       C.POINTER(C.c_float)]
+        self._check(fn(self.ctx, _p(arr), int(n).bit_length() - 1, nb, int(o1), count, _p(out), int(use_mfma), int(reps),
+                       C.byref(ms)))
+        return out, ms.value
+
+    def fwd_dct_groups_arm(self, groups, use_mfma, o1=0, reps=1):
+        """(coefficients, kernel ms) of groups of 8x8 or 16x16 residual blocks (as fwd_dct_groups): the i8-MFMA version
+        the search runs (use_mfma, residuals within +-255) or the v_dot2 templates."""
+        return self._groups_arm(self.lib.wrenc_gpu_test_fwd_dct_mfma, groups, o1, use_mfma, reps)
+
+    def inv_dct_groups_arm(self, groups, use_mfma, o1=0, reps=1):
+        """(residuals, kernel ms) of groups of 8x8 or 16x16 dequantised blocks, the same two arms."""
+        return self._groups_arm(self.lib.wrenc_gpu_test_inv_dct_mfma, groups, o1, use_mfma, reps)
 
     def dequantize_groups(self, groups, o1=0):
         return self._groups(self.lib.wrenc_gpu_test_dequantize_nb, groups, o1)
