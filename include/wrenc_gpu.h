@@ -420,6 +420,28 @@ int wrenc_gpu_device_info(const wrenc_gpu_ctx* ctx, long long* wave_slots, int* 
  * device holds, CUs x waves per CU), so that a SMALL encode call mixes TEAM and WAVE diagonals as a big one does on
  * the real figure (tests/test_gpu_groups.py).  slots <= 0 restores the device's value.  Results do not depend on it. */
 int wrenc_gpu_test_set_wave_slots(wrenc_gpu_ctx* ctx, long long slots);
+/* Test entry, needs no context and no device: the launch plan of an encode call (wrenc_amd/csrc/encode_plan.h) -- what
+ * wrenc_gpu_encode issues for pictures of ctu_cols x ctu_rows CTUs with the QPs qps[0 .. n_pictures - 1] (0..63, in slot
+ * order) under `schedule`, `wave_slots` and the depth (depth3: max_split_depth == 3), with the library's own build constants.
+ * A launch: its stream (lane), the kernel (team: 1, wave: 0), the anti-diagonal with its first CTU row and its number of
+ * CTUs, the kernel's pictures as entries first .. first + n - 1 of the call's list (a call at one QP has no list: of its
+ * slots), the grid, the first group (wave kernel of a mixed call, else -1), the QP whose constant block it takes (-1: the
+ * groups name the blocks), the (diagonal, lane) pair it belongs to -- the unit wrenc_gpu_last_encode_stats counts and
+ * times as a launch -- and the CTU-pictures it searches without padding.
+ * info is always filled.  launches (launches_cap records), entries (the picture of each list entry; entries_cap ints) and
+ * groups (QP and pictures per group of WPB entries; 2 x groups_cap ints) may be NULL with a capacity of 0; WRENC_GPU_EINVAL
+ * where a capacity is smaller than what info reports, and for arguments wrenc_gpu_encode could not be called with. */
+typedef struct wrenc_gpu_plan_launch {
+    int32_t lane, team, diag, r_min, count, first, n, grid, group, qp, span;
+    int64_t ctus;
+} wrenc_gpu_plan_launch;
+typedef struct wrenc_gpu_plan_info {
+    int32_t n_launches, n_entries, n_groups, n_lanes, n_spans, schedule; /* schedule: what runs (AUTO = both kernels) */
+    int32_t wpb, team, encode_lanes, team_below_pct, team_below_pct_depth3; /* the build constants the plan was made with */
+} wrenc_gpu_plan_info;
+int wrenc_gpu_test_plan(int ctu_cols, int ctu_rows, const int* qps, int n_pictures, int schedule, long long wave_slots, int depth3,
+                        wrenc_gpu_plan_info* info, wrenc_gpu_plan_launch* launches, int launches_cap, int* entries, int entries_cap,
+                        int* groups, int groups_cap);
 /* Test entry: how many workgroups since context creation found the scratch partition of their XCD full and took a
  * region of the shared overflow partition instead (wrenc_gpu.hip, acquire_scratch).  0 on MI355X: the saved
  * reconstructions of the search then stay behind the L2 of the XCD that wrote them.  Waits for the device. */

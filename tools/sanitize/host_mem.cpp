@@ -1,10 +1,11 @@
-// ASan + UBSan over wrenc_amd/csrc/host_mem.h: DevBuf against stub definitions of the three HIP calls it uses (malloc and
-// free behind them, a count of live allocations, a switch that makes the k-th allocation fail and leaves HIP's error
-// pending).  A double free or a leak is the sanitizer's to report.  Stand-alone (tools/sanitize/run.sh builds and runs it,
-// no HIP library linked); never loaded into Python.
+// ASan + UBSan over wrenc_amd/csrc/host_mem.h: DevBuf, HipStream and HipEvent against stub definitions of the HIP calls they
+// use (malloc and free behind them, counts of live allocations and live handles, a switch that makes the k-th allocation
+// or creation fail and leaves HIP's error pending).  A double free or a leak is the sanitizer's to report.  Stand-alone
+// (tools/sanitize/run.sh builds and runs it, no HIP library linked); never loaded into Python.
 #include <cstdio>
 #include <cstdlib>
 #include <utility>
+#include <vector>
 
 #include "../../wrenc_amd/csrc/host_mem.h"
 
@@ -31,6 +32,31 @@ extern "C" hipError_t hipGetLastError(void) {
     g_pending = hipSuccess;
     return e;
 }
+
+// streams and events: a handle is a small allocation of its own (a double destroy or a leak is the sanitizer's to report);
+// creations count with the allocations, so that arm() makes the k-th creation of any kind fail
+static int g_live_handles = 0;
+template <class H>
+static hipError_t make_handle(H* h) {
+    ++g_allocs;
+    if (g_allocs == g_fail_at) {
+        *h = (H)16;
+        return g_pending = hipErrorOutOfMemory;
+    }
+    *h = (H)malloc(1);
+    ++g_live_handles;
+    return hipSuccess;
+}
+template <class H>
+static hipError_t drop_handle(H h) {
+    free((void*)h);
+    --g_live_handles;
+    return hipSuccess;
+}
+extern "C" hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { return make_handle(s); }
+extern "C" hipError_t hipStreamDestroy(hipStream_t s) { return drop_handle(s); }
+extern "C" hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return make_handle(e); }
+extern "C" hipError_t hipEventDestroy(hipEvent_t e) { return drop_handle(e); }
 
 static void arm(int fail_at) {
     g_allocs = 0;
@@ -75,7 +101,92 @@ static hipError_t make_pair(Pair& p) {
     return hipSuccess;
 }
 
+using wrenc::HipEvent;
+using wrenc::HipStream;
+
+struct Handles { // the streams and events of a context in small, memory between them
+    HipStream stream;
+    HipEvent fork;
+    std::vector<HipEvent> ring;
+    std::vector<HipStream> lanes;
+    DevBuf<int> mem;
+    HipStream copy;
+    HipEvent timing[2];
+};
+static hipError_t fill(Handles& h) { // 1 + 1 + 3 + 2 + 1 + 1 + 2 = 11 creations
+    if (hipError_t e = h.stream.create(hipStreamNonBlocking)) return e;
+    if (hipError_t e = h.fork.create()) return e;
+    h.ring.resize(3);
+    for (HipEvent& ev : h.ring)
+        if (hipError_t e = ev.create(hipEventDisableTiming)) return e;
+    h.lanes.resize(2);
+    for (HipStream& s : h.lanes)
+        if (hipError_t e = s.create(hipStreamNonBlocking)) return e;
+    if (hipError_t e = h.mem.alloc(4)) return e;
+    if (hipError_t e = h.copy.create(hipStreamNonBlocking)) return e;
+    for (HipEvent& ev : h.timing)
+        if (hipError_t e = ev.create()) return e;
+    return hipSuccess;
+}
+
+template <class Handle>
+static int handle_cases() {
+    arm(0);
+    {
+        Handle a;
+        CHECK(!a && a.get() == nullptr && g_live_handles == 0);
+        CHECK(a.create() == hipSuccess && a && g_live_handles == 1);
+        CHECK(a.create(1) == hipSuccess && a && g_live_handles == 1); // create over a held handle destroys the old one
+        // a failed create holds nothing and leaves no error pending
+        arm(1);
+        CHECK(a.create() == hipErrorOutOfMemory && !a && a.get() == nullptr && g_live_handles == 0 && g_pending == hipSuccess);
+        arm(0);
+        CHECK(a.create() == hipSuccess && g_live_handles == 1); // usable again
+        a.reset();
+        CHECK(!a && g_live_handles == 0);
+        a.reset();
+        CHECK(a.create() == hipSuccess && g_live_handles == 1);
+    } // the destructor destroys
+    CHECK(g_live_handles == 0);
+    {
+        // moves leave one owner
+        Handle a;
+        CHECK(a.create() == hipSuccess);
+        const auto h = a.get();
+        Handle b(std::move(a));
+        CHECK(!a && b.get() == h && g_live_handles == 1);
+        Handle c;
+        CHECK(c.create() == hipSuccess && g_live_handles == 2);
+        c = std::move(b); // what c held is destroyed
+        CHECK(!b && c.get() == h && g_live_handles == 1);
+        Handle& self = c;
+        c = std::move(self);
+        CHECK(c.get() == h && g_live_handles == 1);
+        // a growing vector moves its handles (the pool of timing events)
+        std::vector<Handle> pool;
+        for (int i = 0; i < 9; ++i) {
+            Handle e;
+            CHECK(e.create() == hipSuccess);
+            pool.push_back(std::move(e));
+        }
+        CHECK(g_live_handles == 10);
+    }
+    CHECK(g_live_handles == 0);
+    return 0;
+}
+
 int main() {
+    if (handle_cases<HipStream>() || handle_cases<HipEvent>()) return 1;
+    // the handles of one holder, the k-th creation failing: nothing is left once the holder is gone
+    for (int k = 1; k <= 12; ++k) {
+        arm(k);
+        {
+            Handles h;
+            const hipError_t e = fill(h);
+            CHECK((e == hipSuccess) == (k == 12) && g_live_handles + g_live == (k == 12 ? 11 : k - 1) && g_pending == hipSuccess);
+        }
+        CHECK(g_live_handles == 0 && g_live == 0);
+    }
     arm(0);
     {
         DevBuf<int> b;
@@ -141,6 +252,7 @@ int main() {
         CHECK(make_pair(p) == hipSuccess && p.scratch && p.map && p.scratch.count() == 100 && p.map.count() == 5 && g_live == 2);
     }
     CHECK(g_live == 0);
-    printf("host_mem: DevBuf clean, no live allocation at exit\n");
+    CHECK(g_live_handles == 0);
+    printf("host_mem: DevBuf, HipStream and HipEvent clean, no live allocation or handle at exit\n");
     return 0;
 }

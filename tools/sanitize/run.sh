@@ -39,7 +39,12 @@ ${CLANGXX:-/opt/rocm/lib/llvm/bin/clang++} -O1 -g -std=c++17 -fsanitize=address,
 g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined \
     -o "$T/rate_vbv" "$R/tools/sanitize/rate_vbv.cpp" $H0/rate_control.cpp
 "$T/rate_vbv"
-# the owner of device memory (wrenc_amd/csrc/host_mem.h) against stub definitions of the HIP calls it uses: no HIP library
+# the launch plan of an encode call (wrenc_amd/csrc/encode_plan.h) over the sweep of tests/test_encode_plan.py
+g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined \
+    -o "$T/encode_plan" "$R/tools/sanitize/encode_plan.cpp"
+"$T/encode_plan"
+# the owners of device memory, streams and events (wrenc_amd/csrc/host_mem.h) against stub definitions of the HIP calls they
+# use: no HIP library
 g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined \
     -D__HIP_PLATFORM_AMD__ -I"${ROCM_PATH:-/opt/rocm}/include" -o "$T/host_mem" "$R/tools/sanitize/host_mem.cpp"
 "$T/host_mem"

@@ -1,5 +1,6 @@
-// host_mem.h -- device memory with an owner (host code only).  The one place that allocates and frees device memory:
-// what a context or a test entry holds in a DevBuf is freed when the holder goes, on every path.
+// host_mem.h -- device memory, streams and events with an owner (host code only).  The one place that allocates and frees
+// device memory and that creates and destroys streams and events: what a context or a test entry holds in a DevBuf, a
+// HipStream or a HipEvent is released when the holder goes, on every path.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -52,5 +53,50 @@ private:
     T* p_ = nullptr;
     size_t n_ = 0;
 };
+
+// A stream or an event of the current device, or nothing.  Movable, not copyable; the destructor destroys the handle
+// (whoever holds a stream synchronises it first where work may still be queued on it).
+template <class H, hipError_t (*Create)(H*, unsigned), hipError_t (*Destroy)(H)>
+class HipHandle {
+public:
+    HipHandle() = default;
+    HipHandle(const HipHandle&) = delete;
+    HipHandle& operator=(const HipHandle&) = delete;
+    HipHandle(HipHandle&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    HipHandle& operator=(HipHandle&& o) noexcept {
+        if (this != &o) {
+            reset();
+            h_ = o.h_;
+            o.h_ = nullptr;
+        }
+        return *this;
+    }
+    ~HipHandle() { reset(); }
+
+    // replaces what is held by a new handle (flags 0: the default stream or event).  On failure nothing is held and HIP's
+    // last error is cleared, as DevBuf::alloc does.
+    hipError_t create(unsigned flags = 0) {
+        reset();
+        H h = nullptr;
+        const hipError_t e = Create(&h, flags);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return e;
+        }
+        h_ = h;
+        return hipSuccess;
+    }
+    void reset() {
+        if (h_) (void)Destroy(h_);
+        h_ = nullptr;
+    }
+    H get() const { return h_; }
+    explicit operator bool() const { return h_ != nullptr; }
+
+private:
+    H h_ = nullptr;
+};
+using HipStream = HipHandle<hipStream_t, hipStreamCreateWithFlags, hipStreamDestroy>;
+using HipEvent = HipHandle<hipEvent_t, hipEventCreateWithFlags, hipEventDestroy>;
 
 } // namespace wrenc

@@ -17,6 +17,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "encode_plan.h"
 #include "host_mem.h"
 
 #include <cmath>
@@ -677,6 +678,10 @@ constexpr int kEncodeLanes = WRENC_ENCODE_LANES;
 // 3840x2176 (60 pictures: 89.0 against 86.1 frames/s; 90: 102.6 / 100.9; 128: 115.8 / 114.5; 7680x4320, 32 pictures:
 // 23.2 / 22.5; gpurun_out/s69, s70); at depth 2 it is 50 % still (128 pictures of 1080p: 459 against 454 at 65 %).
 constexpr int kTeamBelowSlotsPct = 50, kTeamBelowSlotsPctDepth3 = 65;
+// what plan_encode (encode_plan.h) is given of this build
+constexpr PlanBuild kPlanBuild = {WPB, kTeam, kEncodeLanes, kTeamBelowSlotsPct, kTeamBelowSlotsPctDepth3};
+static_assert(kPlanAuto == WRENC_GPU_SCHEDULE_AUTO && kPlanWave == WRENC_GPU_SCHEDULE_WAVE && kPlanTeam == WRENC_GPU_SCHEDULE_TEAM,
+              "encode_plan.h restates wrenc_gpu_schedule");
 
 // DCT-2 integer cosines c[j] ~ 64*sqrt(2)*cos(j*pi/128), H.266 8.7.4.5
 // (the reference's 64-point matrix, transformer.rs:934-1191, is row k = c[(2n+1)k])
@@ -756,24 +761,31 @@ struct wrenc_gpu_ctx {
     wrenc_gpu_config cfg;
     long long wave_slots = 0;                  // waves of the search kernel the device holds at once
     long long device_wave_slots = 0;           // (wave_slots can be overridden by a test: wrenc_gpu_test_set_wave_slots)
-    hipStream_t stream = nullptr;              // lane 0 of the encode; timing events
-    hipStream_t copy_stream = nullptr;         // uploads and downloads: they overlap the search of other slots
-    hipEvent_t ev_uploaded = nullptr;          // end of the uploads an encode call has to wait for
+    // Device memory, streams and events belong to DevBuf, HipStream and HipEvent members (host_mem.h): `delete ctx`
+    // releases them, wrenc_gpu_destroy lists none of them.
+    HipStream stream;                          // lane 0 of the encode; timing events
+    HipStream copy_stream;                     // uploads and downloads: they overlap the search of other slots
+    HipEvent ev_uploaded;                      // end of the uploads an encode call has to wait for
     bool uploads_pending = false;
-    std::vector<hipEvent_t> enc_events;        // ring: one "this encode call is done" event per call in flight
+    std::vector<HipEvent> enc_events;          // ring: one "this encode call is done" event per call in flight
     size_t enc_event_next = 0;
-    std::vector<hipEvent_t> slot_event;        // per slot: the event of the encode call that last searched it
-    std::vector<hipStream_t> lanes;            // extra encode lanes (pictures are independent)
-    std::vector<hipEvent_t> lane_done;
-    hipEvent_t ev_fork = nullptr;
-    hipEvent_t last_done = nullptr;            // completion event of the most recent encode call
-    // Device memory belongs to DevBuf members (host_mem.h): `delete ctx` frees it, wrenc_gpu_destroy lists none of it.
-    DevBuf<DevConst> d_const;
-    // per-picture QP (wrenc_gpu_set_slot_qp): one constant block per QP in use, built on first use and kept until destroy
-    // (a call in flight may read it); the QP of every slot (-1: the context's); per encode call in flight (ring of
-    // enc_events), the call's picture list and its groups (grown on demand), host copy kept until the call is done
-    DevBuf<DevConst> d_qconst[64];
-    std::unique_ptr<wrenc_gpu_config> qcfg[64]; // the per-QP config a block was built from (its lambdas are the QP's)
+    std::vector<hipEvent_t> slot_event;        // per slot: the event (of enc_events) of the encode call that last searched it
+    std::vector<HipStream> lanes;              // extra encode lanes (pictures are independent)
+    std::vector<HipEvent> lane_done;
+    HipEvent ev_fork;
+    hipEvent_t last_done = nullptr;            // completion event (of enc_events) of the most recent encode call
+    // One constant block per QP in use: the context's from wrenc_gpu_create, the others from wrenc_gpu_set_slot_qp on first
+    // use.  A block is never changed or freed while the context lives (a call in flight may read it); the lambdas it was
+    // built from are what a later config for the same QP must repeat.
+    struct QpConst {
+        DevBuf<DevConst> d;
+        int64_t lambda_q = 0;
+        float lambda_rd = 0.f, lambda_rd_chroma = 0.f;
+    };
+    QpConst qconst[64];
+    const DevConst* ctx_const() const { return qconst[cfg.qp].d.get(); }
+    // per-picture QP (wrenc_gpu_set_slot_qp): the QP of every slot; per encode call in flight (ring of enc_events), the
+    // call's picture list and its groups (grown on demand), host copy kept until the call is done
     std::vector<int> slot_qp;
     struct CallList {
         DevBuf<PicBufs> d_pics;
@@ -814,11 +826,10 @@ struct wrenc_gpu_ctx {
     // made by the first encode call, both or neither:
     DevBuf<uint8_t> d_pred_scratch; // kScratchSlots x WPB x kWaveScratch: saved reconstructions (dev_search.h copy_block)
     DevBuf<unsigned long long> d_slot_map; // kScratchSlots bits: scratch regions in use
-    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
-    std::vector<hipEvent_t> ev_pool;
-    int last_launches = 0;
-    std::vector<char> launch_team;             // per launch of the last call: the team kernel?
-    std::vector<long long> launch_ctus;        // ... and the CTU-pictures it searched
+    HipEvent ev_begin, ev_end;
+    std::vector<HipEvent> ev_pool;             // two per span of the plan (encode_plan.h): around a lane's launches of a diagonal
+    Plan plan;                                 // of the most recent encode call; its vectors are reused from call to call
+    std::vector<int> call_qp;                  // ... and the QPs of its pictures, what the plan was made from
     bool stats_enabled = false; // per-launch timing events: bench / profiling only (wrenc_gpu_stats_enable)
     // Per-call scratch of the read-backs that wait for the search, grown on demand: each call asks its buffers for what
     // its pictures need (DevBuf::grow), and a buffer that is large enough stays.
@@ -836,11 +847,11 @@ struct wrenc_gpu_ctx {
     // hash read-back (made on first use: a context that never asks launches and allocates what it always did): a stream
     // of its own -- an MD5 pass is long, and on the copy stream it would stand in front of the next batch's uploads --,
     // the CRC's tables, the waves' partials of one call and the pictures' values, grown on demand
-    hipStream_t hash_stream = nullptr;
+    HipStream hash_stream;
     DevBuf<HashTables> d_htables;
     DevBuf<uint32_t> d_hpartial;
     DevBuf<wrenc_picture_hash> d_hvalues;
-    hipEvent_t hash_ev[2] = {nullptr, nullptr}; // measurement mode (stats_enabled): around the last hash pass
+    HipEvent hash_ev[2];                        // measurement mode (stats_enabled): around the last hash pass
     bool hash_timed = false;
     // complexity read-back: the waves' triples, the pictures' totals and CTU maps of one call, for every slot at once
     // (allocated on first use and never again: a later call must not free device memory under a search in flight)
@@ -851,7 +862,6 @@ struct wrenc_gpu_ctx {
     DevBuf<RateHistPartial> d_rpartial;
     DevBuf<RateHistCounts> d_rsums;
     int schedule = WRENC_GPU_SCHEDULE_AUTO;
-    int last_schedule = WRENC_GPU_SCHEDULE_WAVE; // what the most recent encode call ran
     bool stats_valid = false;
     std::string err;
     int ctu_cols = 0, ctu_rows = 0;
@@ -898,7 +908,7 @@ int check_slots(wrenc_gpu_ctx* ctx, int first, int n, int min_state, const char*
 // the copy stream (or `st`) waits for the encode calls that searched these slots and for nothing queued after them (the
 // slots of one read-back usually share one call's event: each event is waited for once)
 int wait_for_search(wrenc_gpu_ctx* ctx, int first, int n, hipStream_t st = nullptr) {
-    hipStream_t cs = st ? st : ctx->copy_stream;
+    hipStream_t cs = st ? st : ctx->copy_stream.get();
     hipEvent_t last = nullptr;
     for (int s = first; s < first + n; ++s)
         if (ctx->slot_event[s] && ctx->slot_event[s] != last) {
@@ -910,7 +920,7 @@ int wait_for_search(wrenc_gpu_ctx* ctx, int first, int n, hipStream_t st = nullp
 
 // the encode calls' sticky overflow word, read on the copy stream (or `st`) behind what is queued there, as a status
 int read_overflow(wrenc_gpu_ctx* ctx, hipStream_t st = nullptr) {
-    hipStream_t cs = st ? st : ctx->copy_stream;
+    hipStream_t cs = st ? st : ctx->copy_stream.get();
     int ovf = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&ovf, ctx->d_overflow.get(), sizeof(int), hipMemcpyDeviceToHost, cs));
     HIP_TRY(ctx, hipStreamSynchronize(cs));
@@ -924,7 +934,7 @@ int copy_maps(wrenc_gpu_ctx* ctx, int slot, uint8_t* cu_log2_size, uint8_t* luma
               uint8_t* rec_cb, uint8_t* rec_cr) {
     const wrenc_gpu_config& c = ctx->cfg;
     const PicBufs& b = ctx->slots[slot];
-    hipStream_t cs = ctx->copy_stream;
+    hipStream_t cs = ctx->copy_stream.get();
     const size_t n4 = (size_t)(c.width / 4) * (c.height / 4), n8 = (size_t)(c.width / 8) * (c.height / 8);
     if (cu_log2_size) HIP_TRY(ctx, hipMemcpyAsync(cu_log2_size, b.cu_log2, n4, hipMemcpyDeviceToHost, cs));
     if (luma_mode) HIP_TRY(ctx, hipMemcpyAsync(luma_mode, b.luma_mode, n4, hipMemcpyDeviceToHost, cs));
@@ -1224,28 +1234,23 @@ int run_block_test(wrenc_gpu_ctx* ctx, const int16_t* in, int log2n, int count, 
     if (log2n < 2 || log2n > 5 || count < 1 || nb < 1) return fail(ctx, WRENC_GPU_EINVAL, "log2n must be 2..5 and count >= 1");
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
     const size_t n = (size_t)count * nb << (2 * log2n);
-    struct Event {
-        hipEvent_t e = nullptr;
-        ~Event() {
-            if (e) (void)hipEventDestroy(e);
-        }
-    } e0, e1;
+    HipEvent e0, e1;
     DevBuf<int16_t> d_in, d_out;
     HIP_TRY(ctx, d_in.alloc(n));
     HIP_TRY(ctx, d_out.alloc(n));
     if (kernel_ms) {
         *kernel_ms = 0.f;
-        HIP_TRY(ctx, hipEventCreate(&e0.e));
-        HIP_TRY(ctx, hipEventCreate(&e1.e));
+        HIP_TRY(ctx, e0.create());
+        HIP_TRY(ctx, e1.create());
     }
-    HIP_TRY(ctx, hipMemcpyAsync(d_in.get(), in, n * sizeof(int16_t), hipMemcpyHostToDevice, ctx->stream));
-    if (kernel_ms) HIP_TRY(ctx, hipEventRecord(e0.e, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_in.get(), in, n * sizeof(int16_t), hipMemcpyHostToDevice, ctx->stream.get()));
+    if (kernel_ms) HIP_TRY(ctx, hipEventRecord(e0.get(), ctx->stream.get()));
     launch(d_in.get(), d_out.get());
     HIP_TRY(ctx, hipGetLastError());
-    if (kernel_ms) HIP_TRY(ctx, hipEventRecord(e1.e, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(out, d_out.get(), n * sizeof(int16_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (kernel_ms) HIP_TRY(ctx, hipEventElapsedTime(kernel_ms, e0.e, e1.e));
+    if (kernel_ms) HIP_TRY(ctx, hipEventRecord(e1.get(), ctx->stream.get()));
+    HIP_TRY(ctx, hipMemcpyAsync(out, d_out.get(), n * sizeof(int16_t), hipMemcpyDeviceToHost, ctx->stream.get()));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream.get()));
+    if (kernel_ms) HIP_TRY(ctx, hipEventElapsedTime(kernel_ms, e0.get(), e1.get()));
     return WRENC_GPU_OK;
 }
 
@@ -1278,9 +1283,9 @@ int load_test_picture(wrenc_gpu_ctx* ctx, const uint8_t* const org[3], const uin
 // (include/wrenc_gpu.h: "keep a word of their own and never poison a context")
 int take_test_overflow(wrenc_gpu_ctx* ctx, int rc) {
     int ovf = 0;
-    hipError_t e = hipMemcpyAsync(&ovf, ctx->d_overflow.get() + 1, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(ctx->d_overflow.get() + 1, 0, sizeof(int), ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    hipError_t e = hipMemcpyAsync(&ovf, ctx->d_overflow.get() + 1, sizeof(int), hipMemcpyDeviceToHost, ctx->stream.get());
+    if (e == hipSuccess) e = hipMemsetAsync(ctx->d_overflow.get() + 1, 0, sizeof(int), ctx->stream.get());
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream.get());
     if (rc != WRENC_GPU_OK) return rc;
     if (e != hipSuccess) return fail(ctx, WRENC_GPU_EHIP, hipGetErrorString(e));
     if (!ovf) return WRENC_GPU_OK;
@@ -1424,24 +1429,13 @@ const char* wrenc_gpu_last_error(const wrenc_gpu_ctx* ctx) { return ctx ? ctx->e
 void wrenc_gpu_destroy(wrenc_gpu_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->cfg.device);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (hipStream_t st : ctx->lanes) (void)hipStreamSynchronize(st);
-    if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
-    if (ctx->hash_stream) (void)hipStreamSynchronize(ctx->hash_stream);
-    if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
-    if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
-    for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
-    for (hipStream_t st : ctx->lanes) (void)hipStreamDestroy(st);
-    for (hipEvent_t e : ctx->lane_done) (void)hipEventDestroy(e);
-    if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
-    if (ctx->ev_uploaded) (void)hipEventDestroy(ctx->ev_uploaded);
-    for (hipEvent_t e : ctx->enc_events) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->hash_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (ctx->hash_stream) (void)hipStreamDestroy(ctx->hash_stream);
-    if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx; // (frees the device memory: every stream has been synchronised above)
+    // every stream that exists (a context whose creation failed half-way has only some)
+    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream.get());
+    for (const HipStream& st : ctx->lanes)
+        if (st) (void)hipStreamSynchronize(st.get());
+    if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream.get());
+    if (ctx->hash_stream) (void)hipStreamSynchronize(ctx->hash_stream.get());
+    delete ctx; // (frees the device memory and destroys the streams and events: every stream has been synchronised above)
 }
 
 // The trellis keeps path costs in 32 bits (dev_quant.h, above kNoBranch): exact as long as one step costs less than 2^25,
@@ -1458,6 +1452,19 @@ static bool rate_model_fits(const wrenc_gpu_config& cfg) {
 }
 static const char* const kRateModelMsg =
     "the quantiser's rate model (lambda_q x dq_table) is outside the range the device's 32-bit trellis costs cover";
+
+// The constant block of qc.qp into the context's table (wrenc_gpu_ctx::qconst), built from `qc`: the context's own config
+// or one that differs from it in the QP and the lambdas only.  hipErrorOutOfMemory where the host has no memory either.
+static hipError_t make_qp_const(wrenc_gpu_ctx* ctx, const wrenc_gpu_config& qc) {
+    std::unique_ptr<DevConst> hk(new (std::nothrow) DevConst());
+    if (!hk) return hipErrorOutOfMemory;
+    fill_dev_const(qc, *hk);
+    DevBuf<DevConst> d;
+    if (hipError_t e = d.alloc(1)) return e;
+    if (hipError_t e = hipMemcpy(d.get(), hk.get(), sizeof(DevConst), hipMemcpyHostToDevice)) return e;
+    ctx->qconst[qc.qp] = wrenc_gpu_ctx::QpConst{std::move(d), qc.lambda_q, qc.lambda_rd, qc.lambda_rd_chroma};
+    return hipSuccess;
+}
 
 int wrenc_gpu_create(const wrenc_gpu_config* cfg, wrenc_gpu_ctx** out) {
     if (!cfg || !out) return fail(nullptr, WRENC_GPU_EINVAL, "null argument");
@@ -1499,38 +1506,25 @@ int wrenc_gpu_create(const wrenc_gpu_config* cfg, wrenc_gpu_ctx** out) {
                         std::string(#expr) + ": " + hipGetErrorString(e_));                        \
     } while (0)
     CREATE_TRY(hipSetDevice(cfg->device));
-    CREATE_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
-    CREATE_TRY(hipEventCreateWithFlags(&ctx->ev_uploaded, hipEventDisableTiming));
-    for (int i = 0; i < 8; ++i) {
-        hipEvent_t e = nullptr;
-        CREATE_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        ctx->enc_events.push_back(e);
-    }
+    CREATE_TRY(ctx->stream.create(hipStreamNonBlocking));
+    CREATE_TRY(ctx->ev_uploaded.create(hipEventDisableTiming));
+    ctx->enc_events.resize(8);
+    for (HipEvent& e : ctx->enc_events) CREATE_TRY(e.create(hipEventDisableTiming));
     ctx->slot_event.assign((size_t)cfg->n_slots, nullptr);
-    CREATE_TRY(hipEventCreate(&ctx->ev_fork));
-    for (int i = 1; i < kEncodeLanes; ++i) {
-        hipStream_t st = nullptr;
-        CREATE_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        ctx->lanes.push_back(st);
-        hipEvent_t e = nullptr;
-        CREATE_TRY(hipEventCreate(&e));
-        ctx->lane_done.push_back(e);
+    CREATE_TRY(ctx->ev_fork.create());
+    ctx->lanes.resize(kEncodeLanes - 1);
+    ctx->lane_done.resize(kEncodeLanes - 1);
+    for (int i = 0; i < kEncodeLanes - 1; ++i) {
+        CREATE_TRY(ctx->lanes[(size_t)i].create(hipStreamNonBlocking));
+        CREATE_TRY(ctx->lane_done[(size_t)i].create());
     }
     // Created after the encode lanes on purpose: the runtime deals streams onto its hardware queues in
     // creation order (4 per process unless GPU_MAX_HW_QUEUES says otherwise), and two lanes on one queue
     // would run one after the other.  With 4 queues the copy stream shares lane 0's.
-    CREATE_TRY(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    CREATE_TRY(hipEventCreate(&ctx->ev_begin));
-    CREATE_TRY(hipEventCreate(&ctx->ev_end));
-    {
-        DevConst* hk = new (std::nothrow) DevConst();
-        if (!hk) return bail(WRENC_GPU_ENOMEM, "out of host memory");
-        fill_dev_const(*cfg, *hk);
-        hipError_t e = ctx->d_const.alloc(1);
-        if (e == hipSuccess) e = hipMemcpy(ctx->d_const.get(), hk, sizeof(DevConst), hipMemcpyHostToDevice);
-        delete hk;
-        CREATE_TRY(e);
-    }
+    CREATE_TRY(ctx->copy_stream.create(hipStreamNonBlocking));
+    CREATE_TRY(ctx->ev_begin.create());
+    CREATE_TRY(ctx->ev_end.create());
+    CREATE_TRY(make_qp_const(ctx, *cfg));
     CREATE_TRY(ctx->d_mismatch.alloc(1));
     CREATE_TRY(hipMemset(ctx->d_mismatch.get(), 0, sizeof(unsigned long long)));
     CREATE_TRY(ctx->d_overflow.alloc(2)); // [0]: encode calls (sticky), [1]: the building-block test entries
@@ -1538,7 +1532,7 @@ int wrenc_gpu_create(const wrenc_gpu_config* cfg, wrenc_gpu_ctx** out) {
     ctx->slots.assign(cfg->n_slots, PicBufs{});
     ctx->slot_mem.resize((size_t)cfg->n_slots);
     ctx->state.assign(cfg->n_slots, 0);
-    ctx->slot_qp.assign(cfg->n_slots, -1);
+    ctx->slot_qp.assign(cfg->n_slots, cfg->qp);
     ctx->call_lists.resize(ctx->enc_events.size());
     for (int s = 0; s < cfg->n_slots; ++s) {
         PicBufs& b = ctx->slots[s];
@@ -1572,12 +1566,12 @@ int wrenc_gpu_create(const wrenc_gpu_config* cfg, wrenc_gpu_ctx** out) {
         b.chroma_mode = m.chroma_mode.get();
         b.ctu_cost = m.ctu_cost.get();
         // the planes start zeroed, with no block marked as holding levels (PicBufs::lev_dirty)
-        CREATE_TRY(hipMemsetAsync(b.lev[0], 0, (wh + wh / 2) * sizeof(int16_t), ctx->stream));
-        CREATE_TRY(hipMemsetAsync(b.lev_dirty, 0, n_ctus * 4 * sizeof(uint32_t), ctx->stream));
+        CREATE_TRY(hipMemsetAsync(b.lev[0], 0, (wh + wh / 2) * sizeof(int16_t), ctx->stream.get()));
+        CREATE_TRY(hipMemsetAsync(b.lev_dirty, 0, n_ctus * 4 * sizeof(uint32_t), ctx->stream.get()));
     }
     CREATE_TRY(ctx->d_slots.alloc((size_t)cfg->n_slots));
     CREATE_TRY(hipMemcpy(ctx->d_slots.get(), ctx->slots.data(), sizeof(PicBufs) * cfg->n_slots, hipMemcpyHostToDevice));
-    CREATE_TRY(hipStreamSynchronize(ctx->stream)); // the level planes are zero before anything can reach them
+    CREATE_TRY(hipStreamSynchronize(ctx->stream.get())); // the level planes are zero before anything can reach them
 #undef CREATE_TRY
     *out = ctx;
     return WRENC_GPU_OK;
@@ -1587,7 +1581,7 @@ int wrenc_gpu_create(const wrenc_gpu_config* cfg, wrenc_gpu_ctx** out) {
 static int finish_upload(wrenc_gpu_ctx* ctx, int slot) {
     const size_t w = ctx->cfg.width, h = ctx->cfg.height, vw = (size_t)ctx->vis_w, vh = (size_t)ctx->vis_h;
     PicBufs& b = ctx->slots[slot];
-    hipStream_t cs = ctx->copy_stream;
+    hipStream_t cs = ctx->copy_stream.get();
     // a picture smaller than the coded size: its last column and row replicated into the margin of the three planes
     // (dev_pad.h), behind the copies and in front of the tiling
     if (vw != w || vh != h) {
@@ -1618,8 +1612,8 @@ int wrenc_gpu_upload(wrenc_gpu_ctx* ctx, int slot, const uint8_t* y, const uint8
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
     PicBufs& b = ctx->slots[slot];
     // the planes may still be read by a search in flight on this slot
-    if (ctx->slot_event[slot]) HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->slot_event[slot], 0));
-    hipStream_t cs = ctx->copy_stream;
+    if (ctx->slot_event[slot]) HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream.get(), ctx->slot_event[slot], 0));
+    hipStream_t cs = ctx->copy_stream.get();
     if (scaling) {
         // Source-size planes into the context's staging planes, then the scaler (dev_scale.h) writes the visible
         // rectangle of the slot's planes.  Copies, scaler, pad and retile all run on copy_stream, in order: the one set of
@@ -1883,8 +1877,8 @@ int wrenc_gpu_upload_planes(wrenc_gpu_ctx* ctx, int slot, const void* const plan
     const size_t w = ctx->cfg.width, h = ctx->cfg.height;
     PicBufs& b = ctx->slots[slot];
     // the planes may still be read by a search in flight on this slot
-    if (ctx->slot_event[slot]) HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->slot_event[slot], 0));
-    hipStream_t cs = ctx->copy_stream;
+    if (ctx->slot_event[slot]) HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream.get(), ctx->slot_event[slot], 0));
+    hipStream_t cs = ctx->copy_stream.get();
     // the caller's bytes as they are -- a 10-bit picture crosses the bus once -- and behind them the converter (dev_format.h)
     FormatArgs a = {};
     a.raw = ctx->d_raw.get();
@@ -1939,19 +1933,19 @@ int wrenc_gpu_test_download_originals(wrenc_gpu_ctx* ctx, int slot, uint8_t* y, 
     uint8_t* out[3] = {y, cb, cr};
     // behind the slot's upload on the copy stream; a search only reads the planes
     for (int p = 0; p < 3; ++p)
-        HIP_TRY(ctx, hipMemcpyAsync(out[p], b.org[p], plane_bytes(ctx->cfg, p, 1), hipMemcpyDeviceToHost, ctx->copy_stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->copy_stream));
+        HIP_TRY(ctx, hipMemcpyAsync(out[p], b.org[p], plane_bytes(ctx->cfg, p, 1), hipMemcpyDeviceToHost, ctx->copy_stream.get()));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->copy_stream.get()));
     return WRENC_GPU_OK;
 }
 
 int wrenc_gpu_set_slot_qp(wrenc_gpu_ctx* ctx, int slot, const wrenc_gpu_config* qcfg) {
     if (!ctx) return WRENC_GPU_EINVAL;
     if (slot < 0 || slot >= ctx->cfg.n_slots) return fail(ctx, WRENC_GPU_EINVAL, "bad slot");
+    const wrenc_gpu_config& c = ctx->cfg;
     if (!qcfg) {
-        ctx->slot_qp[slot] = -1;
+        ctx->slot_qp[slot] = c.qp;
         return WRENC_GPU_OK;
     }
-    const wrenc_gpu_config& c = ctx->cfg;
     if (qcfg->qp < 0 || qcfg->qp > 63) return fail(ctx, WRENC_GPU_EINVAL, "qp out of range 0..63");
     if (qcfg->width != c.width || qcfg->height != c.height || qcfg->max_split_depth != c.max_split_depth ||
         memcmp(qcfg->lv_table, c.lv_table, sizeof(c.lv_table)) || memcmp(qcfg->dq_table, c.dq_table, sizeof(c.dq_table)) ||
@@ -1959,37 +1953,24 @@ int wrenc_gpu_set_slot_qp(wrenc_gpu_ctx* ctx, int slot, const wrenc_gpu_config* 
         memcmp(qcfg->header_bits_chroma, c.header_bits_chroma, sizeof(c.header_bits_chroma)))
         return fail(ctx, WRENC_GPU_EINVAL,
                     "a slot's config may differ from the context's in qp, lambda_q, lambda_rd and lambda_rd_chroma only");
-    const auto same_lambdas = [](const wrenc_gpu_config& a, const wrenc_gpu_config& b) {
-        return a.lambda_q == b.lambda_q && !memcmp(&a.lambda_rd, &b.lambda_rd, sizeof(float)) &&
-               !memcmp(&a.lambda_rd_chroma, &b.lambda_rd_chroma, sizeof(float));
-    };
     const int q = qcfg->qp;
-    const wrenc_gpu_config* known = q == c.qp ? &c : ctx->qcfg[q].get();
-    if (known) {
-        if (!same_lambdas(*qcfg, *known)) return fail(ctx, WRENC_GPU_EINVAL, "the context has another lambda set for this QP");
-        ctx->slot_qp[slot] = q == c.qp ? -1 : q;
+    const wrenc_gpu_ctx::QpConst& known = ctx->qconst[q];
+    if (known.d) {
+        if (qcfg->lambda_q != known.lambda_q || memcmp(&qcfg->lambda_rd, &known.lambda_rd, sizeof(float)) ||
+            memcmp(&qcfg->lambda_rd_chroma, &known.lambda_rd_chroma, sizeof(float)))
+            return fail(ctx, WRENC_GPU_EINVAL, "the context has another lambda set for this QP");
+        ctx->slot_qp[slot] = q;
         return WRENC_GPU_OK;
     }
     if (!rate_model_fits(*qcfg)) return fail(ctx, WRENC_GPU_EINVAL, kRateModelMsg);
     // the QP's constant block, built once: it is never changed or freed while the context lives, so a call in flight
     // that reads it is not disturbed
     HIP_TRY(ctx, hipSetDevice(c.device));
-    std::unique_ptr<DevConst> hk(new (std::nothrow) DevConst());
-    std::unique_ptr<wrenc_gpu_config> kept(new (std::nothrow) wrenc_gpu_config(*qcfg));
-    DevBuf<DevConst> d;
-    hipError_t e = hipErrorOutOfMemory;
-    if (hk && kept) {
-        fill_dev_const(*qcfg, *hk);
-        e = d.alloc(1);
-        if (e == hipSuccess) e = hipMemcpy(d.get(), hk.get(), sizeof(DevConst), hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess) {
+    if (const hipError_t e = make_qp_const(ctx, *qcfg)) {
         (void)hipGetLastError();
         return fail(ctx, e == hipErrorOutOfMemory ? WRENC_GPU_ENOMEM : WRENC_GPU_EHIP,
                     std::string("constant block of a QP: ") + hipGetErrorString(e));
     }
-    ctx->d_qconst[q] = std::move(d);
-    ctx->qcfg[q] = std::move(kept);
     ctx->slot_qp[slot] = q;
     return WRENC_GPU_OK;
 }
@@ -1998,62 +1979,40 @@ int wrenc_gpu_encode(wrenc_gpu_ctx* ctx, int first_slot, int n_pictures) {
     if (!ctx) return WRENC_GPU_EINVAL;
     if (const int rc = check_slots(ctx, first_slot, n_pictures, 1, "slot range out of bounds")) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+    const bool timed = ctx->stats_enabled;
+    // the timing events are re-recorded by every call: the previous call's must have been reached first
+    if (timed && ctx->stats_valid) HIP_TRY(ctx, hipEventSynchronize(ctx->ev_end.get()));
+    ctx->stats_valid = false; // until this call has recorded the events that go with its plan
+    // The whole schedule is decided before anything is queued (encode_plan.h), and kept: the statistics entry points read it.
     // The pictures' QPs are read now: a later wrenc_gpu_set_slot_qp does not change this call.  A call at one QP runs its
     // slots in place with that QP's constant block; a mixed one from a list of its own (CallGroup, above the kernels).
-    const DevConst* d_k = ctx->d_const.get();
+    const bool d3 = ctx->cfg.max_split_depth == 3; // the kernels built with / without the 4x4 leaves of split 8x8 CUs
+    Plan& plan = ctx->plan;
+    ctx->call_qp.assign(ctx->slot_qp.begin() + first_slot, ctx->slot_qp.begin() + first_slot + n_pictures);
+    plan_encode(plan, ctx->ctu_cols, ctx->ctu_rows, ctx->call_qp.data(), n_pictures, ctx->schedule, ctx->wave_slots, d3, kPlanBuild);
     const PicBufs* d_pics = ctx->d_slots.get();
     const CallGroup* d_groups = nullptr;
-    wrenc_gpu_ctx::CallList* cl = nullptr;
-    int list_first = first_slot, n_entries = n_pictures;
-    {
-        const int q0 = ctx->slot_qp[first_slot];
-        bool mixed = false;
-        for (int s = first_slot; s < first_slot + n_pictures; ++s) mixed |= ctx->slot_qp[s] != q0;
-        if (!mixed && q0 >= 0) d_k = ctx->d_qconst[q0].get();
-        if (mixed) {
-            // this call's list: the ring entry of the completion event it will record, last used by the call that recorded
-            // that event before -- which must be done before the list is rewritten
-            const size_t ring = ctx->enc_event_next % ctx->enc_events.size();
-            HIP_TRY(ctx, hipEventSynchronize(ctx->enc_events[ring]));
-            cl = &ctx->call_lists[ring];
-            cl->pics.clear();
-            cl->groups.clear();
-            // QP classes in ascending order, each padded to whole groups of WPB (padding repeats the class's last picture)
-            for (int q = 0; q < 64; ++q) {
-                int n_q = 0;
-                for (int s = first_slot; s < first_slot + n_pictures; ++s)
-                    if ((ctx->slot_qp[s] < 0 ? ctx->cfg.qp : ctx->slot_qp[s]) == q) {
-                        cl->pics.push_back(ctx->slots[s]);
-                        ++n_q;
-                    }
-                if (!n_q) continue;
-                while (cl->pics.size() % WPB) cl->pics.push_back(cl->pics.back());
-                const DevConst* kq = q == ctx->cfg.qp ? ctx->d_const.get() : ctx->d_qconst[q].get();
-                for (int g = 0; g * WPB < n_q; ++g) cl->groups.push_back(CallGroup{kq, n_q - g * WPB < WPB ? n_q - g * WPB : WPB});
-            }
-            n_entries = (int)cl->pics.size();
-            if (cl->d_pics.grow((size_t)n_entries) != hipSuccess || cl->d_groups.grow((size_t)n_entries / WPB) != hipSuccess)
-                return fail(ctx, WRENC_GPU_ENOMEM, "no device memory for the picture list of a mixed-QP call");
-            HIP_TRY(ctx, hipMemcpyAsync(cl->d_pics.get(), cl->pics.data(), sizeof(PicBufs) * n_entries, hipMemcpyHostToDevice, ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(cl->d_groups.get(), cl->groups.data(), sizeof(CallGroup) * cl->groups.size(), hipMemcpyHostToDevice,
-                                        ctx->stream));
-            d_pics = cl->d_pics.get();
-            d_groups = cl->d_groups.get();
-            list_first = 0;
-        }
+    int list_first = first_slot;
+    if (plan.mixed()) {
+        // this call's list: the ring entry of the completion event it will record, last used by the call that recorded
+        // that event before -- which must be done before the list is rewritten
+        const size_t ring = ctx->enc_event_next % ctx->enc_events.size();
+        HIP_TRY(ctx, hipEventSynchronize(ctx->enc_events[ring].get()));
+        wrenc_gpu_ctx::CallList& cl = ctx->call_lists[ring];
+        cl.pics.clear();
+        cl.groups.clear();
+        for (const int i : plan.entries) cl.pics.push_back(ctx->slots[(size_t)(first_slot + i)]);
+        for (const PlanGroup& g : plan.groups) cl.groups.push_back(CallGroup{ctx->qconst[g.qp].d.get(), g.n_real});
+        if (cl.d_pics.grow(cl.pics.size()) != hipSuccess || cl.d_groups.grow(cl.groups.size()) != hipSuccess)
+            return fail(ctx, WRENC_GPU_ENOMEM, "no device memory for the picture list of a mixed-QP call");
+        HIP_TRY(ctx, hipMemcpyAsync(cl.d_pics.get(), cl.pics.data(), sizeof(PicBufs) * cl.pics.size(), hipMemcpyHostToDevice, ctx->stream.get()));
+        HIP_TRY(ctx, hipMemcpyAsync(cl.d_groups.get(), cl.groups.data(), sizeof(CallGroup) * cl.groups.size(), hipMemcpyHostToDevice,
+                                    ctx->stream.get()));
+        d_pics = cl.d_pics.get();
+        d_groups = cl.d_groups.get();
+        list_first = 0;
     }
-    const int cols = ctx->ctu_cols, rows = ctx->ctu_rows;
-    const int ndiag = cols + 2 * (rows - 1);
-    // Which schedule, decided PER ANTI-DIAGONAL: one wave per CTU fills the GPU only with thousands of CTUs
-    // runnable side by side (pictures x CTUs of the diagonal); below that a team of kTeam waves per CTU
-    // shortens the CTU's chain of dependent evaluations instead (kTeamBelowSlotsPct above).  The thin first and last diagonals of a big batch run as teams, its wide ones as waves.
-    // Pictures are dealt to lanes in units of WPB (the wave schedule's workgroup) whatever the schedule, so a
-    // picture stays on one stream; a team launch covers its lane's pictures in groups of WPB / kTeam.
-    const int per_group = WPB;
-    constexpr int kTeamsPerGroup = WPB >= kTeam ? WPB / kTeam : 1;
-    const int total_groups = (n_entries + per_group - 1) / per_group;
-    int n_team_diags = 0, n_wave_diags = 0;
-    const int n_lanes = total_groups < kEncodeLanes ? total_groups : kEncodeLanes;
+    const int n_lanes = plan.n_lanes;
     if (!ctx->d_pred_scratch) { // into locals first: a call that fails here leaves the context with neither
         DevBuf<uint8_t> scratch;
         DevBuf<unsigned long long> map;
@@ -2063,112 +2022,55 @@ int wrenc_gpu_encode(wrenc_gpu_ctx* ctx, int first_slot, int n_pictures) {
         ctx->d_pred_scratch = std::move(scratch);
         ctx->d_slot_map = std::move(map);
     }
-    const bool timed = ctx->stats_enabled;
-    if (timed) {
-        // the timing events are re-recorded by every call: the previous call's must have been reached first
-        if (ctx->stats_valid) HIP_TRY(ctx, hipEventSynchronize(ctx->ev_end));
-        while ((int)ctx->ev_pool.size() < 2 * ndiag * n_lanes) {
-            hipEvent_t e;
-            HIP_TRY(ctx, hipEventCreate(&e));
-            ctx->ev_pool.push_back(e);
-        }
+    while (timed && ctx->ev_pool.size() < 2 * (size_t)plan.n_spans) {
+        HipEvent e;
+        HIP_TRY(ctx, e.create());
+        ctx->ev_pool.push_back(std::move(e));
     }
     // The scratch-region bitmap is only ever changed by running workgroups (acquire at start, release at
     // end).  A kernel that was aborted would leave its bits set for good, so the map is cleared whenever no
     // encode call is in flight (the last call's completion event has been reached).
     if (ctx->last_done == nullptr || hipEventQuery(ctx->last_done) == hipSuccess)
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_slot_map.get(), 0, kScratchSlots / 8, ctx->stream)); // (not the overflow counter)
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_slot_map.get(), 0, kScratchSlots / 8, ctx->stream.get())); // (not the overflow counter)
     if (ctx->uploads_pending) {
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_uploaded, ctx->copy_stream));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_uploaded, 0));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_uploaded.get(), ctx->copy_stream.get()));
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream.get(), ctx->ev_uploaded.get(), 0));
         ctx->uploads_pending = false;
     }
-    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_begin, ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-    for (int l = 1; l < n_lanes; ++l) HIP_TRY(ctx, hipStreamWaitEvent(ctx->lanes[l - 1], ctx->ev_fork, 0));
-    int launches = 0;
-    const bool d3 = ctx->cfg.max_split_depth == 3; // the kernels built with / without the 4x4 leaves of split 8x8 CUs
-    ctx->launch_team.clear();
-    ctx->launch_ctus.clear();
-    for (int d = 0; d < ndiag; ++d) {
-        // rows r with 0 <= d - 2r < cols
-        int r_min = d - (cols - 1);
-        r_min = r_min <= 0 ? 0 : (r_min + 1) / 2;
-        int r_max = d / 2;
-        if (r_max > rows - 1) r_max = rows - 1;
-        const int count = r_max - r_min + 1;
-        if (count <= 0) continue;
-        const bool team = ctx->schedule == WRENC_GPU_SCHEDULE_TEAM ||
-                          (ctx->schedule == WRENC_GPU_SCHEDULE_AUTO &&
-                           (long long)n_pictures * count * 100 <= ctx->wave_slots * (d3 ? kTeamBelowSlotsPctDepth3 : kTeamBelowSlotsPct));
-        ++(team ? n_team_diags : n_wave_diags);
-        for (int l = 0; l < n_lanes; ++l) {
-            const int g0 = (int)((long long)total_groups * l / n_lanes), g1 = (int)((long long)total_groups * (l + 1) / n_lanes);
-            const int lane_first = list_first + g0 * per_group;
-            int lane_pics = (g1 - g0) * per_group;
-            if (g0 * per_group + lane_pics > n_entries) lane_pics = n_entries - g0 * per_group;
-            if (lane_pics <= 0) continue;
-            const CallGroup* lane_groups = d_groups ? d_groups + g0 : nullptr;
-            hipStream_t st = l == 0 ? ctx->stream : ctx->lanes[l - 1];
-            if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_pool[2 * launches], st));
-            if (team) {
-                // a call at one QP: one launch; a mixed call: one per QP class of the lane, its pictures only (a class's
-                // real pictures are contiguous, its padding is at its end)
-                for (int ga = g0; ga < g1;) {
-                    const DevConst* kq = d_k;
-                    int gb = g1, first = lane_first, n = lane_pics;
-                    if (cl) {
-                        kq = cl->groups[(size_t)ga].k;
-                        n = 0;
-                        for (gb = ga; gb < g1 && cl->groups[(size_t)gb].k == kq; ++gb) n += cl->groups[(size_t)gb].n_real;
-                        first = ga * per_group;
-                    }
-                    const dim3 grid(count * ((n + kTeamsPerGroup - 1) / kTeamsPerGroup));
-#define WRENC_LAUNCH(KERNEL)                                                                                                   \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL), grid, dim3(64 * WPB), 0, st, kq, d_pics, first, n, d, r_min, count,             \
-                       ctx->d_pred_scratch.get(), ctx->d_slot_map.get(), ctx->d_mismatch.get(), ctx->d_overflow.get())
-                    if (d3)
-                        WRENC_LAUNCH(ctu_search_team_kernel<true>);
-                    else
-                        WRENC_LAUNCH(ctu_search_team_kernel<false>);
-#undef WRENC_LAUNCH
-                    HIP_TRY(ctx, hipGetLastError());
-                    ga = gb;
-                }
-            } else {
-                const dim3 grid(count * (g1 - g0));
-#define WRENC_LAUNCH(KERNEL)                                                                                                   \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL), grid, dim3(64 * WPB), 0, st, d_k, d_pics, lane_first, lane_pics, d, r_min, count, \
-                       ctx->d_pred_scratch.get(), ctx->d_slot_map.get(), ctx->d_mismatch.get(), ctx->d_overflow.get(), lane_groups)
-                if (d3)
-                    WRENC_LAUNCH(ctu_search_kernel<true>);
-                else
-                    WRENC_LAUNCH(ctu_search_kernel<false>);
-#undef WRENC_LAUNCH
-                HIP_TRY(ctx, hipGetLastError());
-            }
-            if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_pool[2 * launches + 1], st));
-            ctx->launch_team.push_back(team ? 1 : 0);
-            int lane_real = lane_pics; // (without a mixed call's padding)
-            if (cl) {
-                lane_real = 0;
-                for (int g = g0; g < g1; ++g) lane_real += cl->groups[(size_t)g].n_real;
-            }
-            ctx->launch_ctus.push_back((long long)count * lane_real);
-            ++launches;
-        }
+    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_begin.get(), ctx->stream.get()));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_fork.get(), ctx->stream.get()));
+    for (int l = 1; l < n_lanes; ++l) HIP_TRY(ctx, hipStreamWaitEvent(ctx->lanes[l - 1].get(), ctx->ev_fork.get(), 0));
+    for (size_t i = 0; i < plan.launches.size(); ++i) {
+        const PlanLaunch& L = plan.launches[i];
+        hipStream_t st = L.lane == 0 ? ctx->stream.get() : ctx->lanes[L.lane - 1].get();
+        // a span's launches (one, or one per QP class for the teams of a mixed call) follow each other: one pair of events
+        const bool opens = i == 0 || plan.launches[i - 1].span != L.span;
+        const bool closes = i + 1 == plan.launches.size() || plan.launches[i + 1].span != L.span;
+        if (timed && opens) HIP_TRY(ctx, hipEventRecord(ctx->ev_pool[2 * (size_t)L.span].get(), st));
+        // (the wave kernel of a mixed call takes each group's block from `groups` and ignores the one it is given)
+        const DevConst* k = ctx->qconst[L.qp < 0 ? ctx->cfg.qp : L.qp].d.get();
+        const auto launch = [&](auto kernel, auto... groups) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)L.grid), dim3(64 * WPB), 0, st, k, d_pics, list_first + L.first, L.n, L.diag, L.r_min,
+                               L.count, ctx->d_pred_scratch.get(), ctx->d_slot_map.get(), ctx->d_mismatch.get(), ctx->d_overflow.get(),
+                               groups...);
+        };
+        const CallGroup* groups = L.group < 0 ? nullptr : d_groups + L.group;
+        if (L.team)
+            d3 ? launch(ctu_search_team_kernel<true>) : launch(ctu_search_team_kernel<false>);
+        else
+            d3 ? launch(ctu_search_kernel<true>, groups) : launch(ctu_search_kernel<false>, groups);
+        HIP_TRY(ctx, hipGetLastError());
+        if (timed && closes) HIP_TRY(ctx, hipEventRecord(ctx->ev_pool[2 * (size_t)L.span + 1].get(), st));
     }
     for (int l = 1; l < n_lanes; ++l) {
-        HIP_TRY(ctx, hipEventRecord(ctx->lane_done[l - 1], ctx->lanes[l - 1]));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->lane_done[l - 1], 0));
+        HIP_TRY(ctx, hipEventRecord(ctx->lane_done[l - 1].get(), ctx->lanes[l - 1].get()));
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream.get(), ctx->lane_done[l - 1].get(), 0));
     }
-    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_end, ctx->stream));
+    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_end.get(), ctx->stream.get()));
     // downloads of these slots wait for this call only, not for searches queued after it
-    hipEvent_t done = ctx->enc_events[ctx->enc_event_next++ % ctx->enc_events.size()];
-    HIP_TRY(ctx, hipEventRecord(done, ctx->stream));
+    hipEvent_t done = ctx->enc_events[ctx->enc_event_next++ % ctx->enc_events.size()].get();
+    HIP_TRY(ctx, hipEventRecord(done, ctx->stream.get()));
     ctx->last_done = done;
-    ctx->last_schedule = n_wave_diags == 0 ? WRENC_GPU_SCHEDULE_TEAM : (n_team_diags == 0 ? WRENC_GPU_SCHEDULE_WAVE : WRENC_GPU_SCHEDULE_AUTO);
-    ctx->last_launches = launches;
     ctx->stats_valid = timed;
     for (int s = first_slot; s < first_slot + n_pictures; ++s) {
         ctx->state[s] = 2;
@@ -2180,9 +2082,9 @@ int wrenc_gpu_encode(wrenc_gpu_ctx* ctx, int first_slot, int n_pictures) {
 int wrenc_gpu_sync(wrenc_gpu_ctx* ctx) {
     if (!ctx) return WRENC_GPU_EINVAL;
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->copy_stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (hipStream_t st : ctx->lanes) HIP_TRY(ctx, hipStreamSynchronize(st));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->copy_stream.get()));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream.get()));
+    for (const HipStream& st : ctx->lanes) HIP_TRY(ctx, hipStreamSynchronize(st.get()));
     return read_overflow(ctx);
 }
 
@@ -2194,7 +2096,7 @@ int wrenc_gpu_download(wrenc_gpu_ctx* ctx, int slot, wrenc_gpu_picture* out) {
     const wrenc_gpu_config& c = ctx->cfg;
     int16_t* lev[3] = {out->lev_y, out->lev_cb, out->lev_cr};
     // on the copy stream, behind the encode call that searched this slot and nothing later
-    hipStream_t cs = ctx->copy_stream;
+    hipStream_t cs = ctx->copy_stream.get();
     if (const int rc = wait_for_search(ctx, slot, 1)) return rc;
     for (int k = 0; k < 3; ++k)
         if (lev[k]) HIP_TRY(ctx, hipMemcpyAsync(lev[k], b.lev[k], plane_bytes(c, k, 2), hipMemcpyDeviceToHost, cs));
@@ -2221,7 +2123,7 @@ int wrenc_gpu_download_compact(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_
     HIP_TRY(ctx, ctx->d_cmask.grow((size_t)n * mask_words));
     HIP_TRY(ctx, ctx->d_cpayload.grow((size_t)n * blocks * 16));
     HIP_TRY(ctx, ctx->d_ccount.grow((size_t)n));
-    hipStream_t cs = ctx->copy_stream;
+    hipStream_t cs = ctx->copy_stream.get();
     if (const int rc = wait_for_search(ctx, first_slot, n)) return rc;
     hipLaunchKernelGGL(compact_levels_kernel, dim3(n), dim3(1024), 0, cs, ctx->d_slots.get(), first_slot, c.width, c.height, ctx->d_cmask.get(),
                        mask_words, ctx->d_cpayload.get(), blocks, ctx->d_ccount.get());
@@ -2265,7 +2167,7 @@ int wrenc_gpu_download_tokens(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_g
     if (const hipError_t e = ctx->d_tok_pool.grow(pages * kTokPage)) return no_room(e);
     if (const hipError_t e = ctx->d_tok_counter.grow(kCounterWords)) return no_room(e);
     if (const hipError_t e = ctx->d_tok_first.grow((size_t)n * ctus)) return no_room(e);
-    hipStream_t cs = ctx->copy_stream;
+    hipStream_t cs = ctx->copy_stream.get();
     if (const int rc = wait_for_search(ctx, first_slot, n)) return rc;
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_tok_counter.get(), 0, kCounterWords * sizeof(unsigned), cs));
     const int waves = n * ctus;
@@ -2273,7 +2175,7 @@ int wrenc_gpu_download_tokens(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_g
     int n_pools = 1;
     while (n_pools < kTokPools && n_pools * 32 <= waves) n_pools *= 2;
     const size_t sub = pages / (size_t)n_pools; // pages per sub-pool
-    hipLaunchKernelGGL(residual_tokens_kernel, dim3((waves + 3) / 4), dim3(256), 0, cs, ctx->d_const.get(), ctx->d_slots.get(), first_slot, n,
+    hipLaunchKernelGGL(residual_tokens_kernel, dim3((waves + 3) / 4), dim3(256), 0, cs, ctx->ctx_const(), ctx->d_slots.get(), first_slot, n,
                        ctx->d_tok_pool.get(), (unsigned)sub, n_pools - 1, ctx->d_tok_counter.get(), ctx->d_tok_first.get(), (int*)(ctx->d_tok_counter.get() + kCounterWords - 1));
     HIP_TRY(ctx, hipGetLastError());
     std::vector<unsigned> cnt((size_t)kCounterWords);
@@ -2339,7 +2241,7 @@ int wrenc_gpu_download_metrics(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_
     HIP_TRY(ctx, ctx->d_mpartial.grow((size_t)n * per_pic));
     HIP_TRY(ctx, ctx->d_msums.grow((size_t)n));
     // on the copy stream, behind the encode call that searched these slots and nothing later
-    hipStream_t cs = ctx->copy_stream;
+    hipStream_t cs = ctx->copy_stream.get();
     if (const int rc = wait_for_search(ctx, first_slot, n)) return rc;
     HIP_TRY(ctx, launch_metrics(c, vw, vh, cs, ctx->d_slots.get(), first_slot, n, ctx->d_mpartial.get(), ctx->d_msums.get(), nullptr));
     std::vector<MetricsSums> sums((size_t)n);
@@ -2360,7 +2262,7 @@ int wrenc_gpu_download_complexity(wrenc_gpu_ctx* ctx, int first_slot, int n, wre
     if (!ctx->d_xmap) HIP_TRY(ctx, ctx->d_xmap.alloc((size_t)c.n_slots * n_ctus));
     // on the copy stream: behind the slots' uploads (queued there) and behind no search -- the pass reads the originals only,
     // which a search of the same slot reads too and nothing but an upload writes
-    hipStream_t cs = ctx->copy_stream;
+    hipStream_t cs = ctx->copy_stream.get();
     const size_t waves = (size_t)n * per_pic;
     hipLaunchKernelGGL(complexity_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, cs, ctx->d_slots.get(), first_slot, n, c.width,
                        c.height, ctx->d_xpartial.get(), ctx->d_xmap.get());
@@ -2387,7 +2289,7 @@ int wrenc_gpu_download_rate_hist(wrenc_gpu_ctx* ctx, int first_slot, int n, wren
     if (!ctx->d_rpartial) HIP_TRY(ctx, ctx->d_rpartial.alloc((size_t)c.n_slots * per_pic));
     if (!ctx->d_rsums) HIP_TRY(ctx, ctx->d_rsums.alloc((size_t)c.n_slots));
     // on the copy stream: behind the slots' uploads and behind no search, as the complexity pass
-    hipStream_t cs = ctx->copy_stream;
+    hipStream_t cs = ctx->copy_stream.get();
     const size_t waves = (size_t)n * per_pic;
     hipLaunchKernelGGL(rate_hist_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, cs, ctx->d_slots.get(), first_slot, n, c.width, c.height,
                        ctx->d_rpartial.get());
@@ -2497,28 +2399,28 @@ int wrenc_gpu_download_hashes(wrenc_gpu_ctx* ctx, int first_slot, int n, int has
     if (const int rc = check_slots(ctx, first_slot, n, 2, "slot range out of bounds")) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
     const wrenc_gpu_config& c = ctx->cfg;
-    if (!ctx->hash_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->hash_stream, hipStreamNonBlocking));
+    if (!ctx->hash_stream) HIP_TRY(ctx, ctx->hash_stream.create(hipStreamNonBlocking));
     if (!ctx->d_htables) { // held by the context once they are filled
         DevBuf<HashTables> t;
         HIP_TRY(ctx, t.alloc(1));
-        HIP_TRY(ctx, upload_hash_tables(t.get(), ctx->hash_stream));
+        HIP_TRY(ctx, upload_hash_tables(t.get(), ctx->hash_stream.get()));
         ctx->d_htables = std::move(t);
     }
     HIP_TRY(ctx, ctx->d_hpartial.grow((size_t)n * hash_partials(c)));
     HIP_TRY(ctx, ctx->d_hvalues.grow((size_t)n));
     // on the hash stream, behind the encode call that searched these slots and nothing later; the search of other slots
     // and the copy stream's uploads go on meanwhile
-    hipStream_t hs = ctx->hash_stream;
+    hipStream_t hs = ctx->hash_stream.get();
     if (const int rc = wait_for_search(ctx, first_slot, n, hs)) return rc;
     ctx->hash_timed = false;
     if (ctx->stats_enabled) {
-        for (hipEvent_t& e : ctx->hash_ev)
-            if (!e) HIP_TRY(ctx, hipEventCreate(&e));
-        HIP_TRY(ctx, hipEventRecord(ctx->hash_ev[0], hs));
+        for (HipEvent& e : ctx->hash_ev)
+            if (!e) HIP_TRY(ctx, e.create());
+        HIP_TRY(ctx, hipEventRecord(ctx->hash_ev[0].get(), hs));
     }
     HIP_TRY(ctx, launch_hashes(c, hs, ctx->d_slots.get(), first_slot, n, hash_type, ctx->d_htables.get(), ctx->d_hpartial.get(), ctx->d_hvalues.get()));
     if (ctx->stats_enabled) {
-        HIP_TRY(ctx, hipEventRecord(ctx->hash_ev[1], hs));
+        HIP_TRY(ctx, hipEventRecord(ctx->hash_ev[1].get(), hs));
         ctx->hash_timed = true;
     }
     HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_hvalues.get(), (size_t)n * sizeof(wrenc_picture_hash), hipMemcpyDeviceToHost, hs));
@@ -2529,7 +2431,7 @@ int wrenc_gpu_last_hash_ms(wrenc_gpu_ctx* ctx, float* ms) {
     if (!ctx || !ms) return WRENC_GPU_EINVAL;
     if (!ctx->hash_timed) return fail(ctx, WRENC_GPU_ESTATE, "no timed hash pass: wrenc_gpu_stats_enable, then wrenc_gpu_download_hashes");
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-    HIP_TRY(ctx, hipEventElapsedTime(ms, ctx->hash_ev[0], ctx->hash_ev[1]));
+    HIP_TRY(ctx, hipEventElapsedTime(ms, ctx->hash_ev[0].get(), ctx->hash_ev[1].get()));
     return WRENC_GPU_OK;
 }
 
@@ -2643,18 +2545,18 @@ int wrenc_gpu_last_encode_stats(wrenc_gpu_ctx* ctx, float* total_ms, float* kern
     if (!ctx->stats_enabled) return fail(ctx, WRENC_GPU_ESTATE, "per-launch timing is off (wrenc_gpu_stats_enable)");
     if (!ctx->stats_valid) return fail(ctx, WRENC_GPU_ESTATE, "no encode has been queued since timing was switched on");
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-    HIP_TRY(ctx, hipEventSynchronize(ctx->ev_end));
+    HIP_TRY(ctx, hipEventSynchronize(ctx->ev_end.get()));
     float t = 0.f;
-    HIP_TRY(ctx, hipEventElapsedTime(&t, ctx->ev_begin, ctx->ev_end));
+    HIP_TRY(ctx, hipEventElapsedTime(&t, ctx->ev_begin.get(), ctx->ev_end.get()));
     float sum = 0.f;
-    for (int i = 0; i < ctx->last_launches; ++i) {
+    for (size_t i = 0; i < (size_t)ctx->plan.n_spans; ++i) {
         float k = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&k, ctx->ev_pool[2 * i], ctx->ev_pool[2 * i + 1]));
+        HIP_TRY(ctx, hipEventElapsedTime(&k, ctx->ev_pool[2 * i].get(), ctx->ev_pool[2 * i + 1].get()));
         sum += k;
     }
     if (total_ms) *total_ms = t;
     if (kernel_ms_sum) *kernel_ms_sum = sum;
-    if (n_launches) *n_launches = ctx->last_launches;
+    if (n_launches) *n_launches = ctx->plan.n_spans;
     return WRENC_GPU_OK;
 }
 
@@ -2663,15 +2565,19 @@ int wrenc_gpu_last_encode_kernel_stats(wrenc_gpu_ctx* ctx, wrenc_gpu_kernel_stat
     if (!ctx->stats_enabled) return fail(ctx, WRENC_GPU_ESTATE, "per-launch timing is off (wrenc_gpu_stats_enable)");
     if (!ctx->stats_valid) return fail(ctx, WRENC_GPU_ESTATE, "no encode has been queued since timing was switched on");
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-    HIP_TRY(ctx, hipEventSynchronize(ctx->ev_end));
+    HIP_TRY(ctx, hipEventSynchronize(ctx->ev_end.get()));
     for (int k = 0; k < 2; ++k) out[k] = wrenc_gpu_kernel_stats{0.f, 0, 0};
-    for (int i = 0; i < ctx->last_launches; ++i) {
+    // per span (a lane's launches of one diagonal, all of one kernel): its pair of events once, the CTU-pictures of each launch
+    int span = -1;
+    for (const PlanLaunch& L : ctx->plan.launches) {
+        wrenc_gpu_kernel_stats& o = out[L.team];
+        o.ctu_pictures += L.ctus;
+        if (L.span == span) continue;
+        span = L.span;
         float ms = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_pool[2 * i], ctx->ev_pool[2 * i + 1]));
-        wrenc_gpu_kernel_stats& o = out[ctx->launch_team[(size_t)i] ? 1 : 0];
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_pool[2 * (size_t)span].get(), ctx->ev_pool[2 * (size_t)span + 1].get()));
         o.ms_sum += ms;
         o.launches += 1;
-        o.ctu_pictures += ctx->launch_ctus[(size_t)i];
     }
     return WRENC_GPU_OK;
 }
@@ -2684,7 +2590,31 @@ int wrenc_gpu_set_schedule(wrenc_gpu_ctx* ctx, int schedule) {
     return WRENC_GPU_OK;
 }
 
-int wrenc_gpu_last_schedule(const wrenc_gpu_ctx* ctx) { return ctx ? ctx->last_schedule : WRENC_GPU_EINVAL; }
+int wrenc_gpu_last_schedule(const wrenc_gpu_ctx* ctx) { return ctx ? ctx->plan.schedule : WRENC_GPU_EINVAL; }
+
+int wrenc_gpu_test_plan(int ctu_cols, int ctu_rows, const int* qps, int n_pictures, int schedule, long long wave_slots, int depth3,
+                        wrenc_gpu_plan_info* info, wrenc_gpu_plan_launch* launches, int launches_cap, int* entries, int entries_cap,
+                        int* groups, int groups_cap) {
+    if (!qps || !info || ctu_cols < 1 || ctu_rows < 1 || n_pictures < 1 || wave_slots < 1) return WRENC_GPU_EINVAL;
+    if (schedule != WRENC_GPU_SCHEDULE_AUTO && schedule != WRENC_GPU_SCHEDULE_WAVE && schedule != WRENC_GPU_SCHEDULE_TEAM)
+        return WRENC_GPU_EINVAL;
+    for (int i = 0; i < n_pictures; ++i)
+        if (qps[i] < 0 || qps[i] > 63) return WRENC_GPU_EINVAL;
+    Plan p;
+    plan_encode(p, ctu_cols, ctu_rows, qps, n_pictures, schedule, wave_slots, depth3 != 0, kPlanBuild);
+    *info = wrenc_gpu_plan_info{(int32_t)p.launches.size(), (int32_t)p.entries.size(), (int32_t)p.groups.size(), p.n_lanes, p.n_spans,
+                                p.schedule, kPlanBuild.wpb, kPlanBuild.team, kPlanBuild.lanes, kPlanBuild.team_below_pct,
+                                kPlanBuild.team_below_pct_d3};
+    if ((!launches && launches_cap) || (!entries && entries_cap) || (!groups && groups_cap)) return WRENC_GPU_EINVAL;
+    if (launches_cap < info->n_launches || entries_cap < info->n_entries || groups_cap < info->n_groups) return WRENC_GPU_EINVAL;
+    for (size_t i = 0; i < p.launches.size(); ++i) {
+        const PlanLaunch& L = p.launches[i];
+        launches[i] = wrenc_gpu_plan_launch{L.lane, L.team, L.diag, L.r_min, L.count, L.first, L.n, L.grid, L.group, L.qp, L.span, L.ctus};
+    }
+    for (size_t i = 0; i < p.entries.size(); ++i) entries[i] = p.entries[i];
+    for (size_t i = 0; i < p.groups.size(); ++i) groups[2 * i] = p.groups[i].qp, groups[2 * i + 1] = p.groups[i].n_real;
+    return WRENC_GPU_OK;
+}
 
 int wrenc_gpu_device_info(const wrenc_gpu_ctx* ctx, long long* wave_slots, int* encode_lanes) {
     if (!ctx) return WRENC_GPU_EINVAL;
@@ -2705,7 +2635,7 @@ int wrenc_gpu_test_head_ranges(wrenc_gpu_ctx* ctx, int counts[4], int ranges[24]
     DevBuf<int> d;
     HIP_TRY(ctx, d.alloc(4));
     HIP_TRY(ctx, hipMemset(d.get(), 0, 4 * sizeof(int)));
-    hipLaunchKernelGGL(test_head_ranges_kernel, dim3(1024, 8), dim3(64), 0, 0, ctx->d_const.get(), d.get());
+    hipLaunchKernelGGL(test_head_ranges_kernel, dim3(1024, 8), dim3(64), 0, 0, ctx->ctx_const(), d.get());
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipDeviceSynchronize());
     HIP_TRY(ctx, hipMemcpy(counts, d.get(), 4 * sizeof(int), hipMemcpyDeviceToHost));
@@ -2724,7 +2654,7 @@ int wrenc_gpu_test_avail_tab(wrenc_gpu_ctx* ctx, int* differences) {
     DevBuf<int> d;
     HIP_TRY(ctx, d.alloc(1));
     HIP_TRY(ctx, hipMemset(d.get(), 0, sizeof(int)));
-    hipLaunchKernelGGL(test_avail_tab_kernel, dim3(ctx->ctu_cols * ctx->ctu_rows, 4), dim3(64), 0, 0, ctx->d_const.get(), d.get());
+    hipLaunchKernelGGL(test_avail_tab_kernel, dim3(ctx->ctu_cols * ctx->ctu_rows, 4), dim3(64), 0, 0, ctx->ctx_const(), d.get());
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipDeviceSynchronize());
     HIP_TRY(ctx, hipMemcpy(differences, d.get(), sizeof(int), hipMemcpyDeviceToHost));
@@ -2753,7 +2683,7 @@ int wrenc_gpu_stats_enable(wrenc_gpu_ctx* ctx, int on) {
 int wrenc_gpu_final_pass_mismatches(wrenc_gpu_ctx* ctx, long long* count) {
     if (!ctx || !count) return WRENC_GPU_EINVAL;
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream.get()));
     unsigned long long v = 0;
     HIP_TRY(ctx, hipMemcpy(&v, ctx->d_mismatch.get(), sizeof(v), hipMemcpyDeviceToHost));
     *count = (long long)v;
@@ -2781,7 +2711,7 @@ extern "C" long wrenc_gpu_trace_read(wrenc_gpu_ctx* ctx, int* out, long max_reco
 // diagnostic build only: read and clear the per-phase cycle counters
 int wrenc_gpu_prof_read(wrenc_gpu_ctx* ctx, unsigned long long* out, int n) {
     if (!ctx || !out) return WRENC_GPU_EINVAL;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream.get()));
     unsigned long long host[PH_COUNT];
     HIP_TRY(ctx, hipMemcpyFromSymbol(host, HIP_SYMBOL(g_prof), sizeof(host)));
     for (int i = 0; i < n && i < PH_COUNT; ++i) out[i] = host[i];
@@ -2841,9 +2771,9 @@ static int run_dct_group(wrenc_gpu_ctx* ctx, const int16_t* in, int log2n, int n
     float ms = 0.f;
     const int rc = run_block_test(ctx, in, log2n, count, out, [&](int16_t* i, int16_t* o) {
         if (inverse)
-            hipLaunchKernelGGL(test_inv_dct_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const.get(), i, log2n, nb, o1, o, arm, reps);
+            hipLaunchKernelGGL(test_inv_dct_kernel, dim3(count), dim3(64), 0, ctx->stream.get(), ctx->ctx_const(), i, log2n, nb, o1, o, arm, reps);
         else
-            hipLaunchKernelGGL(test_fwd_dct_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const.get(), i, log2n, nb, o1, o, arm, reps);
+            hipLaunchKernelGGL(test_fwd_dct_kernel, dim3(count), dim3(64), 0, ctx->stream.get(), ctx->ctx_const(), i, log2n, nb, o1, o, arm, reps);
     }, nb, kernel_ms ? &ms : nullptr);
     if (kernel_ms) *kernel_ms = ms;
     return rc;
@@ -2875,9 +2805,9 @@ static int run_dct32_bench(wrenc_gpu_ctx* ctx, const int16_t* in, int count, int
     float ms = 0.f;
     const int rc = run_block_test(ctx, in, 5, count, out, [&](int16_t* i, int16_t* o) {
         if (inverse)
-            hipLaunchKernelGGL(test_inv_dct32_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const.get(), i, o, use_mfma, reps);
+            hipLaunchKernelGGL(test_inv_dct32_kernel, dim3(count), dim3(64), 0, ctx->stream.get(), ctx->ctx_const(), i, o, use_mfma, reps);
         else
-            hipLaunchKernelGGL(test_fwd_dct32_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const.get(), i, o, use_mfma, reps);
+            hipLaunchKernelGGL(test_fwd_dct32_kernel, dim3(count), dim3(64), 0, ctx->stream.get(), ctx->ctx_const(), i, o, use_mfma, reps);
     }, 1, &ms);
     if (kernel_ms) *kernel_ms = ms;
     return rc;
@@ -2898,19 +2828,19 @@ int wrenc_gpu_test_inv_dct(wrenc_gpu_ctx* ctx, const int16_t* deq, int log2n, in
 }
 int wrenc_gpu_test_fwd_dct4_reg(wrenc_gpu_ctx* ctx, const int16_t* res, int count, int16_t* coef) {
     return run_block_test(ctx, res, 2, count, coef, [&](int16_t* i, int16_t* o) {
-        hipLaunchKernelGGL(test_dct4_reg_kernel, dim3((count + 3) / 4), dim3(64), 0, ctx->stream, ctx->d_const.get(), i, count, 0, o);
+        hipLaunchKernelGGL(test_dct4_reg_kernel, dim3((count + 3) / 4), dim3(64), 0, ctx->stream.get(), ctx->ctx_const(), i, count, 0, o);
     });
 }
 int wrenc_gpu_test_inv_dct4_reg(wrenc_gpu_ctx* ctx, const int16_t* levels, int count, int16_t* res) {
     return run_block_test(ctx, levels, 2, count, res, [&](int16_t* i, int16_t* o) {
-        hipLaunchKernelGGL(test_dct4_reg_kernel, dim3((count + 3) / 4), dim3(64), 0, ctx->stream, ctx->d_const.get(), i, count, 1, o);
+        hipLaunchKernelGGL(test_dct4_reg_kernel, dim3((count + 3) / 4), dim3(64), 0, ctx->stream.get(), ctx->ctx_const(), i, count, 1, o);
     });
 }
 int wrenc_gpu_test_dequantize_nb(wrenc_gpu_ctx* ctx, const int16_t* levels, int log2n, int nb, int o1, int count, int16_t* deq) {
     if (!ctx || !levels || !deq) return WRENC_GPU_EINVAL;
     if (const char* why = group_shape_error(log2n, nb, o1, kGroupMaxBlocks)) return fail(ctx, WRENC_GPU_EINVAL, why);
     return run_block_test(ctx, levels, log2n, count, deq, [&](int16_t* i, int16_t* o) {
-        hipLaunchKernelGGL(test_dequantize_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const.get(), i, log2n, nb, o1, o);
+        hipLaunchKernelGGL(test_dequantize_kernel, dim3(count), dim3(64), 0, ctx->stream.get(), ctx->ctx_const(), i, log2n, nb, o1, o);
     }, nb);
 }
 int wrenc_gpu_test_dequantize(wrenc_gpu_ctx* ctx, const int16_t* levels, int log2n, int count, int16_t* deq) {
@@ -2929,7 +2859,7 @@ int wrenc_gpu_test_quantize_nb(wrenc_gpu_ctx* ctx, const int16_t* coef, int log2
         HIP_TRY(ctx, d_cost.alloc((size_t)count));
         HIP_TRY(ctx, d_any.alloc((size_t)count));
         const int rc = run_block_test(ctx, coef, log2n, count, levels, [&](int16_t* i, int16_t* o) {
-            hipLaunchKernelGGL(test_quantize_kernel, dim3(count), dim3(64), 0, ctx->stream, ctx->d_const.get(), i, log2n, nb, o,
+            hipLaunchKernelGGL(test_quantize_kernel, dim3(count), dim3(64), 0, ctx->stream.get(), ctx->ctx_const(), i, log2n, nb, o,
                                d_cost.get(), d_any.get(), ctx->d_overflow.get() + 1);
         }, nb);
         if (rc) return rc;
@@ -2951,7 +2881,7 @@ int wrenc_gpu_test_quantize_p16(wrenc_gpu_ctx* ctx, const int16_t* coef, int cou
     return take_test_overflow(ctx, [&]() -> int {
         HIP_TRY(ctx, d_cost.alloc((size_t)count));
         const int rc = run_block_test(ctx, coef, 2, count, levels, [&](int16_t* i, int16_t* o) {
-            hipLaunchKernelGGL(test_quantize_p16_kernel, dim3((count + 3) / 4), dim3(64), 0, ctx->stream, ctx->d_const.get(), i, count, o,
+            hipLaunchKernelGGL(test_quantize_p16_kernel, dim3((count + 3) / 4), dim3(64), 0, ctx->stream.get(), ctx->ctx_const(), i, count, o,
                                d_cost.get(), ctx->d_overflow.get() + 1);
         });
         if (rc) return rc;
@@ -2975,10 +2905,10 @@ int wrenc_gpu_test_quantize_pk(wrenc_gpu_ctx* ctx, const int16_t* coef, int log2
         HIP_TRY(ctx, d_out.alloc(total));
         HIP_TRY(ctx, d_cost.alloc(n_costs));
         HIP_TRY(ctx, hipMemcpy(d_in.get(), coef, total * sizeof(int16_t), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(test_quantize_pk_kernel, dim3(n_packs), dim3(64), 0, ctx->stream, ctx->d_const.get(), d_in.get(), log2n, nc,
+        hipLaunchKernelGGL(test_quantize_pk_kernel, dim3(n_packs), dim3(64), 0, ctx->stream.get(), ctx->ctx_const(), d_in.get(), log2n, nc,
                            d_out.get(), d_cost.get(), ctx->d_overflow.get() + 1);
         HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream.get()));
         HIP_TRY(ctx, hipMemcpy(levels, d_out.get(), total * sizeof(int16_t), hipMemcpyDeviceToHost));
         HIP_TRY(ctx, hipMemcpy(level_cost, d_cost.get(), sizeof(long long) * n_costs, hipMemcpyDeviceToHost));
         return WRENC_GPU_OK;
@@ -3033,10 +2963,10 @@ int wrenc_gpu_test_predict(wrenc_gpu_ctx* ctx, const uint8_t* rec_y, const uint8
     HIP_TRY(ctx, d_out.alloc(total));
     HIP_TRY(ctx, d_items.alloc(dev_items.size()));
     HIP_TRY(ctx, hipMemcpy(d_items.get(), dev_items.data(), dev_items.size() * sizeof(int), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(test_predict_kernel, dim3(n_items), dim3(64), 0, ctx->stream, ctx->d_const.get(), d_planes.get(), d_items.get(),
+    hipLaunchKernelGGL(test_predict_kernel, dim3(n_items), dim3(64), 0, ctx->stream.get(), ctx->ctx_const(), d_planes.get(), d_items.get(),
                        d_scratch.get(), d_out.get());
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream.get()));
     HIP_TRY(ctx, hipMemcpy(out, d_out.get(), total, hipMemcpyDeviceToHost));
     return WRENC_GPU_OK;
 }

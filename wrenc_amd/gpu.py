@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = [
     "wrenc_gpu_format_from_name", "wrenc_gpu_format_name", "wrenc_gpu_format_layout",
     "wrenc_gpu_download_hashes", "wrenc_gpu_test_hash", "wrenc_gpu_last_hash_ms",
     "wrenc_gpu_download_rate_hist", "wrenc_gpu_rate_hist_bin", "wrenc_gpu_rate_hist_host",
+    "wrenc_gpu_test_plan",
 ]
 
 
@@ -130,6 +131,41 @@ def rate_hist_host(y, cb, cr):
     if rc:
         raise WrencGpuError(rc, "rate_hist_host(%d x %d)" % (w, h))
     return _hist_array(out, 1)[0]
+
+
+class PlanLaunch(C.Structure):
+    """wrenc_gpu_plan_launch"""
+    _fields_ = [(k, C.c_int32) for k in ("lane", "team", "diag", "r_min", "count", "first", "n", "grid", "group", "qp", "span")]
+    _fields_ += [("ctus", C.c_int64)]
+
+
+class PlanInfo(C.Structure):
+    """wrenc_gpu_plan_info"""
+    _fields_ = [(k, C.c_int32) for k in ("n_launches", "n_entries", "n_groups", "n_lanes", "n_spans", "schedule", "wpb", "team",
+                                         "encode_lanes", "team_below_pct", "team_below_pct_depth3")]
+
+
+def encode_plan(ctu_cols, ctu_rows, qps, schedule, wave_slots, depth3):
+    """wrenc_gpu_test_plan (host only, no device): the launch plan of an encode call as a dict of the info record's fields
+    plus "launches" (a list of dicts, the fields of wrenc_gpu_plan_launch), "entries" and "groups" ((qp, n_real) pairs)."""
+    lib = load_library()
+    q = (C.c_int * len(qps))(*[int(x) for x in qps])
+    info = PlanInfo()
+    lib.wrenc_gpu_test_plan.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    args = (int(ctu_cols), int(ctu_rows), q, len(qps), int(schedule), int(wave_slots), 1 if depth3 else 0, C.byref(info))
+    lib.wrenc_gpu_test_plan(*args, None, 0, None, 0, None, 0)       # the sizes (an error where the arguments are refused, below)
+    launches = (PlanLaunch * max(1, info.n_launches))()
+    entries = (C.c_int * max(1, info.n_entries))()
+    groups = (C.c_int * max(2, 2 * info.n_groups))()
+    rc = lib.wrenc_gpu_test_plan(*args, launches, info.n_launches, entries, info.n_entries, groups, info.n_groups)
+    if rc:
+        raise WrencGpuError(rc, "encode_plan(%d x %d CTUs, %d pictures)" % (ctu_cols, ctu_rows, len(qps)))
+    out = {k: getattr(info, k) for k, _ in PlanInfo._fields_}
+    out["launches"] = [{k: getattr(launches[i], k) for k, _ in PlanLaunch._fields_} for i in range(info.n_launches)]
+    out["entries"] = list(entries[:info.n_entries])
+    out["groups"] = [(groups[2 * i], groups[2 * i + 1]) for i in range(info.n_groups)]
+    return out
 
 
 def metrics_values(width, height, m):
