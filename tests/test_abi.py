@@ -11,8 +11,11 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+HEADERS = ("wrenc_gpu.h", "wrenc_gpu_test.h")     # the product's C ABI, and the block tests' (which includes the first)
+
+
 def _declared_symbols():
-    txt = open(os.path.join(ROOT, "include", "wrenc_gpu.h")).read()
+    txt = "".join(open(os.path.join(ROOT, "include", h)).read() for h in HEADERS)
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     return sorted(set(re.findall(r"\b(wrenc_gpu_[a-z0-9_]+)\s*\(", txt)))
 
@@ -25,6 +28,67 @@ def test_library_exports_every_declared_symbol(built):
     for name in declared:
         assert hasattr(lib, name), name
     assert sorted(gpu.EXPORTED_SYMBOLS) == declared
+
+
+def _c_class(decl):
+    """The class of a C parameter or return type as the prototype table must render it."""
+    decl = decl.strip()
+    if "*" in decl or "[" in decl:
+        return "pointer"
+    words = [w for w in re.findall(r"[A-Za-z_][A-Za-z_0-9]*", decl) if w not in ("const", "unsigned", "signed")]
+    for name, cls in (("void", "void"), ("size_t", "size_t"), ("double", "double"), ("float", "float")):
+        if words[0] == name:
+            return cls
+    if words[:2] == ["long", "long"]:
+        return "longlong"
+    assert words[0] == "int", decl
+    return "int"
+
+
+def _declarations():
+    """{function: (class of the return value, [class of each parameter])} of the two headers' C declarations."""
+    out = {}
+    for header in HEADERS:
+        txt = open(os.path.join(ROOT, "include", header)).read()
+        txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+        txt = re.sub(r"^\s*#.*$", "", txt, flags=re.M)
+        txt = re.sub(r"\b(typedef\s+)?(struct|enum)\b[^;{]*\{[^}]*\}[^;]*;", "", txt)
+        for stmt in txt.split(";"):
+            m = re.match(r"\s*(?:extern\s+\"C\"\s*\{)?\s*([^(]*?)\b(wrenc_gpu_[a-z0-9_]+)\s*\((.*)\)\s*$", stmt, flags=re.S)
+            if not m:
+                continue
+            ret, name, params = m.groups()
+            params = [p for p in params.split(",") if p.strip() != "void"]
+            assert name not in out, name
+            out[name] = (_c_class(ret), [_c_class(p) for p in params])
+    return out
+
+
+def test_prototype_table_matches_the_headers():
+    """wrenc_amd/gpu.py keeps ONE table of ctypes prototypes: every function the two headers declare is in it with the same
+    number of parameters and the same class of each parameter and of the return value (a pointer or array -> a pointer
+    type, int, size_t, long long, float, double, void), and nothing assigns a prototype outside the table's application."""
+    from wrenc_amd import gpu
+    pointers = (C.c_void_p, C.c_char_p)
+    classes = {"int": C.c_int, "size_t": C.c_size_t, "longlong": C.c_longlong, "float": C.c_float, "double": C.c_double, "void": None}
+
+    def same(cls, ctype):
+        if cls == "pointer":
+            return ctype in pointers or (isinstance(ctype, type) and issubclass(ctype, C._Pointer))
+        return ctype is classes[cls]
+
+    decls = _declarations()
+    assert sorted(decls) == sorted(gpu.PROTOTYPES) == sorted(gpu.EXPORTED_SYMBOLS)
+    for name, (ret, params) in decls.items():
+        restype, argtypes = gpu.PROTOTYPES[name]
+        assert same(ret, restype), (name, ret, restype)
+        assert len(argtypes) == len(params), (name, params, argtypes)
+        for i, (cls, ctype) in enumerate(zip(params, argtypes)):
+            assert same(cls, ctype), (name, i, cls, ctype)
+    src = open(os.path.join(ROOT, "wrenc_amd", "gpu.py")).read()
+    assert len(re.findall(r"\.argtypes\s*=", src)) == 1 and len(re.findall(r"\.restype\s*=", src)) == 1
+    assert re.search(r"for name, \(restype, argtypes\) in PROTOTYPES\.items\(\):\n +fn = getattr\(lib, name\)\n +fn\.restype = restype\n"
+                     r" +fn\.argtypes = argtypes\n", src)
 
 
 def test_default_config_matches_oracle_tables(built):

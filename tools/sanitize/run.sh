@@ -43,6 +43,10 @@ g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -fno-
 g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined \
     -o "$T/encode_plan" "$R/tools/sanitize/encode_plan.cpp"
 "$T/encode_plan"
+# the items of wrenc_gpu_test_predict (wrenc_amd/csrc/predict_items.h): the cases of tests/test_predict_layout.py and random items
+g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined \
+    -o "$T/predict_items" "$R/tools/sanitize/predict_items.cpp"
+"$T/predict_items"
 # the owners of device memory, streams and events (wrenc_amd/csrc/host_mem.h) against stub definitions of the HIP calls they
 # use: no HIP library
 g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined \

@@ -1,6 +1,7 @@
 // wrenc_gpu.hip -- kernels + C ABI (include/wrenc_gpu.h) of the MI355X all-intra
-// RD-search path.  Built for gfx950 only:
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -o libwrenc_gpu.so wrenc_gpu.hip
+// RD-search path.  Built for gfx950 only, together with the block tests' unit (wrenc_gpu_test.hip: the kernels and entries
+// of include/wrenc_gpu_test.h; a code object of its own, so nothing there reaches the code of the kernels here):
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -o libwrenc_gpu.so wrenc_gpu.hip wrenc_gpu_test.hip
 //
 // Scheduling: a picture's CTUs depend on their left, above-left, above and
 // above-right neighbours (encoder_context.rs:934-948), so CTU (r, c) can run once
@@ -9,26 +10,13 @@
 // between launches is the only synchronisation between CTUs.  (The one in-kernel
 // wait is a workgroup's acquire of a scratch region from a bitmap that always has
 // more regions than workgroups can be resident, see ctu_search_kernel.)
-#include "../../include/wrenc_gpu.h"
-#include "../../include/wrenc_scale.h"
-#include "../../include/wrenc_format.h"
-#include "../../include/wrenc_ratecurve.h"
-#include "wrenc_dev.h"
-
-#include <hip/hip_runtime.h>
-
-#include "encode_plan.h"
-#include "host_mem.h"
+#include "gpu_ctx.h"
 
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <memory>
 #include <new>
-#include <string>
-#include <vector>
-
-using namespace wrenc;
 
 // ---------------------------------------------------------------------------
 // kernels
@@ -184,15 +172,6 @@ __global__ __launch_bounds__(1024) void compact_levels_kernel(const PicBufs* __r
     if (threadIdx.x == 0) counts[blockIdx.x] = s_base;
 }
 
-// A mixed-QP encode call (wrenc_gpu_set_slot_qp) runs its pictures from a per-call list, ordered by QP and padded so that
-// every group of WPB consecutive entries holds ONE QP: load_tables fills the workgroup's LDS tables (lambda_q x dq_table)
-// with each thread reading its own wave's constant block, so a workgroup must never mix blocks.  Per group: the QP's
-// constant block and how many of its WPB entries are pictures (the rest are padding: same work, no stores).
-struct CallGroup {
-    const DevConst* k;
-    int n_real;
-};
-
 // Wave schedule: one workgroup = the same CTU of WPB consecutive pictures, one wave each.
 // D3: built for max-split-depth 3 (with the 4x4 leaves of split 8x8 CUs) or for the smaller depths (without)
 // groups: NULL for a call at one QP (block k); else the call's groups from this launch's first one (k unused).
@@ -271,386 +250,6 @@ __global__ __launch_bounds__(64 * WPB, 5) void ctu_search_team_kernel(const DevC
     if (ovf && LANE == 0) atomicOr(overflow, 1);
     if (SHT.lvb.pad_ && LANE == 0) atomicOr(overflow, 2); // a meeting point of the level schedule timed out
     release_scratch(slot_map, scratch_slot);
-}
-
-// building-block kernels: one wave per group of nb blocks of side 1 << lg, laid out [blk][y][x]; the transforms and the
-// dequantiser work on r1[o1 ..], where the search puts a pack's chroma behind its luma (the host entries check that the
-// group fits r1 and r2)
-__global__ __launch_bounds__(64) void test_fwd_dct_kernel(const DevConst* __restrict__ k,
-                                                          const int16_t* in, int lg, int nb, int o1, int16_t* out,
-                                                          int arm, int reps) {
-    Ctx c = {};
-    c.k = (const CONST_AS DevConst*)k;
-    const int total = nb << (2 * lg);
-    // arm: DCT_SEARCH, or the version of the 8x8 / 16x16 transforms the host names (dev_transform.h); reps repeats the
-    // transform of the same group for the micro-benchmark
-    for (int rep = 0; rep < reps; ++rep) {
-        for (int i = threadIdx.x; i < total; i += 64) SH.r1[o1 + i] = in[(size_t)blockIdx.x * total + i];
-        WSYNC();
-        if (arm == DCT_VDOT2)
-            fwd_dct_lg<DCT_VDOT2>(c, lg, nb, o1);
-        else if (arm == DCT_MFMA)
-            fwd_dct_lg<DCT_MFMA>(c, lg, nb, o1);
-        else
-            fwd_dct_lg(c, lg, nb, o1);
-    }
-    for (int i = threadIdx.x; i < total; i += 64) out[(size_t)blockIdx.x * total + i] = SH.r1[o1 + i];
-}
-
-// MFMA experiment: the 32x32 forward transform as i8 MFMAs (dev_transform.h); `reps` repeats the transform
-// of the same block in place for the micro-benchmark (the result of the last repetition is stored)
-__shared__ int32_t s_h32[33 * 32]; // the v_dot2 arm's i32 intermediate (the search kernel has no such room)
-__global__ __launch_bounds__(64) void test_fwd_dct32_kernel(const DevConst* __restrict__ k, const int16_t* in, int16_t* out,
-                                                           int mfma, int reps) {
-    Ctx c = {};
-    c.k = (const CONST_AS DevConst*)k;
-    for (int rep = 0; rep < reps; ++rep) {
-        for (int i = threadIdx.x; i < 1024; i += 64) SH.r1[i] = in[(size_t)blockIdx.x * 1024 + i];
-        WSYNC();
-        if (mfma)
-            fwd_dct32_mfma(c, 0);
-        else
-            fwd_dct<5, (int)sizeof(s_h32)>(c, 1, 0, (LDS_AS int32_t*)s_h32);
-    }
-    for (int i = threadIdx.x; i < 1024; i += 64) out[(size_t)blockIdx.x * 1024 + i] = SH.r1[i];
-}
-
-// the same for the inverse 32x32 transform: dequantised blocks in (row-major), residuals out
-__global__ __launch_bounds__(64) void test_inv_dct32_kernel(const DevConst* __restrict__ k, const int16_t* in, int16_t* out,
-                                                           int mfma, int reps) {
-    Ctx c = {};
-    c.k = (const CONST_AS DevConst*)k;
-    for (int rep = 0; rep < reps; ++rep) {
-        for (int i = threadIdx.x; i < 1024; i += 64) // transposed load: dT[x][i] = d[i][x]
-            ((int16_t*)SH.r2)[(i & 31) * 32 + (i >> 5)] = in[(size_t)blockIdx.x * 1024 + i];
-        WSYNC();
-        if (mfma)
-            inv_dct32_mfma(c, 0);
-        else
-            inv_dct<5>(c, 1, 0);
-    }
-    for (int i = threadIdx.x; i < 1024; i += 64) out[(size_t)blockIdx.x * 1024 + i] = SH.r1[i];
-}
-
-__global__ __launch_bounds__(64) void test_inv_dct_kernel(const DevConst* __restrict__ k,
-                                                          const int16_t* in, int lg, int nb, int o1, int16_t* out,
-                                                          int arm, int reps) {
-    Ctx c = {};
-    c.k = (const CONST_AS DevConst*)k;
-    const int n = 1 << lg, nn = n * n, total = nb * nn;
-    for (int rep = 0; rep < reps; ++rep) {
-        for (int i = threadIdx.x; i < total; i += 64) { // transposed load, block by block: dT[blk][x][i] = d[blk][i][x]
-            const int ii = i & (nn - 1);
-            ((int16_t*)SH.r2)[(i - ii) + (ii & (n - 1)) * n + (ii >> lg)] = in[(size_t)blockIdx.x * total + i];
-        }
-        WSYNC();
-        if (arm == DCT_VDOT2)
-            inv_dct_lg<DCT_VDOT2>(c, lg, nb, o1);
-        else if (arm == DCT_MFMA)
-            inv_dct_lg<DCT_MFMA>(c, lg, nb, o1);
-        else
-            inv_dct_lg(c, lg, nb, o1);
-    }
-    for (int i = threadIdx.x; i < total; i += 64) out[(size_t)blockIdx.x * total + i] = SH.r1[o1 + i];
-}
-
-// quantize_solo: nb = 1 (a luma block) or 2 (the Cb + Cr pair) blocks at r1[0 ..]; per group the summed level cost and the
-// *any_level the function reported
-__global__ __launch_bounds__(64) void test_quantize_kernel(const DevConst* __restrict__ k,
-                                                           const int16_t* in, int lg, int nb, int16_t* out,
-                                                           long long* cost, int* any_level, int* overflow) {
-    Ctx c = {};
-    c.k = (const CONST_AS DevConst*)k;
-    load_tables(c);
-    const int total = nb << (2 * lg);
-    for (int i = threadIdx.x; i < total; i += 64) SH.r1[i] = in[(size_t)blockIdx.x * total + i];
-    WSYNC();
-    int ovf = 0;
-    bool any = false;
-    const long long lc = quantize_solo(c, lg, nb, &ovf, &any);
-    for (int i = threadIdx.x; i < total; i += 64) out[(size_t)blockIdx.x * total + i] = SH.r1[i];
-    if (threadIdx.x == 0) {
-        cost[blockIdx.x] = lc;
-        any_level[blockIdx.x] = any ? 1 : 0;
-        if (ovf) atomicOr(overflow, 1);
-    }
-}
-
-// DevConst::head_rng against the functions it stands for, over every 16-bit coefficient (grid: 1024 blocks of 64 lanes;
-// block size and DC flag in blockIdx.y): out[0] += coefficients the range lets into the region that head_alpha ends it
-// at (never allowed), out[1] += coefficients the range ends the region at that head_alpha would let in (allowed, not
-// expected), out[2] += coefficients whose "quotient >= 2" differs from the range's, out[3] += alpha differences
-__global__ __launch_bounds__(64) void test_head_ranges_kernel(const DevConst* __restrict__ kk, int* out) {
-    Ctx c = {};
-    c.k = (const CONST_AS DevConst*)kk;
-    load_tables(c);
-    const CONST_AS DevConst* k = c.k;
-    const int lg = 2 + (int)(blockIdx.y >> 1);
-    const bool dcn = blockIdx.y & 1;
-    const int tc = (int)(blockIdx.x * 64 + threadIdx.x) - 32768;
-    const int sh = lg + 4, off = (1 << sh) >> 1;
-    const HeadK hk = head_consts(sh, off, k->lsc);
-    const HeadT ht = head_ranges(k, lg);
-    const int qd = quotient(k, tc, sh, off);
-    bool bad;
-    const int alpha = head_alpha(tc, qd, dcn, hk, &bad);
-    const bool rbad = head_bad(tc, dcn, ht);
-    if (bad && !rbad) atomicAdd(out + 0, 1);
-    if (!bad && rbad) atomicAdd(out + 1, 1);
-    if ((qd >= 2) != head_sig(tc, ht)) atomicAdd(out + 2, 1);
-    if (alpha != head_alpha1(tc, hk)) atomicAdd(out + 3, 1);
-}
-
-// DevConst::avail_tab + the picture's edges (block_avail_mask) against the formulas (block_avail_formula): one block per
-// thread -- blockIdx.x = CTU, threadIdx.x = 4x4 position, blockIdx.y = size -- for luma and chroma spacing; *out +=
-// differences
-__global__ __launch_bounds__(64) void test_avail_tab_kernel(const DevConst* __restrict__ kk, int* out) {
-    Ctx c = {};
-    c.k = (const CONST_AS DevConst*)kk;
-    c.W = kk->W;
-    c.ctu_x = 32 * (int)(blockIdx.x % (unsigned)kk->ctu_cols);
-    c.ctu_y = 32 * (int)(blockIdx.x / (unsigned)kk->ctu_cols);
-    const int lg = 2 + (int)blockIdx.y;
-    const int bx = 4 * (int)(threadIdx.x & 7), by = 4 * (int)(threadIdx.x >> 3);
-    if ((bx | by) & ((1 << lg) - 1)) return;
-    for (int st = 1; st <= 2; ++st)
-        if (block_avail_formula(c, bx, by, lg, st) != block_avail_mask(c, bx, by, lg, st)) atomicAdd(out, 1);
-    // what cclm_params reads off the mask
-    const int m = block_avail_mask(c, bx, by, lg, 1), tn = 1 << lg, gx = c.ctu_x + bx, gy = c.ctu_y + by;
-    if (above_right_avail(c, bx, by, lg) != (((m >> 4) & 1) != 0)) atomicAdd(out, 1);
-    if (below_left_avail(c, bx, by, lg) != ((m & 1) != 0)) atomicAdd(out, 1);
-    if (nb_avail(c, gx, gy, tn, gx - 1, gy, false, false) != (((m >> 1) & 1) != 0)) atomicAdd(out, 1);
-    if (nb_avail(c, gx, gy, tn, gx, gy - 1, false, false) != (((m >> 3) & 1) != 0)) atomicAdd(out, 1);
-}
-
-// quantize_p16_reg (the packed 4x4 leaf search's quantiser): each wave takes up to four consecutive 4x4 blocks
-__global__ __launch_bounds__(64) void test_quantize_p16_kernel(const DevConst* __restrict__ k, const int16_t* in, int count,
-                                                               int16_t* out, long long* cost, int* overflow) {
-    Ctx c = {};
-    c.k = (const CONST_AS DevConst*)k;
-    load_tables(c);
-    const int first = 4 * blockIdx.x;
-    const int nb = min(4, count - first);
-    const bool mine = threadIdx.x < 16 * nb;
-    int ovf = 0, any = 0;
-    long long lvl[4];
-    // the lane's coefficient in, the lane's level out
-    const int level = quantize_p16_reg(c, nb, mine ? (int)in[(size_t)first * 16 + threadIdx.x] : 0, &ovf, lvl, &any);
-    if (mine) out[(size_t)first * 16 + threadIdx.x] = (int16_t)level;
-    if (threadIdx.x == 0) {
-        for (int b = 0; b < nb; ++b) cost[first + b] = lvl[b];
-        if (ovf) atomicOr(overflow, 1);
-    }
-}
-
-// The register transforms of the 4x4 passes (dev_transform.h): four consecutive 4x4 blocks per wave, lane = (block,
-// sample); forward: residuals -> fwd_dct4_reg; inverse: levels -> dequantize4_lane -> inv_dct4_reg.  Every lane runs the
-// transform (rows past the last block carry zeros) and only the lanes of a block load and store.
-__global__ __launch_bounds__(64) void test_dct4_reg_kernel(const DevConst* __restrict__ k, const int16_t* in, int count, int inverse,
-                                                           int16_t* out) {
-    Ctx c = {};
-    c.k = (const CONST_AS DevConst*)k;
-    const size_t at = (size_t)blockIdx.x * 64 + threadIdx.x;
-    const bool mine = at < (size_t)count * 16;
-    const int v = mine ? (int)in[at] : 0;
-    const int r = inverse ? inv_dct4_reg(dequantize4_lane(c, v)) : fwd_dct4_reg(v);
-    if (mine) out[at] = (int16_t)r;
-}
-
-// quantize_pk (the packed leaf searches' quantiser): one wave per pack of nc candidates
-__global__ __launch_bounds__(64) void test_quantize_pk_kernel(const DevConst* __restrict__ k, const int16_t* in, int lgl, int nc,
-                                                              int16_t* out, long long* cost, int* overflow) {
-    Ctx c = {};
-    c.k = (const CONST_AS DevConst*)k;
-    load_tables(c);
-    const int total = nc * 3 * (1 << (2 * lgl)) / 2;
-    for (int i = threadIdx.x; i < total; i += 64) SH.r1[i] = in[(size_t)blockIdx.x * total + i];
-    WSYNC();
-    int ovf = 0;
-    bool any_y = false, any_c = false;
-    long long ly[3], lc[3];
-    if (lgl == 3)
-        quantize_pk<3>(c, nc, &ovf, ly, lc, &any_y, &any_c);
-    else
-        quantize_pk<4>(c, nc, &ovf, ly, lc, &any_y, &any_c);
-    for (int i = threadIdx.x; i < total; i += 64) out[(size_t)blockIdx.x * total + i] = SH.r1[i];
-    if (threadIdx.x == 0) {
-        for (int b = 0; b < nc; ++b) {
-            cost[((size_t)blockIdx.x * nc + b) * 2] = ly[b];
-            cost[((size_t)blockIdx.x * nc + b) * 2 + 1] = lc[b];
-        }
-        if (ovf) atomicOr(overflow, 1);
-    }
-}
-
-__global__ __launch_bounds__(64) void test_dequantize_kernel(const DevConst* __restrict__ k,
-                                                             const int16_t* in, int lg, int nb, int o1, int16_t* out) {
-    Ctx c = {};
-    c.k = (const CONST_AS DevConst*)k;
-    const int n = 1 << lg, nn = n * n, total = nb * nn;
-    for (int i = threadIdx.x; i < total; i += 64) SH.r1[o1 + i] = in[(size_t)blockIdx.x * total + i];
-    WSYNC();
-    dequantize_t(c, lg, nb, o1);
-    for (int i = threadIdx.x; i < total; i += 64) { // undo the transpose, block by block
-        const int ii = i & (nn - 1);
-        out[(size_t)blockIdx.x * total + i] = ((const int16_t*)SH.r2)[(i - ii) + (ii & (n - 1)) * n + (ii >> lg)];
-    }
-}
-
-// Prediction of single blocks in the environment of given reconstruction planes (one wave per item):
-// the CTU's reconstruction tile and border are loaded from the planes, then reference samples +
-// prediction run exactly as in a full evaluation of the final pass (prediction bytes to scratch).
-// item = {x, y (luma, picture), log2 luma size, comp (0 luma block, 1 Cb+Cr pair), mode, output offset}
-// comp 3 + comps (comps: bit 0 luma, bit 1 the chroma pair): a SAD LIST (sad_list_angular) of the block against its own samples
-// in the planes as "originals"; mode = m0 | entries << 8 | stride << 16, entry j = m0 + j * stride (kNoMode beyond 66); the
-// output is the 16 accumulators of lanes 0..15 (u32 each); comp 7: the CCLM SAD list of the chroma pair (mode 0), same output
-// comp 8 / 9: a FULL candidate (predict_full) of the luma block / the chroma pair into the recon tile, residuals against the
-// block's own samples in the planes as originals (a CTU tile of originals is staged for c.org, and stage_org_leaf runs for
-// blocks <= 16x16, as in the search); comp 10: the luma part of an 8x8 pack (predict_pack8_luma) into PRED_PARK, mode =
-// m0 | m1 << 8 | m2 << 16 | candidates << 24; comp 11: a 16x16 pack, luma and chroma pair (pack16_predict), into
-// PRED_PARK16, mode = m0 | m1 << 8 | candidates << 24 (a candidate mode of 255 = kNoMode rides along as zeros).  The output
-// is the prediction bytes read back from the destination, in the layout of the destination, then the i16 residuals of r1.
-constexpr int kTestPredictScratch = 1024 + kOrgTile; // per item: PRED_SCRATCH | the CTU's tile of originals
-__global__ __launch_bounds__(64) void test_predict_kernel(const DevConst* __restrict__ k, const uint8_t* planes,
-                                                          const int* items, uint8_t* scratch, uint8_t* out) {
-    const int* it = items + 6 * blockIdx.x;
-    const int x = it[0], y = it[1], tlg = it[2], comp = it[3], mode = it[4];
-    Ctx c = {};
-    c.k = (const CONST_AS DevConst*)k;
-    c.org = (const GLOBAL_AS uint8_t*)planes; // residuals are computed against these and ignored
-    c.W = k->W;
-    c.WH = k->W * k->H;
-    c.pred_scratch = scratch + (size_t)blockIdx.x * kTestPredictScratch;
-    c.ctu_x = x & ~31;
-    c.ctu_y = y & ~31;
-    c.write = 1;
-    load_tables(c);
-    const int W = c.W, Wc = W >> 1;
-    const GLOBAL_AS uint8_t* rec = (const GLOBAL_AS uint8_t*)planes;
-    for (int i = LANE; i < 72; i += 64) {
-        const int gx = c.ctu_x - 4 + i, gy = c.ctu_y - 1;
-        SH.recYtop[i] = (gx >= 0 && gx < W && gy >= 0) ? rec[(size_t)gy * W + gx] : 0;
-    }
-    for (int i = LANE; i < 32 * 36; i += 64) {
-        const int yy = i / 36, xx = i % 36 - 4;
-        const int gx = c.ctu_x + xx, gy = c.ctu_y + yy;
-        SH.recY[yy * 36 + xx + 4] = gx >= 0 ? rec[(size_t)gy * W + gx] : 0;
-    }
-    for (int pc = 1; pc < 3; ++pc) {
-        for (int i = LANE; i < 40; i += 64) {
-            const int gx = (c.ctu_x >> 1) - 4 + i, gy = (c.ctu_y >> 1) - 1;
-            SH.recCtop[pc - 1][i] = (gx >= 0 && gx < Wc && gy >= 0) ? rec[plane_off(c, pc) + (size_t)gy * Wc + gx] : 0;
-        }
-        for (int i = LANE; i < 16 * 20; i += 64) {
-            const int yy = i / 20, xx = i % 20 - 4;
-            const int gx = (c.ctu_x >> 1) + xx, gy = (c.ctu_y >> 1) + yy;
-            SH.recC[pc - 1][yy * 20 + xx + 4] = gx >= 0 ? rec[plane_off(c, pc) + (size_t)gy * Wc + gx] : 0;
-        }
-    }
-    WSYNC();
-    const int tx = x & 31, ty = y & 31;
-    if (comp == 2) {
-        // the packed predictor of the 4x4 leaf search: the item's mode in row 0, other modes in the rows next to it
-        build_refs(c, 0, tx, ty, 2);
-        const int row = LANE >> 4;
-        const int v = predict4_lane(c, row == 0 ? mode : (mode + 1 + 22 * row) % 67);
-        if (LANE < 16) out[it[5] + LANE] = (uint8_t)v;
-        return;
-    }
-    if (comp == 7) { // the CCLM SAD list of the chroma pair (sad_list_cclm): lanes 0..2 = LT_CCLM, T_CCLM, L_CCLM
-        uint8_t* oc = (uint8_t*)SH.r2 + org_byte(1, tlg);
-        const int nc = 1 << (tlg - 1);
-        for (int i = LANE; i < 2 * nc * nc; i += 64) {
-            const int pl = i >= nc * nc ? 1 : 0, ii = i - pl * nc * nc;
-            oc[i] = rec[plane_off(c, 1 + pl) + (size_t)((y >> 1) + ii / nc) * Wc + (x >> 1) + ii % nc];
-        }
-        WSYNC();
-        const unsigned acc = sad_list_cclm(c, tx, ty, tlg);
-        if (LANE < 16) ((uint32_t*)(out + it[5]))[LANE] = acc;
-        return;
-    }
-    if (comp >= 4 && comp < 8) {
-        const int comps = comp - 3, m0 = mode & 255, nm = (mode >> 8) & 255, stride = mode >> 16;
-        // the originals where a SAD list reads them (stage_org / stage_org_leaf's layout): luma, then Cb | Cr
-        uint8_t* ol = (uint8_t*)SH.r2 + org_byte(0, tlg);
-        uint8_t* oc = (uint8_t*)SH.r2 + org_byte(1, tlg);
-        const int n = 1 << tlg, nc = n >> 1;
-        for (int i = LANE; i < n * n; i += 64) ol[i] = rec[(size_t)(y + (i >> tlg)) * W + x + (i & (n - 1))];
-        if (comps & 2)
-            for (int i = LANE; i < 2 * nc * nc; i += 64) {
-                const int pl = i >= nc * nc ? 1 : 0, ii = i - pl * nc * nc;
-                oc[i] = rec[plane_off(c, 1 + pl) + (size_t)((y >> 1) + ii / nc) * Wc + (x >> 1) + ii % nc];
-            }
-        WSYNC();
-        if (comps & 1) build_refs(c, 0, tx, ty, tlg);
-        if (comps & 2) build_refs(c, 1, tx, ty, tlg);
-        unsigned long long lo = 0, hi = 0;
-        for (int j = 0; j < nm; ++j) {
-            const int m = m0 + j * stride;
-            const unsigned long long e = (unsigned long long)(m <= 66 ? m : kNoMode) << (8 * (j & 7));
-            if (j < 8) lo |= e; else hi |= e;
-        }
-        const unsigned acc = sad_list_angular(c, comps, tx, ty, tlg, nm, lo, hi);
-        if (LANE < 16) ((uint32_t*)(out + it[5]))[LANE] = acc;
-        return;
-    }
-    if (comp >= 8) {
-        // the CTU's originals as retile_kernel lays them out: Y 32x32 | Cb 16x16 | Cr 16x16 (samples outside the picture: 0)
-        uint8_t* tile = c.pred_scratch + 1024;
-        for (int i = LANE; i < kOrgTile; i += 64) {
-            const int pc = i < 1024 ? 0 : 1 + ((i - 1024) >> 8);
-            const int ii = pc ? (i - 1024) & 255 : i;
-            const int lgw = pc ? 4 : 5;
-            const int gx = (pc ? c.ctu_x >> 1 : c.ctu_x) + (ii & ((1 << lgw) - 1)), gy = (pc ? c.ctu_y >> 1 : c.ctu_y) + (ii >> lgw);
-            const int pw = pc ? Wc : W, ph = pc ? k->H >> 1 : k->H;
-            tile[i] = (gx < pw && gy < ph) ? rec[plane_off(c, pc) + (size_t)gy * pw + gx] : 0;
-        }
-        __threadfence_block();
-        WSYNC();
-        c.org = (const GLOBAL_AS uint8_t*)tile;
-        const int comps = comp == 8 ? 1 : (comp == 9 ? 2 : (comp == 10 ? 1 : 3));
-        if (tlg <= 4) stage_org_leaf(c, comps, tx, ty, tlg);
-        uint8_t* op = out + it[5];
-        if (comp <= 9) {
-            const int cmp = comp - 8;
-            if (mode < LT_CCLM) build_refs(c, cmp, tx, ty, tlg);
-            predict_full(c, cmp, tx, ty, tlg, mode, 0, PRED_TILE);
-            const int lg = tlg - cmp, n = 1 << lg, total = (cmp ? 2 : 1) * n * n;
-            for (int i = LANE; i < total; i += 64) {
-                const int blk = i >> (2 * lg), ii = i & (n * n - 1);
-                op[i] = (uint8_t)rec_get(cmp + blk, (tx >> cmp) + (ii & (n - 1)), (ty >> cmp) + (ii >> lg));
-                ((int16_t*)(op + total))[i] = SH.r1[i];
-            }
-            return;
-        }
-        const int nc = mode >> 24, m0 = mode & 255, m1 = (mode >> 8) & 255, m2 = (mode >> 16) & 255;
-        if (comp == 10) {
-            build_refs(c, 0, tx, ty, 3);
-            predict_pack8_luma(c, nc, m0, m1, m2);
-            WSYNC();
-            const uint8_t* park = (const uint8_t*)SH.decw + kParkByte;
-            for (int i = LANE; i < 64 * nc; i += 64) {
-                op[i] = park[i];
-                ((int16_t*)(op + 64 * nc))[i] = SH.r1[i];
-            }
-            return;
-        }
-        build_refs(c, 0, tx, ty, 4);
-        build_refs(c, 1, tx, ty, 4);
-        pack16_predict(c, tx, ty, nc, m0, m1);
-        WSYNC();
-        for (int i = LANE; i < 384 * nc; i += 64) {
-            op[i] = *park16(i, 256 * nc);
-            ((int16_t*)(op + 384 * nc))[i] = SH.r1[i];
-        }
-        return;
-    }
-    if (mode < LT_CCLM) build_refs(c, comp, tx, ty, tlg);
-    predict_full(c, comp, tx, ty, tlg, mode, 0, PRED_SCRATCH);
-    const int n = 1 << (tlg - (comp ? 1 : 0));
-    const int total = (comp ? 2 : 1) * n * n;
-    __threadfence_block();
-    for (int i = LANE; i < total; i += 64) out[it[5] + i] = c.pred_scratch[i];
 }
 
 // ---------------------------------------------------------------------------
@@ -757,118 +356,7 @@ static_assert(scan_closed_form_holds(), "dev_scan.h: the closed form differs fro
 
 } // namespace
 
-struct wrenc_gpu_ctx {
-    wrenc_gpu_config cfg;
-    long long wave_slots = 0;                  // waves of the search kernel the device holds at once
-    long long device_wave_slots = 0;           // (wave_slots can be overridden by a test: wrenc_gpu_test_set_wave_slots)
-    // Device memory, streams and events belong to DevBuf, HipStream and HipEvent members (host_mem.h): `delete ctx`
-    // releases them, wrenc_gpu_destroy lists none of them.
-    HipStream stream;                          // lane 0 of the encode; timing events
-    HipStream copy_stream;                     // uploads and downloads: they overlap the search of other slots
-    HipEvent ev_uploaded;                      // end of the uploads an encode call has to wait for
-    bool uploads_pending = false;
-    std::vector<HipEvent> enc_events;          // ring: one "this encode call is done" event per call in flight
-    size_t enc_event_next = 0;
-    std::vector<hipEvent_t> slot_event;        // per slot: the event (of enc_events) of the encode call that last searched it
-    std::vector<HipStream> lanes;              // extra encode lanes (pictures are independent)
-    std::vector<HipEvent> lane_done;
-    HipEvent ev_fork;
-    hipEvent_t last_done = nullptr;            // completion event (of enc_events) of the most recent encode call
-    // One constant block per QP in use: the context's from wrenc_gpu_create, the others from wrenc_gpu_set_slot_qp on first
-    // use.  A block is never changed or freed while the context lives (a call in flight may read it); the lambdas it was
-    // built from are what a later config for the same QP must repeat.
-    struct QpConst {
-        DevBuf<DevConst> d;
-        int64_t lambda_q = 0;
-        float lambda_rd = 0.f, lambda_rd_chroma = 0.f;
-    };
-    QpConst qconst[64];
-    const DevConst* ctx_const() const { return qconst[cfg.qp].d.get(); }
-    // per-picture QP (wrenc_gpu_set_slot_qp): the QP of every slot; per encode call in flight (ring of enc_events), the
-    // call's picture list and its groups (grown on demand), host copy kept until the call is done
-    std::vector<int> slot_qp;
-    struct CallList {
-        DevBuf<PicBufs> d_pics;
-        DevBuf<CallGroup> d_groups;             // (one per WPB entries of d_pics)
-        std::vector<PicBufs> pics;
-        std::vector<CallGroup> groups;
-    };
-    std::vector<CallList> call_lists;
-    // what a slot's PicBufs points into: Y | Cb | Cr as one slab each for originals, reconstruction and levels
-    struct SlotMem {
-        DevBuf<uint8_t> org, org_t, border, rec;
-        DevBuf<int16_t> lev;
-        DevBuf<uint32_t> lev_dirty;
-        DevBuf<uint8_t> cu_log2, luma_mode, chroma_mode;
-        DevBuf<float> ctu_cost;
-    };
-    std::vector<SlotMem> slot_mem;
-    DevBuf<PicBufs> d_slots;
-    std::vector<PicBufs> slots;
-    std::vector<int> state; // 0 empty, 1 uploaded, 2 encoded
-    // the size of the caller's pictures (wrenc_gpu_set_visible_size); the coded size unless one is set
-    int vis_w = 0, vis_h = 0;
-    bool any_upload = false;
-    // a scaling context (wrenc_gpu_set_source_size): the size of the caller's pictures (0: none set, the visible size), the
-    // staging planes the upload copies them into (one set per context: copies, scaler, pad and retile of every slot run
-    // on copy_stream, in order, so a picture is scaled out of them before the next one is copied in), the filter's tables
-    // (one allocation) and the kernel's arguments but for the slot
-    int src_w = 0, src_h = 0;
-    DevBuf<uint8_t> d_stage, d_scale_tab;
-    ScaleArgs scale_args = {};
-    // the format of the caller's pictures (wrenc_gpu_set_source_format; 0: planar 8-bit 4:2:0, the plain upload) and the raw
-    // staging planes wrenc_gpu_upload_planes copies them into as they come: one set per context, like the scaler's and by
-    // the same argument, allocated when the format is set or, where the sizes came later, at the first upload
-    int src_format = 0;
-    DevBuf<uint8_t> d_raw;
-    DevBuf<unsigned long long> d_mismatch;
-    DevBuf<int> d_overflow;
-    // made by the first encode call, both or neither:
-    DevBuf<uint8_t> d_pred_scratch; // kScratchSlots x WPB x kWaveScratch: saved reconstructions (dev_search.h copy_block)
-    DevBuf<unsigned long long> d_slot_map; // kScratchSlots bits: scratch regions in use
-    HipEvent ev_begin, ev_end;
-    std::vector<HipEvent> ev_pool;             // two per span of the plan (encode_plan.h): around a lane's launches of a diagonal
-    Plan plan;                                 // of the most recent encode call; its vectors are reused from call to call
-    std::vector<int> call_qp;                  // ... and the QPs of its pictures, what the plan was made from
-    bool stats_enabled = false; // per-launch timing events: bench / profiling only (wrenc_gpu_stats_enable)
-    // Per-call scratch of the read-backs that wait for the search, grown on demand: each call asks its buffers for what
-    // its pictures need (DevBuf::grow), and a buffer that is large enough stays.
-    // compact read-back: masks, payloads with room for every block, counts
-    DevBuf<uint32_t> d_cmask;
-    DevBuf<int16_t> d_cpayload;
-    DevBuf<unsigned> d_ccount;
-    // token read-back: the page pool of one call, its allocation counter, the CTUs' first pages
-    DevBuf<uint32_t> d_tok_pool;
-    DevBuf<unsigned> d_tok_counter;
-    DevBuf<uint32_t> d_tok_first;
-    // metrics read-back: the waves' partial sums of one call and the pictures' totals
-    DevBuf<MetricsPartial> d_mpartial;
-    DevBuf<MetricsSums> d_msums;
-    // hash read-back (made on first use: a context that never asks launches and allocates what it always did): a stream
-    // of its own -- an MD5 pass is long, and on the copy stream it would stand in front of the next batch's uploads --,
-    // the CRC's tables, the waves' partials of one call and the pictures' values, grown on demand
-    HipStream hash_stream;
-    DevBuf<HashTables> d_htables;
-    DevBuf<uint32_t> d_hpartial;
-    DevBuf<wrenc_picture_hash> d_hvalues;
-    HipEvent hash_ev[2];                        // measurement mode (stats_enabled): around the last hash pass
-    bool hash_timed = false;
-    // complexity read-back: the waves' triples, the pictures' totals and CTU maps of one call, for every slot at once
-    // (allocated on first use and never again: a later call must not free device memory under a search in flight)
-    DevBuf<ComplexityPartial> d_xpartial, d_xsums;
-    DevBuf<uint32_t> d_xmap;
-    // rate histogram read-back: the waves' counts of one call and the pictures' tables, for every slot at once (allocated
-    // on first use and never again, as the complexity scratch)
-    DevBuf<RateHistPartial> d_rpartial;
-    DevBuf<RateHistCounts> d_rsums;
-    int schedule = WRENC_GPU_SCHEDULE_AUTO;
-    bool stats_valid = false;
-    std::string err;
-    int ctu_cols = 0, ctu_rows = 0;
-};
-
-namespace {
-
+// (gpu_ctx.h: shared with the block tests' unit)
 int fail(wrenc_gpu_ctx* ctx, int code, const std::string& msg) {
     if (ctx)
         ctx->err = msg;
@@ -877,21 +365,12 @@ int fail(wrenc_gpu_ctx* ctx, int code, const std::string& msg) {
     return code;
 }
 
-// returns WRENC_GPU_EHIP where `expr` fails.  HIP's last error is cleared then, so that the next call's launch check
-// (hipGetLastError) does not report this failure as its own; what the caller holds in DevBufs is freed by the return.
-#define HIP_TRY(ctx, expr)                                                                        \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            (void)hipGetLastError();                                                              \
-            return fail(ctx, WRENC_GPU_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-        }                                                                                         \
-    } while (0)
-
 size_t plane_bytes(const wrenc_gpu_config& c, int comp, size_t elem) {
     const size_t w = comp ? c.width / 2 : c.width, h = comp ? c.height / 2 : c.height;
     return w * h * elem;
 }
+
+namespace {
 
 // ---- the steps the read-back entry points share (wrenc_gpu_sync, wrenc_gpu_download, _download_compact, _download_tokens) ----
 
@@ -1100,6 +579,9 @@ void fill_split_floors(const wrenc_gpu_config& cfg, DevConst& k) {
     k.cand_floor_ang = ang;
 }
 
+} // namespace
+
+// (gpu_ctx.h: the block tests read a config's constants too)
 void fill_dev_const(const wrenc_gpu_config& cfg, DevConst& k) {
     memset(&k, 0, sizeof(k));
     fill_split_floors(cfg, k);
@@ -1222,76 +704,68 @@ void fill_dev_const(const wrenc_gpu_config& cfg, DevConst& k) {
     fill_avail_tab(k);
 }
 
-} // namespace
+// the metrics pass over n pictures of `slots` from `first` on, on `st`: the waves' partial sums, then the pictures' totals
+// (maps: the test entry's per-window values, else NULL)
+// vw x vh: the rectangle that is measured, the coded size or a context's visible size (the window variant of the kernel)
+hipError_t launch_metrics(const wrenc_gpu_config& c, int vw, int vh, hipStream_t st, const PicBufs* slots, int first, int n,
+                          MetricsPartial* partials, MetricsSums* sums, float* maps) {
+    const int per_pic = met_plane(vw, vh, 0).waves + 2 * met_plane(vw, vh, 1).waves;
+    const long long waves = (long long)n * per_pic;
+    const dim3 grid((unsigned)((waves + 3) / 4));
+    if ((vw != c.width || vh != c.height) && maps) return hipErrorInvalidValue; // the window variant stores no maps
+    if (vw != c.width || vh != c.height)
+        hipLaunchKernelGGL((metrics_kernel<false, true>), grid, dim3(256), 0, st, slots, first, n, c.width, c.height, vw, vh, partials, maps);
+    else if (maps)
+        hipLaunchKernelGGL((metrics_kernel<true, false>), grid, dim3(256), 0, st, slots, first, n, c.width, c.height, vw, vh, partials, maps);
+    else
+        hipLaunchKernelGGL((metrics_kernel<false, false>), grid, dim3(256), 0, st, slots, first, n, c.width, c.height, vw, vh, partials, maps);
+    hipLaunchKernelGGL(metrics_finish_kernel, dim3(n), dim3(64), 0, st, partials, vw, vh, sums);
+    return hipGetLastError();
+}
 
-namespace {
-// `count` groups of `nb` blocks to the device, launch(d_in, d_out) on the context's stream, as many blocks back.
-// kernel_ms: NULL, or where the HIP-event duration of what `launch` queued goes (the 32x32 micro-benchmark)
-template <class Launch>
-int run_block_test(wrenc_gpu_ctx* ctx, const int16_t* in, int log2n, int count, int16_t* out, Launch launch, int nb = 1,
-                   float* kernel_ms = nullptr) {
-    if (!ctx || !in || !out) return WRENC_GPU_EINVAL;
-    if (log2n < 2 || log2n > 5 || count < 1 || nb < 1) return fail(ctx, WRENC_GPU_EINVAL, "log2n must be 2..5 and count >= 1");
-    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-    const size_t n = (size_t)count * nb << (2 * log2n);
-    HipEvent e0, e1;
-    DevBuf<int16_t> d_in, d_out;
-    HIP_TRY(ctx, d_in.alloc(n));
-    HIP_TRY(ctx, d_out.alloc(n));
-    if (kernel_ms) {
-        *kernel_ms = 0.f;
-        HIP_TRY(ctx, e0.create());
-        HIP_TRY(ctx, e1.create());
+void fill_metrics(int vw, int vh, const MetricsSums& s, wrenc_gpu_metrics& m) {
+    for (int p = 0; p < 3; ++p) {
+        m.sse[p] = s.sse[p];
+        m.ssim_sum[p] = s.ssim[p];
+        m.ssim_windows[p] = (uint32_t)met_plane(vw, vh, p ? 1 : 0).windows;
     }
-    HIP_TRY(ctx, hipMemcpyAsync(d_in.get(), in, n * sizeof(int16_t), hipMemcpyHostToDevice, ctx->stream.get()));
-    if (kernel_ms) HIP_TRY(ctx, hipEventRecord(e0.get(), ctx->stream.get()));
-    launch(d_in.get(), d_out.get());
-    HIP_TRY(ctx, hipGetLastError());
-    if (kernel_ms) HIP_TRY(ctx, hipEventRecord(e1.get(), ctx->stream.get()));
-    HIP_TRY(ctx, hipMemcpyAsync(out, d_out.get(), n * sizeof(int16_t), hipMemcpyDeviceToHost, ctx->stream.get()));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream.get()));
-    if (kernel_ms) HIP_TRY(ctx, hipEventElapsedTime(kernel_ms, e0.get(), e1.get()));
-    return WRENC_GPU_OK;
 }
 
-// A picture of a test entry's own (never a slot of the context): up to two sets of three planes of the context's size, Y |
-// Cb | Cr as one slab each like a slot's, in `slab`.  `pic`: NULL, or where the device's PicBufs of it goes.
-int load_test_picture(wrenc_gpu_ctx* ctx, const uint8_t* const org[3], const uint8_t* const rec[3], DevBuf<uint8_t>& slab,
-                      DevBuf<PicBufs>* pic) {
-    const wrenc_gpu_config& c = ctx->cfg;
-    const size_t wh = (size_t)c.width * c.height;
-    HIP_TRY(ctx, slab.alloc(((org ? 1 : 0) + (rec ? 1 : 0)) * (wh + wh / 2)));
-    PicBufs pb = {};
-    uint8_t* at = slab.get();
-    for (int p = 0; p < 6; ++p) {
-        const uint8_t* const* from = p < 3 ? org : rec;
-        if (!from) continue;
-        const int comp = p % 3;
-        if (p < 3) pb.org[comp] = at; else pb.rec[comp] = at;
-        HIP_TRY(ctx, hipMemcpy(at, from[comp], plane_bytes(c, comp, 1), hipMemcpyHostToDevice));
-        at += plane_bytes(c, comp, 1);
+// the hash pass over n pictures of `slots` from `first` on, on `st` (dev_hash.h): an MD5 lane per plane, or the waves'
+// partials and the finish; `tables` is read by the CRC only
+hipError_t launch_hashes(const wrenc_gpu_config& c, hipStream_t st, const PicBufs* slots, int first, int n, int hash_type,
+                         const HashTables* tables, uint32_t* partials, wrenc_picture_hash* values) {
+    if (hash_type == WRENC_HASH_MD5) {
+        hipLaunchKernelGGL(hash_md5_kernel, dim3((unsigned)md5_waves(n)), dim3(64), 0, st, slots, first, n, c.width, c.height, values);
+        return hipGetLastError();
     }
-    if (!pic) return WRENC_GPU_OK;
-    HIP_TRY(ctx, pic->alloc(1));
-    HIP_TRY(ctx, hipMemcpy(pic->get(), &pb, sizeof(pb), hipMemcpyHostToDevice));
-    return WRENC_GPU_OK;
+    const HashPlane L = hash_plane(c.width, c.height, 0), C = hash_plane(c.width, c.height, 1);
+    const long long waves = (long long)n * (L.pieces + 2 * C.pieces);
+    // a workgroup of the CRC pass copies the tables to LDS first: few enough workgroups that each takes many pieces
+    const long long groups = (waves + 3) / 4;
+    const dim3 grid((unsigned)(groups < 2048 ? groups : 2048));
+    const uint32_t start_l = hash_crc_start_term(L.bytes), start_c = hash_crc_start_term(C.bytes);
+    if (hash_type == WRENC_HASH_CRC) {
+        hipLaunchKernelGGL(hash_piece_kernel<true>, grid, dim3(256), 0, st, slots, first, n, c.width, c.height, tables, partials);
+        hipLaunchKernelGGL(hash_finish_kernel<true>, dim3((unsigned)n, 3), dim3(64), 0, st, partials, c.width, c.height, tables, start_l, start_c, values);
+    } else {
+        hipLaunchKernelGGL(hash_piece_kernel<false>, grid, dim3(256), 0, st, slots, first, n, c.width, c.height, tables, partials);
+        hipLaunchKernelGGL(hash_finish_kernel<false>, dim3((unsigned)n, 3), dim3(64), 0, st, partials, c.width, c.height, tables, start_l, start_c, values);
+    }
+    return hipGetLastError();
 }
 
-// the quantiser test entries' own overflow word (d_overflow[1]), read once the entry's kernel has finished and cleared
-// again whatever `rc`, the entry's status so far, is: the call that raised it fails with WRENC_GPU_ELEVEL -- or with the
-// earlier failure `rc` names --, and the next call on the context starts clean either way
-// (include/wrenc_gpu.h: "keep a word of their own and never poison a context")
-int take_test_overflow(wrenc_gpu_ctx* ctx, int rc) {
-    int ovf = 0;
-    hipError_t e = hipMemcpyAsync(&ovf, ctx->d_overflow.get() + 1, sizeof(int), hipMemcpyDeviceToHost, ctx->stream.get());
-    if (e == hipSuccess) e = hipMemsetAsync(ctx->d_overflow.get() + 1, 0, sizeof(int), ctx->stream.get());
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream.get());
-    if (rc != WRENC_GPU_OK) return rc;
-    if (e != hipSuccess) return fail(ctx, WRENC_GPU_EHIP, hipGetErrorString(e));
-    if (!ovf) return WRENC_GPU_OK;
-    return fail(ctx, WRENC_GPU_ELEVEL, "a quantised level reached 1024 (reference panics: block_splitter.rs:453)");
+size_t hash_partials(const wrenc_gpu_config& c) {
+    return (size_t)hash_plane(c.width, c.height, 0).pieces + 2 * (size_t)hash_plane(c.width, c.height, 1).pieces;
 }
-} // namespace
+
+// the CRC's tables, in place before anything queued on `st` after this call reads them
+static hipError_t upload_hash_tables(HashTables* d_tables, hipStream_t st) {
+    HashTables t;
+    hash_fill_tables(t);
+    const hipError_t e = hipMemcpyAsync(d_tables, &t, sizeof(t), hipMemcpyHostToDevice, st);
+    return e != hipSuccess ? e : hipStreamSynchronize(st);
+}
 
 extern "C" {
 
@@ -2203,33 +1677,6 @@ int wrenc_gpu_download_tokens(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_g
     return WRENC_GPU_OK;
 }
 
-// the metrics pass over n pictures of `slots` from `first` on, on `st`: the waves' partial sums, then the pictures' totals
-// (maps: the test entry's per-window values, else NULL)
-// vw x vh: the rectangle that is measured, the coded size or a context's visible size (the window variant of the kernel)
-static hipError_t launch_metrics(const wrenc_gpu_config& c, int vw, int vh, hipStream_t st, const PicBufs* slots, int first, int n,
-                                 MetricsPartial* partials, MetricsSums* sums, float* maps) {
-    const int per_pic = met_plane(vw, vh, 0).waves + 2 * met_plane(vw, vh, 1).waves;
-    const long long waves = (long long)n * per_pic;
-    const dim3 grid((unsigned)((waves + 3) / 4));
-    if ((vw != c.width || vh != c.height) && maps) return hipErrorInvalidValue; // the window variant stores no maps
-    if (vw != c.width || vh != c.height)
-        hipLaunchKernelGGL((metrics_kernel<false, true>), grid, dim3(256), 0, st, slots, first, n, c.width, c.height, vw, vh, partials, maps);
-    else if (maps)
-        hipLaunchKernelGGL((metrics_kernel<true, false>), grid, dim3(256), 0, st, slots, first, n, c.width, c.height, vw, vh, partials, maps);
-    else
-        hipLaunchKernelGGL((metrics_kernel<false, false>), grid, dim3(256), 0, st, slots, first, n, c.width, c.height, vw, vh, partials, maps);
-    hipLaunchKernelGGL(metrics_finish_kernel, dim3(n), dim3(64), 0, st, partials, vw, vh, sums);
-    return hipGetLastError();
-}
-
-static void fill_metrics(int vw, int vh, const MetricsSums& s, wrenc_gpu_metrics& m) {
-    for (int p = 0; p < 3; ++p) {
-        m.sse[p] = s.sse[p];
-        m.ssim_sum[p] = s.ssim[p];
-        m.ssim_windows[p] = (uint32_t)met_plane(vw, vh, p ? 1 : 0).windows;
-    }
-}
-
 int wrenc_gpu_download_metrics(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_gpu_metrics* out) {
     if (!ctx || !out) return WRENC_GPU_EINVAL;
     if (const int rc = check_slots(ctx, first_slot, n, 2, "slot range out of bounds")) return rc;
@@ -2323,75 +1770,6 @@ void wrenc_gpu_metrics_values(int width, int height, const wrenc_gpu_metrics* m,
     ssim[0] = (4.0 * ssim[1] + ssim[2] + ssim[3]) / 6.0;
 }
 
-int wrenc_gpu_test_metrics(wrenc_gpu_ctx* ctx, const uint8_t* const org[3], const uint8_t* const rec[3], wrenc_gpu_metrics* out,
-                           float* const ssim_map[3]) {
-    if (!ctx || !org || !rec || !out) return WRENC_GPU_EINVAL;
-    for (int p = 0; p < 3; ++p)
-        if (!org[p] || !rec[p]) return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_test_metrics: null plane");
-    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-    const wrenc_gpu_config& c = ctx->cfg;
-    const MetPlane L = met_plane(c.width, c.height, 0), C = met_plane(c.width, c.height, 1);
-    const size_t n_win = (size_t)L.windows + 2 * (size_t)C.windows;
-    DevBuf<uint8_t> d_planes;
-    DevBuf<PicBufs> d_pic;
-    DevBuf<MetricsPartial> d_part;
-    DevBuf<MetricsSums> d_sums;
-    DevBuf<float> d_map;
-    MetricsSums sums = {};
-    std::vector<float> map(ssim_map ? n_win : 0);
-    if (const int rc = load_test_picture(ctx, org, rec, d_planes, &d_pic)) return rc;
-    HIP_TRY(ctx, d_part.alloc((size_t)(L.waves + 2 * C.waves)));
-    HIP_TRY(ctx, d_sums.alloc(1));
-    if (ssim_map) HIP_TRY(ctx, d_map.alloc(n_win));
-    HIP_TRY(ctx, launch_metrics(c, c.width, c.height, 0, d_pic.get(), 0, 1, d_part.get(), d_sums.get(), d_map.get()));
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    HIP_TRY(ctx, hipMemcpy(&sums, d_sums.get(), sizeof(sums), hipMemcpyDeviceToHost));
-    if (ssim_map) HIP_TRY(ctx, hipMemcpy(map.data(), d_map.get(), n_win * sizeof(float), hipMemcpyDeviceToHost));
-    fill_metrics(c.width, c.height, sums, *out);
-    if (ssim_map) {
-        const size_t at[3] = {0, (size_t)L.windows, (size_t)L.windows + (size_t)C.windows};
-        for (int p = 0; p < 3; ++p)
-            if (ssim_map[p]) memcpy(ssim_map[p], map.data() + at[p], (size_t)(p ? C.windows : L.windows) * sizeof(float));
-    }
-    return WRENC_GPU_OK;
-}
-
-// the hash pass over n pictures of `slots` from `first` on, on `st` (dev_hash.h): an MD5 lane per plane, or the waves'
-// partials and the finish; `tables` is read by the CRC only
-static hipError_t launch_hashes(const wrenc_gpu_config& c, hipStream_t st, const PicBufs* slots, int first, int n, int hash_type,
-                                const HashTables* tables, uint32_t* partials, wrenc_picture_hash* values) {
-    if (hash_type == WRENC_HASH_MD5) {
-        hipLaunchKernelGGL(hash_md5_kernel, dim3((unsigned)md5_waves(n)), dim3(64), 0, st, slots, first, n, c.width, c.height, values);
-        return hipGetLastError();
-    }
-    const HashPlane L = hash_plane(c.width, c.height, 0), C = hash_plane(c.width, c.height, 1);
-    const long long waves = (long long)n * (L.pieces + 2 * C.pieces);
-    // a workgroup of the CRC pass copies the tables to LDS first: few enough workgroups that each takes many pieces
-    const long long groups = (waves + 3) / 4;
-    const dim3 grid((unsigned)(groups < 2048 ? groups : 2048));
-    const uint32_t start_l = hash_crc_start_term(L.bytes), start_c = hash_crc_start_term(C.bytes);
-    if (hash_type == WRENC_HASH_CRC) {
-        hipLaunchKernelGGL(hash_piece_kernel<true>, grid, dim3(256), 0, st, slots, first, n, c.width, c.height, tables, partials);
-        hipLaunchKernelGGL(hash_finish_kernel<true>, dim3((unsigned)n, 3), dim3(64), 0, st, partials, c.width, c.height, tables, start_l, start_c, values);
-    } else {
-        hipLaunchKernelGGL(hash_piece_kernel<false>, grid, dim3(256), 0, st, slots, first, n, c.width, c.height, tables, partials);
-        hipLaunchKernelGGL(hash_finish_kernel<false>, dim3((unsigned)n, 3), dim3(64), 0, st, partials, c.width, c.height, tables, start_l, start_c, values);
-    }
-    return hipGetLastError();
-}
-
-static size_t hash_partials(const wrenc_gpu_config& c) {
-    return (size_t)hash_plane(c.width, c.height, 0).pieces + 2 * (size_t)hash_plane(c.width, c.height, 1).pieces;
-}
-
-// the CRC's tables, in place before anything queued on `st` after this call reads them
-static hipError_t upload_hash_tables(HashTables* d_tables, hipStream_t st) {
-    HashTables t;
-    hash_fill_tables(t);
-    const hipError_t e = hipMemcpyAsync(d_tables, &t, sizeof(t), hipMemcpyHostToDevice, st);
-    return e != hipSuccess ? e : hipStreamSynchronize(st);
-}
-
 int wrenc_gpu_download_hashes(wrenc_gpu_ctx* ctx, int first_slot, int n, int hash_type, wrenc_picture_hash* out) {
     if (!ctx || !out) return WRENC_GPU_EINVAL;
     if (hash_type != WRENC_HASH_MD5 && hash_type != WRENC_HASH_CRC && hash_type != WRENC_HASH_CHECKSUM)
@@ -2432,30 +1810,6 @@ int wrenc_gpu_last_hash_ms(wrenc_gpu_ctx* ctx, float* ms) {
     if (!ctx->hash_timed) return fail(ctx, WRENC_GPU_ESTATE, "no timed hash pass: wrenc_gpu_stats_enable, then wrenc_gpu_download_hashes");
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
     HIP_TRY(ctx, hipEventElapsedTime(ms, ctx->hash_ev[0].get(), ctx->hash_ev[1].get()));
-    return WRENC_GPU_OK;
-}
-
-int wrenc_gpu_test_hash(wrenc_gpu_ctx* ctx, const uint8_t* const rec[3], int hash_type, wrenc_picture_hash* out) {
-    if (!ctx || !rec || !out) return WRENC_GPU_EINVAL;
-    if (hash_type != WRENC_HASH_MD5 && hash_type != WRENC_HASH_CRC && hash_type != WRENC_HASH_CHECKSUM)
-        return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_test_hash: unknown hash type");
-    for (int p = 0; p < 3; ++p)
-        if (!rec[p]) return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_test_hash: null plane");
-    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-    const wrenc_gpu_config& c = ctx->cfg;
-    DevBuf<uint8_t> d_planes;
-    DevBuf<PicBufs> d_pic;
-    DevBuf<HashTables> d_tables;
-    DevBuf<uint32_t> d_part;
-    DevBuf<wrenc_picture_hash> d_values;
-    if (const int rc = load_test_picture(ctx, nullptr, rec, d_planes, &d_pic)) return rc;
-    HIP_TRY(ctx, d_tables.alloc(1));
-    HIP_TRY(ctx, d_part.alloc(hash_partials(c)));
-    HIP_TRY(ctx, d_values.alloc(1));
-    HIP_TRY(ctx, upload_hash_tables(d_tables.get(), 0));
-    HIP_TRY(ctx, launch_hashes(c, 0, d_pic.get(), 0, 1, hash_type, d_tables.get(), d_part.get(), d_values.get()));
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    HIP_TRY(ctx, hipMemcpy(out, d_values.get(), sizeof(*out), hipMemcpyDeviceToHost));
     return WRENC_GPU_OK;
 }
 
@@ -2629,38 +1983,6 @@ int wrenc_gpu_test_set_wave_slots(wrenc_gpu_ctx* ctx, long long slots) {
     return WRENC_GPU_OK;
 }
 
-int wrenc_gpu_test_head_ranges(wrenc_gpu_ctx* ctx, int counts[4], int ranges[24]) {
-    if (!ctx || !counts) return WRENC_GPU_EINVAL;
-    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-    DevBuf<int> d;
-    HIP_TRY(ctx, d.alloc(4));
-    HIP_TRY(ctx, hipMemset(d.get(), 0, 4 * sizeof(int)));
-    hipLaunchKernelGGL(test_head_ranges_kernel, dim3(1024, 8), dim3(64), 0, 0, ctx->ctx_const(), d.get());
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    HIP_TRY(ctx, hipMemcpy(counts, d.get(), 4 * sizeof(int), hipMemcpyDeviceToHost));
-    if (ranges) {
-        DevConst* hk = new DevConst;
-        fill_dev_const(ctx->cfg, *hk);
-        memcpy(ranges, hk->head_rng, sizeof(hk->head_rng));
-        delete hk;
-    }
-    return WRENC_GPU_OK;
-}
-
-int wrenc_gpu_test_avail_tab(wrenc_gpu_ctx* ctx, int* differences) {
-    if (!ctx || !differences) return WRENC_GPU_EINVAL;
-    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-    DevBuf<int> d;
-    HIP_TRY(ctx, d.alloc(1));
-    HIP_TRY(ctx, hipMemset(d.get(), 0, sizeof(int)));
-    hipLaunchKernelGGL(test_avail_tab_kernel, dim3(ctx->ctu_cols * ctx->ctu_rows, 4), dim3(64), 0, 0, ctx->ctx_const(), d.get());
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    HIP_TRY(ctx, hipMemcpy(differences, d.get(), sizeof(int), hipMemcpyDeviceToHost));
-    return WRENC_GPU_OK;
-}
-
 int wrenc_gpu_test_scratch_overflows(wrenc_gpu_ctx* ctx, long long* count) {
     if (!ctx || !count) return WRENC_GPU_EINVAL;
     *count = 0;
@@ -2720,255 +2042,5 @@ int wrenc_gpu_prof_read(wrenc_gpu_ctx* ctx, unsigned long long* out, int n) {
     return WRENC_GPU_OK;
 }
 #endif
-
-// ---- building-block entry points ----
-
-// the 32x32 forward transform runs as i8 MFMAs on two base-256 digits of the residual (fwd_dct32_mfma): exact for
-// |residual| <= 255, which is all the search can produce; the test entries refuse anything else
-static bool residuals_fit_9_bits(const int16_t* res, size_t n) {
-    for (size_t i = 0; i < n; ++i)
-        if (res[i] < -255 || res[i] > 255) return false;
-    return true;
-}
-
-// What the group entries refuse, before anything is allocated or launched: a group the device functions are not written
-// for or that does not fit the wave's buffers (r1: 1024 i16 from o1 on; r2: the 1024 i16 of the scan-order or transposed
-// blocks).  nb_max: 2 for the quantiser (a luma block or the Cb + Cr pair).  nullptr = fine.
-static const char* group_shape_error(int log2n, int nb, int o1, int nb_max) {
-    if (log2n < 2 || log2n > 5) return "log2n must be 2..5";
-    if (nb < 1 || nb > nb_max) return "nb outside what the device function takes";
-    if (log2n == 5 && nb > 1) return "a 32x32 block is always alone";
-    if (o1 < 0 || (o1 & 1)) return "o1 must be even and >= 0";
-    if ((nb << (2 * log2n)) > 1024) return "the group does not fit r2";
-    if (o1 + (nb << (2 * log2n)) > 1024) return "the group does not fit r1 behind o1";
-    return nullptr;
-}
-constexpr int kGroupMaxBlocks = 64; // (1024 / 16: group_shape_error's size rules are what bounds a transform group)
-
-// The 8x8 and 16x16 transforms exist as i8 MFMAs too (fwd_dct_mfma / inv_dct_mfma; the search runs them at 16x16):
-// 16-byte row reads, so o1 a multiple of 8, and for the forward transform |residual| <= 255.  The search has both by
-// construction; a test group that has not runs the retained v_dot2 templates (the host decides before the launch: no
-// data-dependent branch on the device).
-static bool group_takes_mfma(const int16_t* res, int log2n, int nb, int o1, int count, bool inverse) {
-    if (o1 & 7) return false;
-    return inverse || count < 1 || residuals_fit_9_bits(res, (size_t)count * ((size_t)nb << (2 * log2n)));
-}
-// use_mfma: -1 = the plain entries: what the search runs at this size where the group meets its preconditions, else the
-// v_dot2 templates; 0 = the v_dot2 templates; 1 = the MFMA versions, or EINVAL
-static int run_dct_group(wrenc_gpu_ctx* ctx, const int16_t* in, int log2n, int nb, int o1, int count, int16_t* out,
-                         int use_mfma, int reps, float* kernel_ms, bool inverse) {
-    if (!ctx || !in || !out || reps < 1) return WRENC_GPU_EINVAL;
-    if (const char* why = group_shape_error(log2n, nb, o1, kGroupMaxBlocks)) return fail(ctx, WRENC_GPU_EINVAL, why);
-    if (!inverse && log2n == 5 && count >= 1 && !residuals_fit_9_bits(in, (size_t)count * 1024))
-        return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_test_fwd_dct: a 32x32 residual lies outside +-255");
-    int arm = DCT_SEARCH; // (4x4 and 32x32: nothing to choose)
-    if (log2n == 3 || log2n == 4) {
-        const bool takes = group_takes_mfma(in, log2n, nb, o1, count, inverse);
-        if (use_mfma == 1 && !takes)
-            return fail(ctx, WRENC_GPU_EINVAL, "the MFMA transforms take residuals within +-255 and an o1 that is a multiple of 8");
-        arm = use_mfma == 1 ? DCT_MFMA : (use_mfma == 0 || !takes ? DCT_VDOT2 : DCT_SEARCH);
-    }
-    float ms = 0.f;
-    const int rc = run_block_test(ctx, in, log2n, count, out, [&](int16_t* i, int16_t* o) {
-        if (inverse)
-            hipLaunchKernelGGL(test_inv_dct_kernel, dim3(count), dim3(64), 0, ctx->stream.get(), ctx->ctx_const(), i, log2n, nb, o1, o, arm, reps);
-        else
-            hipLaunchKernelGGL(test_fwd_dct_kernel, dim3(count), dim3(64), 0, ctx->stream.get(), ctx->ctx_const(), i, log2n, nb, o1, o, arm, reps);
-    }, nb, kernel_ms ? &ms : nullptr);
-    if (kernel_ms) *kernel_ms = ms;
-    return rc;
-}
-int wrenc_gpu_test_fwd_dct_nb(wrenc_gpu_ctx* ctx, const int16_t* res, int log2n, int nb, int o1, int count, int16_t* coef) {
-    return run_dct_group(ctx, res, log2n, nb, o1, count, coef, -1, 1, nullptr, false);
-}
-int wrenc_gpu_test_fwd_dct_mfma(wrenc_gpu_ctx* ctx, const int16_t* res, int log2n, int nb, int o1, int count, int16_t* coef,
-                                int use_mfma, int reps, float* kernel_ms) {
-    if (!ctx) return WRENC_GPU_EINVAL;
-    if (log2n != 3 && log2n != 4) return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_test_fwd_dct_mfma: log2n must be 3 or 4");
-    return run_dct_group(ctx, res, log2n, nb, o1, count, coef, use_mfma ? 1 : 0, reps, kernel_ms, false);
-}
-int wrenc_gpu_test_inv_dct_mfma(wrenc_gpu_ctx* ctx, const int16_t* deq, int log2n, int nb, int o1, int count, int16_t* res,
-                                int use_mfma, int reps, float* kernel_ms) {
-    if (!ctx) return WRENC_GPU_EINVAL;
-    if (log2n != 3 && log2n != 4) return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_test_inv_dct_mfma: log2n must be 3 or 4");
-    return run_dct_group(ctx, deq, log2n, nb, o1, count, res, use_mfma ? 1 : 0, reps, kernel_ms, true);
-}
-int wrenc_gpu_test_fwd_dct(wrenc_gpu_ctx* ctx, const int16_t* res, int log2n, int count, int16_t* coef) {
-    return wrenc_gpu_test_fwd_dct_nb(ctx, res, log2n, 1, 0, count, coef);
-}
-// a 32x32 transform micro-benchmark: `count` blocks, `reps` repetitions each, HIP-event duration of the one kernel
-static int run_dct32_bench(wrenc_gpu_ctx* ctx, const int16_t* in, int count, int16_t* out, int use_mfma, int reps,
-                           float* kernel_ms, bool inverse) {
-    if (!ctx || !in || !out || count < 1 || reps < 1) return WRENC_GPU_EINVAL;
-    if (!inverse && use_mfma && !residuals_fit_9_bits(in, (size_t)count * 1024))
-        return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_test_fwd_dct32: a residual lies outside +-255 (MFMA path)");
-    float ms = 0.f;
-    const int rc = run_block_test(ctx, in, 5, count, out, [&](int16_t* i, int16_t* o) {
-        if (inverse)
-            hipLaunchKernelGGL(test_inv_dct32_kernel, dim3(count), dim3(64), 0, ctx->stream.get(), ctx->ctx_const(), i, o, use_mfma, reps);
-        else
-            hipLaunchKernelGGL(test_fwd_dct32_kernel, dim3(count), dim3(64), 0, ctx->stream.get(), ctx->ctx_const(), i, o, use_mfma, reps);
-    }, 1, &ms);
-    if (kernel_ms) *kernel_ms = ms;
-    return rc;
-}
-int wrenc_gpu_test_fwd_dct32(wrenc_gpu_ctx* ctx, const int16_t* res, int count, int16_t* coef, int use_mfma, int reps,
-                             float* kernel_ms) {
-    return run_dct32_bench(ctx, res, count, coef, use_mfma, reps, kernel_ms, false);
-}
-int wrenc_gpu_test_inv_dct32(wrenc_gpu_ctx* ctx, const int16_t* deq, int count, int16_t* res, int use_mfma, int reps,
-                             float* kernel_ms) {
-    return run_dct32_bench(ctx, deq, count, res, use_mfma, reps, kernel_ms, true);
-}
-int wrenc_gpu_test_inv_dct_nb(wrenc_gpu_ctx* ctx, const int16_t* deq, int log2n, int nb, int o1, int count, int16_t* res) {
-    return run_dct_group(ctx, deq, log2n, nb, o1, count, res, -1, 1, nullptr, true);
-}
-int wrenc_gpu_test_inv_dct(wrenc_gpu_ctx* ctx, const int16_t* deq, int log2n, int count, int16_t* res) {
-    return wrenc_gpu_test_inv_dct_nb(ctx, deq, log2n, 1, 0, count, res);
-}
-int wrenc_gpu_test_fwd_dct4_reg(wrenc_gpu_ctx* ctx, const int16_t* res, int count, int16_t* coef) {
-    return run_block_test(ctx, res, 2, count, coef, [&](int16_t* i, int16_t* o) {
-        hipLaunchKernelGGL(test_dct4_reg_kernel, dim3((count + 3) / 4), dim3(64), 0, ctx->stream.get(), ctx->ctx_const(), i, count, 0, o);
-    });
-}
-int wrenc_gpu_test_inv_dct4_reg(wrenc_gpu_ctx* ctx, const int16_t* levels, int count, int16_t* res) {
-    return run_block_test(ctx, levels, 2, count, res, [&](int16_t* i, int16_t* o) {
-        hipLaunchKernelGGL(test_dct4_reg_kernel, dim3((count + 3) / 4), dim3(64), 0, ctx->stream.get(), ctx->ctx_const(), i, count, 1, o);
-    });
-}
-int wrenc_gpu_test_dequantize_nb(wrenc_gpu_ctx* ctx, const int16_t* levels, int log2n, int nb, int o1, int count, int16_t* deq) {
-    if (!ctx || !levels || !deq) return WRENC_GPU_EINVAL;
-    if (const char* why = group_shape_error(log2n, nb, o1, kGroupMaxBlocks)) return fail(ctx, WRENC_GPU_EINVAL, why);
-    return run_block_test(ctx, levels, log2n, count, deq, [&](int16_t* i, int16_t* o) {
-        hipLaunchKernelGGL(test_dequantize_kernel, dim3(count), dim3(64), 0, ctx->stream.get(), ctx->ctx_const(), i, log2n, nb, o1, o);
-    }, nb);
-}
-int wrenc_gpu_test_dequantize(wrenc_gpu_ctx* ctx, const int16_t* levels, int log2n, int count, int16_t* deq) {
-    return wrenc_gpu_test_dequantize_nb(ctx, levels, log2n, 1, 0, count, deq);
-}
-// (any_level may be null: the one-block entry does not hand it on)
-int wrenc_gpu_test_quantize_nb(wrenc_gpu_ctx* ctx, const int16_t* coef, int log2n, int nb, int count, int16_t* levels,
-                               int64_t* level_cost, int32_t* any_level) {
-    if (!ctx || !coef || !levels || !level_cost) return WRENC_GPU_EINVAL;
-    if (const char* why = group_shape_error(log2n, nb, 0, 2)) return fail(ctx, WRENC_GPU_EINVAL, why);
-    if (count < 1) return fail(ctx, WRENC_GPU_EINVAL, "count must be >= 1");
-    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-    DevBuf<long long> d_cost;
-    DevBuf<int> d_any;
-    return take_test_overflow(ctx, [&]() -> int {
-        HIP_TRY(ctx, d_cost.alloc((size_t)count));
-        HIP_TRY(ctx, d_any.alloc((size_t)count));
-        const int rc = run_block_test(ctx, coef, log2n, count, levels, [&](int16_t* i, int16_t* o) {
-            hipLaunchKernelGGL(test_quantize_kernel, dim3(count), dim3(64), 0, ctx->stream.get(), ctx->ctx_const(), i, log2n, nb, o,
-                               d_cost.get(), d_any.get(), ctx->d_overflow.get() + 1);
-        }, nb);
-        if (rc) return rc;
-        HIP_TRY(ctx, hipMemcpy(level_cost, d_cost.get(), sizeof(long long) * count, hipMemcpyDeviceToHost));
-        if (any_level) HIP_TRY(ctx, hipMemcpy(any_level, d_any.get(), sizeof(int) * count, hipMemcpyDeviceToHost));
-        return WRENC_GPU_OK;
-    }());
-}
-int wrenc_gpu_test_quantize(wrenc_gpu_ctx* ctx, const int16_t* coef, int log2n, int count, int16_t* levels,
-                            int64_t* level_cost) {
-    return wrenc_gpu_test_quantize_nb(ctx, coef, log2n, 1, count, levels, level_cost, nullptr);
-}
-
-int wrenc_gpu_test_quantize_p16(wrenc_gpu_ctx* ctx, const int16_t* coef, int count, int16_t* levels, int64_t* level_cost) {
-    if (!ctx || !level_cost) return WRENC_GPU_EINVAL;
-    if (count < 1) return fail(ctx, WRENC_GPU_EINVAL, "count must be >= 1");
-    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-    DevBuf<long long> d_cost;
-    return take_test_overflow(ctx, [&]() -> int {
-        HIP_TRY(ctx, d_cost.alloc((size_t)count));
-        const int rc = run_block_test(ctx, coef, 2, count, levels, [&](int16_t* i, int16_t* o) {
-            hipLaunchKernelGGL(test_quantize_p16_kernel, dim3((count + 3) / 4), dim3(64), 0, ctx->stream.get(), ctx->ctx_const(), i, count, o,
-                               d_cost.get(), ctx->d_overflow.get() + 1);
-        });
-        if (rc) return rc;
-        HIP_TRY(ctx, hipMemcpy(level_cost, d_cost.get(), sizeof(long long) * count, hipMemcpyDeviceToHost));
-        return WRENC_GPU_OK;
-    }());
-}
-
-int wrenc_gpu_test_quantize_pk(wrenc_gpu_ctx* ctx, const int16_t* coef, int log2n, int nc, int n_packs, int16_t* levels,
-                               int64_t* level_cost) {
-    if (!ctx || !coef || !levels || !level_cost) return WRENC_GPU_EINVAL;
-    if (!((log2n == 3 && nc >= 1 && nc <= 3) || (log2n == 4 && nc >= 1 && nc <= 2)) || n_packs < 1)
-        return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_test_quantize_pk: log2n 3 with nc 1..3 or log2n 4 with nc 1..2");
-    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-    const size_t total = (size_t)n_packs * nc * 3 * ((size_t)1 << (2 * log2n)) / 2;
-    const size_t n_costs = (size_t)2 * nc * n_packs;
-    DevBuf<int16_t> d_in, d_out;
-    DevBuf<long long> d_cost;
-    return take_test_overflow(ctx, [&]() -> int {
-        HIP_TRY(ctx, d_in.alloc(total));
-        HIP_TRY(ctx, d_out.alloc(total));
-        HIP_TRY(ctx, d_cost.alloc(n_costs));
-        HIP_TRY(ctx, hipMemcpy(d_in.get(), coef, total * sizeof(int16_t), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(test_quantize_pk_kernel, dim3(n_packs), dim3(64), 0, ctx->stream.get(), ctx->ctx_const(), d_in.get(), log2n, nc,
-                           d_out.get(), d_cost.get(), ctx->d_overflow.get() + 1);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream.get()));
-        HIP_TRY(ctx, hipMemcpy(levels, d_out.get(), total * sizeof(int16_t), hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(level_cost, d_cost.get(), sizeof(long long) * n_costs, hipMemcpyDeviceToHost));
-        return WRENC_GPU_OK;
-    }());
-}
-
-int wrenc_gpu_test_predict(wrenc_gpu_ctx* ctx, const uint8_t* rec_y, const uint8_t* rec_cb, const uint8_t* rec_cr,
-                           int n_items, const int32_t* items, uint8_t* out, size_t out_bytes) {
-    if (!ctx || !rec_y || !rec_cb || !rec_cr || !items || !out || n_items < 1) return WRENC_GPU_EINVAL;
-    const int W = ctx->cfg.width, H = ctx->cfg.height;
-    // operand shapes are checked on the host: a bad item must never reach the kernel
-    std::vector<int> dev_items((size_t)n_items * 6);
-    size_t total = 0;
-    for (int i = 0; i < n_items; ++i) {
-        const int32_t* q = items + 5 * i;
-        const int x = q[0], y = q[1], lg = q[2], comp = q[3], mode = q[4];
-        const int n = 1 << lg;
-        const bool list = comp >= 4 && comp <= 6; // a SAD list: mode = m0 | entries << 8 | stride << 16
-        const int m0 = mode & 255, nm = (mode >> 8) & 255, stride = mode >> 16;
-        bool ok = lg >= 2 && lg <= 5 && x >= 0 && y >= 0 && x + n <= W && y + n <= H && !(x & (n - 1)) && !(y & (n - 1));
-        const bool pack = comp == 10 || comp == 11; // mode = m0 | m1 << 8 | m2 << 16 | candidates << 24, 255 = kNoMode
-        const int pk_nc = mode >> 24;
-        if (pack) {
-            ok = ok && mode >= 0 && lg == (comp == 10 ? 3 : 4) && pk_nc >= 1 && pk_nc <= (comp == 10 ? 3 : 2);
-            for (int j = 0; ok && j < pk_nc; ++j) {
-                const int m = (mode >> (8 * j)) & 255;
-                ok = m <= 66 || m == kNoMode;
-            }
-        } else if (comp == 8 || comp == 9) {
-            ok = ok && (comp == 8 || lg >= 3) && ((mode >= 0 && mode <= 66) || (comp == 9 && mode >= LT_CCLM && mode <= T_CCLM));
-        } else {
-            ok = ok && (comp == 0 || (comp == 1 && lg >= 3) || (comp == 2 && lg == 2) || (comp == 4) || (list && lg >= 3) ||
-                        (comp == 7 && lg >= 3)) &&
-                 (comp == 7 ? mode == 0 : list ? (mode >= 0 && m0 >= 2 && m0 <= 66 && nm >= 1 && nm <= 16 && stride >= 1 && stride <= 64)
-                       : ((mode >= 0 && mode <= 66) || (comp == 1 && mode >= LT_CCLM && mode <= T_CCLM)));
-        }
-        if (!ok) return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_test_predict: bad item");
-        int* d = &dev_items[(size_t)i * 6];
-        d[0] = x; d[1] = y; d[2] = lg; d[3] = comp; d[4] = mode; d[5] = (int)total;
-        // (the full-candidate items: prediction bytes, then as many i16 residuals)
-        total += (list || comp == 7) ? 64 : comp == 8 ? 3 * (size_t)n * n : comp == 9 ? 3 * (size_t)n * n / 2
-                 : comp == 10 ? 3 * 64 * (size_t)pk_nc : comp == 11 ? 3 * 384 * (size_t)pk_nc
-                 : (comp == 1 ? (size_t)n * n / 2 : (size_t)n * n);
-    }
-    if (total != out_bytes) return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_test_predict: output size does not match the items");
-    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-    const uint8_t* const rec[3] = {rec_y, rec_cb, rec_cr};
-    DevBuf<uint8_t> d_planes, d_scratch, d_out;
-    DevBuf<int> d_items;
-    if (const int rc = load_test_picture(ctx, nullptr, rec, d_planes, nullptr)) return rc;
-    HIP_TRY(ctx, d_scratch.alloc((size_t)n_items * kTestPredictScratch));
-    HIP_TRY(ctx, d_out.alloc(total));
-    HIP_TRY(ctx, d_items.alloc(dev_items.size()));
-    HIP_TRY(ctx, hipMemcpy(d_items.get(), dev_items.data(), dev_items.size() * sizeof(int), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(test_predict_kernel, dim3(n_items), dim3(64), 0, ctx->stream.get(), ctx->ctx_const(), d_planes.get(), d_items.get(),
-                       d_scratch.get(), d_out.get());
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream.get()));
-    HIP_TRY(ctx, hipMemcpy(out, d_out.get(), total, hipMemcpyDeviceToHost));
-    return WRENC_GPU_OK;
-}
 
 } // extern "C"

@@ -17,21 +17,85 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("WRENC_GPU_LIB", os.path.join(_HERE, "csrc", "libwrenc_gpu.so"))
 
-EXPORTED_SYMBOLS = [
-    "wrenc_gpu_default_config", "wrenc_gpu_config_extra_params", "wrenc_gpu_create", "wrenc_gpu_destroy", "wrenc_gpu_last_error",
-    "wrenc_gpu_upload", "wrenc_gpu_encode", "wrenc_gpu_set_slot_qp", "wrenc_gpu_sync", "wrenc_gpu_download", "wrenc_gpu_download_compact", "wrenc_gpu_compact_mask_words", "wrenc_gpu_expand_levels", "wrenc_gpu_download_tokens", "wrenc_gpu_download_metrics", "wrenc_gpu_download_complexity", "wrenc_gpu_metrics_values", "wrenc_gpu_test_metrics", "wrenc_gpu_test_load_record", "wrenc_gpu_device_info",
-    "wrenc_gpu_alloc_host", "wrenc_gpu_free_host", "wrenc_gpu_encode_picture", "wrenc_gpu_set_schedule", "wrenc_gpu_last_schedule", "wrenc_gpu_stats_enable", "wrenc_gpu_last_encode_stats", "wrenc_gpu_last_encode_kernel_stats", "wrenc_gpu_final_pass_mismatches",
-    "wrenc_gpu_test_fwd_dct", "wrenc_gpu_test_inv_dct", "wrenc_gpu_test_quantize",
-    "wrenc_gpu_test_fwd_dct_nb", "wrenc_gpu_test_inv_dct_nb", "wrenc_gpu_test_fwd_dct_mfma", "wrenc_gpu_test_inv_dct_mfma", "wrenc_gpu_test_quantize_nb", "wrenc_gpu_test_dequantize_nb",
-    "wrenc_gpu_test_dequantize","wrenc_gpu_test_predict", "wrenc_gpu_test_fwd_dct32", "wrenc_gpu_test_inv_dct32", "wrenc_gpu_test_quantize_p16", "wrenc_gpu_test_quantize_pk", "wrenc_gpu_test_fwd_dct4_reg", "wrenc_gpu_test_inv_dct4_reg", "wrenc_gpu_test_set_wave_slots", "wrenc_gpu_test_scratch_overflows", "wrenc_gpu_test_head_ranges", "wrenc_gpu_test_avail_tab",
-    "wrenc_gpu_set_visible_size", "wrenc_gpu_visible_size", "wrenc_gpu_test_download_originals",
-    "wrenc_gpu_set_source_size", "wrenc_gpu_source_size", "wrenc_gpu_scale_taps",
-    "wrenc_gpu_set_source_format", "wrenc_gpu_source_format", "wrenc_gpu_upload_planes",
-    "wrenc_gpu_format_from_name", "wrenc_gpu_format_name", "wrenc_gpu_format_layout",
-    "wrenc_gpu_download_hashes", "wrenc_gpu_test_hash", "wrenc_gpu_last_hash_ms",
-    "wrenc_gpu_download_rate_hist", "wrenc_gpu_rate_hist_bin", "wrenc_gpu_rate_hist_host",
-    "wrenc_gpu_test_plan",
-]
+# Every function of include/wrenc_gpu.h and include/wrenc_gpu_test.h: name -> (restype, argtypes).  load_library() applies
+# the table once; nothing else assigns a prototype (tests/test_abi.py holds it against the headers' declarations).
+# Pointers are void pointers: callers pass arrays, byref() and addresses alike.
+_I, _P, _S, _Z, _LL = C.c_int, C.c_void_p, C.c_char_p, C.c_size_t, C.c_longlong
+PROTOTYPES = {
+    "wrenc_gpu_default_config": (_I, [_P, _I, _I, _I, _I]),
+    "wrenc_gpu_config_extra_params": (_I, [_P, _S]),
+    "wrenc_gpu_create": (_I, [_P, _P]),
+    "wrenc_gpu_destroy": (None, [_P]),
+    "wrenc_gpu_last_error": (_S, [_P]),
+    "wrenc_gpu_upload": (_I, [_P, _I, _P, _P, _P, _Z, _Z]),
+    "wrenc_gpu_set_visible_size": (_I, [_P, _I, _I]),
+    "wrenc_gpu_visible_size": (_I, [_P, _P, _P]),
+    "wrenc_gpu_set_source_size": (_I, [_P, _I, _I]),
+    "wrenc_gpu_source_size": (_I, [_P, _P, _P]),
+    "wrenc_gpu_scale_taps": (_I, [_I, _I, _I, _P, _P, _P]),
+    "wrenc_gpu_set_source_format": (_I, [_P, _I]),
+    "wrenc_gpu_source_format": (_I, [_P]),
+    "wrenc_gpu_upload_planes": (_I, [_P, _I, _P, _P]),
+    "wrenc_gpu_format_from_name": (_I, [_S]),
+    "wrenc_gpu_format_name": (_S, [_I]),
+    "wrenc_gpu_format_layout": (_I, [_I, _I, _I, _P]),
+    "wrenc_gpu_encode": (_I, [_P, _I, _I]),
+    "wrenc_gpu_set_slot_qp": (_I, [_P, _I, _P]),
+    "wrenc_gpu_sync": (_I, [_P]),
+    "wrenc_gpu_download": (_I, [_P, _I, _P]),
+    "wrenc_gpu_compact_mask_words": (_Z, [_I, _I]),
+    "wrenc_gpu_download_compact": (_I, [_P, _I, _I, _P]),
+    "wrenc_gpu_expand_levels": (None, [_I, _I, _P, _P, _P, _P, _P]),
+    "wrenc_gpu_download_tokens": (_I, [_P, _I, _I, _P, _P, _Z, _P]),
+    "wrenc_gpu_download_metrics": (_I, [_P, _I, _I, _P]),
+    "wrenc_gpu_download_complexity": (_I, [_P, _I, _I, _P]),
+    "wrenc_gpu_download_rate_hist": (_I, [_P, _I, _I, _P]),
+    "wrenc_gpu_rate_hist_bin": (_I, [_I]),
+    "wrenc_gpu_rate_hist_host": (_I, [_I, _I, _P, _P, _P, _P]),
+    "wrenc_gpu_metrics_values": (None, [_I, _I, _P, _P, _P]),
+    "wrenc_gpu_download_hashes": (_I, [_P, _I, _I, _I, _P]),
+    "wrenc_gpu_last_hash_ms": (_I, [_P, _P]),
+    "wrenc_gpu_alloc_host": (_P, [_P, _Z]),
+    "wrenc_gpu_free_host": (None, [_P, _P]),
+    "wrenc_gpu_encode_picture": (_I, [_P, _P, _P, _P, _P]),
+    "wrenc_gpu_set_schedule": (_I, [_P, _I]),
+    "wrenc_gpu_last_schedule": (_I, [_P]),
+    "wrenc_gpu_device_info": (_I, [_P, _P, _P]),
+    "wrenc_gpu_stats_enable": (_I, [_P, _I]),
+    "wrenc_gpu_last_encode_stats": (_I, [_P, _P, _P, _P]),
+    "wrenc_gpu_last_encode_kernel_stats": (_I, [_P, _P]),
+    "wrenc_gpu_final_pass_mismatches": (_I, [_P, _P]),
+    # test hooks on a context's state, and the planner
+    "wrenc_gpu_test_download_originals": (_I, [_P, _I, _P, _P, _P]),
+    "wrenc_gpu_test_load_record": (_I, [_P, _I, _P]),
+    "wrenc_gpu_test_set_wave_slots": (_I, [_P, _LL]),
+    "wrenc_gpu_test_scratch_overflows": (_I, [_P, _P]),
+    "wrenc_gpu_test_plan": (_I, [_I, _I, _P, _I, _I, _LL, _I, _P, _P, _I, _P, _I, _P, _I]),
+    # include/wrenc_gpu_test.h
+    "wrenc_gpu_test_metrics": (_I, [_P, _P, _P, _P, _P]),
+    "wrenc_gpu_test_hash": (_I, [_P, _P, _I, _P]),
+    "wrenc_gpu_test_head_ranges": (_I, [_P, _P, _P]),
+    "wrenc_gpu_test_avail_tab": (_I, [_P, _P]),
+    "wrenc_gpu_test_fwd_dct": (_I, [_P, _P, _I, _I, _P]),
+    "wrenc_gpu_test_inv_dct": (_I, [_P, _P, _I, _I, _P]),
+    "wrenc_gpu_test_dequantize": (_I, [_P, _P, _I, _I, _P]),
+    "wrenc_gpu_test_quantize": (_I, [_P, _P, _I, _I, _P, _P]),
+    "wrenc_gpu_test_fwd_dct32": (_I, [_P, _P, _I, _P, _I, _I, _P]),
+    "wrenc_gpu_test_inv_dct32": (_I, [_P, _P, _I, _P, _I, _I, _P]),
+    "wrenc_gpu_test_fwd_dct_nb": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "wrenc_gpu_test_inv_dct_nb": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "wrenc_gpu_test_dequantize_nb": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "wrenc_gpu_test_quantize_nb": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    "wrenc_gpu_test_fwd_dct_mfma": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
+    "wrenc_gpu_test_inv_dct_mfma": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
+    "wrenc_gpu_test_fwd_dct4_reg": (_I, [_P, _P, _I, _P]),
+    "wrenc_gpu_test_inv_dct4_reg": (_I, [_P, _P, _I, _P]),
+    "wrenc_gpu_test_quantize_p16": (_I, [_P, _P, _I, _P, _P]),
+    "wrenc_gpu_test_quantize_pk": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "wrenc_gpu_test_predict": (_I, [_P, _P, _P, _P, _I, _P, _P, _Z]),
+    "wrenc_gpu_test_predict_layout": (_I, [_I, _I, _I, _P, _P]),
+}
+EXPORTED_SYMBOLS = list(PROTOTYPES)
 
 
 class Config(C.Structure):
@@ -110,7 +174,6 @@ def rate_hist_bin(magnitude):
     """wrenc_gpu_rate_hist_bin (host only): the bin of a coefficient magnitude 0 .. 16,320 (include/wrenc_ratecurve.h);
     WrencGpuError outside."""
     lib = load_library()
-    lib.wrenc_gpu_rate_hist_bin.argtypes = [C.c_int]
     rc = lib.wrenc_gpu_rate_hist_bin(int(magnitude))
     if rc < 0:
         raise WrencGpuError(rc, "rate_hist_bin(%d)" % magnitude)
@@ -126,7 +189,6 @@ def rate_hist_host(y, cb, cr):
         raise WrencGpuError(-1, "rate_hist_host: planes of %s" % ([p.shape for p in planes],))
     lib = load_library()
     out = (RateHist * 1)()
-    lib.wrenc_gpu_rate_hist_host.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     rc = lib.wrenc_gpu_rate_hist_host(w, h, _p(planes[0]), _p(planes[1]), _p(planes[2]), out)
     if rc:
         raise WrencGpuError(rc, "rate_hist_host(%d x %d)" % (w, h))
@@ -151,8 +213,6 @@ def encode_plan(ctu_cols, ctu_rows, qps, schedule, wave_slots, depth3):
     lib = load_library()
     q = (C.c_int * len(qps))(*[int(x) for x in qps])
     info = PlanInfo()
-    lib.wrenc_gpu_test_plan.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p,
-                                        C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     args = (int(ctu_cols), int(ctu_rows), q, len(qps), int(schedule), int(wave_slots), 1 if depth3 else 0, C.byref(info))
     lib.wrenc_gpu_test_plan(*args, None, 0, None, 0, None, 0)       # the sizes (an error where the arguments are refused, below)
     launches = (PlanLaunch * max(1, info.n_launches))()
@@ -173,8 +233,6 @@ def metrics_values(width, height, m):
     shape of metrics.frame_metrics."""
     lib = load_library()
     psnr, ssim = (C.c_double * 4)(), (C.c_double * 4)()
-    lib.wrenc_gpu_metrics_values.restype = None
-    lib.wrenc_gpu_metrics_values.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.wrenc_gpu_metrics_values(width, height, C.byref(m), psnr, ssim)
     names = ("Avg", "Y", "U", "V")
     return {"PSNR": dict(zip(names, psnr)), "SSIM": dict(zip(names, ssim)),
@@ -187,7 +245,6 @@ def scale_taps(n_in, n_out, o):
     lib = load_library()
     first, n = C.c_int(), C.c_int()
     coef = (C.c_int16 * 17)()
-    lib.wrenc_gpu_scale_taps.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     rc = lib.wrenc_gpu_scale_taps(int(n_in), int(n_out), int(o), C.byref(first), C.byref(n), coef)
     if rc:
         raise WrencGpuError(rc, "scale_taps(%d, %d, %d)" % (n_in, n_out, o))
@@ -203,7 +260,6 @@ def format_from_name(name):
     """wrenc_gpu_format_from_name (host only): the id of a source format named as ffmpeg names it (include/wrenc_format.h);
     WrencGpuError for an unknown name."""
     lib = load_library()
-    lib.wrenc_gpu_format_from_name.argtypes = [C.c_char_p]
     rc = lib.wrenc_gpu_format_from_name(name.encode() if name is not None else None)
     if rc < 0:
         raise WrencGpuError(rc, "format_from_name(%r)" % (name,))
@@ -213,8 +269,6 @@ def format_from_name(name):
 def format_name(fmt):
     """wrenc_gpu_format_name (host only): the name of a format id, None for an unknown one."""
     lib = load_library()
-    lib.wrenc_gpu_format_name.argtypes = [C.c_int]
-    lib.wrenc_gpu_format_name.restype = C.c_char_p
     name = lib.wrenc_gpu_format_name(int(fmt))
     return name.decode() if name is not None else None
 
@@ -228,7 +282,6 @@ def format_layout(fmt, w, h):
     file: {"n_planes", "bytes_per_sample", "row_bytes", "rows", "offset" (a list per plane), "frame_bytes"}."""
     lib = load_library()
     out = FormatLayout()
-    lib.wrenc_gpu_format_layout.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
     rc = lib.wrenc_gpu_format_layout(_format_id(fmt), int(w), int(h), C.byref(out))
     if rc:
         raise WrencGpuError(rc, "format_layout(%r, %d, %d)" % (fmt, w, h))
@@ -254,31 +307,10 @@ def load_library():
             raise FileNotFoundError(
                 "%s not built: run `python -c 'import __graft_entry__ as g; g.build()'`" % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
-        lib.wrenc_gpu_last_error.restype = C.c_char_p
-        lib.wrenc_gpu_last_error.argtypes = [C.c_void_p]
-        lib.wrenc_gpu_create.argtypes = [C.POINTER(Config), C.POINTER(C.c_void_p)]
-        lib.wrenc_gpu_destroy.argtypes = [C.c_void_p]
-        lib.wrenc_gpu_destroy.restype = None
-        lib.wrenc_gpu_upload.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_size_t, C.c_size_t]
-        lib.wrenc_gpu_encode.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        lib.wrenc_gpu_sync.argtypes = [C.c_void_p]
-        lib.wrenc_gpu_download.argtypes = [C.c_void_p, C.c_int, C.POINTER(Picture)]
-        lib.wrenc_gpu_encode_picture.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                 C.POINTER(Picture)]
-        lib.wrenc_gpu_last_encode_stats.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float),
-                                                    C.POINTER(C.c_int)]
-        lib.wrenc_gpu_final_pass_mismatches.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
-        for name in ("fwd_dct", "inv_dct", "dequantize"):
-            getattr(lib, "wrenc_gpu_test_" + name).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                                               C.c_void_p]
-        lib.wrenc_gpu_test_quantize.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
-                                                C.c_void_p]
-        for name in ("fwd_dct_nb", "inv_dct_nb", "dequantize_nb"):   # (ctx, in, log2n, nb, o1, count, out)
-            getattr(lib, "wrenc_gpu_test_" + name).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                               C.c_void_p]
-        lib.wrenc_gpu_test_quantize_nb.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                                   C.c_void_p, C.c_void_p]
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            fn = getattr(lib, name)
+            fn.restype = restype
+            fn.argtypes = argtypes
         _lib = lib
     return _lib
 
@@ -375,8 +407,6 @@ class Encoder:
 
     def close(self):
         if self.ctx:
-            self.lib.wrenc_gpu_free_host.restype = None
-            self.lib.wrenc_gpu_free_host.argtypes = [C.c_void_p, C.c_void_p]
             for ptr in self._pinned:
                 self.lib.wrenc_gpu_free_host(self.ctx, ptr)
             self._pinned = []
@@ -410,11 +440,9 @@ class Encoder:
 
     def set_source_format(self, fmt):
         """wrenc_gpu_set_source_format (an id or a name): before the first upload; 0 / "yuv420p" restores the plain behaviour."""
-        self.lib.wrenc_gpu_set_source_format.argtypes = [C.c_void_p, C.c_int]
         self._check(self.lib.wrenc_gpu_set_source_format(self.ctx, _format_id(fmt)))
 
     def source_format(self):
-        self.lib.wrenc_gpu_source_format.argtypes = [C.c_void_p]
         return self.lib.wrenc_gpu_source_format(self.ctx)
 
     def upload_planes(self, slot, planes):
@@ -426,12 +454,10 @@ class Encoder:
         self._keep[slot] = planes  # host buffers must outlive the async copy
         ptr = (C.c_void_p * 3)(*[a.ctypes.data for a in planes])
         stride = (C.c_size_t * 3)(*[a.strides[0] for a in planes])
-        self.lib.wrenc_gpu_upload_planes.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         self._check(self.lib.wrenc_gpu_upload_planes(self.ctx, slot, ptr, stride))
 
     def set_visible_size(self, vis_w, vis_h):
         """wrenc_gpu_set_visible_size: before the first upload; the coded size itself restores the plain behaviour."""
-        self.lib.wrenc_gpu_set_visible_size.argtypes = [C.c_void_p, C.c_int, C.c_int]
         self._check(self.lib.wrenc_gpu_set_visible_size(self.ctx, int(vis_w), int(vis_h)))
         self.vis_width, self.vis_height = int(vis_w), int(vis_h)
         self.src_width, self.src_height = self.source_size()
@@ -439,19 +465,16 @@ class Encoder:
     def set_source_size(self, src_w, src_h):
         """wrenc_gpu_set_source_size: upload takes planes of this size and the device scales them to the visible size; before
         the first upload and after any set_visible_size; the visible size itself restores the plain behaviour."""
-        self.lib.wrenc_gpu_set_source_size.argtypes = [C.c_void_p, C.c_int, C.c_int]
         self._check(self.lib.wrenc_gpu_set_source_size(self.ctx, int(src_w), int(src_h)))
         self.src_width, self.src_height = int(src_w), int(src_h)
 
     def source_size(self):
         w, h = C.c_int(), C.c_int()
-        self.lib.wrenc_gpu_source_size.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         self._check(self.lib.wrenc_gpu_source_size(self.ctx, C.byref(w), C.byref(h)))
         return w.value, h.value
 
     def visible_size(self):
         w, h = C.c_int(), C.c_int()
-        self.lib.wrenc_gpu_visible_size.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         self._check(self.lib.wrenc_gpu_visible_size(self.ctx, C.byref(w), C.byref(h)))
         return w.value, h.value
 
@@ -460,7 +483,6 @@ class Encoder:
         y = np.zeros((self.height, self.width), np.uint8)
         cb = np.zeros((self.height // 2, self.width // 2), np.uint8)
         cr = np.zeros_like(cb)
-        self.lib.wrenc_gpu_test_download_originals.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         self._check(self.lib.wrenc_gpu_test_download_originals(self.ctx, slot, _p(y), _p(cb), _p(cr)))
         return y, cb, cr
 
@@ -480,7 +502,6 @@ class Encoder:
 
     def set_slot_config(self, slot, qcfg):
         """wrenc_gpu_set_slot_qp with a config of the caller's (None: the context's)."""
-        self.lib.wrenc_gpu_set_slot_qp.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         self._check(self.lib.wrenc_gpu_set_slot_qp(self.ctx, slot, C.addressof(qcfg) if qcfg is not None else None))
 
     def sync(self):
@@ -489,8 +510,6 @@ class Encoder:
     def download_compact(self, first_slot, n, payload_cap=None):
         """The compact read-back of n slots (include/wrenc_gpu.h): per picture (mask, payload[:n_blocks], maps dict)."""
         w, h = self.width, self.height
-        self.lib.wrenc_gpu_compact_mask_words.restype = C.c_size_t
-        self.lib.wrenc_gpu_compact_mask_words.argtypes = [C.c_int, C.c_int]
         words = self.lib.wrenc_gpu_compact_mask_words(w, h)
         blocks = (w // 4) * (h // 4) * 3 // 2
         cap = blocks if payload_cap is None else payload_cap
@@ -505,7 +524,6 @@ class Encoder:
             for name, arr in maps.items():
                 setattr(outs[k], name, _p(arr).value)
             keep.append((mask, pay, maps))
-        self.lib.wrenc_gpu_download_compact.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         self._check(self.lib.wrenc_gpu_download_compact(self.ctx, first_slot, n, outs))
         return [(m, p[:outs[k].n_blocks], maps) for k, (m, p, maps) in enumerate(keep)]
 
@@ -526,7 +544,6 @@ class Encoder:
                 setattr(outs[k], name, _p(arr).value)
             pics.append(d)
         used = C.c_size_t()
-        self.lib.wrenc_gpu_download_tokens.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         rc = self.lib.wrenc_gpu_download_tokens(self.ctx, first_slot, n, outs, _p(pool), pool_words, C.byref(used))
         while rc == -3 and grow and pool_words < (1 << 31):     # WRENC_GPU_ENOMEM: a bigger pool (the pass is cheap)
             pool_words *= 4
@@ -541,7 +558,6 @@ class Encoder:
         picture {"PSNR": {...}, "SSIM": {...}} as metrics.frame_metrics gives them, the raw sums under "_raw".  With a visible
         size: of that rectangle."""
         outs = (Metrics * max(n, 1))()
-        self.lib.wrenc_gpu_download_metrics.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         self._check(self.lib.wrenc_gpu_download_metrics(self.ctx, first_slot, n, outs))
         return [metrics_values(self.vis_width, self.vis_height, outs[k]) for k in range(n)]
 
@@ -552,7 +568,6 @@ class Encoder:
         maps = [np.zeros((self.height // 32, self.width // 32), np.uint32) if ctu_map else None for _ in range(max(n, 0))]
         for k, m in enumerate(maps):
             outs[k].ctu_satd = _p(m).value if m is not None else None
-        self.lib.wrenc_gpu_download_complexity.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         self._check(self.lib.wrenc_gpu_download_complexity(self.ctx, first_slot, n, outs))
         return [{"satd": [int(v) for v in outs[k].satd], "ctu_satd": maps[k]} for k in range(n)]
 
@@ -560,7 +575,6 @@ class Encoder:
         """The rate histograms of n slots' originals (include/wrenc_gpu.h, wrenc_gpu_download_rate_hist), before or after
         their search: an (n, 3, 64) uint64 array, count[picture][plane][bin]."""
         outs = (RateHist * max(n, 1))()
-        self.lib.wrenc_gpu_download_rate_hist.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         self._check(self.lib.wrenc_gpu_download_rate_hist(self.ctx, first_slot, n, outs))
         return _hist_array(outs, n)
 
@@ -573,7 +587,6 @@ class Encoder:
         assert [a.shape for a in o] == shapes and [a.shape for a in r] == shapes
         out = Metrics()
         wins = [np.zeros((hh // 4 - 1, ww // 4 - 1), np.float32) for hh, ww in shapes] if maps else None
-        self.lib.wrenc_gpu_test_metrics.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         self._check(self.lib.wrenc_gpu_test_metrics(self.ctx, (C.c_void_p * 3)(*[_p(a).value for a in o]),
                                                     (C.c_void_p * 3)(*[_p(a).value for a in r]), C.byref(out),
                                                     (C.c_void_p * 3)(*[_p(a).value for a in wins]) if maps else None))
@@ -584,14 +597,12 @@ class Encoder:
         """The decoded picture hash of n encoded slots' reconstruction (include/wrenc_gpu.h, wrenc_gpu_download_hashes):
         per picture a PictureHash; hash_type an id of include/wrenc_hash.h or "md5" / "crc" / "checksum"."""
         outs = (PictureHash * max(n, 1))()
-        self.lib.wrenc_gpu_download_hashes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         self._check(self.lib.wrenc_gpu_download_hashes(self.ctx, first_slot, n, _hash_id(hash_type), outs))
         return [outs[k] for k in range(n)]
 
     def last_hash_ms(self):
         """Device time of the last download_hashes call's kernels (HIP events; after stats_enable())."""
         ms = C.c_float()
-        self.lib.wrenc_gpu_last_hash_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         self._check(self.lib.wrenc_gpu_last_hash_ms(self.ctx, C.byref(ms)))
         return ms.value
 
@@ -600,7 +611,6 @@ class Encoder:
         r = [np.ascontiguousarray(a, np.uint8) for a in rec]
         assert [a.shape for a in r] == [(self.height, self.width)] + [(self.height // 2, self.width // 2)] * 2
         out = PictureHash()
-        self.lib.wrenc_gpu_test_hash.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         self._check(self.lib.wrenc_gpu_test_hash(self.ctx, (C.c_void_p * 3)(*[_p(a).value for a in r]), _hash_id(hash_type),
                                                  C.byref(out)))
         return out
@@ -608,7 +618,6 @@ class Encoder:
     def device_info(self):
         """(wavefronts of the search kernel the device holds at once, HIP streams an encode call uses)."""
         slots, lanes = C.c_longlong(), C.c_int()
-        self.lib.wrenc_gpu_device_info.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         self._check(self.lib.wrenc_gpu_device_info(self.ctx, C.byref(slots), C.byref(lanes)))
         return int(slots.value), int(lanes.value)
 
@@ -616,7 +625,6 @@ class Encoder:
         """Test entry: put a record (maps + level planes) into a slot as if a search had produced it."""
         keep = {k: np.ascontiguousarray(rec[k]) for k in ("lev_y", "lev_cb", "lev_cr", "cu_log2_size", "luma_mode", "chroma_mode")}
         pic = Picture(*[_p(keep[k]) if k in keep else None for k in _PIC_KEYS])
-        self.lib.wrenc_gpu_test_load_record.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         self._check(self.lib.wrenc_gpu_test_load_record(self.ctx, slot, C.byref(pic)))
 
     def expand_levels(self, mask, payload):
@@ -626,16 +634,12 @@ class Encoder:
         lcb = np.empty((h // 2, w // 2), np.int16)
         lcr = np.empty((h // 2, w // 2), np.int16)
         pay = np.ascontiguousarray(payload, np.int16)
-        self.lib.wrenc_gpu_expand_levels.restype = None
-        self.lib.wrenc_gpu_expand_levels.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         self.lib.wrenc_gpu_expand_levels(w, h, _p(mask), _p(pay), _p(ly), _p(lcb), _p(lcr))
         return ly, lcb, lcr
 
     def alloc_host(self, nbytes):
         """A page-locked uint8 array (wrenc_gpu_alloc_host): transfers from / to it run at PCIe rate.  Freed
         by close(); do not use it afterwards."""
-        self.lib.wrenc_gpu_alloc_host.restype = C.c_void_p
-        self.lib.wrenc_gpu_alloc_host.argtypes = [C.c_void_p, C.c_size_t]
         ptr = self.lib.wrenc_gpu_alloc_host(self.ctx, nbytes)
         if not ptr:
             raise WrencGpuError(-3, self.lib.wrenc_gpu_last_error(self.ctx).decode())
@@ -662,22 +666,18 @@ class Encoder:
 
     def set_schedule(self, schedule):
         """How CTUs map to wavefronts (include/wrenc_gpu.h: wrenc_gpu_schedule); results are the same either way."""
-        self.lib.wrenc_gpu_set_schedule.argtypes = [C.c_void_p, C.c_int]
         self._check(self.lib.wrenc_gpu_set_schedule(self.ctx, int(schedule)))
 
     def last_schedule(self):
-        self.lib.wrenc_gpu_last_schedule.argtypes = [C.c_void_p]
         return self.lib.wrenc_gpu_last_schedule(self.ctx)
 
     def test_set_wave_slots(self, slots):
         """Test entry: the wave-slot count AUTO compares a diagonal with (<= 0: the device's)."""
-        self.lib.wrenc_gpu_test_set_wave_slots.argtypes = [C.c_void_p, C.c_longlong]
         self._check(self.lib.wrenc_gpu_test_set_wave_slots(self.ctx, int(slots)))
 
     def test_scratch_overflows(self):
         """Test entry: workgroups that took a scratch region outside their XCD's partition (0 on MI355X)."""
         n = C.c_longlong(0)
-        self.lib.wrenc_gpu_test_scratch_overflows.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
         self._check(self.lib.wrenc_gpu_test_scratch_overflows(self.ctx, C.byref(n)))
         return int(n.value)
 
@@ -685,20 +685,17 @@ class Encoder:
         """Test entry: (counts[4], ranges[4][6]) of wrenc_gpu_test_head_ranges (include/wrenc_gpu.h)."""
         counts = (C.c_int * 4)()
         ranges = (C.c_int * 24)()
-        self.lib.wrenc_gpu_test_head_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         self._check(self.lib.wrenc_gpu_test_head_ranges(self.ctx, counts, ranges))
         return list(counts), np.array(list(ranges), dtype=np.int64).reshape(4, 6)
 
     def test_avail_tab(self):
         """Test entry: blocks whose table-derived segment availability differs from the reference's rules (must be 0)."""
         n = C.c_int(0)
-        self.lib.wrenc_gpu_test_avail_tab.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         self._check(self.lib.wrenc_gpu_test_avail_tab(self.ctx, C.byref(n)))
         return int(n.value)
 
     def stats_enable(self, on=True):
         """Per-launch timing events (measurement mode, see include/wrenc_gpu.h)."""
-        self.lib.wrenc_gpu_stats_enable.argtypes = [C.c_void_p, C.c_int]
         self._check(self.lib.wrenc_gpu_stats_enable(self.ctx, 1 if on else 0))
 
     def last_encode_stats(self):
@@ -711,7 +708,6 @@ class Encoder:
         class KS(C.Structure):
             _fields_ = [("ms_sum", C.c_float), ("launches", C.c_int32), ("ctu_pictures", C.c_int64)]
         out = (KS * 2)()
-        self.lib.wrenc_gpu_last_encode_kernel_stats.argtypes = [C.c_void_p, C.c_void_p]
         self._check(self.lib.wrenc_gpu_last_encode_kernel_stats(self.ctx, out))
         return {n: {"ms_sum": out[i].ms_sum, "launches": out[i].launches, "ctu_pictures": out[i].ctu_pictures}
                 for i, n in enumerate(("wave", "team"))}
@@ -738,8 +734,6 @@ class Encoder:
         assert arr.shape[1:] == (32, 32)
         out = np.zeros_like(arr)
         ms = C.c_float()
-        self.lib.wrenc_gpu_test_fwd_dct32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                                      C.POINTER(C.c_float)]
         self._check(self.lib.wrenc_gpu_test_fwd_dct32(self.ctx, _p(arr), arr.shape[0], _p(out), int(use_mfma), int(reps),
                                                       C.byref(ms)))
         return out, ms.value
@@ -750,8 +744,6 @@ class Encoder:
         assert arr.shape[1:] == (32, 32)
         out = np.zeros_like(arr)
         ms = C.c_float()
-        self.lib.wrenc_gpu_test_inv_dct32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                                      C.POINTER(C.c_float)]
         self._check(self.lib.wrenc_gpu_test_inv_dct32(self.ctx, _p(arr), arr.shape[0], _p(out), int(use_mfma), int(reps),
                                                       C.byref(ms)))
         return out, ms.value
@@ -782,8 +774,6 @@ class Encoder:
         count, nb, n, _ = arr.shape
         out = np.zeros_like(arr)
         ms = C.c_float()
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                       C.POINTER(C.c_float)]
         self._check(fn(self.ctx, _p(arr), int(n).bit_length() - 1, nb, int(o1), count, _p(out), int(use_mfma), int(reps),
                        C.byref(ms)))
         return out, ms.value
@@ -817,7 +807,6 @@ class Encoder:
         arr = np.ascontiguousarray(blocks, np.int16)
         assert arr.shape[1:] == (4, 4)
         out = np.zeros_like(arr)
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         self._check(fn(self.ctx, _p(arr), arr.shape[0], _p(out)))
         return out
 
@@ -829,24 +818,28 @@ class Encoder:
         """4x4 blocks of levels -> residuals: in-lane dequantisation at the context's QP + the register inverse transform."""
         return self._blocks4_reg(self.lib.wrenc_gpu_test_inv_dct4_reg, levels)
 
+    def _predict(self, rec_y, rec_cb, rec_cr, items):
+        """wrenc_gpu_test_predict on (n, 5) int32 items: (the output bytes, where each item's start: n + 1 offsets, by
+        wrenc_gpu_test_predict_layout -- a bad item is left to the entry itself to refuse)."""
+        planes = [np.ascontiguousarray(a, np.uint8) for a in (rec_y, rec_cb, rec_cr)]
+        assert planes[0].shape == (self.height, self.width)
+        at = np.zeros(len(items) + 1, np.uintp)
+        laid = self.lib.wrenc_gpu_test_predict_layout(self.width, self.height, len(items), _p(items), _p(at)) == 0
+        out = np.zeros(int(at[-1]) if laid else 1, np.uint8)
+        self._check(self.lib.wrenc_gpu_test_predict(self.ctx, _p(planes[0]), _p(planes[1]), _p(planes[2]), len(items),
+                                                    _p(items), _p(out), out.size))
+        return out, [int(v) for v in at]
+
     def predict_blocks(self, rec_y, rec_cb, rec_cr, items):
         """items: (n, 5) int32 {x, y, log2 luma size, comp (0 luma, 1 Cb+Cr pair, 2 luma 4x4 through the packed predictor
         of the 4x4 leaf search), mode}; returns the list of predicted blocks (luma: (n, n); pair: (2, n/2, n/2))."""
         items = np.ascontiguousarray(items, np.int32).reshape(-1, 5)
-        sizes = [((1 << int(q[2])) ** 2) // (2 if q[3] == 1 else 1) for q in items]
-        out = np.zeros(int(sum(sizes)), np.uint8)
-        planes = [np.ascontiguousarray(a, np.uint8) for a in (rec_y, rec_cb, rec_cr)]
-        assert planes[0].shape == (self.height, self.width)
-        self.lib.wrenc_gpu_test_predict.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                                    C.c_void_p, C.c_size_t]
-        self._check(self.lib.wrenc_gpu_test_predict(self.ctx, _p(planes[0]), _p(planes[1]), _p(planes[2]), len(items),
-                                                    _p(items), _p(out), out.size))
-        res, at = [], 0
-        for q, sz in zip(items, sizes):
+        out, at = self._predict(rec_y, rec_cb, rec_cr, items)
+        res = []
+        for k, q in enumerate(items):
             n = 1 << int(q[2])
-            blk = out[at:at + sz]
+            blk = out[at[k]:at[k + 1]]
             res.append(blk.reshape(2, n // 2, n // 2) if q[3] == 1 else blk.reshape(n, n))
-            at += sz
         return res
 
     NO_MODE = 255   # a pack candidate that is not evaluated (dev_predict.h, kNoMode): rides along as zeros
@@ -869,23 +862,14 @@ class Encoder:
         int16 arrays of shape (n, n) (kind 8), (2, n/2, n/2) (9), (candidates, 8, 8) (10); kind 11: each a pair
         (luma (candidates, 16, 16), chroma (candidates, 2, 8, 8))."""
         items = np.ascontiguousarray(items, np.int32).reshape(-1, 5)
-        sizes = []
-        for q in items:
-            nn, kind, nc = (1 << int(q[2])) ** 2, int(q[3]), int(q[4]) >> 24
-            assert kind in (8, 9, 10, 11)
-            sizes.append({8: nn, 9: nn // 2, 10: 64 * nc, 11: 384 * nc}[kind])
-        out = np.zeros(3 * int(sum(sizes)), np.uint8)
-        planes = [np.ascontiguousarray(a, np.uint8) for a in (rec_y, rec_cb, rec_cr)]
-        assert planes[0].shape == (self.height, self.width)
-        self.lib.wrenc_gpu_test_predict.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                                    C.c_void_p, C.c_size_t]
-        self._check(self.lib.wrenc_gpu_test_predict(self.ctx, _p(planes[0]), _p(planes[1]), _p(planes[2]), len(items),
-                                                    _p(items), _p(out), out.size))
-        res, at = [], 0
-        for q, sz in zip(items, sizes):
+        assert all(int(q[3]) in (8, 9, 10, 11) for q in items)
+        out, at = self._predict(rec_y, rec_cb, rec_cr, items)
+        res = []
+        for k, q in enumerate(items):
             n, kind, nc = 1 << int(q[2]), int(q[3]), int(q[4]) >> 24
+            sz = (at[k + 1] - at[k]) // 3                 # prediction bytes, then as many int16 residuals
             pair = []
-            for arr in (out[at:at + sz], out[at + sz:at + 3 * sz].view(np.int16)):
+            for arr in (out[at[k]:at[k] + sz], out[at[k] + sz:at[k + 1]].view(np.int16)):
                 if kind == 8:
                     pair.append(arr.reshape(n, n))
                 elif kind == 9:
@@ -895,7 +879,6 @@ class Encoder:
                 else:
                     pair.append((arr[:256 * nc].reshape(nc, 16, 16), arr[256 * nc:].reshape(nc, 2, 8, 8)))
             res.append(tuple(pair))
-            at += 3 * sz
         return res
 
     def sad_lists(self, rec_y, rec_cb, rec_cr, items):
@@ -907,13 +890,7 @@ class Encoder:
         dev[:, :3] = it[:, :3]
         dev[:, 3] = np.where(it[:, 3] == 4, 7, 3 + it[:, 3])   # comps 4: the CCLM list of the chroma pair (lanes 0..2: LT, T, L)
         dev[:, 4] = np.where(it[:, 3] == 4, 0, it[:, 4] | (it[:, 5] << 8) | (it[:, 6] << 16))
-        out = np.zeros(64 * len(it), np.uint8)
-        planes = [np.ascontiguousarray(a, np.uint8) for a in (rec_y, rec_cb, rec_cr)]
-        assert planes[0].shape == (self.height, self.width)
-        self.lib.wrenc_gpu_test_predict.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                                    C.c_void_p, C.c_size_t]
-        self._check(self.lib.wrenc_gpu_test_predict(self.ctx, _p(planes[0]), _p(planes[1]), _p(planes[2]), len(dev),
-                                                    _p(dev), _p(out), out.size))
+        out, _ = self._predict(rec_y, rec_cb, rec_cr, dev)
         return out.view(np.uint32).reshape(len(it), 16)
 
     def quantize_p16(self, blocks):
@@ -923,7 +900,6 @@ class Encoder:
         assert n == 4
         out = np.zeros_like(arr)
         cost = np.zeros(count, np.int64)
-        self.lib.wrenc_gpu_test_quantize_p16.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         self._check(self.lib.wrenc_gpu_test_quantize_p16(self.ctx, _p(arr), count, _p(out), _p(cost)))
         return out, cost
 
@@ -935,7 +911,6 @@ class Encoder:
         assert arr.shape[1] == nc * 3 * (1 << (2 * log2n)) // 2
         out = np.zeros_like(arr)
         cost = np.zeros((n_packs, nc, 2), np.int64)
-        self.lib.wrenc_gpu_test_quantize_pk.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         self._check(self.lib.wrenc_gpu_test_quantize_pk(self.ctx, _p(arr), int(log2n), int(nc), n_packs, _p(out), _p(cost)))
         return out, cost
 
