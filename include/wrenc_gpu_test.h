@@ -108,6 +108,12 @@ int wrenc_gpu_test_inv_dct_mfma(wrenc_gpu_ctx* ctx, const int16_t* deq, int log2
 int wrenc_gpu_test_fwd_dct4_reg(wrenc_gpu_ctx* ctx, const int16_t* res, int count, int16_t* coef);
 int wrenc_gpu_test_inv_dct4_reg(wrenc_gpu_ctx* ctx, const int16_t* levels, int count, int16_t* res);
 
+/* The row reconstruction of the full candidates and the 16x16 packs (wrenc_amd/csrc/dev_predict.h recon_row4): `count`
+ * rows of four samples, one per lane.  pred, org: 4 bytes per row; res: 4 int16 per row, any value.  rec: the four
+ * reconstructed bytes of each row, clamp((int16)(pred + res)); ssd[row]: the row's squared error against org. */
+int wrenc_gpu_test_recon_rows(wrenc_gpu_ctx* ctx, const uint8_t* pred, const int16_t* res, const uint8_t* org, int count,
+                              uint8_t* rec, uint32_t* ssd);
+
 /* Intra prediction of single blocks (intra_predictor.rs:56-144: reference-sample build :146-353, PLANAR
  * :759-1146, DC :1148-1285, ANGULAR 2..66 :1287-1602, PDPC :355-757, CCLM :1604-2055) in the environment of
  * given reconstruction planes of the context's picture size.  items: n_items x 5 int32 {x, y (luma, picture

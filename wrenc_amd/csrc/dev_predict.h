@@ -683,15 +683,23 @@ __device__ __forceinline__ uint32_t ang_row4(const AngPar& p, bool luma, const u
         const bool pdpc = c0 < (3 << p.n_scale);
         const int side = p.vertical ? oL + 1 : oA;
         const int alrs = SH.refs[oL];
+        int sv[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const int wp = pdpc ? pdpc_w(p.n_scale, c0 + k) : 0;
             const int dk = p.kind == 1 ? 0 : ((M24(c0 + k + 1, p.inv_angle) + 256) >> 9);
-            const int sv = SH.refs[side + (pdpc ? along + dk : 0)];
-            const int rs = p.kind == 1 ? (int)(int16_t)(sv - alrs + v[k]) : sv;
-            const int pv = (int16_t)(M24(rs, wp) + M24(64 - wp, v[k]) + 32) >> 6;
-            v[k] = min(max(pv, 0), 255);
+            sv[k] = SH.refs[side + (pdpc ? along + dk : 0)];
         }
+        // the blend two samples at a time (dev_pk16.h).  Past 3 << n_scale the weight is 0 by its own formula --
+        // (2 c) >> n_scale >= 6 there -- so `pdpc` guards the reads above and nothing else.
+        pk16 out[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const pk16 w = pk16_pdpc_w2(p.n_scale, pk16_positions(c0 + 2 * h));
+            const pk16 vv = {(short)v[2 * h], (short)v[2 * h + 1]}, s = {(short)sv[2 * h], (short)sv[2 * h + 1]};
+            const pk16 rs = p.kind == 1 ? pk16_add_wrap(s - pk16_splat(alrs), vv) : s;
+            out[h] = pk16_clamp255(pk16_pdpc_blend(rs, w, pk16_splat(64) - w, vv));
+        }
+        return pk16_pack(out[0], out[1]);
     }
     return pack4(v);
 }
@@ -704,22 +712,17 @@ __device__ __forceinline__ uint32_t planar_dc_row4(int mode, int lg, int oL, int
     const int ly = SH.refs[oL + y + 1];
     const int lb = SH.refs[oL + n + 1], an = SH.refs[oA + n];
     const int wt = pdpc_w(n_scale, y);
-    int v[4];
+    // two samples at a time (dev_pk16.h): what depends on the row alone as scalars, what depends on x as pairs
+    const int dl = an - ly, kk = M24(n - 1, ly) + an + M24(y + 1, lb) + n;
+    pk16 v[2];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int x = x0 + k;
-        const int ax = (int)((a4 >> (8 * k)) & 255u);
-        int p = dcv;
-        if (mode == PLANAR) {
-            const int pv = M24(n - 1 - y, ax) + M24(y + 1, lb);
-            const int ph = M24(n - 1 - x, ly) + M24(x + 1, an);
-            p = ((pv + ph + n) >> (lg + 1)) & 0xFF;
-        }
-        const int wl = pdpc_w(n_scale, x);
-        p = (int16_t)(M24(ly, wl) + M24(ax, wt) + M24(64 - wt - wl, p) + 32) >> 6;
-        v[k] = min(max(p, 0), 255);
+    for (int h = 0; h < 2; ++h) {
+        const pk16 ax = h ? pk16_hi(a4) : pk16_lo(a4);
+        const pk16 pos = pk16_positions(x0 + 2 * h);
+        const pk16 p = mode == PLANAR ? pk16_planar2(ax, pos, n - 1 - y, dl, kk, lg) : pk16_splat(dcv);
+        v[h] = pk16_planar_dc_blend(ax, p, pk16_pdpc_w2(n_scale, pos), ly, wt);
     }
-    return pack4(v);
+    return pk16_pack(v[0], v[1]);
 }
 
 // Prediction of a FULL candidate: one luma block (comp 0) or the Cb+Cr pair (comp 1), the arithmetic and the results of
@@ -1220,14 +1223,22 @@ __device__ WRENC_SAD_INLINE unsigned sad_list_angular(const Ctx& c, int comps, i
                 const ref_t* side = SH.refs + (vertical ? oL + 1 : oA);
                 const int alrs = SH.refs[oL];
                 const int tb = (((mic << cs) + blk) << lgs) + n + c0;
-                // per sample across the direction (k): the PDPC weight, 0 for a lane without PDPC or beyond its reach, and
-                // where its reference sits relative to `along`
-                int wp[4], dk[4];
+                // per sample across the direction (k): where its PDPC reference sits relative to `along`
+                int dk[4];
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    wp[k] = pdpc ? pdpc_w(n_scale, c0 + k) : 0;
-                    dk[k] = kind == 1 ? 0 : ((M24(c0 + k + 1, inv_angle) + 256) >> 9);
+                for (int k = 0; k < 4; ++k) dk[k] = kind == 1 ? 0 : ((M24(c0 + k + 1, inv_angle) + 256) >> 9);
+#ifndef WRENC_EXP_OLD_PDPC
+                // per pair of samples (h), once per entry (dev_pk16.h, pk16_pdpc_blend_folded): the PDPC weight w, 0 for a
+                // lane without PDPC or beyond its reach, and what the blend multiplies and adds besides -- mode 18 / 50
+                // blends side - corner + v, which moves w from the reference's factor to v's and the corner to the constant
+                pk16 wq[2], wa[2], wc[2];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    wq[h] = pdpc ? pk16_pdpc_w2(n_scale, pk16_positions(c0 + 2 * h)) : pk16_splat(0);
+                    wa[h] = kind == 1 ? pk16_splat(64) : pk16_splat(64) - wq[h];
+                    wc[h] = kind == 1 ? pk16_mad(wq[h], pk16_splat(-alrs), pk16_splat(32)) : pk16_splat(32);
                 }
+#endif
                 int sad = 0;
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
@@ -1263,21 +1274,23 @@ __device__ WRENC_SAD_INLINE unsigned sad_list_angular(const Ctx& c, int comps, i
                             v[k] = min(max(pv_, 0), 255);
                         }
                     }
-                    if (false) {
-                        for (int k = 0; k < 4; ++k) {
+                    uint32_t packed = pack4(v);
 #else
+                    uint32_t packed;
                     if (any_pdpc) { // (wave-uniform; inside it every lane runs the same code: a lane without PDPC weighs by 0,
                                     // as does a sample beyond 3 << n_scale, so what is read for those does not matter)
+                        pk16 out[2];
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-#endif
-                            const int sv = side[pdpc ? along + dk[k] : 0];
-                            const int rs = kind == 1 ? (int)(int16_t)(sv - alrs + v[k]) : sv;
-                            const int pv = (int16_t)(M24(rs, wp[k]) + M24(64 - wp[k], v[k]) + 32) >> 6;
-                            v[k] = min(max(pv, 0), 255);
+                        for (int h = 0; h < 2; ++h) {
+                            const pk16 s = {(short)side[pdpc ? along + dk[2 * h] : 0], (short)side[pdpc ? along + dk[2 * h + 1] : 0]};
+                            const pk16 vv = {(short)v[2 * h], (short)v[2 * h + 1]};
+                            out[h] = pk16_clamp255(pk16_pdpc_blend_folded(s, wq[h], vv, wa[h], wc[h]));
                         }
+                        packed = pk16_pack(out[0], out[1]);
+                    } else {
+                        packed = pack4(v);
                     }
-                    const uint32_t packed = (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16) | ((uint32_t)v[3] << 24);
+#endif
                     const uint32_t org = vertical ? (r == 0 ? o0 : (r == 1 ? o1 : (r == 2 ? o2 : o3)))
                                                   : (r == 0 ? t0 : (r == 1 ? t1 : (r == 2 ? t2 : t3)));
                     sad = (int)__builtin_amdgcn_sad_u8(packed, org, (uint32_t)sad);

@@ -14,6 +14,7 @@
 // What is computed follows the reference function by function (paths relative to the reference's
 // src/, cited at each function); how it is computed is wave-parallel:
 //   dev_predict.h    intra_predictor.rs:56-2055     lane = sample; SAD lists of many modes in one loop
+//   dev_pk16.h       (helpers of the rows)          two samples of a row per 16-bit packed instruction
 //   dev_transform.h  transformer.rs:2040-2737       lane = basis row, v_dot2 / v_mad_i24
 //   dev_quant.h      quantizer.rs:338-759           backward 4-state Viterbi, one lane per state, DPP
 //   dev_search.h     block_splitter.rs:64-1154, ctu_encoder.rs:1421-1461
@@ -39,6 +40,7 @@
 #include <stdint.h>
 
 #include "dev_common.h"
+#include "dev_pk16.h"
 #include "dev_predict.h"
 #include "dev_transform.h"
 #include "dev_scan.h"

@@ -216,6 +216,17 @@ __global__ __launch_bounds__(64) void test_dct4_reg_kernel(const DevConst* __res
     if (mine) out[at] = (int16_t)r;
 }
 
+// recon_row4 (dev_predict.h): one row of four samples per lane, the lanes past the last row neither load nor store
+__global__ __launch_bounds__(64) void test_recon_rows_kernel(const uint32_t* pred, const uint2* res, const uint32_t* org, int count,
+                                                             uint32_t* rec, uint32_t* ssd) {
+    const size_t at = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (at >= (size_t)count) return;
+    unsigned s = 0;
+    int v[4];
+    rec[at] = recon_row4(pred[at], res[at], org[at], v, s);
+    ssd[at] = s;
+}
+
 // quantize_pk (the packed leaf searches' quantiser): one wave per pack of nc candidates
 __global__ __launch_bounds__(64) void test_quantize_pk_kernel(const DevConst* __restrict__ k, const int16_t* in, int lgl, int nc,
                                                               int16_t* out, long long* cost, int* overflow) {
@@ -786,6 +797,20 @@ int wrenc_gpu_test_quantize_pk(wrenc_gpu_ctx* ctx, const int16_t* coef, int log2
                            out.as<int16_t>(), cost.as<long long>(), ctx->d_overflow.get() + 1);
         return hipSuccess;
     }));
+}
+
+int wrenc_gpu_test_recon_rows(wrenc_gpu_ctx* ctx, const uint8_t* pred, const int16_t* res, const uint8_t* org, int count,
+                              uint8_t* rec, uint32_t* ssd) {
+    if (!ctx || !pred || !res || !org || !rec || !ssd) return WRENC_GPU_EINVAL;
+    if (count < 1) return fail(ctx, WRENC_GPU_EINVAL, "count must be >= 1");
+    const size_t n = (size_t)count * 4;
+    TestBuf d_pred = buf_in(pred, n), d_res = buf_in(res, n), d_org = buf_in(org, n), d_rec = buf_out(rec, n),
+            d_ssd = buf_out(ssd, (size_t)count);
+    return run_on_stream(ctx, {&d_pred, &d_res, &d_org, &d_rec, &d_ssd}, [&](hipStream_t st) {
+        hipLaunchKernelGGL(test_recon_rows_kernel, dim3((count + 63) / 64), dim3(64), 0, st, d_pred.as<uint32_t>(), d_res.as<uint2>(),
+                           d_org.as<uint32_t>(), count, d_rec.as<uint32_t>(), d_ssd.as<uint32_t>());
+        return hipSuccess;
+    });
 }
 
 int wrenc_gpu_test_predict_layout(int width, int height, int n_items, const int32_t* items, size_t* offsets) {

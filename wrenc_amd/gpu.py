@@ -92,6 +92,7 @@ PROTOTYPES = {
     "wrenc_gpu_test_inv_dct4_reg": (_I, [_P, _P, _I, _P]),
     "wrenc_gpu_test_quantize_p16": (_I, [_P, _P, _I, _P, _P]),
     "wrenc_gpu_test_quantize_pk": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "wrenc_gpu_test_recon_rows": (_I, [_P, _P, _P, _P, _I, _P, _P]),
     "wrenc_gpu_test_predict": (_I, [_P, _P, _P, _P, _I, _P, _P, _Z]),
     "wrenc_gpu_test_predict_layout": (_I, [_I, _I, _I, _P, _P]),
 }
@@ -817,6 +818,17 @@ class Encoder:
     def inv_dct4_reg(self, levels):
         """4x4 blocks of levels -> residuals: in-lane dequantisation at the context's QP + the register inverse transform."""
         return self._blocks4_reg(self.lib.wrenc_gpu_test_inv_dct4_reg, levels)
+
+    def recon_rows(self, pred, res, org):
+        """Rows of four samples through the search's row reconstruction: pred, org (n, 4) uint8, res (n, 4) int16 (any
+        value) -> (reconstruction (n, 4) uint8, squared error per row (n,) uint32)."""
+        pred, org = (np.ascontiguousarray(a, np.uint8) for a in (pred, org))
+        res = np.ascontiguousarray(res, np.int16)
+        assert pred.ndim == 2 and pred.shape[1] == 4 and res.shape == pred.shape == org.shape
+        rec = np.zeros_like(pred)
+        ssd = np.zeros(pred.shape[0], np.uint32)
+        self._check(self.lib.wrenc_gpu_test_recon_rows(self.ctx, _p(pred), _p(res), _p(org), pred.shape[0], _p(rec), _p(ssd)))
+        return rec, ssd
 
     def _predict(self, rec_y, rec_cb, rec_cr, items):
         """wrenc_gpu_test_predict on (n, 5) int32 items: (the output bytes, where each item's start: n + 1 offsets, by
