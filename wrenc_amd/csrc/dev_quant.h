@@ -72,16 +72,6 @@ __device__ __forceinline__ int position_map(int tc, int qd, bool dcn, int nib) {
 // single comparison KB < KA (KA = u + CA, KB = w + CB) is exact: choseB == pick1 ^ par.
 constexpr int kNoBranch = 1 << 27;
 
-// lambda_q * dq_table[idx] (quantizer.rs:29-31): the first 256 entries are in LDS; larger levels are
-// rare, and a wave without any takes no branch
-__device__ __forceinline__ int ldq_fast(const Ctx& c, int idx) {
-    int v = SHT.ldq[min(idx, 255)];
-    if (__ballot(idx > 255) != 0ULL) {
-        if (idx > 255) v = (int)c.k->ldq[idx];
-    }
-    return v;
-}
-
 // |(tc << sh) - off| / lsc, the quotient every decision of a position starts from (quantizer.rs:378, :441); 0 for a
 // zero coefficient.  Recomputed where it is needed (a shift, one v_mul_hi_u32 by a 32-bit reciprocal, a shift) rather
 // than kept per position: the 2 KB that array took are what lets a fifth workgroup fit the CU's LDS.
@@ -89,6 +79,18 @@ __device__ __forceinline__ int quotient(const CONST_AS DevConst* k, int tc, int 
     int S = (int)((unsigned)tc << sh) - off;
     if (tc < 0) S = -S;
     return tc == 0 ? 0 : (int)(__umulhi((unsigned)S, k->div_magic) >> k->div_shift);
+}
+
+// A trace lane's at most four positions: coefficient, quotient and decision nibble.  The forward trace needs them twice,
+// for the state map and for emit_level, with the levels' stores to r1 in between: kept in registers, they are read from
+// LDS and divided once.
+struct TracePos {
+    int tc[4], qd[4], nib[4];
+};
+__device__ __forceinline__ void trace_pos_load(TracePos& t, int j, const CONST_AS DevConst* k, int tc, int sh, int off, DecMasks dm, int p) {
+    t.tc[j] = tc;
+    t.qd[j] = quotient(k, tc, sh, off);
+    t.nib[j] = dec_nib(dm, p);
 }
 
 // Chunk entry of one position (see the comment above kNoBranch): writes (u, w) of the three state
@@ -101,6 +103,21 @@ __device__ __forceinline__ void chunk_entry(const Ctx& c, int* en, int tc, int q
                                             int* ovf) {
     const bool nz = tc != 0;
     int c0d[2], c1d[2], par[2];
+    // lambda_q * dq_table[idx] (quantizer.rs:29-31) of the position's four levels: idx = min(a0 + 1, 1023) and min(a0 + 2, 1023)
+    // in the two delta classes, and class 1's a0 is class 0's (a) or a + 1 -- three consecutive entries a + 1 .. a + 3, read
+    // once and selected by the parity of qd.  The first 256 entries are in LDS; larger levels are rare, and a wave without
+    // any takes no branch (one test for the three).
+    const int a = qd >> 1;
+    const int e = (!dcn && (qd & 1)) ? 1 : 0;     // a0 of class 1 - a0 of class 0
+    const int32_t* tq = &SHT.ldq[min(a, 252)];
+    int t1 = tq[1], t2 = tq[2], t3 = tq[3];
+    if (__ballot(a > 252) != 0ULL) {
+        if (a > 252) {
+            t1 = (int)ldq_at(c, min(a + 1, 1023));
+            t2 = (int)ldq_at(c, min(a + 2, 1023));
+            t3 = (int)ldq_at(c, min(a + 3, 1023));
+        }
+    }
 #pragma unroll
     for (int d = 0; d < 2; ++d) {
         const int a0 = (qd + (dcn ? 0 : d)) >> 1; // quantizer.rs:378 / :441
@@ -115,7 +132,7 @@ __device__ __forceinline__ void chunk_entry(const Ctx& c, int* en, int tc, int q
         const int d0 = abs(tc - ((M24(q0, lsc) + off) >> sh)); // |q| <= 2047, lsc < 2^21
         const int d1 = abs(tc - ((M24(q1, lsc) + off) >> sh));
         if (nz && a1 + 1 >= 1024) *ovf = 1;
-        const int l0 = ldq_fast(c, min(a0 + 1, 1023)), l1 = ldq_fast(c, min(a1 + 1, 1023));
+        const int l0 = (d && e) ? t2 : t1, l1 = (d && e) ? t3 : t2;
         c0d[d] = nz ? 128 * d0 + l0 : ldq1;       // zero coefficient outside the trailing run: dq_table[1] (:433)
         c1d[d] = nz ? 128 * d1 + l1 : kNoBranch;
         par[d] = nz ? (a0 & 1) : 0;               // parity of a0 -> which successor state
@@ -137,7 +154,8 @@ __device__ __forceinline__ void chunk_entry(const Ctx& c, int* en, int tc, int q
     *adj_out = (tzp && zero0) ? 1 : 0;
 }
 
-// level-cost table (block_splitter.rs:436-458), same access pattern as ldq_fast
+// level-cost table (block_splitter.rs:436-458): the first 256 entries are in LDS; larger levels are rare, and a wave
+// without any takes no branch
 __device__ __forceinline__ int lv_fast(const Ctx& c, int a) {
     int v = SHT.lv[min(a, 255)];
     if (__ballot(a > 255) != 0ULL) {
@@ -428,6 +446,9 @@ __device__ __forceinline__ long long quantize_solo(Ctx c, int lg, int nb, int* o
     for (int base = P - CH; base >= 0 && base + CH > 16 * lowest; base -= CH) {
         PROF_MARK(qb0_);
         WSYNC();
+        // parities of a0 in the two delta classes and the state-0 flag of the chunk's positions, bit = lane = position
+        // blk * CH + i: wave-uniform, and this wave walks, so the walkers take their 16-bit slices from these registers
+        unsigned long long b0, b1, ba;
         {
             const bool mine = LANE < nb * CH;
             const int blk = LANE >= CH ? 1 : 0;
@@ -439,13 +460,9 @@ __device__ __forceinline__ long long quantize_solo(Ctx c, int lg, int nb, int* o
                 chunk_entry(c, cc + LANE * 6, tc, quotient(k, tc, sh, off), p == P - 1, p <= (blk ? istar1 : istar0),
                             sh, off, lsc, ldq1, &par0, &par1, &adj, &ovf);
             }
-            const unsigned long long b0 = __ballot(mine && par0), b1 = __ballot(mine && par1), ba = __ballot(mine && adj);
-            if (mine && (LANE & 15) == 0) {
-                uint16_t* pm = SH.q_pm[blk][i >> 4];
-                pm[0] = (uint16_t)(b0 >> LANE);
-                pm[1] = (uint16_t)(b1 >> LANE);
-                pm[2] = (uint16_t)((ba >> (LANE + 15)) & 1);
-            }
+            b0 = __ballot(mine && par0);
+            b1 = __ballot(mine && par1);
+            ba = __ballot(mine && adj);
         }
         WSYNC();
         PROF_MARK(qb1_);
@@ -453,9 +470,9 @@ __device__ __forceinline__ long long quantize_solo(Ctx c, int lg, int nb, int* o
             for (int g16 = CH - 16; g16 >= 0; g16 -= 16) { // one 4x4 sub-block per iteration
                 const int sb = (base + g16) >> 4;
                 if (sb < lowest) break;                     // (uniform) every block's head is proven zero from here on
-                const uint16_t* pm = SH.q_pm[wblk][g16 >> 4];
-                const unsigned parmask = pm[st > 1 ? 1 : 0];
-                const bool adj = st == 0 && pm[2] != 0;
+                const int at = wblk * CH + g16;             // the sub-block's first lane of the chunk
+                const unsigned parmask = (uint16_t)((st > 1 ? b1 : b0) >> at);
+                const bool adj = st == 0 && ((ba >> (at + 15)) & 1ULL) != 0ULL;
                 int2 cur[16];
 #pragma unroll
                 for (int kk = 0; kk < 16; ++kk) cur[kk] = *(const int2*)&wcc[(g16 + kk) * 6 + 2 * cls];
@@ -514,7 +531,19 @@ __device__ __forceinline__ long long quantize_solo(Ctx c, int lg, int nb, int* o
     int fmap = kMapId;
     const DecMasks dm = dec_masks(bdec, act ? p0 : 0); // a lane's positions lie in one sub-block (per divides 16)
     const int org = blk * P + scan_sb_origin(lg, act ? p0 >> 4 : 0); // ... whose levels go to raster org + the position's offset
-    if (act) {
+    // (uniform) no lane has more than four positions -- what is left of a chain below its proven head seldom is more than
+    // 256 positions: they stay in registers for emit_level (TracePos)
+    const bool few = __ballot(per > 4) == 0ULL;
+    TracePos tp;
+    if (few) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (!(act && j < per)) continue;
+            const int p = p0 + j;
+            trace_pos_load(tp, j, k, btcs[p], sh, off, dm, p);
+            fmap = compose_map(position_map(tp.tc[j], tp.qd[j], p == P - 1, tp.nib[j]), fmap);
+        }
+    } else if (act) {
         for (int j = 0; j < per; ++j) {
             const int p = p0 + j;
             const int tc = btcs[p];
@@ -533,7 +562,16 @@ __device__ __forceinline__ long long quantize_solo(Ctx c, int lg, int nb, int* o
     long long sum_nz = 0;
     unsigned zmask = 0;
     int fnz = P;
-    if (act) {
+    if (few) {
+        int state = entry;
+        const unsigned long long nibs = scan_nibs_from(p0 & 15);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (!(act && j < per)) continue;
+            SH.r1[org + scan_nib_offset(lg, (int)(nibs >> (4 * j)) & 15)] =
+                (int16_t)emit_level(c, tp.tc[j], tp.qd[j], p0 + j == P - 1, tp.nib[j], p0 + j, j, state, zmask, sum_nz, fnz, ovf);
+        }
+    } else if (act) {
         int state = entry;
         unsigned long long nibs = scan_nibs_from(p0 & 15);
         for (int j = 0; j < per; ++j, nibs >>= 4) {
@@ -599,16 +637,13 @@ __device__ __forceinline__ int quantize_p16_reg(Ctx c, int nb, int coef, int* ov
     const int qd = quotient(k, tc, sh, off); // (0 for a lane without a block)
     const int ldq1 = (int)ldq_at(c, 1);
     int ovf = 0;
+    unsigned long long b0, b1, ba; // parities and state-0 flag, bit = lane = position 16 blk + p (see quantize_solo)
     {
         int par0 = 0, par1 = 0, adj = 0;
         if (mine) chunk_entry(c, cc + lane * 6, tc, qd, p == P - 1, p <= istar, sh, off, lsc, ldq1, &par0, &par1, &adj, &ovf);
-        const unsigned long long b0 = __ballot(mine && par0), b1 = __ballot(mine && par1), ba = __ballot(mine && adj);
-        if (mine && p == 0) {
-            uint16_t* pm = SH.q_pm[0][blk];
-            pm[0] = (uint16_t)(b0 >> lane);
-            pm[1] = (uint16_t)(b1 >> lane);
-            pm[2] = (uint16_t)((ba >> (lane + 15)) & 1);
-        }
+        b0 = __ballot(mine && par0);
+        b1 = __ballot(mine && par1);
+        ba = __ballot(mine && adj);
     }
     WSYNC();
     PROF_MARK(qb1_);
@@ -618,9 +653,8 @@ __device__ __forceinline__ int quantize_p16_reg(Ctx c, int nb, int coef, int* ov
         if (quad < nb) {
             const int cls = st == 0 ? 0 : (st == 1 ? 1 : 2);
             const int32_t* wcc = cc + quad * P * 6;
-            const uint16_t* pm = SH.q_pm[0][quad];
-            const unsigned parmask = pm[st > 1 ? 1 : 0];
-            const bool adj = st == 0 && pm[2] != 0;
+            const unsigned parmask = (uint16_t)((st > 1 ? b1 : b0) >> (16 * quad));
+            const bool adj = st == 0 && ((ba >> (16 * quad + 15)) & 1ULL) != 0ULL;
             int2 cur[16];
 #pragma unroll
             for (int kk = 0; kk < 16; ++kk) cur[kk] = *(const int2*)&wcc[kk * 6 + 2 * cls];
@@ -709,7 +743,7 @@ __device__ __forceinline__ int dequantize4_lane(const Ctx& c, int level) {
 // cost of the luma block and of the chroma pair (block_splitter.rs:436-458) and whether any level of the pack's luma /
 // chroma blocks is non-zero.  A chroma trace pass runs only where one of its chains has something to trace: a chain
 // proven zero from end to end keeps the zeros of the zero-fill, costs nothing and has no level.
-// Scratch: r2[0, 3 PL nc) scan-order coefficients, r1 chunk entries, decw decisions (72 / 192 u16), q_pm.
+// Scratch: r2[0, 3 PL nc) scan-order coefficients, r1 chunk entries, decw decisions (72 / 192 u16), q_pm[1] (ist).
 // ---------------------------------------------------------------------------
 
 // forward trace + level cost of up to four blocks of 64 positions, block b = row b (16 lanes, four consecutive
@@ -730,12 +764,13 @@ __device__ __forceinline__ void trace_rows64(const Ctx& c, int nblk, const int16
     const DecMasks dm = dec_masks(dec16 + b * 16, act ? p0 : 0);
     const int org = rbase + b * 64 + scan_sb_origin_ct<3>(act ? p0 >> 4 : 0);
     int fmap = kMapId;
-    if (act) {
-        for (int j = 0; j < per; ++j) {
-            const int p = p0 + j;
-            const int tc = btcs[p];
-            fmap = compose_map(position_map(tc, quotient(k, tc, sh, off), p == 63, dec_nib(dm, p)), fmap);
-        }
+    TracePos tp;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (!(act && j < per)) continue;
+        const int p = p0 + j;
+        trace_pos_load(tp, j, k, btcs[p], sh, off, dm, p);
+        fmap = compose_map(position_map(tp.tc[j], tp.qd[j], p == 63, tp.nib[j]), fmap);
     }
     int pre = fmap;
     pre = compose_map(pre, __builtin_amdgcn_update_dpp(kMapId, pre, 0x111, 0xF, 0xF, false)); // row_shr:1
@@ -747,14 +782,14 @@ __device__ __forceinline__ void trace_rows64(const Ctx& c, int nblk, const int16
     long long sum_nz = 0;
     unsigned zmask = 0;
     int fnz = 64;
-    if (act) {
+    {
         int state = entry;
-        unsigned long long nibs = scan_nibs_from(p0 & 15);
-        for (int j = 0; j < per; ++j, nibs >>= 4) {
-            const int p = p0 + j;
-            const int tc = btcs[p];
-            SH.r1[org + scan_nib_offset(3, (int)nibs & 15)] = (int16_t)emit_level(c, tc, quotient(k, tc, sh, off), p == 63, dec_nib(dm, p), p, j,
-                                                                                 state, zmask, sum_nz, fnz, ovf);
+        const unsigned long long nibs = scan_nibs_from(p0 & 15);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (!(act && j < per)) continue;
+            SH.r1[org + scan_nib_offset(3, (int)(nibs >> (4 * j)) & 15)] =
+                (int16_t)emit_level(c, tp.tc[j], tp.qd[j], p0 + j == 63, tp.nib[j], p0 + j, j, state, zmask, sum_nz, fnz, ovf);
         }
     }
     const int pf = row_min_i32(fnz); // zeros before a block's first non-zero level cost nothing
@@ -823,12 +858,13 @@ __device__ __forceinline__ void trace_wave256(const Ctx& c, const int16_t* tcs, 
     const DecMasks dm = dec_masks(dec16, act ? p0 : 0);
     const int org = rbase + scan_sb_origin_ct<4>(act ? p0 >> 4 : 0);
     int fmap = kMapId;
-    if (act) {
-        for (int j = 0; j < per; ++j) {
-            const int p = p0 + j;
-            const int tc = tcs[p];
-            fmap = compose_map(position_map(tc, quotient(k, tc, sh, off), p == 255, dec_nib(dm, p)), fmap);
-        }
+    TracePos tp;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (!(act && j < per)) continue;
+        const int p = p0 + j;
+        trace_pos_load(tp, j, k, tcs[p], sh, off, dm, p);
+        fmap = compose_map(position_map(tp.tc[j], tp.qd[j], p == 255, tp.nib[j]), fmap);
     }
     int pre = fmap;
     pre = compose_map(pre, __builtin_amdgcn_update_dpp(kMapId, pre, 0x111, 0xF, 0xF, false)); // row_shr:1
@@ -842,14 +878,14 @@ __device__ __forceinline__ void trace_wave256(const Ctx& c, const int16_t* tcs, 
     long long sum_nz = 0;
     unsigned zmask = 0;
     int fnz = 256;
-    if (act) {
+    {
         int state = entry;
-        unsigned long long nibs = scan_nibs_from(p0 & 15);
-        for (int j = 0; j < per; ++j, nibs >>= 4) {
-            const int p = p0 + j;
-            const int tc = tcs[p];
-            SH.r1[org + scan_nib_offset(4, (int)nibs & 15)] = (int16_t)emit_level(c, tc, quotient(k, tc, sh, off), p == 255, dec_nib(dm, p), p, j,
-                                                                                 state, zmask, sum_nz, fnz, ovf);
+        const unsigned long long nibs = scan_nibs_from(p0 & 15);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (!(act && j < per)) continue;
+            SH.r1[org + scan_nib_offset(4, (int)(nibs >> (4 * j)) & 15)] =
+                (int16_t)emit_level(c, tp.tc[j], tp.qd[j], p0 + j == 255, tp.nib[j], p0 + j, j, state, zmask, sum_nz, fnz, ovf);
         }
     }
     const int pf = wave_min_i32(fnz);
@@ -1021,6 +1057,7 @@ __device__ __forceinline__ void quantize_pk(Ctx c, int nc, int* overflow, long l
         // this lane's row: chain, sub-block of the round
         const int myid = row == 0 ? rid[0] : (row == 1 ? rid[1] : (row == 2 ? rid[2] : rid[3]));
         const int mysb = (row == 0 ? rlow[0] + rleft[0] : (row == 1 ? rlow[1] + rleft[1] : (row == 2 ? rlow[2] + rleft[2] : rlow[3] + rleft[3]))) - 1;
+        unsigned long long b0, b1, ba; // parities and state-0 flag of the round, bit = lane = position 16 row + i16 (see quantize_solo)
         {
             const bool mine = myid >= 0;
             const bool is_l = myid < 4;
@@ -1033,13 +1070,9 @@ __device__ __forceinline__ void quantize_pk(Ctx c, int nc, int* overflow, long l
                 chunk_entry(c, cc + lane * 6, tc, quotient(k, tc, sh, off), p == (is_l ? PL - 1 : PC - 1), p <= first, sh, off, lsc, ldq1,
                             &par0, &par1, &adj, &ovf);
             }
-            const unsigned long long b0 = __ballot(mine && par0), b1 = __ballot(mine && par1), ba = __ballot(mine && adj);
-            if (mine && i16 == 0) {
-                uint16_t* pm = SH.q_pm[0][row];
-                pm[0] = (uint16_t)(b0 >> lane);
-                pm[1] = (uint16_t)(b1 >> lane);
-                pm[2] = (uint16_t)((ba >> (lane + 15)) & 1);
-            }
+            b0 = __ballot(mine && par0);
+            b1 = __ballot(mine && par1);
+            ba = __ballot(mine && adj);
         }
         WSYNC();
         PROF_MARK(qb1_);
@@ -1055,9 +1088,8 @@ __device__ __forceinline__ void quantize_pk(Ctx c, int nc, int* overflow, long l
                 if (wfresh) C = 0; // a new chain
                 const int wsb = wlow + wleft - 1;
                 const int32_t* wcc = cc + quad * 16 * 6;
-                const uint16_t* pm = SH.q_pm[0][quad];
-                const unsigned parmask = pm[st > 1 ? 1 : 0];
-                const bool adj = st == 0 && pm[2] != 0;
+                const unsigned parmask = (uint16_t)((st > 1 ? b1 : b0) >> (16 * quad));
+                const bool adj = st == 0 && ((ba >> (16 * quad + 15)) & 1ULL) != 0ULL;
                 int2 cur[16];
 #pragma unroll
                 for (int kk = 0; kk < 16; ++kk) cur[kk] = *(const int2*)&wcc[kk * 6 + 2 * cls];
