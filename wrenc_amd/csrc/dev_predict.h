@@ -554,6 +554,11 @@ __device__ __forceinline__ uint32_t refs_load4(int at) {
     const uint32_t* p = (const uint32_t*)(SH.refs + (at & ~3));
     return __builtin_amdgcn_alignbyte(p[1], p[0], at & 3);
 }
+// clip(x >> 6, 0, 255) for samples that pack4 then joins, clamped first and shifted as an unsigned value.  Written as a
+// shift followed by the clamp, two neighbours in straight-line code are compiled to one v_ashr_pk_u8_i32 whose result the
+// compiler ORs with the other two bytes as if its upper half were zero, and on the device it is not (dev_scale.h,
+// scale_clip8: the same finding).
+__device__ __forceinline__ int clip8_shr6(int x) { return (int)((uint32_t)min(max(x, 0), (256 << 6) - 1) >> 6); }
 __device__ __forceinline__ uint32_t pack4(const int (&v)[4]) {
     return (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16) | ((uint32_t)v[3] << 24);
 }
@@ -659,23 +664,30 @@ __device__ __forceinline__ uint8_t ang_table_entry(const AngPar& p, int n, int e
 // vertical modes, a column x for the horizontal ones), samples c0 .. c0 + 3 of it.  tab: the block's projected main
 // reference (dword-aligned).  The four share the projection (i_idx, i_fact), the filter word and one 7-byte window of the
 // table.  PDPC weighs by the position across the direction and is over after 3 << n_scale samples; its reference runs
-// along it: left[] = L + 1 for the vertical modes, above[] = A (as rows_per_lane of sad_list_angular).
-__device__ __forceinline__ uint32_t ang_row4(const AngPar& p, bool luma, const uint8_t* tab, int n, int oL, int oA,
-                                             int along, int c0) {
+// along it: left[] = L + 1 for the vertical modes, above[] = A (as rows_per_lane of sad_list_angular).  LUMA: the luma
+// filters (the word of the smoothing filter or of the table, by a select: every lane computes the one and reads the other)
+// with their clamp, or the two-tap chroma filter.
+template <bool LUMA>
+__device__ __forceinline__ uint32_t ang_row4(const AngPar& p, const uint8_t* tab, int n, int oL, int oA, int along, int c0) {
     const int pr = M24(along + 1, p.angle);
     const int i_idx = pr >> 5, i_fact = pr & 31;
     const int ta = n + c0 + i_idx; // the four samples' taps = ref[ta + k + 0..3]
     const uint32_t* tp = (const uint32_t*)(tab + (ta & ~3));
     const uint32_t w0 = tp[0], w1 = tp[1], w2 = tp[2];
     const uint32_t lo = __builtin_amdgcn_alignbyte(w1, w0, ta & 3), hi = __builtin_amdgcn_alignbyte(w2, w1, ta & 3);
-    const int wgt = luma ? (p.filter_flag ? 0x00102010 + (i_fact >> 1) * 0x0100FEFF : *(const int*)&SHT.fc[i_fact][0])
-                         : (((32 - i_fact) << 8) | (i_fact << 16));
+    int wgt;
+    if (LUMA) {
+        const int w_smooth = 0x00102010 + (i_fact >> 1) * 0x0100FEFF, w_tab = *(const int*)&SHT.fc[i_fact][0];
+        wgt = p.filter_flag ? w_smooth : w_tab;
+    } else {
+        wgt = ((32 - i_fact) << 8) | (i_fact << 16);
+    }
     int v[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int taps = (int)(k == 0 ? lo : __builtin_amdgcn_alignbyte(hi, lo, k));
-        if (luma) // (chroma: i_fact == 0 gives the second tap itself; a convex combination of 8-bit samples needs no clamp)
-            v[k] = min(max(__builtin_amdgcn_sdot4(wgt, taps, 8192 + 32, false) >> 6, 0), 255);
+        if (LUMA) // (chroma: i_fact == 0 gives the second tap itself; a convex combination of 8-bit samples needs no clamp)
+            v[k] = clip8_shr6(__builtin_amdgcn_sdot4(wgt, taps, 8192 + 32, false));
         else
             v[k] = __builtin_amdgcn_sdot4(wgt, taps, 4096 + 16, false) >> 5;
     }
@@ -733,9 +745,13 @@ __device__ __forceinline__ uint32_t planar_dc_row4(int mode, int lg, int oL, int
 // in registers (quad_transpose_bytes) -- so every lane ends with a row: one dword of originals in, one dword of
 // prediction and eight bytes of residual out (emit_row4), row-major where fwd_dct_lg reads them.
 // nb n^2 / 4 rows: one pass of the wave up to a 16x16 luma block, two for the 16x16 chroma pair, four for 32x32 luma.
+// COMP is a constant of the function and the mode's class (CCLM / PLANAR, DC / angular, wave-uniform) of the row loop: one
+// loop per class, none of them with a branch on either.
 constexpr int kAngTabByte = 1280, kAngTabStride = 104; // the projected main reference: byte offset in r2 (below kOrgLeaf), stride per block
-__device__ __forceinline__ void predict_full(Ctx c, int comp, int tx, int ty, int tlg, int mode, int rbase = 0,
+template <int COMP>
+__device__ __forceinline__ void predict_full(Ctx c, int tx, int ty, int tlg, int mode, int rbase = 0,
                                              int to_tile = PRED_TILE, int nl = 0, CclmPick pick = CclmPick{}) {
+    constexpr int comp = COMP;
 #ifdef WRENC_EXP_SKIP_PRED // instruction-count experiment only (profiles/r04_issue_model.md): nothing predicted
     return;
 #endif
@@ -743,13 +759,12 @@ __device__ __forceinline__ void predict_full(Ctx c, int comp, int tx, int ty, in
     rbase = uni(rbase);
     to_tile = uni(to_tile);
     nl = uni(nl);
-    comp = uni(comp);
     tx = uni(tx);
     ty = uni(ty);
     tlg = uni(tlg);
     mode = uni(mode);
-    const int cs = comp ? 1 : 0;
-    const int nb = comp ? 2 : 1;
+    constexpr int cs = comp ? 1 : 0;
+    constexpr int nb = comp ? 2 : 1;
     const int lg = tlg - cs;
     const int n = 1 << lg;
     const int cx = tx >> cs, cy = ty >> cs;
@@ -795,40 +810,50 @@ __device__ __forceinline__ void predict_full(Ctx c, int comp, int tx, int ty, in
     }
     const bool vertical = !ang || ap.vertical;
     // ---- the rows ----
+    constexpr int kRowsCclm = 0, kRowsPlanarDc = 1, kRowsAngular = 2;
+    auto row_loop = [&](auto cls_) {
+        constexpr int CLS = decltype(cls_)::value;
 #pragma unroll 1
-    for (int base = 0; base < rows; base += 64) {
-        const bool on = base + lane < rows;
-        const int t = (base + lane) & (rows - 1); // (a lane beyond the rows repeats one of them and stores nothing)
-        const int blk = t >> (2 * lg - 2);
-        const int bq = (t >> 2) & ((1 << (2 * lgb)) - 1);
-        const int x0 = 4 * (bq & ((1 << lgb) - 1)), y0 = 4 * (bq >> lgb);
-        const int y = y0 + j;                        // the row this lane stores: samples x0 .. x0 + 3 of it
-        const int i = (blk << (2 * lg)) + (y << lg) + x0;
-        const uint32_t org = org_row4(c, comp, blk, cx + x0, cy + y, obyte, i, olds); // issued early
-        const int oL = blk ? R_LC1 : oL0, oA = blk ? R_AC1 : oA0;
-        uint32_t packed;
-        if (cclm) {
-            int v[4];
+        for (int base = 0; base < rows; base += 64) {
+            const bool on = base + lane < rows;
+            const int t = (base + lane) & (rows - 1); // (a lane beyond the rows repeats one of them and stores nothing)
+            const int blk = t >> (2 * lg - 2);
+            const int bq = (t >> 2) & ((1 << (2 * lgb)) - 1);
+            const int x0 = 4 * (bq & ((1 << lgb) - 1)), y0 = 4 * (bq >> lgb);
+            const int y = y0 + j;                        // the row this lane stores: samples x0 .. x0 + 3 of it
+            const int i = (blk << (2 * lg)) + (y << lg) + x0;
+            const uint32_t org = org_row4(c, comp, blk, cx + x0, cy + y, obyte, i, olds); // issued early
+            const int oL = blk ? R_LC1 : oL0, oA = blk ? R_AC1 : oA0;
+            uint32_t packed;
+            if (CLS == kRowsCclm) {
+                int v[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (cp.flat128) {
-                    v[k] = 128;
-                } else {
-                    const int ds = cclm_ds6(c, tx, ty, 2 * y, 2 * (x0 + k), cp.avail_l);
-                    const int m = (M24(ds, blk ? cp.a1 : cp.a0) >> (blk ? cp.k1 : cp.k0)) + (blk ? cp.b1 : cp.b0);
-                    v[k] = min(max(m, 0), 255);
+                for (int k = 0; k < 4; ++k) {
+                    if (cp.flat128) {
+                        v[k] = 128;
+                    } else {
+                        const int ds = cclm_ds6(c, tx, ty, 2 * y, 2 * (x0 + k), cp.avail_l);
+                        const int m = (M24(ds, blk ? cp.a1 : cp.a0) >> (blk ? cp.k1 : cp.k0)) + (blk ? cp.b1 : cp.b0);
+                        v[k] = min(max(m, 0), 255);
+                    }
                 }
+                packed = pack4(v);
+            } else if (CLS == kRowsPlanarDc) {
+                packed = planar_dc_row4(mode, lg, oL, oA, x0, y, blk ? dcv1 : dcv0);
+            } else {
+                // along / across the prediction direction: this lane's line is `along`, its samples c0 .. c0 + 3 of it
+                packed = ang_row4<comp == 0>(ap, rm + blk * kAngTabStride, n, oL, oA, (vertical ? y0 : x0) + j, vertical ? x0 : y0);
+                if (!vertical) packed = quad_transpose_bytes(packed, j);
             }
-            packed = pack4(v);
-        } else if (!ang) {
-            packed = planar_dc_row4(mode, lg, oL, oA, x0, y, blk ? dcv1 : dcv0);
-        } else {
-            // along / across the prediction direction: this lane's line is `along`, its samples c0 .. c0 + 3 of it
-            packed = ang_row4(ap, comp == 0, rm + blk * kAngTabStride, n, oL, oA, (vertical ? y0 : x0) + j, vertical ? x0 : y0);
-            if (!vertical) packed = quad_transpose_bytes(packed, j);
+            if (on) emit_row4(c, org, packed, rbase + i, comp + blk, cx + x0, cy + y, to_tile, nl);
         }
-        if (on) emit_row4(c, org, packed, rbase + i, comp + blk, cx + x0, cy + y, to_tile, nl);
-    }
+    };
+    if (cclm)
+        row_loop(std::integral_constant<int, kRowsCclm>());
+    else if (!ang)
+        row_loop(std::integral_constant<int, kRowsPlanarDc>());
+    else
+        row_loop(std::integral_constant<int, kRowsAngular>());
     WSYNC();
 }
 
@@ -870,7 +895,7 @@ __device__ __forceinline__ void predict_pack8_luma(const Ctx& c, int nc, int m0,
     const bool vertical = !ang || ap.vertical;
     uint32_t packed = 0;
     if (ang)
-        packed = ang_row4(ap, true, rm, n, oL, oA, (vertical ? y0 : x0) + j, vertical ? x0 : y0);
+        packed = ang_row4<true>(ap, rm, n, oL, oA, (vertical ? y0 : x0) + j, vertical ? x0 : y0);
     else if (on)
         packed = planar_dc_row4(mode, lg, oL, oA, x0, y, dcv);
     const uint32_t turned = quad_transpose_bytes(packed, j); // (every lane: the four lanes of a quad share their candidate)
@@ -1059,11 +1084,13 @@ __device__ WRENC_SAD_INLINE unsigned sad_list_angular(const Ctx& c, int comps, i
     uint8_t* tab = (uint8_t*)SH.r1;
     uint32_t* ptab = (uint32_t*)SH.decw + 32; // [entry]: inv_angle (low half) | vertical << 16 | valid << 17
     uint32_t* ptab2 = (uint32_t*)SH.decw + 48; // [entry]: angle (low half) | flags << 16 | mode << 24
-#pragma unroll 1
-    for (int comp = 0; comp < 2; ++comp) {
-        if (!((comps >> comp) & 1)) continue;
-        const int cs = comp ? 1 : 0;
-        const int nb = comp ? 2 : 1;
+    // One component of the list.  The body is instantiated per component (round 19): comp is a constant in it, so cs, nb,
+    // the R_* offsets, the dot weights with their bias, shift and clamp, and the filtered-reference rule of luma fold
+    // away -- a wave-uniform branch on comp in front of every sample is what the compiler made of a run-time comp.
+    auto one_comp = [&](auto comp_) {
+        constexpr int comp = decltype(comp_)::value;
+        constexpr int cs = comp ? 1 : 0;
+        constexpr int nb = comp ? 2 : 1;
         const int lg = tlg - cs;
         const int n = 1 << lg;
         const int nn = n * n;
@@ -1240,8 +1267,10 @@ __device__ WRENC_SAD_INLINE unsigned sad_list_angular(const Ctx& c, int comps, i
                 }
 #endif
                 int sad = 0;
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
+                // one row of four samples.  PDPC_ (wave-uniform, decided once per iteration, not per row): without it the R
+                // rows of an iteration are one basic block
+                auto row = [&](auto pdpc_, int r) {
+                    constexpr bool PDPC_ = decltype(pdpc_)::value;
                     const int along = a0 + r;
                     const int pr = M24(along + 1, angle);
                     const int i_idx = pr >> 5, i_fact = pr & 31;
@@ -1250,13 +1279,19 @@ __device__ WRENC_SAD_INLINE unsigned sad_list_angular(const Ctx& c, int comps, i
                     const uint32_t w0 = tp[0], w1 = tp[1], w2 = tp[2];
                     const uint32_t lo = __builtin_amdgcn_alignbyte(w1, w0, ta & 3), hi = __builtin_amdgcn_alignbyte(w2, w1, ta & 3);
                     int v[4];
-                    const int wgt = comp == 0 ? (filter_flag ? 0x00102010 + (i_fact >> 1) * 0x0100FEFF : *(const int*)&SHT.fc[i_fact][0])
-                                              : (((32 - i_fact) << 8) | (i_fact << 16));
+                    int wgt;
+                    if (comp == 0) { // every lane computes the smoothing filter's word and reads the table's: a select, no
+                                     // lane-divergent branch around the read
+                        const int w_smooth = 0x00102010 + (i_fact >> 1) * 0x0100FEFF, w_tab = *(const int*)&SHT.fc[i_fact][0];
+                        wgt = filter_flag ? w_smooth : w_tab;
+                    } else {
+                        wgt = ((32 - i_fact) << 8) | (i_fact << 16);
+                    }
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         const int taps = (int)(k == 0 ? lo : __builtin_amdgcn_alignbyte(hi, lo, k));
                         if (comp == 0)
-                            v[k] = min(max(__builtin_amdgcn_sdot4(wgt, taps, 8192 + 32, false) >> 6, 0), 255);
+                            v[k] = clip8_shr6(__builtin_amdgcn_sdot4(wgt, taps, 8192 + 32, false));
                         else
                             v[k] = __builtin_amdgcn_sdot4(wgt, taps, 4096 + 16, false) >> 5;
                     }
@@ -1277,8 +1312,8 @@ __device__ WRENC_SAD_INLINE unsigned sad_list_angular(const Ctx& c, int comps, i
                     uint32_t packed = pack4(v);
 #else
                     uint32_t packed;
-                    if (any_pdpc) { // (wave-uniform; inside it every lane runs the same code: a lane without PDPC weighs by 0,
-                                    // as does a sample beyond 3 << n_scale, so what is read for those does not matter)
+                    if (PDPC_) { // (inside it every lane runs the same code: a lane without PDPC weighs by 0, as does a
+                                 // sample beyond 3 << n_scale, so what is read for those does not matter)
                         pk16 out[2];
 #pragma unroll
                         for (int h = 0; h < 2; ++h) {
@@ -1294,7 +1329,19 @@ __device__ WRENC_SAD_INLINE unsigned sad_list_angular(const Ctx& c, int comps, i
                     const uint32_t org = vertical ? (r == 0 ? o0 : (r == 1 ? o1 : (r == 2 ? o2 : o3)))
                                                   : (r == 0 ? t0 : (r == 1 ? t1 : (r == 2 ? t2 : t3)));
                     sad = (int)__builtin_amdgcn_sad_u8(packed, org, (uint32_t)sad);
+                };
+#ifdef WRENC_EXP_OLD_PDPC
+#pragma unroll
+                for (int r = 0; r < R; ++r) row(std::true_type(), r);
+#else
+                if (any_pdpc) {
+#pragma unroll
+                    for (int r = 0; r < R; ++r) row(std::true_type(), r);
+                } else {
+#pragma unroll
+                    for (int r = 0; r < R; ++r) row(std::false_type(), r);
                 }
+#endif
                 if (!on) sad = 0;
                 // the entry's total: over the G lanes of its rows
                 int tot = sad;
@@ -1320,13 +1367,13 @@ __device__ WRENC_SAD_INLINE unsigned sad_list_angular(const Ctx& c, int comps, i
             rows_per_lane(std::integral_constant<int, 4>());
             PROF_MARK(sl2_);
             PROF_ADD2(PH_LEAF + 9, sl1_, sl2_);
-            continue;
+            return;
         }
         if (costL_ <= cost1_) {
             rows_per_lane(std::integral_constant<int, 1>());
             PROF_MARK(sl3_);
             PROF_ADD2(PH_LEAF + 12, sl1_, sl3_);
-            continue;
+            return;
         }
         // ---- entry by entry: one predicted sample per lane and iteration, |org - pred| summed ----
 #pragma unroll 1
@@ -1396,7 +1443,9 @@ __device__ WRENC_SAD_INLINE unsigned sad_list_angular(const Ctx& c, int comps, i
         WSYNC(); // the next component overwrites the tables
         PROF_MARK(sl4_);
         PROF_ADD2(PH_LEAF + 10, sl1_, sl4_);
-    }
+    };
+    if (comps & 1) one_comp(std::integral_constant<int, 0>());
+    if (comps & 2) one_comp(std::integral_constant<int, 1>());
     return acc;
 }
 

@@ -145,7 +145,10 @@ __device__ __forceinline__ void full_front(const Ctx& c, const Req& q, int comp,
     }
     PROF_MARK(t0_);
     PROF_ADD2(PH_REFS, tr0_, t0_);
-    predict_full(c, comp, q.tx, q.ty, q.tlg, mode, rbase, PRED_TILE, 0, pick);
+    if (comp == 0)
+        predict_full<0>(c, q.tx, q.ty, q.tlg, mode, rbase, PRED_TILE, 0, pick);
+    else
+        predict_full<1>(c, q.tx, q.ty, q.tlg, mode, rbase, PRED_TILE, 0, pick);
     PROF_MARK(t1_);
     PROF_ADD2(PH_PREDICT, t0_, t1_);
     PROF_ADD2(PH_PRED + (mode >= LT_CCLM ? 5 : (q.tlg == 5 ? 0 : (q.tlg == 4 ? 1 : 6))), t0_, t1_);
@@ -1398,8 +1401,8 @@ __device__ __forceinline__ void pack16_predict(const Ctx& c, int tx, int ty, int
     for (int cd = 0; cd < nc; ++cd) {
         const int mode = cd == 0 ? m0 : m1;
         if (mode != kNoMode) {
-            predict_full(c, 0, tx, ty, 4, mode, 256 * cd, PRED_PARK16, nL);
-            predict_full(c, 1, tx, ty, 4, mode, nL + 128 * cd, PRED_PARK16, nL);
+            predict_full<0>(c, tx, ty, 4, mode, 256 * cd, PRED_PARK16, nL);
+            predict_full<1>(c, tx, ty, 4, mode, nL + 128 * cd, PRED_PARK16, nL);
         } else { // a candidate outside 2..66 rides along as a zero block
             for (int i = lane; i < 256; i += 64) {
                 SH.r1[256 * cd + i] = 0;

@@ -296,7 +296,10 @@ __device__ __forceinline__ void item_stage_chroma(Ctx& c, const PredictItem& q) 
 __device__ __forceinline__ void item_predict(Ctx& c, const PredictItem& q) {
     const int comp = q.kind;
     if (q.mode < LT_CCLM) build_refs(c, comp, q.tx, q.ty, q.tlg);
-    predict_full(c, comp, q.tx, q.ty, q.tlg, q.mode, 0, PRED_SCRATCH);
+    if (comp == 0)
+        predict_full<0>(c, q.tx, q.ty, q.tlg, q.mode, 0, PRED_SCRATCH);
+    else
+        predict_full<1>(c, q.tx, q.ty, q.tlg, q.mode, 0, PRED_SCRATCH);
     const int n = 1 << (q.tlg - (comp ? 1 : 0));
     const int total = (comp ? 2 : 1) * n * n;
     __threadfence_block();
@@ -363,7 +366,10 @@ __device__ __forceinline__ void item_full(Ctx& c, const PredictItem& q) {
     const int cmp = q.kind - PK_FULL_LUMA;
     item_stage_originals(c, q, 1 + cmp);
     if (q.mode < LT_CCLM) build_refs(c, cmp, q.tx, q.ty, q.tlg);
-    predict_full(c, cmp, q.tx, q.ty, q.tlg, q.mode, 0, PRED_TILE);
+    if (cmp == 0)
+        predict_full<0>(c, q.tx, q.ty, q.tlg, q.mode, 0, PRED_TILE);
+    else
+        predict_full<1>(c, q.tx, q.ty, q.tlg, q.mode, 0, PRED_TILE);
     const int lg = q.tlg - cmp, n = 1 << lg, total = (cmp ? 2 : 1) * n * n;
     for (int i = LANE; i < total; i += 64) {
         const int blk = i >> (2 * lg), ii = i & (n * n - 1);
