@@ -143,6 +143,12 @@ int wrenc_gpu_test_predict(wrenc_gpu_ctx* ctx, const uint8_t* rec_y, const uint8
  * WRENC_GPU_EINVAL at the first item wrenc_gpu_test_predict would refuse (offsets then holds no layout). */
 int wrenc_gpu_test_predict_layout(int width, int height, int n_items, const int32_t* items, size_t* offsets);
 
+/* Host only, needs no context and no device: the constant block the device would be given for `cfg` (wrenc_amd/csrc/dev_const.h,
+ * DevConst) is built, and the bytes of its member `name` ("split_floor", "scan_idx", "fdct_b", ...: the member's name, arrays
+ * as they lie in memory) are copied to `out`.  Returns their count; WRENC_GPU_EINVAL for a NULL argument, a name the block
+ * does not have, a `cap` smaller than the member, or a rate model wrenc_gpu_create refuses. */
+int wrenc_gpu_test_const_field(const wrenc_gpu_config* cfg, const char* name, void* out, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

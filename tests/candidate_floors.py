@@ -1,6 +1,6 @@
 """The candidate cut of the 4x4 luma leaf search (wrenc_amd/csrc/dev_search.h, kCandidateCut / leaf4_search) on the host,
 for the tests and for tools/candidate_floor_model.py: the per-class floors recomputed from a config's tables with the
-formula of fill_split_floors (wrenc_amd/csrc/wrenc_gpu.hip), the search-time MPM list of every 4x4 DUAL_TREE_LUMA leaf of
+formula of fill_split_floors (wrenc_amd/csrc/const_block.cpp), the search-time MPM list of every 4x4 DUAL_TREE_LUMA leaf of
 an oracle encode, the oracle's candidate trace grouped per leaf, and a leaf search replayed under the rule.
 Nothing here touches a GPU."""
 import numpy as np

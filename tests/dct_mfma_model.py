@@ -42,7 +42,7 @@ def basis_abs_row_sum(n):
 
 @functools.lru_cache(maxsize=None)
 def tables(n):
-    """the host's fill of the operand tables (wrenc_gpu.hip fill_dev_const), [m][h][j]"""
+    """the host's fill of the operand tables (const_block.cpp fill_dev_const), [m][h][j]"""
     T = basis(n)
     s = T.sum(axis=0)                                      # S[y] = sum_i T[i][y]
     t = {"fdct_b": np.zeros((32, 2, 16), np.int64), "idct_b": np.zeros((32, 2, 16), np.int64),

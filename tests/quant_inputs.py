@@ -47,6 +47,17 @@ def shift(n):
     return n.bit_length() - 1 + 4
 
 
+def reciprocal(qp):
+    """(lsc, m, k - 32): the level scale of a QP and the reciprocal the device divides by it with (DevConst::lsc, div_magic,
+    div_shift; const_block.cpp, fill_dev_const): m = floor(2^k / lsc) + 1, k = 26 + ceil(log2 lsc), q = mulhi(n, m) >> (k - 32)."""
+    lsc = level_scale(qp)
+    lg = 0
+    while (1 << lg) < lsc:
+        lg += 1
+    k = 26 + lg
+    return lsc, (1 << k) // lsc + 1, k - 32
+
+
 def quotient(tc, qp, n):
     sh = shift(n)
     s = (int(tc) << sh) - (1 << (sh - 1))

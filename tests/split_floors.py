@@ -1,6 +1,6 @@
 """The split cut with floors (wrenc_amd/csrc/dev_search.h, split_floor_cut) on the host, for the tests and for
 tools/split_floor_model.py: the floors recomputed from a config's tables with the formula of fill_split_floors
-(wrenc_amd/csrc/wrenc_gpu.hip), the oracle's candidate trace in evaluation order, the cost of every leaf and node of an
+(wrenc_amd/csrc/const_block.cpp), the oracle's candidate trace in evaluation order, the cost of every leaf and node of an
 exhaustive search taken from it, and the search replayed under a cut rule with counts of what it visits.
 Nothing here touches a GPU."""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""The candidate cut of the 4x4 luma leaf search (wrenc_amd/csrc/dev_search.h, kCandidateCut; wrenc_gpu.hip,
+"""The candidate cut of the 4x4 luma leaf search (wrenc_amd/csrc/dev_search.h, kCandidateCut; const_block.cpp,
 fill_split_floors) on the CPU, from the oracle alone (tests/candidate_floors.py holds the floors and the replay).
 
   * Every traced full candidate of every 4x4 DUAL_TREE_LUMA leaf costs at least the floor of its mode class, in f32, with

@@ -61,11 +61,11 @@ def test_prediction_tables_equal_the_reference_source():
     angle, fc, fg = ref["intra_angle"], ref["f_c"], ref["f_g"]
     assert len(angle) == 95 and len(fc) == 128 and len(fg) == 128
     assert fg == [v for p in range(32) for v in (16 - (p >> 1), 32 - (p >> 1), 16 + (p >> 1), p >> 1)]   # both copies compute it
-    for path in (os.path.join(root, "oracle", "wrenc_oracle.cpp"), os.path.join(root, "wrenc_amd", "csrc", "wrenc_gpu.hip")):
+    for path in (os.path.join(root, "oracle", "wrenc_oracle.cpp"), os.path.join(root, "wrenc_amd", "csrc", "const_block.cpp")):
         assert _c_table(path, "kIntraAngle[95]") == angle, path
         assert _c_table(path, "kFC[32][4]") == fc, path
     assert ref["level_scale"] == [40, 45, 51, 57, 64, 72]
-    assert _c_table(os.path.join(root, "wrenc_amd", "csrc", "wrenc_gpu.hip"), "level_scale[6]") == [40, 45, 51, 57, 64, 72]
+    assert _c_table(os.path.join(root, "wrenc_amd", "csrc", "const_block.cpp"), "level_scale[6]") == [40, 45, 51, 57, 64, 72]
     # dependent-quantisation state machine (encoder_context.rs:339): oracle, host writer, stream parser (the device walk
     # has it folded into its lane permutations, dev_quant.h:295-296, and is covered by the parity tests)
     trans = ref["q_state_trans"]
@@ -260,19 +260,17 @@ def test_extreme_content():
 
 
 def test_reciprocal_quotient_is_exact_at_every_qp():
-    """The device divides by the level scale with one 32-bit multiply-high (wrenc_gpu.hip fill_dev_const: m = floor(2^k /
-    lsc) + 1, k = 26 + ceil(log2 lsc), q = mulhi(n, m) >> (k - 32)).  n = |(tc << sh) - off| <= (32768 << 9) + 256 < 2^26 at
+    """The device divides by the level scale with one 32-bit multiply-high (const_block.cpp fill_dev_const: m = floor(2^k /
+    lsc) + 1, k = 26 + ceil(log2 lsc), q = mulhi(n, m) >> (k - 32); quant_inputs.reciprocal states it, and
+    tests/test_const_block.py holds the library's numbers against that).  n = |(tc << sh) - off| <= (32768 << 9) + 256 < 2^26 at
     every block size whatever the QP; the quotient is exact there for every level scale QP 0..63 gives: checked at every
     multiple of lsc +- 1 below 2^26 (where a reciprocal first fails) and at random n."""
-    scale = [40, 45, 51, 57, 64, 72]
+    import quant_inputs as qi
+    assert qi.LEVEL_SCALE == [40, 45, 51, 57, 64, 72]
     rng = np.random.default_rng(5)
     for qp in range(64):
-        lsc = (16 * scale[(qp + 1) % 6]) << ((qp + 1) // 6)
-        lg = 0
-        while (1 << lg) < lsc:
-            lg += 1
-        k = 26 + lg
-        m = (1 << k) // lsc + 1
+        lsc, m, shift = qi.reciprocal(qp)
+        k = shift + 32
         assert m < 1 << 32 and k >= 32
         q = np.arange(1, (1 << 26) // lsc + 1, dtype=np.uint64) * np.uint64(lsc)
         n = np.concatenate([q - np.uint64(1), q, q + np.uint64(1), rng.integers(0, 1 << 26, 20000).astype(np.uint64),

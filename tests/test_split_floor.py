@@ -1,4 +1,4 @@
-"""The split cut's floors (wrenc_amd/csrc/dev_search.h, split_floor_cut; wrenc_gpu.hip, fill_split_floors) on the CPU.
+"""The split cut's floors (wrenc_amd/csrc/dev_search.h, split_floor_cut; const_block.cpp, fill_split_floors) on the CPU.
 
 The rule: before a child of a split is searched, the partial sum of the children searched so far plus the floor of every
 child still to come, added one by one in z-order in f32, is compared with the unsplit cost; strictly greater means the

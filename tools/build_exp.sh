@@ -11,7 +11,8 @@ shift
 mkdir -p xbuild
 rm -f "xbuild/$name.so" "xbuild/$name.flags"
 if ! /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -mllvm -sink-insts-to-avoid-spills=1 -mllvm -disable-machine-licm \
-        -DWRENC_EXPERIMENT_BUILD "$@" -o "xbuild/$name.so" wrenc_amd/csrc/wrenc_gpu.hip wrenc_amd/csrc/wrenc_gpu_test.hip > "xbuild/$name.log" 2>&1; then
+        -DWRENC_EXPERIMENT_BUILD "$@" -o "xbuild/$name.so" wrenc_amd/csrc/wrenc_gpu.hip wrenc_amd/csrc/wrenc_gpu_io.hip \
+        wrenc_amd/csrc/const_block.cpp wrenc_amd/csrc/wrenc_gpu_test.hip > "xbuild/$name.log" 2>&1; then
     grep -E " error|error:" "xbuild/$name.log" >&2 || tail -n 20 "xbuild/$name.log" >&2
     rm -f "xbuild/$name.so"
     echo "build_exp.sh: $name failed (xbuild/$name.log)" >&2

@@ -1,6 +1,7 @@
 """Phase shares of a CTU-wave from the diagnostic build (never the product library):
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -mllvm -sink-insts-to-avoid-spills=1 -DWRENC_PROFILE \
-        -o xbuild/libwrenc_gpu_prof.so wrenc_amd/csrc/wrenc_gpu.hip wrenc_amd/csrc/wrenc_gpu_test.hip
+        -o xbuild/libwrenc_gpu_prof.so wrenc_amd/csrc/wrenc_gpu.hip wrenc_amd/csrc/wrenc_gpu_io.hip wrenc_amd/csrc/const_block.cpp \
+        wrenc_amd/csrc/wrenc_gpu_test.hip
   python tools/phase_profile.py WxH DEPTH B SCHEDULE [1 = textured content]
 (WRENC_PROF_LIB=path: another -DWRENC_PROFILE build, e.g. one with -DWRENC_EXHAUSTIVE_SPLITS.)
 The counters are s_memtime differences of thread 0 of each workgroup (wave 0 = member 0 of its team in the team

@@ -52,4 +52,9 @@ g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -fno-
 g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined \
     -D__HIP_PLATFORM_AMD__ -I"${ROCM_PATH:-/opt/rocm}/include" -o "$T/host_mem" "$R/tools/sanitize/host_mem.cpp"
 "$T/host_mem"
+# the rate model and the constant block (wrenc_amd/csrc/const_block.cpp): every QP and depth, the --extra-params strings of the
+# tests and malformed ones; the library's own source under g++, warnings on: no HIP
+g++ -O1 -g -std=c++17 -Wall -Wextra -ffp-contract=off -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined \
+    -o "$T/const_block" "$R/tools/sanitize/const_block.cpp" "$R/wrenc_amd/csrc/const_block.cpp"
+"$T/const_block"
 rm -rf "$T"

@@ -21,31 +21,13 @@
 // LDS per workgroup: 96 x 288 input bytes + 96 x 64 int16 = 39 KB (four workgroups per CU); at 4:1 a tile uses 80 x 272 of
 // the input part.
 #pragma once
+#include "scale_args.h" // ScaleAxis, ScaleArgs
 
 namespace wrenc {
 
 constexpr int kScaleTileW = 64, kScaleTileH = 16;
 constexpr int kScaleSpanX = 288, kScaleSpanY = 96; // input columns / rows of a tile that the LDS holds
 constexpr int kScaleCoefs = 16;                    // coefficients per output sample in the tables
-
-// one axis of one plane size (luma or chroma)
-struct ScaleAxis {
-    const int* first;       // [n_out]: input index of the first tap (may be negative)
-    const int16_t* coef;    // [n_out][kScaleCoefs]: zero behind the sample's own taps
-    const int* tile_base;   // [tiles]: the smallest `first` of the tile's samples; x: rounded down to a multiple of 4
-    int n_in, n_out;
-    int taps;               // coefficients the passes run over: the longest list of the axis, rounded up to even
-    int span;               // input samples from tile_base that a tile's taps reach at most (<= kScaleSpanX / kScaleSpanY)
-};
-
-struct ScaleArgs {
-    ScaleAxis x[2], y[2];   // [0] luma, [1] chroma
-    const uint8_t* src[3];  // staging planes
-    int src_pitch[2];       // ... and their pitch, luma and chroma: multiples of 16
-    uint8_t* dst;           // a slot's originals, Y | Cb | Cr back to back at the coded size (PicBufs::org[0])
-    int W, H;               // the coded size
-    int tiles_x[2], tiles[2]; // tiles per row and per plane, luma and chroma
-};
 
 __device__ __forceinline__ void scale_load_coefs(const int16_t* coef, int o, uint32_t cw[kScaleCoefs / 2]) {
     const uint4* p = (const uint4*)(coef + (size_t)o * kScaleCoefs);

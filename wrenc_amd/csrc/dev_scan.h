@@ -1,6 +1,6 @@
 // The coefficient scan as arithmetic: raster index y * n + x of reverse-scan position p in a block of side n = 1 << lg
 // (p = 0: last in scan), the mapping DevConst::scan_idx holds as a table (ctu.rs:54-77, 827-845).  No memory, no LDS,
-// no static table: the quantisers (dev_quant.h) compute the index instead of loading it.  wrenc_gpu.hip holds every
+// no static table: the quantisers (dev_quant.h) compute the index instead of loading it.  const_block.cpp holds every
 // function here against the table's construction at compile time, for every p of every size.
 //
 // The scan visits the 4x4 sub-blocks of the block along up-right diagonals, and the 16 positions of a sub-block the

@@ -23,7 +23,7 @@ __device__ __forceinline__ int dot2(uint32_t a, uint32_t b, int acc) { // v_dot2
 // transformer.rs:2040-2378.  The i32 intermediate of all nb blocks goes through r2 at once when it fits its
 // 2 KB, block after block otherwise (the two 16x16 blocks of a 32x32 CU's chroma pair).
 // h: the intermediate's buffer of HBYTES bytes in LDS (r2 in the search; the micro-benchmark of the 32x32 v_dot2
-// version brings its own, wrenc_gpu.hip).
+// version brings its own, wrenc_gpu_test.hip).
 template <int LG, int HBYTES>
 __device__ void fwd_dct(Ctx c, int nb, int o1, LDS_AS int32_t* h) {
     constexpr int N = 1 << LG;
@@ -522,7 +522,7 @@ __device__ __forceinline__ int inv_dct4_reg(int deq) {
 // Which code runs at 8x8 and 16x16 (ARM, a literal: the branches fold away).  DCT_SEARCH, what every caller in the search
 // passes: 16x16 as i8 MFMAs (fwd_dct_mfma / inv_dct_mfma, +3.0 % frames/s on the headline workload), 8x8 through the v_dot2
 // templates -- the MFMA version of that size is exact, but faster in the micro-benchmark only from three blocks per
-// group up, and its gain in the search (+0.2 %) did not clear the project's margin.  DCT_VDOT2 / DCT_MFMA: the building-block kernels (wrenc_gpu.hip)
+// group up, and its gain in the search (+0.2 %) did not clear the project's margin.  DCT_VDOT2 / DCT_MFMA: the building-block kernels (wrenc_gpu_test.hip)
 // name the arm, for groups the digit scheme does not take (a residual outside +-255, an o1 that is no multiple of 8),
 // for the parity tests of both versions at both sizes and for the micro-benchmark (tools/dct_bench.py).
 enum { DCT_SEARCH, DCT_VDOT2, DCT_MFMA };

@@ -1,15 +1,21 @@
-// gpu_ctx.h -- what the two units of libwrenc_gpu.so share (private to them): the context, the error path and the host
-// functions that both the product's entry points (wrenc_gpu.hip) and the block tests' (wrenc_gpu_test.hip) call.  Each
-// of those functions is defined once, in wrenc_gpu.hip, and stays inside the library (hidden visibility).
+// gpu_ctx.h -- what the HIP units of libwrenc_gpu.so share (private to them): the context, the error path and the host
+// functions that more than one of the search's entry points (wrenc_gpu.hip), the picture I/O (wrenc_gpu_io.hip) and the
+// block tests (wrenc_gpu_test.hip) call.  Each of those functions is defined once, in the unit named at its declaration,
+// and stays inside the library (hidden visibility).  The device headers come from the units themselves: this file needs
+// dev_common.h alone, and the read-backs' device types by name only.
 #pragma once
 #include "../../include/wrenc_gpu.h"
 #include "../../include/wrenc_scale.h"
 #include "../../include/wrenc_format.h"
+#include "../../include/wrenc_hash.h"
 #include "../../include/wrenc_ratecurve.h"
-#include "wrenc_dev.h"
 
 #include <hip/hip_runtime.h>
+#include <stdint.h>
 
+#include "dev_common.h"
+#include "scale_args.h"
+#include "const_block.h"
 #include "encode_plan.h"
 #include "host_mem.h"
 
@@ -17,6 +23,18 @@
 #include <vector>
 
 using namespace wrenc;
+
+namespace wrenc {
+// what the read-backs' scratch holds (dev_metrics.h, dev_hash.h, dev_complexity.h, dev_ratecurve.h): complete in
+// wrenc_gpu_io.hip, names only in the search unit.  The context has the same layout in both because a DevBuf<T> is a
+// pointer and a count whatever T is (host_mem.h), and destroying or moving one needs no complete T.
+struct MetricsPartial;
+struct MetricsSums;
+struct HashTables;
+struct ComplexityPartial;
+struct RateHistPartial;
+struct RateHistCounts;
+} // namespace wrenc
 
 // A mixed-QP encode call (wrenc_gpu_set_slot_qp) runs its pictures from a per-call list, ordered by QP and padded so that
 // every group of WPB consecutive entries holds ONE QP: load_tables fills the workgroup's LDS tables (lambda_q x dq_table)
@@ -136,9 +154,8 @@ struct wrenc_gpu_ctx {
     std::string err;
     int ctu_cols = 0, ctu_rows = 0;
 };
-#define WRENC_HIDDEN __attribute__((visibility("hidden")))
 
-// the message goes to the context, or (ctx NULL: wrenc_gpu_create) to the thread's creation error; returns `code`
+// wrenc_gpu.hip: the message goes to the context, or (ctx NULL: wrenc_gpu_create) to the thread's creation error; returns `code`
 WRENC_HIDDEN int fail(wrenc_gpu_ctx* ctx, int code, const std::string& msg);
 
 // returns WRENC_GPU_EHIP where `expr` fails.  HIP's last error is cleared then, so that the next call's launch check
@@ -152,9 +169,11 @@ WRENC_HIDDEN int fail(wrenc_gpu_ctx* ctx, int code, const std::string& msg);
         }                                                                                         \
     } while (0)
 
-WRENC_HIDDEN size_t plane_bytes(const wrenc_gpu_config& c, int comp, size_t elem);
-WRENC_HIDDEN void fill_dev_const(const wrenc_gpu_config& cfg, DevConst& k);
-// the metrics and hash passes over pictures of any PicBufs array, on any stream (comments at the definitions)
+WRENC_HIDDEN size_t plane_bytes(const wrenc_gpu_config& c, int comp, size_t elem); // wrenc_gpu.hip
+// (fill_dev_const, which the block tests call too, and the rate model: const_block.h)
+// wrenc_gpu_io.hip: the slots of a call exist and are uploaded (min_state 1) or searched (2)
+WRENC_HIDDEN int check_slots(wrenc_gpu_ctx* ctx, int first, int n, int min_state, const char* range_msg);
+// wrenc_gpu_io.hip: the metrics and hash passes over pictures of any PicBufs array, on any stream (comments at the definitions)
 WRENC_HIDDEN hipError_t launch_metrics(const wrenc_gpu_config& c, int vw, int vh, hipStream_t st, const PicBufs* slots, int first, int n,
                                        MetricsPartial* partials, MetricsSums* sums, float* maps);
 WRENC_HIDDEN void fill_metrics(int vw, int vh, const MetricsSums& s, wrenc_gpu_metrics& m);

@@ -7,6 +7,7 @@
 namespace wrenc {
 
 // `count` elements of T on the current device, or nothing.  Movable, not copyable; the destructor frees.
+// (A pointer and a count, and only alloc / grow ask for sizeof(T): gpu_ctx.h holds DevBufs of types one unit only names.)
 template <class T>
 class DevBuf {
 public:

@@ -12,16 +12,26 @@
 // calls, no scratch, every branch scalar.
 //
 // What is computed follows the reference function by function (paths relative to the reference's
-// src/, cited at each function); how it is computed is wave-parallel:
+// src/, cited at each function); how it is computed is wave-parallel.
+//
+// The search's headers, included below (wrenc_gpu.hip holds the search kernels, wrenc_gpu_test.hip runs their functions
+// on single blocks), each with the part of the reference it follows and how its lanes share the work:
+//   dev_const.h      (wrenc_gpu_config)             the constant block of a QP, plain C++ (filled by const_block.cpp)
+//   dev_common.h     (shared by every device header) per-picture buffers, the LDS working set, search state, wave helpers
 //   dev_predict.h    intra_predictor.rs:56-2055     lane = sample; SAD lists of many modes in one loop
 //   dev_pk16.h       (helpers of the rows)          two samples of a row per 16-bit packed instruction
 //   dev_transform.h  transformer.rs:2040-2737       lane = basis row, v_dot2 / v_mad_i24
+//   dev_scan.h       ctu.rs:54-77, 827-845          the coefficient scan as arithmetic
 //   dev_quant.h      quantizer.rs:338-759           backward 4-state Viterbi, one lane per state, DPP
 //   dev_search.h     block_splitter.rs:64-1154, ctu_encoder.rs:1421-1461
+// The picture passes, included by the unit that launches them (wrenc_gpu_io.hip) over dev_common.h and two helpers of the
+// search (dev_quant.h's state maps for the tokens, dev_transform.h's dot2 for the scaler):
 //   dev_bins.h       ctu_encoder.rs:1786-2269       residual_coding as a token stream for the host's arithmetic coder
 //   dev_metrics.h    (the evaluation harness)       PSNR / SSIM sums of originals against the reconstruction
 //   dev_hash.h       (no counterpart)               decoded picture hash (MD5, CRC, checksum) of the reconstruction
+//   dev_complexity.h (no counterpart)               SATD of the originals per CTU and picture, for the rate control
 //   dev_ratecurve.h  (no counterpart)               rate histogram of the originals (prediction, Hadamard, magnitude bins)
+//   dev_pad.h        (no counterpart)               a picture's last column and row replicated into the coded size's margin
 //   dev_scale.h      (no counterpart)               resampling of an uploaded picture to the visible size
 //   dev_format.h     (no counterpart)               10-bit, NV12 / P010 and 4:2:2 uploads to the 8-bit 4:2:0 planes
 #pragma once
@@ -46,12 +56,3 @@
 #include "dev_scan.h"
 #include "dev_quant.h"
 #include "dev_search.h"
-#define WRENC_TOKENS_KERNEL_TU
-#include "dev_bins.h"
-#include "dev_metrics.h"
-#include "dev_hash.h"
-#include "dev_complexity.h"
-#include "dev_ratecurve.h"
-#include "dev_pad.h"
-#include "dev_scale.h"
-#include "dev_format.h"

@@ -9,15 +9,19 @@
 #undef WRENC_TRACE
 #undef WRENC_PROFILE
 #include <hip/hip_runtime.h>
-// Some dev_*.h headers define kernels that are no templates (pad, scale, complexity, ...).  This unit needs the headers
-// for the context's types and launches none of their kernels: here they are device functions nothing calls, so they
-// are neither compiled a second time nor defined twice in the library.
+// dev_metrics.h and dev_hash.h define kernels that are no templates.  This unit needs the two headers for what its
+// metrics and hash entries hand to the launchers of wrenc_gpu_io.hip (MetricsPartial, HashTables, met_plane, ...) and
+// launches none of their kernels: here they are device functions nothing calls, so they are neither compiled a second
+// time nor defined twice in the library.
 #pragma push_macro("__global__")
 #pragma push_macro("__launch_bounds__")
 #undef __global__
 #undef __launch_bounds__
 #define __global__ static __device__
 #define __launch_bounds__(...)
+#include "wrenc_dev.h"
+#include "dev_metrics.h"
+#include "dev_hash.h"
 #include "gpu_ctx.h"
 #pragma pop_macro("__launch_bounds__")
 #pragma pop_macro("__global__")
@@ -847,6 +851,34 @@ int wrenc_gpu_test_predict(wrenc_gpu_ctx* ctx, const uint8_t* rec_y, const uint8
                            scratch.as<uint8_t>(), res.as<uint8_t>());
         return hipSuccess;
     });
+}
+
+int wrenc_gpu_test_const_field(const wrenc_gpu_config* cfg, const char* name, void* out, size_t cap) {
+    if (!cfg || !name || !out) return WRENC_GPU_EINVAL;
+    if (!rate_model_fits(*cfg)) return WRENC_GPU_EINVAL; // (as wrenc_gpu_create: fill_dev_const multiplies lambda_q and dq_table)
+#define CONST_FIELD(m) {#m, offsetof(DevConst, m), sizeof(DevConst::m)}
+    static const struct { const char* name; size_t at, bytes; } fields[] = {
+        CONST_FIELD(W), CONST_FIELD(H), CONST_FIELD(qp), CONST_FIELD(max_depth), CONST_FIELD(ctu_cols), CONST_FIELD(ctu_rows),
+        CONST_FIELD(lsc), CONST_FIELD(div_magic), CONST_FIELD(div_shift), CONST_FIELD(lambda_q), CONST_FIELD(lambda_rd),
+        CONST_FIELD(lambda_rd_chroma), CONST_FIELD(ldq), CONST_FIELD(lv), CONST_FIELD(hb_luma), CONST_FIELD(hb_chroma),
+        CONST_FIELD(dct), CONST_FIELD(dct_t), CONST_FIELD(diag4), CONST_FIELD(diag_sb), CONST_FIELD(scan_idx),
+        CONST_FIELD(intra_angle), CONST_FIELD(ang_tab), CONST_FIELD(fc), CONST_FIELD(dct32_a), CONST_FIELD(dct32_p),
+        CONST_FIELD(idct32_b), CONST_FIELD(idct32_p), CONST_FIELD(idct32_k1), CONST_FIELD(idct32_k2), CONST_FIELD(fdct_b),
+        CONST_FIELD(fdct16_p), CONST_FIELD(fdct8_p), CONST_FIELD(idct_b), CONST_FIELD(idct16_p), CONST_FIELD(idct8_p),
+        CONST_FIELD(idct_k1), CONST_FIELD(idct16_k2), CONST_FIELD(idct8_k2), CONST_FIELD(head_rng), CONST_FIELD(avail_tab),
+        CONST_FIELD(split_floor), CONST_FIELD(cand_floor), CONST_FIELD(cand_floor_ang),
+    };
+#undef CONST_FIELD
+    for (const auto& f : fields) {
+        if (strcmp(name, f.name)) continue;
+        if (cap < f.bytes) return WRENC_GPU_EINVAL;
+        std::unique_ptr<DevConst> hk(new (std::nothrow) DevConst());
+        if (!hk) return WRENC_GPU_ENOMEM;
+        fill_dev_const(*cfg, *hk);
+        memcpy(out, (const char*)hk.get() + f.at, f.bytes);
+        return (int)f.bytes;
+    }
+    return WRENC_GPU_EINVAL;
 }
 
 } // extern "C"

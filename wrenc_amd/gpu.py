@@ -95,6 +95,7 @@ PROTOTYPES = {
     "wrenc_gpu_test_recon_rows": (_I, [_P, _P, _P, _P, _I, _P, _P]),
     "wrenc_gpu_test_predict": (_I, [_P, _P, _P, _P, _I, _P, _P, _Z]),
     "wrenc_gpu_test_predict_layout": (_I, [_I, _I, _I, _P, _P]),
+    "wrenc_gpu_test_const_field": (_I, [_P, _S, _P, _Z]),
 }
 EXPORTED_SYMBOLS = list(PROTOTYPES)
 
@@ -329,6 +330,17 @@ def default_config(width, height, qp, max_split_depth, device=0, n_slots=1, extr
     cfg.device = device
     cfg.n_slots = n_slots
     return cfg
+
+
+def const_field(cfg, name, dtype):
+    """wrenc_gpu_test_const_field (host only): member `name` of the constant block the device is given for `cfg`, as a flat
+    array of `dtype`; WrencGpuError for a name the block does not have."""
+    lib = load_library()
+    buf = np.zeros(1 << 16, np.uint8)   # (the largest member, dct, is 8 KiB)
+    n = lib.wrenc_gpu_test_const_field(C.byref(cfg), name.encode(), _p(buf), buf.size)
+    if n < 0:
+        raise WrencGpuError(n, "const_field(%r)" % (name,))
+    return buf[:n].view(dtype).copy()
 
 
 def _p(a):
