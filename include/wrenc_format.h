@@ -15,6 +15,9 @@
  *     4   yuv422p      Y w x h, Cb w/2 x h, Cr w/2 x h                          u8
  *     5   yuv422p10le  as 4                                                     u16 little-endian, low 10 bits
  *
+ * These are layouts of Y'CbCr samples: nothing here changes colour or range.  RGB sources, and with them the colour matrix
+ * and the range, live in wrenc_rgb.h (wrenc_gpu_set_source_rgb), with layout ids of their own.
+ *
  * Conversion, no dithering.
  *   The 10-bit value s of a word v:  low-bit formats s = min(v, 1023) -- stray high bits saturate, they do not wrap;
  *                                    p010le s = v >> 6 -- the low six bits are ignored.

@@ -208,6 +208,49 @@ int wrenc_gpu_upload_planes(wrenc_gpu_ctx* ctx, int slot, const void* const plan
 int wrenc_gpu_format_from_name(const char* name);
 const char* wrenc_gpu_format_name(int format);
 int wrenc_gpu_format_layout(int format, int w, int h, struct wrenc_gpu_format_layout* out);
+/* RGB sources.  wrenc_rgb.h names five layouts (rgb24 = 0, bgr24, rgb0, bgr0, gbrp: an id space of their own, separate from
+ * the format ids above), two matrices (bt709 = 0, bt601 = 1) and two ranges (tv = 0, pc = 1) and defines the conversion to
+ * 8-bit 4:2:0 Y'CbCr in integers: luma per pixel, chroma from the 2x2 mean, rounded once.  wrenc_gpu_set_source_rgb makes
+ * wrenc_gpu_upload_planes take the layout's planes as wrenc_gpu_rgb_layout numbers them -- plane[0] alone for the packed
+ * layouts, G, B, R for gbrp -- copy them into the raw staging planes as with a source format, and a kernel behind the copies
+ * (wrenc_amd/csrc/dev_rgb.h) writes the converted picture, bit for bit what wrenc_gpu_rgb_convert_host gives: into the
+ * scaler's staging planes when a source size is set -- conversion comes BEFORE scaling -- else into the slot's planes.
+ * Everything behind the upload sees the converted picture.  The stream carries no VUI: matrix and range are NOT signalled.
+ * The rules of wrenc_gpu_set_source_format apply: any order with the size setters; WRENC_GPU_EINVAL for an unknown layout,
+ * matrix or range; WRENC_GPU_ESTATE once any slot has been uploaded into; layout -1 (matrix and range are then not read)
+ * puts the context back, and a context on which no RGB source is set launches and allocates nothing it did not before.
+ * An RGB source and a non-zero source format exclude each other: while one is set, setting the other returns
+ * WRENC_GPU_ESTATE (wrenc_gpu_set_source_format(ctx, 0) stays a no-op that succeeds).  While an RGB source is set
+ * wrenc_gpu_upload and wrenc_gpu_encode_picture return WRENC_GPU_ESTATE and wrenc_gpu_source_format keeps returning 0.
+ * wrenc_gpu_source_rgb: the three ids; layout -1 (and 0, 0) when none is set. */
+int wrenc_gpu_set_source_rgb(wrenc_gpu_ctx* ctx, int layout, int matrix, int range);
+int wrenc_gpu_source_rgb(const wrenc_gpu_ctx* ctx, int* layout, int* matrix, int* range);
+/* Host only, callable without a device.  The id of a layout's name ("rgba" and "bgra" are aliases of rgb0 and bgr0) or
+ * WRENC_GPU_EINVAL; the name of an id or NULL; the layout of a tightly packed w x h frame (n_planes 1 or 3; the limits of
+ * wrenc_gpu_format_layout); the nine coefficients in the order yr yg yb, br bg bb, rr rg rb, then yoff; and the rules of
+ * wrenc_rgb.h over a whole picture -- planes and strides as wrenc_gpu_rgb_layout numbers them, y of w x h and cb, cr of
+ * w/2 x h/2 bytes tightly packed -- which is what the device can be held against.  WRENC_GPU_EINVAL for an unknown id, a
+ * size outside the limits, a null pointer that is read or a stride smaller than the row. */
+int wrenc_gpu_rgb_from_name(const char* name);
+const char* wrenc_gpu_rgb_name(int layout);
+int wrenc_gpu_rgb_layout(int layout, int w, int h, struct wrenc_gpu_format_layout* out);
+int wrenc_gpu_rgb_coefficients(int matrix, int range, int out[10]);
+int wrenc_gpu_rgb_convert_host(int layout, int matrix, int range, int w, int h, const void* const plane[3], const size_t stride_bytes[3],
+                               uint8_t* y, uint8_t* cb, uint8_t* cr);
+/* Pictures that are already in device memory.  wrenc_gpu_upload_planes with planes that are DEVICE memory of the context's
+ * device, for every source kind: format 0, the other formats and RGB.  The data is COPIED (device to device) into the places
+ * the host entry copies to -- the kernels keep the alignment and read-past-row guarantees of the library's own pitches --;
+ * the caller's memory is not read in place.  The null, stride and alignment checks of the host entry apply, and each plane
+ * that is read must be device memory of the context's device (hipPointerGetAttributes): WRENC_GPU_EINVAL for a host pointer,
+ * pinned or not, and for memory of another device.
+ * Ordering, with no host wait in the call.  producer_stream is a hipStream_t; NULL is the null stream (PyTorch's default
+ * stream on ROCm), handled like any other: the context's copy stream is non-blocking and does not synchronise with it by
+ * itself.  The call records an event on the producer stream and the copy stream waits for it; once this upload's copies are
+ * queued it records an event on the copy stream and the producer stream waits for that.  So the caller may queue the upload
+ * right behind the work that writes the planes, and work that overwrites or frees them right behind the upload, on that
+ * stream, without synchronising.  Work on OTHER streams that touches the planes is the caller's to order. */
+int wrenc_gpu_upload_planes_device(wrenc_gpu_ctx* ctx, int slot, const void* const plane[3], const size_t stride_bytes[3],
+                                   void* producer_stream);
 /* Test entry: the coded-size original planes a slot holds (width*height, then (width/2)*(height/2) twice), margin
  * included.  Blocking, behind the copy stream.  WRENC_GPU_ESTATE for a slot never uploaded into. */
 int wrenc_gpu_test_download_originals(wrenc_gpu_ctx* ctx, int slot, uint8_t* y, uint8_t* cb, uint8_t* cr);

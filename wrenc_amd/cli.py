@@ -6,7 +6,8 @@ arguments, so that `python -m wrenc_amd.cli` and the program are one pipeline.
 
 The program takes the reference's options (main.rs:85-115) and a few of its own (README; among them --pad, with which
 --output-size may be any even size such as 1920x1080, and --hash md5|crc|checksum, which puts a decoded picture hash SEI
-behind every slice); its standard streams are
+behind every slice, and --input-format rgb24|bgr24|rgb0|bgr0|rgba|bgra|gbrp with --colorspace bt709|bt601 and --range tv|pc
+for RGB frames, which the device converts); its standard streams are
 this process's and its exit status is this one's: 0 on success and, like the reference, on argument and I/O errors
 (main.rs:127-133); 101 where the reference panics.  There is no CPU path: without an MI355X the command fails.
 """

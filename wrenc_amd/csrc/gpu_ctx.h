@@ -7,6 +7,7 @@
 #include "../../include/wrenc_gpu.h"
 #include "../../include/wrenc_scale.h"
 #include "../../include/wrenc_format.h"
+#include "../../include/wrenc_rgb.h"
 #include "../../include/wrenc_hash.h"
 #include "../../include/wrenc_ratecurve.h"
 
@@ -109,6 +110,12 @@ struct wrenc_gpu_ctx {
     // the same argument, allocated when the format is set or, where the sizes came later, at the first upload
     int src_format = 0;
     DevBuf<uint8_t> d_raw;
+    // an RGB source (wrenc_gpu_set_source_rgb; layout -1: none): exclusive with a non-zero format, the same raw staging
+    // planes, dev_rgb.h's converter in the place of dev_format.h's
+    int src_rgb = -1, rgb_matrix = 0, rgb_range = 0;
+    // device-resident planes (wrenc_gpu_upload_planes_device; made on first use): "the producer stream has written the
+    // planes" for copy_stream to wait for, and "the copies have read them" for the producer stream to wait for
+    HipEvent ev_producer, ev_copied;
     DevBuf<unsigned long long> d_mismatch;
     DevBuf<int> d_overflow;
     // made by the first encode call, both or neither:

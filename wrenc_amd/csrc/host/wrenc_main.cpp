@@ -44,6 +44,10 @@
 // from wrenc_gpu_format_layout -- and uploaded as it is (wrenc_gpu_upload_planes); the device converts it to 8-bit 4:2:0
 // behind the copy and in front of the scaler.  Everything else is the run on the converted pictures: --reconst stays 8-bit
 // 4:2:0 of --output-size and --metrics compares the reconstruction with the CONVERTED (and scaled) originals.
+// The name may also be an RGB layout (include/wrenc_rgb.h): rgb24, bgr24, rgb0, bgr0 (rgba and bgra are aliases) or gbrp.  The
+// device then makes Y'CbCr of the frames by --colorspace bt709|bt601 (default bt709) and --range tv|pc (default tv)
+// (wrenc_gpu_set_source_rgb); the two options are argument errors with a YUV input.  The stream carries no VUI: what was
+// chosen is not signalled in it.
 //
 // --hash md5|crc|checksum: every picture's slice is followed by a decoded picture hash SEI (H.274; include/wrenc_hash.h), so
 // that any conforming decoder checks what it decodes against what this encoder reconstructed.  The device takes the hash
@@ -180,6 +184,8 @@ struct Options {
     bool scale = false;
     int in_w = 0, in_h = 0;    // the size of the input's frames: --input-size with --scale, else vis_w x vis_h
     int format = 0;            // --input-format: their pixel format (wrenc_format.h), yuv420p unless given
+    int rgb = -1;              // ... or their RGB layout (wrenc_rgb.h), -1: none; then --colorspace and --range say how the
+    int rgb_matrix = 0, rgb_range = 0; // device makes Y'CbCr of them: bt709 | bt601, tv | pc
     int hash = -1;             // --hash: the type of the decoded picture hash SEI behind every slice (wrenc_hash.h), -1: none
     int depth = 3, batch = 64, n_threads = 8;
     bool verbose = false;
@@ -219,7 +225,8 @@ std::vector<int> read_qp_file(const char* path, long num_pictures) {
 
 Options parse_options(int argc, char** argv) {
     Options o;
-    const char *in_size = nullptr, *out_size = nullptr, *device_list = nullptr, *qp_file = nullptr, *bitrate = nullptr, *fps = nullptr, *vbv = nullptr;
+    const char *in_size = nullptr, *out_size = nullptr, *device_list = nullptr, *qp_file = nullptr, *bitrate = nullptr, *fps = nullptr, *vbv = nullptr,
+               *colorspace = nullptr, *range = nullptr;
     int device = 0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -251,7 +258,23 @@ Options parse_options(int argc, char** argv) {
         else if (a == "--input-format") {
             const char* v = val();
             o.format = wrenc_gpu_format_from_name(v);
-            if (o.format < 0) die("Invalid input-format: %s (yuv420p, nv12, yuv420p10le, p010le, yuv422p, yuv422p10le)", v);
+            o.rgb = -1;
+            if (o.format < 0) { // not one of the six formats: an RGB layout (include/wrenc_rgb.h)
+                o.format = 0;
+                o.rgb = wrenc_gpu_rgb_from_name(v);
+                if (o.rgb < 0)
+                    die("Invalid input-format: %s (yuv420p, nv12, yuv420p10le, p010le, yuv422p, yuv422p10le; rgb24, bgr24, rgb0, bgr0, rgba, bgra, gbrp)", v);
+            }
+        }
+        else if (a == "--colorspace") {
+            colorspace = val();
+            o.rgb_matrix = !strcmp(colorspace, "bt709") ? 0 : (!strcmp(colorspace, "bt601") ? 1 : -1);
+            if (o.rgb_matrix < 0) die("Invalid colorspace: %s (bt709, bt601)", colorspace);
+        }
+        else if (a == "--range") {
+            range = val();
+            o.rgb_range = !strcmp(range, "tv") ? 0 : (!strcmp(range, "pc") ? 1 : -1);
+            if (o.rgb_range < 0) die("Invalid range: %s (tv, pc)", range);
         }
         else if (a == "--hash") {
             const std::string v = val();
@@ -273,6 +296,8 @@ Options parse_options(int argc, char** argv) {
     }
     if (!o.input || !o.output || !in_size || !out_size || o.num_pictures < 0)
         die("the following options are required: --input --output --input-size --output-size --num-pictures");
+    if ((colorspace || range) && o.rgb < 0)
+        die("%s needs an RGB --input-format (rgb24, bgr24, rgb0, bgr0, rgba, bgra, gbrp): a YUV input is not converted", colorspace ? "--colorspace" : "--range");
     int iw = 0, ih = 0;
     if (!parse_size(in_size, iw, ih)) die("Invalid input-size: %s", in_size); // used with --scale only (below); otherwise parsed and unused, as in main.rs:164-174
     if (!parse_size(out_size, o.w, o.h)) die("Invalid output-size: %s", out_size);
@@ -358,11 +383,11 @@ struct Geometry {
     size_t ipic;            // ... and its bytes
     size_t n4, maps;        // 4x4 luma blocks; bytes of cu_log2_size | luma_mode | chroma_mode
     size_t mask_words, level_blocks, n_ctus;
-    Geometry(int w_, int h_, int vw_, int vh_, int iw_, int ih_, int format)
+    Geometry(int w_, int h_, int vw_, int vh_, int iw_, int ih_, int format, int rgb)
         : w(w_), h(h_), vw(vw_), vh(vh_), iw(iw_), ih(ih_), ysz((size_t)w_ * h_), csz(ysz / 4), pic(ysz + 2 * csz), in(), ipic(0),
           n4(ysz / 16), maps(2 * n4 + ysz / 64), mask_words(wrenc_gpu_compact_mask_words(w_, h_)), level_blocks(pic / 16),
           n_ctus((size_t)(w_ / 32) * (h_ / 32)) {
-        if (wrenc_gpu_format_layout(format, iw_, ih_, &in)) die("input frames must be of an even size, at least 16x16: %dx%d", iw_, ih_);
+        if (rgb >= 0 ? wrenc_gpu_rgb_layout(rgb, iw_, ih_, &in) : wrenc_gpu_format_layout(format, iw_, ih_, &in)) die("input frames must be of an even size, at least 16x16: %dx%d", iw_, ih_);
         ipic = in.frame_bytes;
     }
 };
@@ -864,9 +889,10 @@ int main(int argc, char** argv) {
         if (o.pad && wrenc_gpu_set_visible_size(ctx, o.vis_w, o.vis_h)) fatal("%s", wrenc_gpu_last_error(ctx));
         if (o.scale && wrenc_gpu_set_source_size(ctx, o.in_w, o.in_h)) fatal("%s", wrenc_gpu_last_error(ctx)); // after the visible size
         if (o.format && wrenc_gpu_set_source_format(ctx, o.format)) fatal("%s", wrenc_gpu_last_error(ctx));
+        if (o.rgb >= 0 && wrenc_gpu_set_source_rgb(ctx, o.rgb, o.rgb_matrix, o.rgb_range)) fatal("%s", wrenc_gpu_last_error(ctx));
         ctxs.push_back(ctx);
     }
-    const Geometry g(o.w, o.h, o.vis_w, o.vis_h, o.in_w, o.in_h, o.format);
+    const Geometry g(o.w, o.h, o.vis_w, o.vis_h, o.in_w, o.in_h, o.format, o.rgb);
     std::vector<HostSet> units = make_units(o, g, ctxs, per_dev, frec != nullptr);
     size_t hdr_bytes = 0, rate_hdr_bytes = 0;
     {

@@ -34,6 +34,7 @@
 //   dev_pad.h        (no counterpart)               a picture's last column and row replicated into the coded size's margin
 //   dev_scale.h      (no counterpart)               resampling of an uploaded picture to the visible size
 //   dev_format.h     (no counterpart)               10-bit, NV12 / P010 and 4:2:2 uploads to the 8-bit 4:2:0 planes
+//   dev_rgb.h        (no counterpart)               RGB uploads to the 8-bit 4:2:0 Y'CbCr planes (matrix, range, 2x2 chroma mean)
 #pragma once
 
 // The WRENC_EXP_* switches are measurement builds (tools/README.md); several of them give wrong results on purpose.

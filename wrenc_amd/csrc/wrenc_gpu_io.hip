@@ -1,6 +1,6 @@
 // wrenc_gpu_io.hip -- pictures in and results out: every upload path of the C ABI (include/wrenc_gpu.h: plain, strided,
-// visible size, scaler, source formats) and every read-back (maps, compact, tokens, metrics, complexity, rate histogram,
-// hashes), with the kernels they launch.  A translation unit and a code object of its own in libwrenc_gpu.so (the command
+// visible size, scaler, source formats, RGB sources, device-resident planes) and every read-back (maps, compact, tokens,
+// metrics, complexity, rate histogram, hashes), with the kernels they launch.  A translation unit and a code object of its own in libwrenc_gpu.so (the command
 // is at the top of wrenc_gpu.hip): what is added or changed here cannot move an instruction of the search kernels.
 //
 // The trace and profile builds (-DWRENC_TRACE, -DWRENC_PROFILE) define their device globals in dev_common.h; nothing here
@@ -23,6 +23,7 @@
 #include "dev_pad.h"
 #include "dev_scale.h"
 #include "dev_format.h"
+#include "dev_rgb.h"
 
 #include <cmath>
 #include <cstring>
@@ -243,6 +244,13 @@ static hipError_t upload_hash_tables(HashTables* d_tables, hipStream_t st) {
     return e != hipSuccess ? e : hipStreamSynchronize(st);
 }
 
+// the RGB converter over one picture (dev_rgb.h), layout L
+template <int L>
+static void launch_rgb(const RgbArgs& a, hipStream_t cs) {
+    const dim3 grid((unsigned)((a.w + 64 * kRgbGroup - 1) / (64 * kRgbGroup)), (unsigned)((a.h / 2 + kRgbRows - 1) / kRgbRows));
+    hipLaunchKernelGGL(convert_rgb_kernel<L>, grid, dim3(64, kRgbRows), 0, cs, a);
+}
+
 extern "C" {
 
 // what every upload ends with, on copy_stream behind whatever wrote the visible rectangle of the slot's planes
@@ -267,11 +275,39 @@ static int finish_upload(wrenc_gpu_ctx* ctx, int slot) {
     return WRENC_GPU_OK;
 }
 
-int wrenc_gpu_upload(wrenc_gpu_ctx* ctx, int slot, const uint8_t* y, const uint8_t* cb, const uint8_t* cr,
-                     size_t stride_y, size_t stride_c) {
-    if (!ctx) return WRENC_GPU_EINVAL;
+// Where the planes of an upload lie: host memory (the entries that take host pointers) or memory of the context's device
+// (wrenc_gpu_upload_planes_device), whose copies are ordered against the caller's stream on both sides.
+struct PlaneSource {
+    hipMemcpyKind kind = hipMemcpyHostToDevice;
+    bool device = false;
+    hipStream_t producer = nullptr;
+};
+
+// device-resident planes: copy_stream goes on only behind what the producer stream has queued so far ...
+static int wait_for_producer(wrenc_gpu_ctx* ctx, const PlaneSource& from) {
+    if (!from.device) return WRENC_GPU_OK;
+    if (!ctx->ev_producer) HIP_TRY(ctx, ctx->ev_producer.create(hipEventDisableTiming));
+    if (!ctx->ev_copied) HIP_TRY(ctx, ctx->ev_copied.create(hipEventDisableTiming));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_producer.get(), from.producer));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream.get(), ctx->ev_producer.get(), 0));
+    return WRENC_GPU_OK;
+}
+
+// ... and what the producer stream queues from now on runs behind the copies of this upload, which are all queued: the
+// caller may overwrite or free the planes on that stream right away.  No host wait on either side.
+static int release_producer(wrenc_gpu_ctx* ctx, const PlaneSource& from) {
+    if (!from.device) return WRENC_GPU_OK;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_copied.get(), ctx->copy_stream.get()));
+    HIP_TRY(ctx, hipStreamWaitEvent(from.producer, ctx->ev_copied.get(), 0));
+    return WRENC_GPU_OK;
+}
+
+// the plain upload: planar 8-bit 4:2:0 planes of the source size (wrenc_gpu_upload, and format 0 of the entries below)
+static int upload_plain(wrenc_gpu_ctx* ctx, int slot, const uint8_t* y, const uint8_t* cb, const uint8_t* cr, size_t stride_y, size_t stride_c,
+                        const PlaneSource& from) {
     if (slot < 0 || slot >= ctx->cfg.n_slots || !y || !cb || !cr) return fail(ctx, WRENC_GPU_EINVAL, "bad slot or null plane");
     if (ctx->src_format) return fail(ctx, WRENC_GPU_ESTATE, "a source format is set: the planes go through wrenc_gpu_upload_planes");
+    if (ctx->src_rgb >= 0) return fail(ctx, WRENC_GPU_ESTATE, "an RGB source is set: the planes go through wrenc_gpu_upload_planes");
     const size_t w = ctx->cfg.width, h = ctx->cfg.height;
     const size_t vw = (size_t)ctx->vis_w, vh = (size_t)ctx->vis_h; // the slot's picture; w x h unless a visible size is set
     const bool scaling = ctx->src_w != 0;
@@ -282,6 +318,7 @@ int wrenc_gpu_upload(wrenc_gpu_ctx* ctx, int slot, const uint8_t* y, const uint8
     // the planes may still be read by a search in flight on this slot
     if (ctx->slot_event[slot]) HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream.get(), ctx->slot_event[slot], 0));
     hipStream_t cs = ctx->copy_stream.get();
+    if (const int rc = wait_for_producer(ctx, from)) return rc;
     if (scaling) {
         // Source-size planes into the context's staging planes, then the scaler (dev_scale.h) writes the visible
         // rectangle of the slot's planes.  Copies, scaler, pad and retile all run on copy_stream, in order: the one set of
@@ -291,18 +328,26 @@ int wrenc_gpu_upload(wrenc_gpu_ctx* ctx, int slot, const uint8_t* y, const uint8
         // converted out of, and the scaler's planes -- which the converter then writes in place of the copies -- scaled
         // out of, before the next upload's first copy starts.
         ScaleArgs a = ctx->scale_args;
-        const uint8_t* const from[3] = {y, cb, cr};
+        const uint8_t* const planes[3] = {y, cb, cr};
         for (int p = 0; p < 3; ++p)
-            HIP_TRY(ctx, hipMemcpy2DAsync((void*)a.src[p], (size_t)a.src_pitch[p ? 1 : 0], from[p], p ? stride_c : stride_y,
-                                          p ? sw / 2 : sw, p ? sh / 2 : sh, hipMemcpyHostToDevice, cs));
+            HIP_TRY(ctx, hipMemcpy2DAsync((void*)a.src[p], (size_t)a.src_pitch[p ? 1 : 0], planes[p], p ? stride_c : stride_y,
+                                          p ? sw / 2 : sw, p ? sh / 2 : sh, from.kind, cs));
+        if (const int rc = release_producer(ctx, from)) return rc;
         a.dst = (uint8_t*)b.org[0];
         hipLaunchKernelGGL(scale_kernel, dim3((unsigned)(a.tiles[0] + 2 * a.tiles[1])), dim3(256), 0, cs, a);
     } else {
-        HIP_TRY(ctx, hipMemcpy2DAsync((void*)b.org[0], w, y, stride_y, vw, vh, hipMemcpyHostToDevice, cs));
-        HIP_TRY(ctx, hipMemcpy2DAsync((void*)b.org[1], w / 2, cb, stride_c, vw / 2, vh / 2, hipMemcpyHostToDevice, cs));
-        HIP_TRY(ctx, hipMemcpy2DAsync((void*)b.org[2], w / 2, cr, stride_c, vw / 2, vh / 2, hipMemcpyHostToDevice, cs));
+        HIP_TRY(ctx, hipMemcpy2DAsync((void*)b.org[0], w, y, stride_y, vw, vh, from.kind, cs));
+        HIP_TRY(ctx, hipMemcpy2DAsync((void*)b.org[1], w / 2, cb, stride_c, vw / 2, vh / 2, from.kind, cs));
+        HIP_TRY(ctx, hipMemcpy2DAsync((void*)b.org[2], w / 2, cr, stride_c, vw / 2, vh / 2, from.kind, cs));
+        if (const int rc = release_producer(ctx, from)) return rc;
     }
     return finish_upload(ctx, slot);
+}
+
+int wrenc_gpu_upload(wrenc_gpu_ctx* ctx, int slot, const uint8_t* y, const uint8_t* cb, const uint8_t* cr,
+                     size_t stride_y, size_t stride_c) {
+    if (!ctx) return WRENC_GPU_EINVAL;
+    return upload_plain(ctx, slot, y, cb, cr, stride_y, stride_c, PlaneSource{});
 }
 
 int wrenc_gpu_set_visible_size(wrenc_gpu_ctx* ctx, int vis_w, int vis_h) {
@@ -469,20 +514,42 @@ int wrenc_gpu_format_layout(int format, int w, int h, struct wrenc_gpu_format_la
     return wrenc_format_layout(format, w, h, out) ? WRENC_GPU_EINVAL : WRENC_GPU_OK;
 }
 
+int wrenc_gpu_rgb_from_name(const char* name) {
+    const int l = wrenc_rgb_from_name(name);
+    return l < 0 ? WRENC_GPU_EINVAL : l;
+}
+
+const char* wrenc_gpu_rgb_name(int layout) { return wrenc_rgb_name(layout); }
+
+int wrenc_gpu_rgb_layout(int layout, int w, int h, struct wrenc_gpu_format_layout* out) {
+    return wrenc_rgb_layout(layout, w, h, out) ? WRENC_GPU_EINVAL : WRENC_GPU_OK;
+}
+
+int wrenc_gpu_rgb_coefficients(int matrix, int range, int out[10]) { return wrenc_rgb_coefficients(matrix, range, out) ? WRENC_GPU_EINVAL : WRENC_GPU_OK; }
+
+int wrenc_gpu_rgb_convert_host(int layout, int matrix, int range, int w, int h, const void* const plane[3], const size_t stride_bytes[3],
+                               uint8_t* y, uint8_t* cb, uint8_t* cr) {
+    if (!plane) return WRENC_GPU_EINVAL;
+    const uint8_t* const from[3] = {(const uint8_t*)plane[0], (const uint8_t*)plane[1], (const uint8_t*)plane[2]};
+    return wrenc_rgb_convert(layout, matrix, range, w, h, from, stride_bytes, y, cb, cr) ? WRENC_GPU_EINVAL : WRENC_GPU_OK;
+}
+
 namespace {
 
-// the raw staging planes of the context's format at its source size: pitches, offsets and the bytes of the allocation
+// the raw staging planes of the context's format or RGB layout at its source size: pitches, offsets and the bytes of the
+// allocation
 struct RawStage {
     struct wrenc_gpu_format_layout lay;
     size_t pitch[3], off[3], bytes;
 };
 
-bool raw_stage(const wrenc_gpu_ctx* ctx, int format, RawStage& r) {
+// rgb < 0: source format `format` (dev_format.h's pitch); else RGB layout `rgb` (dev_rgb.h's, with room for the last lane's reads)
+bool raw_stage(const wrenc_gpu_ctx* ctx, int format, int rgb, RawStage& r) {
     const int sw = ctx->src_w ? ctx->src_w : ctx->vis_w, sh = ctx->src_w ? ctx->src_h : ctx->vis_h;
-    if (wrenc_format_layout(format, sw, sh, &r.lay)) return false;
+    if (rgb >= 0 ? wrenc_rgb_layout(rgb, sw, sh, &r.lay) : wrenc_format_layout(format, sw, sh, &r.lay)) return false;
     r.bytes = 0;
     for (int p = 0; p < 3; ++p) {
-        r.pitch[p] = format_raw_pitch(r.lay.row_bytes[p]);
+        r.pitch[p] = rgb >= 0 && p < r.lay.n_planes ? rgb_raw_pitch(rgb, sw) : format_raw_pitch(r.lay.row_bytes[p]);
         r.off[p] = r.bytes;
         r.bytes += r.pitch[p] * r.lay.rows[p];
     }
@@ -498,40 +565,18 @@ int ensure_raw_stage(wrenc_gpu_ctx* ctx, const RawStage& r) {
     return WRENC_GPU_OK;
 }
 
-} // namespace
-
-int wrenc_gpu_set_source_format(wrenc_gpu_ctx* ctx, int format) {
-    if (!ctx) return WRENC_GPU_EINVAL;
-    if (!wrenc_format_valid(format)) return fail(ctx, WRENC_GPU_EINVAL, "unknown source format");
-    if (ctx->any_upload) return fail(ctx, WRENC_GPU_ESTATE, "the source format must be set before the first upload");
-    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-    if (format == WRENC_FORMAT_YUV420P) {
-        ctx->d_raw.reset();
-        ctx->src_format = 0;
-        return WRENC_GPU_OK;
-    }
-    RawStage r;
-    if (!raw_stage(ctx, format, r)) return fail(ctx, WRENC_GPU_EINVAL, "the source format needs pictures of an even size, at least 16x16");
-    const int rc = ensure_raw_stage(ctx, r);
-    if (rc) return rc;
-    ctx->src_format = format;
-    return WRENC_GPU_OK;
-}
-
-int wrenc_gpu_source_format(const wrenc_gpu_ctx* ctx) { return ctx ? ctx->src_format : WRENC_GPU_EINVAL; }
-
-int wrenc_gpu_upload_planes(wrenc_gpu_ctx* ctx, int slot, const void* const plane[3], const size_t stride_bytes[3]) {
-    if (!ctx) return WRENC_GPU_EINVAL;
+// the planes of the context's source kind -- format 0, another format or an RGB layout -- from `from` into slot `slot`
+int upload_planes_from(wrenc_gpu_ctx* ctx, int slot, const void* const plane[3], const size_t stride_bytes[3], const PlaneSource& from) {
     if (!plane || !stride_bytes) return fail(ctx, WRENC_GPU_EINVAL, "null plane or stride list");
-    const int format = ctx->src_format;
-    if (format == WRENC_FORMAT_YUV420P) {
+    const int format = ctx->src_format, rgb = ctx->src_rgb;
+    if (format == WRENC_FORMAT_YUV420P && rgb < 0) {
         if (stride_bytes[1] != stride_bytes[2]) return fail(ctx, WRENC_GPU_EINVAL, "yuv420p: the two chroma planes share one stride");
-        return wrenc_gpu_upload(ctx, slot, (const uint8_t*)plane[0], (const uint8_t*)plane[1], (const uint8_t*)plane[2], stride_bytes[0],
-                                stride_bytes[1]);
+        return upload_plain(ctx, slot, (const uint8_t*)plane[0], (const uint8_t*)plane[1], (const uint8_t*)plane[2], stride_bytes[0],
+                            stride_bytes[1], from);
     }
     if (slot < 0 || slot >= ctx->cfg.n_slots) return fail(ctx, WRENC_GPU_EINVAL, "bad slot or null plane");
     RawStage r;
-    if (!raw_stage(ctx, format, r)) return fail(ctx, WRENC_GPU_EINVAL, "the source format needs pictures of an even size, at least 16x16");
+    if (!raw_stage(ctx, format, rgb, r)) return fail(ctx, WRENC_GPU_EINVAL, "the source format needs pictures of an even size, at least 16x16");
     for (int p = 0; p < r.lay.n_planes; ++p) {
         if (!plane[p]) return fail(ctx, WRENC_GPU_EINVAL, "bad slot or null plane");
         if (stride_bytes[p] < r.lay.row_bytes[p]) return fail(ctx, WRENC_GPU_EINVAL, "stride smaller than row");
@@ -547,42 +592,79 @@ int wrenc_gpu_upload_planes(wrenc_gpu_ctx* ctx, int slot, const void* const plan
     // the planes may still be read by a search in flight on this slot
     if (ctx->slot_event[slot]) HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream.get(), ctx->slot_event[slot], 0));
     hipStream_t cs = ctx->copy_stream.get();
-    // the caller's bytes as they are -- a 10-bit picture crosses the bus once -- and behind them the converter (dev_format.h)
-    FormatArgs a = {};
-    a.raw = ctx->d_raw.get();
-    for (int p = 0; p < r.lay.n_planes; ++p) {
+    if (const int rcw = wait_for_producer(ctx, from)) return rcw;
+    // the caller's bytes as they are -- a 10-bit picture crosses the bus once -- and behind them the converter (dev_format.h,
+    // dev_rgb.h)
+    for (int p = 0; p < r.lay.n_planes; ++p)
         HIP_TRY(ctx, hipMemcpy2DAsync((void*)(ctx->d_raw.get() + r.off[p]), r.pitch[p], plane[p], stride_bytes[p], r.lay.row_bytes[p], r.lay.rows[p],
-                                      hipMemcpyHostToDevice, cs));
-        a.raw_off[p] = r.off[p];
-        a.raw_pitch[p] = (int)r.pitch[p];
-    }
+                                      from.kind, cs));
+    if (const int rcr = release_producer(ctx, from)) return rcr;
+    // the 8-bit planes the converter writes
+    uint8_t* dst;
+    size_t dst_off[3] = {0, 0, 0};
+    int dst_pitch[2], cw, ch;
     if (scaling) { // into the scaler's staging planes, in the place of wrenc_gpu_upload's copies
         const ScaleArgs& s = ctx->scale_args;
-        a.dst = ctx->d_stage.get();
-        for (int p = 0; p < 3; ++p) a.dst_off[p] = (size_t)(s.src[p] - s.src[0]);
-        a.dst_pitch[0] = s.src_pitch[0];
-        a.dst_pitch[1] = s.src_pitch[1];
-        a.w = ctx->src_w;
-        a.h = ctx->src_h;
+        dst = ctx->d_stage.get();
+        for (int p = 0; p < 3; ++p) dst_off[p] = (size_t)(s.src[p] - s.src[0]);
+        dst_pitch[0] = s.src_pitch[0];
+        dst_pitch[1] = s.src_pitch[1];
+        cw = ctx->src_w;
+        ch = ctx->src_h;
     } else { // into the visible rectangle of the slot's planes
-        a.dst = (uint8_t*)b.org[0];
-        a.dst_off[1] = w * h;
-        a.dst_off[2] = w * h + w * h / 4;
-        a.dst_pitch[0] = (int)w;
-        a.dst_pitch[1] = (int)(w / 2);
-        a.w = ctx->vis_w;
-        a.h = ctx->vis_h;
+        dst = (uint8_t*)b.org[0];
+        dst_off[1] = w * h;
+        dst_off[2] = w * h + w * h / 4;
+        dst_pitch[0] = (int)w;
+        dst_pitch[1] = (int)(w / 2);
+        cw = ctx->vis_w;
+        ch = ctx->vis_h;
     }
-    a.row_blocks[0] = (a.h + kFormatRows - 1) / kFormatRows;
-    a.row_blocks[1] = (a.h / 2 + kFormatRows - 1) / kFormatRows;
-    const dim3 grid((unsigned)((a.w + 64 * kFormatGroup - 1) / (64 * kFormatGroup)),
-                    (unsigned)(a.row_blocks[0] + (r.lay.n_planes == 2 ? 1 : 2) * a.row_blocks[1])), block(64, kFormatRows);
-    switch (format) {
-    case WRENC_FORMAT_NV12: hipLaunchKernelGGL(convert_format_kernel<WRENC_FORMAT_NV12>, grid, block, 0, cs, a); break;
-    case WRENC_FORMAT_YUV420P10LE: hipLaunchKernelGGL(convert_format_kernel<WRENC_FORMAT_YUV420P10LE>, grid, block, 0, cs, a); break;
-    case WRENC_FORMAT_P010LE: hipLaunchKernelGGL(convert_format_kernel<WRENC_FORMAT_P010LE>, grid, block, 0, cs, a); break;
-    case WRENC_FORMAT_YUV422P: hipLaunchKernelGGL(convert_format_kernel<WRENC_FORMAT_YUV422P>, grid, block, 0, cs, a); break;
-    default: hipLaunchKernelGGL(convert_format_kernel<WRENC_FORMAT_YUV422P10LE>, grid, block, 0, cs, a); break;
+    if (rgb >= 0) {
+        RgbArgs a = {};
+        a.raw = ctx->d_raw.get();
+        a.dst = dst;
+        for (int p = 0; p < 3; ++p) {
+            a.raw_off[p] = r.off[p];
+            a.dst_off[p] = dst_off[p];
+        }
+        a.raw_pitch = (int)r.pitch[0];
+        a.dst_pitch[0] = dst_pitch[0];
+        a.dst_pitch[1] = dst_pitch[1];
+        a.w = cw;
+        a.h = ch;
+        wrenc_rgb_coefficients(ctx->rgb_matrix, ctx->rgb_range, a.k);
+        switch (rgb) {
+        case WRENC_RGB_RGB24: launch_rgb<WRENC_RGB_RGB24>(a, cs); break;
+        case WRENC_RGB_BGR24: launch_rgb<WRENC_RGB_BGR24>(a, cs); break;
+        case WRENC_RGB_RGB0: launch_rgb<WRENC_RGB_RGB0>(a, cs); break;
+        case WRENC_RGB_BGR0: launch_rgb<WRENC_RGB_BGR0>(a, cs); break;
+        default: launch_rgb<WRENC_RGB_GBRP>(a, cs); break;
+        }
+    } else {
+        FormatArgs a = {};
+        a.raw = ctx->d_raw.get();
+        a.dst = dst;
+        for (int p = 0; p < 3; ++p) {
+            a.raw_off[p] = r.off[p];
+            a.raw_pitch[p] = (int)r.pitch[p];
+            a.dst_off[p] = dst_off[p];
+        }
+        a.dst_pitch[0] = dst_pitch[0];
+        a.dst_pitch[1] = dst_pitch[1];
+        a.w = cw;
+        a.h = ch;
+        a.row_blocks[0] = (a.h + kFormatRows - 1) / kFormatRows;
+        a.row_blocks[1] = (a.h / 2 + kFormatRows - 1) / kFormatRows;
+        const dim3 grid((unsigned)((a.w + 64 * kFormatGroup - 1) / (64 * kFormatGroup)),
+                        (unsigned)(a.row_blocks[0] + (r.lay.n_planes == 2 ? 1 : 2) * a.row_blocks[1])), block(64, kFormatRows);
+        switch (format) {
+        case WRENC_FORMAT_NV12: hipLaunchKernelGGL(convert_format_kernel<WRENC_FORMAT_NV12>, grid, block, 0, cs, a); break;
+        case WRENC_FORMAT_YUV420P10LE: hipLaunchKernelGGL(convert_format_kernel<WRENC_FORMAT_YUV420P10LE>, grid, block, 0, cs, a); break;
+        case WRENC_FORMAT_P010LE: hipLaunchKernelGGL(convert_format_kernel<WRENC_FORMAT_P010LE>, grid, block, 0, cs, a); break;
+        case WRENC_FORMAT_YUV422P: hipLaunchKernelGGL(convert_format_kernel<WRENC_FORMAT_YUV422P>, grid, block, 0, cs, a); break;
+        default: hipLaunchKernelGGL(convert_format_kernel<WRENC_FORMAT_YUV422P10LE>, grid, block, 0, cs, a); break;
+        }
     }
     if (scaling) {
         ScaleArgs s = ctx->scale_args;
@@ -590,6 +672,93 @@ int wrenc_gpu_upload_planes(wrenc_gpu_ctx* ctx, int slot, const void* const plan
         hipLaunchKernelGGL(scale_kernel, dim3((unsigned)(s.tiles[0] + 2 * s.tiles[1])), dim3(256), 0, cs, s);
     }
     return finish_upload(ctx, slot);
+}
+
+} // namespace
+
+int wrenc_gpu_set_source_format(wrenc_gpu_ctx* ctx, int format) {
+    if (!ctx) return WRENC_GPU_EINVAL;
+    if (!wrenc_format_valid(format)) return fail(ctx, WRENC_GPU_EINVAL, "unknown source format");
+    if (ctx->any_upload) return fail(ctx, WRENC_GPU_ESTATE, "the source format must be set before the first upload");
+    if (ctx->src_rgb >= 0) { // the raw staging planes are the RGB source's
+        if (format != WRENC_FORMAT_YUV420P) return fail(ctx, WRENC_GPU_ESTATE, "an RGB source is set (wrenc_gpu_set_source_rgb): put it back with layout -1 first");
+        return WRENC_GPU_OK;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+    if (format == WRENC_FORMAT_YUV420P) {
+        ctx->d_raw.reset();
+        ctx->src_format = 0;
+        return WRENC_GPU_OK;
+    }
+    RawStage r;
+    if (!raw_stage(ctx, format, -1, r)) return fail(ctx, WRENC_GPU_EINVAL, "the source format needs pictures of an even size, at least 16x16");
+    const int rc = ensure_raw_stage(ctx, r);
+    if (rc) return rc;
+    ctx->src_format = format;
+    return WRENC_GPU_OK;
+}
+
+int wrenc_gpu_source_format(const wrenc_gpu_ctx* ctx) { return ctx ? ctx->src_format : WRENC_GPU_EINVAL; }
+
+int wrenc_gpu_set_source_rgb(wrenc_gpu_ctx* ctx, int layout, int matrix, int range) {
+    if (!ctx) return WRENC_GPU_EINVAL;
+    if (layout != -1 && (!wrenc_rgb_valid(layout) || !wrenc_rgb_matrix_valid(matrix) || !wrenc_rgb_range_valid(range)))
+        return fail(ctx, WRENC_GPU_EINVAL, "unknown RGB layout, matrix or range");
+    if (ctx->any_upload) return fail(ctx, WRENC_GPU_ESTATE, "the RGB source must be set before the first upload");
+    if (ctx->src_format) return fail(ctx, WRENC_GPU_ESTATE, "a source format is set (wrenc_gpu_set_source_format): put it back to 0 first");
+    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+    if (layout == -1) {
+        ctx->d_raw.reset();
+        ctx->src_rgb = -1;
+        return WRENC_GPU_OK;
+    }
+    RawStage r;
+    if (!raw_stage(ctx, 0, layout, r)) return fail(ctx, WRENC_GPU_EINVAL, "an RGB source needs pictures of an even size, at least 16x16");
+    const int rc = ensure_raw_stage(ctx, r);
+    if (rc) return rc;
+    ctx->src_rgb = layout;
+    ctx->rgb_matrix = matrix;
+    ctx->rgb_range = range;
+    return WRENC_GPU_OK;
+}
+
+int wrenc_gpu_source_rgb(const wrenc_gpu_ctx* ctx, int* layout, int* matrix, int* range) {
+    if (!ctx || !layout || !matrix || !range) return WRENC_GPU_EINVAL;
+    *layout = ctx->src_rgb;
+    *matrix = ctx->src_rgb >= 0 ? ctx->rgb_matrix : 0;
+    *range = ctx->src_rgb >= 0 ? ctx->rgb_range : 0;
+    return WRENC_GPU_OK;
+}
+
+int wrenc_gpu_upload_planes(wrenc_gpu_ctx* ctx, int slot, const void* const plane[3], const size_t stride_bytes[3]) {
+    if (!ctx) return WRENC_GPU_EINVAL;
+    return upload_planes_from(ctx, slot, plane, stride_bytes, PlaneSource{});
+}
+
+int wrenc_gpu_upload_planes_device(wrenc_gpu_ctx* ctx, int slot, const void* const plane[3], const size_t stride_bytes[3], void* producer_stream) {
+    if (!ctx) return WRENC_GPU_EINVAL;
+    if (!plane || !stride_bytes) return fail(ctx, WRENC_GPU_EINVAL, "null plane or stride list");
+    // the planes this source kind reads
+    int n = 3;
+    if (ctx->src_format || ctx->src_rgb >= 0) {
+        RawStage r;
+        if (!raw_stage(ctx, ctx->src_format, ctx->src_rgb, r)) return fail(ctx, WRENC_GPU_EINVAL, "the source format needs pictures of an even size, at least 16x16");
+        n = r.lay.n_planes;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+    for (int p = 0; p < n; ++p) {
+        if (!plane[p]) return fail(ctx, WRENC_GPU_EINVAL, "bad slot or null plane");
+        hipPointerAttribute_t at = {};
+        const hipError_t e = hipPointerGetAttributes(&at, plane[p]);
+        if (e != hipSuccess) (void)hipGetLastError(); // a pointer the runtime does not know: plain host memory
+        if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != ctx->cfg.device)
+            return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_upload_planes_device: a plane is not memory of the context's device (host planes go through wrenc_gpu_upload_planes)");
+    }
+    PlaneSource from;
+    from.kind = hipMemcpyDeviceToDevice;
+    from.device = true;
+    from.producer = (hipStream_t)producer_stream;
+    return upload_planes_from(ctx, slot, plane, stride_bytes, from);
 }
 
 int wrenc_gpu_test_download_originals(wrenc_gpu_ctx* ctx, int slot, uint8_t* y, uint8_t* cb, uint8_t* cr) {

@@ -39,6 +39,14 @@ PROTOTYPES = {
     "wrenc_gpu_format_from_name": (_I, [_S]),
     "wrenc_gpu_format_name": (_S, [_I]),
     "wrenc_gpu_format_layout": (_I, [_I, _I, _I, _P]),
+    "wrenc_gpu_set_source_rgb": (_I, [_P, _I, _I, _I]),
+    "wrenc_gpu_source_rgb": (_I, [_P, _P, _P, _P]),
+    "wrenc_gpu_rgb_from_name": (_I, [_S]),
+    "wrenc_gpu_rgb_name": (_S, [_I]),
+    "wrenc_gpu_rgb_layout": (_I, [_I, _I, _I, _P]),
+    "wrenc_gpu_rgb_coefficients": (_I, [_I, _I, _P]),
+    "wrenc_gpu_rgb_convert_host": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "wrenc_gpu_upload_planes_device": (_I, [_P, _I, _P, _P, _P]),
     "wrenc_gpu_encode": (_I, [_P, _I, _I]),
     "wrenc_gpu_set_slot_qp": (_I, [_P, _I, _P]),
     "wrenc_gpu_sync": (_I, [_P]),
@@ -292,6 +300,101 @@ def format_layout(fmt, w, h):
             "offset": list(out.offset[:n]), "frame_bytes": out.frame_bytes}
 
 
+RGB_MATRICES = {"bt709": 0, "bt601": 1}   # include/wrenc_rgb.h
+RGB_RANGES = {"tv": 0, "pc": 1}
+
+
+def rgb_from_name(name):
+    """wrenc_gpu_rgb_from_name (host only): the id of an RGB layout named as ffmpeg names it (include/wrenc_rgb.h; "rgba" and
+    "bgra" are aliases of rgb0 and bgr0); WrencGpuError for an unknown name."""
+    lib = load_library()
+    rc = lib.wrenc_gpu_rgb_from_name(name.encode() if name is not None else None)
+    if rc < 0:
+        raise WrencGpuError(rc, "rgb_from_name(%r)" % (name,))
+    return rc
+
+
+def rgb_name(layout):
+    """wrenc_gpu_rgb_name (host only): the name of a layout id, None for an unknown one."""
+    lib = load_library()
+    name = lib.wrenc_gpu_rgb_name(int(layout))
+    return name.decode() if name is not None else None
+
+
+def _rgb_id(layout):
+    return rgb_from_name(layout) if isinstance(layout, str) else int(layout)
+
+
+def _rgb_matrix_id(matrix):
+    if isinstance(matrix, str):
+        if matrix not in RGB_MATRICES:
+            raise WrencGpuError(-1, "unknown matrix %r" % (matrix,))
+        return RGB_MATRICES[matrix]
+    return int(matrix)
+
+
+def _rgb_range_id(rng):
+    if isinstance(rng, str):
+        if rng not in RGB_RANGES:
+            raise WrencGpuError(-1, "unknown range %r" % (rng,))
+        return RGB_RANGES[rng]
+    return int(rng)
+
+
+def rgb_layout(layout, w, h):
+    """wrenc_gpu_rgb_layout (host only): a tightly packed w x h frame of RGB layout `layout` (an id or a name) as it lies in a
+    raw file, the dict of format_layout."""
+    lib = load_library()
+    out = FormatLayout()
+    rc = lib.wrenc_gpu_rgb_layout(_rgb_id(layout), int(w), int(h), C.byref(out))
+    if rc:
+        raise WrencGpuError(rc, "rgb_layout(%r, %d, %d)" % (layout, w, h))
+    n = out.n_planes
+    return {"n_planes": n, "bytes_per_sample": out.bytes_per_sample, "row_bytes": list(out.row_bytes[:n]), "rows": list(out.rows[:n]),
+            "offset": list(out.offset[:n]), "frame_bytes": out.frame_bytes}
+
+
+def rgb_coefficients(matrix, rng):
+    """wrenc_gpu_rgb_coefficients (host only): [yr, yg, yb, br, bg, bb, rr, rg, rb, yoff] of a matrix and a range (ids or names)."""
+    lib = load_library()
+    out = (C.c_int * 10)()
+    rc = lib.wrenc_gpu_rgb_coefficients(_rgb_matrix_id(matrix), _rgb_range_id(rng), out)
+    if rc:
+        raise WrencGpuError(rc, "rgb_coefficients(%r, %r)" % (matrix, rng))
+    return list(out)
+
+
+def _rgb_planes(planes):
+    """One array or a sequence of arrays -> a tuple of 2-D uint8 arrays whose last axis is contiguous."""
+    if isinstance(planes, np.ndarray):
+        planes = (planes,)
+    planes = tuple(np.asarray(a) for a in planes)
+    assert len(planes) in (1, 3) and all(a.ndim == 2 and a.dtype == np.uint8 and a.strides[1] == 1 for a in planes)
+    return planes
+
+
+def rgb_convert_host(layout, matrix, rng, w, h, planes):
+    """wrenc_gpu_rgb_convert_host (host only): the rules of include/wrenc_rgb.h over a whole w x h picture.  planes: one
+    rows x 3w or rows x 4w uint8 array for a packed layout, three arrays G, B, R for gbrp, possibly views into wider arrays.
+    Returns (y, cb, cr)."""
+    lib = load_library()
+    planes = _rgb_planes(planes)
+    ptr = (C.c_void_p * 3)(*[a.ctypes.data for a in planes])
+    stride = (C.c_size_t * 3)(*[a.strides[0] for a in planes])
+    w, h = int(w), int(h)
+    y = np.zeros((max(h, 0), max(w, 0)), np.uint8)
+    cb = np.zeros((max(h, 0) // 2, max(w, 0) // 2), np.uint8)
+    cr = np.zeros_like(cb)
+    lay = FormatLayout()
+    if lib.wrenc_gpu_rgb_layout(_rgb_id(layout), w, h, C.byref(lay)) == 0:   # what the C side will read must be there
+        if len(planes) != lay.n_planes or any(a.shape != (h, lay.row_bytes[p]) for p, a in enumerate(planes)):
+            raise WrencGpuError(-1, "rgb_convert_host: planes of %s" % ([a.shape for a in planes],))
+    rc = lib.wrenc_gpu_rgb_convert_host(_rgb_id(layout), _rgb_matrix_id(matrix), _rgb_range_id(rng), w, h, ptr, stride, _p(y), _p(cb), _p(cr))
+    if rc:
+        raise WrencGpuError(rc, "rgb_convert_host(%r, %r, %r, %d, %d)" % (layout, matrix, rng, w, h))
+    return y, cb, cr
+
+
 class WrencGpuError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("wrenc_gpu error %d: %s" % (code, msg))
@@ -371,14 +474,17 @@ class Encoder:
     SliceEncoder::encode uses in place of the per-CTU split_ct loop."""
 
     def __init__(self, width, height, qp=26, max_split_depth=3, device=0, n_slots=1, config=None, extra_params=None,
-                 schedule=None, visible=None, source=None, source_format=None):
+                 schedule=None, visible=None, source=None, source_format=None,
+                 source_rgb=None):
         """width x height: the coded size, whole 32x32 CTUs.  visible=(w, h): the pictures are that size (even, at least
         16x16, the coded size its round-up to multiples of 32): upload takes planes of it, the device replicates their last
         column and row into the margin, and download_metrics reports that rectangle (wrenc_gpu_set_visible_size).
         source=(w, h): the pictures are THAT size and the device resamples them to the visible size (the coded size when
         none is given) in front of everything else (wrenc_gpu_set_source_size).
         source_format: an id or a name of include/wrenc_format.h; the pictures come in that format through upload_planes and
-        the device converts them to 8-bit 4:2:0 first of all (wrenc_gpu_set_source_format)."""
+        the device converts them to 8-bit 4:2:0 first of all (wrenc_gpu_set_source_format).
+        source_rgb=(layout, matrix, range), ids or names of include/wrenc_rgb.h: the pictures are RGB, come through upload_rgb
+        and are converted to Y'CbCr on the device (wrenc_gpu_set_source_rgb); exclusive with a non-zero source_format."""
         self.lib = load_library()
         self.cfg = config if config is not None else default_config(width, height, qp, max_split_depth,
                                                                      device, n_slots, extra_params)
@@ -410,6 +516,12 @@ class Encoder:
         if source_format is not None:
             try:
                 self.set_source_format(source_format)
+            except WrencGpuError:
+                self.close()
+                raise
+        if source_rgb is not None:
+            try:
+                self.set_source_rgb(*((source_rgb,) if isinstance(source_rgb, (str, int)) else source_rgb))
             except WrencGpuError:
                 self.close()
                 raise
@@ -468,6 +580,42 @@ class Encoder:
         ptr = (C.c_void_p * 3)(*[a.ctypes.data for a in planes])
         stride = (C.c_size_t * 3)(*[a.strides[0] for a in planes])
         self._check(self.lib.wrenc_gpu_upload_planes(self.ctx, slot, ptr, stride))
+
+    def set_source_rgb(self, layout, matrix="bt709", rng="tv"):
+        """wrenc_gpu_set_source_rgb (ids or names of include/wrenc_rgb.h): before the first upload; the pictures come as RGB
+        through upload_rgb (or upload_device) and the device converts them to 8-bit 4:2:0 first of all.  layout None or -1
+        puts the context back."""
+        if layout is None or (not isinstance(layout, str) and int(layout) == -1):
+            self._check(self.lib.wrenc_gpu_set_source_rgb(self.ctx, -1, 0, 0))
+        else:
+            self._check(self.lib.wrenc_gpu_set_source_rgb(self.ctx, _rgb_id(layout), _rgb_matrix_id(matrix), _rgb_range_id(rng)))
+
+    def source_rgb(self):
+        """wrenc_gpu_source_rgb: (layout, matrix, range) as ids; layout -1 when no RGB source is set."""
+        out = [C.c_int(), C.c_int(), C.c_int()]
+        self._check(self.lib.wrenc_gpu_source_rgb(self.ctx, *[C.byref(v) for v in out]))
+        return tuple(v.value for v in out)
+
+    def upload_rgb(self, slot, planes):
+        """wrenc_gpu_upload_planes on a context with an RGB source: one rows x 3w (rgb24, bgr24) or rows x 4w (rgb0, bgr0)
+        uint8 array, or three arrays G, B, R (gbrp), at the source size; views into wider arrays (last axis contiguous) give
+        their own row strides to the C ABI."""
+        planes = _rgb_planes(planes)
+        self._keep[slot] = planes  # host buffers must outlive the async copy
+        ptr = (C.c_void_p * 3)(*[a.ctypes.data for a in planes])
+        stride = (C.c_size_t * 3)(*[a.strides[0] for a in planes])
+        self._check(self.lib.wrenc_gpu_upload_planes(self.ctx, slot, ptr, stride))
+
+    def upload_device(self, slot, pointers, strides, stream=0):
+        """wrenc_gpu_upload_planes_device: the planes of the context's source kind as DEVICE addresses (plain integers, one to
+        three) with their row strides in bytes; stream: the hipStream_t (an integer; 0 the null stream) that wrote them and
+        may overwrite them right behind this call.  No host wait; the planes are copied."""
+        pointers = [int(p) if p else None for p in pointers]
+        strides = [int(s) for s in strides]
+        assert 1 <= len(pointers) <= 3 and len(strides) == len(pointers)
+        ptr = (C.c_void_p * 3)(*pointers)
+        stride = (C.c_size_t * 3)(*strides)
+        self._check(self.lib.wrenc_gpu_upload_planes_device(self.ctx, slot, ptr, stride, C.c_void_p(int(stream) if stream else None)))
 
     def set_visible_size(self, vis_w, vis_h):
         """wrenc_gpu_set_visible_size: before the first upload; the coded size itself restores the plain behaviour."""
