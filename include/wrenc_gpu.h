@@ -343,6 +343,10 @@ int wrenc_gpu_download_tokens(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_g
 /* Test entry: put an arbitrary record (maps + level planes, as wrenc_gpu_download fills them) into a slot as if a search
  * had produced it, so that the token pass can be compared with the host-only writer on records no search emits. */
 int wrenc_gpu_test_load_record(wrenc_gpu_ctx* ctx, int slot, const wrenc_gpu_picture* rec);
+/* Test entry: put coded-size planes (width*height, then (width/2)*(height/2) twice) into a slot's reconstruction and mark the
+ * slot encoded, so that wrenc_gpu_download_recon can be held against wrenc_recon.h on content no search emits, with a
+ * margin unlike the visible edge.  Blocking. */
+int wrenc_gpu_test_load_recon(wrenc_gpu_ctx* ctx, int slot, const uint8_t* y, const uint8_t* cb, const uint8_t* cr);
 
 /* Metrics read-back: PSNR and SSIM of what a slot was given against what the search made of it, without the planes
  * crossing the bus.  A device pass behind the search reads the slot's originals (the upload's target) and its
@@ -425,6 +429,49 @@ int wrenc_gpu_download_hashes(wrenc_gpu_ctx* ctx, int first_slot, int n, int has
  * the pass's stream.  Taken only in measurement mode (wrenc_gpu_stats_enable); WRENC_GPU_ESTATE when the last call was
  * not timed. */
 int wrenc_gpu_last_hash_ms(wrenc_gpu_ctx* ctx, float* ms);
+
+/* Reconstruction out: the coded picture as the caller wants it, made on the device.  wrenc_recon.h defines the output as a
+ * function of the VISIBLE reconstruction alone -- what a decoder outputs behind the conformance window; the margin of a
+ * padded context is never read -- in seven formats of ONE id space (rgb24 = 0, bgr24, rgb0, bgr0, gbrp as in wrenc_rgb.h, then
+ * yuv420p = 5 and nv12 = 6), RGB by a matrix and a range with wrenc_rgb.h's ids from centre-sited bilinear chroma, in
+ * integers, each sample rounded once.  A kernel behind the slot's search (wrenc_amd/csrc/dev_recon.h) writes the picture,
+ * bit for bit what wrenc_gpu_recon_convert_host gives, into staging planes of the library's own (one set per context with
+ * the library's alignment, allocated at the first call: WRENC_GPU_ENOMEM from that call when it fails); a 2-D copy with the
+ * caller's strides then fills the caller's planes, and nothing outside the rows' bytes is written there.
+ * Both entries: plane[p] and stride_bytes[p] as wrenc_gpu_recon_layout numbers the planes at the context's visible size
+ * (the coded size when none is set); matrix and range are not read for the YUV outputs.  They run on a stream of their own
+ * (made at the first call) behind the encode call that searched the slot and nothing queued later, as
+ * wrenc_gpu_download_hashes does, and delay neither the search of other slots nor uploads.  WRENC_GPU_ESTATE unless the
+ * slot is in the encoded state (an upload into the slot puts it back to "uploaded", as for the metrics);
+ * WRENC_GPU_EINVAL for a bad slot, a null format, an unknown id, a null plane that is written or a stride below the row.
+ * They change nothing in the slot; the same planes give the same bytes in any slot, batch and run.  A context that never
+ * calls them launches and allocates nothing it did not before.
+ * wrenc_gpu_download_recon: to host memory, blocking.  Only the visible picture in the output format crosses the bus,
+ * once.  Any host memory works; the page-locked memory of wrenc_gpu_alloc_host runs at bus rate.
+ * wrenc_gpu_download_recon_device: to DEVICE memory of the context's device (hipPointerGetAttributes: WRENC_GPU_EINVAL for
+ * a host pointer, pinned or not, and for memory of another device), with no host wait -- the mirror of
+ * wrenc_gpu_upload_planes_device.  consumer_stream is a hipStream_t; NULL is the null stream, handled like any other.  The
+ * call records an event on the consumer stream and the copies into the caller's planes wait for it, so earlier work on that
+ * stream that reads or writes the destination finishes first; behind the copies it records an event that the consumer
+ * stream waits for, so what the caller queues there next sees the picture.  Work on OTHER streams is the caller's to
+ * order.  The staging planes are reused by the next call on the context, behind this one's copies; an encode call queued
+ * later waits for this call's kernel before it rewrites the slot. */
+typedef struct wrenc_gpu_recon_format { int32_t format, matrix, range; } wrenc_gpu_recon_format;
+int wrenc_gpu_download_recon(wrenc_gpu_ctx* ctx, int slot, const wrenc_gpu_recon_format* format, void* const plane[3], const size_t stride_bytes[3]);
+int wrenc_gpu_download_recon_device(wrenc_gpu_ctx* ctx, int slot, const wrenc_gpu_recon_format* format, void* const plane[3],
+                                    const size_t stride_bytes[3], void* consumer_stream);
+/* Host only, callable without a device.  The id of an output format's name ("rgba" and "bgra" are aliases of rgb0 and bgr0)
+ * or WRENC_GPU_EINVAL; the name of an id or NULL; the layout of a tightly packed w x h frame (the limits of
+ * wrenc_gpu_format_layout); the coefficients in the order cy rv gu gv bu, then yoff; and the rules of wrenc_recon.h over a
+ * whole picture -- y of w x h and cb, cr of w/2 x h/2 bytes tightly packed, to planes and strides as wrenc_gpu_recon_layout
+ * numbers them -- which is what the device can be held against.  WRENC_GPU_EINVAL for an unknown id, a size outside the
+ * limits, a null pointer that is used or a stride smaller than the row. */
+int wrenc_gpu_recon_from_name(const char* name);
+const char* wrenc_gpu_recon_name(int format);
+int wrenc_gpu_recon_layout(int format, int w, int h, struct wrenc_gpu_format_layout* out);
+int wrenc_gpu_recon_coefficients(int matrix, int range, int out[6]);
+int wrenc_gpu_recon_convert_host(int format, int matrix, int range, int w, int h, const uint8_t* y, const uint8_t* cb, const uint8_t* cr,
+                                 void* const plane[3], const size_t stride_bytes[3]);
 
 /* Page-locked host memory for the planes handed to wrenc_gpu_upload / wrenc_gpu_download: transfers from
  * and to it run at PCIe rate and truly asynchronously (pageable buffers are staged by the runtime at a

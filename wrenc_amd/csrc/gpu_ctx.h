@@ -8,6 +8,7 @@
 #include "../../include/wrenc_scale.h"
 #include "../../include/wrenc_format.h"
 #include "../../include/wrenc_rgb.h"
+#include "../../include/wrenc_recon.h"
 #include "../../include/wrenc_hash.h"
 #include "../../include/wrenc_ratecurve.h"
 
@@ -148,6 +149,16 @@ struct wrenc_gpu_ctx {
     DevBuf<wrenc_picture_hash> d_hvalues;
     HipEvent hash_ev[2];                        // measurement mode (stats_enabled): around the last hash pass
     bool hash_timed = false;
+    // reconstruction out (wrenc_gpu_download_recon, _download_recon_device; all made on first use): a stream of its own, as
+    // the hashes have and for the same reason; the staging planes the kernels of dev_recon.h write, one set per context
+    // with room for the largest output format, reused by the next call behind this one's copies (one stream, in order);
+    // the device entry's events: "the consumer stream has reached the call" for the copies to wait for, "the copies are
+    // done" for the consumer stream to wait for, and "the kernel has read the slot's reconstruction", which the next
+    // encode call waits for while recon_read_pending (the host entry returns behind its kernel and leaves nothing pending)
+    HipStream recon_stream;
+    DevBuf<uint8_t> d_recon;
+    HipEvent ev_consumer, ev_recon_copied, ev_recon_read;
+    bool recon_read_pending = false;
     // complexity read-back: the waves' triples, the pictures' totals and CTU maps of one call, for every slot at once
     // (allocated on first use and never again: a later call must not free device memory under a search in flight)
     DevBuf<ComplexityPartial> d_xpartial, d_xsums;

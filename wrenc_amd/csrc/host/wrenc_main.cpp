@@ -49,6 +49,13 @@
 // (wrenc_gpu_set_source_rgb); the two options are argument errors with a YUV input.  The stream carries no VUI: what was
 // chosen is not signalled in it.
 //
+// --reconst-format yuv420p|nv12|rgb24|bgr24|rgb0|bgr0|rgba|bgra|gbrp (with --reconst): the frames of --reconst in that format
+// at --output-size, made on the device behind the search (wrenc_gpu_download_recon; include/wrenc_recon.h): the crop, the
+// interleave or the conversion to RGB by --reconst-colorspace bt709|bt601 and --reconst-range tv|pc, which default to
+// --colorspace and --range of an RGB input and to bt709 tv otherwise and are argument errors with a YUV reconst format.
+// The batch's read-back then leaves the coded planes on the device.  Without the option the planes are read back and
+// cropped here as before; --reconst-format yuv420p writes the same file; the stream never depends on these options.
+//
 // --hash md5|crc|checksum: every picture's slice is followed by a decoded picture hash SEI (H.274; include/wrenc_hash.h), so
 // that any conforming decoder checks what it decodes against what this encoder reconstructed.  The device takes the hash
 // of the reconstruction it holds (wrenc_gpu_download_hashes: the coded planes, --pad's margin included, as a decoder
@@ -86,6 +93,7 @@
 #include "../../../include/wrenc_bitstream_window.h"
 #include "../../../include/wrenc_gpu.h"
 #include "../../../include/wrenc_rate.h"
+#include "../../../include/wrenc_recon.h"
 
 namespace {
 
@@ -186,6 +194,8 @@ struct Options {
     int format = 0;            // --input-format: their pixel format (wrenc_format.h), yuv420p unless given
     int rgb = -1;              // ... or their RGB layout (wrenc_rgb.h), -1: none; then --colorspace and --range say how the
     int rgb_matrix = 0, rgb_range = 0; // device makes Y'CbCr of them: bt709 | bt601, tv | pc
+    int rec_format = -1;       // --reconst-format: the output format of --reconst's frames (wrenc_recon.h), made on the device by
+    int rec_matrix = 0, rec_range = 0; // wrenc_gpu_download_recon; -1: none given, the planes are read back and cropped here
     int hash = -1;             // --hash: the type of the decoded picture hash SEI behind every slice (wrenc_hash.h), -1: none
     int depth = 3, batch = 64, n_threads = 8;
     bool verbose = false;
@@ -226,7 +236,7 @@ std::vector<int> read_qp_file(const char* path, long num_pictures) {
 Options parse_options(int argc, char** argv) {
     Options o;
     const char *in_size = nullptr, *out_size = nullptr, *device_list = nullptr, *qp_file = nullptr, *bitrate = nullptr, *fps = nullptr, *vbv = nullptr,
-               *colorspace = nullptr, *range = nullptr;
+               *colorspace = nullptr, *range = nullptr, *rec_colorspace = nullptr, *rec_range = nullptr;
     int device = 0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -276,6 +286,21 @@ Options parse_options(int argc, char** argv) {
             o.rgb_range = !strcmp(range, "tv") ? 0 : (!strcmp(range, "pc") ? 1 : -1);
             if (o.rgb_range < 0) die("Invalid range: %s (tv, pc)", range);
         }
+        else if (a == "--reconst-format") {
+            const char* v = val();
+            o.rec_format = wrenc_gpu_recon_from_name(v);
+            if (o.rec_format < 0) die("Invalid reconst-format: %s (yuv420p, nv12; rgb24, bgr24, rgb0, bgr0, rgba, bgra, gbrp)", v);
+        }
+        else if (a == "--reconst-colorspace") {
+            rec_colorspace = val();
+            o.rec_matrix = !strcmp(rec_colorspace, "bt709") ? 0 : (!strcmp(rec_colorspace, "bt601") ? 1 : -1);
+            if (o.rec_matrix < 0) die("Invalid reconst-colorspace: %s (bt709, bt601)", rec_colorspace);
+        }
+        else if (a == "--reconst-range") {
+            rec_range = val();
+            o.rec_range = !strcmp(rec_range, "tv") ? 0 : (!strcmp(rec_range, "pc") ? 1 : -1);
+            if (o.rec_range < 0) die("Invalid reconst-range: %s (tv, pc)", rec_range);
+        }
         else if (a == "--hash") {
             const std::string v = val();
             o.hash = v == "md5" ? WRENC_HASH_MD5 : (v == "crc" ? WRENC_HASH_CRC : (v == "checksum" ? WRENC_HASH_CHECKSUM : -1));
@@ -298,6 +323,13 @@ Options parse_options(int argc, char** argv) {
         die("the following options are required: --input --output --input-size --output-size --num-pictures");
     if ((colorspace || range) && o.rgb < 0)
         die("%s needs an RGB --input-format (rgb24, bgr24, rgb0, bgr0, rgba, bgra, gbrp): a YUV input is not converted", colorspace ? "--colorspace" : "--range");
+    if (o.rec_format >= 0 && !o.reconst) die("--reconst-format needs --reconst: it is the format of that file's frames");
+    if ((rec_colorspace || rec_range) && !wrenc_recon_is_rgb(o.rec_format))
+        die("%s needs an RGB --reconst-format (rgb24, bgr24, rgb0, bgr0, rgba, bgra, gbrp): a YUV reconstruction is not converted",
+            rec_colorspace ? "--reconst-colorspace" : "--reconst-range");
+    // the way back is the way in unless said otherwise: an RGB input's matrix and range, else bt709 tv
+    if (!rec_colorspace) o.rec_matrix = o.rgb >= 0 ? o.rgb_matrix : 0;
+    if (!rec_range) o.rec_range = o.rgb >= 0 ? o.rgb_range : 0;
     int iw = 0, ih = 0;
     if (!parse_size(in_size, iw, ih)) die("Invalid input-size: %s", in_size); // used with --scale only (below); otherwise parsed and unused, as in main.rs:164-174
     if (!parse_size(out_size, o.w, o.h)) die("Invalid output-size: %s", out_size);
@@ -381,14 +413,20 @@ struct Geometry {
     size_t ysz, csz, pic;   // bytes of luma, of one chroma plane, of the picture
     struct wrenc_gpu_format_layout in; // the planes of a frame of the input as it lies in the file (wrenc_gpu_format_layout)
     size_t ipic;            // ... and its bytes
+    struct wrenc_gpu_format_layout rec; // --reconst-format: the planes of a frame of --reconst (wrenc_gpu_recon_layout) ...
+    size_t rpic;            // ... and its bytes; without the option the coded planes as they are read back: pic
     size_t n4, maps;        // 4x4 luma blocks; bytes of cu_log2_size | luma_mode | chroma_mode
     size_t mask_words, level_blocks, n_ctus;
-    Geometry(int w_, int h_, int vw_, int vh_, int iw_, int ih_, int format, int rgb)
+    Geometry(int w_, int h_, int vw_, int vh_, int iw_, int ih_, int format, int rgb, int rec_format)
         : w(w_), h(h_), vw(vw_), vh(vh_), iw(iw_), ih(ih_), ysz((size_t)w_ * h_), csz(ysz / 4), pic(ysz + 2 * csz), in(), ipic(0),
-          n4(ysz / 16), maps(2 * n4 + ysz / 64), mask_words(wrenc_gpu_compact_mask_words(w_, h_)), level_blocks(pic / 16),
+          rec(), rpic(pic), n4(ysz / 16), maps(2 * n4 + ysz / 64), mask_words(wrenc_gpu_compact_mask_words(w_, h_)), level_blocks(pic / 16),
           n_ctus((size_t)(w_ / 32) * (h_ / 32)) {
         if (rgb >= 0 ? wrenc_gpu_rgb_layout(rgb, iw_, ih_, &in) : wrenc_gpu_format_layout(format, iw_, ih_, &in)) die("input frames must be of an even size, at least 16x16: %dx%d", iw_, ih_);
         ipic = in.frame_bytes;
+        if (rec_format >= 0) {
+            if (wrenc_gpu_recon_layout(rec_format, vw_, vh_, &rec)) die("--reconst-format needs frames of an even size, at least 16x16: %dx%d", vw_, vh_);
+            rpic = rec.frame_bytes;
+        }
     }
 };
 
@@ -455,7 +493,7 @@ std::vector<HostSet> make_units(const Options& o, const Geometry& g, const std::
         s.base = (int)(u / n_dev) * o.batch;
         s.in = (uint8_t*)wrenc_gpu_alloc_host(s.ctx, g.ipic * batch);
         s.maps = (uint8_t*)wrenc_gpu_alloc_host(s.ctx, g.maps * batch);
-        if (with_rec) s.rec = (uint8_t*)wrenc_gpu_alloc_host(s.ctx, g.pic * batch);
+        if (with_rec) s.rec = (uint8_t*)wrenc_gpu_alloc_host(s.ctx, g.rpic * batch);
         if (!s.in || !s.maps || (with_rec && !s.rec)) fatal("%s", wrenc_gpu_last_error(s.ctx));
         if (o.tokens) {
             s.tok_cap = token_pool_words(g, o.min_qp, o.batch);
@@ -651,10 +689,20 @@ struct Run {
         }
         // --hash: of the reconstruction where it lies, 48 bytes a picture (the unit's slices of the batch before are out)
         if (o.hash >= 0) gpu_check(s, wrenc_gpu_download_hashes(s.ctx, s.base + k0, n, o.hash, s.hashes.data() + k0));
+        // --reconst-format: the frames of --reconst as the device makes them, cropped and converted (include/wrenc_recon.h); the
+        // coded planes then stay where they are
+        if (frec && o.rec_format >= 0) {
+            const wrenc_gpu_recon_format f = {o.rec_format, o.rec_matrix, o.rec_range};
+            for (int k = k0; k < k0 + n; ++k) {
+                uint8_t* frame = s.rec + g.rpic * k;
+                void* const plane[3] = {frame + g.rec.offset[0], frame + g.rec.offset[1], frame + g.rec.offset[2]};
+                gpu_check(s, wrenc_gpu_download_recon(s.ctx, s.base + k, &f, plane, g.rec.row_bytes));
+            }
+        }
         if (s.tok_pool) {
             for (int k = k0; k < k0 + n; ++k) {
                 uint8_t* m = s.maps + g.maps * k;
-                uint8_t* r = frec ? s.rec + g.pic * k : nullptr;
+                uint8_t* r = frec && o.rec_format < 0 ? s.rec + g.pic * k : nullptr;
                 s.tks[(size_t)k] = wrenc_gpu_tokens{s.tok_first + g.n_ctus * k, m, m + g.n4, m + 2 * g.n4, r, r ? r + g.ysz : nullptr, r ? r + g.ysz + g.csz : nullptr};
             }
             const int rc = wrenc_gpu_download_tokens(s.ctx, s.base + k0, n, s.tks.data() + k0, s.tok_pool, s.tok_cap, &s.tok_used);
@@ -666,7 +714,7 @@ struct Run {
         }
         for (int k = k0; k < k0 + n; ++k) {
             uint8_t* m = s.maps + g.maps * k;
-            uint8_t* r = frec ? s.rec + g.pic * k : nullptr;
+            uint8_t* r = frec && o.rec_format < 0 ? s.rec + g.pic * k : nullptr;
             s.cps[(size_t)k] = wrenc_gpu_compact{s.mask + g.mask_words * k, s.lev + g.pic * k, g.level_blocks, 0, m, m + g.n4, m + 2 * g.n4,
                                                  r, r ? r + g.ysz : nullptr, r ? r + g.ysz + g.csz : nullptr};
         }
@@ -781,7 +829,8 @@ struct Run {
             fwrite(s.nal[(size_t)k].data(), 1, s.len[(size_t)k], fout);
             bytes += s.len[(size_t)k];
             if (o.metrics) pic_bytes.push_back(s.len[(size_t)k]);
-            if (frec) write_reconst(s.rec + g.pic * k); // main.rs:387-399
+            if (frec && o.rec_format >= 0) fwrite(s.rec + g.rpic * k, 1, g.rpic, frec);
+            else if (frec) write_reconst(s.rec + g.pic * k); // main.rs:387-399
         }
         if (o.vbv_bits > 0) { // (reported picture by picture, above)
             if (o.verbose && s.bs_count > 0)
@@ -892,7 +941,7 @@ int main(int argc, char** argv) {
         if (o.rgb >= 0 && wrenc_gpu_set_source_rgb(ctx, o.rgb, o.rgb_matrix, o.rgb_range)) fatal("%s", wrenc_gpu_last_error(ctx));
         ctxs.push_back(ctx);
     }
-    const Geometry g(o.w, o.h, o.vis_w, o.vis_h, o.in_w, o.in_h, o.format, o.rgb);
+    const Geometry g(o.w, o.h, o.vis_w, o.vis_h, o.in_w, o.in_h, o.format, o.rgb, o.rec_format);
     std::vector<HostSet> units = make_units(o, g, ctxs, per_dev, frec != nullptr);
     size_t hdr_bytes = 0, rate_hdr_bytes = 0;
     {

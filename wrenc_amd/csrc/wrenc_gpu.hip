@@ -245,6 +245,7 @@ void wrenc_gpu_destroy(wrenc_gpu_ctx* ctx) {
         if (st) (void)hipStreamSynchronize(st.get());
     if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream.get());
     if (ctx->hash_stream) (void)hipStreamSynchronize(ctx->hash_stream.get());
+    if (ctx->recon_stream) (void)hipStreamSynchronize(ctx->recon_stream.get());
     delete ctx; // (frees the device memory and destroys the streams and events: every stream has been synchronised above)
 }
 
@@ -470,6 +471,11 @@ int wrenc_gpu_encode(wrenc_gpu_ctx* ctx, int first_slot, int n_pictures) {
         HIP_TRY(ctx, hipEventRecord(ctx->ev_uploaded.get(), ctx->copy_stream.get()));
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream.get(), ctx->ev_uploaded.get(), 0));
         ctx->uploads_pending = false;
+    }
+    // a wrenc_gpu_download_recon_device queued without a host wait may still be reading a reconstruction this call rewrites
+    if (ctx->recon_read_pending) {
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream.get(), ctx->ev_recon_read.get(), 0));
+        ctx->recon_read_pending = false;
     }
     if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_begin.get(), ctx->stream.get()));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_fork.get(), ctx->stream.get()));

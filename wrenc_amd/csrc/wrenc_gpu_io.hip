@@ -1,6 +1,6 @@
 // wrenc_gpu_io.hip -- pictures in and results out: every upload path of the C ABI (include/wrenc_gpu.h: plain, strided,
 // visible size, scaler, source formats, RGB sources, device-resident planes) and every read-back (maps, compact, tokens,
-// metrics, complexity, rate histogram, hashes), with the kernels they launch.  A translation unit and a code object of its own in libwrenc_gpu.so (the command
+// metrics, complexity, rate histogram, hashes, the reconstruction in an output format), with the kernels they launch.  A translation unit and a code object of its own in libwrenc_gpu.so (the command
 // is at the top of wrenc_gpu.hip): what is added or changed here cannot move an instruction of the search kernels.
 //
 // The trace and profile builds (-DWRENC_TRACE, -DWRENC_PROFILE) define their device globals in dev_common.h; nothing here
@@ -24,6 +24,7 @@
 #include "dev_scale.h"
 #include "dev_format.h"
 #include "dev_rgb.h"
+#include "dev_recon.h"
 
 #include <cmath>
 #include <cstring>
@@ -249,6 +250,13 @@ template <int L>
 static void launch_rgb(const RgbArgs& a, hipStream_t cs) {
     const dim3 grid((unsigned)((a.w + 64 * kRgbGroup - 1) / (64 * kRgbGroup)), (unsigned)((a.h / 2 + kRgbRows - 1) / kRgbRows));
     hipLaunchKernelGGL(convert_rgb_kernel<L>, grid, dim3(64, kRgbRows), 0, cs, a);
+}
+
+// the RGB output of one picture's reconstruction (dev_recon.h), layout L
+template <int L>
+static void launch_recon_rgb(const ReconArgs& a, hipStream_t st) {
+    const dim3 grid((unsigned)((a.w + 64 * kReconGroup - 1) / (64 * kReconGroup)), (unsigned)((a.h / 2 + kReconRows - 1) / kReconRows));
+    hipLaunchKernelGGL(recon_rgb_kernel<L>, grid, dim3(64, kReconRows), 0, st, a);
 }
 
 extern "C" {
@@ -1032,6 +1040,174 @@ int wrenc_gpu_last_hash_ms(wrenc_gpu_ctx* ctx, float* ms) {
     if (!ctx->hash_timed) return fail(ctx, WRENC_GPU_ESTATE, "no timed hash pass: wrenc_gpu_stats_enable, then wrenc_gpu_download_hashes");
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
     HIP_TRY(ctx, hipEventElapsedTime(ms, ctx->hash_ev[0].get(), ctx->hash_ev[1].get()));
+    return WRENC_GPU_OK;
+}
+
+int wrenc_gpu_recon_from_name(const char* name) {
+    const int f = wrenc_recon_from_name(name);
+    return f < 0 ? WRENC_GPU_EINVAL : f;
+}
+
+const char* wrenc_gpu_recon_name(int format) { return wrenc_recon_name(format); }
+
+int wrenc_gpu_recon_layout(int format, int w, int h, struct wrenc_gpu_format_layout* out) {
+    return wrenc_recon_layout(format, w, h, out) ? WRENC_GPU_EINVAL : WRENC_GPU_OK;
+}
+
+int wrenc_gpu_recon_coefficients(int matrix, int range, int out[6]) { return wrenc_recon_coefficients(matrix, range, out) ? WRENC_GPU_EINVAL : WRENC_GPU_OK; }
+
+int wrenc_gpu_recon_convert_host(int format, int matrix, int range, int w, int h, const uint8_t* y, const uint8_t* cb, const uint8_t* cr,
+                                 void* const plane[3], const size_t stride_bytes[3]) {
+    if (!plane) return WRENC_GPU_EINVAL;
+    uint8_t* const to[3] = {(uint8_t*)plane[0], (uint8_t*)plane[1], (uint8_t*)plane[2]};
+    return wrenc_recon_convert(format, matrix, range, w, h, y, cb, cr, to, stride_bytes) ? WRENC_GPU_EINVAL : WRENC_GPU_OK;
+}
+
+namespace {
+
+// the recon staging planes of output format `format` at the context's visible size: the frame's layout, the planes'
+// pitches (dev_recon.h) and offsets, and the bytes they take
+struct ReconStage {
+    struct wrenc_gpu_format_layout lay;
+    size_t pitch[3], off[3], bytes;
+};
+
+bool recon_stage(const wrenc_gpu_ctx* ctx, int format, ReconStage& r) {
+    const int vw = ctx->vis_w, vh = ctx->vis_h;
+    if (wrenc_recon_layout(format, vw, vh, &r.lay)) return false;
+    r.bytes = 0;
+    for (int p = 0; p < 3; ++p) {
+        r.pitch[p] = r.off[p] = 0;
+        if (p >= r.lay.n_planes) continue;
+        r.pitch[p] = recon_stage_pitch(format, p, wrenc_recon_is_rgb(format) || !p ? vw : vw / 2);
+        r.off[p] = r.bytes;
+        r.bytes += r.pitch[p] * r.lay.rows[p];
+    }
+    return true;
+}
+
+// What the two recon entries share: the checks, the staging planes, the wait for the slot's search and the kernel, all on
+// the recon stream; `r` is then what the caller's planes are copied from.  device: each plane written must be memory of the
+// context's device.
+int recon_to_stage(wrenc_gpu_ctx* ctx, int slot, const wrenc_gpu_recon_format* fmt, void* const plane[3], const size_t stride_bytes[3], bool device,
+                   ReconStage& r) {
+    if (!fmt || !plane || !stride_bytes) return fail(ctx, WRENC_GPU_EINVAL, "null format, plane list or stride list");
+    if (const int rc = check_slots(ctx, slot, 1, 2, "bad slot")) return rc;
+    int k[6] = {0, 0, 0, 0, 0, 0};
+    if (!wrenc_recon_valid(fmt->format) || (wrenc_recon_is_rgb(fmt->format) && wrenc_recon_coefficients(fmt->matrix, fmt->range, k)))
+        return fail(ctx, WRENC_GPU_EINVAL, "unknown recon format, matrix or range");
+    if (!recon_stage(ctx, fmt->format, r)) return fail(ctx, WRENC_GPU_EINVAL, "the recon formats need pictures of an even size, at least 16x16");
+    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+    for (int p = 0; p < r.lay.n_planes; ++p) {
+        if (!plane[p]) return fail(ctx, WRENC_GPU_EINVAL, "null plane");
+        if (stride_bytes[p] < r.lay.row_bytes[p]) return fail(ctx, WRENC_GPU_EINVAL, "stride smaller than row");
+        if (!device) continue;
+        hipPointerAttribute_t at = {};
+        const hipError_t e = hipPointerGetAttributes(&at, plane[p]);
+        if (e != hipSuccess) (void)hipGetLastError(); // a pointer the runtime does not know: plain host memory
+        if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != ctx->cfg.device)
+            return fail(ctx, WRENC_GPU_EINVAL, "wrenc_gpu_download_recon_device: a plane is not memory of the context's device (host planes go through wrenc_gpu_download_recon)");
+    }
+    if (!ctx->recon_stream) HIP_TRY(ctx, ctx->recon_stream.create(hipStreamNonBlocking));
+    if (!ctx->ev_recon_read) HIP_TRY(ctx, ctx->ev_recon_read.create(hipEventDisableTiming));
+    if (!ctx->d_recon) { // once, with room for every output format: a later call frees nothing under work in flight
+        size_t most = 0;
+        for (int f = 0; f < WRENC_RECON_COUNT; ++f) {
+            ReconStage s;
+            if (recon_stage(ctx, f, s) && s.bytes > most) most = s.bytes;
+        }
+        const hipError_t e = ctx->d_recon.alloc(most);
+        if (e != hipSuccess)
+            return fail(ctx, e == hipErrorOutOfMemory ? WRENC_GPU_ENOMEM : WRENC_GPU_EHIP, std::string("recon staging planes: ") + hipGetErrorString(e));
+    }
+    // on the recon stream, behind the encode call that searched the slot and nothing later, and behind the copies of the
+    // call before (same stream); the search of other slots and the copy stream's uploads go on meanwhile
+    hipStream_t rs = ctx->recon_stream.get();
+    if (const int rc = wait_for_search(ctx, slot, 1, rs)) return rc;
+    const wrenc_gpu_config& c = ctx->cfg;
+    const PicBufs& b = ctx->slots[slot];
+    ReconArgs a = {};
+    for (int p = 0; p < 3; ++p) {
+        a.rec[p] = b.rec[p];
+        a.dst_off[p] = r.off[p];
+        a.dst_pitch[p] = (int)r.pitch[p];
+    }
+    a.dst = ctx->d_recon.get();
+    a.W = c.width;
+    a.w = ctx->vis_w;
+    a.h = ctx->vis_h;
+    if (wrenc_recon_is_rgb(fmt->format)) {
+        a.cy16 = 16 * k[0];
+        a.yk = (1 << 17) - 16 * k[0] * k[5];
+        a.rv = k[1], a.gu = k[2], a.gv = k[3], a.bu = k[4];
+        switch (fmt->format) {
+        case WRENC_RGB_RGB24: launch_recon_rgb<WRENC_RGB_RGB24>(a, rs); break;
+        case WRENC_RGB_BGR24: launch_recon_rgb<WRENC_RGB_BGR24>(a, rs); break;
+        case WRENC_RGB_RGB0: launch_recon_rgb<WRENC_RGB_RGB0>(a, rs); break;
+        case WRENC_RGB_BGR0: launch_recon_rgb<WRENC_RGB_BGR0>(a, rs); break;
+        default: launch_recon_rgb<WRENC_RGB_GBRP>(a, rs); break;
+        }
+    } else {
+        const bool pairs = fmt->format == WRENC_RECON_NV12;
+        a.row_blocks[0] = (a.h + kReconRows - 1) / kReconRows;
+        a.row_blocks[1] = (a.h / 2 + kReconRows - 1) / kReconRows;
+        const dim3 grid((unsigned)((a.w + 64 * kReconGroup - 1) / (64 * kReconGroup)), (unsigned)(a.row_blocks[0] + (pairs ? 1 : 2) * a.row_blocks[1]));
+        if (pairs)
+            hipLaunchKernelGGL(recon_yuv_kernel<true>, grid, dim3(64, kReconRows), 0, rs, a);
+        else
+            hipLaunchKernelGGL(recon_yuv_kernel<false>, grid, dim3(64, kReconRows), 0, rs, a);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return WRENC_GPU_OK;
+}
+
+} // namespace
+
+int wrenc_gpu_download_recon(wrenc_gpu_ctx* ctx, int slot, const wrenc_gpu_recon_format* format, void* const plane[3], const size_t stride_bytes[3]) {
+    if (!ctx) return WRENC_GPU_EINVAL;
+    ReconStage r;
+    if (const int rc = recon_to_stage(ctx, slot, format, plane, stride_bytes, false, r)) return rc;
+    hipStream_t rs = ctx->recon_stream.get();
+    // the visible picture in the output format, once over the bus
+    for (int p = 0; p < r.lay.n_planes; ++p)
+        HIP_TRY(ctx, hipMemcpy2DAsync(plane[p], stride_bytes[p], ctx->d_recon.get() + r.off[p], r.pitch[p], r.lay.row_bytes[p], r.lay.rows[p],
+                                      hipMemcpyDeviceToHost, rs));
+    return read_overflow(ctx, rs); // (synchronises the stream)
+}
+
+int wrenc_gpu_download_recon_device(wrenc_gpu_ctx* ctx, int slot, const wrenc_gpu_recon_format* format, void* const plane[3],
+                                    const size_t stride_bytes[3], void* consumer_stream) {
+    if (!ctx) return WRENC_GPU_EINVAL;
+    ReconStage r;
+    if (const int rc = recon_to_stage(ctx, slot, format, plane, stride_bytes, true, r)) return rc;
+    hipStream_t rs = ctx->recon_stream.get(), consumer = (hipStream_t)consumer_stream;
+    if (!ctx->ev_consumer) HIP_TRY(ctx, ctx->ev_consumer.create(hipEventDisableTiming));
+    if (!ctx->ev_recon_copied) HIP_TRY(ctx, ctx->ev_recon_copied.create(hipEventDisableTiming));
+    // no host wait: an encode call queued later must not rewrite the slot's planes under the kernel
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_recon_read.get(), rs));
+    ctx->recon_read_pending = true;
+    // the copies into the caller's planes go on only behind what the consumer stream has queued so far (the kernel does
+    // not wait: it writes the library's staging planes) ...
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_consumer.get(), consumer));
+    HIP_TRY(ctx, hipStreamWaitEvent(rs, ctx->ev_consumer.get(), 0));
+    for (int p = 0; p < r.lay.n_planes; ++p)
+        HIP_TRY(ctx, hipMemcpy2DAsync(plane[p], stride_bytes[p], ctx->d_recon.get() + r.off[p], r.pitch[p], r.lay.row_bytes[p], r.lay.rows[p],
+                                      hipMemcpyDeviceToDevice, rs));
+    // ... and what the consumer stream queues from now on runs behind them
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_recon_copied.get(), rs));
+    HIP_TRY(ctx, hipStreamWaitEvent(consumer, ctx->ev_recon_copied.get(), 0));
+    return WRENC_GPU_OK;
+}
+
+int wrenc_gpu_test_load_recon(wrenc_gpu_ctx* ctx, int slot, const uint8_t* y, const uint8_t* cb, const uint8_t* cr) {
+    if (!ctx) return WRENC_GPU_EINVAL;
+    if (slot < 0 || slot >= ctx->cfg.n_slots || !y || !cb || !cr) return fail(ctx, WRENC_GPU_EINVAL, "bad slot or null plane");
+    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    const PicBufs& b = ctx->slots[slot];
+    const uint8_t* from[3] = {y, cb, cr};
+    for (int p = 0; p < 3; ++p) HIP_TRY(ctx, hipMemcpy(b.rec[p], from[p], plane_bytes(ctx->cfg, p, 1), hipMemcpyHostToDevice));
+    ctx->state[slot] = 2;
     return WRENC_GPU_OK;
 }
 

@@ -63,6 +63,13 @@ PROTOTYPES = {
     "wrenc_gpu_metrics_values": (None, [_I, _I, _P, _P, _P]),
     "wrenc_gpu_download_hashes": (_I, [_P, _I, _I, _I, _P]),
     "wrenc_gpu_last_hash_ms": (_I, [_P, _P]),
+    "wrenc_gpu_download_recon": (_I, [_P, _I, _P, _P, _P]),
+    "wrenc_gpu_download_recon_device": (_I, [_P, _I, _P, _P, _P, _P]),
+    "wrenc_gpu_recon_from_name": (_I, [_S]),
+    "wrenc_gpu_recon_name": (_S, [_I]),
+    "wrenc_gpu_recon_layout": (_I, [_I, _I, _I, _P]),
+    "wrenc_gpu_recon_coefficients": (_I, [_I, _I, _P]),
+    "wrenc_gpu_recon_convert_host": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "wrenc_gpu_alloc_host": (_P, [_P, _Z]),
     "wrenc_gpu_free_host": (None, [_P, _P]),
     "wrenc_gpu_encode_picture": (_I, [_P, _P, _P, _P, _P]),
@@ -76,6 +83,7 @@ PROTOTYPES = {
     # test hooks on a context's state, and the planner
     "wrenc_gpu_test_download_originals": (_I, [_P, _I, _P, _P, _P]),
     "wrenc_gpu_test_load_record": (_I, [_P, _I, _P]),
+    "wrenc_gpu_test_load_recon": (_I, [_P, _I, _P, _P, _P]),
     "wrenc_gpu_test_set_wave_slots": (_I, [_P, _LL]),
     "wrenc_gpu_test_scratch_overflows": (_I, [_P, _P]),
     "wrenc_gpu_test_plan": (_I, [_I, _I, _P, _I, _I, _LL, _I, _P, _P, _I, _P, _I, _P, _I]),
@@ -393,6 +401,87 @@ def rgb_convert_host(layout, matrix, rng, w, h, planes):
     if rc:
         raise WrencGpuError(rc, "rgb_convert_host(%r, %r, %r, %d, %d)" % (layout, matrix, rng, w, h))
     return y, cb, cr
+
+
+class ReconFormat(C.Structure):
+    _fields_ = [("format", C.c_int32), ("matrix", C.c_int32), ("range", C.c_int32)]
+
+
+def recon_from_name(name):
+    """wrenc_gpu_recon_from_name (host only): the id of an output format of the reconstruction (include/wrenc_recon.h: the
+    RGB layouts of wrenc_rgb.h with their ids and aliases, then yuv420p and nv12); WrencGpuError for an unknown name."""
+    lib = load_library()
+    rc = lib.wrenc_gpu_recon_from_name(name.encode() if name is not None else None)
+    if rc < 0:
+        raise WrencGpuError(rc, "recon_from_name(%r)" % (name,))
+    return rc
+
+
+def recon_name(fmt):
+    """wrenc_gpu_recon_name (host only): the name of an output format id, None for an unknown one."""
+    lib = load_library()
+    name = lib.wrenc_gpu_recon_name(int(fmt))
+    return name.decode() if name is not None else None
+
+
+def _recon_id(fmt):
+    return recon_from_name(fmt) if isinstance(fmt, str) else int(fmt)
+
+
+def recon_layout(fmt, w, h):
+    """wrenc_gpu_recon_layout (host only): a tightly packed w x h frame of output format `fmt` (an id or a name), the dict of
+    format_layout."""
+    lib = load_library()
+    out = FormatLayout()
+    rc = lib.wrenc_gpu_recon_layout(_recon_id(fmt), int(w), int(h), C.byref(out))
+    if rc:
+        raise WrencGpuError(rc, "recon_layout(%r, %d, %d)" % (fmt, w, h))
+    n = out.n_planes
+    return {"n_planes": n, "bytes_per_sample": out.bytes_per_sample, "row_bytes": list(out.row_bytes[:n]), "rows": list(out.rows[:n]),
+            "offset": list(out.offset[:n]), "frame_bytes": out.frame_bytes}
+
+
+def recon_coefficients(matrix, rng):
+    """wrenc_gpu_recon_coefficients (host only): [cy, rv, gu, gv, bu, yoff] of a matrix and a range (ids or names)."""
+    lib = load_library()
+    out = (C.c_int * 6)()
+    rc = lib.wrenc_gpu_recon_coefficients(_rgb_matrix_id(matrix), _rgb_range_id(rng), out)
+    if rc:
+        raise WrencGpuError(rc, "recon_coefficients(%r, %r)" % (matrix, rng))
+    return list(out)
+
+
+def _recon_planes(fmt, w, h, out, what):
+    """The planes a recon call fills: fresh arrays of the layout's shapes, or the caller's `out` (2-D uint8 arrays of those
+    shapes, possibly views into wider arrays with the last axis contiguous).  Returns (planes, pointer array, stride array)."""
+    lay = recon_layout(fmt, w, h)
+    shapes = [(lay["rows"][p], lay["row_bytes"][p]) for p in range(lay["n_planes"])]
+    if out is None:
+        out = [np.zeros(s, np.uint8) for s in shapes]
+    else:
+        out = [out] if isinstance(out, np.ndarray) else list(out)
+        if len(out) != len(shapes) or any(not isinstance(a, np.ndarray) or a.dtype != np.uint8 or a.shape != s or a.strides[1] != 1
+                                          or not a.flags.writeable for a, s in zip(out, shapes)):
+            raise WrencGpuError(-1, "%s: out must be writable uint8 arrays of shapes %s" % (what, shapes))
+    ptr = (C.c_void_p * 3)(*[a.ctypes.data for a in out])
+    stride = (C.c_size_t * 3)(*[a.strides[0] for a in out])
+    return out, ptr, stride
+
+
+def recon_convert_host(fmt, matrix, rng, w, h, y, cb, cr, out=None):
+    """wrenc_gpu_recon_convert_host (host only): the rules of include/wrenc_recon.h over a whole picture, from the visible
+    planes y (h x w), cb and cr (h/2 x w/2) to the planes of output format `fmt` as recon_layout numbers them: a list of
+    2-D uint8 arrays (rows x row_bytes), fresh ones or `out` filled in place."""
+    lib = load_library()
+    w, h = int(w), int(h)
+    y, cb, cr = (np.ascontiguousarray(a, np.uint8) for a in (y, cb, cr))
+    if y.shape != (h, w) or cb.shape != (h // 2, w // 2) or cr.shape != cb.shape:
+        raise WrencGpuError(-1, "recon_convert_host: planes of %s" % ([a.shape for a in (y, cb, cr)],))
+    planes, ptr, stride = _recon_planes(fmt, w, h, out, "recon_convert_host")
+    rc = lib.wrenc_gpu_recon_convert_host(_recon_id(fmt), _rgb_matrix_id(matrix), _rgb_range_id(rng), w, h, _p(y), _p(cb), _p(cr), ptr, stride)
+    if rc:
+        raise WrencGpuError(rc, "recon_convert_host(%r, %r, %r, %d, %d)" % (fmt, matrix, rng, w, h))
+    return planes
 
 
 class WrencGpuError(RuntimeError):
@@ -787,6 +876,36 @@ class Encoder:
         keep = {k: np.ascontiguousarray(rec[k]) for k in ("lev_y", "lev_cb", "lev_cr", "cu_log2_size", "luma_mode", "chroma_mode")}
         pic = Picture(*[_p(keep[k]) if k in keep else None for k in _PIC_KEYS])
         self._check(self.lib.wrenc_gpu_test_load_record(self.ctx, slot, C.byref(pic)))
+
+    def test_load_recon(self, slot, y, cb, cr):
+        """Test entry: put coded-size planes into a slot's reconstruction and mark the slot encoded."""
+        y, cb, cr = (np.ascontiguousarray(a, np.uint8) for a in (y, cb, cr))
+        assert y.shape == (self.height, self.width) and cb.shape == cr.shape == (self.height // 2, self.width // 2)
+        self._check(self.lib.wrenc_gpu_test_load_recon(self.ctx, slot, _p(y), _p(cb), _p(cr)))
+
+    def download_recon(self, slot, fmt="yuv420p", matrix="bt709", rng="tv", out=None):
+        """wrenc_gpu_download_recon: the slot's reconstruction at the visible size in output format `fmt` (an id or a name of
+        include/wrenc_recon.h), made on the device; matrix and rng (ids or names) are read for the RGB formats only.
+        Returns a list of 2-D uint8 arrays (rows x row_bytes) as recon_layout numbers the planes: fresh ones, or `out`
+        (views into wider arrays keep their row strides; only the rows' bytes are written)."""
+        w, h = self.visible_size()
+        planes, ptr, stride = _recon_planes(fmt, w, h, out, "download_recon")
+        f = ReconFormat(_recon_id(fmt), _rgb_matrix_id(matrix), _rgb_range_id(rng))
+        self._check(self.lib.wrenc_gpu_download_recon(self.ctx, slot, C.byref(f), ptr, stride))
+        return planes
+
+    def download_recon_device(self, slot, fmt, pointers, strides, stream=0, matrix="bt709", rng="tv"):
+        """wrenc_gpu_download_recon_device: as download_recon, into DEVICE memory: the planes' addresses (plain integers, one
+        to three) and row strides in bytes; stream: the hipStream_t (an integer; 0 the null stream) that consumes the
+        picture: the copies run behind what it has queued so far, and what it queues next runs behind them.  No host
+        wait."""
+        pointers = [int(p) if p else None for p in pointers]
+        strides = [int(s) for s in strides]
+        assert 1 <= len(pointers) <= 3 and len(strides) == len(pointers)
+        ptr = (C.c_void_p * 3)(*pointers)
+        stride = (C.c_size_t * 3)(*strides)
+        f = ReconFormat(_recon_id(fmt), _rgb_matrix_id(matrix), _rgb_range_id(rng))
+        self._check(self.lib.wrenc_gpu_download_recon_device(self.ctx, slot, C.byref(f), ptr, stride, C.c_void_p(int(stream) if stream else None)))
 
     def expand_levels(self, mask, payload):
         """Dense level planes from a compact record (host only)."""

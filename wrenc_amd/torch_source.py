@@ -1,4 +1,5 @@
-"""Pictures that are torch tensors on the GPU, into an encoder without a trip over the bus (wrenc_gpu_upload_planes_device).
+"""Pictures that are torch tensors on the GPU, into an encoder and the reconstruction back out of it without a trip over the bus
+(wrenc_gpu_upload_planes_device, wrenc_gpu_download_recon_device).
 
 torch is imported here and nowhere else in the package: wrenc_amd.gpu stays a ctypes binding of the C ABI.
 
@@ -86,3 +87,51 @@ def upload_tensor(enc, slot, t, stream=None):
     if stream is None:
         stream = torch.cuda.current_stream(first.device).cuda_stream
     enc.upload_device(slot, [p for p, _ in planes], [s for _, s in planes], stream)
+
+
+def to_float(t):
+    """A uint8 tensor -> float in [0, 1] by t.float() / 255: the inverse of to_uint8 up to torch's floating-point arithmetic."""
+    return t.float() / 255
+
+
+def download_tensor(enc, slot, fmt, matrix="bt709", rng="tv", out=None, stream=None):
+    """The reconstruction of encoded slot `slot` as tensor(s) on the encoder's device, at its visible size, without a trip
+    over the bus (wrenc_gpu_download_recon_device; include/wrenc_recon.h defines the picture).  The shapes mirror
+    upload_tensor:
+        rgb24 / bgr24   one (H, W, 3) uint8 tensor
+        rgb0 / bgr0     one (H, W, 4) uint8 tensor (the fourth byte is 255)
+        gbrp            one (3, H, W) uint8 tensor in R, G, B order -- a model's CHW image
+        yuv420p / nv12  a tuple of plane tensors (rows x bytes)
+    out: the tensor(s) to fill instead of fresh ones -- views into larger tensors work, the samples of a row must be packed;
+    nothing outside the views is written.  stream: a hipStream_t as an integer; None takes torch.cuda.current_stream of the
+    encoder's device.  The copies run behind what that stream has queued so far and what it queues next runs behind them:
+    nothing synchronises.  ValueError for an `out` that does not fit; gpu.WrencGpuError for what the library refuses."""
+    fid = gpu.recon_from_name(fmt) if isinstance(fmt, str) else int(fmt)
+    w, h = enc.visible_size()
+    device = enc.cfg.device
+    dev = torch.device("cuda", device)
+    lay = gpu.recon_layout(fid, w, h)
+    if fid in _PACKED:
+        c = _PACKED[fid]
+        if out is None:
+            out = torch.empty((h, w, c), dtype=torch.uint8, device=dev)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.dim() != 3 or tuple(out.shape) != (h, w, c):
+            raise ValueError("%s fills a (%d, %d, %d) uint8 tensor" % (gpu.recon_name(fid), h, w, c))
+        planes = [_plane(out, h, w * c, device, "the picture")]
+    elif fid == _GBRP:
+        if out is None:
+            out = torch.empty((3, h, w), dtype=torch.uint8, device=dev)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.dim() != 3 or tuple(out.shape) != (3, h, w):
+            raise ValueError("gbrp fills a (3, %d, %d) uint8 tensor in R, G, B order" % (h, w))
+        planes = [_plane(out[c], h, w, device, "plane %d" % c) for c in (1, 2, 0)]
+    else:
+        shapes = [(lay["rows"][p], lay["row_bytes"][p]) for p in range(lay["n_planes"])]
+        if out is None:
+            out = tuple(torch.empty(s, dtype=torch.uint8, device=dev) for s in shapes)
+        elif not isinstance(out, (tuple, list)) or len(out) != len(shapes) or any(not isinstance(p, torch.Tensor) or p.dtype != torch.uint8 for p in out):
+            raise ValueError("%s fills a tuple of %d uint8 plane tensors" % (gpu.recon_name(fid), len(shapes)))
+        planes = [_plane(p, s[0], s[1], device, "plane %d" % i) for i, (p, s) in enumerate(zip(out, shapes))]
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    enc.download_recon_device(slot, fid, [p for p, _ in planes], [s for _, s in planes], stream, matrix=matrix, rng=rng)
+    return out
