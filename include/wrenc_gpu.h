@@ -27,6 +27,7 @@
 #include "wrenc_format.h"
 #include "wrenc_hash.h"
 #include "wrenc_ratecurve.h"
+#include "wrenc_distcurve.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -406,6 +407,21 @@ int wrenc_gpu_download_rate_hist(wrenc_gpu_ctx* ctx, int first_slot, int n, wren
  * (WRENC_GPU_EINVAL for a bad size or a null pointer). */
 int wrenc_gpu_rate_hist_bin(int magnitude);
 int wrenc_gpu_rate_hist_host(int width, int height, const uint8_t* y, const uint8_t* cb, const uint8_t* cr, wrenc_rate_hist* out);
+
+/* Distortion curve read-back: the squared error that quantising a slot's residual coefficients leaves at every QP 0 .. 63,
+ * from its originals alone, BEFORE any search -- what a quality target chooses a picture's QP by
+ * (include/wrenc_rate_quality.h).  The definition, in exact integers, is include/wrenc_distcurve.h: the coefficients of the
+ * rate histogram (same blocks, prediction and transform), each quantised with the step of every QP, and per plane and QP
+ * the sum of the squared errors; sse8 / 4096 predicts the plane's sample-domain SSE.  1536 bytes a picture over the bus; the
+ * same planes give the same table in any slot, batch and run.  The calling rules are wrenc_gpu_download_rate_hist's: n slots
+ * in one call, blocking, on the copy stream behind the slots' uploads and behind no search; every slot that holds
+ * originals; WRENC_GPU_ESTATE for a slot never uploaded into, WRENC_GPU_EINVAL for a bad range; changes nothing in the
+ * slot.  Its scratch is allocated on the first call, for every slot at once: a context that never calls it launches and
+ * allocates nothing it did not before. */
+int wrenc_gpu_download_dist_curve(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_dist_curve* out);
+/* Host only, no device: the table of a picture of width x height (multiples of 16, at least 16; tightly packed planes) by
+ * wrenc_distcurve.h itself (WRENC_GPU_EINVAL for a bad size or a null pointer). */
+int wrenc_gpu_dist_curve_host(int width, int height, const uint8_t* y, const uint8_t* cb, const uint8_t* cr, wrenc_dist_curve* out);
 
 /* Host only, no device: PSNR (dB) and SSIM as {Avg, Y, U, V} in wrenc_amd/metrics.py's definitions:
  * plane PSNR 10 log10(255^2 n / sse) (+infinity for sse 0), Avg from the MSE over all samples of the frame,

@@ -39,6 +39,13 @@ ${CLANGXX:-/opt/rocm/lib/llvm/bin/clang++} -O1 -g -std=c++17 -fsanitize=address,
 g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined \
     -o "$T/rate_vbv" "$R/tools/sanitize/rate_vbv.cpp" $H0/rate_control.cpp
 "$T/rate_vbv"
+# the quality mode's host code: the distortion curve's definition (include/wrenc_distcurve.h), the kernel's division-free
+# quantiser (wrenc_amd/csrc/distcurve_quant.h) against it at every magnitude and QP, and the controller
+# (include/wrenc_rate_quality.h) over random curves and PSNR tables.  -ffp-contract=off as the library is built: the
+# quantiser's multiply-adds are explicit fmaf calls either way, the flag keeps everything around them uncontracted too
+g++ -O1 -g -std=c++17 -ffp-contract=off -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined \
+    -o "$T/rate_quality" "$R/tools/sanitize/rate_quality.cpp" $H0/rate_quality.cpp
+"$T/rate_quality"
 # the launch plan of an encode call (wrenc_amd/csrc/encode_plan.h) over the sweep of tests/test_encode_plan.py
 g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined \
     -o "$T/encode_plan" "$R/tools/sanitize/encode_plan.cpp"

@@ -22,6 +22,9 @@ EXPORTED_RATE_SYMBOLS = ("wrenc_rate_prior", "wrenc_rate_create", "wrenc_rate_de
 # its buffer model (include/wrenc_rate_vbv.h)
 EXPORTED_RATE_VBV_SYMBOLS = ("wrenc_rate_curve", "wrenc_rate_curve_prior", "wrenc_rate_enable_vbv", "wrenc_rate_choose_vbv",
                              "wrenc_rate_vbv_allowance", "wrenc_rate_recode")
+# quality controller (include/wrenc_rate_quality.h)
+EXPORTED_QUALITY_SYMBOLS = ("wrenc_quality_create", "wrenc_quality_destroy", "wrenc_quality_predict", "wrenc_quality_choose",
+                            "wrenc_quality_report", "wrenc_quality_correction", "wrenc_quality_totals", "wrenc_quality_tries")
 # decoded picture hash SEI (include/wrenc_bitstream_hash.h)
 EXPORTED_HASH_SYMBOLS = ("wrenc_bs_picture_hash", "wrenc_bs_write_hash_sei")
 

@@ -85,14 +85,12 @@ __device__ __forceinline__ void rh_predict(const RhBlock& b, bool has_top, bool 
     }
 }
 
-// The coefficients of blocks a (low halves) and b (high halves) counted into the wave's sub-histograms hist_a / hist_b
-// (already at the lane's column) and, the zeros, into the lane's zeros_a / zeros_b.
-__device__ __forceinline__ void rh_pair(const RhBlock& a, const RhBlock& b, bool top_a, bool top_b, bool has_left, bool own,
-                                        uint32_t* hist_a, uint32_t* hist_b, uint32_t& zeros_a, uint32_t& zeros_b) {
+// The coefficients of blocks a (low halves) and b (high halves): wrenc_ratecurve_block of each (dev_distcurve.h starts
+// from them too)
+__device__ __forceinline__ void rh_coefficients(const RhBlock& a, const RhBlock& b, bool top_a, bool top_b, bool has_left, Pk16 v[64]) {
     Dwords2 pa[8], pb[8];
     rh_predict(a, top_a, has_left, pa);
     rh_predict(b, top_b, has_left, pb);
-    Pk16 v[64];
 #pragma unroll
     for (int y = 0; y < 8; ++y)
 #pragma unroll
@@ -111,6 +109,14 @@ __device__ __forceinline__ void rh_pair(const RhBlock& a, const RhBlock& b, bool
                 v[i] = p + q;
                 v[i | h] = p - q;
             }
+}
+
+// The coefficients of blocks a and b counted into the wave's sub-histograms hist_a / hist_b (already at the lane's column)
+// and, the zeros, into the lane's zeros_a / zeros_b.
+__device__ __forceinline__ void rh_pair(const RhBlock& a, const RhBlock& b, bool top_a, bool top_b, bool has_left, bool own,
+                                        uint32_t* hist_a, uint32_t* hist_b, uint32_t& zeros_a, uint32_t& zeros_b) {
+    Pk16 v[64];
+    rh_coefficients(a, b, top_a, top_b, has_left, v);
 #pragma unroll
     for (int i = 0; i < 64; ++i) {
         const uint32_t w = __builtin_bit_cast(uint32_t, __builtin_elementwise_abs(v[i]));

@@ -27,7 +27,7 @@
 using namespace wrenc;
 
 namespace wrenc {
-// what the read-backs' scratch holds (dev_metrics.h, dev_hash.h, dev_complexity.h, dev_ratecurve.h): complete in
+// what the read-backs' scratch holds (dev_metrics.h, dev_hash.h, dev_complexity.h, dev_ratecurve.h, dev_distcurve.h): complete in
 // wrenc_gpu_io.hip, names only in the search unit.  The context has the same layout in both because a DevBuf<T> is a
 // pointer and a count whatever T is (host_mem.h), and destroying or moving one needs no complete T.
 struct MetricsPartial;
@@ -36,6 +36,7 @@ struct HashTables;
 struct ComplexityPartial;
 struct RateHistPartial;
 struct RateHistCounts;
+struct DistCurveSums;
 } // namespace wrenc
 
 // A mixed-QP encode call (wrenc_gpu_set_slot_qp) runs its pictures from a per-call list, ordered by QP and padded so that
@@ -167,6 +168,8 @@ struct wrenc_gpu_ctx {
     // on first use and never again, as the complexity scratch)
     DevBuf<RateHistPartial> d_rpartial;
     DevBuf<RateHistCounts> d_rsums;
+    // distortion curve read-back: the waves' sums of one call and the pictures' tables, by the same rule
+    DevBuf<DistCurveSums> d_dpartial, d_dsums;
     int schedule = WRENC_GPU_SCHEDULE_AUTO;
     bool stats_valid = false;
     std::string err;

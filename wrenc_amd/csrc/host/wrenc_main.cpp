@@ -62,6 +62,10 @@
 // hashes them; 48 bytes a picture over the bus) and the SEI's NAL unit (wrenc_bs_write_hash_sei) is part of the picture's
 // bytes: --bitrate charges it and --metrics' frame_bytes include it.  Without the option nothing is launched or written.
 //
+// --target-psnr DB [--max-recodes N] (not with --bitrate, --vbv-bufsize, --qp-file): every picture at the largest QP whose luma
+// PSNR is at least DB (include/wrenc_rate_quality.h on wrenc_gpu_download_dist_curve and the device's metrics); the flow is
+// --vbv-bufsize's: a unit's batch is flushed before the unit uploads again, and a picture the controller does not accept is
+// searched again in its slot, read back and written once more.  Without the option nothing of it is launched or allocated.
 // --vbv-bufsize KBIT (with --bitrate): every picture's size is bounded by a leaky bucket of KBIT * 1000 bits that fills by
 // bitrate / fps bits per picture and starts full (include/wrenc_rate.h: the buffer model; the parameter sets are charged to
 // picture 0, the hash SEI to its picture).  Every batch is measured by wrenc_gpu_download_rate_hist, not by its complexity,
@@ -93,6 +97,7 @@
 #include "../../../include/wrenc_bitstream_window.h"
 #include "../../../include/wrenc_gpu.h"
 #include "../../../include/wrenc_rate.h"
+#include "../../../include/wrenc_rate_quality.h"
 #include "../../../include/wrenc_recon.h"
 
 namespace {
@@ -206,6 +211,8 @@ struct Options {
     int min_qp = 26;         // the smallest QP of the run
     double bitrate = 0, fps = 30; // --bitrate (kbit/s, 0: none) and --fps
     double vbv_bits = 0;          // --vbv-bufsize in bits (0: no buffer model)
+    double target_psnr = 0;       // --target-psnr in dB of luma PSNR (0: none) and --max-recodes
+    int max_recodes = 3;
 };
 
 // --qp-file: whitespace-separated integers 0..63, entry i the QP of picture i, at least one per picture
@@ -235,7 +242,7 @@ std::vector<int> read_qp_file(const char* path, long num_pictures) {
 
 Options parse_options(int argc, char** argv) {
     Options o;
-    const char *in_size = nullptr, *out_size = nullptr, *device_list = nullptr, *qp_file = nullptr, *bitrate = nullptr, *fps = nullptr, *vbv = nullptr,
+    const char *in_size = nullptr, *out_size = nullptr, *device_list = nullptr, *qp_file = nullptr, *bitrate = nullptr, *fps = nullptr, *vbv = nullptr, *target_psnr = nullptr, *max_recodes = nullptr,
                *colorspace = nullptr, *range = nullptr, *rec_colorspace = nullptr, *rec_range = nullptr;
     int device = 0;
     for (int i = 1; i < argc; ++i) {
@@ -255,6 +262,8 @@ Options parse_options(int argc, char** argv) {
         else if (a == "--bitrate") bitrate = val();
         else if (a == "--fps") fps = val();
         else if (a == "--vbv-bufsize") vbv = val();
+        else if (a == "--target-psnr") target_psnr = val();
+        else if (a == "--max-recodes") max_recodes = val();
         else if (a == "--max-split-depth") o.depth = atoi(val());
         else if (a == "--extra-params") o.extra = val();
         else if (a == "--batch") o.batch = atoi(val());
@@ -382,6 +391,18 @@ Options parse_options(int argc, char** argv) {
         o.vbv_bits = kbit * 1000.0;
         if (o.vbv_bits < o.bitrate * 1000.0 / o.fps)
             die("vbv-bufsize %s kbit is smaller than one picture's share of the bitrate, %.3f kbit", vbv, o.bitrate / o.fps);
+    }
+    if (target_psnr) {
+        if (bitrate || vbv || qp_file) die("--target-psnr excludes --bitrate, --vbv-bufsize and --qp-file: the QPs come from the quality target");
+        if (!positive(target_psnr, o.target_psnr)) die("Invalid target-psnr: %s (dB of luma PSNR, a number above 0)", target_psnr);
+        o.ramp_mode = 2; // (auto looks at the clock: the batches, and with them the QPs, must not depend on it)
+    }
+    if (max_recodes) {
+        if (!target_psnr) die("--max-recodes needs --target-psnr");
+        char* end = nullptr;
+        const long v = strtol(max_recodes, &end, 10);
+        if (end == max_recodes || *end || v < 0 || v > WRENC_QUALITY_MAX_RECODES) die("Invalid max-recodes: %s (0 .. %d)", max_recodes, WRENC_QUALITY_MAX_RECODES);
+        o.max_recodes = (int)v;
     }
     if (qp_file) {
         o.pic_qp = read_qp_file(qp_file, o.num_pictures);
@@ -571,12 +592,44 @@ struct Run {
     std::vector<double> vbv_left;
     std::vector<int> vbv_recodes;
     long vbv_reencoded = 0, vbv_violations = 0;
+    // --target-psnr: a controller per unit (a unit's batch is chosen while the other unit's is still to be reported; each
+    // learns from its own batches, in an order that the options alone decide), the batch's curves, every picture's codings
+    // and the run's counts
+    std::vector<std::pair<const HostSet*, wrenc_quality*>> quality;
+    int quality_qp_max = 63;
+    std::vector<wrenc_dist_curve> curves;
+    std::vector<int> quality_tries;
+    long quality_reencoded = 0, quality_misses = 0;
 
-    int slice_qp(long picture) const { return rate ? rate_qp[(size_t)picture] : (o.pic_qp.empty() ? o.qp : o.pic_qp[(size_t)picture]); }
+    wrenc_quality* quality_of(const HostSet& s) {
+        for (const auto& q : quality)
+            if (q.first == &s) return q.second;
+        wrenc_quality* q = wrenc_quality_create(o.target_psnr, 0, quality_qp_max, o.max_recodes);
+        if (!q) fatal("quality control: bad configuration");
+        quality.emplace_back(&s, q);
+        return q;
+    }
+
+    int slice_qp(long picture) const { return rate || o.target_psnr > 0 ? rate_qp[(size_t)picture] : (o.pic_qp.empty() ? o.qp : o.pic_qp[(size_t)picture]); }
 
     // The QPs of the unit's uploaded batch: measured on the device while the other unit's search keeps it busy, chosen
     // with every byte count known by now, set slot by slot.
     void choose_qps(HostSet& s) {
+        if (o.target_psnr > 0) { // the unit's previous batch is out already (main)
+            curves.resize((size_t)s.count);
+            gpu_check(s, wrenc_gpu_download_dist_curve(s.ctx, s.base, s.count, curves.data()));
+            std::vector<int32_t> qps((size_t)s.count);
+            if (wrenc_quality_choose(quality_of(s), s.count, curves.data(), o.w, o.h, qps.data())) fatal("quality control: choose failed");
+            int lo = 63, hi = 0;
+            for (int k = 0; k < s.count; ++k) {
+                rate_qp[(size_t)(poc + k)] = qps[(size_t)k];
+                gpu_check(s, wrenc_gpu_set_slot_qp(s.ctx, s.base + k, config_of(qps[(size_t)k])));
+                lo = qps[(size_t)k] < lo ? qps[(size_t)k] : lo;
+                hi = qps[(size_t)k] > hi ? qps[(size_t)k] : hi;
+            }
+            if (o.verbose) fprintf(stderr, "  batch at picture %ld: QP %d .. %d (a QP per picture)\n", poc, lo, hi);
+            return;
+        }
         if (o.vbv_bits > 0) { // the unit's previous batch is out already (main): nothing to flush here
             hists.resize((size_t)s.count);
             gpu_check(s, wrenc_gpu_download_rate_hist(s.ctx, s.base, s.count, hists.data()));
@@ -668,7 +721,7 @@ struct Run {
                 upload(s, k);
             }
         }
-        if (s.count && rate) choose_qps(s);
+        if (s.count && (rate || o.target_psnr > 0)) choose_qps(s);
         if (s.count) gpu_check(s, wrenc_gpu_encode(s.ctx, s.base, s.count));
         poc += s.count;
     }
@@ -820,10 +873,44 @@ struct Run {
         if (wrenc_rate_report(rate, 1, &bytes_k)) fatal("rate control: report failed");
     }
 
+    // --target-psnr: picture k of the batch being flushed against the target.  Its coding's luma SSE goes to the unit's
+    // controller, which keeps it or names the QP to search it again at while its slot still holds the originals; the
+    // picture is then read back and written again on this thread.  Where the coding to keep is an earlier one (a higher QP
+    // fell below the target), the picture is searched once more at that QP: the same coding, nothing is kept in memory.
+    void enforce_quality(HostSet& s, int k) {
+        const size_t picture = (size_t)(s.bs_first_poc + k);
+        wrenc_quality* q = quality_of(s);
+        int codings = 1;
+        while (!s.status[(size_t)k]) {
+            wrenc_gpu_metrics m;
+            gpu_check(s, wrenc_gpu_download_metrics(s.ctx, s.base + k, 1, &m));
+            int32_t next = 0;
+            int accepted = 0;
+            if (wrenc_quality_report(q, k, rate_qp[picture], m.sse[0], (uint64_t)o.vis_w * (uint64_t)o.vis_h, &next, &accepted))
+                fatal("quality control: report failed");
+            if (accepted && next == rate_qp[picture]) break;
+            rate_qp[picture] = next;
+            ++codings;
+            gpu_check(s, wrenc_gpu_set_slot_qp(s.ctx, s.base + k, config_of(next)));
+            gpu_check(s, wrenc_gpu_encode(s.ctx, s.base + k, 1));
+            const bool batch_tokens = s.bs_tokens;
+            s.bs_tokens = read_back(s, k, 1, s.bs_first_poc);
+            write_picture(s, k);
+            s.bs_tokens = batch_tokens;
+            if (accepted) break;
+        }
+        quality_tries[picture] = codings;
+        quality_reencoded += codings - 1;
+    }
+
     void flush(HostSet& s) {
         pool.wait();
         const long reenc0 = vbv_reencoded, viol0 = vbv_violations;
+        const long q_reenc0 = quality_reencoded;
+        uint64_t q_miss0 = 0, q_miss1 = 0;
+        if (o.target_psnr > 0) wrenc_quality_totals(quality_of(s), nullptr, &q_miss0);
         for (int k = 0; k < s.bs_count; ++k) {
+            if (o.target_psnr > 0) enforce_quality(s, k);
             if (o.vbv_bits > 0) enforce_vbv(s, k);
             if (s.status[(size_t)k]) fatal("wrenc_bs_write_picture failed with %d on picture %d", s.status[(size_t)k], s.bs_first_poc + k);
             fwrite(s.nal[(size_t)k].data(), 1, s.len[(size_t)k], fout);
@@ -831,6 +918,12 @@ struct Run {
             if (o.metrics) pic_bytes.push_back(s.len[(size_t)k]);
             if (frec && o.rec_format >= 0) fwrite(s.rec + g.rpic * k, 1, g.rpic, frec);
             else if (frec) write_reconst(s.rec + g.pic * k); // main.rs:387-399
+        }
+        if (o.target_psnr > 0) {
+            wrenc_quality_totals(quality_of(s), nullptr, &q_miss1);
+            quality_misses += (long)(q_miss1 - q_miss0);
+            if (o.verbose && s.bs_count > 0)
+                fprintf(stderr, "  quality: batch at picture %d: %ld re-encoded, %ld misses\n", s.bs_first_poc, quality_reencoded - q_reenc0, (long)(q_miss1 - q_miss0));
         }
         if (o.vbv_bits > 0) { // (reported picture by picture, above)
             if (o.verbose && s.bs_count > 0)
@@ -897,6 +990,11 @@ void write_metrics_report(const Run& run, const char* path, unsigned long long s
     if (o.vbv_bits > 0) { // fullness: the bits left in the bucket once the picture is taken out, negative for a violation
         fprintf(f, ",\n \"vbv\": {\"bufsize_bits\": %.17g, \"reencoded\": %ld, \"violations\": %ld, \"fullness\": [", o.vbv_bits, run.vbv_reencoded, run.vbv_violations);
         for (size_t i = 0; i < n; ++i) fprintf(f, "%s%.17g", i ? ", " : "", run.vbv_left[i]);
+        fputs("]}", f);
+    }
+    if (o.target_psnr > 0) {
+        fprintf(f, ",\n \"quality\": {\"target_psnr\": %.17g, \"reencoded\": %ld, \"misses\": %ld, \"tries\": [", o.target_psnr, run.quality_reencoded, run.quality_misses);
+        for (size_t i = 0; i < n; ++i) fprintf(f, "%s%d", i ? ", " : "", run.quality_tries[i]);
         fputs("]}", f);
     }
     fputs("}\n", f);
@@ -977,6 +1075,13 @@ int main(int argc, char** argv) {
         run.rate_qp.assign((size_t)o.num_pictures, o.qp);
         if (o.verbose) fprintf(stderr, "rate control: %.1f kbit/s at %.3g pictures/s = %.1f bytes per picture, QP 0 .. %d\n", o.bitrate, o.fps, target_bytes, qp_max);
     }
+    if (o.target_psnr > 0 && o.num_pictures > 0) { // (the QPs stay below the first one --extra-params pushes out of range, as above)
+        while (run.quality_qp_max > o.qp && wrenc_gpu_set_slot_qp(ctxs[0], 0, run.config_of(run.quality_qp_max)) == WRENC_GPU_EINVAL) --run.quality_qp_max;
+        if (wrenc_gpu_set_slot_qp(ctxs[0], 0, nullptr)) fatal("%s", wrenc_gpu_last_error(ctxs[0]));
+        run.rate_qp.assign((size_t)o.num_pictures, o.qp);
+        run.quality_tries.assign((size_t)o.num_pictures, 0);
+        if (o.verbose) fprintf(stderr, "quality control: luma PSNR of at least %.3f dB, at most %d re-encodes a picture, QP 0 .. %d\n", o.target_psnr, o.max_recodes, run.quality_qp_max);
+    }
     // Fill every unit, then go round: read the oldest batch back (waits for its search only), collect the
     // slices of the batch before it (written meanwhile), start this batch's slices, and give the unit the next
     // batch.  With --reconst the planes of a batch are written out before its unit is read back into again.
@@ -1008,7 +1113,7 @@ int main(int argc, char** argv) {
         run.start_slices(s, tokens);
         pending = &s;
         s.count = 0;
-        if (o.vbv_bits > 0) { // the unit's batch out, and enforced, while its slots still hold the originals
+        if (o.vbv_bits > 0 || o.target_psnr > 0) { // the unit's batch out, and enforced, while its slots still hold the originals
             const auto tf = std::chrono::steady_clock::now();
             run.flush(s);
             pending = nullptr;
@@ -1042,6 +1147,8 @@ int main(int argc, char** argv) {
         fprintf(stderr, "rate control: target %.1f kbit/s, achieved %.1f kbit/s (%.0f of %.0f bytes, ratio %.4f)\n", o.bitrate,
                 total / (double)run.pictures * 8.0 * o.fps / 1000.0, total, want, total / want);
     }
+    if (o.target_psnr > 0) fprintf(stderr, "quality: %ld re-encoded, %ld misses\n", run.quality_reencoded, run.quality_misses);
+    for (const auto& q : run.quality) wrenc_quality_destroy(q.second);
     wrenc_rate_destroy(run.rate);
     if (o.verbose) {
         const double dt = since(t_start);

@@ -31,6 +31,7 @@
 //   dev_hash.h       (no counterpart)               decoded picture hash (MD5, CRC, checksum) of the reconstruction
 //   dev_complexity.h (no counterpart)               SATD of the originals per CTU and picture, for the rate control
 //   dev_ratecurve.h  (no counterpart)               rate histogram of the originals (prediction, Hadamard, magnitude bins)
+//   dev_distcurve.h  (no counterpart)               distortion curve of the originals (the same coefficients at all 64 QPs)
 //   dev_pad.h        (no counterpart)               a picture's last column and row replicated into the coded size's margin
 //   dev_scale.h      (no counterpart)               resampling of an uploaded picture to the visible size
 //   dev_format.h     (no counterpart)               10-bit, NV12 / P010 and 4:2:2 uploads to the 8-bit 4:2:0 planes

@@ -1,6 +1,6 @@
 // wrenc_gpu_io.hip -- pictures in and results out: every upload path of the C ABI (include/wrenc_gpu.h: plain, strided,
 // visible size, scaler, source formats, RGB sources, device-resident planes) and every read-back (maps, compact, tokens,
-// metrics, complexity, rate histogram, hashes, the reconstruction in an output format), with the kernels they launch.  A translation unit and a code object of its own in libwrenc_gpu.so (the command
+// metrics, complexity, rate histogram, distortion curve, hashes, the reconstruction in an output format), with the kernels they launch.  A translation unit and a code object of its own in libwrenc_gpu.so (the command
 // is at the top of wrenc_gpu.hip): what is added or changed here cannot move an instruction of the search kernels.
 //
 // The trace and profile builds (-DWRENC_TRACE, -DWRENC_PROFILE) define their device globals in dev_common.h; nothing here
@@ -20,6 +20,7 @@
 #include "dev_hash.h"
 #include "dev_complexity.h"
 #include "dev_ratecurve.h"
+#include "dev_distcurve.h"
 #include "dev_pad.h"
 #include "dev_scale.h"
 #include "dev_format.h"
@@ -984,6 +985,31 @@ int wrenc_gpu_rate_hist_bin(int magnitude) {
 
 int wrenc_gpu_rate_hist_host(int width, int height, const uint8_t* y, const uint8_t* cb, const uint8_t* cr, wrenc_rate_hist* out) {
     return wrenc_ratecurve_picture(y, cb, cr, width, height, out) ? WRENC_GPU_EINVAL : WRENC_GPU_OK;
+}
+
+int wrenc_gpu_download_dist_curve(wrenc_gpu_ctx* ctx, int first_slot, int n, wrenc_dist_curve* out) {
+    if (!ctx || !out) return WRENC_GPU_EINVAL;
+    const wrenc_gpu_config& c = ctx->cfg;
+    if (const int rc = check_slots(ctx, first_slot, n, 1, "slot range out of bounds")) return rc;
+    HIP_TRY(ctx, hipSetDevice(c.device));
+    static_assert(sizeof(DistCurveSums) == sizeof(wrenc_dist_curve), "the device's table is the ABI's");
+    const size_t per_pic = (size_t)cplx_waves(c.width, c.height);
+    if (!ctx->d_dpartial) HIP_TRY(ctx, ctx->d_dpartial.alloc((size_t)c.n_slots * per_pic));
+    if (!ctx->d_dsums) HIP_TRY(ctx, ctx->d_dsums.alloc((size_t)c.n_slots));
+    // on the copy stream: behind the slots' uploads and behind no search, as the rate histogram
+    hipStream_t cs = ctx->copy_stream.get();
+    const size_t waves = (size_t)n * per_pic;
+    hipLaunchKernelGGL(dist_curve_kernel, dim3((unsigned)((waves + kDcWaves - 1) / kDcWaves)), dim3(64 * kDcWaves), 0, cs, ctx->d_slots.get(),
+                       first_slot, n, c.width, c.height, ctx->d_dpartial.get());
+    hipLaunchKernelGGL(dist_curve_finish_kernel, dim3(n), dim3(192), 0, cs, ctx->d_dpartial.get(), c.width, c.height, ctx->d_dsums.get());
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_dsums.get(), (size_t)n * sizeof(wrenc_dist_curve), hipMemcpyDeviceToHost, cs));
+    HIP_TRY(ctx, hipStreamSynchronize(cs));
+    return WRENC_GPU_OK;
+}
+
+int wrenc_gpu_dist_curve_host(int width, int height, const uint8_t* y, const uint8_t* cb, const uint8_t* cr, wrenc_dist_curve* out) {
+    return wrenc_distcurve_picture(y, cb, cr, width, height, out) ? WRENC_GPU_EINVAL : WRENC_GPU_OK;
 }
 
 void wrenc_gpu_metrics_values(int width, int height, const wrenc_gpu_metrics* m, double psnr[4], double ssim[4]) {

@@ -60,6 +60,8 @@ PROTOTYPES = {
     "wrenc_gpu_download_rate_hist": (_I, [_P, _I, _I, _P]),
     "wrenc_gpu_rate_hist_bin": (_I, [_I]),
     "wrenc_gpu_rate_hist_host": (_I, [_I, _I, _P, _P, _P, _P]),
+    "wrenc_gpu_download_dist_curve": (_I, [_P, _I, _I, _P]),
+    "wrenc_gpu_dist_curve_host": (_I, [_I, _I, _P, _P, _P, _P]),
     "wrenc_gpu_metrics_values": (None, [_I, _I, _P, _P, _P]),
     "wrenc_gpu_download_hashes": (_I, [_P, _I, _I, _I, _P]),
     "wrenc_gpu_last_hash_ms": (_I, [_P, _P]),
@@ -184,8 +186,8 @@ class RateHist(C.Structure):
     _fields_ = [("count", (C.c_uint64 * RATE_HIST_BINS) * 3)]
 
 
-def _hist_array(hists, n):
-    return np.frombuffer(hists, np.uint64).reshape(-1, 3, RATE_HIST_BINS)[:n].copy()
+def _hist_array(hists, n, columns=RATE_HIST_BINS):
+    return np.frombuffer(hists, np.uint64).reshape(-1, 3, columns)[:n].copy()
 
 
 def rate_hist_bin(magnitude):
@@ -211,6 +213,29 @@ def rate_hist_host(y, cb, cr):
     if rc:
         raise WrencGpuError(rc, "rate_hist_host(%d x %d)" % (w, h))
     return _hist_array(out, 1)[0]
+
+
+DIST_CURVE_QPS = 64                           # include/wrenc_distcurve.h
+
+
+class DistCurve(C.Structure):
+    """wrenc_dist_curve: sse8[plane][qp], Y, Cb, Cr."""
+    _fields_ = [("sse8", (C.c_uint64 * DIST_CURVE_QPS) * 3)]
+
+
+def dist_curve_host(y, cb, cr):
+    """wrenc_gpu_dist_curve_host (host only): the distortion curve of a picture by include/wrenc_distcurve.h itself, a (3, 64)
+    uint64 array; WrencGpuError for planes that are not h x w, h/2 x w/2, h/2 x w/2 with w and h multiples of 16."""
+    planes = [np.ascontiguousarray(p, np.uint8) for p in (y, cb, cr)]
+    h, w = planes[0].shape if planes[0].ndim == 2 else (0, 0)
+    if any(p.ndim != 2 for p in planes) or planes[1].shape != (h // 2, w // 2) or planes[2].shape != (h // 2, w // 2):
+        raise WrencGpuError(-1, "dist_curve_host: planes of %s" % ([p.shape for p in planes],))
+    lib = load_library()
+    out = (DistCurve * 1)()
+    rc = lib.wrenc_gpu_dist_curve_host(w, h, _p(planes[0]), _p(planes[1]), _p(planes[2]), out)
+    if rc:
+        raise WrencGpuError(rc, "dist_curve_host(%d x %d)" % (w, h))
+    return _hist_array(out, 1, DIST_CURVE_QPS)[0]
 
 
 class PlanLaunch(C.Structure):
@@ -827,6 +852,13 @@ class Encoder:
         outs = (RateHist * max(n, 1))()
         self._check(self.lib.wrenc_gpu_download_rate_hist(self.ctx, first_slot, n, outs))
         return _hist_array(outs, n)
+
+    def download_dist_curve(self, first_slot, n):
+        """The distortion curves of n slots' originals (include/wrenc_gpu.h, wrenc_gpu_download_dist_curve), before or after
+        their search: an (n, 3, 64) uint64 array, sse8[picture][plane][qp]."""
+        outs = (DistCurve * max(n, 1))()
+        self._check(self.lib.wrenc_gpu_download_dist_curve(self.ctx, first_slot, n, outs))
+        return _hist_array(outs, n, DIST_CURVE_QPS)
 
     def test_metrics(self, org, rec, maps=False):
         """Test entry: the metrics kernel on two arbitrary pictures (y, cb, cr) of the context's size.  Returns the entry of

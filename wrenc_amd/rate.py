@@ -132,3 +132,89 @@ class Controller:
             self.close()
         except Exception:
             pass
+
+
+# the quality controller (include/wrenc_rate_quality.h)
+QUALITY_PRIOR, QUALITY_LEARN, QUALITY_MAX_RECODES = -0.9, 0.25, 8
+
+
+def _quality_lib():
+    lib = bitstream.load_library()
+    lib.wrenc_quality_create.restype = C.c_void_p
+    lib.wrenc_quality_create.argtypes = [C.c_double, C.c_int, C.c_int, C.c_int]
+    lib.wrenc_quality_destroy.restype = None
+    lib.wrenc_quality_destroy.argtypes = [C.c_void_p]
+    lib.wrenc_quality_predict.restype = C.c_double
+    lib.wrenc_quality_predict.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    lib.wrenc_quality_choose.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.wrenc_quality_report.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.wrenc_quality_correction.restype = C.c_double
+    lib.wrenc_quality_correction.argtypes = [C.c_void_p]
+    lib.wrenc_quality_totals.restype = None
+    lib.wrenc_quality_totals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.wrenc_quality_tries.argtypes = [C.c_void_p, C.c_int]
+    return lib
+
+
+def _curves(curves):
+    curves = np.ascontiguousarray(curves, np.uint64)
+    if curves.ndim < 2 or curves.shape[-2:] != (3, 64):
+        raise RateError("a distortion curve is (3, 64) sums")
+    return curves.reshape(-1, 3, 64)
+
+
+def quality_predict(curve, width, height):
+    """wrenc_quality_predict: the luma PSNR one (3, 64) distortion curve (wrenc_amd.gpu download_dist_curve) predicts at
+    every QP, uncorrected."""
+    curve = _curves(curve)
+    if len(curve) != 1:
+        raise RateError("quality_predict: one curve")
+    lib = _quality_lib()
+    return np.array([lib.wrenc_quality_predict(curve.ctypes.data, width, height, q) for q in range(64)])
+
+
+class QualityController:
+    def __init__(self, target_psnr, qp_min=0, qp_max=63, max_recodes=3):
+        self.lib = _quality_lib()
+        self.q = C.c_void_p(self.lib.wrenc_quality_create(float(target_psnr), qp_min, qp_max, max_recodes))
+        if not self.q:
+            raise RateError("wrenc_quality_create: bad configuration")
+
+    def choose(self, curves, width, height):
+        """curves: (n, 3, 64) distortion curves of the next n pictures, the current batch from now on; returns their QPs."""
+        curves = np.zeros((0, 3, 64), np.uint64) if len(curves) == 0 else _curves(curves)
+        qp = np.zeros(max(len(curves), 1), np.int32)
+        if self.lib.wrenc_quality_choose(self.q, len(curves), curves.ctypes.data, width, height, qp.ctypes.data):
+            raise RateError("wrenc_quality_choose")
+        return [int(v) for v in qp[:len(curves)]]
+
+    def report(self, picture, qp, sse_y, samples_y):
+        """(accepted, qp): the QP of the coding to keep, or the one to code picture `picture` of the batch again at."""
+        nxt, acc = C.c_int32(), C.c_int()
+        if self.lib.wrenc_quality_report(self.q, picture, qp, int(sse_y), int(samples_y), C.byref(nxt), C.byref(acc)):
+            raise RateError("wrenc_quality_report: not a picture of the batch, accepted already, or a QP tried before")
+        return bool(acc.value), nxt.value
+
+    @property
+    def correction(self):
+        return self.lib.wrenc_quality_correction(self.q)
+
+    def totals(self):
+        """(reencoded, misses) since the controller was made."""
+        r, m = C.c_uint64(), C.c_uint64()
+        self.lib.wrenc_quality_totals(self.q, C.byref(r), C.byref(m))
+        return r.value, m.value
+
+    def tries(self, picture):
+        return self.lib.wrenc_quality_tries(self.q, picture)
+
+    def close(self):
+        if self.q:
+            self.lib.wrenc_quality_destroy(self.q)
+            self.q = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
