@@ -54,10 +54,10 @@ names = (["predict", "fdct", "q_pre", "q_back", "q_trace", "deq", "idct", "recon
          + ["st%d_m%d" % (k, m) for k in range(12) for m in range(4)] + ["y4"] + ["stn%d" % k for k in range(12)] + ["y5"]
          + ["ev%d" % i for i in range(64)] + ["y6"] + ["evn%d" % i for i in range(64)] + ["y7"] + ["quant_t%d" % (4 << i) for i in range(4)] + ["y8"]
          + ["leaf8_packA", "leaf8_sad", "leaf8_packB", "leaf8_cclm", "leaf16_packA", "leaf16_sad", "leaf16_packB", "leaf16_packC",
-            "sad_tables", "sad_blocks", "sad_samples", "leaf8_cclm_sad", "sad_lines"] + ["y9"]
+            "sad_tables", "sad_blocks", "sad_samples", "leaf8_cclm_sad", "sad_lines", "leaf32_full", "leaf32_sad", "leaf32_cclm"] + ["y9"]
          + ["leaf4_stage", "leaf4_packA", "leaf4_sad", "leaf4_packB", "leafc4", "split8_other"] + ["y10"] + ["hist%d" % i for i in range(64)]
          + ["y11"] + CUTS + FLOOR_CUTS + CAND_CUTS + ["y12"] + PRED_BY + ["y13"] + RECON_BY + ["y14"] + SPARSE)
-KINDS = ["sadlist", "full", "nop/copy", "sadsearch", "cclmsearch", "serve8", "?", "leaf8", "leaf16", "split8", "serve4", "node8"] + ["?"] * 4
+KINDS = ["sadlist", "full", "nop/copy", "sadsearch", "cclmsearch", "serve8", "?", "leaf8", "leaf16", "split8", "serve4", "node8", "leaf32"] + ["?"] * 3
 N = len(names)
 out = (C.c_ulonglong * N)()
 enc.lib.wrenc_gpu_prof_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int]

@@ -386,6 +386,10 @@ struct LdsTab {
 };
 __shared__ Lds SHW[WPB];
 __shared__ LdsTab SHT;
+#if !defined(WRENC_EXP_LDS_PAD) && WRENC_WPB == 4
+// the layout the occupancy rests on: 31,968 bytes per workgroup, 25 granules of 1280, five workgroups per CU (encode_ctu)
+static_assert(sizeof(Lds) * WPB + sizeof(LdsTab) == 31968, "the workgroup's LDS is 31,968 bytes");
+#endif
 #define WAVE (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)))
 #define SH (SHW[WAVE])
 
@@ -427,7 +431,7 @@ __device__ __forceinline__ Ctx uni(Ctx c) {
 // Diagnostic build only (-DWRENC_PROFILE): per-phase cycle counters, summed per wave and
 // added to a global table at CTU end.  Never compiled into the product library.
 #ifdef WRENC_PROFILE
-enum { PH_PREDICT, PH_FDCT, PH_QPRE, PH_QBACK, PH_QTRACE, PH_DEQ, PH_IDCT, PH_RECON, PH_TOTAL, PH_CTRL, PH_REFS, PH_SKIP, PH_NSTEP, PH_NFULL, PH_PSZ, PH_PSZ_END = PH_PSZ + 8, PH_PCNT, PH_PCNT_END = PH_PCNT + 8, PH_QB_PRE, PH_QB_WAIT1, PH_QB_WALK, PH_QB_WAIT2, PH_XCHG, PH_COPY, PH_CB, PH_CB_END = PH_CB + 32, PH_CBN, PH_CBN_END = PH_CBN + 32, PH_MEM, PH_MEM_END = PH_MEM + 16, PH_ST, PH_ST_END = PH_ST + 48, PH_STN, PH_STN_END = PH_STN + 12, PH_EV, PH_EV_END = PH_EV + 64, PH_EVN, PH_EVN_END = PH_EVN + 64, PH_QZ, PH_QZ_END = PH_QZ + 4, PH_LEAF, PH_LEAF_END = PH_LEAF + 13, PH_L4, PH_L4_END = PH_L4 + 6, PH_HIST, PH_HIST_END = PH_HIST + 64, PH_CUT, PH_CUT_END = PH_CUT + 8, PH_PRED, PH_PRED_END = PH_PRED + 8, PH_REC, PH_REC_END = PH_REC + 4, PH_SPARSE, PH_SPARSE_END = PH_SPARSE + 16, PH_COUNT }; // PH_HIST: CTU durations, buckets of 2^17 ticks; PH_CUT: children a split cut left unsearched (4x4 luma leaves, chroma leaves, 16x16 nodes, 8x8 nodes), then the cuts that only the floors decided, the partial sum alone being <= the unsplit cost (inside an 8x8 split, between nodes), then the 4x4 luma leaves whose candidate floors skipped the SAD search and pack B / pack B alone (kCandidateCut)
+enum { PH_PREDICT, PH_FDCT, PH_QPRE, PH_QBACK, PH_QTRACE, PH_DEQ, PH_IDCT, PH_RECON, PH_TOTAL, PH_CTRL, PH_REFS, PH_SKIP, PH_NSTEP, PH_NFULL, PH_PSZ, PH_PSZ_END = PH_PSZ + 8, PH_PCNT, PH_PCNT_END = PH_PCNT + 8, PH_QB_PRE, PH_QB_WAIT1, PH_QB_WALK, PH_QB_WAIT2, PH_XCHG, PH_COPY, PH_CB, PH_CB_END = PH_CB + 32, PH_CBN, PH_CBN_END = PH_CBN + 32, PH_MEM, PH_MEM_END = PH_MEM + 16, PH_ST, PH_ST_END = PH_ST + 48, PH_STN, PH_STN_END = PH_STN + 12, PH_EV, PH_EV_END = PH_EV + 64, PH_EVN, PH_EVN_END = PH_EVN + 64, PH_QZ, PH_QZ_END = PH_QZ + 4, PH_LEAF, PH_LEAF_END = PH_LEAF + 16, PH_L4, PH_L4_END = PH_L4 + 6, PH_HIST, PH_HIST_END = PH_HIST + 64, PH_CUT, PH_CUT_END = PH_CUT + 8, PH_PRED, PH_PRED_END = PH_PRED + 8, PH_REC, PH_REC_END = PH_REC + 4, PH_SPARSE, PH_SPARSE_END = PH_SPARSE + 16, PH_COUNT }; // PH_HIST: CTU durations, buckets of 2^17 ticks; PH_CUT: children a split cut left unsearched (4x4 luma leaves, chroma leaves, 16x16 nodes, 8x8 nodes), then the cuts that only the floors decided, the partial sum alone being <= the unsplit cost (inside an 8x8 split, between nodes), then the 4x4 luma leaves whose candidate floors skipped the SAD search and pack B / pack B alone (kCandidateCut)
 // PH_PRED: PH_PREDICT by caller -- full_front at 32x32, at 16x16, pack16_eval, the luma part of pack8_eval, the predict4_lane
 // passes, the CCLM predictions, full_front of blocks up to 8x8 (the final pass), the SAD requests; PH_REC: PH_RECON by
 // caller -- full_back, pack16_eval, pack8_eval, pass4_reg

@@ -11,7 +11,7 @@ namespace wrenc {
 // ---------------------------------------------------------------------------
 // (the numbers index the profile build's counters, tools/phase_profile.py: 6 stays free)
 enum { K_SADLIST = 0, K_FULL = 1, K_NOP = 2, K_SADSEARCH = 3, K_CCLMSEARCH = 4, K_SERVE8 = 5, K_LEAF8 = 7, K_LEAF16 = 8, K_SPLIT8 = 9, K_SERVE4 = 10,
-       K_NODE8 = 11 };
+       K_NODE8 = 11, K_LEAF32 = 12 };
 enum { COPY_NONE = 0, COPY_SAVE = 1, COPY_RESTORE = 2, COPY_PULL = 3 };
 
 // Split cut (wave schedule): a node's children are searched only until their partial cost, summed in z-order in f32 from
@@ -46,9 +46,10 @@ constexpr bool kCandidateCut = true;
 #endif
 
 struct Req {
-    int kind;       // K_FULL: predict .. reconstruct (block_splitter.rs:146-185) of a 32x32 candidate or a final-pass block;
+    int kind;       // K_FULL: predict .. reconstruct (block_splitter.rs:146-185) of a 32x32 candidate of the team schedule or a
+                    // final-pass block;
                     // K_NOP: nothing but the pre_copy;
-                    // K_SADSEARCH: the whole SAD part of a 32x32 leaf search in
+                    // K_SADSEARCH (team kernels): the whole SAD part of a 32x32 leaf search in
                     // one request -- the 13 directional candidates, their first minimum and the two step-search
                     // rounds around it (:899-973): returns the mode (Res::imin) and its SAD (Res::vmin);
                     // K_CCLMSEARCH: the CCLM part of a 16x16 / 32x32 leaf search in one request -- the SADs of LT / T / L_CCLM, the
@@ -65,7 +66,10 @@ struct Req {
                     // candidates in packs of two (leaf16_search): Res::imin = the best luma mode, vmin = its cost, + its parts
                     // K_NODE8 (wave kernel at max-split-depth 3): one 8x8 node decided inside the request -- its unsplit
                     // candidate, its split, the comparison and the restore (node8_search): Res::vmin = the node's cost
-    int comps;      // bit 0: luma block, bit 1: Cb+Cr pair
+                    // K_LEAF32 (wave kernels): the whole search of the CTU's 32x32 SINGLE_TREE leaf in one request, its
+                    // candidates one after the other (full_search); its best candidate is kept in slot copy_slot:
+                    // Res::vmin = the cost, imin / imin2 = luma / chroma mode
+    int comps;     // bit 0: luma block, bit 1: Cb+Cr pair
     int tx, ty, tlg;
     int ml, mc;     // K_FULL: luma / chroma mode; K_SADLIST: mc = the CCLM mode
     bool active;    // false: the request computes nothing (a candidate the reference skips keeps its place in the sequence)
@@ -411,6 +415,8 @@ __device__ __forceinline__ Res split8_search(const Ctx& c, const Req& q, int* ov
 __device__ __forceinline__ void fill_maps(int bx, int by, int lg, int luma_mode, int chroma_mode, bool luma, bool chroma);
 __device__ __forceinline__ void serve_pack4(const Ctx& c, const Req& q, int* overflow);
 __device__ __forceinline__ void serve_pack8(const Ctx& c, const Req& q, int* overflow);
+template <bool TEAM, bool L32>
+__device__ __forceinline__ Res full_search(const Ctx& c, const PicBufs& pb, const Req& q, int* overflow);
 
 // The CCLM probe of a block's chroma pair: get_chroma_intra_pred_aux_cost of LT, T, L_CCLM in one sample pass, their trace
 // records, then the pick of block_splitter.rs:847-854 (SADs are integers < 2^20: comparing them is comparing the
@@ -513,73 +519,13 @@ __device__ __forceinline__ Res evaluate(const Ctx& c, const PicBufs& pb, const R
         serve_pack4(c, q, overflow);
         return r;
     }
-    int mc = q.mc;
-    CclmPick cpick_ = CclmPick{};
-    if (q.kind == K_CCLMSEARCH) {
-        // the three CCLM probes and the pick (cclm_probe); the evaluation follows below
-        if (q.tlg > 4) stage_org(c, 2, q.tx, q.ty, q.tlg);
-        CclmParams call_;
-        mc = cclm_probe(c, q.tx, q.ty, q.tlg, q.tree, &call_);
-        r.imin = mc;
-        cpick_ = cclm_pick(call_, 2 * cclm_mode_index(mc)); // the evaluation below predicts with these
-    }
-    if (q.kind == K_FULL || q.kind == K_CCLMSEARCH) {
-        // Component by component (the two share r1 / r2): a search candidate that gets here is a 32x32 block or a chroma
-        // pair alone, a final-pass block is evaluated once.  One copy of each stage.  Every trellis walk is the wave's own.
-        // (A round per component, the stages in loops over the round's components: the shape is kept for the register
-        // allocator's sake -- one flat loop cost the wave kernels 6 KB of reloaded scalars and 1 % of their speed)
-#pragma unroll 1
-        for (int round = 0; round < 2; ++round) {
-            const int cset = q.comps & (1 << round);
-            if (!cset) continue;
-            if (q.active) {
-#pragma unroll 1
-                for (int comp = 0; comp < 2; ++comp)
-                    if ((cset >> comp) & 1) {
-                        PROF_MARK(tf0_);
-                        full_front(c, q, comp, comp ? mc : q.ml, 0, cpick_);
-                        PROF_MARK(tf1_);
-                        PROF_ADD2(PH_PSZ + ((q.tlg - 2) * 2 + comp), tf0_, tf1_);
-                        PROF_ADD2(PH_PCNT + ((q.tlg - 2) * 2 + comp), 0, 1);
-                    }
-            }
-            PROF_MARK(ts0_);
-            bool any_y = false, any_c = false;
-            {
-                bool any = false;
-                long long lvl = 0;
-                if (q.active)
-                    lvl = quantize_solo(c, q.tlg - round, round ? 2 : 1, overflow, &any);
-                if (round) {
-                    r.lvl_c = lvl;
-                    any_c = any;
-                } else {
-                    r.lvl_y = lvl;
-                    any_y = any;
-                }
-            }
-            PROF_MARK(ts1_);
-            PROF_ADD2(PH_QZ + ((q.tlg - 2) & 3), ts0_, ts1_);
-            if (!q.active) {
-                PROF_ADD2(PH_SKIP, ts0_, ts1_);
-                continue;
-            }
-#pragma unroll 1
-            for (int comp = 0; comp < 2; ++comp) {
-                if (!((cset >> comp) & 1)) continue;
-                PROF_MARK(tb0_);
-                const uint32_t ssd = full_back(c, pb, q, comp, 0, comp ? any_c : any_y);
-                PROF_MARK(tb1_);
-                PROF_ADD2(PH_PSZ + ((q.tlg - 2) * 2 + comp), tb0_, tb1_);
-                if (comp)
-                    r.ssd_c = ssd;
-                else
-                    r.ssd_y = ssd;
-            }
-        }
-        return r;
-    }
-    // K_SADSEARCH / K_SADLIST: get_intra_pred_aux_cost / get_chroma_intra_pred_aux_cost
+    // the full evaluations, one by one: a single candidate, the CCLM part of a 16x16 leaf, or (wave kernels) the whole
+    // 32x32 leaf -- one copy of the stages for the three (full_search)
+    if (!TEAM && q.kind == K_LEAF32) return full_search<TEAM, true>(c, pb, q, overflow);
+    if (q.kind == K_FULL || q.kind == K_CCLMSEARCH) return full_search<TEAM, false>(c, pb, q, overflow);
+    // K_SADSEARCH / K_SADLIST: get_intra_pred_aux_cost / get_chroma_intra_pred_aux_cost.  Only the team kernels ask for
+    // them (leaf_step_team): the wave kernels' 32x32 SAD search runs inside K_LEAF32, so they are built without this copy.
+    if constexpr (!TEAM) return r;
     PROF_MARK(tr0_);
     if (q.refs0 && (q.comps & 1)) build_refs(c, 0, q.tx, q.ty, q.tlg);
     if (q.refs1 && (q.comps & 2)) build_refs(c, 1, q.tx, q.ty, q.tlg);
@@ -1541,6 +1487,189 @@ __device__ __forceinline__ Res leaf16_search(const Ctx& c, const Req& q, int* ov
     return r;
 }
 
+// ---------------------------------------------------------------------------
+// full_search: the full evaluations that go through r1 / r2 one component at a time -- a 32x32 candidate, a chroma pair
+// alone, a final-pass block -- as STEPS of one loop around one copy of the stages (full_front, quantize_solo, full_back).
+//   K_FULL:       one step, the request's candidate.
+//   K_CCLMSEARCH: one step: the three CCLM probes and the pick (cclm_probe), then the chroma pair under the picked mode.
+//   K_LEAF32 (wave kernels): the whole search of the CTU's 32x32 SINGLE_TREE leaf (block_splitter.rs:794-1078) in one
+//       request, six steps: planar, DC, [the SAD search: sad_search] cm, cm - 1, cm + 1, [the winner's luma back, the
+//       probes and the pick] the chroma pair under the picked CCLM mode.  The decisions are the reference's in its order:
+//       the first minimum of [planar, DC, cm, cm - 1, cm + 1] as a running strict-less update, a neighbour outside 2..66
+//       not evaluated (f32::MAX there: never a new minimum), DM chroma unless the CCLM candidate is strictly cheaper
+//       (dm_keeps).  Made once per leaf: both reference builds (step 0), the MPM list, the staged originals of the SAD
+//       lists; the chroma pair is staged again in front of the probes because the three candidates in between run
+//       their transforms through r2, where the staged originals live.  The running best -- cost, mode, class, parts --
+//       stays in scalars across the steps.  A new best goes to slot q.copy_slot straight after its evaluation (the
+//       unsplit slot 1 + level when the node's split is searched next, ctu_step), luma and DM chroma; the winner's luma
+//       comes back from there unless the tile still holds it, and its DM chroma when DM wins.  Until round 20 every step
+//       was a request of its own with a control step of leaf_step in between, every save or restore rode on the next
+//       request or on an empty one, and the SAD search and the CCLM part were two more kinds of request.
+// Res of K_LEAF32: vmin = the leaf's cost, imin / imin2 = its luma / chroma mode.
+// L32: the instantiation that serves K_LEAF32 and nothing else -- six steps, the block's place and size known when it is
+// built (the CTU's 32x32 block: tx = ty = 0, log2 size 5); the other one serves K_FULL / K_CCLMSEARCH in one step and
+// compiles to what evaluate()'s branch was.  One instantiation for all three behind a run-time step count cost the
+// wave kernels 165 more spilled scalars and 1.5 % of the headline.
+// (A round per component, the stages in loops over the round's components: the shape is kept for the register
+// allocator's sake -- one flat loop cost the wave kernels 6 KB of reloaded scalars and 1 % of their speed)
+// ---------------------------------------------------------------------------
+template <bool TEAM, bool L32>
+__device__ __forceinline__ Res full_search(const Ctx& c, const PicBufs& pb, const Req& q, int* overflow) {
+    Res r = res_none();
+    constexpr bool l32 = !TEAM && L32;
+    // (the CTU's 32x32 block: its place and size are known when the code is built)
+    const int tx = l32 ? 0 : q.tx, ty = l32 ? 0 : q.ty, tlg = l32 ? 5 : q.tlg;
+    Req qe = {}; // the step's candidate (only what the stages and sad_search read)
+    qe.tx = tx;
+    qe.ty = ty;
+    qe.tlg = tlg;
+    qe.tree = q.tree;
+    qe.final = q.final;
+    qe.comps = q.comps;
+    qe.ml = q.ml;
+    qe.active = q.active;
+    qe.refs0 = q.refs0;
+    qe.refs1 = q.refs1;
+    int mc = q.mc;
+    CclmPick cpick_ = CclmPick{};
+    // K_LEAF32: the running best, the directional mode of the SAD search, "the tile holds the best candidate", the
+    // winner's DM chroma cost (:1040)
+    LeafBest best = leaf_best_init(PLANAR);
+    MpmList mpl_ = {};
+    int cm = 0;
+    bool tile_best = false;
+    float dm_cost = 0.0f;
+    if (l32) mpl_ = mpm_list(c, tx, ty, tlg);
+    constexpr int steps = l32 ? 6 : 1;
+#pragma unroll 1
+    for (int k = 0; k < steps; ++k) {
+        PROF_MARK(lk0_);
+        bool probe = !l32 && q.kind == K_CCLMSEARCH;
+        if (l32 && (k == 3 ? cm < 3 : (k == 4 && cm + 1 > 66))) continue;
+        if (l32) {
+            if (k == 2) {
+                // the 13 directional candidates, their first minimum and both step-search rounds (:899-973)
+                PROF_MARK(ls0_);
+                stage_org(c, 3, tx, ty, tlg);
+                unsigned smin;
+                sad_search(c, qe, cm, smin);
+                cm = uni(cm);
+                PROF_MARK(ls1_);
+                PROF_ADD2(PH_LEAF + 14, ls0_, ls1_);
+            }
+            // step_search(mode, 1, _, aux = false) on {cm, cm - 1, cm + 1} (:974)
+            const int mode = k == 0 ? PLANAR : (k == 1 ? DC : (k == 2 ? cm : (k == 3 ? cm - 1 : cm + 1)));
+            qe.ml = mode;
+            mc = mode;
+            qe.refs0 = qe.refs1 = k == 0;
+            if (k == 5) {
+                // the winner is decided (:975-978); :989-1037 re-runs its luma to have it in the tile: here it comes back
+                // from the slot; :1040 repeats its chroma evaluation: the parts are re-used
+                if (!tile_best) copy_block(c, COPY_RESTORE, 1, q.copy_slot, tx, ty, tlg);
+                dm_cost = uni_f(assemble_chroma_cost(c, best.mode, best.e));
+                if (c.trace && LANE == 0)
+                    TRACE_REC(c.ctu_x + tx, c.ctu_y + ty, tlg, TREE_SINGLE, 3, 0, best.mode, __float_as_int(dm_cost));
+                qe.comps = 2;
+                qe.ml = 0;
+                probe = true;
+            }
+        }
+        PROF_MARK(lkc_);
+        if (probe) {
+            // the three CCLM probes and the pick (cclm_probe); the evaluation follows below
+            if (tlg > 4) stage_org(c, 2, tx, ty, tlg);
+            CclmParams call_;
+            mc = cclm_probe(c, tx, ty, tlg, q.tree, &call_);
+            r.imin = mc;
+            cpick_ = cclm_pick(call_, 2 * cclm_mode_index(mc)); // the evaluation below predicts with these
+        }
+#pragma unroll 1
+        for (int round = 0; round < 2; ++round) {
+            const int cset = qe.comps & (1 << round);
+            if (!cset) continue;
+            if (qe.active) {
+#pragma unroll 1
+                for (int comp = 0; comp < 2; ++comp)
+                    if ((cset >> comp) & 1) {
+                        PROF_MARK(tf0_);
+                        full_front(c, qe, comp, comp ? mc : qe.ml, 0, cpick_);
+                        PROF_MARK(tf1_);
+                        PROF_ADD2(PH_PSZ + ((tlg - 2) * 2 + comp), tf0_, tf1_);
+                        PROF_ADD2(PH_PCNT + ((tlg - 2) * 2 + comp), 0, 1);
+                    }
+            }
+            PROF_MARK(ts0_);
+            bool any_y = false, any_c = false;
+            {
+                bool any = false;
+                long long lvl = 0;
+                if (qe.active)
+                    lvl = quantize_solo(c, tlg - round, round ? 2 : 1, overflow, &any);
+                if (round) {
+                    r.lvl_c = lvl;
+                    any_c = any;
+                } else {
+                    r.lvl_y = lvl;
+                    any_y = any;
+                }
+            }
+            PROF_MARK(ts1_);
+            PROF_ADD2(PH_QZ + ((tlg - 2) & 3), ts0_, ts1_);
+            if (!qe.active) {
+                PROF_ADD2(PH_SKIP, ts0_, ts1_);
+                continue;
+            }
+#pragma unroll 1
+            for (int comp = 0; comp < 2; ++comp) {
+                if (!((cset >> comp) & 1)) continue;
+                PROF_MARK(tb0_);
+                const uint32_t ssd = full_back(c, pb, qe, comp, 0, comp ? any_c : any_y);
+                PROF_MARK(tb1_);
+                PROF_ADD2(PH_PSZ + ((tlg - 2) * 2 + comp), tb0_, tb1_);
+                if (comp)
+                    r.ssd_c = ssd;
+                else
+                    r.ssd_y = ssd;
+            }
+        }
+        if (!l32) continue;
+        EvalParts e;
+        e.ssd_y = r.ssd_y;
+        e.ssd_c = r.ssd_c;
+        e.lvl_y = r.lvl_y;
+        e.lvl_c = r.lvl_c;
+        if (k < 5) {
+            // a full candidate: its cost, its trace record, the running first minimum; a new best is saved at once, any
+            // other candidate has overwritten the tile
+            tile_best = leaf_candidate(c, tx, ty, tlg, TREE_SINGLE, mpl_, best, k, qe.ml, e);
+            if (tile_best) copy_block(c, COPY_SAVE, 3, q.copy_slot, tx, ty, tlg);
+            PROF_MARK(lk1_);
+            PROF_ADD2(PH_LEAF + 13, lkc_, lk1_);
+            continue;
+        }
+        // the CCLM candidate = the winner's luma parts + the chroma parts just evaluated; :1062-1072 the final
+        // get_intra_pred_cost with the winner's class from its candidate evaluation.  DM wins: its chroma pair comes back
+        const int cclm = mc;
+        e.ssd_y = best.e.ssd_y;
+        e.lvl_y = best.e.lvl_y;
+        const float cclm_cost = uni_f(assemble_chroma_cost(c, cclm, e));
+        if (c.trace && LANE == 0)
+            TRACE_REC(c.ctu_x + tx, c.ctu_y + ty, tlg, TREE_SINGLE, 3, 0, cclm, __float_as_int(cclm_cost));
+        r.imin = best.mode;
+        if (dm_keeps(dm_cost, cclm_cost)) {
+            r.vmin = uni_f(assemble_cost(c, TREE_SINGLE, best.cls, best.mode, best.e));
+            r.imin2 = best.mode;
+            copy_block(c, COPY_RESTORE, 2, q.copy_slot, tx, ty, tlg);
+        } else {
+            r.vmin = uni_f(assemble_cost(c, TREE_SINGLE, best.cls, cclm, e));
+            r.imin2 = cclm;
+        }
+        PROF_MARK(lk2_);
+        PROF_ADD2(PH_LEAF + 15, lk0_, lk2_);
+    }
+    return r;
+}
+
 // the decision maps of a block: at most 8 x 8 units of 4x4 (one lane each), sizes are powers of two
 __device__ __forceinline__ void fill_maps(int bx, int by, int lg, int luma_mode, int chroma_mode, bool luma,
                                           bool chroma) {
@@ -1681,7 +1810,7 @@ __device__ __forceinline__ void req_copy(Req& q, int mode, int comps, int slot, 
 
 // (the numbers index the profile build's counters, tools/phase_profile.py: the gaps are states that are gone)
 enum {
-    C_START = 0, C_PLANAR = 1, C_DCM = 2, C_LIST = 3, C_F0 = 6, C_F1 = 7, C_F2 = 8, C_CCLM = 11, C_DM = 12,
+    C_START = 0, C_CCLM = 11, C_DM = 12,
     C_L8 = 20, C_L16 = 21, C_WINNER = 22
 };
 
@@ -1827,42 +1956,15 @@ __device__ __forceinline__ void leaf_take(LeafSF& s, float val, const EvalParts&
     s.mode = (uint8_t)mode;
     s.best_cls = (uint8_t)cls;
 }
-// wave schedule, result of a full candidate: running first minimum over the candidates in the reference's order; a new
-// best is saved by the next request, any other active candidate has overwritten the tile
-__device__ __forceinline__ void leaf_offer(LeafSF& s, float val, const EvalParts& parts, int mode, int cls) {
-    if (val < s.best_cost) {
-        leaf_take(s, val, parts, mode, cls);
-        s.need_save = 1;
-        s.tile_best = 1;
-    } else if (s.op_act) {
-        s.tile_best = 0;
-    }
-}
-
 // One step of the search of a SINGLE_TREE leaf (block_splitter.rs:886-1078).  An 8x8 leaf is one request (C_L8), a 16x16
-// leaf one request and its CCLM part (C_L16, C_WINNER ..); the candidate-by-candidate states C_PLANAR .. C_F2 serve the
-// 32x32 leaf alone.  r is the result of the request the
-// previous step made (unused at the first step).  Returns false when the leaf is decided
-// (s.cost, s.luma_mode, s.chroma_mode).  The reference's "first minimum wins" selections are kept
-// as strict-less running updates in the reference's candidate order; a candidate = one request
-// (luma block and chroma pair together, SAD candidates as one list).
+// leaf one request and its CCLM part (C_L16, C_WINNER ..); of a 32x32 leaf only the CCLM part of the team schedule's
+// member 0 runs here (from C_WINNER), the wave kernels search theirs in one request (K_LEAF32, ctu_step).  r is the
+// result of the request the previous step made (unused at the first step).  Returns false when the leaf is decided
+// (s.cost, s.luma_mode, s.chroma_mode).
 __device__ __forceinline__ bool leaf_step(const Ctx& c, LeafSF& s, const Res& r, Req& q) {
     constexpr int tree = TREE_SINGLE;
     int cont = s.cont;
-    // RD cost of the full evaluation that just came back (candidates of C_PLANAR .. C_F2)
-    float val = 0.0f;
-    int cls = 0;
     const EvalParts rp = res_parts(r);
-    if (cont == C_PLANAR || cont == C_DCM || cont == C_F0 || cont == C_F1 || cont == C_F2) {
-        if (s.op_act) {
-            cls = mpm_class(c, s.bx, s.by, s.lg, s.op_ml);
-            val = uni_f(assemble_cost(c, tree, cls, s.op_mc, rp));
-            if (c.trace && LANE == 0)
-                TRACE_REC(c.ctu_x + s.bx, c.ctu_y + s.by, s.lg, tree, 1, s.op_ml, s.op_mc, __float_as_int(val));
-        } else {
-            val = 3.40282347e+38f; // a skipped evaluation is f32::MAX in the reference
-        }
-    }
     for (;;) {
         switch (cont) {
         case C_START: // candidates {0,1,2,7,13,18,23,29,34,39,45,50,55,60,66} (:887)
@@ -1870,11 +1972,9 @@ __device__ __forceinline__ bool leaf_step(const Ctx& c, LeafSF& s, const Res& r,
                 leaf_leaf8(s, q, C_L8);
                 return true;
             }
-            if (s.lg == 4) { // a 16x16 leaf: its five full candidates and the SAD search in one request
-                leaf_leaf16(s, q, C_L16);
-                return true;
-            }
-            leaf_full(s, q, 3, PLANAR, PLANAR, true, C_PLANAR);
+            // a 16x16 leaf: its five full candidates and the SAD search in one request.  (A 32x32 leaf never starts here: the
+            // wave kernels search it inside K_LEAF32, the team's member 0 joins at C_WINNER, leaf_step_team TC_D)
+            leaf_leaf16(s, q, C_L16);
             return true;
         case C_L16: // the winner of [planar, DC, cm, cm - 1, cm + 1] is in the tile; it is saved by the next request
             leaf_take(s, r.vmin, rp, r.imin, mpm_class(c, s.bx, s.by, s.lg, r.imin));
@@ -1887,44 +1987,6 @@ __device__ __forceinline__ bool leaf_step(const Ctx& c, LeafSF& s, const Res& r,
             s.luma_mode = (uint8_t)r.imin;
             s.chroma_mode = (uint8_t)r.imin2;
             return false;
-        case C_PLANAR:
-            leaf_take(s, val, rp, PLANAR, cls);
-            s.need_save = 1;
-            s.tile_best = 1;
-            leaf_full(s, q, 3, DC, DC, true, C_DCM);
-            return true;
-        case C_DCM:
-            leaf_offer(s, val, rp, DC, cls);
-            // the 13 directional candidates, their first minimum (:899-904) and step_search(mode, 2, cost, aux = true)
-            // (:905-973) in ONE request: the evaluator runs the three lists back to back
-            leaf_sadsearch(s, q, C_LIST);
-            return true;
-        case C_LIST: {
-            // step_search(mode, 1, _, aux=false) (:974) on {cur, cur - 1, cur + 1}, then the minimum of
-            // {planar, DC, dir} (:975-978): first minimum of [planar, DC, cur, cur - 1, cur + 1], kept as
-            // one running best.  Out-of-range neighbours are "evaluated" inactive (the request computes nothing)
-            const int cm = r.imin;
-            s.cur_mode = (uint8_t)cm;
-            s.cur_cost = r.vmin;
-            leaf_full(s, q, 3, cm, cm, true, C_F0);
-            return true;
-        }
-        case C_F0: {
-            const int cm = s.cur_mode;
-            leaf_offer(s, val, rp, cm, cls);
-            leaf_full(s, q, 3, cm - 1, cm - 1, !(cm < 3), C_F1);
-            return true;
-        }
-        case C_F1: {
-            const int cm = s.cur_mode;
-            leaf_offer(s, val, rp, cm - 1, cls);
-            leaf_full(s, q, 3, cm + 1, cm + 1, !(cm + 1 > 66), C_F2);
-            return true;
-        }
-        case C_F2:
-            leaf_offer(s, val, rp, s.cur_mode + 1, cls);
-            cont = C_WINNER;
-            break;
         case C_WINNER: {
             s.cost = s.best_cost;
             const int m = s.mode;
@@ -2319,8 +2381,8 @@ __device__ __forceinline__ void lv_post_split(int L, float sp) {
 // slots in global scratch they were saved to (copy_block): the reference's cache_reconsts /
 // restore_reconsts (block_splitter.rs:807-840, 1085-1145), with the saved planes kept in L2/HBM
 // instead of LDS.
-// (the numbers index the profile build's counters, tools/phase_profile.py: 4 and 5 were states of the 4x4 leaf walk K_SPLIT8 replaced)
-enum { T_START = 0, T_ENTER = 1, T_NODE_LEAF = 2, T_NODE8 = 3, T_REGEN_DONE = 6, T_RETURN = 7, T_FINAL_Z = 8, T_FZ_TAIL = 9, T_FZ_NEXT = 10,
+// (the numbers index the profile build's counters, tools/phase_profile.py: 5 was a state of the 4x4 leaf walk K_SPLIT8 replaced)
+enum { T_START = 0, T_ENTER = 1, T_NODE_LEAF = 2, T_NODE8 = 3, T_LEAF32 = 4, T_REGEN_DONE = 6, T_RETURN = 7, T_FINAL_Z = 8, T_FZ_TAIL = 9, T_FZ_NEXT = 10,
        T_LV_UNIT = 11, T_LV_LEAFDONE = 12, T_LV_UP = 13, T_SPLIT8 = 14, T_LV_SERVE = 15 };
 
 template <bool TEAM, bool D3>
@@ -2365,6 +2427,16 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
                     t.pend = 0;
                 }
                 t.cont = T_NODE8;
+                return true;
+            }
+            if (!TEAM && lg == 5) {
+                // wave schedule, the CTU's 32x32 leaf: the whole search in ONE request (K_LEAF32, full_search), its best
+                // candidate kept in slot copy_slot -- the unsplit slot when the split is tested next, see below
+                req_full(q, 3, t.bx, t.by, 5, 0, 0, true, true, true, false);
+                q.kind = K_LEAF32;
+                q.tree = TREE_SINGLE;
+                q.copy_slot = t.level < t.max_depth ? 1 + t.level : 0;
+                t.cont = T_LEAF32;
                 return true;
             }
             // wave schedule, a node whose split is tested next: the search saves its best candidate straight to the
@@ -2436,6 +2508,16 @@ __device__ __forceinline__ bool ctu_step(Ctx& c, const Res& r, Req& q) {
             cont = T_ENTER;
             break;
         }
+        case T_LEAF32: {
+            if constexpr (!TEAM) { // the 32x32 leaf is decided: on as after any leaf search
+                t.leaf.cost = r.vmin;
+                t.leaf.luma_mode = (uint8_t)r.imin;
+                t.leaf.chroma_mode = (uint8_t)r.imin2;
+                cont = T_NODE_LEAF;
+                break;
+            }
+            }
+            break;
         case T_NODE8: {
             if constexpr (!TEAM && D3) { // the 8x8 node's cost came back
                 t.ret = r.vmin;
