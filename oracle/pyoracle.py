@@ -294,6 +294,7 @@ def encode_picture_traced(y, cb, cr, qp, max_split_depth):
     trace = {}
     for rec in buf.tolist():
         trace.setdefault(tuple(rec[:7]), set()).add(rec[7] & 0xFFFFFFFF)
+    out["trace_records"] = int(n)       # records made, re-evaluations included (the dictionary holds the distinct keys)
     return out, trace
 
 

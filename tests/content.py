@@ -1,6 +1,54 @@
-"""Synthetic picture content shared by the parity tests: chosen to drive every mode family (see
-test_gpu_content.py)."""
+"""Synthetic picture content shared by the parity tests: one kind per tool of the search (see
+test_gpu_content.py), and what a record says about the tool a kind is there for."""
 import numpy as np
+
+# intraPredAngle of the modes 50 .. 66 (and, mirrored, 18 .. 2; negated, 50 .. 34 and 18 .. 34) in H.266
+_ANGLES = (0, 1, 2, 3, 4, 6, 8, 10, 12, 14, 16, 18, 20, 23, 26, 29, 32)
+STRIPES_SHARE = 0.45     # the oracle gives 0.50 (stripes70) .. 0.85 over test_gpu_content.CASES
+CCLM_SHARE = 0.70        # the oracle gives 0.75 .. 0.96
+
+
+def stripe_modes(deg):
+    """The angular mode(s) along which `stripesDEG` content is constant: the picture is a function of x cos a + y sin a, so
+    it is constant along (-sin a, cos a) -- (-tan a, 1) for a vertical mode of intraPredAngle 32 tan a, (1, -cot a) for a
+    horizontal one.  45 degrees is both mode 2 and mode 66."""
+    a = (deg + 90.0) % 180.0 - 90.0                     # -90 .. 90
+    if abs(a) <= 45.0:
+        t = 32.0 * np.tan(a * np.pi / 180.0)
+        k = int(np.argmin([abs(abs(t) - v) for v in _ANGLES]))
+        modes = {50 + k if t >= 0 else 50 - k}
+    else:
+        t = 32.0 / np.tan(a * np.pi / 180.0)
+        k = int(np.argmin([abs(abs(t) - v) for v in _ANGLES]))
+        modes = {18 - k if t >= 0 else 18 + k}
+    if modes & {2, 66}:
+        modes = {2, 66}
+    return modes
+
+
+def _cu_tops(rec):
+    cu = rec["cu_log2_size"]
+    yy, xx = np.mgrid[0:cu.shape[0], 0:cu.shape[1]]
+    n4 = 1 << (cu.astype(np.int64) - 2)
+    return (yy % n4 == 0) & (xx % n4 == 0)
+
+
+def stripes_share(deg, rec):
+    """The share of the record's CUs whose luma mode lies within +-3 of the stripes' direction."""
+    modes = rec["luma_mode"][_cu_tops(rec)].astype(np.int64)
+    near = np.zeros(modes.shape, bool)
+    for m in stripe_modes(deg):
+        near |= (np.abs(modes - m) <= 3) & (modes >= 2)
+    return float(near.mean())
+
+
+def cclm_share(rec):
+    """The share of the record's chroma blocks (one per CU of 8x8 and above, one per split 8x8) coded with a CCLM mode."""
+    cu8 = np.maximum(rec["cu_log2_size"][::2, ::2].astype(np.int64), 3)
+    yy, xx = np.mgrid[0:cu8.shape[0], 0:cu8.shape[1]]
+    n8 = 1 << (cu8 - 3)
+    tops = (yy % n8 == 0) & (xx % n8 == 0)
+    return float((rec["chroma_mode"][tops] >= 81).mean())
 
 
 def content(kind, w, h, seed):
